@@ -14,7 +14,9 @@ synthetic class-conditional clips (5 s @ 44.1 kHz) -- the reference also runs it
 a one-off pre-pass (Code/settransformer.py:43-53).  value = sets/s of all ranks divided by
 the sets one clip yields at this framing (cfg2: 431).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and
+reports; --full adds the spread windows, the roofline of the dominant kernels and the CPU
+baseline.  --dump-outputs DIR writes what the last timed step computed (dump_outputs()).
 """
 import argparse
 import ctypes as C
@@ -247,6 +249,27 @@ def measure_kernel(L, _lib, tr, dev, kid, ksteps, peak):
     }
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tr):
+    """What the caller of the timed step receives after its last step: the logits and mean loss of
+    that step's batch, the updated parameters and the Adam moments, as <out_dir>/<name>.npy
+    (float32).  An array above its share of DUMP_BUDGET_BYTES is written as a fixed sample of its
+    elements instead: the same seeded, sorted flat indices for the same size on every run."""
+    torch.cuda.synchronize(tr.dev)
+    arrays = {"logits": tr.eng.logits, "loss": tr.eng.loss, "params": tr.eng.flat,
+              "adam_m": tr.m, "adam_v": tr.v}
+    cap = DUMP_BUDGET_BYTES // len(arrays) // 4             # float32 elements per array
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > cap:
+            idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -260,12 +283,22 @@ def main():
                          "f32 = exact parity path")
     ap.add_argument("--clips", type=int, default=48, help="synthetic clips in the corpus")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--windows", type=int, default=50,
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the spread "
+                         "windows, the roofline of the dominant kernels and the CPU baseline "
+                         "(without it a run sets up, warms up, times --steps steps and reports)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the roofline")
+    ap.add_argument("--windows", type=int, default=None,
                     help="extra timed windows of --steps steps each after the headline window "
-                         "(spread estimate: median / p10 / p90 in 'windows'; 0 = off)")
+                         "(spread estimate: median / p10 / p90 in 'windows'; 0 = off; "
+                         "default 50 with --full, else 0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (logits, loss, parameters, Adam "
+                         "moments) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 50 if args.full else 0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -388,6 +421,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr)
     # spread: more windows of the same K steps, each bracketed like the headline window (bounded
     # to ~10 s so that slow configurations still finish in minutes)
     win_ms = []
@@ -441,7 +476,7 @@ def main():
                                                 / cfg["sets_per_clip"], 3)}
 
     # ---- roofline of the dominant kernel(s): HIP events on their launch stream, live ------
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # un-captured steps of the same workload so that the events bracket real launches
         tr_use_graph = tr.use_graph
         tr.use_graph = False
@@ -524,7 +559,7 @@ def main():
     if world > 1:
         dist.barrier()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, N)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -9,17 +9,17 @@ O=$R/gpurun_out/r02
 rm -rf $O && mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # --- bench lines (the default invocation is the driver's) ---
-python3 $R/bench.py > $O/bf16_cfg2_bench.json 2> $O/bf16_cfg2_bench.err
-python3 $R/bench.py --mode f32 --no-cpu-baseline > $O/f32_cfg2_bench.json 2>> $O/bench.err
-python3 $R/bench.py --config cfg3 --no-cpu-baseline > $O/bf16_cfg3_bench.json 2>> $O/bench.err
-python3 $R/bench.py --config cfg4 --steps 50 --warmup 5 --no-cpu-baseline > $O/bf16_cfg4_bench.json 2>> $O/bench.err
-python3 $R/bench.py --config cfg4 --mode fp8 --steps 50 --warmup 5 --no-cpu-baseline > $O/fp8_cfg4_bench.json 2>> $O/bench.err
-python3 $R/bench.py --config cfg5 --steps 50 --warmup 5 --no-cpu-baseline > $O/bf16_cfg5_bench.json 2>> $O/bench.err
-python3 $R/bench.py --config cfg5 --mode fp8 --steps 50 --warmup 5 --no-cpu-baseline > $O/fp8_cfg5_bench.json 2>> $O/bench.err
-python3 $R/bench.py --batch 1024 --steps 50 --warmup 5 --no-cpu-baseline > $O/bf16_cfg2_B1024_bench.json 2>> $O/bench.err
+python3 $R/bench.py --full > $O/bf16_cfg2_bench.json 2> $O/bf16_cfg2_bench.err
+python3 $R/bench.py --full --mode f32 --no-cpu-baseline > $O/f32_cfg2_bench.json 2>> $O/bench.err
+python3 $R/bench.py --full --config cfg3 --no-cpu-baseline > $O/bf16_cfg3_bench.json 2>> $O/bench.err
+python3 $R/bench.py --full --config cfg4 --steps 50 --warmup 5 --no-cpu-baseline > $O/bf16_cfg4_bench.json 2>> $O/bench.err
+python3 $R/bench.py --full --config cfg4 --mode fp8 --steps 50 --warmup 5 --no-cpu-baseline > $O/fp8_cfg4_bench.json 2>> $O/bench.err
+python3 $R/bench.py --full --config cfg5 --steps 50 --warmup 5 --no-cpu-baseline > $O/bf16_cfg5_bench.json 2>> $O/bench.err
+python3 $R/bench.py --full --config cfg5 --mode fp8 --steps 50 --warmup 5 --no-cpu-baseline > $O/fp8_cfg5_bench.json 2>> $O/bench.err
+python3 $R/bench.py --full --batch 1024 --steps 50 --warmup 5 --no-cpu-baseline > $O/bf16_cfg2_B1024_bench.json 2>> $O/bench.err
 echo "bench lines done"
 # --- kernel statistics ---
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_cfg2 -- python3 $R/bench.py --no-cpu-baseline > $O/stats_cfg2.json 2> $O/stats_cfg2.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_cfg2 -- python3 $R/bench.py --full --no-cpu-baseline > $O/stats_cfg2.json 2> $O/stats_cfg2.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_cfg4 -- python3 $R/bench.py --config cfg4 --steps 20 --warmup 3 --windows 1 --no-cpu-baseline --no-roofline > $O/stats_cfg4.json 2> $O/stats_cfg4.err
 echo "kernel stats done"
 # --- HBM traffic of the cfg2 step (separate passes per counter, as the guide prescribes) ---

@@ -66,7 +66,7 @@ def test_round_trip(tmp_path, arch, din, wrap):
     back, cfg2 = runfiles.load_run(js)
     assert cfg2 == shipped and isinstance(back, torch.nn.DataParallel)
     for (k, a), (_, b) in zip(net.state_dict().items(), back.module.state_dict().items()):
-        assert torch.equal(a, b.cpu()), k
+        assert torch.equal(a.cpu(), b.cpu()), k     # (DataParallel moved ``net`` to the GPU, if any)
 
 
 def test_loads_the_reference_layout(tmp_path, golden_ckpt):
