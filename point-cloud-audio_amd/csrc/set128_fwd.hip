@@ -329,6 +329,16 @@ __device__ __forceinline__ void mab1_phase(const Set128Layer& L, const Ctx& c, c
             acc[t][nb][e] = v;
           }
       }
+      if (DQ == 4) {
+        // the backward reads them at dq = 4 (mab1_saves_qp: k_mab1_bwd recomputes them from the
+        // points only for up to three columns); the same stores as the hidden layer's below
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+          for (int t = 0; t < 2; ++t)
+            *reinterpret_cast<bf16x4*>(L.QpS + (c.row0 + n0 + 16 * nb + r) * D + 32 * j + 16 * t + 4 * g) =
+                pack4(acc[t][nb]);
+      }
     } else {
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {

@@ -27,12 +27,14 @@ GRAD_SUBSAMPLE = 37     # stride of the stored sub-sample when full_grads is Fal
 
 def pc_input(seed: int, B: int, N: int, din: int) -> np.ndarray:
     """Spectrogram-shaped point sets: f in [0,0.5], t in [0,0.116],
-    logmag ~ clip(N(-9,3^2), -18.4, 0)."""
+    logmag ~ clip(N(-9,3^2), -18.4, 0).  Other layer-1 widths the kernels
+    accept (din = 1: logmag alone; din >= 4: f, t, uniform [0, 1) columns, logmag) draw their extra
+    columns after logmag, so din = 2 / 3 sets are the same as ever."""
     rng = np.random.Generator(np.random.PCG64(seed))
     x = np.empty((B, N, din), dtype=np.float32)
     if din == 2:
         x[:, :, 0] = np.linspace(0.0, 0.5, N, dtype=np.float64)[None, :]
-    else:
+    elif din >= 3:
         nt = 10 if N % 10 == 0 and N >= 10 else 1
         F = N // nt
         f = np.tile(np.linspace(0.0, 0.5, F), nt)
@@ -41,6 +43,8 @@ def pc_input(seed: int, B: int, N: int, din: int) -> np.ndarray:
         x[:, :, 1] = t[None, :]
     mag = np.clip(rng.normal(-9.0, 3.0, size=(B, N)), -18.4, 0.0)
     x[:, :, din - 1] = mag
+    if din > 3:
+        x[:, :, 2:din - 1] = rng.uniform(0.0, 1.0, size=(B, N, din - 3))
     return x
 
 

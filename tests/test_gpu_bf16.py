@@ -222,6 +222,7 @@ def test_engine_bf16_vs_golden(dev, golden_st):
 MAB0_CASES = [      # B, N, m, dk, d, h   (query = learned [m, d], shared by all sets)
     (3, 200, 16, 128, 128, 4),      # ISAB mab0, ragged N
     (4, 130, 1, 128, 128, 4),       # PMA: one seed, 4 score rows padded to 16
+    (3, 150, 2, 128, 128, 4),       # PMA: two seeds, 8 score rows (the nq <= 2 epilogue)
     (3, 77, 16, 2, 128, 4),         # layer 1 (f, logmag): exact fp32
     (2, 33, 16, 3, 128, 4),
     (2, 1, 16, 128, 128, 4),        # a single key
@@ -231,6 +232,10 @@ MAB0_CASES = [      # B, N, m, dk, d, h   (query = learned [m, d], shared by all
     (2, 515, 2, 256, 256, 8),       # two seeds: all 16 score rows live, ragged N
     (2, 300, 16, 256, 256, 8),      # 16 queries: the 16x16x16 products of the backward
     (2, 77, 32, 3, 256, 8),         # layer 1: reassociated fp32 kernels, 256 score rows
+    (2, 333, 8, 2, 256, 8),         # layer 1 with 64 score rows (mab0_d256_supported: R = 64), ragged N
+    (3, 261, 8, 3, 256, 8),
+    (2, 261, 16, 2, 256, 8),        # layer 1 with 128 score rows (R = 128)
+    (3, 333, 16, 3, 256, 8),
     (2, 1, 32, 256, 256, 8),        # a single key
 ]
 

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+from dispatch import launches
 from util import T, close, close_robust
 
 import inputs as gi
@@ -33,9 +34,10 @@ def dev():
     return torch.device("cuda", 0)
 
 
-def _run(dev, net, X, y, B, N, set128, head=True):
+def _run(dev, net, X, y, B, N, set128, head=True, witness=False):
     """head: the PMA epilogue / classifier / loss stages in the set-resident launch's tail (the default)
-    or as the launch of their own (k_pma_head1, ``PCA_SET128_HEAD=0``)."""
+    or as the launch of their own (k_pma_head1, ``PCA_SET128_HEAD=0``).  witness: also return how often
+    one more eager step launched k_set128_fwd (tests/dispatch.py)."""
     from pca_hip import _lib, trainer
     old = {k: os.environ.get(k) for k in ("PCA_SET128", "PCA_SET128_HEAD")}
     os.environ["PCA_SET128"] = "1" if set128 else "0"
@@ -45,7 +47,12 @@ def _run(dev, net, X, y, B, N, set128, head=True):
         eng.fwd_bwd(X, y, phase=-1)
         torch.cuda.synchronize()
         eng.check_handoffs()           # no bounded spin-wait of the pair hand-offs expired
-        return eng.logits.clone(), float(eng.loss), eng.grads.clone()
+        out = eng.logits.clone(), float(eng.loss), eng.grads.clone()
+        if witness:
+            n = launches(lambda: eng.fwd_bwd(X, y, phase=-1), ("set_fwd",))["set_fwd"]
+            eng.check_handoffs()
+            return (*out, n)
+        return out
     finally:
         for k, v in old.items():
             if v is None:
@@ -65,8 +72,13 @@ def test_set128_forward_equals_per_block_launches(dev, B, N, din, head):
                     num_heads=h).to(dev)
     X = T(gi.pc_input(7000 + N, B, N, din), dev)
     y = T(gi.labels(7001 + N, B, C), dev)
-    lg0, loss0, g0 = _run(dev, net, X, y, B, N, set128=False)
-    lg1, loss1, g1 = _run(dev, net, X, y, B, N, set128=True, head=head)
+    lg0, loss0, g0, n0 = _run(dev, net, X, y, B, N, set128=False, witness=True)
+    lg1, loss1, g1, n1 = _run(dev, net, X, y, B, N, set128=True, head=head, witness=True)
+    # the two arms must differ in the path taken (set128_shape_ok: every workgroup pair resident at once,
+    # 16 cdiv(B, 8) <= CUs), or the comparison below is vacuous
+    fits = 16 * -(-B // 8) <= torch.cuda.get_device_properties(0).multi_processor_count
+    assert n0 == 0, f"PCA_SET128=0 launched k_set128_fwd {n0} times"
+    assert n1 == (1 if fits else 0), f"B={B}: k_set128_fwd launched {n1} times per step (fits: {fits})"
     assert torch.isfinite(lg1).all() and torch.isfinite(g1).all()
     # bf16 activations: a one-ulp difference of a merged fp32 statistic can flip the rounding of a few
     # hidden activations; everything else is the same arithmetic
