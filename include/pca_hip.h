@@ -47,7 +47,10 @@ enum { PCA_F32 = 0, PCA_BF16 = 1 };
  * {16, 32} inducing points; forward-only calls -- saved == NULL, sized by
  * pca_mab_fwd_ws_bytes() -- also the many-queries block at d = 256, 8 heads, 32 keys) and
  * return PCA_EUNSUPPORTED / 0 bytes otherwise: the caller falls back to PCA_MODE_F32
- * explicitly.  The ST engine (pca_st_*) runs blocks without a fused kernel as the same chain
+ * explicitly.  Lowest precedence, pca_mab_* only: a self-attention shape (q_shared = 0, nq = nk,
+ * dq = dk, ln = 0; head dim 32 with d <= 256, or head dim 8 / 16 with d <= 128) runs the bf16-operand
+ * chain with its attention on a fused core that never builds the nq x nk scores (sizes linear in nq);
+ * PCA_MODE_FP8 runs it exactly as PCA_MODE_BF16 (no fp8 operands).  The ST engine (pca_st_*) runs blocks without a fused kernel as the same chain
  * of GEMMs with bf16 MFMA operands (pca_gemm_bf16). */
 /* PCA_MODE_FP8 (BASELINE configs[4]): as PCA_MODE_BF16, but these d x d projections of the forward
  * take fp8 e4m3 (OCP) MFMA operands: fc_o of the many-queries block (d = 128 and 256) and fc_k,

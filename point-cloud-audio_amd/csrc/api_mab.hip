@@ -6,10 +6,11 @@ namespace pca {
 
 
 
-static int check_f32(const pca_mab_shape* s, bool inference) {
-  // the exact path exchanges fp32 only; the fused kernels validate their own dtypes
-  PCA_REQUIRE(mab_kind(*s, inference) != 0 || (s->q_dtype == PCA_F32 && s->k_dtype == PCA_F32 &&
-                                    s->y_dtype == PCA_F32),
+// kind as the C entry points see it (abi_kind below)
+static int check_f32(const pca_mab_shape* s, int kind) {
+  // the GEMM chains (kinds 0 and 4) exchange fp32 only; the fused kernels validate their own dtypes
+  PCA_REQUIRE((kind != 0 && kind != 4) || (s->q_dtype == PCA_F32 && s->k_dtype == PCA_F32 &&
+                                           s->y_dtype == PCA_F32),
               "mab: the exact fp32 path needs fp32 Q, K and Y");
   return PCA_OK;
 }
@@ -72,6 +73,29 @@ int mab_bwd_any(const pca_mab_shape& s, const void* Q, const void* K, const pca_
   return mab_f32_bwd(s, (const float*)Q, (const float*)K, p, saved, (const float*)dY,
                      (float*)dQ, (float*)dK, dk_accumulate, g, ws, st);
 }
+
+// kind 4 = a self-attention-shaped block (SAB, set_transformer-master/modules.py:35-41: per-set queries,
+// nq = nk, dq = dk) that kinds 1-3 do not take, in PCA_MODE_BF16 or PCA_MODE_FP8 (run alike: no fp8
+// operands): the bf16-operand chain of mab_f32.hip with its attention on the fused core (attn_core.hip,
+// head dims 8 / 16 / 32), so nothing of size nq x nk is ever stored.  Only the pca_mab_* entry points
+// select it; the ST engine dispatches on mab_kind and keeps its blocks as they are.
+static int abi_kind(const pca_mab_shape& s, bool inference = false) {
+  const int k = mab_kind(s, inference);
+  return k == 0 && attn_core_sab_ok(s) ? 4 : k;
+}
+static size_t abi_saved_bytes(const pca_mab_shape& s) {
+  return abi_kind(s) == 4 ? mab_f32_saved_bytes(s, true) : mab_saved_bytes_any(s);
+}
+static size_t abi_fwd_ws_bytes(const pca_mab_shape& s) {
+  const int ki = abi_kind(s, true), kt = abi_kind(s, false);
+  if (ki != 4 && kt != 4) return mab_fwd_ws_bytes_any(s);
+  // the chain's scratch is its saved block; an inference-only kernel of the shape (kind 3) needs its own
+  const size_t a = mab_f32_saved_bytes(s, true), b = ki == 3 ? sd64_fwd_ws_bytes(s) : 0;
+  return a > b ? a : b;
+}
+static size_t abi_bwd_ws_bytes(const pca_mab_shape& s) {
+  return abi_kind(s) == 4 ? mab_f32_bwd_ws_bytes(s, true) : mab_bwd_ws_bytes_any(s);
+}
 }  // namespace pca
 
 namespace pca {
@@ -94,7 +118,7 @@ extern "C" {
 // arithmetic at this level); callers that want "bf16 where available" query
 // pca_mab_saved_bytes() first, which returns 0 for unsupported bf16 shapes.
 static int bf16_demand(const pca_mab_shape* s, bool inference = false) {
-  if ((s->mode == PCA_MODE_BF16 || s->mode == PCA_MODE_FP8) && pca::mab_kind(*s, inference) == 0) {
+  if ((s->mode == PCA_MODE_BF16 || s->mode == PCA_MODE_FP8) && pca::abi_kind(*s, inference) == 0) {
     pca::set_error("mab: no bf16 / fp8 kernel for B=%d nq=%d nk=%d dq=%d dk=%d d=%d h=%d q_shared=%d",
                    s->B, s->nq, s->nk, s->dq, s->dk, s->d, s->h, s->q_shared);
     return PCA_EUNSUPPORTED;
@@ -108,15 +132,15 @@ static int bf16_demand(const pca_mab_shape* s, bool inference = false) {
 
 size_t pca_mab_saved_bytes(const pca_mab_shape* s) {
   if (pca::validate_shape(s) != PCA_OK || bf16_demand(s) != PCA_OK) return 0;
-  return pca::mab_saved_bytes_any(*s);
+  return pca::abi_saved_bytes(*s);
 }
 size_t pca_mab_fwd_ws_bytes(const pca_mab_shape* s) {
   if (pca::validate_shape(s) != PCA_OK || bf16_demand(s, true) != PCA_OK) return 0;
-  return pca::mab_fwd_ws_bytes_any(*s);
+  return pca::abi_fwd_ws_bytes(*s);
 }
 size_t pca_mab_bwd_ws_bytes(const pca_mab_shape* s) {
   if (pca::validate_shape(s) != PCA_OK || bf16_demand(s) != PCA_OK) return 0;
-  return pca::mab_bwd_ws_bytes_any(*s);
+  return pca::abi_bwd_ws_bytes(*s);
 }
 
 
@@ -136,9 +160,14 @@ int pca_mab_fwd(const pca_mab_shape* s, const void* Q, const void* K,
   PCA_REQUIRE(p->wq && p->bq && p->wk && p->bk && p->wv && p->bv && p->wo && p->bo,
               "mab_fwd: null parameter");
   PCA_TRY(bf16_demand(s, saved == nullptr));
-  PCA_TRY(pca::check_f32(s, saved == nullptr));
-  PCA_REQUIRE(ws != nullptr || (saved != nullptr && pca::mab_kind(*s, false) == 0),
+  const int kind = pca::abi_kind(*s, saved == nullptr);
+  PCA_TRY(pca::check_f32(s, kind));
+  PCA_REQUIRE(ws != nullptr || (saved != nullptr && (kind == 0 || kind == 4)),
               "mab_fwd: scratch block required");
+  if (kind == 4)
+    PCA_WITH_HANDOFF_CHECK("pca_mab_fwd", false,
+                           pca::mab_f32_fwd(*s, (const float*)Q, (const float*)K, *p, (float*)Y,
+                                            saved ? saved : ws, pca::as_stream(stream), true));
   PCA_WITH_HANDOFF_CHECK("pca_mab_fwd", false,
                          pca::mab_fwd_any(*s, Q, K, *p, Y, saved, ws, pca::as_stream(stream)));
 }
@@ -151,7 +180,13 @@ int pca_mab_bwd(const pca_mab_shape* s, const void* Q, const void* K,
   PCA_REQUIRE(g->wq && g->bq && g->wk && g->bk && g->wv && g->bv && g->wo && g->bo,
               "mab_bwd: null gradient buffer");
   PCA_TRY(bf16_demand(s));
-  PCA_TRY(pca::check_f32(s, false));
+  const int kind = pca::abi_kind(*s);
+  PCA_TRY(pca::check_f32(s, kind));
+  if (kind == 4)
+    PCA_WITH_HANDOFF_CHECK("pca_mab_bwd", false,
+                           pca::mab_f32_bwd(*s, (const float*)Q, (const float*)K, *p, saved, (const float*)dY,
+                                            (float*)dQ, (float*)dK, dk_accumulate, *g, ws,
+                                            pca::as_stream(stream), true));
   PCA_WITH_HANDOFF_CHECK("pca_mab_bwd", false,
                          pca::mab_bwd_any(*s, Q, K, *p, saved, dY, dQ, dK, dk_accumulate, *g, ws,
                                           pca::as_stream(stream)));

@@ -38,6 +38,8 @@
 
 #include <math.h>
 
+#include <mutex>
+
 namespace pca {
 
 namespace {
@@ -545,6 +547,396 @@ __global__ __launch_bounds__(64 * NW, 4) void k_attnc_bwd_kv(const AttnCoreArgs 
   }
 }
 
+// ---- head dim 32 (self-attention blocks through the C ABI only: attn_core_sab_ok) --------------------
+// The same contract, structure and LDS images as above, with v_mfma_f32_16x16x32_bf16: K = 32 is the
+// whole head, so a score tile of 16 x 16 is ONE MFMA per head, and a product that sums over the streamed
+// rows takes 32 of them per MFMA.  Lane (r, g) holds the register side's row r, features 8 g .. 8 g + 7
+// of its wave's head as the B operand; the streamed side's row form gives the A operand of the score
+// products (two 8-byte reads per lane), its transposed form the A operand of the products that sum over
+// the streamed rows: two score tiles u = 2 s, 2 s + 1 pack into one B operand whose k-slot (g, i) is
+// streamed row 32 s + perm32(8 g + i), and the transposed reads take the same rows (4 g .. and 16 + 4 g ..).
+// Output rows are the head's features in two halves of 16 (two accumulators).
+// A wave keeps FOUR 16-row tiles of the register side (a 64-row group: the Plan's unit here) against
+// every staged chunk, so each chunk is staged once per 64 register rows, not per 16.
+// Staging: 4 d items of 4 rows x 4 features per chunk, 2 d threads (h = d / 32 waves): two items each.
+constexpr int T32 = 4;         // 16-row tiles per wave and group
+
+__device__ __forceinline__ bf16x8 cat8(bf16x4 lo, bf16x4 hi) {
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+// 8 features of a [rows][d] fp32 row as a bf16 operand (p: the first of them; 32-byte aligned)
+__device__ __forceinline__ bf16x8 ld8_bf16(const float* p) {
+  const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
+  return pack8(f32x4{lo.x, lo.y, lo.z, lo.w}, f32x4{hi.x, hi.y, hi.z, hi.w});
+}
+// row form: streamed row `row`, head features 8 g .. 8 g + 7 (the A operand of a score product)
+__device__ __forceinline__ bf16x8 rd_row(const __bf16* Rw, int row, int d, int f0) {
+  const __bf16* p = Rw + row * (d + 4) + f0;
+  return cat8(*reinterpret_cast<const bf16x4*>(p), *reinterpret_cast<const bf16x4*>(p + 4));
+}
+// transposed form: feature `f`, streamed rows 32 s + 4 g .. + 3 and 32 s + 16 + 4 g .. + 3
+__device__ __forceinline__ bf16x8 rd_tr(const __bf16* Tr, int f, int s, int g) {
+  const __bf16* p = Tr + f * (CH + 4) + 32 * s + 4 * g;
+  return cat8(*reinterpret_cast<const bf16x4*>(p), *reinterpret_cast<const bf16x4*>(p + 16));
+}
+// a chunk of X (and Y) into LDS, both items of every thread
+template <bool XROW, bool XTR, bool YROW, bool YTR>
+__device__ __forceinline__ void stage32(const float* __restrict__ X, const float* __restrict__ Y, int nrows,
+                                        int r0, int d, int tid, int nthr, __bf16* Xr, __bf16* Xt, __bf16* Yr,
+                                        __bf16* Yt) {
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const StageId id = stage_id(d, tid + k * nthr);
+    const Staged x = stage_load(X, nrows, r0, d, id);
+    const Staged y = stage_load(Y, nrows, r0, d, id);
+    stage_store<XROW, XTR>(x, nrows, r0, d, id, Xr, Xt);
+    stage_store<YROW, YTR>(y, nrows, r0, d, id, Yr, Yt);
+  }
+}
+
+// S > 1: part as k_attnc_fwd, merged by k_attnc_fwd_merge
+__global__ __launch_bounds__(512) void k_attn32_fwd(const AttnCoreArgs a) {
+  extern __shared__ __attribute__((aligned(16))) __bf16 lds[];
+  const int tid = threadIdx.x, lane = tid & 63, j = tid >> 6, r = lane & 15, g = lane >> 4;
+  const int nthr = blockDim.x, d = a.d, nq = a.nq, nk = a.nk;
+  int b, xt, sp;
+  wg_coords(a, b, xt, sp);
+  if (b >= a.B) return;
+  __bf16* Krow = lds;
+  __bf16* Vtr = lds + row_elems(d);
+  int len = nk;
+  if (a.lengths != nullptr) len = a.lengths[b] < nk ? a.lengths[b] : nk;
+  const int nlive = (len + CH - 1) / CH;
+  const int cb = sp * a.cps, ce = cb + a.cps < nlive ? cb + a.cps : nlive;
+  const bool single = ce - cb == 1;
+  const float* Kb = a.Kp + (int64_t)b * nk * d;
+  const float* Vb = a.Vp + (int64_t)b * nk * d;
+  const float* Qb = a.Qp + (int64_t)b * a.qb + j * 32;
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  bool staged = false;
+  for (int t = xt; t < a.nt; t += a.gt) {
+    const int q0 = t * 64;
+    bf16x8 qo[T32];
+    float m[T32], l[T32];
+    f32x4 acc[T32][2];
+#pragma unroll
+    for (int i = 0; i < T32; ++i) {
+      const int qi = q0 + 16 * i + r < nq ? q0 + 16 * i + r : nq - 1;
+      qo[i] = ld8_bf16(Qb + (int64_t)qi * d + 8 * g);
+      m[i] = -INFINITY; l[i] = 0.f;
+      acc[i][0] = z4; acc[i][1] = z4;
+    }
+    const bool fill = !(single && staged);
+    for (int c = cb; c < ce; ++c) {
+      if (fill) {
+        __syncthreads();                               // the previous chunk is consumed
+        stage32<true, false, false, true>(Kb, Vb, nk, c * CH, d, tid, nthr, Krow, nullptr, nullptr, Vtr);
+        __syncthreads();
+      }
+      bf16x8 ka[4], va[2][2];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) ka[u] = rd_row(Krow, 16 * u + r, d, j * 32 + 8 * g);
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) va[s2][hh] = rd_tr(Vtr, j * 32 + 16 * hh + r, s2, g);
+      const int klim = len - c * CH;                   // live keys of the chunk (>= 1; may exceed 64)
+#pragma unroll
+      for (int i = 0; i < T32; ++i) {
+        f32x4 s[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s[u] = mfma32(ka[u], qo[i], z4);   // [key 16 u + 4 g + e][query r]
+        if (klim < CH) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              if (16 * u + 4 * g + e >= klim) s[u][e] = -INFINITY;
+        }
+        float mt = max2(max2(s[0][0], s[0][1]), max2(s[0][2], s[0][3]));
+#pragma unroll
+        for (int u = 1; u < 4; ++u) mt = max2(mt, max2(max2(s[u][0], s[u][1]), max2(s[u][2], s[u][3])));
+        mt = wave16_max(mt);
+        const float mn = max2(m[i], mt * a.c);
+        const float alpha = __builtin_amdgcn_exp2f(m[i] - mn);
+        float ls = 0.f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            s[u][e] = __builtin_amdgcn_exp2f(fmaf(s[u][e], a.c, -mn));
+            ls += s[u][e];
+          }
+        l[i] = fmaf(l[i], alpha, ls);
+        m[i] = mn;
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[i][hh][e] *= alpha;
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          const bf16x8 pb = pack8(s[2 * s2], s[2 * s2 + 1]);
+#pragma unroll
+          for (int hh = 0; hh < 2; ++hh) acc[i][hh] = mfma32(va[s2][hh], pb, acc[i][hh]);  // [feature][query r]
+        }
+      }
+    }
+    staged = true;
+#pragma unroll
+    for (int i = 0; i < T32; ++i) {
+      const int q = q0 + 16 * i + r;
+      const float lt = wave16_sum(l[i]);
+      if (q >= nq) continue;
+      if (a.S == 1) {
+        const float inv = 1.f / lt;
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+          const int f = j * 32 + 16 * hh + 4 * g;
+          const float4 q4 = *reinterpret_cast<const float4*>(a.Qp + (int64_t)b * a.qb + (int64_t)q * d + f);
+          *reinterpret_cast<float4*>(a.Oout + ((int64_t)b * nq + q) * d + f) =
+              float4{q4.x + acc[i][hh][0] * inv, q4.y + acc[i][hh][1] * inv, q4.z + acc[i][hh][2] * inv,
+                     q4.w + acc[i][hh][3] * inv};
+        }
+        if (g == 0) a.LSE[((int64_t)b * a.h + j) * nq + q] = m[i] + log2f(lt);
+      } else {
+        float* ml = a.part;
+        float* pa = a.part + (int64_t)a.B * a.S * a.h * nq * 2;
+        const int64_t bs = (int64_t)b * a.S + sp;
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh)
+          *reinterpret_cast<float4*>(pa + (bs * nq + q) * d + j * 32 + 16 * hh + 4 * g) =
+              float4{acc[i][hh][0], acc[i][hh][1], acc[i][hh][2], acc[i][hh][3]};
+        if (g == 0) *reinterpret_cast<float2*>(ml + ((bs * a.h + j) * nq + q) * 2) = float2{m[i], lt};
+      }
+    }
+  }
+}
+
+// S > 1: part = dQ partials [B][S][nq][d] (without the residual), summed onto dO by k_attnc_sum
+__global__ __launch_bounds__(512) void k_attn32_bwd_q(const AttnCoreArgs a) {
+  extern __shared__ __attribute__((aligned(16))) __bf16 lds[];
+  const int tid = threadIdx.x, lane = tid & 63, j = tid >> 6, r = lane & 15, g = lane >> 4;
+  const int nthr = blockDim.x, d = a.d, nq = a.nq, nk = a.nk;
+  int b, xt, sp;
+  wg_coords(a, b, xt, sp);
+  if (b >= a.B) return;
+  __bf16* Krow = lds;
+  __bf16* Vrow = Krow + row_elems(d);
+  __bf16* Ktr = Vrow + row_elems(d);
+  int len = nk;
+  if (a.lengths != nullptr) len = a.lengths[b] < nk ? a.lengths[b] : nk;
+  const int nlive = (len + CH - 1) / CH;
+  const int cb = sp * a.cps, ce = cb + a.cps < nlive ? cb + a.cps : nlive;
+  const bool single = ce - cb == 1;
+  const float* Kb = a.Kp + (int64_t)b * nk * d;
+  const float* Vb = a.Vp + (int64_t)b * nk * d;
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  bool staged = false;
+  for (int t = xt; t < a.nt; t += a.gt) {
+    const int q0 = t * 64;
+    bf16x8 qo[T32], dob[T32];
+    float nlse[T32], nds[T32];
+    f32x4 acc[T32][2];
+#pragma unroll
+    for (int i = 0; i < T32; ++i) {
+      const int qi = q0 + 16 * i + r < nq ? q0 + 16 * i + r : nq - 1;
+      const int64_t orow = ((int64_t)b * nq + qi) * d + j * 32 + 8 * g;
+      const float* qp = a.Qp + (int64_t)b * a.qb + (int64_t)qi * d + j * 32 + 8 * g;
+      float dl = 0.f;
+#pragma unroll
+      for (int h4 = 0; h4 < 2; ++h4) {          // delta = rowdot(dO, O - Q_) over the head's 32 features
+        const float4 o4 = *reinterpret_cast<const float4*>(a.O + orow + 4 * h4);
+        const float4 d4 = *reinterpret_cast<const float4*>(a.dO + orow + 4 * h4);
+        const float4 q4 = *reinterpret_cast<const float4*>(qp + 4 * h4);
+        dl += d4.x * (o4.x - q4.x) + d4.y * (o4.y - q4.y) + d4.z * (o4.z - q4.z) + d4.w * (o4.w - q4.w);
+      }
+      const float delta = wave16_sum(dl);
+      qo[i] = ld8_bf16(qp);
+      dob[i] = ld8_bf16(a.dO + orow);
+      nlse[i] = -a.LSE[((int64_t)b * a.h + j) * nq + qi];
+      nds[i] = -delta * a.scale;
+      acc[i][0] = z4; acc[i][1] = z4;
+      if (g == 0 && sp == 0 && q0 + 16 * i + r < nq) a.Delta[((int64_t)b * a.h + j) * nq + qi] = delta;
+    }
+    const bool fill = !(single && staged);
+    for (int c = cb; c < ce; ++c) {
+      if (fill) {
+        __syncthreads();
+        stage32<true, true, true, false>(Kb, Vb, nk, c * CH, d, tid, nthr, Krow, Ktr, Vrow, nullptr);
+        __syncthreads();
+      }
+      bf16x8 ka[4], vv[4], kt[2][2];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        ka[u] = rd_row(Krow, 16 * u + r, d, j * 32 + 8 * g);
+        vv[u] = rd_row(Vrow, 16 * u + r, d, j * 32 + 8 * g);
+      }
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) kt[s2][hh] = rd_tr(Ktr, j * 32 + 16 * hh + r, s2, g);
+      const int klim = len - c * CH;
+#pragma unroll
+      for (int i = 0; i < T32; ++i) {
+        f32x4 ds[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const f32x4 s = mfma32(ka[u], qo[i], z4);     // [key 16 u + 4 g + e][query r]
+          const f32x4 dp = mfma32(vv[u], dob[i], z4);   // dP^T = V dO^T
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            float pe = __builtin_amdgcn_exp2f(fmaf(s[e], a.c, nlse[i]));
+            if (klim < CH) pe = 16 * u + 4 * g + e < klim ? pe : 0.f;
+            ds[u][e] = pe * fmaf(dp[e], a.scale, nds[i]);
+          }
+        }
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          const bf16x8 db = pack8(ds[2 * s2], ds[2 * s2 + 1]);
+#pragma unroll
+          for (int hh = 0; hh < 2; ++hh) acc[i][hh] = mfma32(kt[s2][hh], db, acc[i][hh]);  // dQ^T += K^T dS^T
+        }
+      }
+    }
+    staged = true;
+#pragma unroll
+    for (int i = 0; i < T32; ++i) {
+      const int q = q0 + 16 * i + r;
+      if (q >= nq) continue;
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        const int f = j * 32 + 16 * hh + 4 * g;
+        if (a.S == 1) {
+          const int64_t o = ((int64_t)b * nq + q) * d + f;
+          const float4 d4 = *reinterpret_cast<const float4*>(a.dO + o);
+          *reinterpret_cast<float4*>(a.dQp + o) =       // + the residual Q_
+              float4{d4.x + acc[i][hh][0], d4.y + acc[i][hh][1], d4.z + acc[i][hh][2], d4.w + acc[i][hh][3]};
+        } else {
+          *reinterpret_cast<float4*>(a.part + (((int64_t)b * a.S + sp) * nq + q) * d + f) =
+              float4{acc[i][hh][0], acc[i][hh][1], acc[i][hh][2], acc[i][hh][3]};
+        }
+      }
+    }
+  }
+}
+
+// S > 1: part = { dK partials [B][S][nk][d], dV partials [B][S][nk][d] }, summed by k_attnc_sum
+__global__ __launch_bounds__(512) void k_attn32_bwd_kv(const AttnCoreArgs a) {
+  extern __shared__ __attribute__((aligned(16))) __bf16 lds[];
+  const int tid = threadIdx.x, lane = tid & 63, j = tid >> 6, r = lane & 15, g = lane >> 4;
+  const int nthr = blockDim.x, d = a.d, nq = a.nq, nk = a.nk, h = a.h;
+  int b, xt, sp;
+  wg_coords(a, b, xt, sp);
+  if (b >= a.B) return;
+  __bf16* Qrow = lds;
+  __bf16* Drow = Qrow + row_elems(d);
+  __bf16* Qtr = Drow + row_elems(d);
+  __bf16* Dtr = Qtr + tr_elems(d);
+  const int nb16 = 2 * row_elems(d) + 2 * tr_elems(d);
+  float* lseS = reinterpret_cast<float*>(lds + ((nb16 + 7) & ~7));   // [h][CH] each; one entry per thread
+  float* delS = lseS + h * CH;
+  int len = nk;
+  if (a.lengths != nullptr) len = a.lengths[b] < nk ? a.lengths[b] : nk;
+  const int nch = (nq + CH - 1) / CH;
+  const int cb = sp * a.cps, ce = cb + a.cps < nch ? cb + a.cps : nch;
+  const bool single = ce - cb == 1;
+  const float* Qb = a.Qp + (int64_t)b * a.qb;
+  const float* dOb = a.dO + (int64_t)b * nq * d;
+  const float* lseb = a.LSE + ((int64_t)b * h + j) * nq;
+  const float* delb = a.Delta + ((int64_t)b * h + j) * nq;
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  bool staged = false;
+  for (int t = xt; t < a.nt; t += a.gt) {
+    const int k0 = t * 64;
+    bf16x8 kb[T32], vb[T32];                           // B operands [k = feature][col = key r]
+    bool dead[T32];
+    f32x4 dk[T32][2], dv[T32][2];
+#pragma unroll
+    for (int i = 0; i < T32; ++i) {
+      const int ki = k0 + 16 * i + r < nk ? k0 + 16 * i + r : nk - 1;
+      const int64_t o = ((int64_t)b * nk + ki) * d + j * 32 + 8 * g;
+      kb[i] = ld8_bf16(a.Kp + o);
+      vb[i] = ld8_bf16(a.Vp + o);
+      dead[i] = k0 + 16 * i + r >= len;                // masked keys: P = 0, zero gradient rows
+      dk[i][0] = dk[i][1] = dv[i][0] = dv[i][1] = z4;
+    }
+    const bool fill = !(single && staged);
+    for (int c = cb; c < ce; ++c) {
+      if (fill) {
+        __syncthreads();
+        const int qq = c * CH + lane;                  // this thread's entry: head j (its wave), query qq
+        const int qc = qq < nq ? qq : nq - 1;
+        const float lr = lseb[qc], er = delb[qc];
+        stage32<true, true, true, true>(Qb, dOb, nq, c * CH, d, tid, nthr, Qrow, Qtr, Drow, Dtr);
+        lseS[j * CH + lane] = qq < nq ? -lr : -INFINITY;      // queries past the end: P = 2^(-inf) = 0
+        delS[j * CH + lane] = qq < nq ? -er * a.scale : 0.f;
+        __syncthreads();
+      }
+      // 32 queries (one k-step of the products over queries) at a time: two score tiles u = 2 s2, 2 s2 + 1
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        bf16x8 qa[2], doa[2], qt[2], dot[2];
+        float nl4[2][4], nd4[2][4];
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+          const int u = 2 * s2 + w;
+          qa[w] = rd_row(Qrow, 16 * u + r, d, j * 32 + 8 * g);     // A operand [query r][k = feature]
+          doa[w] = rd_row(Drow, 16 * u + r, d, j * 32 + 8 * g);
+          const float4 nl = *reinterpret_cast<const float4*>(lseS + j * CH + 16 * u + 4 * g);
+          const float4 nd = *reinterpret_cast<const float4*>(delS + j * CH + 16 * u + 4 * g);
+          nl4[w][0] = nl.x; nl4[w][1] = nl.y; nl4[w][2] = nl.z; nl4[w][3] = nl.w;
+          nd4[w][0] = nd.x; nd4[w][1] = nd.y; nd4[w][2] = nd.z; nd4[w][3] = nd.w;
+        }
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+          qt[hh] = rd_tr(Qtr, j * 32 + 16 * hh + r, s2, g);         // Q^T, dO^T: [feature][k = query]
+          dot[hh] = rd_tr(Dtr, j * 32 + 16 * hh + r, s2, g);
+        }
+#pragma unroll
+        for (int i = 0; i < T32; ++i) {
+          f32x4 p[2], ds[2];
+#pragma unroll
+          for (int w = 0; w < 2; ++w) {
+            const f32x4 sc = mfma32(qa[w], kb[i], z4);   // [query 16 u + 4 g + e][key r]
+            const f32x4 dp = mfma32(doa[w], vb[i], z4);  // dP = dO V^T
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float pe = __builtin_amdgcn_exp2f(fmaf(sc[e], a.c, nl4[w][e]));
+              p[w][e] = dead[i] ? 0.f : pe;
+              ds[w][e] = p[w][e] * fmaf(dp[e], a.scale, nd4[w][e]);
+            }
+          }
+          const bf16x8 pb = pack8(p[0], p[1]);
+          const bf16x8 db = pack8(ds[0], ds[1]);
+#pragma unroll
+          for (int hh = 0; hh < 2; ++hh) {
+            dv[i][hh] = mfma32(dot[hh], pb, dv[i][hh]);       // dV^T += dO^T P   [feature][key r]
+            dk[i][hh] = mfma32(qt[hh], db, dk[i][hh]);        // dK^T += Q^T dS
+          }
+        }
+      }
+    }
+    staged = true;
+#pragma unroll
+    for (int i = 0; i < T32; ++i) {
+      const int kr = k0 + 16 * i + r;
+      if (kr >= nk) continue;
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        float *pk = a.dKp, *pv = a.dVp;
+        int64_t o = ((int64_t)b * nk + kr) * d + j * 32 + 16 * hh + 4 * g;
+        if (a.S > 1) {
+          pk = a.part;
+          pv = a.part + (int64_t)a.B * a.S * nk * d;
+          o = (((int64_t)b * a.S + sp) * nk + kr) * d + j * 32 + 16 * hh + 4 * g;
+        }
+        *reinterpret_cast<float4*>(pk + o) = float4{dk[i][hh][0], dk[i][hh][1], dk[i][hh][2], dk[i][hh][3]};
+        *reinterpret_cast<float4*>(pv + o) = float4{dv[i][hh][0], dv[i][hh][1], dv[i][hh][2], dv[i][hh][3]};
+      }
+    }
+  }
+}
+
 inline AttnCoreArgs core_args(const pca_mab_shape& s, const Plan& p) {
   AttnCoreArgs a{};
   a.B = s.B; a.nq = s.nq; a.nk = s.nk; a.d = s.d; a.dh = s.d / s.h; a.h = s.h;
@@ -561,6 +953,23 @@ inline unsigned grid_of(const pca_mab_shape& s, const Plan& p) {
 inline size_t fwd_part_elems(const pca_mab_shape& s, const Plan& p) {
   return p.S > 1 ? (size_t)s.B * p.S * s.nq * (2 * s.h + s.d) : 0;
 }
+// the head-dim-32 kernels hold 64-row groups of the register side: a Plan "tile" of theirs is 64 rows
+inline bool dh32(const pca_mab_shape& s) { return s.d == 32 * s.h; }
+inline Plan core_plan(const pca_mab_shape& s, int reg_rows, int str_rows) {
+  return plan_of(s.B, dh32(s) ? (int)cdiv(reg_rows, 4) : reg_rows, str_rows);
+}
+// dynamic LDS above 64 KB: the d = 256 images of the head-dim-32 kernels (up to 146 KB), the d = 128
+// images of the small core's k_attnc_bwd_kv (78 KB at 8 heads of dim 16, 82 KB at 16 heads of dim 8)
+void allow_big_lds() {
+  static std::once_flag once;
+  std::call_once(once, [] {
+    const void* ks[] = {reinterpret_cast<const void*>(k_attn32_fwd), reinterpret_cast<const void*>(k_attn32_bwd_q),
+                        reinterpret_cast<const void*>(k_attn32_bwd_kv),
+                        reinterpret_cast<const void*>(k_attnc_bwd_kv<8>),
+                        reinterpret_cast<const void*>(k_attnc_bwd_kv<16>)};
+    for (const void* k : ks) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  });
+}
 
 }  // namespace
 
@@ -573,13 +982,23 @@ bool attn_core_ok(const pca_mab_shape& s) {
          s.h <= 16;
 }
 
+// self-attention-shaped blocks (per-set queries, nq = nk, dq = dk) in the bf16-operand modes: head dims
+// 8 and 16 on the kernels above up to d = 128 (16 waves), head dim 32 on the k_attn32_* kernels up to
+// d = 256 (8 waves; 146 KB of LDS in k_attn32_bwd_kv)
+bool attn_core_sab_ok(const pca_mab_shape& s) {
+  const int dh = s.d / s.h;
+  if (s.mode == PCA_MODE_F32 || s.ln || s.q_shared || s.nq != s.nk || s.dq != s.dk) return false;
+  if (dh == 32) return s.h <= 8;
+  return (dh == 8 || dh == 16) && s.d <= 128;
+}
+
 // floats behind `LSE` (forward) / `Delta` (backward): the statistics [B][h][nq], then the partial
 // results of a launch whose streamed side is cut (Plan::S > 1)
 size_t attn_core_fwd_elems(const pca_mab_shape& s) {
-  return (size_t)s.B * s.h * s.nq + fwd_part_elems(s, plan_of(s.B, s.nq, s.nk));
+  return (size_t)s.B * s.h * s.nq + fwd_part_elems(s, core_plan(s, s.nq, s.nk));
 }
 size_t attn_core_bwd_elems(const pca_mab_shape& s) {
-  const Plan pq = plan_of(s.B, s.nq, s.nk), pk = plan_of(s.B, s.nk, s.nq);
+  const Plan pq = core_plan(s, s.nq, s.nk), pk = core_plan(s, s.nk, s.nq);
   const size_t eq = pq.S > 1 ? (size_t)s.B * pq.S * s.nq * s.d : 0;
   const size_t ek = pk.S > 1 ? 2 * (size_t)s.B * pk.S * s.nk * s.d : 0;
   return (size_t)s.B * s.h * s.nq + (eq > ek ? eq : ek);
@@ -587,12 +1006,14 @@ size_t attn_core_bwd_elems(const pca_mab_shape& s) {
 
 int attn_core_fwd(const pca_mab_shape& s, const float* Qp, const float* Kp, const float* Vp, float* O,
                   float* LSE, hipStream_t st) {
-  const Plan p = plan_of(s.B, s.nq, s.nk);
+  const Plan p = core_plan(s, s.nq, s.nk);
   AttnCoreArgs a = core_args(s, p);
   a.Qp = Qp; a.Kp = Kp; a.Vp = Vp; a.Oout = O; a.LSE = LSE;
   a.part = LSE + (size_t)s.B * s.h * s.nq;
   const size_t ldsb = (size_t)(row_elems(s.d) + tr_elems(s.d)) * sizeof(__bf16);
-  if (s.h <= 8) hipLaunchKernelGGL(k_attnc_fwd<8>, dim3(grid_of(s, p)), dim3(64 * s.h), ldsb, st, a);
+  if (dh32(s) || s.d > 64) allow_big_lds();
+  if (dh32(s)) hipLaunchKernelGGL(k_attn32_fwd, dim3(grid_of(s, p)), dim3(64 * s.h), ldsb, st, a);
+  else if (s.h <= 8) hipLaunchKernelGGL(k_attnc_fwd<8>, dim3(grid_of(s, p)), dim3(64 * s.h), ldsb, st, a);
   else hipLaunchKernelGGL(k_attnc_fwd<16>, dim3(grid_of(s, p)), dim3(64 * s.h), ldsb, st, a);
   PCA_TRY(check_launch("k_attnc_fwd"));
   if (p.S > 1) {
@@ -609,12 +1030,14 @@ int attn_core_bwd(const pca_mab_shape& s, const float* Qp, const float* Kp, cons
                   float* Delta, hipStream_t st) {
   float* part = Delta + (size_t)s.B * s.h * s.nq;
   {
-    const Plan p = plan_of(s.B, s.nq, s.nk);
+    const Plan p = core_plan(s, s.nq, s.nk);
     AttnCoreArgs a = core_args(s, p);
     a.Qp = Qp; a.Kp = Kp; a.Vp = Vp; a.O = O; a.LSE = const_cast<float*>(LSE); a.dO = dO;
     a.dQp = dQp; a.Delta = Delta; a.part = part;
     const size_t ldsb = (size_t)(2 * row_elems(s.d) + tr_elems(s.d)) * sizeof(__bf16);
-    if (s.h <= 8) hipLaunchKernelGGL(k_attnc_bwd_q<8>, dim3(grid_of(s, p)), dim3(64 * s.h), ldsb, st, a);
+    if (dh32(s) || s.d > 64) allow_big_lds();
+    if (dh32(s)) hipLaunchKernelGGL(k_attn32_bwd_q, dim3(grid_of(s, p)), dim3(64 * s.h), ldsb, st, a);
+    else if (s.h <= 8) hipLaunchKernelGGL(k_attnc_bwd_q<8>, dim3(grid_of(s, p)), dim3(64 * s.h), ldsb, st, a);
   else hipLaunchKernelGGL(k_attnc_bwd_q<16>, dim3(grid_of(s, p)), dim3(64 * s.h), ldsb, st, a);
     PCA_TRY(check_launch("k_attnc_bwd_q"));
     if (p.S > 1) {
@@ -624,13 +1047,14 @@ int attn_core_bwd(const pca_mab_shape& s, const float* Qp, const float* Kp, cons
       PCA_TRY(check_launch("k_attnc_sum"));
     }
   }
-  const Plan p = plan_of(s.B, s.nk, s.nq);
+  const Plan p = core_plan(s, s.nk, s.nq);
   AttnCoreArgs a = core_args(s, p);
   a.Qp = Qp; a.Kp = Kp; a.Vp = Vp; a.LSE = const_cast<float*>(LSE); a.dO = dO;
   a.dKp = dKp; a.dVp = dVp; a.Delta = Delta; a.part = part;
   const size_t nb16 = 2 * (size_t)row_elems(s.d) + 2 * (size_t)tr_elems(s.d);
   const size_t ldsb = ((nb16 + 7) & ~(size_t)7) * sizeof(__bf16) + 2 * (size_t)s.h * CH * sizeof(float);
-  if (s.h <= 8) hipLaunchKernelGGL(k_attnc_bwd_kv<8>, dim3(grid_of(s, p)), dim3(64 * s.h), ldsb, st, a);
+  if (dh32(s)) hipLaunchKernelGGL(k_attn32_bwd_kv, dim3(grid_of(s, p)), dim3(64 * s.h), ldsb, st, a);
+  else if (s.h <= 8) hipLaunchKernelGGL(k_attnc_bwd_kv<8>, dim3(grid_of(s, p)), dim3(64 * s.h), ldsb, st, a);
   else hipLaunchKernelGGL(k_attnc_bwd_kv<16>, dim3(grid_of(s, p)), dim3(64 * s.h), ldsb, st, a);
   PCA_TRY(check_launch("k_attnc_bwd_kv"));
   if (p.S > 1) {

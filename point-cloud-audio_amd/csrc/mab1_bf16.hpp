@@ -243,6 +243,10 @@ int prep_weight_f8(const float* src, void* dst, int rows, int cols, int mode, fl
 // fused attention core of the bf16-operand GEMM chain for head dims <= 16 (attn_core.hip): O = Q_ + A V_
 // and its adjoint without the [B h, nq, nk] matrix A (LSE [B][h][nq] is what is saved instead)
 bool attn_core_ok(const pca_mab_shape& s);
+// self-attention-shaped blocks (SAB) reached through the C ABI only (kind 4, api_mab.hip): the same core
+// for head dims 8 / 16 at d <= 128, and its head-dim-32 kernels for d <= 256.  Never consulted by the
+// ST engine, whose blocks keep attn_core_ok.
+bool attn_core_sab_ok(const pca_mab_shape& s);
 // floats of the forward's saved statistics area / of the backward's Delta scratch
 size_t attn_core_fwd_elems(const pca_mab_shape& s);
 size_t attn_core_bwd_elems(const pca_mab_shape& s);
@@ -268,14 +272,22 @@ int lin64_fc_o_bwd(const float* dY, const float* Z, const float* W, float* dZ, f
                    hipStream_t st);
 // exact fp32 path (mab_f32.hip)
 int validate_shape(const pca_mab_shape* s);
-size_t mab_f32_saved_bytes(const pca_mab_shape& s);
-size_t mab_f32_bwd_ws_bytes(const pca_mab_shape& s);
+// core / sab = true (kind 4, attn_core_sab_ok shapes): the attention runs on the fused core and the
+// backward's weight gradients on wgrad_rows; false: the core where attn_core_ok holds, else through the
+// materialised A, and linear_dw_db
+size_t mab_f32_saved_bytes(const pca_mab_shape& s, bool core = false);
+size_t mab_f32_bwd_ws_bytes(const pca_mab_shape& s, bool sab = false);
 int mab_f32_fwd(const pca_mab_shape& s, const float* Q, const float* K,
-                const pca_mab_params& p, float* Y, void* saved, hipStream_t st);
+                const pca_mab_params& p, float* Y, void* saved, hipStream_t st, bool core = false);
 int mab_f32_bwd(const pca_mab_shape& s, const float* Q, const float* K,
                 const pca_mab_params& p, const void* saved, const float* dY, float* dQ,
                 float* dK, int dk_accumulate, const pca_mab_grads& g, void* ws,
-                hipStream_t st);
+                hipStream_t st, bool sab = false);
+// dW[dout][din] += dY[M][dout]^T X[M][din], db += colsum(dY) with bf16 MFMA operands, bitwise reproducible
+// (wgrad_rows.hip); ws: wgrad_rows_ws_elems floats
+size_t wgrad_rows_ws_elems(int64_t M, int dout, int din);
+int wgrad_rows(const float* dY, const float* X, float* dW, float* db, int64_t M, int din, int dout, float* ws,
+               hipStream_t st);
 // while alive: linear_fwd_f32 / linear_bwd_f32 / linear_dx_acc_f32 use k_gemm_bf16 instead of the
 // exact fp32 GEMM: mode 1 = bf16 MFMA operands, mode 2 = hi + lo bf16 pairs (fp32-level results
 // at the same launch cost); fp32 accumulation and I/O

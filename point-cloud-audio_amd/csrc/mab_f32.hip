@@ -36,7 +36,7 @@ struct SavedF32 {
   float *O1, *Ypre, *mean0, *rstd0, *mean1, *rstd1;
 };
 
-inline size_t saved_elems(const pca_mab_shape& s, SavedF32* out, void* base) {
+inline size_t saved_elems(const pca_mab_shape& s, SavedF32* out, void* base, bool core) {
   const int64_t Bq = s.q_shared ? 1 : s.B;
   Carver c(base);
   SavedF32 v;
@@ -44,7 +44,7 @@ inline size_t saved_elems(const pca_mab_shape& s, SavedF32* out, void* base) {
   v.Kp = c.take<float>((size_t)s.B * s.nk * s.d);
   v.Vp = c.take<float>((size_t)s.B * s.nk * s.d);
   // (the fused attention core keeps the log-sum-exp [B][h][nq] here instead of the matrix A)
-  v.A = c.take<float>(attn_core_ok(s) ? attn_core_fwd_elems(s) : (size_t)s.B * s.h * s.nq * s.nk);
+  v.A = c.take<float>(core ? attn_core_fwd_elems(s) : (size_t)s.B * s.h * s.nq * s.nk);
   v.O = c.take<float>((size_t)s.B * s.nq * s.d);
   v.Z = c.take<float>((size_t)s.B * s.nq * s.d);
   v.O1 = v.Ypre = v.mean0 = v.rstd0 = v.mean1 = v.rstd1 = nullptr;
@@ -65,21 +65,29 @@ struct BwdWsF32 {
   float *dZ, *dO, *dQp, *dA, *dKp, *dVp, *dQps;
   float* dYp;       // ln = 1: gradient w.r.t. the input of ln1
   float* Wt;        // [d][d]: a transposed weight (linear_dx of large bf16-mode problems)
+  float* wpart;     // self-attention blocks (kind 4): the slabs of the deterministic weight gradients
 };
 
-inline size_t bwd_ws_elems(const pca_mab_shape& s, BwdWsF32* out, void* base) {
+inline size_t bwd_ws_elems(const pca_mab_shape& s, BwdWsF32* out, void* base, bool core, bool sab) {
   Carver c(base);
   BwdWsF32 v;
   v.dZ = c.take<float>((size_t)s.B * s.nq * s.d);
   v.dO = c.take<float>((size_t)s.B * s.nq * s.d);
   v.dQp = c.take<float>((size_t)s.B * s.nq * s.d);
-  v.dA = c.take<float>(attn_core_ok(s) ? attn_core_bwd_elems(s) : (size_t)s.B * s.h * s.nq * s.nk);
+  v.dA = c.take<float>(core ? attn_core_bwd_elems(s) : (size_t)s.B * s.h * s.nq * s.nk);
   v.dKp = c.take<float>((size_t)s.B * s.nk * s.d);
   v.dVp = c.take<float>((size_t)s.B * s.nk * s.d);
   v.dQps = c.take<float>((size_t)s.nq * s.d);
   v.dYp = s.ln ? c.take<float>((size_t)s.B * s.nq * s.d) : nullptr;
   const int wmax = s.dq > s.dk ? (s.dq > s.d ? s.dq : s.d) : (s.dk > s.d ? s.dk : s.d);
   v.Wt = c.take<float>((size_t)s.d * wmax);
+  v.wpart = nullptr;
+  if (sab) {   // fc_q, fc_k, fc_v over the inputs, fc_o over O: one launch at a time
+    const size_t a = wgrad_rows_ws_elems((int64_t)s.B * s.nk, s.d, s.dk);
+    const size_t b = wgrad_rows_ws_elems((int64_t)s.B * s.nq, s.d, s.dq);
+    const size_t o = wgrad_rows_ws_elems((int64_t)s.B * s.nq, s.d, s.d);
+    v.wpart = c.take<float>(a > b ? (a > o ? a : o) : (b > o ? b : o));
+  }
   if (out) *out = v;
   return c.off;
 }
@@ -161,14 +169,19 @@ int validate_shape(const pca_mab_shape* s) {
   return PCA_OK;
 }
 
-size_t mab_f32_saved_bytes(const pca_mab_shape& s) { return saved_elems(s, nullptr, nullptr); }
-size_t mab_f32_bwd_ws_bytes(const pca_mab_shape& s) { return bwd_ws_elems(s, nullptr, nullptr); }
+size_t mab_f32_saved_bytes(const pca_mab_shape& s, bool core) {
+  return saved_elems(s, nullptr, nullptr, core || attn_core_ok(s));
+}
+size_t mab_f32_bwd_ws_bytes(const pca_mab_shape& s, bool sab) {
+  return bwd_ws_elems(s, nullptr, nullptr, sab || attn_core_ok(s), sab);
+}
 
 int mab_f32_fwd(const pca_mab_shape& s, const float* Q, const float* K,
-                const pca_mab_params& p, float* Y, void* saved, hipStream_t st) {
+                const pca_mab_params& p, float* Y, void* saved, hipStream_t st, bool core) {
   OperandMode om(s);
+  core = core || attn_core_ok(s);
   SavedF32 v;
-  saved_elems(s, &v, saved);
+  saved_elems(s, &v, saved, core);
   const int64_t Bq = s.q_shared ? 1 : s.B;
   const int d = s.d, h = s.h, dh = d / h, nq = s.nq, nk = s.nk;
   const int64_t qb = s.q_shared ? 0 : (int64_t)nq * d;   // batch stride of Qp
@@ -178,8 +191,9 @@ int mab_f32_fwd(const pca_mab_shape& s, const float* Q, const float* K,
   PCA_TRY(linear(K, p.wk, p.bk, v.Kp, (int64_t)s.B * nk, s.dk, d, 0, st)); // :21
   PCA_TRY(linear(K, p.wv, p.bv, v.Vp, (int64_t)s.B * nk, s.dk, d, 0, st)); // :21
 
-  if (attn_core_ok(s)) {
-    // head dim <= 16 in the bf16-operand mode: scores, softmax and A V in one launch, A never exists
+  if (core) {
+    // head dim <= 16 in the bf16-operand mode (or a self-attention block at head dim 32): scores,
+    // softmax and A V in one launch, A never exists
     PCA_TRY(attn_core_fwd(s, v.Qp, v.Kp, v.Vp, v.O, v.A, st));             // :28-29
   } else {
   {  // S[b,j] = Qp_j Kp_j^T  -> A buffer                                       :28
@@ -221,12 +235,18 @@ int mab_f32_fwd(const pca_mab_shape& s, const float* Q, const float* K,
 int mab_f32_bwd(const pca_mab_shape& s, const float* Q, const float* K,
                 const pca_mab_params& p, const void* saved, const float* dY, float* dQ,
                 float* dK, int dk_accumulate, const pca_mab_grads& g, void* ws,
-                hipStream_t st) {
+                hipStream_t st, bool sab) {
   OperandMode om(s);
+  const bool core = sab || attn_core_ok(s);
   SavedF32 v;
-  saved_elems(s, &v, const_cast<void*>(saved));
+  saved_elems(s, &v, const_cast<void*>(saved), core);
   BwdWsF32 w;
-  bwd_ws_elems(s, &w, ws);
+  bwd_ws_elems(s, &w, ws, core, sab);
+  // weight + bias gradients: a self-attention block takes the deterministic row-slab kernels (wgrad_rows.hip)
+  auto wgrad = [&](const float* dYg, const float* X, float* dW, float* db, int64_t M, int din, int dout) {
+    return sab ? wgrad_rows(dYg, X, dW, db, M, din, dout, w.wpart, st)
+               : linear_dw_db(dYg, X, dW, db, M, din, dout, st);
+  };
   const int d = s.d, h = s.h, dh = d / h, nq = s.nq, nk = s.nk;
   const int64_t Mq = (int64_t)s.B * nq, Mk = (int64_t)s.B * nk;
   const int64_t qb = s.q_shared ? 0 : (int64_t)nq * d;
@@ -245,17 +265,17 @@ int mab_f32_bwd(const pca_mab_shape& s, const float* Q, const float* K,
       lin64_ok(v.Z, w.dZ, Mq, d, d)) {
     // dZ = dY . [Z > 0] and dO = dY + dZ Wo in one launch (linear64.hip)
     PCA_TRY(lin64_fc_o_bwd(dYe, v.Z, p.wo, w.dZ, w.dO, Mq, st));
-    PCA_TRY(linear_dw_db(w.dZ, Oe, g.wo, g.bo, Mq, d, d, st));
+    PCA_TRY(wgrad(w.dZ, Oe, g.wo, g.bo, Mq, d, d));
   } else {
     PCA_TRY(relu_bwd(dYe, v.Z, w.dZ, Mq * d, st));
-    PCA_TRY(linear_dw_db(w.dZ, Oe, g.wo, g.bo, Mq, d, d, st));
+    PCA_TRY(wgrad(w.dZ, Oe, g.wo, g.bo, Mq, d, d));
     PCA_TRY(copy_rows(dYe, Mq, w.dO, Mq, d, st));
     PCA_TRY(linear_dx(w.dZ, p.wo, w.dO, Mq, d, d, 1, st, w.Wt));
   }
   if (s.ln)     // in place: every element is read before it is rewritten
     PCA_TRY(layernorm_bwd(w.dO, v.O, v.mean0, v.rstd0, p.ln0_w, w.dO, g.ln0_w, g.ln0_b, Mq, d, st));
 
-  if (attn_core_ok(s)) {
+  if (core) {
     // the adjoint of the fused core: P recomputed from the saved log-sum-exp, dQp (incl. the residual),
     // dKp and dVp written once each (w.dA holds delta = rowdot(dO, A V))
     PCA_TRY(attn_core_bwd(s, v.Qp, v.Kp, v.Vp, v.O, v.A, w.dO, w.dQp, w.dKp, w.dVp, w.dA, st));
@@ -293,8 +313,8 @@ int mab_f32_bwd(const pca_mab_shape& s, const float* Q, const float* K,
   }
 
   // fc_k / fc_v
-  PCA_TRY(linear_dw_db(w.dKp, K, g.wk, g.bk, Mk, s.dk, d, st));
-  PCA_TRY(linear_dw_db(w.dVp, K, g.wv, g.bv, Mk, s.dk, d, st));
+  PCA_TRY(wgrad(w.dKp, K, g.wk, g.bk, Mk, s.dk, d));
+  PCA_TRY(wgrad(w.dVp, K, g.wv, g.bv, Mk, s.dk, d));
   if (dK != nullptr) {
     PCA_TRY(linear_dx(w.dKp, p.wk, dK, Mk, s.dk, d, dk_accumulate ? 1 : 0, st, w.Wt));
     PCA_TRY(linear_dx(w.dVp, p.wv, dK, Mk, s.dk, d, 1, st, w.Wt));
@@ -306,7 +326,7 @@ int mab_f32_bwd(const pca_mab_shape& s, const float* Q, const float* K,
     PCA_TRY(linear_dw_db(w.dQps, Q, g.wq, g.bq, nq, s.dq, d, st));
     if (dQ != nullptr) PCA_TRY(linear_dx(w.dQps, p.wq, dQ, nq, s.dq, d, 1, st));
   } else {
-    PCA_TRY(linear_dw_db(w.dQp, Q, g.wq, g.bq, Mq, s.dq, d, st));
+    PCA_TRY(wgrad(w.dQp, Q, g.wq, g.bq, Mq, s.dq, d));
     if (dQ != nullptr) PCA_TRY(linear_dx(w.dQp, p.wq, dQ, Mq, s.dq, d, 0, st, w.Wt));
   }
   return PCA_OK;

@@ -65,7 +65,13 @@ class MAB(nn.Module):
 
 
 class SAB(nn.Module):
-    """Self-attention block MAB(X, X), reference modules.py:35-41."""
+    """Self-attention block MAB(X, X), reference modules.py:35-41.
+
+    In 'bf16' / 'fp8' mode (and so under 'auto') it runs at any set size, ``lengths`` or not: SAB
+    shapes that no fused block kernel takes (all but N = 16 / 32 without lengths at d = 128) run the
+    bf16-operand chain with the attention on a fused core that never builds the N x N scores (head
+    dim 32 up to d = 256, head dims 8 / 16 up to d = 128; memory linear in N).  Head dim 64,
+    ``ln=True`` and wider shapes stay exact fp32 ('auto') or raise ('bf16')."""
 
     def __init__(self, dim_in, dim_out, num_heads, ln=False):
         super().__init__()

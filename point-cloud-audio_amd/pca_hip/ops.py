@@ -24,7 +24,9 @@ def set_mode(mode: str) -> None:
     'bf16' = bf16 MFMA operands with fp32 accumulate/softmax (fails for shapes the fused
     kernels do not cover), 'fp8' = as bf16 with fp8 (e4m3) operands in fc_o of the many-queries
     blocks and fc_k / fc_v of the d = 256 few-queries block (fc_q stays bf16:
-    include/pca_hip.h), 'auto' = bf16 where covered, else f32."""
+    include/pca_hip.h), 'auto' = bf16 where covered, else f32.  Self-attention blocks (modules.SAB:
+    per-set queries, Q = K) are covered at every set size for head dims 8 / 16 / 32 (fp8 runs them as
+    bf16), so 'auto' resolves them to bf16."""
     global _MODE
     if mode not in ("f32", "bf16", "fp8", "auto"):
         raise ValueError(mode)
