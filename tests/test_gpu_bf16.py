@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from emu import mab0_forward_bf16emu
+import grad_bars as gb
 from util import T, close, close_robust
 
 pytestmark = pytest.mark.gpu
@@ -214,6 +215,8 @@ def test_engine_bf16_vs_golden(dev, golden_st):
         off += prm.numel()
         worst = max(worst, close_robust(gr, golden_st[f"{name}/g/{k}"], BWD_TOL, k,
                                         outlier_frac=2e-3))
+    gb.judge(eng.grads, golden_st.sub(f"{name}/g/"), gb.BF16_VS_ORACLE, gb.shapes_of(net),
+             f"{name} engine bf16 vs golden")
     print(f"engine bf16: logits err {err:.2e}, worst grad err {worst:.2e}")
     inf = trainer.STEngine(net, B, N, mode=_lib.MODE_BF16, training=False)
     close(inf.forward(X), ref, FWD_TOL, "logits(inference)")
@@ -444,6 +447,15 @@ def test_engine_bf16_generic_gemm_path(dev, golden_st, ci):
             worst = max(worst, close_robust(gr.reshape(-1)[::gi.GRAD_SUBSAMPLE],
                                             golden_st[f"{name}/gsub/{k}"], 5e-2, k,
                                             outlier_frac=5e-3))
+    if full:
+        gb.judge(eng.grads, golden_st.sub(f"{name}/g/"), gb.BF16_VS_ORACLE, gb.shapes_of(net),
+                 f"{name} bf16 generic path vs golden")
+    else:
+        sub = {k: v.reshape(-1)[::gi.GRAD_SUBSAMPLE]
+               for k, v in gb.split(eng.grads, gb.shapes_of(net)).items()}
+        gb.judge(sub, golden_st.sub(f"{name}/gsub/"), gb.BF16_VS_ORACLE,
+                 [(k, tuple(v.shape)) for k, v in sub.items()],
+                 f"{name} bf16 generic path vs golden (subsampled)")
     print(f"{name} bf16 generic path: logits err {err:.2e}, worst grad err {worst:.2e}")
     inf = trainer.STEngine(net, B, N, mode=_lib.MODE_BF16, training=False)
     close(inf.forward(X), ref, 3e-2, "logits(inference)")
@@ -474,6 +486,7 @@ def test_engine_bf16_generic_path_large_rows(dev):
         worst = max(worst, close_robust(eng.grads[off:off + n], exact.grads[off:off + n], 5e-2, k,
                                         outlier_frac=5e-3))
         off += n
+    gb.judge(eng.grads, exact.grads, gb.BF16_VS_ORACLE, gb.shapes_of(net), "bf16 chain vs fp32 chain")
     print(f"configs[3] architecture, B=16 N=4096: logits err {err:.2e}, worst grad err {worst:.2e}")
     inf = trainer.STEngine(net, B, N, mode=_lib.MODE_BF16, training=False)    # fused mab1 forward
     close(inf.forward(X), exact.logits, 3e-2, "logits(inference)")

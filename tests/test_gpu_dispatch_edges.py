@@ -28,6 +28,7 @@ import pytest
 import torch
 
 from dispatch import launches
+import grad_bars as gb
 from util import T, close, close_robust
 
 import inputs as gi
@@ -114,7 +115,8 @@ def _train(dev, net, Xn, yn, mode, set128=True, families=FUSED + ("set_fwd", "ge
     return (*out, n, eng)
 
 
-def _vs_oracle(net, Xn, yn, h, lg, loss, g, ftol=ST_FWD_TOL, gtol=ST_BWD_TOL, frac=5e-3):
+def _vs_oracle(net, Xn, yn, h, lg, loss, g, ftol=ST_FWD_TOL, gtol=ST_BWD_TOL, frac=5e-3,
+               bar=gb.BF16_VS_ORACLE):
     from oracle import st_oracle as orc
     B = Xn.shape[0]
     # a ReLU of the PMA's fc_o whose bf16-rounded pre-activation changes sign moves a whole row of that
@@ -129,6 +131,8 @@ def _vs_oracle(net, Xn, yn, h, lg, loss, g, ftol=ST_FWD_TOL, gtol=ST_BWD_TOL, fr
                                         k + " vs oracle", outlier_frac=frac))
         off += prm.numel()
     assert off == g.numel()
+    gb.judge(g, ref_g, bar, gb.shapes_of(net), f"B={B} N={Xn.shape[1]} vs oracle",
+             outlier_frac=max(frac, bar.outlier_frac), zero=gb.SINGLE_KEY if Xn.shape[1] == 1 else ())
     return e, worst
 
 
@@ -141,6 +145,7 @@ def _vs_per_block(net, lg1, loss1, g1, lg0, loss0, g0):
         close_robust(g1[off:off + prm.numel()].view_as(prm), g0[off:off + prm.numel()].view_as(prm).cpu(),
                      6e-3, k + " vs per-block", outlier_frac=1e-3)
         off += prm.numel()
+    gb.judge(g1, g0, gb.PEER, gb.shapes_of(net), "set-resident vs per-block")
 
 
 def _max_fitting_batch():
@@ -518,7 +523,7 @@ def test_d128_m32_mixed_dispatch(dev, mode):
         e, w = _vs_oracle(net, Xn, yn, h, lg, loss, g)
     else:
         assert n["mab1_fwd"] == 0 and n["mab1_bwd"] == 0, n
-        e, w = _vs_oracle(net, Xn, yn, h, lg, loss, g, F8_FWD_TOL, F8_BWD_TOL, 1e-2)
+        e, w = _vs_oracle(net, Xn, yn, h, lg, loss, g, F8_FWD_TOL, F8_BWD_TOL, 1e-2, bar=gb.FP8_VS_ORACLE)
     assert n["set_fwd"] == 0, n
     print(f"d128 m32 {mode}: {n}; logits {e:.2e}, worst grad {w:.2e}")
 

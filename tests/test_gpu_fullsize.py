@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import grad_bars as gb
 from util import T, close, close_robust
 
 import inputs as gi
@@ -58,6 +59,8 @@ def _check(dev, B, N, din, d, h, m, C, mode, seed):
         else:
             worst = max(worst, close_robust(g, ref_g[k], 5e-2, k, outlier_frac=1e-3))
     assert off == eng.grads.numel()
+    gb.judge(eng.grads, ref_g, gb.F32 if mode == "f32" else gb.BF16_VS_ORACLE, gb.shapes_of(net),
+             f"B={B} N={N} d={d} {mode} vs oracle")
     inf = trainer.STEngine(net, B, N, md, training=False)
     close(inf.forward(T(X, dev)), ref_lg.reshape(B, C), tol_l, "logits(inference)")
     print(f"B={B} N={N} din={din} d={d} m={m} {mode}: logits err {e_lg:.2e}, worst grad err {worst:.2e}")
@@ -243,6 +246,10 @@ def _check_vs_emulation(dev, B, N, mode, lengths, seed):
         close_robust(g, ref_g[k], 5e-2 if not fp8 else 1e-1, k + " vs exact oracle",
                      outlier_frac=1e-3 if not fp8 else 1e-2)
     assert off == eng.grads.numel()
+    shapes = gb.shapes_of(net)
+    gb.judge(eng.grads, emu_g, gb.FP8_VS_EMU if fp8 else gb.BF16_VS_EMU, shapes, f"{mode} vs emulation")
+    gb.judge(eng.grads, ref_g, gb.FP8_VS_ORACLE if fp8 else gb.BF16_VS_ORACLE, shapes,
+             f"{mode} vs exact oracle")
     print(f"B={B} N={N} {mode} lengths {min(lengths)}..{max(lengths)}: logits vs emulation {e1:.2e}, "
           f"worst grad vs emulation {worst:.2e}")
 

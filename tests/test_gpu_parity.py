@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import inputs as gi
+import grad_bars as gb
 from util import T, close
 
 pytestmark = pytest.mark.gpu
@@ -145,6 +146,14 @@ def test_st_golden(dev, golden_st, case):
                   BWD_TOL, k)
             nrm = float(golden_st[f"{name}/gnorm/{k}"])
             assert abs(float(p.grad.double().norm()) - nrm) <= 2e-4 * max(nrm, 1e-3), k
+    gb.own_close(X.grad, golden_st[f"{name}/dX"], gb.F32, "dX")
+    if full:
+        gb.judge({k: p.grad for k, p in net.named_parameters()}, golden_st.sub(f"{name}/g/"), gb.F32,
+                 gb.shapes_of(net), f"{name} module vs golden")
+    else:
+        sub = {k: p.grad.reshape(-1)[::gi.GRAD_SUBSAMPLE] for k, p in net.named_parameters()}
+        gb.judge(sub, golden_st.sub(f"{name}/gsub/"), gb.F32, [(k, tuple(v.shape)) for k, v in sub.items()],
+                 f"{name} module vs golden (subsampled)")
 
 
 @pytest.mark.parametrize("tag,din,Ns", [("fst", 2, gi.CKPT_2D_N), ("tst", 3, gi.CKPT_3D_N)])
@@ -392,6 +401,14 @@ def test_engine_golden(dev, golden_st, case):
             else:
                 close(g.reshape(-1)[::gi.GRAD_SUBSAMPLE], golden_st[f"{name}/gsub/{k}"],
                       BWD_TOL, k)
+        if full:
+            gb.judge(eng.grads, golden_st.sub(f"{name}/g/"), gb.F32, gb.shapes_of(net),
+                     f"{name} engine phases {phases} vs golden")
+        else:
+            sub = {k: v.reshape(-1)[::gi.GRAD_SUBSAMPLE]
+                   for k, v in gb.split(eng.grads, gb.shapes_of(net)).items()}
+            gb.judge(sub, golden_st.sub(f"{name}/gsub/"), gb.F32,
+                     [(k, tuple(v.shape)) for k, v in sub.items()], f"{name} engine phases {phases} vs golden (subsampled)")
 
 
 @pytest.mark.parametrize("use_graph", [False, True], ids=["eager", "hipgraph"])

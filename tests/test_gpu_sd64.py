@@ -111,6 +111,7 @@ def test_shipped_shape_train_step_fused_core(dev, case):
     import models
     from oracle import st_oracle as orc
     from pca_hip import _lib, trainer
+    import grad_bars as gb
     from util import T, close_robust
     din, d, h, m, C, B, N, lengths = case
     torch.manual_seed(77 + N)
@@ -141,9 +142,12 @@ def test_shipped_shape_train_step_fused_core(dev, case):
     for k, prm in net.named_parameters():
         close_robust(eng.grads[off:off + prm.numel()].view_as(prm), ref_g[k], 5e-2, k, outlier_frac=2e-3)
         off += prm.numel()
+    shapes = gb.shapes_of(net)
+    gb.judge(eng.grads, ref_g, gb.BF16_VS_ORACLE, shapes, f"d={d} N={N} vs oracle")
     # the exact mode of the library on the same batch (it materialises A like the reference)
     e32 = trainer.STEngine(net, B, N, _lib.MODE_F32, training=True)
     e32.fwd_bwd(T(X, dev), T(y, dev), lengths=ld)
     torch.cuda.synchronize()
     close(eng.logits, e32.logits.cpu(), 3e-2, "logits vs fp32 mode")
     close_robust(eng.grads, e32.grads.cpu(), 5e-2, "grads vs fp32 mode", outlier_frac=2e-3)
+    gb.judge(eng.grads, e32.grads, gb.BF16_VS_ORACLE, shapes, f"d={d} N={N} vs fp32 mode")

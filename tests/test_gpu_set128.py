@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from dispatch import launches
+import grad_bars as gb
 from util import T, close, close_robust
 
 import inputs as gi
@@ -90,6 +91,7 @@ def test_set128_forward_equals_per_block_launches(dev, B, N, din, head):
         bref = g0[off:off + prm.numel()].view_as(prm).cpu()
         off += prm.numel()
         worst = max(worst, close_robust(a, bref, 6e-3, k, outlier_frac=1e-3))
+    gb.judge(g1, g0, gb.PEER, gb.shapes_of(net), f"B={B} N={N} din={din} set-resident vs per-block")
     print(f"B={B} N={N} din={din}: logits {e:.2e}, worst grad {worst:.2e}")
 
 
@@ -112,6 +114,7 @@ def test_set128_train_step_vs_oracle(dev, B, N, din):
     for k, prm in net.named_parameters():
         close_robust(g[off:off + prm.numel()].view_as(prm), ref_g[k], 5e-2, k, outlier_frac=5e-3)
         off += prm.numel()
+    gb.judge(g, ref_g, gb.BF16_VS_ORACLE, gb.shapes_of(net), f"B={B} N={N} din={din} vs oracle")
 
 
 def test_handoff_timeouts_are_surfaced(dev):

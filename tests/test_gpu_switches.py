@@ -95,6 +95,8 @@ CLOSE_CASES = [
 @pytest.mark.parametrize("shape,var", CLOSE_CASES, ids=[c[1] for c in CLOSE_CASES])
 def test_switch_is_numerically_neutral(shape, var, tmp_path):
     import numpy as np
+    import grad_bars as gb
+    from oracle import st_oracle as orc
     from util import close, close_robust
     fa, fb = str(tmp_path / "a.npz"), str(tmp_path / "b.npz")
     _run(shape, {"PCA_TEST_DUMP": fa})
@@ -103,3 +105,7 @@ def test_switch_is_numerically_neutral(shape, var, tmp_path):
     close(a["logits"], b["logits"], 3e-2, f"{var}: logits")
     assert abs(float(a["loss"][0]) - float(b["loss"][0])) < 3e-2
     close_robust(a["grads"], b["grads"], 5e-2, f"{var}: gradients", outlier_frac=5e-3)
+    # the same 45 gradients tensor by tensor, each on its own scale
+    B, N, din, d, h, m, C = shape
+    shapes = orc.st_param_shapes(din, 1, C, m, d)
+    gb.judge(a["grads"], b["grads"], gb.PEER, shapes, f"{var}=1 vs {var}=0")

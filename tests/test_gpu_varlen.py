@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import inputs as gi
+import grad_bars as gb
 from util import T, close, close_robust
 
 pytestmark = pytest.mark.gpu
@@ -76,6 +77,8 @@ def test_mask_equals_truncation_engine(dev, case, mode):
             close(g, ref_g[k], tol_b, k)
         else:
             close_robust(g, ref_g[k], 5e-2, k, outlier_frac=2e-3)
+    gb.judge(eng.grads, ref_g, gb.F32 if mode == "f32" else gb.BF16_VS_ORACLE, gb.shapes_of(net),
+             f"{name} {mode} vs truncated oracle")
     # garbage in the padding must not matter as long as it is finite
     X2 = X.copy()
     for b, L in enumerate(lengths):
@@ -144,6 +147,10 @@ def test_cfg5_train_step_vs_emulation(dev, mode):
         close_robust(g, ref_g[k], 5e-2 if not fp8 else 1e-1, k + " vs exact oracle",
                      outlier_frac=2e-3 if not fp8 else 1e-2)
     assert off == eng.grads.numel()
+    shapes = gb.shapes_of(net)
+    gb.judge(eng.grads, emu_g, gb.FP8_VS_EMU if fp8 else gb.BF16_VS_EMU, shapes, f"cfg5 {mode} vs emulation")
+    gb.judge(eng.grads, ref_g, gb.FP8_VS_ORACLE if fp8 else gb.BF16_VS_ORACLE, shapes,
+             f"cfg5 {mode} vs exact oracle")
     print(f"cfg5 {mode} train step: logits vs emulation {e1:.2e}, worst grad vs emulation {worst:.2e}")
     if fp8:       # not the bf16 kernels under another name
         engb = trainer.STEngine(net, B, N, _lib.MODE_BF16, training=True)
@@ -177,6 +184,8 @@ def test_mask_equals_truncation_modules(dev):
     close(lg, ref, 2e-5, "logits")
     for k, p in net.named_parameters():
         close(got[k], p.grad, 2e-4, k)
+    gb.judge(got, {k: p.grad for k, p in net.named_parameters()}, gb.F32, gb.shapes_of(net),
+             "masked vs per-set module calls")
     with torch.no_grad():
         close(net(Xd, torch.tensor(lengths)), ref, 2e-5, "logits(no_grad)")
 
