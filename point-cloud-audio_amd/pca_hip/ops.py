@@ -106,17 +106,44 @@ def _lengths(key_lengths, B: int, like: torch.Tensor):
     return kl
 
 
-def _pick_mode(s: MabShape, inference: bool = False) -> MabShape:
+def _unbuilt_input_grad(s: MabShape, need_dq: bool, need_dk: bool) -> Optional[str]:
+    """The input gradient a fused block of this shape cannot return, or None.  The layer-1 fused
+    kernels take the point set itself: the many-queries block (per-set queries, keys of width d) has
+    no dQ at dq <= 4, the few-queries block (shared queries) no dK at dk <= 4 - pca_mab_bwd returns
+    PCA_EUNSUPPORTED for them (csrc/mab1_bwd_bf16.hip, csrc/mab0_bwd_bf16.hip, csrc/d256_host.hip).
+    A self-attention block (dq = dk) runs the chain, which has both."""
+    if need_dq and not s.q_shared and s.dq <= 4 and s.dk == s.d:
+        return "dQ"
+    if need_dk and s.q_shared and s.dk <= 4:
+        return "dK"
+    return None
+
+
+def _pick_mode(s: MabShape, inference: bool = False, need_dq: bool = False,
+               need_dk: bool = False) -> MabShape:
     """Resolve the arithmetic mode of one block: 'bf16' demands the fused kernel, 'auto' takes
     it where the library has one for this shape (pca_mab_saved_bytes() > 0; forward-only calls
     ask pca_mab_fwd_ws_bytes(), which also covers the kernels that have no backward yet) else
-    exact fp32."""
+    exact fp32.  A training block whose backward must return an input gradient the fused kernel
+    does not build (``_unbuilt_input_grad``) resolves to exact fp32 under 'auto' and raises here,
+    at the forward, under 'bf16' / 'fp8'."""
     if _MODE == "f32":
         return s
     s.mode = _lib.MODE_FP8 if _MODE == "fp8" else _lib.MODE_BF16
     probe = lib().pca_mab_fwd_ws_bytes if inference else lib().pca_mab_saved_bytes
     if _MODE == "auto" and probe(C.byref(s)) == 0:
         s.mode = _lib.MODE_F32
+        return s
+    if not inference and probe(C.byref(s)) > 0:
+        bad = _unbuilt_input_grad(s, need_dq, need_dk)
+        if bad is not None and _MODE == "auto":
+            s.mode = _lib.MODE_F32
+        elif bad is not None:
+            raise _lib.PcaHipError(
+                f"mab: mode '{_MODE}' has no fused backward that returns {bad} for B={s.B} nq={s.nq} "
+                f"nk={s.nk} dq={s.dq} dk={s.dk} d={s.d} h={s.h} q_shared={s.q_shared} (the layer-1 "
+                f"kernels do not build the input gradient at width <= 4); use mode 'auto' or 'f32', "
+                f"or do not require the gradient of the {'query' if bad == 'dQ' else 'keys'}")
     return s
 
 
@@ -143,7 +170,8 @@ class _MabFn(torch.autograd.Function):
         if params[0].shape[1] != dq or params[2].shape[1] != dk:
             raise RuntimeError("MAB: input width does not match fc_q / fc_k")
         kl = _lengths(key_lengths, B, K)
-        s = _pick_mode(_shape(B, nq, nk, dq, dk, d, num_heads, q_shared, k_lengths=kl, ln=ln))
+        s = _pick_mode(_shape(B, nq, nk, dq, dk, d, num_heads, q_shared, k_lengths=kl, ln=ln),
+                       need_dq=ctx.needs_input_grad[0], need_dk=ctx.needs_input_grad[1])
         ctx.kl = kl                       # keeps the device array alive for the backward
         ctx.ln = ln
         L = lib()
