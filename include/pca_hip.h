@@ -126,6 +126,17 @@ int pca_stft_logmag_batch(const float* waves, const int64_t* wave_off, const int
                           int win_length, int hop, int n_bins, float* out, int64_t stride_f,
                           int64_t stride_t, void* stream);
 
+/* pca_stft_logmag_batch with the magnitude divided by `norm` instead of n_fft:
+ * log(1e-8 + |STFT(wave)| / norm)
+ * replaces: Code/pc_temp3d_eval.py:75, Code/pceval.py:76 (librosa.stft(x, n_fft=2**ceil(log2 N),
+ *           win_length=N, ...)/Nfft with Nfft = N: the re-framing loops divide by the window length)
+ * norm > 0 (fp64); norm == n_fft is bit-identical to pca_stft_logmag_batch. */
+int pca_stft_logmag_batch_norm(const float* waves, const int64_t* wave_off,
+                               const int64_t* frame_off, int n_clips, int64_t max_len,
+                               int64_t min_len, int n_fft, int win_length, int hop, int n_bins,
+                               float* out, int64_t stride_f, int64_t stride_t, double norm,
+                               void* stream);
+
 /* 2-D point sets for a batch of frames
  * replaces: Code/dataset.py:50-54  ESC_pc.__getitem__ (+ default_collate)
  * spec element (f, t) at spec[f*stride_f + t*stride_t]; farr[F] float32 (the
@@ -306,6 +317,16 @@ size_t pca_linear_bwd_ws_bytes(int64_t M, int din, int dout);
 int pca_cross_entropy(const float* logits, const int64_t* labels, int B, int C,
                       float grad_scale, float* loss_out, float* dlogits,
                       float* stats_out, void* stream);
+
+/* Correct-prediction tally of an evaluation batch
+ * replaces: Code/pceval.py:95, Code/pc_temp3d_eval.py:97, Code/rebut_expts.py:106
+ *           (correct += (preds.argmax(dim=1) == lbls).sum().item(), a host sync per batch)
+ * counts[slot] += #{b < B : argmax_c logits[b, c] == labels[b]}; logits[B, C] fp32, labels[B]
+ * int64, counts int64 (device).  argmax as torch.argmax: the first maximum wins, NaN counts as the
+ * maximum.  Integer adds only: the count is exact and independent of launch order, and a caller
+ * reads it once after many batches. */
+int pca_eval_tally(const float* logits, const int64_t* labels, int B, int C, int64_t* counts,
+                   int slot, void* stream);
 
 /* torch.optim.Adam(lr, betas, eps, weight_decay) with COUPLED L2, one fused pass
  * over a flat parameter vector.  replaces: Code/settransformer.py:89-91,106,108

@@ -1,6 +1,7 @@
 // STFT log-magnitude and point-set packing: the data side of the hot path.
 //
 //   k_stft_logmag  : Code/settransformer.py:49-50  librosa.stft(...)/Nfft ; log(1e-8+|.|)
+//                    (the divisor is an argument: Code/pc_temp3d_eval.py:75 divides by N)
 //   k_pack_2d      : Code/dataset.py:50-54         ESC_pc.__getitem__ for a whole batch
 //   k_pack_3d      : Code/dataset.py:160-166       ESC_pc_temp.__getitem__ for a whole batch
 //
@@ -30,7 +31,8 @@ __global__ __launch_bounds__(256) void k_stft_logmag(const float* __restrict__ w
                                                       float* __restrict__ out,
                                                       int64_t stride_f, int64_t stride_t,
                                                       const int64_t* __restrict__ wave_off,
-                                                      const int64_t* __restrict__ frame_off) {
+                                                      const int64_t* __restrict__ frame_off,
+                                                      double norm) {
   extern __shared__ __attribute__((aligned(16))) double2 lds_c[];
   double2* x = lds_c;                 // [n_fft]
   double2* tw = lds_c + n_fft;        // [n_fft/2]  exp(-2 pi i k / n_fft)
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(256) void k_stft_logmag(const float* __restrict__ w
     __syncthreads();
   }
 
-  const double inv = 1.0 / (double)n_fft;
+  const double inv = 1.0 / norm;
   for (int f = tid; f < n_bins; f += 256) {
     const double2 v = x[f];
     // the reference rounds the spectrum to complex64 before |.| (librosa dtype=complex64)
@@ -230,14 +232,15 @@ int pca_stft_logmag(const float* wave, int64_t L, int n_fft, int win_length, int
   });
   hipLaunchKernelGGL(pca::k_stft_logmag, dim3((unsigned)T), dim3(256), lds,
                      pca::as_stream(stream), wave, L, n_fft, log2n, win_length, hop, n_bins,
-                     out, stride_f, stride_t, (const int64_t*)nullptr, (const int64_t*)nullptr);
+                     out, stride_f, stride_t, (const int64_t*)nullptr, (const int64_t*)nullptr,
+                     (double)n_fft);
   return pca::check_launch("k_stft_logmag");
 }
 
-int pca_stft_logmag_batch(const float* waves, const int64_t* wave_off, const int64_t* frame_off,
+int pca_stft_logmag_batch_norm(const float* waves, const int64_t* wave_off, const int64_t* frame_off,
                           int n_clips, int64_t max_len, int64_t min_len, int n_fft,
                           int win_length, int hop, int n_bins, float* out, int64_t stride_f,
-                          int64_t stride_t, void* stream) {
+                          int64_t stride_t, double norm, void* stream) {
   PCA_REQUIRE(waves && wave_off && frame_off && out, "stft_logmag_batch: null pointer");
   PCA_REQUIRE(n_clips > 0 && n_clips <= 65535, "stft_logmag_batch: n_clips=%d", n_clips);
   PCA_REQUIRE(n_fft >= 64 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0,
@@ -246,6 +249,8 @@ int pca_stft_logmag_batch(const float* waves, const int64_t* wave_off, const int
               win_length);
   PCA_REQUIRE(hop > 0, "stft_logmag_batch: hop=%d", hop);
   PCA_REQUIRE(n_bins > 0 && n_bins <= n_fft / 2 + 1, "stft_logmag_batch: n_bins=%d", n_bins);
+  PCA_REQUIRE(norm > 0.0 && norm <= 1.0e300, "stft_logmag_batch: norm=%g must be positive and finite",
+              norm);
   PCA_REQUIRE(min_len > n_fft / 2 && max_len >= min_len,
               "stft_logmag_batch: reflect padding needs every clip longer than n_fft/2 "
               "(shortest %lld, longest %lld)", (long long)min_len, (long long)max_len);
@@ -260,8 +265,17 @@ int pca_stft_logmag_batch(const float* waves, const int64_t* wave_off, const int
   });
   hipLaunchKernelGGL(pca::k_stft_logmag, dim3((unsigned)T, (unsigned)n_clips), dim3(256), lds,
                      pca::as_stream(stream), waves, (int64_t)0, n_fft, log2n, win_length, hop,
-                     n_bins, out, stride_f, stride_t, wave_off, frame_off);
+                     n_bins, out, stride_f, stride_t, wave_off, frame_off, norm);
   return pca::check_launch("k_stft_logmag(batch)");
+}
+
+int pca_stft_logmag_batch(const float* waves, const int64_t* wave_off, const int64_t* frame_off,
+                          int n_clips, int64_t max_len, int64_t min_len, int n_fft,
+                          int win_length, int hop, int n_bins, float* out, int64_t stride_f,
+                          int64_t stride_t, void* stream) {
+  return pca_stft_logmag_batch_norm(waves, wave_off, frame_off, n_clips, max_len, min_len, n_fft,
+                                    win_length, hop, n_bins, out, stride_f, stride_t,
+                                    (double)n_fft, stream);
 }
 
 int pca_pack_points_2d(const float* spec, int64_t stride_f, int64_t stride_t,

@@ -1,6 +1,7 @@
 // Loss and optimiser of the train step (Code/settransformer.py:88-91,104-108):
 // nn.CrossEntropyLoss (mean) forward+gradient in one launch, and torch.optim.Adam with
-// coupled weight decay as one fused pass over a flat parameter vector.
+// coupled weight decay as one fused pass over a flat parameter vector.  Also the correct-count
+// tally of the evaluation sweeps (Code/pceval.py:95, (preds.argmax(dim=1) == lbls).sum()).
 #include "mab1_bf16.hpp"
 #include "terminal_bodies.hpp"
 #include "pma_head_bodies.hpp"
@@ -52,6 +53,39 @@ __global__ __launch_bounds__(256) void k_cross_entropy(const float* __restrict__
       if (am == (int)y) atomicAdd(&stats[1], 1.f);
     }
   }
+}
+
+// torch.argmax order of two (value, index) candidates: NaN is the maximum, equal values (and two
+// NaNs) go to the lower index
+__device__ inline bool argmax_before(float a, int ia, float b, int ib) {
+  const bool na = a != a, nb = b != b;
+  if (na != nb) return na;
+  if (!na && a != b) return a > b;
+  return ia < ib;
+}
+
+// one wave per sample: counts[slot] += #(argmax_c logits[b, c] == labels[b]); integer atomics, so the
+// count does not depend on the order the waves finish in
+__global__ __launch_bounds__(256) void k_eval_tally(const float* __restrict__ logits,
+                                                     const int64_t* __restrict__ labels, int B,
+                                                     int C, unsigned long long* __restrict__ count) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float* x = logits + (int64_t)b * C;
+  float m = -INFINITY;
+  int am = 0x7fffffff;
+  for (int j = lane; j < C; j += 64) {
+    const float v = x[j];
+    if (argmax_before(v, j, m, am)) { m = v; am = j; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(m, o, 64);
+    const int oa = __shfl_xor(am, o, 64);
+    if (argmax_before(om, oa, m, am)) { m = om; am = oa; }
+  }
+  if (lane == 0 && (int64_t)am == labels[b]) atomicAdd(count, 1ull);
 }
 
 // ---------------------------------------------------------------------------------
@@ -193,6 +227,17 @@ int pca_cross_entropy(const float* logits, const int64_t* labels, int B, int C,
   hipLaunchKernelGGL(pca::k_cross_entropy, dim3((unsigned)pca::cdiv(B, 4)), dim3(256), 0, st,
                      logits, labels, B, C, grad_scale, loss_out, dlogits, stats_out);
   return pca::check_launch("k_cross_entropy");
+}
+
+int pca_eval_tally(const float* logits, const int64_t* labels, int B, int C, int64_t* counts,
+                   int slot, void* stream) {
+  PCA_REQUIRE(logits && labels && counts, "eval_tally: null pointer");
+  PCA_REQUIRE(B > 0 && C > 0 && slot >= 0, "eval_tally: B=%d C=%d slot=%d", B, C, slot);
+  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counter width");
+  hipLaunchKernelGGL(pca::k_eval_tally, dim3((unsigned)pca::cdiv(B, 4)), dim3(256), 0,
+                     pca::as_stream(stream), logits, labels, B, C,
+                     reinterpret_cast<unsigned long long*>(counts + slot));
+  return pca::check_launch("k_eval_tally");
 }
 
 int pca_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,

@@ -16,6 +16,20 @@ axis is **parity unpinned** (SURVEY.md 8c); the kernel is checked against the CP
 same algorithm (tests/test_resample.py).
 Not covered: ``librosa.load`` / ``effects.trim`` (file decoding and silence trimming: the clips passed
 in are waveforms already).
+
+The other set-model experiments run here at batch scale too:
+
+* ``subsample_sweep``: max-K / random-K sub-sampling, Code/pceval.py:107-192 (FST, per-frame point
+  sets) and Code/pc_temp3d_eval.py:109-201 (3ST, per-chunk point sets);
+* ``importance_sweep``: importance-sampled sets, Code/rebut_expts.py:55-149;
+* ``reframe_sweep_temporal``: the (Fs, N) re-framing of the 3ST, Code/pc_temp3d_eval.py:56-107.
+
+Each K (or N) is one pass over the corpus: selection / packing launches write the point sets of many
+of the reference's 8-set batches - and of all the random draws of that K - into one buffer, ONE
+``STEngine.forward`` of up to a few hundred sets evaluates them, and ``pca_eval_tally`` adds the
+correct predictions to device counters.  The host reads the counters once per K (or N), where the
+reference syncs after every batch (``.item()``).  As in the reference, sets are taken in order and
+only the first ``(n // batch_size) * batch_size`` count.
 """
 import json
 import math
@@ -24,12 +38,16 @@ from typing import Dict, Iterable, List, Optional, Sequence
 import numpy as np
 import torch
 
-import pca_hip
-from dataset import ESC_pc
-from pca_hip import _lib
-from pca_hip.trainer import STEngine
+import ctypes as C
 
-__all__ = ["reframe_sweep", "framewise_dataset"]
+import pca_hip
+from dataset import ESC_pc, ESC_pc_temp
+from pca_hip import _lib
+from pca_hip.trainer import STEngine, st_config
+
+__all__ = ["reframe_sweep", "framewise_dataset", "default_list_K", "sweep_draw", "subsample_sweep",
+           "importance_sweep", "chunk_plan", "temporal_axes", "temporal_dataset",
+           "reframe_sweep_temporal"]
 
 
 def framewise_dataset(clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float, N: int,
@@ -97,4 +115,331 @@ def reframe_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], f
     if json_file is not None:
         with open(json_file, "w") as f:
             json.dump(out, f)
+    return out
+
+
+# ---- batch-scale sweeps of the sub-sampling, importance and 3-D re-framing experiments ---------------
+SETS_PER_CALL = 256            # sets per STEngine.forward when the caller does not say
+WS_BUDGET = 4 << 30            # bytes of engine workspace one call may take (pca_st_ws_bytes)
+
+
+def default_list_K(n: int) -> List[int]:
+    """``np.arange(1, n, 50)`` with the last entry replaced by n: Code/pceval.py:111-112
+    (n = Nfft // 2) and Code/pc_temp3d_eval.py:113-114, Code/rebut_expts.py:55-56
+    (n = Nfft * Ntemp // 2)."""
+    ks = np.arange(1, int(n), 50)
+    if ks.size == 0:
+        return [int(n)]
+    ks[-1] = int(n)
+    return [int(k) for k in ks]
+
+
+def sweep_draw(step: int, run: int, n_runs: int) -> int:
+    """Draw number of random run ``run`` of the ``step``-th K of a sweep (counted from 0 in loop
+    order, across the winF loop of importance_sweep).  Every run of every K has its own, so runs
+    differ; a selection is keyed by (seed, draw, batch slot, set index)."""
+    return 1 + int(step) * int(n_runs) + int(run)
+
+
+def _write_json(out: Dict, path: Optional[str]) -> None:
+    if path is not None:
+        with open(path, "w") as f:
+            json.dump(out, f)
+
+
+def _model_device(model) -> torch.device:
+    return next(getattr(model, "module", model).parameters()).device
+
+
+def _sets_per_call(model, npts: int, mode: int, want: Optional[int]) -> int:
+    """Sets per engine call: ``want``, or SETS_PER_CALL halved until the inference workspace
+    (pca_st_ws_bytes) fits WS_BUDGET."""
+    if want is not None:
+        assert want >= 1
+        return int(want)
+    cap = SETS_PER_CALL
+    L = _lib.lib()
+    while cap > 1:
+        cfg = st_config(model, cap, npts, mode)
+        if L.pca_st_ws_bytes(C.byref(cfg), 0) <= WS_BUDGET:
+            break
+        cap //= 2
+    return cap
+
+
+def _run_pieces(model, npts: int, din: int, mode: int, cap: int, pieces, select,
+                counts: torch.Tensor) -> None:
+    """Evaluate ``pieces`` = [(slot, draw, p0, p1)] (set positions p0 <= p < p1 selected with draw
+    number ``draw``, their correct predictions tallied into counts[slot]) through engine calls of at
+    most ``cap`` sets.  ``select(slot, draw, pos, out, labels_out)`` writes the point sets of the
+    positions ``pos`` (device int64) into ``out`` [n, npts, din] and their labels into labels_out.
+    Enqueues only: nothing here waits for the device."""
+    calls, cur, fill = [], [], 0
+    for slot, draw, p0, p1 in pieces:
+        while p0 < p1:
+            n = min(p1 - p0, cap - fill)
+            cur.append((slot, draw, p0, p0 + n, fill))
+            fill += n
+            p0 += n
+            if fill == cap:
+                calls.append((cur, fill))
+                cur, fill = [], 0
+    if cur:
+        calls.append((cur, fill))
+    dev = counts.device
+    engines = {}
+    for parts, b in calls:
+        if b not in engines:
+            eng = STEngine(model, b, npts, mode, training=False)
+            assert eng.cfg.k == 1, "sweeps score one prediction per set (PMA with one seed)"
+            engines[b] = (eng, torch.empty((b, npts, din), dtype=torch.float32, device=dev),
+                          torch.empty(b, dtype=torch.int64, device=dev))
+        eng, X, lab = engines[b]
+        for slot, draw, p0, p1, off in parts:
+            pos = torch.arange(p0, p1, dtype=torch.int64, device=dev)
+            select(slot, draw, pos, X[off:off + p1 - p0], lab[off:off + p1 - p0])
+        logits = eng.forward(X)
+        for slot, draw, p0, p1, off in parts:
+            pca_hip.eval_tally(logits[off:off + p1 - p0], lab[off:off + p1 - p0], counts, slot)
+
+
+def _resident_sets(spec, labels, farr, tarr, dev):
+    """spec on ``dev`` in float32 with every set contiguous: [F, T] (FST frames) or [F, Nt, S]
+    (3ST chunks) views; farr / tarr rounded to float32 once, as the datasets' .float() does."""
+    x = torch.as_tensor(spec).to(dev, torch.float32)
+    if tarr is None:
+        assert x.dim() == 2, "FST: spec is [F, T]"
+        x = x.t().contiguous().t()
+    else:
+        assert x.dim() == 3, "3ST: spec is [F, Nt, S]"
+        x = x.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+    lab = torch.as_tensor(np.asarray(labels) if not torch.is_tensor(labels) else labels)
+    lab = lab.to(dev, torch.int64).contiguous()
+    f32 = torch.as_tensor(np.asarray(farr, dtype=np.float64)).float().to(dev)
+    t32 = None if tarr is None else \
+        torch.as_tensor(np.asarray(tarr, dtype=np.float64)).float().to(dev)
+    return x, lab, f32, t32
+
+
+def _two_pass_sweep(model, n_sets: int, npts_of_K, din: int, list_K, n_runs: int, batch_size: int,
+                    mode: int, sets_per_call, select_of_K, step0: int = 0):
+    """{K: [mean, var]} of the n_runs random runs and {K: [acc, 0]} of the deterministic pass (slot
+    n_runs); one host read per K."""
+    assert n_runs >= 1 and batch_size >= 1
+    full = (n_sets // batch_size) * batch_size
+    dev = _model_device(model)
+    rand, det = {}, {}
+    for ki, K in enumerate(list_K):
+        if full == 0:
+            rand[K], det[K] = [float("nan"), float("nan")], [float("nan"), 0]
+            continue
+        npts = npts_of_K(K)
+        cap = _sets_per_call(model, npts, mode, sets_per_call)
+        counts = torch.zeros(n_runs + 1, dtype=torch.int64, device=dev)
+        pieces = [(r, sweep_draw(step0 + ki, r, n_runs), 0, full) for r in range(n_runs)]
+        pieces.append((n_runs, 0, 0, full))
+        _run_pieces(model, npts, din, mode, cap, pieces, select_of_K(K), counts)
+        c = counts.tolist()                                    # the one host sync of this K
+        accs = np.array([c[r] / full for r in range(n_runs)])
+        rand[K] = [float(np.mean(accs)), float(np.var(accs))]
+        det[K] = [c[n_runs] / full, 0]
+    return rand, det
+
+
+@torch.no_grad()
+def subsample_sweep(model, spec, labels, farr, tarr=None, list_K: Optional[Iterable[int]] = None,
+                    n_runs: int = 10, batch_size: int = 8, mode: int = _lib.MODE_F32,
+                    seed: int = 0, json_files: Optional[Sequence[str]] = None,
+                    sets_per_call: Optional[int] = None):
+    """Experiment 2 of Code/pceval.py:107-192 (FST) and Code/pc_temp3d_eval.py:109-201 (3ST):
+    accuracy of ``model`` on point sets reduced to K points, for every K in ``list_K``.
+
+    FST: ``spec`` [F, T] frames (all 1 + Nfft/2 bins), ``tarr`` None; the points of a set are
+    (farr[f], x) as utils.pc_randK / pc_maxK -> ESC_pc_ss build them.  Default list_K:
+    default_list_K(F - 1) (n = Nfft // 2).
+    3ST: ``spec`` [F, Nt, S] chunks, ``tarr`` [Nt]; points (farr[f], tarr[t], x) as
+    ESC_pc_temp_randKSS / _maxKSS build them.  Default list_K: default_list_K(F * Nt).
+    ``spec`` may be numpy or torch, host or device; ``labels`` int[T or S].
+
+    For every K: ``n_runs`` random-K runs (mode 1; run r draws with number
+    sweep_draw(index of K, r, n_runs) under ``seed``, batch slot = position of the set inside its
+    selection launch) and one max-K pass (mode 0).  Max-K is exact: the K largest values of each
+    set, as ``(-x).argsort()[:K]`` with equal values in ascending point order.  Random-K matches the
+    reference in distribution only: the reference draws from the global numpy RNG, here the
+    counter-based device stream draws.
+
+    Returns (and, with ``json_files`` = (randK path, maxK path), writes) the two dictionaries of the
+    reference: ``{"data": {K: [mean, var]}, "list_K": [...]}`` (np.var, ddof 0, over the runs) and
+    ``{"data": {K: [acc, 0]}, "list_K": [...]}``."""
+    dev = _model_device(model)
+    x, lab, f32, t32 = _resident_sets(spec, labels, farr, tarr, dev)
+    if tarr is None:
+        F, n_sets = x.shape
+        npts_all, din = F, 2
+        default_n = F - 1
+    else:
+        F, Nt, n_sets = x.shape
+        npts_all, din = F * Nt, 3
+        default_n = F * Nt
+    list_K = default_list_K(default_n) if list_K is None else [int(k) for k in list_K]
+    assert all(1 <= k <= npts_all for k in list_K), (list_K, npts_all)
+
+    def select_of_K(K):
+        def select(slot, draw, pos, out, labels_out):
+            m = pca_hip.MAXK if slot == n_runs else pca_hip.RANDK
+            pca_hip.subsample_points(x, f32, t32, pos, K, m, seed, draw, lab, out=out,
+                                     labels_out=labels_out)
+        return select
+
+    rand, det = _two_pass_sweep(model, n_sets, lambda K: K, din, list_K, n_runs, batch_size, mode,
+                                sets_per_call, select_of_K)
+    out_r = {"data": rand, "list_K": list_K}
+    out_m = {"data": det, "list_K": list_K}
+    if json_files is not None:
+        _write_json(out_r, json_files[0])
+        _write_json(out_m, json_files[1])
+    return out_r, out_m
+
+
+@torch.no_grad()
+def importance_sweep(model, spec, labels, farr, tarr, list_K: Optional[Iterable[int]] = None,
+                     list_winF: Iterable[int] = (64,), n_runs: int = 10, batch_size: int = 8,
+                     mode: int = _lib.MODE_F32, seed: int = 0,
+                     json_files: Optional[Sequence[str]] = None,
+                     sets_per_call: Optional[int] = None):
+    """The rebuttal experiment, Code/rebut_expts.py:55-149: accuracy of ``model`` on 3ST chunks
+    (``spec`` [F, Nt, S], F >= 2, Nt >= 2) reduced to K importance-sampled points
+    (ESC_pc_temp_importancerandKSS, pca_importance_points), for every smoothing width winF and K.
+
+    ``choice`` 0 (K draws with replacement from the normalised heat map) runs ``n_runs`` times,
+    run r of the i-th (winF, K) pair in loop order drawing with number sweep_draw(i, r, n_runs);
+    it matches the reference in distribution only (the reference draws from torch's global
+    generator).  ``choice`` 1 (the K hottest cells) runs once and is exact.
+
+    Returns (and, with ``json_files`` = (randK path, maxK path), writes) the dictionaries of
+    Code/rebut_expts.py:64-67, nested by winF: ``{"data": {winF: {K: [mean, var]}}, "list_K"}`` and
+    ``{"data": {winF: {K: [acc, 0]}}, "list_K"}``.  Default list_K: default_list_K(F * Nt)."""
+    dev = _model_device(model)
+    x, lab, f32, t32 = _resident_sets(spec, labels, farr, tarr, dev)
+    F, Nt, n_sets = x.shape
+    list_K = default_list_K(F * Nt) if list_K is None else [int(k) for k in list_K]
+    list_winF = [int(w) for w in list_winF]
+    assert all(k >= 1 for k in list_K)
+    rand, det = {}, {}
+    for wi, winF in enumerate(list_winF):
+        kern = pca_hip.importance_kernel(winF).to(dev)
+
+        def select_of_K(K, kern=kern):
+            def select(slot, draw, pos, out, labels_out):
+                choice = 1 if slot == n_runs else 0
+                pca_hip.importance_points(x, f32, t32, pos, K, choice, kern, seed, draw, lab,
+                                          out=out, labels_out=labels_out)
+            return select
+
+        rand[winF], det[winF] = _two_pass_sweep(model, n_sets, lambda K: K, 3, list_K, n_runs,
+                                                batch_size, mode, sets_per_call, select_of_K,
+                                                step0=wi * len(list_K))
+    out_r = {"data": rand, "list_K": list_K}
+    out_m = {"data": det, "list_K": list_K}
+    if json_files is not None:
+        _write_json(out_r, json_files[0])
+        _write_json(out_m, json_files[1])
+    return out_r, out_m
+
+
+def chunk_plan(frames: Sequence[int], Ntemp: int):
+    """Where the Ntemp-frame chunks of a corpus lie when clip c's T_c = frames[c] STFT frames start at
+    row frame_off[c] = the first multiple of Ntemp at or after the end of clip c - 1 (the layout of
+    stft_logmag_batch(..., frame_align=Ntemp)).  Clip c yields T_c // Ntemp chunks, cut from its first
+    frame with the short tail dropped, as ``np.hsplit(a, np.arange(0, T_c, Ntemp))`` minus the pieces
+    narrower than Ntemp (Code/pc_temp3d_eval.py:78-83).  Chunk j covers rows j*Ntemp .. j*Ntemp +
+    Ntemp - 1.  Returns (frame_off [n_clips + 1], chunk ids of the whole chunks in corpus order, the
+    clip of each)."""
+    foff, ids, clip_of = [0], [], []
+    for c, t in enumerate(frames):
+        j0 = foff[-1] // Ntemp
+        for i in range(int(t) // Ntemp):
+            ids.append(j0 + i)
+            clip_of.append(c)
+        foff.append(-(-(foff[-1] + int(t)) // Ntemp) * Ntemp)
+    return foff, ids, clip_of
+
+
+def temporal_axes(fs: float, N: int, Ntemp: int, hf: float = 0.5, F: Optional[int] = None):
+    """(farr, tarr) of Code/pc_temp3d_eval.py:86-87 for analysis length N: farr = linspace(0, fs/2,
+    F) / fs with F = n_fft / 2 bins (Nyquist dropped), tarr = linspace(0, (hf*N/fs)*Ntemp, Ntemp)."""
+    if F is None:
+        F = (1 << int(math.ceil(math.log2(N)))) // 2
+    farr = np.linspace(0, fs / 2, F) / fs
+    tarr = np.linspace(0, ((hf * N) / fs) * Ntemp, Ntemp)
+    return farr, tarr
+
+
+def temporal_dataset(clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float, N: int,
+                     Ntemp: int = 10, hf: float = 0.5):
+    """(ESC_pc_temp over every Ntemp-frame chunk slot of the corpus, device int64 ids of the whole
+    chunks in corpus order) for analysis length N (Code/pc_temp3d_eval.py:70-89): n_fft = 2**ceil(
+    log2 N), win_length N, hop int(N*hf), Nyquist bin dropped, magnitude divided by N.  One STFT launch
+    writes the clips frame-aligned (chunk_plan); the chunks are packed straight from it, so no
+    spectrogram goes through the host."""
+    n_fft = 1 << int(math.ceil(math.log2(N)))
+    hop = int(N * hf)
+    spec, foff = pca_hip.stft_logmag_batch(list(clips), n_fft, win_length=N, hop=hop,
+                                           drop_nyquist=True, frame_major=True, norm=N,
+                                           frame_align=Ntemp)
+    frames = [int(pca_hip.lib().pca_stft_num_frames(int(x.numel()), hop)) for x in clips]
+    plan_off, ids, clip_of = chunk_plan(frames, Ntemp)
+    assert plan_off == foff, (plan_off, foff)
+    F = n_fft // 2
+    S = foff[-1] // Ntemp
+    lab = np.full(S, -1, dtype=np.int64)
+    lab[ids] = np.asarray([int(labels[c]) for c in clip_of], dtype=np.int64)
+    dev = spec.device
+    farr, tarr = temporal_axes(fs, N, Ntemp, hf, F)
+    ds = ESC_pc_temp.from_device(spec.view(S, Ntemp, F), torch.as_tensor(lab).to(dev), farr, tarr)
+    return ds, torch.as_tensor(np.asarray(ids, dtype=np.int64)).to(dev)
+
+
+@torch.no_grad()
+def reframe_sweep_temporal(model, clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float,
+                           list_N: Iterable[int], Ntemp: int = 10, hf: float = 0.5,
+                           list_Fs: Optional[Iterable[float]] = None,
+                           json_file: Optional[str] = None, batch_size: int = 8,
+                           mode: int = _lib.MODE_F32, sets_per_call: Optional[int] = None) -> Dict:
+    """Experiment 1 of Code/pc_temp3d_eval.py:56-107: accuracy of the 3ST ``model`` for every analysis
+    length in ``list_N`` (temporal_dataset) and, with ``list_Fs``, every sampling rate the clips
+    (recorded at ``fs``) are resampled to first (pca_hip.resample: parity unpinned, as in
+    reframe_sweep).  Returns (and optionally writes) ``{"data": {Fs: [acc per N]}, "list_Fs": [...],
+    "list_N": [...]}``; one host read per N."""
+    list_N = [int(n) for n in list_N]
+    if list_Fs is not None:
+        list_Fs = list(list_Fs)
+        data = {}
+        for F in list_Fs:
+            rs = [pca_hip.resample(x, fs, F, scale=True) for x in clips]    # pc_temp3d_eval.py:74
+            data[F] = reframe_sweep_temporal(model, rs, labels, F, list_N, Ntemp, hf,
+                                             batch_size=batch_size, mode=mode,
+                                             sets_per_call=sets_per_call)["data"][F]
+        out = {"data": data, "list_Fs": list_Fs, "list_N": list_N}
+        _write_json(out, json_file)
+        return out
+    dev = _model_device(model)
+    accs: List[float] = []
+    for N in list_N:
+        ds, ids = temporal_dataset(clips, labels, fs, N, Ntemp, hf)
+        full = (ids.numel() // batch_size) * batch_size   # pc_temp3d_eval.py:93-94: no short batch
+        if full == 0:
+            accs.append(float("nan"))
+            continue
+        npts = ds.num_points
+        counts = torch.zeros(1, dtype=torch.int64, device=dev)
+
+        def select(slot, draw, pos, out, labels_out):
+            ds.batch(ids[pos], out=out, labels_out=labels_out)
+
+        _run_pieces(model, npts, 3, mode, _sets_per_call(model, npts, mode, sets_per_call),
+                    [(0, 0, 0, full)], select, counts)
+        accs.append(int(counts.item()) / full)                # the one host sync of this N
+    out = {"data": {fs: accs}, "list_Fs": [fs], "list_N": list_N}
+    _write_json(out, json_file)
     return out

@@ -62,6 +62,9 @@ SIGNATURES = {
     "pca_stft_logmag_batch": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64,
                                         C.c_int, C.c_int, C.c_int, C.c_int, c_fp, C.c_int64,
                                         C.c_int64, c_vp]),
+    "pca_stft_logmag_batch_norm": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64,
+                                             C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, c_fp,
+                                             C.c_int64, C.c_int64, C.c_double, c_vp]),
     "pca_resample": (C.c_int, [c_fp, C.c_int64, C.c_double, c_vp, c_vp, C.c_int, C.c_int, C.c_float, c_fp,
                                C.c_int64, c_vp]),
     "pca_pack_points_2d": (C.c_int, [c_fp, C.c_int64, C.c_int64, c_fp, c_i64p, C.c_int,
@@ -91,6 +94,7 @@ SIGNATURES = {
     "pca_linear_bwd_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "pca_cross_entropy": (C.c_int, [c_fp, c_i64p, C.c_int, C.c_int, C.c_float, c_fp, c_fp,
                                     c_fp, c_vp]),
+    "pca_eval_tally": (C.c_int, [c_fp, c_i64p, C.c_int, C.c_int, c_i64p, C.c_int, c_vp]),
     "pca_debug_poison_lds": (C.c_int, [c_vp]),
     "pca_subsample_points": (C.c_int, [c_fp, C.c_int64, C.c_int64, C.c_int64, c_fp, c_fp, c_vp,
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

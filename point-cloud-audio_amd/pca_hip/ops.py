@@ -314,6 +314,22 @@ def cross_entropy(logits, labels):
     return _CrossEntropyFn.apply(logits, labels)
 
 
+def eval_tally(logits: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor,
+               slot: int = 0) -> torch.Tensor:
+    """counts[slot] += #(logits.argmax(1) == labels) on the device (pca_eval_tally): no host
+    sync; argmax as torch.argmax (first maximum, NaN is the maximum).  logits [B, C] float32,
+    labels int64[B], counts int64 (contiguous).  Returns ``counts``."""
+    _need_cuda(logits, labels, counts)
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
+    assert labels.dtype == torch.int64 and labels.is_contiguous()
+    assert labels.numel() == logits.shape[0]
+    assert counts.dtype == torch.int64 and counts.is_contiguous() and 0 <= slot < counts.numel()
+    with torch.cuda.device(logits.device):
+        check(lib().pca_eval_tally(_ptr(logits), _ptr(labels), logits.shape[0], logits.shape[1],
+                                   _ptr(counts), int(slot), _stream(logits)), "pca_eval_tally")
+    return counts
+
+
 # --------------------------------------------------------------------------- #
 # feature extraction                                                           #
 # --------------------------------------------------------------------------- #
@@ -393,12 +409,22 @@ def resample(wave: torch.Tensor, fs_old: float, fs_new: float, scale: bool = Tru
 
 def stft_logmag_batch(waves, n_fft: int, win_length: Optional[int] = None,
                       hop: Optional[int] = None, drop_nyquist: bool = False,
-                      frame_major: bool = False):
+                      frame_major: bool = False, norm: Optional[float] = None,
+                      frame_align: int = 1):
     """log(1e-8 + |stft|/n_fft) of a list of 1-D float32 device waveforms in ONE launch.
     Returns (spec, frame_off): spec is [F, T_total] (or [T_total, F] with frame_major), clip c
     occupies columns (rows) frame_off[c] : frame_off[c + 1]; each clip's block is bit-identical
-    to stft_logmag(clip)."""
+    to stft_logmag(clip).
+
+    ``norm``: divide the magnitude by ``norm`` instead of n_fft (pca_stft_logmag_batch_norm; the
+    re-framing loops of Code/pc_temp3d_eval.py:75 divide by the window length N); None keeps
+    the n_fft divisor and the plain entry point.
+    ``frame_align`` > 1: every clip's first frame lands on a multiple of ``frame_align`` (and
+    T_total is one too), so that chunks of ``frame_align`` frames never straddle two clips; clip
+    c then holds the first 1 + len_c // hop frames of frame_off[c] : frame_off[c + 1] and the
+    frames after them are zeros."""
     assert len(waves) > 0
+    assert frame_align >= 1
     _need_cuda(*waves)
     dev = waves[0].device
     win_length = n_fft if win_length is None else win_length
@@ -409,23 +435,30 @@ def stft_logmag_batch(waves, n_fft: int, win_length: Optional[int] = None,
     foff = [0]
     for n, t in zip(lens, frames):
         woff.append(woff[-1] + n)
-        foff.append(foff[-1] + t)
+        foff.append(-(-(foff[-1] + t) // frame_align) * frame_align)
     T = foff[-1]
     F = n_fft // 2 if drop_nyquist else n_fft // 2 + 1
     L = lib()
+    alloc = torch.empty if frame_align == 1 else torch.zeros
     with torch.cuda.device(dev):
         cat = torch.cat([_f32c(w).reshape(-1) for w in waves])
         woff_d = torch.tensor(woff, dtype=torch.int64, device=dev)
         foff_d = torch.tensor(foff, dtype=torch.int64, device=dev)
         if frame_major:
-            out = torch.empty((T, F), dtype=torch.float32, device=dev)
+            out = alloc((T, F), dtype=torch.float32, device=dev)
             sf, st = 1, F
         else:
-            out = torch.empty((F, T), dtype=torch.float32, device=dev)
+            out = alloc((F, T), dtype=torch.float32, device=dev)
             sf, st = T, 1
-        check(L.pca_stft_logmag_batch(_ptr(cat), _ptr(woff_d), _ptr(foff_d), len(waves),
-                                      max(lens), min(lens), n_fft, win_length, hop, F, _ptr(out),
-                                      sf, st, _stream(cat)), "pca_stft_logmag_batch")
+        if norm is None:
+            check(L.pca_stft_logmag_batch(_ptr(cat), _ptr(woff_d), _ptr(foff_d), len(waves),
+                                          max(lens), min(lens), n_fft, win_length, hop, F,
+                                          _ptr(out), sf, st, _stream(cat)), "pca_stft_logmag_batch")
+        else:
+            check(L.pca_stft_logmag_batch_norm(_ptr(cat), _ptr(woff_d), _ptr(foff_d), len(waves),
+                                               max(lens), min(lens), n_fft, win_length, hop, F,
+                                               _ptr(out), sf, st, float(norm), _stream(cat)),
+                  "pca_stft_logmag_batch_norm")
     return out, foff
 
 
