@@ -241,6 +241,56 @@ int pca_pack_points_2d_ss(const float* x_tk, const float* f_tk, const int64_t* i
                           void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Fixed-input baselines (eval-mode forward; training stays stock PyTorch)    *
+ * ------------------------------------------------------------------------- */
+/* cell selection of the baseline forwards: the kept cells of PCA_SEL_MAXK / PCA_SEL_RANDK are
+ * exactly those pca_subsample_points selects in its mode 0 / 1 for the same arguments */
+enum { PCA_SEL_MAXK = 0, PCA_SEL_RANDK = 1, PCA_SEL_ALL = 2 };
+
+/* Number of fp32 parameters of baseline_ff(layer_dims, nclasses) (cnn = 0; Nt, Nf unused) or
+ * CNN_classifier(Nt, Nf, layer_dims, nclasses) (cnn = 1), i.e. the length of the flat state_dict
+ * vector the forwards take; -1 (message in pca_last_error) for a shape they refuse. */
+int64_t pca_baseline_param_count(int cnn, int Nt, int Nf, const int* layer_dims_host, int n_dims,
+                                 int nclasses);
+
+/* FB forward of a batch of frames, optionally sub-sampled
+ * replaces: Code/baseline_eval.py:86-91,152-157,178-183  model(imgs) with imgs from
+ *           Code/dataset.py:10-27 ESC_baseline (+ Code/utils.py:86-108 pc_maxK_replace /
+ *           pc_randK_replace in Experiment 2); Code/models.py:47-88 baseline_ff.forward, eval mode
+ * Frame b is spec[f * stride_f + idx[b] * stride_s], f < F (F == layer_dims[0]).  mode
+ * PCA_SEL_ALL: the whole frame; PCA_SEL_MAXK / PCA_SEL_RANDK: all but K bins zeroed (1 <= K <= F
+ * <= 16384), the K kept chosen as pca_subsample_points(..., Nt = 1, mode 0 / 1, seed, draw,
+ * draw_dev) would for the same idx (batch slot b = position in idx).  The zero-filled frame never
+ * leaves the chip.  weights: the flat fp32 state_dict (ENC_NN.Encoder_Layer_i.weight / .bias ...,
+ * ENC_NN.Code_Linear.*), n_weights = pca_baseline_param_count(0, ...); at most 15 layer_dims.
+ * probs[B, nclasses] = softmax(logits) (the nn.Softmax() at the end of the model).  sel (nullable)
+ * [B, K] int32: the kept bins in selection order; labels_out[b] = labels[idx[b]] (both nullable).
+ * fp32 FMA, no atomics: bitwise reproducible. */
+int pca_fb_forward(const float* spec, int64_t stride_f, int64_t stride_s, const int64_t* idx,
+                   int B, int F, const int* layer_dims_host, int n_dims, int nclasses,
+                   const float* weights, int64_t n_weights, int K, int mode, uint64_t seed,
+                   uint64_t draw, const int32_t* draw_dev, float* probs, int32_t* sel,
+                   const int64_t* labels, int64_t* labels_out, void* stream);
+
+/* CNN_temp forward of a batch of frame chunks, optionally sub-sampled
+ * replaces: Code/baseline_temp_eval.py:94-101,151-157,178-184  model(imgs) with imgs from
+ *           Code/dataset.py:82-135 ESC_baseline_temporal / ESC_baseline_temporal_maxK;
+ *           Code/models.py:91-119 CNN_classifier.forward, eval mode
+ * Chunk b is spec[f * stride_f + t * stride_t + idx[b] * stride_s], f < F == Nf, t < Nt
+ * (addressing as pca_pack_points_3d).  Selection as pca_fb_forward over the F*Nt cells in
+ * time-major order p = t*F + f (ESC_baseline_temporal_maxK's order; F*Nt <= 16384 with selection
+ * on).  Conv2d(1, 1, (Nt, kw)), kw = Nf + 1 - layer_dims[0] >= 1, valid, + bias -> [layer_dims[0]],
+ * then the MLP; logits[B, nclasses] (no softmax).  weights: flat fp32 state_dict (cnn.weight,
+ * cnn.bias, linear.Encoder_Layer_i.*, linear.Logits.*), n_weights = pca_baseline_param_count(1,
+ * ...). */
+int pca_cnn_temp_forward(const float* spec, int64_t stride_f, int64_t stride_t, int64_t stride_s,
+                         const int64_t* idx, int B, int F, int Nt, int Nf,
+                         const int* layer_dims_host, int n_dims, int nclasses,
+                         const float* weights, int64_t n_weights, int K, int mode, uint64_t seed,
+                         uint64_t draw, const int32_t* draw_dev, float* logits, int32_t* sel,
+                         const int64_t* labels, int64_t* labels_out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Multihead attention block                                                  *
  * replaces: set_transformer-master/modules.py:19-33 MAB.forward and the       *
  * autograd graph torch builds for it; ISAB (modules.py:51-53) and PMA          *

@@ -14,6 +14,7 @@
 //           distribution can be reproduced, not the stream.
 // HBM traffic: N values read + K rows written per set; the sort itself never leaves LDS.
 #include "pca_common.h"
+#include "select_keys.hpp"
 
 #include <stdint.h>
 
@@ -21,21 +22,6 @@
 
 namespace pca {
 namespace {
-
-// ascending order of the returned key = descending order of v; -0 == +0; NaN last
-__device__ __forceinline__ uint32_t desc_key(float v) {
-  if (v != v) return 0xffffffffu;
-  v += 0.0f;                                        // -0 -> +0
-  const uint32_t u = __float_as_uint(v);
-  const uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~asc;
-}
-// splitmix64 finaliser
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
 
 __global__ __launch_bounds__(1024) void k_subsample(
     const float* __restrict__ spec, int64_t stride_f, int64_t stride_t, int64_t stride_s,
@@ -53,8 +39,7 @@ __global__ __launch_bounds__(1024) void k_subsample(
   const float* __restrict__ base = spec + set * stride_s;
   // one stream per (seed, draw, batch slot, set): a set that appears twice in a batch gets two
   // independent selections, as two __getitem__ calls of the reference would
-  const uint64_t stream = mix64(seed ^ mix64(draw * 0x9e3779b97f4a7c15ull + (uint64_t)set) ^
-                                mix64(0x632be59bd9b4e019ull * (uint64_t)(b + 1)));
+  const uint64_t stream = select_stream(seed, draw, set, b);
   for (int p = tid; p < Np; p += 1024) {
     uint64_t k = ~0ull;
     if (p < N) {
@@ -63,7 +48,7 @@ __global__ __launch_bounds__(1024) void k_subsample(
         const int t = p / F, f = p - t * F;
         hi = desc_key(base[f * stride_f + t * stride_t]);
       } else {
-        hi = (uint32_t)(mix64(stream + (uint64_t)p * 0xd1342543de82ef95ull) >> 32);
+        hi = rand_key(stream, p);
       }
       k = ((uint64_t)hi << 32) | (uint32_t)p;
     }
@@ -160,8 +145,7 @@ __global__ __launch_bounds__(1024) void k_importance(
   __syncthreads();
   if (heat_out != nullptr)
     for (int i = tid; i < N; i += 1024) heat_out[(int64_t)b * N + i] = sx[i];
-  const uint64_t stream = mix64(seed ^ mix64(draw * 0x9e3779b97f4a7c15ull + (uint64_t)set) ^
-                                mix64(0x632be59bd9b4e019ull * (uint64_t)(b + 1)));
+  const uint64_t stream = select_stream(seed, draw, set, b);
   if (choice == 1) {
     // keys alias xt/G0: collect this thread's heat values first
     uint32_t hk[16];

@@ -23,6 +23,9 @@ The other set-model experiments run here at batch scale too:
   sets) and Code/pc_temp3d_eval.py:109-201 (3ST, per-chunk point sets);
 * ``importance_sweep``: importance-sampled sets, Code/rebut_expts.py:55-149;
 * ``reframe_sweep_temporal``: the (Fs, N) re-framing of the 3ST, Code/pc_temp3d_eval.py:56-107.
+* ``baseline_subsample_sweep``, ``baseline_reframe_sweep``, ``baseline_reframe_sweep_temporal``: the
+  same experiments for the fixed-input baselines FB and CNN_temp (Code/baseline_eval.py,
+  Code/baseline_temp_eval.py) on pca_hip.BaselineEngine, the selection fused into the forward launch.
 
 Each K (or N) is one pass over the corpus: selection / packing launches write the point sets of many
 of the reference's 8-set batches - and of all the random draws of that K - into one buffer, ONE
@@ -43,11 +46,13 @@ import ctypes as C
 import pca_hip
 from dataset import ESC_pc, ESC_pc_temp
 from pca_hip import _lib
+from pca_hip.baseline import SEL_ALL, BaselineEngine
 from pca_hip.trainer import STEngine, st_config
 
 __all__ = ["reframe_sweep", "framewise_dataset", "default_list_K", "sweep_draw", "subsample_sweep",
            "importance_sweep", "chunk_plan", "temporal_axes", "temporal_dataset",
-           "reframe_sweep_temporal"]
+           "reframe_sweep_temporal", "baseline_subsample_sweep", "baseline_frames",
+           "baseline_chunks", "baseline_reframe_sweep", "baseline_reframe_sweep_temporal"]
 
 
 def framewise_dataset(clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float, N: int,
@@ -226,19 +231,29 @@ def _two_pass_sweep(model, n_sets: int, npts_of_K, din: int, list_K, n_runs: int
     """{K: [mean, var]} of the n_runs random runs and {K: [acc, 0]} of the deterministic pass (slot
     n_runs); one host read per K."""
     assert n_runs >= 1 and batch_size >= 1
-    full = (n_sets // batch_size) * batch_size
-    dev = _model_device(model)
+
+    def run_K(K, pieces, counts):
+        npts = npts_of_K(K)
+        cap = _sets_per_call(model, npts, mode, sets_per_call)
+        _run_pieces(model, npts, din, mode, cap, pieces, select_of_K(K), counts)
+
+    return _k_passes((n_sets // batch_size) * batch_size, list_K, n_runs, _model_device(model),
+                     run_K, step0)
+
+
+def _k_passes(full: int, list_K, n_runs: int, dev, run_K, step0: int = 0):
+    """The K loop of the two-pass sweeps: for every K, ``run_K(K, pieces, counts)`` evaluates the
+    pieces [(slot, draw, 0, full)] - n_runs random runs, then the deterministic pass in slot n_runs
+    - tallying into counts[slot]; one host read per K."""
     rand, det = {}, {}
     for ki, K in enumerate(list_K):
         if full == 0:
             rand[K], det[K] = [float("nan"), float("nan")], [float("nan"), 0]
             continue
-        npts = npts_of_K(K)
-        cap = _sets_per_call(model, npts, mode, sets_per_call)
         counts = torch.zeros(n_runs + 1, dtype=torch.int64, device=dev)
         pieces = [(r, sweep_draw(step0 + ki, r, n_runs), 0, full) for r in range(n_runs)]
         pieces.append((n_runs, 0, 0, full))
-        _run_pieces(model, npts, din, mode, cap, pieces, select_of_K(K), counts)
+        run_K(K, pieces, counts)
         c = counts.tolist()                                    # the one host sync of this K
         accs = np.array([c[r] / full for r in range(n_runs)])
         rand[K] = [float(np.mean(accs)), float(np.var(accs))]
@@ -443,3 +458,200 @@ def reframe_sweep_temporal(model, clips: Sequence[torch.Tensor], labels: Sequenc
     out = {"data": {fs: accs}, "list_Fs": [fs], "list_N": list_N}
     _write_json(out, json_file)
     return out
+
+
+# ---- the fixed-input baselines (FB, CNN_temp): Code/baseline_eval.py, Code/baseline_temp_eval.py ------
+# The same passes as above on BaselineEngine (pca_fb_forward / pca_cnn_temp_forward): the selection
+# happens inside the forward launch, which reads the sets in place, so one launch per run and K
+# covers up to BASELINE_SETS_PER_CALL sets.  The counting follows the reference scripts: FB counts
+# every frame (batch 128, no batch skipped, Code/baseline_eval.py:84-90,148-157); CNN_temp runs
+# batches of 2 and skips a trailing one-set batch (Code/baseline_temp_eval.py:43,95-96,152-153).
+BASELINE_SETS_PER_CALL = 16384
+FB_BATCH, CNN_TEMP_BATCH = 128, 2
+
+
+def _baseline_engine(model) -> BaselineEngine:
+    return model if isinstance(model, BaselineEngine) else BaselineEngine(model)
+
+
+def _baseline_full(eng: BaselineEngine, n_sets: int) -> int:
+    """Sets that count: all (FB), all but a trailing one-set batch (CNN_temp)."""
+    return (n_sets // CNN_TEMP_BATCH) * CNN_TEMP_BATCH if eng.cnn else n_sets
+
+
+def _baseline_run(eng: BaselineEngine, x, lab, ids, pieces, counts, K=None, sel_of_slot=None,
+                  seed: int = 0, cap: Optional[int] = None) -> None:
+    """Forward + tally of ``pieces`` = [(slot, draw, p0, p1)]: the sets ids[p0:p1] (ids None: the
+    positions themselves), cell selection ``sel_of_slot(slot)`` (default: none), in launches of at
+    most ``cap`` sets.  Enqueues only."""
+    cap = BASELINE_SETS_PER_CALL if cap is None else int(cap)
+    dev = counts.device
+    n_max = min(cap, max(p1 - p0 for _, _, p0, p1 in pieces))
+    out = torch.empty((n_max, eng.nclasses), dtype=torch.float32, device=dev)
+    lab_out = torch.empty(n_max, dtype=torch.int64, device=dev)
+    for slot, draw, p0, p1 in pieces:
+        for a in range(p0, p1, cap):
+            b = min(a + cap, p1)
+            idx = torch.arange(a, b, dtype=torch.int64, device=dev) if ids is None else ids[a:b]
+            mode = SEL_ALL if sel_of_slot is None else sel_of_slot(slot)
+            o, lo = out[:b - a], lab_out[:b - a]
+            eng.forward(x, idx, K, mode, seed, draw, labels=lab, out=o, labels_out=lo)
+            pca_hip.eval_tally(o, lo, counts, slot)
+
+
+@torch.no_grad()
+def baseline_subsample_sweep(model, spec, labels, list_K: Optional[Iterable[int]] = None,
+                             n_runs: int = 10, seed: int = 0,
+                             json_files: Optional[Sequence[str]] = None,
+                             sets_per_call: Optional[int] = None):
+    """Experiment 2 of Code/baseline_eval.py:111-200 (FB) and Code/baseline_temp_eval.py:110-200
+    (CNN_temp): accuracy of the baseline ``model`` (baseline_ff / CNN_classifier or a BaselineEngine)
+    on inputs with all but K cells zeroed, for every K in ``list_K``.
+
+    FB: ``spec`` [F, T] frames (F = layer_dims[0]); the frame's other bins are zeroed as by
+    pc_randK_replace / pc_maxK_replace.  Default list_K: default_list_K(F - 1) (Nfft // 2).
+    CNN_temp: ``spec`` [F, Nt, S] chunks; the chunk's other cells are zeroed as by
+    ESC_baseline_temporal_maxK(flag "rand" / "max") over the cells p = t*F + f.  Default list_K:
+    default_list_K(F * Nt).  ``spec`` may be numpy or torch, host or device; ``labels`` int[T or S].
+
+    For every K: ``n_runs`` random-K runs (run r draws with number sweep_draw(index of K, r, n_runs)
+    under ``seed``, batch slot = position of the set inside its launch) and one max-K pass.  Max-K
+    keeps the cells pca_subsample_points keeps (equal values in ascending cell order, NaN last) and
+    is exact; random-K matches the reference in distribution only.  Returns (and, with
+    ``json_files`` = (randK path, maxK path), writes) ``{"data": {K: [mean, var]}, "list_K"}`` and
+    ``{"data": {K: [acc, 0]}, "list_K"}``, the layout of paper_plots/{FB,CNNTemp}_{randK,maxK}_expt2.json."""
+    eng = _baseline_engine(model)
+    x = torch.as_tensor(spec).to(eng.dev, torch.float32)
+    if eng.cnn:
+        assert x.dim() == 3, "CNN_temp: spec is [F, Nt, S]"
+        x = x.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+    else:
+        assert x.dim() == 2, "FB: spec is [F, T]"
+        x = x.t().contiguous().t()
+    lab = torch.as_tensor(np.asarray(labels) if not torch.is_tensor(labels) else labels)
+    lab = lab.to(eng.dev, torch.int64).contiguous()
+    n_cells = x.shape[0] * (x.shape[1] if eng.cnn else 1)
+    n_sets = x.shape[-1]
+    list_K = default_list_K(n_cells if eng.cnn else n_cells - 1) if list_K is None \
+        else [int(k) for k in list_K]
+    assert all(1 <= k <= n_cells for k in list_K), (list_K, n_cells)
+
+    def run_K(K, pieces, counts):
+        _baseline_run(eng, x, lab, None, pieces, counts, K,
+                      lambda slot: pca_hip.MAXK if slot == n_runs else pca_hip.RANDK, seed,
+                      sets_per_call)
+
+    rand, det = _k_passes(_baseline_full(eng, n_sets), list_K, n_runs, eng.dev, run_K)
+    out_r = {"data": rand, "list_K": list_K}
+    out_m = {"data": det, "list_K": list_K}
+    if json_files is not None:
+        _write_json(out_r, json_files[0])
+        _write_json(out_m, json_files[1])
+    return out_r, out_m
+
+
+def baseline_frames(clips: Sequence[torch.Tensor], labels: Sequence[int], N: int, n_fft: int,
+                    hf: float = 0.5):
+    """(spec [F, T] device view, labels int64 [T]) of every frame of ``clips`` for FB's Experiment 1
+    (Code/baseline_eval.py:71-81): librosa.stft(x, n_fft, win_length=N, hop=int(N*hf), 'hann') /
+    n_fft, log(1e-8 + |.|), all 1 + n_fft/2 bins.  n_fft stays the model's window whatever N is:
+    the input width is fixed."""
+    assert 1 <= N <= n_fft
+    spec, foff = pca_hip.stft_logmag_batch(list(clips), n_fft, win_length=N, hop=int(N * hf),
+                                           frame_major=True)              # [T, F]
+    dev = spec.device
+    lab = torch.cat([torch.full((foff[c + 1] - foff[c],), int(y), dtype=torch.int64, device=dev)
+                     for c, y in enumerate(labels)])
+    return spec.t(), lab
+
+
+def baseline_chunks(clips: Sequence[torch.Tensor], labels: Sequence[int], N: int, n_fft: int,
+                    Ntemp: int = 10, hf: float = 0.5):
+    """(spec [F, Ntemp, S] device view over every Ntemp-frame chunk slot, labels int64 [S], ids of
+    the whole chunks in corpus order) for CNN_temp's Experiment 1 (Code/baseline_temp_eval.py:
+    78-91): librosa.stft(x, n_fft, win_length=N, hop=int(N*hf)) / n_fft, Nyquist bin dropped,
+    log(1e-8 + |.|), chunks of Ntemp frames cut from each clip's first frame, short tail dropped
+    (chunk_plan).  n_fft stays the model's window whatever N is."""
+    assert 1 <= N <= n_fft
+    hop = int(N * hf)
+    spec, foff = pca_hip.stft_logmag_batch(list(clips), n_fft, win_length=N, hop=hop,
+                                           drop_nyquist=True, frame_major=True,
+                                           frame_align=Ntemp)
+    frames = [int(pca_hip.lib().pca_stft_num_frames(int(x.numel()), hop)) for x in clips]
+    plan_off, ids, clip_of = chunk_plan(frames, Ntemp)
+    assert plan_off == foff, (plan_off, foff)
+    F = n_fft // 2
+    S = foff[-1] // Ntemp
+    lab = np.full(S, -1, dtype=np.int64)
+    lab[ids] = np.asarray([int(labels[c]) for c in clip_of], dtype=np.int64)
+    dev = spec.device
+    return (spec.view(S, Ntemp, F).permute(2, 1, 0), torch.as_tensor(lab).to(dev),
+            torch.as_tensor(np.asarray(ids, dtype=np.int64)).to(dev))
+
+
+@torch.no_grad()
+def _baseline_reframe(model, clips, labels, fs, list_N, hf, list_Fs, json_file, n_fft, Ntemp,
+                      sets_per_call):
+    eng = _baseline_engine(model)
+    list_N = [int(n) for n in list_N]
+    if n_fft is None:
+        n_fft = 2 * eng.Nf if eng.cnn else 2 * (eng.layer_dims[0] - 1)
+    if list_Fs is not None:
+        list_Fs = list(list_Fs)
+        data = {}
+        for F in list_Fs:
+            rs = [pca_hip.resample(x, fs, F, scale=True) for x in clips]
+            data[F] = _baseline_reframe(eng, rs, labels, F, list_N, hf, None, None, n_fft, Ntemp,
+                                        sets_per_call)["data"][F]
+        out = {"data": data, "list_Fs": list_Fs, "list_N": list_N}
+        _write_json(out, json_file)
+        return out
+    accs: List[float] = []
+    for N in list_N:
+        if eng.cnn:
+            x, lab, ids = baseline_chunks(clips, labels, N, n_fft, Ntemp, hf)
+            n_sets = ids.numel()
+        else:
+            x, lab = baseline_frames(clips, labels, N, n_fft, hf)
+            ids, n_sets = None, x.shape[1]
+        full = _baseline_full(eng, n_sets)
+        if full == 0:
+            accs.append(float("nan"))
+            continue
+        counts = torch.zeros(1, dtype=torch.int64, device=eng.dev)
+        _baseline_run(eng, x, lab, ids, [(0, 0, 0, full)], counts, cap=sets_per_call)
+        accs.append(int(counts.item()) / full)                # the one host sync of this N
+    out = {"data": {fs: accs}, "list_Fs": [fs], "list_N": list_N}
+    _write_json(out, json_file)
+    return out
+
+
+def baseline_reframe_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float,
+                           list_N: Iterable[int], hf: float = 0.5,
+                           list_Fs: Optional[Iterable[float]] = None,
+                           json_file: Optional[str] = None, n_fft: Optional[int] = None,
+                           sets_per_call: Optional[int] = None) -> Dict:
+    """Experiment 1 of Code/baseline_eval.py:50-103 (FB): accuracy for every analysis length N in
+    ``list_N`` (baseline_frames: n_fft = the model's window 2 * (layer_dims[0] - 1) unless given,
+    divisor n_fft, every frame counts) and, with ``list_Fs``, every sampling rate the clips
+    (recorded at ``fs``) are resampled to first (pca_hip.resample: parity unpinned).  Returns (and
+    optionally writes) ``{"data": {Fs: [acc per N]}, "list_Fs", "list_N"}`` (FB_expt1.json)."""
+    eng = _baseline_engine(model)
+    assert not eng.cnn, "baseline_reframe_sweep takes an FB model (CNN_temp: _temporal)"
+    return _baseline_reframe(eng, clips, labels, fs, list_N, hf, list_Fs, json_file, n_fft, None,
+                             sets_per_call)
+
+
+def baseline_reframe_sweep_temporal(model, clips: Sequence[torch.Tensor], labels: Sequence[int],
+                                    fs: float, list_N: Iterable[int], hf: float = 0.5,
+                                    list_Fs: Optional[Iterable[float]] = None,
+                                    json_file: Optional[str] = None, n_fft: Optional[int] = None,
+                                    sets_per_call: Optional[int] = None) -> Dict:
+    """Experiment 1 of Code/baseline_temp_eval.py:51-107 (CNN_temp): as baseline_reframe_sweep on
+    the model's Nt-frame chunks (baseline_chunks: n_fft = 2 * Nf unless given, Nyquist dropped,
+    divisor n_fft, short tail dropped, a trailing one-set batch of 2 skipped).  Writes the layout of
+    CNNTemp_expt1.json."""
+    eng = _baseline_engine(model)
+    assert eng.cnn, "baseline_reframe_sweep_temporal takes a CNN_temp model"
+    return _baseline_reframe(eng, clips, labels, fs, list_N, hf, list_Fs, json_file, n_fft, eng.Nt,
+                             sets_per_call)

@@ -5,3 +5,4 @@ from .ops import (MAXK, RANDK, cross_entropy, eval_tally, get_mode, importance_k
                   importance_points, linear, mab, mab_infer, pack_points_2d, pack_points_2d_seq, pack_points_2d_ss, pack_points_3d,
                   pack_points_3d_seq, resample, set_mode, stft_logmag, stft_logmag_batch,
                   subsample_points)
+from .baseline import SEL_ALL, BaselineEngine, baseline_config  # noqa: F401

@@ -106,6 +106,14 @@ SIGNATURES = {
                                         c_vp, c_vp, c_vp]),
     "pca_pack_points_2d_ss": (C.c_int, [c_fp, c_fp, c_vp, C.c_int, C.c_int, c_fp, c_vp, c_vp,
                                         c_vp]),
+    "pca_baseline_param_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, c_vp, C.c_int, C.c_int]),
+    "pca_fb_forward": (C.c_int, [c_fp, C.c_int64, C.c_int64, c_i64p, C.c_int, C.c_int, c_vp,
+                                 C.c_int, C.c_int, c_fp, C.c_int64, C.c_int, C.c_int, C.c_uint64,
+                                 C.c_uint64, c_vp, c_fp, c_vp, c_vp, c_vp, c_vp]),
+    "pca_cnn_temp_forward": (C.c_int, [c_fp, C.c_int64, C.c_int64, C.c_int64, c_i64p, C.c_int,
+                                       C.c_int, C.c_int, C.c_int, c_vp, C.c_int, C.c_int, c_fp,
+                                       C.c_int64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, c_vp,
+                                       c_fp, c_vp, c_vp, c_vp, c_vp]),
     "pca_adam_step": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int64, C.c_float, C.c_float,
                                 C.c_float, C.c_float, C.c_float, C.c_float, c_vp, C.c_int, c_vp]),
     "pca_st_param_count": (C.c_int64, [C.POINTER(StConfig)]),
