@@ -1018,6 +1018,19 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
         PCA_TRY(slab_sum_jobs(one, st));
       }
     }
+  } else if (flags & PCA_F_ATTN_DONE) {
+    // the set-resident forward ran the attention backward and left the slabs k_mab0_bwd would have
+    // written: only their fixed-order sum is left
+    PCA_REQUIRE(head_done && R * dk == 512, "mab0_bf16_bwd: set-resident PMA backward with R=%d dk=%d", R, dk);
+    const SlabSumJob sj{w.slabs, w.DG, s.B * mab0_bwd_splits(s), R * dk, 0};
+    if (defer != nullptr) {
+      PCA_REQUIRE(defer->sums.n < 40, "mab0_bf16_bwd: slab-sum table full");
+      defer->sums.j[defer->sums.n++] = sj;
+    } else {
+      SlabSumJobs one{};
+      one.j[one.n++] = sj;
+      PCA_TRY(slab_sum_jobs(one, st));
+    }
   } else {
     const int S = mab0_bwd_splits(s);
     Mab0BwdArgs a{X, v.Gb, v.GtP, w.dTb, w.dTt, w.LSEp, w.Delta, dX, w.DG, s.B, s.nk,

@@ -195,7 +195,9 @@ enum {
   PCA_F_SKIP_HEAD = 8,       // mab0 bwd: dT/Delta images, dZ, dO, dQs already produced
   PCA_F_IMAGES_READY = 16,   // weight images were prepared by the caller (IsabImg)
   PCA_F_PREP_DONE = 32,      // mab0 fwd: Qp / G images were prepared by the caller
-  PCA_F_SKIP_WGRAD = 64      // mab0 bwd: dWo / dWv reductions are done by the caller; DG is clear
+  PCA_F_SKIP_WGRAD = 64,     // mab0 bwd: dWo / dWv reductions are done by the caller; DG is clear
+  PCA_F_ATTN_DONE = 128      // mab0 bwd (PMA, d = 128): the caller's launch ran k_mab0_bwd's part and left
+                             // dX and its dG slabs [B][S][R][128] in the workspace (set128_fwd.hip)
 };
 
 // ---- per-set mid kernels of a fused ISAB (mid_bf16.hip); m = 16, d = 128, h = 4 ----------

@@ -30,7 +30,8 @@ struct Set128Layer {
   const float* bq1;
   const __bf16* WoP;      // K-permuted
   const float* bo1;
-  __bf16 *QpS, *OS, *Y;   // saved Qp (layer 2 only), saved O, the layer's output [B][N][128]
+  __bf16 *QpS, *OS, *Y;   // saved Qp (layer 2 only), saved O, the layer's output [B][N][128] (null:
+                          // not stored - layer 2 when the PMA backward runs in the tail)
   uint32_t* mask;         // ReLU mask words, mab1_mask_index<128> layout
 };
 
@@ -51,6 +52,14 @@ struct Set128FwdArgs {
   int fuse_head;
   float* exP;
   PmaHeadArgs head;
+  // pma_bwd != 0 (needs fuse_head): the PMA's attention backward runs in the tail as well (k_mab0_bwd's
+  // arithmetic on the resident Y2 rows).  Hand-off 3 is then symmetric - both halves publish their
+  // partial and run the head stages on the same merge, half 0 alone writes the head's outputs - and
+  // each half writes dY2 of its rows and its S / 2 dG slabs - the same values k_mab0_bwd wrote
+  int pma_bwd;
+  __bf16* dY2;            // [B][N][128] bf16 (written, not accumulated)
+  float* pma_slabs;       // [B][S][4][128], slab b S + sp over the points [sp N / S, (sp + 1) N / S)
+  int pma_S;              // k_mab0_bwd's point splits per set (mab0_bwd_splits): 2, or 4 at N = 512
 };
 
 // bytes of `flags` (the block the preparation launch clears) / of the whole exchange area

@@ -23,8 +23,8 @@
 // this kernel keeps (same MFMA operand orders, same K-permuted images), so that the existing backward
 // kernels read what it saves.
 //
-// LDS: sY [N/2][256 B] (rows XOR-swizzled as tr_off, so that both the row-major B-operand reads and the
-// transposing ds_read_tr16_b64 reads are conflict-free), sO [N/2][256 B] (the O tile of a many-queries
+// LDS: sY [N/2][256 B] (rows XOR-swizzled by y_off, so that the row-major operand reads, the transposing
+// ds_read_tr16_b64 reads and the whole-row reads are conflict-free), sO [N/2][256 B] (the O tile of a many-queries
 // block: fc_o contracts over all heads' features; between blocks: merge buffers), 32 KiB of images.
 //
 // Roofline unit: MACs_fwd / set = N (3 din d + 7 d^2 + 8 m d + 2 k d) + 6 m d^2 (the
@@ -41,10 +41,17 @@ namespace {
 
 constexpr int D = 128, MQ = 16, ROWB = 256, NT = 1024;
 
-// byte offset of 16-byte chunk ch of row `row` of a [rows][256 B] image (the layout of the X tiles of
-// k_mab0_attn_h4: the XOR term depends on row & 15 only, so any 16-aligned row block is an image)
+// byte offset of 16-byte chunk ch of row `row` of a [rows][256 B] image.  The XOR term depends on row & 15
+// only (any 16-aligned row block is an image); as a map of the row's four bits it is linear with the
+// columns 2, 4, 8, 9, the one that keeps all three read shapes of the kernel conflict-free under the
+// lane groups of MI355X_MICROARCH.md §LDS: ds_read_b128 of the operand rows (lane = (chunk 4 s + g, row r),
+// 16-lane groups {0-3, 12-15, 20-27} ..), ds_read_b64_tr_b16 (two 32-lane groups: rows 4 g + q, chunks
+// 2 t and 2 t + 1) and the ds_read_b128 of whole rows for the coalesced stores (4 rows per instruction).
+// (k_mab0_attn_h4's term ((row & 3) << 2) | ((row >> 2) & 3), used here before, is 2-way on all three.)
+// The ds_write_b64 of accumulator tiles (16 lanes = 16 rows, one 8-byte half of the same chunk) stay
+// 2-way under any 16-byte swizzle.
 __device__ __forceinline__ int y_off(int row, int ch) {
-  return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
+  return 256 * row + 16 * (ch ^ ((((row << 1) & 14) | ((row >> 3) & 1)) ^ (row & 8)));
 }
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 // B operand [k = point (k-slot order of pack8 of two score tiles)][col = feature 16 t + (lane & 15)] of
@@ -458,13 +465,16 @@ __device__ __forceinline__ void mab1_phase(const Set128Layer& L, const Ctx& c, c
   STAMP(stamp0 + 2);
   lds_barrier();                        // Y rows complete (and every head has read the O rows)
   STAMP(stamp0 + 3);
-  // saved O and the block's output: coalesced 16-byte pieces of full rows
+  // saved O and the block's output: coalesced 16-byte pieces of full rows (no output when nothing
+  // after this launch reads it)
+  const bool store_y = L.Y != nullptr;
   for (int p = c.tid; p < c.NH * 16; p += NT) {
     const int row = p >> 4, ch = p & 15;
     *reinterpret_cast<uint4*>(L.OS + (c.row0 + row) * D + ch * 8) =
         *reinterpret_cast<const uint4*>(sO + y_off(row, ch));
-    *reinterpret_cast<uint4*>(L.Y + (c.row0 + row) * D + ch * 8) =
-        *reinterpret_cast<const uint4*>(sY + y_off(row, ch));
+    if (store_y)
+      *reinterpret_cast<uint4*>(L.Y + (c.row0 + row) * D + ch * 8) =
+          *reinterpret_cast<const uint4*>(sY + y_off(row, ch));
   }
   STAMP(stamp0 + 4);
 }
@@ -477,9 +487,20 @@ __device__ __forceinline__ void mab1_phase(const Set128Layer& L, const Ctx& c, c
 // Delta = rowdot(dT, T).  Products over the INPUT index take 8 (16) adjacent lanes per output and a
 // shuffle reduction; products over the OUTPUT index take thread = (column, eighth of the rows), coalesced
 // weight rows, and an LDS reduction.  sPm: this workgroup's PMA partial, theirs: the partner's (sc1).
+// The two partials are merged in the order of the halves, so that both workgroups of a pair compute
+// bit-identical results when both run these stages (pma_bwd); wr: this one writes the global outputs.
+// bw != nullptr: the operands of the tail's attention backward also go to LDS (PmaBwdLds).
 // ---------------------------------------------------------------------------------------------
+// LDS of the PMA attention backward in the tail (in sO, dead by then): G and dT as [16][256 B] images
+// (y_off rows; rows >= 4 zero), their transposes [128][4] bf16, LSE / Delta, the P^T and dS^T tiles of the
+// 32-point tiles ([32 points][16 rows] bf16 each), the dG partials of the summation chains
+struct PmaBwdLds {
+  static constexpr int G = 0, DT = 4096, GT = 8192, DTT = 9216, LD = 10240, PT = 12288, DS = 20480,
+                       RED = 32768;
+};
+
 __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, const float* sPm,
-                                            const float* theirs, float* sh) {
+                                            const float* theirs, float* sh, bool wr, char* bw) {
   constexpr int DH = 32, R = 4;
   float* sT = sh;                 // [4][128] merged, normalised T
   float* sOv = sT + 512;          // O, P, Z, dP, dZ, dO: [128] each
@@ -515,25 +536,27 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     wc4[u] = *reinterpret_cast<const float4*>(a.Wc + (int64_t)(c3 < C ? c3 : 0) * D + 8 * p3 + 4 * u);
   const float qb = a.Qp[fA] + a.bv[fA], bo_f = a.bo[fA], bc3 = a.bc[c3 < C ? c3 : 0];
   const int64_t y = a.labels[b];
-  if (a.zero_ptr != nullptr)
+  if (wr && a.zero_ptr != nullptr)
     for (int i = b * NT + tid; i < a.zero_n; i += B * NT) a.zero_ptr[i] = 0.f;
 
-  // ---- merge the two halves' partials (ordered by half: this is half 0) ----
+  // ---- merge the two halves' partials (ordered by half) ----
   float* sEx = part;                                  // the partner's 520 values
   if (tid < 520) sEx[tid] = pth;
   lds_barrier();
   if (tid < 512) {
+    const float* P0 = c.half ? sEx : sPm;
+    const float* P1 = c.half ? sPm : sEx;
     const int rr = tid >> 7;
-    const float m0 = sPm[512 + rr], m1 = sEx[512 + rr];
+    const float m0 = P0[512 + rr], m1 = P1[512 + rr];
     const float M = fmaxf(m0, m1);
     const float f0 = __builtin_amdgcn_exp2f(m0 - M), f1 = __builtin_amdgcn_exp2f(m1 - M);
-    const float Lt = f0 * sPm[516 + rr] + f1 * sEx[516 + rr];
-    const float v = (f0 * sPm[tid] + f1 * sEx[tid]) / Lt;
+    const float Lt = f0 * P0[516 + rr] + f1 * P1[516 + rr];
+    const float v = (f0 * P0[tid] + f1 * P1[tid]) / Lt;
     sT[tid] = v;
-    a.T[(int64_t)b * R * D + tid] = v;
+    if (wr) a.T[(int64_t)b * R * D + tid] = v;
     if ((tid & 127) == 0) {
       const float lse = M + log2f(Lt);
-      a.LSE[(int64_t)b * R + rr] = lse;
+      if (wr) a.LSE[(int64_t)b * R + rr] = lse;
       sLSE[rr] = lse;
     }
   }
@@ -562,9 +585,11 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     if (pA == 0) {
       const float o1 = sOv[fA], hv = o1 + fmaxf(z1, 0.f);
       const int64_t o = (int64_t)b * D + fA;
-      a.H[o] = hv;
-      a.Osave[o] = o1;
-      a.Zsave[o] = z1;
+      if (wr) {
+        a.H[o] = hv;
+        a.Osave[o] = o1;
+        a.Zsave[o] = z1;
+      }
       sP[fA] = hv;
       sZ[fA] = z1;
     }
@@ -595,7 +620,7 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     if (c3 < C && p3 == 0) {
       acc += bc3;
       sL[c3] = acc;
-      a.logits[(int64_t)b * C + c3] = acc;
+      if (wr) a.logits[(int64_t)b * C + c3] = acc;
     }
   }
   lds_barrier();
@@ -622,14 +647,14 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     const float gs = a.grad_scale / (float)B;
     float g = 0.f;
     if (tid < C) g = (expf(sL[tid] - m) / sm - (tid == y ? 1.f : 0.f)) * gs;
-    if (tid == 0) {
+    if (wr && tid == 0) {
       a.lossv[b] = m + logf(sm) - sL[y];
       a.corrv[b] = *ramax == (int)y ? 1.f : 0.f;
     }
     lds_barrier();
     if (tid < C) {
       sL[tid] = g;
-      a.dlogits[(int64_t)b * C + tid] = g;
+      if (wr) a.dlogits[(int64_t)b * C + tid] = g;
     }
     lds_barrier();
   }
@@ -648,11 +673,11 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     float dp = 0.f;
 #pragma unroll
     for (int p = 0; p < 8; ++p) dp += part[p * D + tid];
-    a.dP[(int64_t)b * D + tid] = dp;
+    if (wr) a.dP[(int64_t)b * D + tid] = dp;
     sdP[tid] = dp;
     const float v = sZ[tid] > 0.f ? dp : 0.f;          // dZ = dP . [Z > 0]
     sdZ[tid] = v;
-    a.dZ[(int64_t)b * D + tid] = v;
+    if (wr) a.dZ[(int64_t)b * D + tid] = v;
   }
   lds_barrier();
   // dO = dP + dZ Wo
@@ -672,10 +697,10 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
 #pragma unroll
     for (int p = 0; p < 8; ++p) v += part[p * D + tid];
     sdO[tid] = v;
-    a.dO[(int64_t)b * D + tid] = v;
+    if (wr) a.dO[(int64_t)b * D + tid] = v;
   }
   lds_barrier();
-  // dT_h = dO_h Wv_h ; Delta = rowdot(dT, T) ; the images k_mab0_bwd reads
+  // dT_h = dO_h Wv_h ; Delta = rowdot(dT, T) ; the images k_mab0_bwd reads (bw: the tail's, in LDS)
   {
     const int j = (tid >> 7) & 3, hlf = tid >> 9;
     float acc = 0.f;
@@ -688,19 +713,33 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     const int j = tid >> 7, f = tid & 127;
     const float acc = part[j * D + f] + part[(4 + j) * D + f];
     const float tv = sT[j * D + f];
-    a.Th[((int64_t)j * B + b) * D + f] = tv;
-    a.dTb[((int64_t)b * a.Rp + j) * D + f] = (__bf16)acc;
-    int pos = 0;
+    if (wr) a.Th[((int64_t)j * B + b) * D + f] = tv;
+    if (bw != nullptr) {
+      const __bf16 v = (__bf16)acc;
+      *reinterpret_cast<__bf16*>(bw + PmaBwdLds::DT + y_off(j, f >> 3) + 2 * (f & 7)) = v;
+      *reinterpret_cast<__bf16*>(bw + PmaBwdLds::DTT + 8 * f + 2 * j) = v;
+    } else {
+      a.dTb[((int64_t)b * a.Rp + j) * D + f] = (__bf16)acc;
+      int pos = 0;
 #pragma unroll
-    for (int p = 0; p < 32; ++p)
-      if (perm32(p) == j) pos = p;
-    a.dTt[((int64_t)b * D + f) * a.Rp + pos] = (__bf16)acc;
+      for (int p = 0; p < 32; ++p)
+        if (perm32(p) == j) pos = p;
+      a.dTt[((int64_t)b * D + f) * a.Rp + pos] = (__bf16)acc;
+    }
     float dl = acc * tv;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) dl += __shfl_xor(dl, o, 64);
     if ((tid & 63) == 0) sDl[2 * j + ((tid >> 6) & 1)] = dl;
   }
   lds_barrier();
+  if (bw != nullptr) {                // LSE, Delta of the four score rows; the images are the tail's
+    if (tid < R) {
+      float* ld = reinterpret_cast<float*>(bw + PmaBwdLds::LD);
+      ld[tid] = sLSE[tid];
+      ld[4 + tid] = sDl[2 * tid] + sDl[2 * tid + 1];
+    }
+    return;
+  }
   for (int r = tid; r < a.Rp; r += NT) {
     a.Delta[(int64_t)b * a.Rp + r] = r < R ? sDl[2 * r] + sDl[2 * r + 1] : 0.f;
     a.LSEp[(int64_t)b * a.Rp + r] = r < R ? sLSE[r] : 1.0e30f;
@@ -714,6 +753,160 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     for (int p = 0; p < 32; ++p)
       if (perm32(p) == ro) pos = p;
     a.dTt[((int64_t)b * D + cc) * a.Rp + rb32 + pos] = (__bf16)0.f;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The PMA's attention backward (k_mab0_bwd<32, true>, mab0_bwd_bf16.hip) over the workgroup's resident
+// rows of Y2, after the head stages have left dT, LSE and Delta of the set's 4 score rows in LDS (bw).
+// It computes what k_mab0_bwd computed, bit for bit: the same MFMAs on the same operands (4 real score
+// rows padded to 32, the K-permuted dT^T / G'^T operands, 32-point tiles), and dG summed in the same
+// order - k_mab0_bwd's workgroup (b, split sp) covered the points [sp per, (sp + 1) per), its wave w the
+// tiles w, w + 4 .. of them, one accumulator chain per wave, the four waves' chains then added in wave
+// order into the slab b S + sp; a half of the set is S / 2 whole splits.
+//   1  wave u < NH / 32, tile u: S^T = G' Y^T, dA^T = dT Y^T -> P^T, dS^T = ln2 P^T (dA^T - Delta): bf16
+//      tiles in LDS ([point][row] image, the one k_mab0_bwd's tr_frag read)
+//   2  wave 4 s + w < 2 S: chain (split s, wave w): dG += dS Y over its tiles (A: dS tile, B: Y, both
+//      through the transposing read) -> LDS
+//   3  wave u: dY^T = dT^T P^T + G'^T dS^T over the tile's own rows of sY -> full 256-byte rows of dY2;
+//      waves 8 .. 15: the chains' sums into the slabs
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ bf16x8 tr_frag_img(const char* img, int rowb, int t, int lane, bool compact) {
+  // B / A operand [k = point (tr_frag's k order) of the 32-row image][col = element 16 t + (lane & 15)]:
+  // rows of 256 B in y_off order, or (compact) of 32 B: the [point][16 rows] P^T / dS^T tiles
+  const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
+  const int a0 = compact ? 32 * (4 * g + q) + 8 * p : y_off(4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
+  const int a1 = compact ? 32 * (16 + 4 * g + q) + 8 * p : y_off(16 + 4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + rowb + a0));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + rowb + a1));
+  const bf16x4 l4 = __builtin_bit_cast(bf16x4, lo), h4 = __builtin_bit_cast(bf16x4, hi);
+  bf16x8 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { r[e] = l4[e]; r[4 + e] = h4[e]; }
+  return r;
+}
+
+__device__ __forceinline__ void pma_bwd_tail(const __bf16* Gpma, __bf16* dY2, float* slabs, int S,
+                                             const Ctx& c, char* sY, char* bw) {
+  constexpr float LN2 = 0.6931471805599453f;
+  const int tid = c.tid, lane = c.lane, r = c.r, g = c.g;
+  const int ntile = c.NH >> 5, sph = S >> 1, tps = ntile / sph;      // tiles, splits of this half, tiles per split
+  // G' image (rows 4 .. 15 of Gpma are zero), its transpose, the zero rows of the dT image
+  if (tid < 256) {
+    const int row = tid >> 4, ch = tid & 15;
+    const bf16x8 v = gload8(Gpma + (int64_t)row * D + ch * 8);
+    *reinterpret_cast<bf16x8*>(bw + PmaBwdLds::G + y_off(row, ch)) = v;
+    if (row < 4) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) *reinterpret_cast<__bf16*>(bw + PmaBwdLds::GT + 8 * (8 * ch + k) + 2 * row) = v[k];
+    }
+  } else if (tid < 256 + 192) {
+    const int row = 4 + ((tid - 256) >> 4), ch = tid & 15;
+    *reinterpret_cast<uint4*>(bw + PmaBwdLds::DT + y_off(row, ch)) = uint4{0u, 0u, 0u, 0u};
+  }
+  lds_barrier();
+  const bf16x4 z4 = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
+  // ---- 1: P^T and dS^T of tile u (rows 4 g + e; only g = 0 are real: LSEp = +1e30 made the rest 0)
+  if (c.wave < ntile) {
+    const char* img = sY + 32 * c.wave * ROWB;
+    const float* ld = reinterpret_cast<const float*>(bw + PmaBwdLds::LD);
+    const float4 l4 = *reinterpret_cast<const float4*>(ld), d4 = *reinterpret_cast<const float4*>(ld + 4);
+    const float lse[4] = {l4.x, l4.y, l4.z, l4.w}, del[4] = {d4.x, d4.y, d4.z, d4.w};
+    char* tPT = bw + PmaBwdLds::PT + c.wave * 1024;
+    char* tDS = bw + PmaBwdLds::DS + c.wave * 1024;
+#pragma unroll
+    for (int pb = 0; pb < 2; ++pb) {
+      f32x4 sv = {0.f, 0.f, 0.f, 0.f}, da = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const bf16x8 xr = *reinterpret_cast<const bf16x8*>(img + y_off(16 * pb + r, 4 * ks + g));
+        sv = mfma32(*reinterpret_cast<const bf16x8*>(bw + PmaBwdLds::G + y_off(r, 4 * ks + g)), xr, sv);
+        da = mfma32(*reinterpret_cast<const bf16x8*>(bw + PmaBwdLds::DT + y_off(r, 4 * ks + g)), xr, da);
+      }
+      f32x4 pt, dst;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float p = g == 0 ? exp2f(sv[e] - lse[e]) : 0.f;
+        pt[e] = p;
+        dst[e] = g == 0 ? LN2 * p * (da[e] - del[e]) : 0.f;     // (+0, as the padded rows were)
+      }
+      *reinterpret_cast<bf16x4*>(tPT + 32 * (16 * pb + r) + 8 * g) = pack4(pt);
+      *reinterpret_cast<bf16x4*>(tDS + 32 * (16 * pb + r) + 8 * g) = pack4(dst);
+    }
+  }
+  lds_barrier();
+  // ---- 2: the dG chains (rows 16 .. 31 of k_mab0_bwd's dG are identically zero and not kept)
+  float* red = reinterpret_cast<float*>(bw + PmaBwdLds::RED);
+  if (c.wave < 4 * sph) {
+    const int sp = c.wave >> 2, w = c.wave & 3;
+    f32x4 dG[8];
+#pragma unroll
+    for (int ft = 0; ft < 8; ++ft) dG[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int u = sp * tps + w; u < (sp + 1) * tps; u += 4) {
+      bf16x8 xtr[8];
+#pragma unroll
+      for (int ft = 0; ft < 8; ++ft) xtr[ft] = tr_frag_img(sY, 32 * u * ROWB, ft, lane, false);
+      const bf16x8 da = tr_frag_img(bw + PmaBwdLds::DS, u * 1024, 0, lane, true);
+#pragma unroll
+      for (int ft = 0; ft < 8; ++ft) dG[ft] = mfma32(da, xtr[ft], dG[ft]);
+    }
+    if (g == 0) {
+#pragma unroll
+      for (int ft = 0; ft < 8; ++ft)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) red[c.wave * 512 + e * D + 16 * ft + r] = dG[ft][e];
+    }
+  }
+  lds_barrier();
+  // ---- 3: dY of tile u; the slabs
+  if (c.wave < ntile) {
+    char* img = sY + 32 * c.wave * ROWB;
+    const char* tPT = bw + PmaBwdLds::PT + c.wave * 1024;
+    const char* tDS = bw + PmaBwdLds::DS + c.wave * 1024;
+    bf16x8 pf[2], df[2];
+#pragma unroll
+    for (int pb = 0; pb < 2; ++pb) {
+      const bf16x4 p4 = *reinterpret_cast<const bf16x4*>(tPT + 32 * (16 * pb + r) + 8 * g);
+      const bf16x4 d4 = *reinterpret_cast<const bf16x4*>(tDS + 32 * (16 * pb + r) + 8 * g);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        pf[pb][e] = p4[e]; pf[pb][4 + e] = z4[e];
+        df[pb][e] = d4[e]; df[pb][4 + e] = z4[e];
+      }
+    }
+#pragma unroll
+    for (int ft = 0; ft < 8; ++ft) {
+      // A operands [feature 16 ft + i][k-slot 8 g + j = score row perm32(8 g + j)]: rows 0 .. 3 sit in
+      // the slots j < 4 of g = 0, every other slot is padding
+      bf16x4 t4 = *reinterpret_cast<const bf16x4*>(bw + PmaBwdLds::DTT + 8 * (16 * ft + r));
+      bf16x4 g4 = *reinterpret_cast<const bf16x4*>(bw + PmaBwdLds::GT + 8 * (16 * ft + r));
+      bf16x8 ta, ga;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        ta[e] = g == 0 ? t4[e] : z4[e]; ta[4 + e] = z4[e];
+        ga[e] = g == 0 ? g4[e] : z4[e]; ga[4 + e] = z4[e];
+      }
+#pragma unroll
+      for (int pb = 0; pb < 2; ++pb) {
+        f32x4 dx = {0.f, 0.f, 0.f, 0.f};
+        dx = mfma32(ta, pf[pb], dx);
+        dx = mfma32(ga, df[pb], dx);
+        *reinterpret_cast<bf16x4*>(img + y_off(16 * pb + r, 2 * ft + (g >> 1)) + 8 * (g & 1)) = pack4(dx);
+      }
+    }
+    // (the tile's rows were last read in stage 2, before the barrier)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int cidx = lane + 64 * k, row = cidx >> 4, ch = cidx & 15;
+      *reinterpret_cast<uint4*>(dY2 + (c.row0 + 32 * c.wave + row) * D + ch * 8) =
+          *reinterpret_cast<const uint4*>(img + y_off(row, ch));
+    }
+  } else if (tid >= 512) {
+    const int i = tid - 512;
+    for (int sp = 0; sp < sph; ++sp) {
+      const float* rs = red + sp * 4 * 512;
+      slabs[((int64_t)c.b * S + c.half * sph + sp) * 512 + i] = rs[i] + rs[512 + i] + rs[1024 + i] + rs[1536 + i];
+    }
   }
 }
 
@@ -1181,20 +1374,29 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
     lds_barrier();
     float* exMine = ap->exP + (int64_t)(b * 2 + c.half) * 528;
     float* exTheirs = ap->exP + (int64_t)(b * 2 + (c.half ^ 1)) * 528;
-    if (c.half == 1) {
-      // hand-off 3 (R1 again: 4-byte write-through stores, drained, barrier, one flag): half 1 is done
+    const bool pbwd = ap->pma_bwd != 0;
+    if (c.half == 1 || pbwd) {
+      // hand-off 3 (R1 again: 4-byte write-through stores, drained, barrier, one flag): half 1 is done,
+      // or (pma_bwd) both halves publish and both go on
       if (tid < 520)
         __hip_atomic_store((__attribute__((address_space(1))) float*)(exMine + tid), sPm[tid],
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       drain_vm();
       lds_barrier();
-      if (tid == 0) flag_store(flags + 4 + (b * 2 + 0) * 2 + 1, 3u);
-      return;
+      if (tid == 0) flag_store(flags + 4 + (b * 2 + 0) * 2 + c.half, 3u);
+      if (!pbwd) return;
     }
-    if (c.wave == 0) flag_wait(flags + 4 + (b * 2 + 0) * 2 + 1, 3u, flags);
+    if (c.wave == 0) flag_wait(flags + 4 + (b * 2 + 0) * 2 + (c.half ^ 1), 3u, flags);
     lds_barrier();
-    head_stages(*(const PmaHeadArgs*)(&ap->head), c, sPm, exTheirs, reinterpret_cast<float*>(sS) + 1024);
+    head_stages(*(const PmaHeadArgs*)(&ap->head), c, sPm, exTheirs, reinterpret_cast<float*>(sS) + 1024,
+                c.half == 0, pbwd ? sO : nullptr);
     STAMP(19);
+    if (pbwd) {
+      ap = launder(ap);
+      rederive(c);
+      pma_bwd_tail(ap->Gpma, ap->dY2, ap->pma_slabs, ap->pma_S, c, sY, sO);
+      STAMP(27);
+    }
   }
 }
 
@@ -1244,9 +1446,18 @@ int set128_fwd_launch(const Set128FwdArgs& a, hipStream_t st) {
   // reference-formulation FLOPs of the three blocks this launch covers (the PMA's
   // epilogue and the classifier run in k_pma_head1), algorithmic bytes: X in, two [N, d] bf16 tensors
   // written and read once each
+  // pma_bwd: plus the PMA attention backward in k_mab0_bwd's units (2 N (2 d^2 + 2 k d) MACs per set), and
+  // the bytes move - dY2 is written instead of Y2
+  PCA_REQUIRE(!a.pma_bwd || (a.fuse_head && a.dY2 != nullptr && a.pma_slabs != nullptr),
+              "set128_fwd: the PMA backward needs the fused head and its outputs");
+  PCA_REQUIRE(!a.pma_bwd || a.pma_S == 2 || (a.pma_S == 4 && a.N == 512),
+              "set128_fwd: PMA backward in %d splits of %d points", a.pma_S, a.N);
   const double Nn = a.N, dd = 128, mm = 16;
-  const double macs = Nn * (3.0 * a.din * dd + 7.0 * dd * dd + 8.0 * mm * dd + 2.0 * dd) + 6.0 * mm * dd * dd;
-  ProfScope ps(PCA_K_SET_FWD, st, 2.0 * macs * a.B, (double)a.B * (4.0 * Nn * a.din + 8.0 * Nn * dd));
+  double macs = Nn * (3.0 * a.din * dd + 7.0 * dd * dd + 8.0 * mm * dd + 2.0 * dd) + 6.0 * mm * dd * dd;
+  if (a.pma_bwd) macs += 2.0 * Nn * (2.0 * dd * dd + 2.0 * dd);
+  // [N, d] bf16 tensors written here and read once later: Y1, Y2 (unless not stored), dY2
+  const double nout = (a.L[1].Y != nullptr ? 2.0 : 1.0) + (a.pma_bwd ? 1.0 : 0.0);
+  ProfScope ps(PCA_K_SET_FWD, st, 2.0 * macs * a.B, (double)a.B * (4.0 * Nn * a.din + 4.0 * Nn * dd * nout));
   const dim3 grid(16 * (unsigned)cdiv(a.B, 8));
   const int key = a.din * 2 + (a.N == 512 ? 1 : 0);       // units per quad of waves: N / 256
   switch (key) {

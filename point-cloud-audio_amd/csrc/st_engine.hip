@@ -302,7 +302,7 @@ int validate(const pca_st_config* c) {
 
 int forward(const pca_st_config& c, const Layout& L, const Shapes& s, const float* p,
             const float* X, Ws& w, bool training, hipStream_t st, const PrepJobs* image_jobs = nullptr,
-            const PmaHeadArgs* head = nullptr) {
+            const PmaHeadArgs* head = nullptr, bool pma_bwd = false) {
   const void* in = X;
   // d = 256: the query side of all three few-queries blocks in the same launch (mab0_d256_prep_collect)
   const bool prep256 = training && s.m0[0].d == 256 && mab_kind(s.m0[0]) == 2 &&
@@ -369,6 +369,15 @@ int forward(const pca_st_config& c, const Layout& L, const Shapes& s, const floa
       S.KpP = v1.KpP; S.VpP = v1.VpP; S.Kt = v1.Kt; S.Vt = v1.Vt;
       S.WqB = im.WqB; S.WqF = p1.wq; S.bq1 = p1.bq; S.WoP = im.WoP; S.bo1 = p1.bo;
       S.QpS = v1.QpS; S.OS = v1.OS; S.Y = reinterpret_cast<__bf16*>(w.Y[li]); S.mask = v1.mask;
+    }
+    if (head != nullptr && pma_bwd) {  // the PMA's attention backward in the tail: Y2 has no reader left
+      a.pma_bwd = 1;
+      a.dY2 = reinterpret_cast<__bf16*>(w.dY2);
+      Mab0BwdWs wb;
+      mab0_carve_bwd_ws(s.pma, &wb, w.scratch);
+      a.pma_slabs = wb.slabs;
+      a.pma_S = mab0_bwd_splits(s.pma);
+      a.L[1].Y = nullptr;
     }
     Carver cs(w.set128_ws);
     a.flags = reinterpret_cast<uint32_t*>(cs.take<char>(set128_flag_bytes(c.B)));   // (cleared by k_prep_all)
@@ -540,12 +549,15 @@ static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, co
     // the set-resident forward runs the head stages in its own tail (PCA_SET128_HEAD=0: as a launch)
     const char* he = getenv("PCA_SET128_HEAD");
     const bool fuse_head = pca::set128_on(*c, s) && c->C <= 64 && !(he != nullptr && he[0] == '0');
+    // ... and then the PMA's attention backward too (PCA_SET128_PMABWD=0: k_mab0_bwd, as a launch)
+    const char* pe = getenv("PCA_SET128_PMABWD");
+    const bool pma_bwd = fuse_head && !(pe != nullptr && pe[0] == '0');
     pca::PmaHeadArgs head{};
     if (fuse_head)
       PCA_TRY(pca::pma_head_args(s.pma, pca::params_at(p, L.pma), w.saved[4], w.scratch, w.P,
                                  p + L.wc, p + L.bc, labels, c->C, grad_scale, w.logits, w.dlogits,
                                  w.dP, g + L.wc, g + L.bc, loss_out, stats, w.clsws, &posts, &head));
-    PCA_TRY(pca::forward(*c, L, s, p, X, w, true, st, &image_jobs, fuse_head ? &head : nullptr));
+    PCA_TRY(pca::forward(*c, L, s, p, X, w, true, st, &image_jobs, fuse_head ? &head : nullptr, pma_bwd));
     if (pca::pma_head_ok(s)) {
       // dec.0 epilogue + dec.1 (Linear) + mean cross-entropy forward and backward + dec.0
       // backward epilogue: one launch, one workgroup per set
@@ -556,7 +568,8 @@ static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, co
                                    w.clsws, &posts, st));
       PCA_TRY(pca::mab0_bf16_bwd_ex(s.pma, p + L.S, w.Y[1], pca::params_at(p, L.pma),
                                     w.saved[4], w.dP, g + L.S, w.dY2, 0,
-                                    pca::grads_at(g, L.pma), w.scratch, pca::PCA_F_SKIP_HEAD, st,
+                                    pca::grads_at(g, L.pma), w.scratch,
+                                    pca::PCA_F_SKIP_HEAD | (pma_bwd ? pca::PCA_F_ATTN_DONE : 0), st,
                                     &posts));
     } else {
     // dec.1 (Linear) + mean cross-entropy, forward and backward
