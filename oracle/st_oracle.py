@@ -519,7 +519,7 @@ def _lin8(x: Tensor, W: Tensor, b: Tensor) -> Tensor:
 def mab1_forward_fp8emu(X: Tensor, H: Tensor, p: Params, num_heads: int,
                         fp8_q: bool = False) -> Tensor:
     """mab_forward(X, H) as csrc/mab1_bf16.hip computes it in PCA_MODE_FP8: fc_o (and fc_q with
-    fp8_q, the library's PCA_FP8_PROJ=qo) with fp8 e4m3 operands (weights scaled per tensor,
+    fp8_q: measured, not built into the library - DESIGN.md 4.6) with fp8 e4m3 operands (weights scaled per tensor,
     activations as they are), everything else as mab1_forward_bf16emu (bf16 K / V images, bf16
     attention operands, fp32 accumulation)."""
     B, nq, dq = X.shape

@@ -561,9 +561,6 @@ __global__ __launch_bounds__(64 * NW, 4) void k_attnc_bwd_kv(const AttnCoreArgs 
 // Staging: 4 d items of 4 rows x 4 features per chunk, 2 d threads (h = d / 32 waves): two items each.
 constexpr int T32 = 4;         // 16-row tiles per wave and group
 
-__device__ __forceinline__ bf16x8 cat8(bf16x4 lo, bf16x4 hi) {
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 // 8 features of a [rows][d] fp32 row as a bf16 operand (p: the first of them; 32-byte aligned)
 __device__ __forceinline__ bf16x8 ld8_bf16(const float* p) {
   const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);

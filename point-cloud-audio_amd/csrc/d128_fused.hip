@@ -42,7 +42,6 @@ struct Fused128Args {
   float scale_log2e;
 };
 
-typedef __attribute__((address_space(3))) void lptr_t;
 
 #define PCA_WAIT_VM_CASE(n) case n: asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory"); break;
 __device__ __forceinline__ void wait_vm128(int n) {
@@ -134,7 +133,7 @@ __global__ __launch_bounds__(64 * (D / 32), 2) void k_isab1_fwd_t(const Fused128
       const int n = n0 + row < a.N ? n0 + row : a.N - 1;
       const __bf16* src = reinterpret_cast<const __bf16*>(a.X) + ((int64_t)b * a.N + n) * D + ch * 8;
       const unsigned ldst = __builtin_amdgcn_readfirstlane(
-          (unsigned)(uintptr_t)(lptr_t*)(dst + (DMA_PER_WAVE * j + i) * 1024));
+          (unsigned)(uintptr_t)(lds_void_t*)(dst + (DMA_PER_WAVE * j + i) * 1024));
       unsigned keep;
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
                    "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"

@@ -3,23 +3,27 @@
 // modules.py:19-33 backwards) that the d = 128 kernels hold in ONE launch do not fit a CU at
 // d = 256 (two 128 KiB weight images), so the backward of the many-queries block runs as
 //
-//   k_rowgemm<BWD_O>     dZ = dY.[Z>0] ; dO = dY + dZ Wo           (Wo^T image resident in LDS)
-//   k_attn1_bwd          per head: P recomputed, dA, dS, dQp = dO + dS Kp ; dKp, dVp of the set
+//   k_attn1_bwd3         dZ = dY.[Z>0] ; dO = dY + dZ Wo (the wave's slice of Wo^T in registers), then
+//                        per head: P recomputed, dA, dS, dQp = dO + dS Kp ; dKp, dVp of the set
 //                        (WAVE = HEAD: a wave owns the 32 features of one head of its 32-point
-//                        tiles - no weight image at all, 9 KiB of LDS per wave)
-//   k_rowgemm<BWD_Q>     dX (+)= dQp Wq                            (Wq^T image resident in LDS)
-//   k_wgrad256           dW[256 x 256] = G^T A over the B*N rows, deterministic two-stage sum
+//                        tiles), k_sum_parts256 sums the per-range dKp / dVp partials
+//   k_rowstream DX1/DX3  dX = dQp Wq (+ dKp Wk + dVp Wv)            (d256_stream.hip)
+//   k_wgrad256(_dma)     dW[256 x 256] = G^T A over the B*N rows, deterministic two-stage sum
 //
 // and the few-queries block (ISAB mab0 at dk = 256) in the reference's own formulation
 // (modules.py:21: the N keys ARE projected) because the four 128 KiB operand images of the
 // reassociated backward exceed the register file + LDS of a CU:
 //
-//   k_rowgemm<PROJ>      Kp / Vp = X Wk^T + bk  (bf16, [B*N, 256])
-//   k_fq_attn_fwd        flash attention of the m shared queries of one head over the set's
-//                        keys (wave = head, head dim 32): online softmax, O partials per range
-//   k_fq_attn_bwd        dKp, dVp (bf16) and the set's dQp; both score orientations are
-//                        recomputed on the MFMA (one extra 16x16x32 each) instead of transposed
-//   k_rowgemm<BWD_Q> x2  dX (+)= dKp Wk + dVp Wv
+//   k_fq_proj_fwd        m = 32: Kp / Vp = X Wk^T + bk (bf16, [B*N, 256]) and the flash attention of
+//                        the m shared queries over the set's keys in one pass over X (wave = head,
+//                        head dim 32): online softmax, O partials per range, k_fq_merge joins them
+//   k_rowstream PROJ2 +  m <= 16: the projection (d256_stream.hip) and the attention as two launches
+//   k_fq_attn_fwd<256,1>
+//   k_fq_attn_bwd2       dKp, dVp (bf16) and the set's dQp; both score orientations are
+//   (m <= 16: _bwd<256,1>) recomputed on the MFMA (one extra 16x16x32 each) instead of transposed
+//   k_rowstream DX2/DX3  dX (+)= dKp Wk + dVp Wv                    (d256_stream.hip)
+//
+// plus the PMA at dk = 256 in the reassociated form (k_pma_*256) and the small per-set / layer-1 kernels.
 //
 // All activations cross these kernels in bf16 ([rows][256], row-major); accumulation, softmax
 // statistics, biases and residuals are fp32.  Layout conventions: mfma_common.hpp.
@@ -34,334 +38,9 @@ namespace pca {
 
 namespace {
 
-constexpr int TP = M1_TP;      // 128 points per 4-wave tile (as the forward: the ReLU mask index)
-
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-// transposed fragment (k = the 32 points of a wave tile: slot (g, j) <-> point perm32(8g + j))
-// from a small row-major bf16 image with `rb` bytes per row, for the 16 columns from col0
-__device__ __forceinline__ bf16x8 tr_frag_small(const char* img, int rb, int col0, int lane) {
-  const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-  const int a0 = (4 * g + q) * rb + (col0 + 4 * p) * 2;
-  const int a1 = (16 + 4 * g + q) * rb + (col0 + 4 * p) * 2;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a1));
-  const bf16x4 l4 = __builtin_bit_cast(bf16x4, lo), h4 = __builtin_bit_cast(bf16x4, hi);
-  bf16x8 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { r[e] = l4[e]; r[4 + e] = h4[e]; }
-  return r;
-}
-
-__device__ __forceinline__ bf16x8 cat8(bf16x4 lo, bf16x4 hi) {
-  bf16x8 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { r[e] = lo[e]; r[4 + e] = hi[e]; }
-  return r;
-}
-__device__ __forceinline__ f32x4 tof(bf16x4 v) {
-  return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-}
-__device__ __forceinline__ bf16x4 zero4b() {
-  return bf16x4{(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
-}
 
 // =====================================================================================
-// k_rowgemm: Out^T[f][pt] = sum_k W[f][k] In^T[k][pt]  with the [D][D] bf16 weight image resident
-// in LDS (K-permuted rows: the B operand comes from accumulator-layout registers, cat8) and one
-// 32-point tile per wave.  Same unit / wave -> point mapping as k_mab1_fwd (the ReLU mask index).
-//
-// Global traffic is full 128-byte lines: a wave moves its [32 rows][256] bf16 tile in four
-// 64-column chunks through a private 4 KiB LDS buffer - 16-byte coalesced loads / stores on the
-// memory side (8 lanes = one 128-byte row segment), 8-byte accumulator-layout accesses on the LDS
-// side.  (Accumulator-layout accesses straight to global memory touch 32 bytes of 16 different
-// rows per instruction; with 8 waves x 16 KiB of rows in flight the 32 KiB L1 re-fetched every
-// line up to four times: measured 209 -> see DESIGN.md.)
-// =====================================================================================
-enum { RG_PROJ = 0, RG_BWD_O = 1, RG_BWD_Q = 2, RG_FWD_O = 3 };
-
-struct RowGemmArgs {
-  const __bf16* In;       // [B*N][D]: PROJ X ; BWD_O dY ; BWD_Q dQp (or dKp / dVp) ; FWD_O O
-  const __bf16* W;        // [D][D] image (see the launcher for which)
-  const float* bias;      // PROJ, FWD_O
-  const float* inv_scale; // F8: 1 / (per-tensor power-of-two scale of the fp8 weight image)
-  const uint32_t* mask;   // BWD_O: ReLU mask bits of the forward
-  uint32_t* mask_out;     // FWD_O (nullable)
-  __bf16* Out;            // PROJ Y ; BWD_O dO ; BWD_Q dX ; FWD_O Y
-  __bf16* Out2;           // BWD_O: dZ
-  int B, N, tiles_per_set, accumulate;
-};
-
-// byte offset of 16-byte piece c16 (0..7) of row `row` in a [32][64] bf16 chunk (128-byte rows);
-// the XOR spreads the 16 rows of an accumulator-layout access over all banks
-__device__ __forceinline__ int cko(int row, int c16) {
-  return row * 128 + ((c16 ^ ((row >> 1) & 7)) << 4);
-}
-
-// NB = 16-point blocks per wave: 2 (8 waves, 256 VGPRs) or 1 (16 waves of 128 VGPRs: four
-// wavefronts per SIMD to hide the memory latency, twice the LDS weight reads per MFMA)
-// F8 (PROJ, FWD_O): W is an fp8 e4m3 image of s * W ([D][D] bytes), the activations are converted
-// to fp8 in registers; the accumulators are rescaled by 1 / s before the bias
-template <int D, int MODE, int NB, bool F8 = false>
-__global__ __launch_bounds__(1024 / NB, 4 / NB) void k_rowgemm(const RowGemmArgs a) {
-  constexpr int NW = 16 / NB, NT = 64 * NW, SUBS = 2;
-  constexpr int DT = D / 16, KS = D / 32, ROWB = F8 ? D : D * 2, NCH = D / 64;
-  static_assert(!F8 || MODE == RG_PROJ || MODE == RG_FWD_O, "fp8 operands: forward projections");
-  constexpr int CB = 16 * NB * 128;       // bytes of a wave's chunk buffer ([16 NB rows][64])
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* sW = smem;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  // wave wv of the workgroup = 16-point blocks [wv * NB, wv * NB + NB) of a 256-point unit; in the
-  // forward's terms (mask index): tile `sub` of the unit, wave (0..3), block nb0 + nb of that wave
-  const int blk0 = wv * NB, sub = blk0 >> 3, wave = (blk0 & 7) >> 1, nb0 = blk0 & 1;
-  const int r = lane & 15, g = lane >> 4;
-  char* myC = smem + D * ROWB + wv * CB;          // (behind the weight image)
-  {
-    constexpr int CPR = ROWB / 16;                 // 16-byte chunks per image row
-    constexpr int NC = D * CPR / NT;
-    uint4 wv[NC];
-    const char* gW = reinterpret_cast<const char*>(a.W);
-#pragma unroll
-    for (int e = 0; e < NC; ++e) {
-      const int c = tid + NT * e, row = c / CPR, c16 = c % CPR;
-      wv[e] = *reinterpret_cast<const uint4*>(gW + (int64_t)row * ROWB + c16 * 16);
-    }
-#pragma unroll
-    for (int e = 0; e < NC; ++e) {
-      const int c = tid + NT * e, row = c / CPR, c16 = c % CPR;
-      if (F8) {
-        *reinterpret_cast<uint2*>(sW + f8off<D>(row, 2 * c16)) = uint2{wv[e].x, wv[e].y};
-        *reinterpret_cast<uint2*>(sW + f8off<D>(row, 2 * c16 + 1)) = uint2{wv[e].z, wv[e].w};
-      } else {
-        *reinterpret_cast<uint4*>(sW + swz(row, c16, ROWB)) = wv[e];
-      }
-    }
-  }
-  const float inv_s = F8 ? a.inv_scale[0] : 1.f;
-  (void)inv_s;
-  __syncthreads();
-  const int units_per_set = (a.tiles_per_set + SUBS - 1) / SUBS;
-  const int total_units = a.B * units_per_set;
-  // coalesced side of the chunk moves: piece i of a lane = row (lane + 64 i) / 8, 16-byte column
-  // (lane + 64 i) % 8; accumulator side: row 16 nb + r, 8 bytes at columns 16 t' + 4 g
-  const int crow0 = lane >> 3, cc16 = lane & 7;
-  for (int unit = blockIdx.x; unit < total_units; unit += gridDim.x) {
-    const int b = unit / units_per_set, tile = (unit - b * units_per_set) * SUBS + sub;
-    if (tile >= a.tiles_per_set) continue;                 // (no barrier inside the loop)
-    const int n_base = tile * TP + wave * 32 + nb0 * 16;
-    const int64_t rowbase = (int64_t)b * a.N + n_base;
-    const int nlive = a.N - n_base;                        // rows of this wave tile that exist
-    // FWD_O keeps O (the bf16 B operand) alive for the residual: its output features are
-    // computed in two halves of 128 so that the accumulators need 64 registers, not 128
-    constexpr int HT = 1, DTH = DT / HT;
-    f32x4 acc[DTH][NB];
-    bf16x8 bop[KS][NB];
-    uint32_t bits[NB][D / 128];
-    if (MODE == RG_BWD_O) {
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int w = 0; w < D / 128; ++w)
-          bits[nb][w] = a.mask[mab1_mask_index<D>(b, a.tiles_per_set, tile, wave, nb0 + nb, w, lane)];
-    }
-    constexpr int NI = 2 * NB;             // 16-byte pieces per lane and chunk
-    uint4 st[2][NI];
-    auto fetch = [&](int c, uint4 (&dst)[NI]) {
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        // rows past the end of the set read its last row instead (never stored: a point only
-        // feeds its own output column) - a load under a divergent condition gets its own basic
-        // block and s_waitcnt vmcnt(0), which serialised the NI loads of a chunk
-        // (BWD_O keeps the guarded form: with the loads free to move, the scheduler hoists them
-        //  over the 128 accumulators it initialises from dY and spills 144 bytes per lane)
-        const int n = n_base + crow0 + 8 * i;
-        if (MODE == RG_BWD_O)
-          dst[i] = n < a.N ? *reinterpret_cast<const uint4*>(a.In + ((int64_t)b * a.N + n) * D +
-                                                             64 * c + 8 * cc16)
-                           : uint4{0u, 0u, 0u, 0u};
-        else
-          dst[i] = *reinterpret_cast<const uint4*>(
-              a.In + ((int64_t)b * a.N + (n < a.N ? n : a.N - 1)) * D + 64 * c + 8 * cc16);
-      }
-    };
-    fetch(0, st[0]);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      if (c + 1 < NCH) fetch(c + 1, st[(c + 1) & 1]);
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-        *reinterpret_cast<uint4*>(myC + cko(crow0 + 8 * i, cc16)) = st[c & 1][i];
-      bf16x4 in4[4][NB];
-#pragma unroll
-      for (int tq = 0; tq < 4; ++tq)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-          in4[tq][nb] = *reinterpret_cast<const bf16x4*>(myC + cko(16 * nb + r, 2 * tq + (g >> 1)) +
-                                                        8 * (g & 1));
-#pragma unroll
-      for (int tq = 0; tq < 4; ++tq) {
-        const int t = 4 * c + tq;
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-          if constexpr (MODE == RG_BWD_O) {
-            acc[t][nb] = tof(in4[tq][nb]);                  // dO starts as dY (residual path)
-            bf16x4 z4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              z4[e] = ((bits[nb][t / 8] >> ((t & 7) * 4 + e)) & 1u) ? in4[tq][nb][e] : (__bf16)0.f;
-            in4[tq][nb] = z4;
-            // dZ goes back through the chunk buffer to leave in full lines
-            *reinterpret_cast<bf16x4*>(myC + cko(16 * nb + r, 2 * tq + (g >> 1)) + 8 * (g & 1)) = z4;
-          }
-        }
-      }
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        bop[2 * c][nb] = cat8(in4[0][nb], in4[1][nb]);
-        bop[2 * c + 1][nb] = cat8(in4[2][nb], in4[3][nb]);
-      }
-      if (MODE == RG_BWD_O) {
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-          const int row = crow0 + 8 * i;
-          const uint4 v = *reinterpret_cast<const uint4*>(myC + cko(row, cc16));
-          if (row < nlive)
-            *reinterpret_cast<uint4*>(a.Out2 + (rowbase + row) * D + 64 * c + 8 * cc16) = v;
-        }
-      }
-    }
-    // FWD_O: Y = O + relu(Z) - O is the bf16 B operand itself (feature 16 t + 4 g + e = element
-    // 4 (t & 1) + e of k-block t / 2); ReLU mask bits in the layout of k_mab1_fwd
-    uint32_t mb[NB][D / 128];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-      for (int w = 0; w < D / 128; ++w) mb[nb][w] = 0u;
-#pragma unroll
-    for (int hf = 0; hf < HT; ++hf) {
-      if (MODE != RG_BWD_O) {
-#pragma unroll
-        for (int tt = 0; tt < DTH; ++tt) {
-          float4 b4 = float4{0.f, 0.f, 0.f, 0.f};
-          if (!F8 && (MODE == RG_PROJ || MODE == RG_FWD_O))
-            b4 = *reinterpret_cast<const float4*>(a.bias + 16 * (hf * DTH + tt) + 4 * g);
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb) acc[tt][nb] = f32x4{b4.x, b4.y, b4.z, b4.w};
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        if (F8) {
-          f8x8 b8[NB];
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb) b8[nb] = bf_to_f8(bop[s][nb]);
-#pragma unroll
-          for (int tt = 0; tt < DTH; ++tt) {
-            const f8x8 wa8 = *reinterpret_cast<const f8x8*>(
-                sW + f8off<D>(16 * (hf * DTH + tt) + r, 4 * s + g));
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) acc[tt][nb] = mfma32_f8(wa8, b8[nb], acc[tt][nb]);
-          }
-        } else {
-#pragma unroll
-          for (int tt = 0; tt < DTH; ++tt) {
-            const bf16x8 wa = *reinterpret_cast<const bf16x8*>(
-                sW + swz(16 * (hf * DTH + tt) + r, 4 * s + g, ROWB));
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) acc[tt][nb] = mfma32(wa, bop[s][nb], acc[tt][nb]);
-          }
-        }
-      }
-      if (F8) {
-#pragma unroll
-        for (int tt = 0; tt < DTH; ++tt) {
-          const float4 b4 = *reinterpret_cast<const float4*>(a.bias + 16 * (hf * DTH + tt) + 4 * g);
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb) {
-            acc[tt][nb][0] = acc[tt][nb][0] * inv_s + b4.x;
-            acc[tt][nb][1] = acc[tt][nb][1] * inv_s + b4.y;
-            acc[tt][nb][2] = acc[tt][nb][2] * inv_s + b4.z;
-            acc[tt][nb][3] = acc[tt][nb][3] * inv_s + b4.w;
-          }
-        }
-      }
-#pragma unroll
-      for (int cc = 0; cc < NCH / HT; ++cc) {
-        const int c = hf * (NCH / HT) + cc;
-#pragma unroll
-        for (int tq = 0; tq < 4; ++tq) {
-          const int t = 4 * c + tq, tt = t - hf * DTH;
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb) {
-            f32x4 v = acc[tt][nb];
-            if (MODE == RG_FWD_O) {
-              const bf16x8 ob = bop[t / 2][nb];
-              const f32x4 of = tof((t & 1) ? __builtin_shufflevector(ob, ob, 4, 5, 6, 7)
-                                           : __builtin_shufflevector(ob, ob, 0, 1, 2, 3));
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                const float zz = v[e];
-                if (zz > 0.f) mb[nb][t / 8] |= 1u << ((t & 7) * 4 + e);
-                v[e] = of[e] + fmaxf(zz, 0.f);
-              }
-            }
-            if (MODE == RG_BWD_Q && a.accumulate) {
-              const int n = 16 * nb + r;
-              if (n < nlive) {
-                const f32x4 o = tof(*reinterpret_cast<const bf16x4*>(a.Out + (rowbase + n) * D +
-                                                                     16 * t + 4 * g));
-                v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3];
-              }
-            }
-            *reinterpret_cast<bf16x4*>(myC + cko(16 * nb + r, 2 * tq + (g >> 1)) + 8 * (g & 1)) =
-                pack4(v);
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-          const int row = crow0 + 8 * i;
-          const uint4 v = *reinterpret_cast<const uint4*>(myC + cko(row, cc16));
-          if (row < nlive)
-            *reinterpret_cast<uint4*>(a.Out + (rowbase + row) * D + 64 * c + 8 * cc16) = v;
-        }
-      }
-    }
-    if (MODE == RG_FWD_O && a.mask_out != nullptr) {
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int w = 0; w < D / 128; ++w)
-          a.mask_out[mab1_mask_index<D>(b, a.tiles_per_set, tile, wave, nb0 + nb, w, lane)] =
-              mb[nb][w];
-    }
-  }
-}
-
-template <int MODE, int NBW, bool F8 = false>
-int launch_rowgemm_nb(const RowGemmArgs& a, hipStream_t st) {
-  constexpr int D = 256;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_rowgemm<D, MODE, NBW, F8>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
-  const int total = a.B * ((a.tiles_per_set + 1) / 2);
-  const int grid = total < 256 ? total : 256;
-  hipLaunchKernelGGL((k_rowgemm<D, MODE, NBW, F8>), dim3(grid), dim3(1024 / NBW),
-                     (size_t)D * D * (F8 ? 1 : 2) + 8 * 4096, st, a);
-  return check_launch("k_rowgemm");
-}
-template <int MODE>
-int launch_rowgemm(const RowGemmArgs& a, hipStream_t st) {
-  // measured at configs[3] (B = 128, N = 4096): 8 waves x 2 blocks is the faster shape for PROJ /
-  // BWD_O / BWD_Q (126 / 147 / 172 us against 133 / 173 / 176), 16 waves x 1 block for FWD_O,
-  // whose 8-wave build spills (181 against 195 us)
-  if (MODE == RG_FWD_O) return launch_rowgemm_nb<MODE, 1>(a, st);
-  return launch_rowgemm_nb<MODE, 2>(a, st);
-}
-
-// =====================================================================================
-// k_attn1_bwd: attention adjoint of the many-queries block, WAVE = HEAD
+// k_attn1_bwd3: fc_o adjoint + attention adjoint of the many-queries block, WAVE = HEAD
 // =====================================================================================
 struct Attn1BwdArgs {
   const __bf16* dO;         // [B*N][D]
@@ -374,205 +53,17 @@ struct Attn1BwdArgs {
   float scale, scale_log2e;
 };
 
-// (k_attn1_bwd, the per-wave global-traffic form of round 1, was removed in round 4: k_attn1_bwd2 below has
-//  been the measured winner since round 2 - DESIGN.md 4.5.)
-
-// k_attn1_bwd2: the attention adjoint of the many-queries block, WAVE = HEAD, with full-line global
-// traffic.  (With every wave fetching its head's 64-byte slice of each row straight from memory - 16 rows
-// x 32 bytes per load instruction, 8-byte stores - it took 243 us at configs[3] for 0.8 GB, 3.3 TB/s.)
-// Here the workgroup moves whole [32 points][256] tiles: Qp and dO arrive by LDS-DMA (1 KiB per wave
-// instruction, double buffered, swizzled like the single-launch forward's tiles), each wave reads /
-// writes its head's slice of the tiles in LDS, and the dQp tile leaves in 16-byte pieces of full rows.
-typedef __attribute__((address_space(3))) void lds_void_t;
-template <int D>
-__global__ __launch_bounds__(64 * (D / 32), 2) void k_attn1_bwd2(const Attn1BwdArgs a) {
-  constexpr int MI = 32, ROWB = D * 2, TILEB = 32 * ROWB;
-  constexpr int PQ = 72, IMG = 32 * PQ;
-  static_assert(D == 256, "8 waves, 2 DMA pieces per wave and tensor");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* sQb = smem;                       // [2][TILEB]
-  char* sOb = smem + 2 * TILEB;           // [2][TILEB]
-  char* sOut = smem + 4 * TILEB;          // dQp tile
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int j = __builtin_amdgcn_readfirstlane(tid >> 6);      // head of this wave
-  const int r = lane & 15, g = lane >> 4;
-  const int b = blockIdx.x / a.nparts, part = blockIdx.x - b * a.nparts;
-  char* myDS = smem + 5 * TILEB + j * 4 * IMG;
-  char* myP = myDS + IMG;
-  char* myQ = myP + IMG;
-  char* myO = myQ + IMG;
-
-  bf16x8 kpa[2], vpa[2], kta[2];
-#pragma unroll
-  for (int kt = 0; kt < 2; ++kt) {
-    const int64_t o = ((int64_t)b * MI + 16 * kt + r) * D + 32 * j + 8 * g;
-    kpa[kt] = *reinterpret_cast<const bf16x8*>(a.KpP + o);
-    vpa[kt] = *reinterpret_cast<const bf16x8*>(a.VpP + o);
-    kta[kt] = *reinterpret_cast<const bf16x8*>(a.Kt + ((int64_t)b * D + 32 * j + 16 * kt + r) * MI +
-                                               8 * g);
-  }
-  f32x4 dkp[2][2], dvp[2][2];
-#pragma unroll
-  for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-      dkp[kt][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      dvp[kt][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  const int n_lo = part * a.pts_per_part;
-  const int n_hi = n_lo + a.pts_per_part < a.N ? n_lo + a.pts_per_part : a.N;
-  const int T = n_lo < n_hi ? (n_hi - n_lo + 31) / 32 : 0;
-  // accumulator-layout 8 bytes of this lane in a tile (row = point r, features 32 j + 16 t + 4 g)
-  // and its coalesced 16-byte piece (row tid / 32, chunk tid % 32), as in k_isab1_fwd256
-  int oD[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) oD[t] = swz(r, 4 * j + 2 * t + (g >> 1), ROWB) + 8 * (g & 1);
-  const int oC = swz(tid >> 5, tid & 31, ROWB);
-  auto lds_barrier = [] {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-  // LDS-DMA of tile k of both tensors (issued from inline asm: see k_isab1_fwd256)
-  auto dma = [&](int k) {
-    const int n0 = n_lo + 32 * k, par = k & 1;
-#pragma unroll
-    for (int w = 0; w < 2; ++w) {
-      const __bf16* base = w == 0 ? a.QpS : a.dO;
-      char* dst = (w == 0 ? sQb : sOb) + par * TILEB;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int p = (2 * j + i) * 64 + lane;
-        const int row = p >> 5, slot = p & 31;
-        const int ch = (slot & ~15) | ((slot ^ row) & 15);
-        const int n = n0 + row < a.N ? n0 + row : a.N - 1;
-        const __bf16* src = base + ((int64_t)b * a.N + n) * D + ch * 8;
-        const unsigned ldst = __builtin_amdgcn_readfirstlane(
-            (unsigned)(uintptr_t)(lds_void_t*)(dst + (2 * j + i) * 1024));
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(src), "s"(ldst) : "memory");
-      }
-    }
-  };
-  if (T > 0) dma(0);
-  for (int k = 0; k < T; ++k) {
-    const int par = k & 1, n0 = n_lo + 32 * k, nlive = n_hi - n0;
-    const char* sQ = sQb + par * TILEB;
-    const char* sO = sOb + par * TILEB;
-    // tile k + 1 starts to stream in; everything older than it and the (two, for a full tile)
-    // dQp stores of tile k - 1 - i.e. this tile's DMA - must have landed
-    if (k + 1 < T) {
-      dma(k + 1);
-      if (k == 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // (tile k - 1 was full: not the last)
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    lds_barrier();                       // B0: both tiles complete; the previous dQp tile is stored
-#pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
-      const bool live = 16 * nb + r < nlive;
-      const bf16x4 qlo = *reinterpret_cast<const bf16x4*>(sQ + oD[0] + 8192 * nb);
-      const bf16x4 qhi = *reinterpret_cast<const bf16x4*>(sQ + oD[1] + 8192 * nb);
-      const bf16x4 o0 = *reinterpret_cast<const bf16x4*>(sO + oD[0] + 8192 * nb);
-      const bf16x4 o1 = *reinterpret_cast<const bf16x4*>(sO + oD[1] + 8192 * nb);
-      const bf16x8 qb = cat8(qlo, qhi), dob = cat8(o0, o1);
-      f32x4 dq0 = tof(o0), dq1 = tof(o1);                 // dQp starts as dO (residual Q_)
-      f32x4 p0 = {0.f, 0.f, 0.f, 0.f}, p1 = p0, da0 = p0, da1 = p0;
-      p0 = mfma32(kpa[0], qb, p0);
-      p1 = mfma32(kpa[1], qb, p1);
-      da0 = mfma32(vpa[0], dob, da0);
-      da1 = mfma32(vpa[1], dob, da1);
-      float mx = fmaxf(fmaxf(fmaxf(p0[0], p0[1]), fmaxf(p0[2], p0[3])),
-                       fmaxf(fmaxf(p1[0], p1[1]), fmaxf(p1[2], p1[3])));
-      mx = wave16_max(mx);
-      float sum = 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        p0[e] = __builtin_amdgcn_exp2f((p0[e] - mx) * a.scale_log2e);
-        p1[e] = __builtin_amdgcn_exp2f((p1[e] - mx) * a.scale_log2e);
-        sum += p0[e] + p1[e];
-      }
-      sum = wave16_sum(sum);
-      const float inv = __builtin_amdgcn_rcpf(sum);
-      float delta = 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        p0[e] *= inv;
-        p1[e] *= inv;
-        delta += p0[e] * da0[e] + p1[e] * da1[e];
-      }
-      delta = wave16_sum(delta);
-      f32x4 ds0, ds1;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        ds0[e] = p0[e] * (da0[e] - delta) * a.scale;
-        ds1[e] = p1[e] * (da1[e] - delta) * a.scale;
-      }
-      // wave-private [point][.] images for the sums over points (padding points: P = dS = 0, so
-      // the duplicated rows the DMA fetched for them do not count)
-      const int pt = 16 * nb + r;
-      const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-      *reinterpret_cast<bf16x4*>(myDS + pt * PQ + 8 * g) = pack4(live ? ds0 : zero4);
-      *reinterpret_cast<bf16x4*>(myDS + pt * PQ + 32 + 8 * g) = pack4(live ? ds1 : zero4);
-      *reinterpret_cast<bf16x4*>(myP + pt * PQ + 8 * g) = pack4(live ? p0 : zero4);
-      *reinterpret_cast<bf16x4*>(myP + pt * PQ + 32 + 8 * g) = pack4(live ? p1 : zero4);
-      *reinterpret_cast<bf16x4*>(myQ + pt * PQ + 8 * g) = qlo;
-      *reinterpret_cast<bf16x4*>(myQ + pt * PQ + 32 + 8 * g) = qhi;
-      *reinterpret_cast<bf16x4*>(myO + pt * PQ + 8 * g) = o0;
-      *reinterpret_cast<bf16x4*>(myO + pt * PQ + 32 + 8 * g) = o1;
-      const bf16x8 dsb = pack8(ds0, ds1);
-      dq0 = mfma32(kta[0], dsb, dq0);
-      dq1 = mfma32(kta[1], dsb, dq1);
-      *reinterpret_cast<bf16x4*>(sOut + oD[0] + 8192 * nb) = pack4(dq0);
-      *reinterpret_cast<bf16x4*>(sOut + oD[1] + 8192 * nb) = pack4(dq1);
-    }
-    bf16x8 qf[2], of[2];
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-      qf[tt] = tr_frag_small(myQ, PQ, 16 * tt, lane);
-      of[tt] = tr_frag_small(myO, PQ, 16 * tt, lane);
-    }
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-      const bf16x8 ads = tr_frag_small(myDS, PQ, 16 * kt, lane);
-      const bf16x8 ap = tr_frag_small(myP, PQ, 16 * kt, lane);
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt) {
-        dkp[kt][tt] = mfma32(ads, qf[tt], dkp[kt][tt]);
-        dvp[kt][tt] = mfma32(ap, of[tt], dvp[kt][tt]);
-      }
-    }
-    lds_barrier();                       // B1: the dQp tile is complete
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int c = tid + 512 * i, row = c >> 5, ch = c & 31;
-      if (row < nlive)
-        *reinterpret_cast<uint4*>(a.dQp + ((int64_t)b * a.N + n0 + row) * D + ch * 8) =
-            *reinterpret_cast<const uint4*>(sOut + oC + 8192 * i);
-    }
-  }
-  const int64_t pbase = ((int64_t)b * a.nparts + part) * MI * D;
-#pragma unroll
-  for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int64_t o = pbase + (int64_t)(16 * kt + 4 * g + e) * D + 32 * j + 16 * tt + r;
-        a.dKpPart[o] = dkp[kt][tt][e];
-        a.dVpPart[o] = dvp[kt][tt][e];
-      }
-}
-
-// k_attn1_bwd3: k_attn1_bwd2 with the fc_o adjoint in front of it (what k_rowgemm<BWD_O> did in
-// a launch of its own): dZ = dY . [Z > 0] ; dO = dY + dZ Wo, the head's 32 columns of dO computed
-// by the wave that consumes them - dO never goes to memory (one [B*N, 256] tensor less written
-// and read per block).  The wave keeps its [32 x 256] slice of Wo^T as MFMA A operands (64
-// registers); the dZ tile is assembled in LDS from the waves' own slices (mask bytes in the
-// forward's layout) and leaves for the weight-gradient pass in full rows.
+// k_attn1_bwd3: fc_o adjoint + attention adjoint of the many-queries block in one launch, WAVE = HEAD,
+// with full-line global traffic.  The workgroup moves whole [32 points][256] tiles: Qp and dY arrive by
+// LDS-DMA (1 KiB per wave instruction, double buffered, swizzled like the single-launch forward's
+// tiles), each wave reads / writes its head's slice of the tiles in LDS, and the dQp tile leaves in
+// 16-byte pieces of full rows.  (With every wave fetching its head's 64-byte slice of each row straight
+// from memory - 16 rows x 32 bytes per load instruction, 8-byte stores - the attention adjoint alone took
+// 243 us at configs[3] for 0.8 GB, 3.3 TB/s.)
+// dZ = dY . [Z > 0] ; dO = dY + dZ Wo: the head's 32 columns of dO are computed by the wave that consumes
+// them - dO never goes to memory.  The wave keeps its [32 x 256] slice of Wo^T as MFMA A operands (64
+// registers); the dZ tile is assembled in LDS from the waves' own slices (mask bytes in the forward's
+// layout) and leaves for the weight-gradient pass in full rows.
 struct Attn1Bwd3Args {
   Attn1BwdArgs base;
   const __bf16* dY;         // [B*N][D]
@@ -898,7 +389,7 @@ __global__ __launch_bounds__(64 * (D / 32), 2) void k_attn1_bwd3(const Attn1Bwd3
       }
 }
 
-// dk[b][i] = sum_p kp[b][p][i] (same for v): the per-range partials of k_attn1_bwd
+// dk[b][i] = sum_p kp[b][p][i] (same for v): the per-range partials of k_attn1_bwd3
 __global__ void k_sum_parts256(const float* __restrict__ kp, const float* __restrict__ vp,
                                float* __restrict__ dk, float* __restrict__ dv, int B, int nparts,
                                int n) {
@@ -2102,8 +1593,8 @@ __global__ __launch_bounds__(64 * (D / 32)) void k_fq_attn_bwd(const FqArgs a) {
   }
 }
 
-// k_fq_attn_bwd2 (m = 32, d = 256): the same arithmetic with full-line global traffic, as
-// k_attn1_bwd2 is to k_attn1_bwd.  The workgroup streams whole [32 keys][256] tiles of Kp and Vp in
+// k_fq_attn_bwd2 (m = 32, d = 256): the same arithmetic as k_fq_attn_bwd with full-line global traffic.
+// The workgroup streams whole [32 keys][256] tiles of Kp and Vp in
 // by LDS-DMA (double buffered), each wave (= head) reads its 64-byte slices from LDS, writes its
 // slices of the dKp / dVp tiles to LDS, and the two tiles leave in 16-byte pieces of full rows -
 // the per-wave form reads 16 rows x 64 bytes per load instruction and writes 8-byte pieces.
@@ -3035,41 +2526,6 @@ __global__ __launch_bounds__(256, 1) void k_pma_bwd256(const PmaArgs a) {
 }  // namespace
 
 // ---- launchers (declared in d256_bf16.hpp) ------------------------------------------------
-int rowgemm256_proj(const __bf16* X, const __bf16* WP, const float* bias, __bf16* Y, int B, int N,
-                    hipStream_t st) {
-  RowGemmArgs a{X, WP, bias, nullptr, nullptr, nullptr, Y, nullptr, B, N, (int)cdiv(N, TP), 0};
-  return launch_rowgemm<RG_PROJ>(a, st);
-}
-int rowgemm256_bwd_o(const __bf16* dY, const uint32_t* mask, const __bf16* WoTP, __bf16* dZ,
-                     __bf16* dO, int B, int N, hipStream_t st) {
-  RowGemmArgs a{dY, WoTP, nullptr, nullptr, mask, nullptr, dO, dZ, B, N, (int)cdiv(N, TP), 0};
-  return launch_rowgemm<RG_BWD_O>(a, st);
-}
-int rowgemm256_dx(const __bf16* G, const __bf16* WTP, __bf16* dX, int B, int N, int accumulate,
-                  hipStream_t st) {
-  RowGemmArgs a{G, WTP, nullptr, nullptr, nullptr, nullptr, dX, nullptr, B, N, (int)cdiv(N, TP),
-                accumulate};
-  return launch_rowgemm<RG_BWD_Q>(a, st);
-}
-int rowgemm256_fwd_o(const __bf16* O, const __bf16* WoP, const float* bo, __bf16* Y, uint32_t* mask,
-                     int B, int N, hipStream_t st) {
-  RowGemmArgs a{O, WoP, bo, nullptr, nullptr, mask, Y, nullptr, B, N, (int)cdiv(N, TP), 0};
-  return launch_rowgemm<RG_FWD_O>(a, st);
-}
-// fp8 (e4m3) operands: W8 = image of s * W written by prep_weight_f8, inv_scale[0] = 1 / s
-int rowgemm256_proj_f8(const __bf16* X, const void* W8, const float* inv_scale, const float* bias,
-                       __bf16* Y, int B, int N, hipStream_t st) {
-  RowGemmArgs a{X, reinterpret_cast<const __bf16*>(W8), bias, inv_scale, nullptr, nullptr, Y,
-                nullptr, B, N, (int)cdiv(N, TP), 0};
-  return launch_rowgemm_nb<RG_PROJ, 2, true>(a, st);
-}
-int rowgemm256_fwd_o_f8(const __bf16* O, const void* W8, const float* inv_scale, const float* bo,
-                        __bf16* Y, uint32_t* mask, int B, int N, hipStream_t st) {
-  RowGemmArgs a{O, reinterpret_cast<const __bf16*>(W8), bo, inv_scale, nullptr, mask, Y, nullptr, B,
-                N, (int)cdiv(N, TP), 0};
-  return launch_rowgemm_nb<RG_FWD_O, 2, true>(a, st);
-}
-
 int attn1_bwd256_parts(int B, int N) {
   // point ranges per set so that B * parts workgroups (2 per CU) cover the chip
   int parts = 1;
@@ -3077,30 +2533,6 @@ int attn1_bwd256_parts(int B, int N) {
   while (parts * 2 <= tiles && B * parts < 512) parts *= 2;
   return parts;
 }
-int attn1_bwd256(const __bf16* dO, const __bf16* QpS, const __bf16* KpP, const __bf16* VpP,
-                 const __bf16* Kt, __bf16* dQp, float* dKpPart, float* dVpPart, float* dKp,
-                 float* dVp, int B, int N, hipStream_t st) {
-  constexpr int D = 256;
-  int parts = attn1_bwd256_parts(B, N);
-  // (k_attn1_bwd2 holds 152 KiB of LDS: one workgroup per CU, so half the ranges of the
-  //  two-per-CU form; the partial buffers are sized for the larger count)
-  if (B * parts > 256 && parts > 1) parts /= 2;
-  const int ppp = (int)cdiv(cdiv(N, 32), parts) * 32;
-  Attn1BwdArgs a{dO, QpS, KpP, VpP, Kt, dQp, dKpPart, dVpPart, B, N, parts, ppp,
-                 1.0f / sqrtf((float)D), 1.4426950408889634f / sqrtf((float)D)};
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn1_bwd2<D>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
-  hipLaunchKernelGGL((k_attn1_bwd2<D>), dim3(B * parts), dim3(64 * (D / 32)),
-                     (size_t)5 * 32 * D * 2 + (size_t)(D / 32) * 4 * 32 * 72, st, a);
-  PCA_TRY(check_launch("k_attn1_bwd"));
-  hipLaunchKernelGGL(k_sum_parts256, dim3((unsigned)cdiv((int64_t)B * 32 * D, 256)), dim3(256), 0,
-                     st, dKpPart, dVpPart, dKp, dVp, B, parts, 32 * D);
-  return check_launch("k_sum_parts256");
-}
-
 // fc_o adjoint + attention adjoint in one launch (k_attn1_bwd3); WoT: transposed natural image
 int attn1_bwd256_fused(const __bf16* dY, const uint32_t* mask, const __bf16* WoT, const __bf16* QpS,
                        const __bf16* KpP, const __bf16* VpP, const __bf16* Kt, __bf16* dZ,
@@ -3169,12 +2601,12 @@ int wgrad256_launch(const Wgrad256Jobs& jobs, void* ws, hipStream_t st) {
   return wgrad256_launch_t(jobs, ws, false, st);
 }
 static bool wgrad256_use_dma() {      // PCA_WGRAD256_DMA=0: the register-staged kernel (A/B measurements)
-  static const bool on = [] { const char* e = getenv("PCA_WGRAD256_DMA"); return !(e && e[0] == '0'); }();
+  static const bool on = env_not_zero("PCA_WGRAD256_DMA");
   return on;
 }
 // May a bf16 job hand over dY + the forward's ReLU mask instead of dZ?  (PCA_D256_DZ_MASK=0: no)
 bool wgrad256_masked_ok(int64_t rows_per_set) {
-  static const bool on = [] { const char* e = getenv("PCA_D256_DZ_MASK"); return !(e && e[0] == '0'); }();
+  static const bool on = env_not_zero("PCA_D256_DZ_MASK");
   return on && wgrad256_use_dma() && rows_per_set % 128 == 0;
 }
 int wgrad256_launch_t(const Wgrad256Jobs& jobs, void* ws, bool f32_operands, hipStream_t st) {
@@ -3261,9 +2693,8 @@ int fq_attn_fwd256(const __bf16* Kp, const __bf16* Vp, const float* Qp, int B, i
   a.scale = 1.0f / sqrtf((float)D);
   a.scale_log2e = 1.4426950408889634f * a.scale;
   const size_t lds = (size_t)(D / 32) * 32 * 72;
-  constexpr bool v1 = false;       // (the per-wave global-traffic form: only for m <= 16 below)
   int S2 = S;
-  if (QT == 2 && !v1) {
+  if (QT == 2) {
     while (S2 > 1 && B * S2 > 256) S2 /= 2;       // 82 KiB of LDS: one workgroup per CU
     a.S = S2;
     static std::once_flag once;
@@ -3272,9 +2703,7 @@ int fq_attn_fwd256(const __bf16* Kp, const __bf16* Vp, const float* Qp, int B, i
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
     hipLaunchKernelGGL(k_fq_attn_fwd2, dim3(B, S2), dim3(512), (size_t)4 * 32 * D * 2 + lds, st, a);
-  } else if (QT == 2) {
-    hipLaunchKernelGGL((k_fq_attn_fwd<D, 2>), dim3(B, S), dim3(512), lds, st, a);
-  } else {
+  } else {          // m <= 16: the per-wave global-traffic form
     hipLaunchKernelGGL((k_fq_attn_fwd<D, 1>), dim3(B, S), dim3(512), lds, st, a);
   }
   PCA_TRY(check_launch("k_fq_attn_fwd"));
@@ -3330,9 +2759,8 @@ int fq_attn_bwd256(const __bf16* Kp, const __bf16* Vp, const float* Qp, const fl
   a.scale = 1.0f / sqrtf((float)D);
   a.scale_log2e = 1.4426950408889634f * a.scale;
   const size_t lds = (size_t)(D / 32) * 32 * 72;
-  constexpr bool v1 = false;       // (the per-wave global-traffic form: only for m <= 16 below)
   int S2 = S;
-  if (QT == 2 && !v1) {
+  if (QT == 2) {
     // full-line traffic through LDS tiles: 114 KiB per workgroup, one per CU - fewer point ranges
     // (the partial buffers are sized for S)
     while (S2 > 1 && B * S2 > 256) S2 /= 2;
@@ -3343,9 +2771,7 @@ int fq_attn_bwd256(const __bf16* Kp, const __bf16* Vp, const float* Qp, const fl
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
     hipLaunchKernelGGL(k_fq_attn_bwd2, dim3(B, S2), dim3(512), (size_t)6 * 32 * D * 2 + lds, st, a);
-  } else if (QT == 2) {
-    hipLaunchKernelGGL((k_fq_attn_bwd<D, 2>), dim3(B, S), dim3(512), lds, st, a);
-  } else {
+  } else {          // m <= 16: the per-wave global-traffic form
     hipLaunchKernelGGL((k_fq_attn_bwd<D, 1>), dim3(B, S), dim3(512), lds, st, a);
   }
   PCA_TRY(check_launch("k_fq_attn_bwd"));

@@ -4,29 +4,9 @@
 
 namespace pca {
 
-// Y = X WP^T + bias   (WP: [256][256] K-permuted image of the nn.Linear weight, prep mode 1)
-int rowgemm256_proj(const __bf16* X, const __bf16* WP, const float* bias, __bf16* Y, int B, int N,
-                    hipStream_t st);
-// Y = O + relu(O Wo^T + bo)  (WoP: prep mode 1 of Wo); mask (nullable): ReLU bits for the backward
-int rowgemm256_fwd_o(const __bf16* O, const __bf16* WoP, const float* bo, __bf16* Y, uint32_t* mask,
-                     int B, int N, hipStream_t st);
-// the same two with fp8 (e4m3) MFMA operands (PCA_MODE_FP8): W8 from prep_weight_f8 (mode 1)
-int rowgemm256_proj_f8(const __bf16* X, const void* W8, const float* inv_scale, const float* bias,
-                       __bf16* Y, int B, int N, hipStream_t st);
-int rowgemm256_fwd_o_f8(const __bf16* O, const void* W8, const float* inv_scale, const float* bo,
-                        __bf16* Y, uint32_t* mask, int B, int N, hipStream_t st);
-// dZ = dY . [Z > 0] (mask bits of k_mab1_fwd) ; dO = dY + dZ Wo   (WoTP: prep mode 2 of Wo)
-int rowgemm256_bwd_o(const __bf16* dY, const uint32_t* mask, const __bf16* WoTP, __bf16* dZ,
-                     __bf16* dO, int B, int N, hipStream_t st);
-// dX (+)= G W   (WTP: prep mode 2 of W)
-int rowgemm256_dx(const __bf16* G, const __bf16* WTP, __bf16* dX, int B, int N, int accumulate,
-                  hipStream_t st);
 // attention adjoint of the many-queries block (m = 32 keys): dQp, and the set's dKp / dVp (fp32,
 // [B][32][256]; the per-range partials are summed into dKp / dVp)
 int attn1_bwd256_parts(int B, int N);
-int attn1_bwd256(const __bf16* dO, const __bf16* QpS, const __bf16* KpP, const __bf16* VpP,
-                 const __bf16* Kt, __bf16* dQp, float* dKpPart, float* dVpPart, float* dKp,
-                 float* dVp, int B, int N, hipStream_t st);
 
 // the whole many-queries block in ONE launch (d256_fused.hip): wave = head, both weight slices in
 // registers.  WqB / WoB: natural bf16 images (prep mode 0); X bf16 [B*N][256] (or fp32 [B*N][dq],
@@ -69,11 +49,10 @@ struct Mab0PrepJobs;
 void mab0_d256_prep_collect(int n, const pca_mab_shape* const* shapes, const float* const* I,
                             const pca_mab_params* params, void* const* saved, Mab0PrepJobs* out);
 void mab0_d256_prep_done(bool on);
-// image modes the d = 256 backward asks for (fc_o / fc_q of the many-queries block, fc_k / fc_v of
-// the few-queries block): they follow the A/B switches of d256_host.hip
-int d256_bwd_wo_mode();
-int d256_bwd_wq_mode();
-int d256_bwd_kv_mode();
+// image mode (prep_weight) of every weight the d = 256 backward takes - fc_o / fc_q of the many-queries
+// block, fc_k / fc_v of the few-queries block: the transposed natural image the register-resident
+// kernels (k_attn1_bwd3, k_rowstream) read
+constexpr int D256_BWD_WMODE = 3;
 void wgrad256_handoff_arm(bool on);
 bool wgrad256_handoff_pending();
 struct DxHandoff {            // mab1's dX = dQp Wq, deferred into the few-queries block's DX launch

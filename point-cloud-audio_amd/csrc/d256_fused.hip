@@ -53,7 +53,6 @@ struct FusedFwdArgs {
 __device__ __forceinline__ int toff(int row, int c16) { return swz(row, c16, ROWB); }
 
 typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
 
 #define PCA_WAIT_VM_CASE(n) case n: asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory"); break;
 __device__ __forceinline__ void wait_vm(int n) {
@@ -167,7 +166,7 @@ __global__ __launch_bounds__(512, 2) void k_isab1_fwd256(const FusedFwdArgs a) {
       // loop (hidden VMEM operations can only make hipcc's own counted waits stricter: the counter
       // retires in order).  M0 = wave-uniform LDS base, written in the statement that uses it.
       const unsigned ldst = __builtin_amdgcn_readfirstlane(
-          (unsigned)(uintptr_t)(lptr_t*)(dst + (DMA_PER_WAVE * j + i) * 1024));
+          (unsigned)(uintptr_t)(lds_void_t*)(dst + (DMA_PER_WAVE * j + i) * 1024));
       unsigned keep;
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
                    "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
@@ -493,7 +492,6 @@ __global__ __launch_bounds__(1024) void k_isab1_fwd256_ab(const FusedFwdArgs a) 
   char* sYb = sOb + 2 * TILEB;              // Y tiles (B only)
   char* sKb = sYb + 2 * TILEB;              // K slices of the current set, wave-private [8][2][64][16 B]
   char* sVb = sKb + TILEB;                  // V slices likewise (16 registers less in role A)
-  constexpr bool VL = true;
   // F8O: the O tile once more as fp8 e4m3 [2][32 points][256 B] (16-byte chunks XOR-swizzled by
   // row): role A converts its slice once, role B's GEMM2 reads fp8 fragments for the K = 128 MFMA
   char* sO8b = sVb + TILEB;
@@ -560,7 +558,7 @@ __global__ __launch_bounds__(1024) void k_isab1_fwd256_ab(const FusedFwdArgs a) 
     //  the tile base is advanced, not recomputed with 64-bit multiplies; LDS
     //  addresses are integers off one base, not pointer casts with their null checks; M0 is read
     //  once before the loop and only restored after a piece)
-    const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t*)smem;
+    const unsigned lds0 = (unsigned)(uintptr_t)(lds_void_t*)smem;
     unsigned m0_keep;
     asm volatile("s_mov_b32 %0, m0" : "=s"(m0_keep));
     int poff[DMA_PER_WAVE], prow[DMA_PER_WAVE];
@@ -648,7 +646,6 @@ __global__ __launch_bounds__(1024) void k_isab1_fwd256_ab(const FusedFwdArgs a) 
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0)
     __syncthreads();                         // biases visible; X tile 0 landed in every wave
     int cur_b = -1;
-    bf16x8 vta[2];
     char* sK = sKb + j * 2048 + lane * 16;   // this lane's 16 bytes of kpa[kt] at + 1024 kt
     char* sV = sVb + j * 2048 + lane * 16;
     int xs = 0;                              // slot of the current unit in the X ring
@@ -674,8 +671,7 @@ __global__ __launch_bounds__(1024) void k_isab1_fwd256_ab(const FusedFwdArgs a) 
                 a.KpP + ((int64_t)b * MI + 16 * kt + r) * D + 32 * j + 8 * g);
             const bf16x8 vt = *reinterpret_cast<const bf16x8*>(
                 a.Vt + ((int64_t)b * D + 32 * j + 16 * kt + r) * MI + 8 * g);
-            if (VL) *reinterpret_cast<bf16x8*>(sV + 1024 * kt) = vt;
-            else vta[kt] = vt;
+            *reinterpret_cast<bf16x8*>(sV + 1024 * kt) = vt;
           }
           cur_b = b;
           __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): before any LDS-DMA of this iteration
@@ -863,8 +859,8 @@ __global__ __launch_bounds__(1024) void k_isab1_fwd256_ab(const FusedFwdArgs a) 
 #pragma unroll
           for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
           const f32x4 sm = mfma32(ones, pb, z4);
-          const f32x4 o0 = mfma32(VL ? *reinterpret_cast<const bf16x8*>(sV) : vta[0], pb, z4);
-          const f32x4 o1 = mfma32(VL ? *reinterpret_cast<const bf16x8*>(sV + 1024) : vta[1], pb, z4);
+          const f32x4 o0 = mfma32(*reinterpret_cast<const bf16x8*>(sV), pb, z4);
+          const f32x4 o1 = mfma32(*reinterpret_cast<const bf16x8*>(sV + 1024), pb, z4);
           const float inv = (abl & 1) ? sm[0] : __builtin_amdgcn_rcpf(sm[0]);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -1132,7 +1128,7 @@ int isab1_fwd256_fused(const void* X, int dq, const __bf16* WqB, const float* Wq
   ProfScope ps(PCA_K_MAB1_FWD, st, 2.0 * pts * ((double)dq * D + (double)D * D + 2.0 * MI * D),
                pts * ((dq <= 4 ? 4.0 : 2.0) * dq + 2.0 * D));
   // PCA_D256_AB=0: the one-role kernel (every wave walks the whole chain; A/B measurements)
-  static const bool ab = [] { const char* e = getenv("PCA_D256_AB"); return !(e && e[0] == '0'); }();
+  static const bool ab = env_not_zero("PCA_D256_AB");
   if (ab) {
     const bool train = OS != nullptr;
     PCA_REQUIRE(!train || mask != nullptr, "isab1_fwd256_fused: training needs the mask buffer");

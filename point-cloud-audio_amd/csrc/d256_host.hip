@@ -28,7 +28,7 @@ inline size_t nelem(const pca_mab_shape& s, bool keys) {
 // =====================================================================================
 struct Mab1D256Ws {
   __bf16 *WoTP, *WqTP;
-  __bf16 *dZ, *dO, *dQp;        // [B*N][D]
+  __bf16 *dZ, *dQp;             // [B*N][D]
   __bf16 *dYb, *Xb, *dXb;       // conversions of fp32 tensors at the ABI (null when bf16)
   float *dKp, *dVp, *dKpPart, *dVpPart;
   void* wg;
@@ -67,7 +67,7 @@ bool mid256_kv_ready() {
 }
 // PCA_D256_MID=0: the five-launch form of round 2 (A/B measurements)
 static bool mid256_on() {
-  static const bool on = [] { const char* e = getenv("PCA_D256_MID"); return !(e && e[0] == '0'); }();
+  static const bool on = env_not_zero("PCA_D256_MID");
   return on;
 }
 void wgrad256_handoff_arm(bool on) {
@@ -75,12 +75,6 @@ void wgrad256_handoff_arm(bool on) {
   if (!on) { g_handoff.has = false; g_handoff.has_dx = false; }
 }
 bool wgrad256_handoff_pending() { return g_handoff.has || g_handoff.has_dx; }
-
-// PCA_ROWSTREAM=0: the LDS-resident-weight row-GEMMs (k_rowgemm) instead of the register-resident
-// streaming ones (d256_stream.hip), for A/B measurements
-static bool rowstream_on() {
-  return true;
-}
 
 static size_t mab1_d256_carve(const pca_mab_shape& s, Mab1D256Ws* out, void* base) {
   Carver c(base);
@@ -90,7 +84,10 @@ static size_t mab1_d256_carve(const pca_mab_shape& s, Mab1D256Ws* out, void* bas
   w.WoTP = c.take<__bf16>((size_t)D * D);
   w.WqTP = c.take<__bf16>((size_t)D * D);
   w.dZ = c.take<__bf16>(M * D);
-  w.dO = c.take<__bf16>(M * D);
+  // (one [B*N][D] block stays reserved here, unused: dO lived in it until the fc_o adjoint moved
+  //  into k_attn1_bwd3.  Giving it back changes mab1_d256_bwd_ws_bytes and pca_st_ws_bytes, whose
+  //  values tests/test_sab_host.py pins (ST_WS, UNCHANGED): drop the block and update both together.)
+  c.take<__bf16>(M * D);
   w.dQp = c.take<__bf16>(M * D);
   if (!abf) {
     w.dYb = c.take<__bf16>(M * D);
@@ -150,14 +147,6 @@ int wgrad256_flush_deferred(BwdDefer& D, hipStream_t st) {
   return wgrad256_launch_t(J, D.wg256_ws, true, st);
 }
 
-// PCA_BWD_O_FUSED=0: fc_o adjoint as its own row-GEMM launch (A/B measurements)
-static bool fuse_o_on() {
-  return true;
-}
-int d256_bwd_wo_mode() { return fuse_o_on() ? 3 : 2; }
-int d256_bwd_wq_mode() { return rowstream_on() ? 3 : 2; }
-int d256_bwd_kv_mode() { return rowstream_on() ? 3 : 2; }
-
 int mab1_d256_bwd(const pca_mab_shape& s, const void* X, const float* Hk, const pca_mab_params& p,
                   const void* saved, const void* dY, void* dX, float* dH, int dk_accumulate,
                   const pca_mab_grads& gr, void* ws, hipStream_t st, BwdDefer* defer) {
@@ -174,12 +163,10 @@ int mab1_d256_bwd(const pca_mab_shape& s, const void* X, const float* Hk, const 
     set_error("mab1_bf16_bwd: dQ for dq <= 4 is not built");
     return PCA_EUNSUPPORTED;
   }
-  // PCA_BWD_O_FUSED=0: fc_o adjoint as its own row-GEMM launch (A/B measurements)
-  const bool fuse_o = fuse_o_on();
   if (want_dx)
-    PCA_TRY(weight_image2(p.wo, &w.WoTP, d256_bwd_wo_mode(), p.wq, &w.WqTP, d256_bwd_wq_mode(), D, D, st));
+    PCA_TRY(weight_image2(p.wo, &w.WoTP, D256_BWD_WMODE, p.wq, &w.WqTP, D256_BWD_WMODE, D, D, st));
   else
-    PCA_TRY(weight_image1(p.wo, &w.WoTP, D, D, d256_bwd_wo_mode(), st));
+    PCA_TRY(weight_image1(p.wo, &w.WoTP, D, D, D256_BWD_WMODE, st));
   const __bf16* dYb = reinterpret_cast<const __bf16*>(dY);
   const __bf16* Xb = small ? nullptr : reinterpret_cast<const __bf16*>(X);
   if (!abf) {
@@ -197,30 +184,22 @@ int mab1_d256_bwd(const pca_mab_shape& s, const void* X, const float* Hk, const 
   const double flops = (double)M * (2.0 * D * D + 8.0 * s.nk * D);
   // dZ = dY . [Z > 0] is read by the fc_o weight-gradient job only: with whole 128-point mask blocks per
   // set that job takes dY and the mask words instead (Wgrad256Job::mask) and dZ is never written
-  const bool dz_masked = fuse_o && wgrad256_masked_ok(s.nq);
+  const bool dz_masked = wgrad256_masked_ok(s.nq);
   const double bytes = (double)M * (2.0 * D + (small ? 4.0 * s.dq : 2.0 * D) + (dz_masked ? 2.0 : 4.0) * D);
   ProfScope ps(PCA_K_MAB1_BWD, st, flops, bytes);
-  if (fuse_o) {
-    // layer 1 (dq <= 4): Qp is recomputed from the points (mab1_saves_qp() == false: not saved)
-    PCA_TRY(attn1_bwd256_fused(dYb, v.mask, w.WoTP, mab1_saves_qp(s) ? v.QpS : nullptr, v.KpP,
-                               v.VpP, v.Kt, dz_masked ? nullptr : w.dZ, w.dQp, w.dKpPart, w.dVpPart, w.dKp, w.dVp, s.B,
-                               s.nq, st, reinterpret_cast<const float*>(X), p.wq, p.bq, s.dq));
-  } else {
-    PCA_TRY(rowgemm256_bwd_o(dYb, v.mask, w.WoTP, w.dZ, w.dO, s.B, s.nq, st));
-    PCA_TRY(attn1_bwd256(w.dO, v.QpS, v.KpP, v.VpP, v.Kt, w.dQp, w.dKpPart, w.dVpPart, w.dKp,
-                         w.dVp, s.B, s.nq, st));
-  }
+  // layer 1 (dq <= 4): Qp is recomputed from the points (mab1_saves_qp() == false: not saved)
+  PCA_TRY(attn1_bwd256_fused(dYb, v.mask, w.WoTP, mab1_saves_qp(s) ? v.QpS : nullptr, v.KpP,
+                             v.VpP, v.Kt, dz_masked ? nullptr : w.dZ, w.dQp, w.dKpPart, w.dVpPart, w.dKp, w.dVp, s.B,
+                             s.nq, st, reinterpret_cast<const float*>(X), p.wq, p.bq, s.dq));
   ps.end();
   if (want_dx) {
     __bf16* dXb = abf ? reinterpret_cast<__bf16*>(dX) : w.dXb;
-    if (rowstream_on() && g_handoff.armed && abf) {
+    if (g_handoff.armed && abf) {
       // deferred: the few-queries block of this ISAB adds its dKp Wk + dVp Wv in the same pass (DX3)
       g_handoff.dx = DxHandoff{w.dQp, w.WqTP, dXb, s.B, s.nq};
       g_handoff.has_dx = true;
-    } else if (rowstream_on()) {
-      PCA_TRY(rowstream256_dx1(w.dQp, w.WqTP, dXb, s.B, s.nq, st));
     } else {
-      PCA_TRY(rowgemm256_dx(w.dQp, w.WqTP, dXb, s.B, s.nq, 0, st));
+      PCA_TRY(rowstream256_dx1(w.dQp, w.WqTP, dXb, s.B, s.nq, st));
     }
     if (!abf) PCA_TRY(cvt_bf16_f32(dXb, reinterpret_cast<float*>(dX), M * D, 0, st));
   }
@@ -405,12 +384,8 @@ int mab0_d256_fwd(const pca_mab_shape& s, const float* I, const void* X, const p
       PCA_TRY(cvt_f32_bf16(reinterpret_cast<const float*>(X), v.Xb, M * D, st));
       Xb = v.Xb;
     }
-    // PCA_FQ_FUSED_FWD=0: projection and attention as two launches (A/B measurements)
-    constexpr bool fq_fused = true;
-    // PCA_FQ_FUSED_F8=0: the fp8 mode on the two-launch form of round 2 (A/B measurements)
-    constexpr bool fq_fused8 = true;
     const bool f8 = s.mode == PCA_MODE_FP8;
-    if ((!f8 || fq_fused8) && rowstream_on() && fq_fused && m > 16) {
+    if (m > 16) {
       // fc_k / fc_v over the keys and the attention in one pass over X (k_fq_proj_fwd)
       const float* inv_kv = invs;
       if (f8) {              // (the engine's one-launch images of the step, when there are any)
@@ -432,33 +407,20 @@ int mab0_d256_fwd(const pca_mab_shape& s, const float* I, const void* X, const p
                                   f8 ? inv_kv : nullptr));                    // modules.py:21,28-29
       ps.end();
     } else {
-    if (s.mode == PCA_MODE_FP8) {           // fc_k / fc_v with fp8 e4m3 operands
-      if (rowstream_on()) {
+      // m <= 16: the projection (one pass over X, weights in registers) and the attention as two launches
+      if (f8) {                                // fc_k / fc_v with fp8 e4m3 operands
         PCA_TRY(prep_weight_f8(p.wk, WkP, D, D, 0, invs, st));
         PCA_TRY(prep_weight_f8(p.wv, WvP, D, D, 0, invs + 1, st));
         PCA_TRY(rowstream256_proj2_f8(Xb, WkP, WvP, invs, p.bk, p.bv, v.Kp, v.Vp, s.B, s.nk, st));
       } else {
-        PCA_TRY(prep_weight_f8(p.wk, WkP, D, D, 1, invs, st));
-        PCA_TRY(prep_weight_f8(p.wv, WvP, D, D, 1, invs + 1, st));
-        PCA_TRY(rowgemm256_proj_f8(Xb, WkP, invs, p.bk, v.Kp, s.B, s.nk, st));
-        PCA_TRY(rowgemm256_proj_f8(Xb, WvP, invs + 1, p.bv, v.Vp, s.B, s.nk, st));
-      }
-    } else {
-      if (rowstream_on()) {                  // one pass over X, weights in registers
         PCA_TRY(weight_image2(p.wk, &WkP, 0, p.wv, &WvP, 0, D, D, st));
         PCA_TRY(rowstream256_proj2(Xb, WkP, WvP, p.bk, p.bv, v.Kp, v.Vp, s.B, s.nk, st));   // modules.py:21
-      } else {
-        PCA_TRY(prep_weight(p.wk, WkP, D, D, 1, st));
-        PCA_TRY(prep_weight(p.wv, WvP, D, D, 1, st));
-        PCA_TRY(rowgemm256_proj(Xb, WkP, p.bk, v.Kp, s.B, s.nk, st));
-        PCA_TRY(rowgemm256_proj(Xb, WvP, p.bv, v.Vp, s.B, s.nk, st));
       }
-    }
-    const double pts = (double)M;
-    ProfScope ps(PCA_K_MAB0_FWD, st, 2.0 * pts * 2.0 * m * D, pts * 4.0 * D);
-    PCA_TRY(fq_attn_fwd256(v.Kp, v.Vp, v.Qp, s.B, s.nk, m, s.k_lengths, v.Op, v.Mp, v.Lp, v.O,
-                           v.LSE, st));                                      // :28-29
-    ps.end();
+      const double pts = (double)M;
+      ProfScope ps(PCA_K_MAB0_FWD, st, 2.0 * pts * 2.0 * m * D, pts * 4.0 * D);
+      PCA_TRY(fq_attn_fwd256(v.Kp, v.Vp, v.Qp, s.B, s.nk, m, s.k_lengths, v.Op, v.Mp, v.Lp, v.O,
+                             v.LSE, st));                                      // :28-29
+      ps.end();
     }
   } else {
     PCA_TRY(mab0_attn_small_launch(reinterpret_cast<const float*>(X), v.Gf, s.B, s.nk, s.h * m,
@@ -600,28 +562,21 @@ int mab0_d256_bwd(const pca_mab_shape& s, const float* I, const void* X, const p
     if (dX != nullptr) {
       const bool f32 = s.k_dtype == PCA_F32;
       __bf16* dXb = f32 ? w.dXb : reinterpret_cast<__bf16*>(dX);
-      if (rowstream_on()) {                  // dKp Wk + dVp Wv in one pass, weights in registers
-        PCA_TRY(weight_image2(p.wk, &w.WkTP, 3, p.wv, &w.WvTP, 3, D, D, st));
-        if (g_handoff.has_dx && !f32 && dk_accumulate && g_handoff.dx.dX == dXb &&
-            g_handoff.dx.B == s.B && g_handoff.dx.N == s.nk) {
-          // ... and mab1's dQp Wq (it would have written dX first; nothing to accumulate onto)
-          g_handoff.has_dx = false;
-          PCA_TRY(rowstream256_dx3(g_handoff.dx.dQp, w.dKp, w.dVp, g_handoff.dx.WqT, w.WkTP, w.WvTP,
-                                   dXb, s.B, s.nk, st));
-        } else {
-          // a pending hand-over that cannot be fused here: mab1's dX has to exist before anything
-          // is accumulated onto it (it used to be written by the later flush,
-          // over this block's sum)
-          if (g_handoff.has_dx) PCA_TRY(wgrad256_handoff_flush_dx(st));
-          PCA_TRY(rowstream256_dx2(w.dKp, w.dVp, w.WkTP, w.WvTP, dXb, s.B, s.nk,
-                                   (!f32 && dk_accumulate) ? 1 : 0, st));
-        }
+      // dKp Wk + dVp Wv in one pass, weights in registers
+      PCA_TRY(weight_image2(p.wk, &w.WkTP, D256_BWD_WMODE, p.wv, &w.WvTP, D256_BWD_WMODE, D, D, st));
+      if (g_handoff.has_dx && !f32 && dk_accumulate && g_handoff.dx.dX == dXb &&
+          g_handoff.dx.B == s.B && g_handoff.dx.N == s.nk) {
+        // ... and mab1's dQp Wq (it would have written dX first; nothing to accumulate onto)
+        g_handoff.has_dx = false;
+        PCA_TRY(rowstream256_dx3(g_handoff.dx.dQp, w.dKp, w.dVp, g_handoff.dx.WqT, w.WkTP, w.WvTP,
+                                 dXb, s.B, s.nk, st));
       } else {
+        // a pending hand-over that cannot be fused here: mab1's dX has to exist before anything
+        // is accumulated onto it (it used to be written by the later flush,
+        // over this block's sum)
         if (g_handoff.has_dx) PCA_TRY(wgrad256_handoff_flush_dx(st));
-        PCA_TRY(prep_weight(p.wk, w.WkTP, D, D, 2, st));
-        PCA_TRY(prep_weight(p.wv, w.WvTP, D, D, 2, st));
-        PCA_TRY(rowgemm256_dx(w.dKp, w.WkTP, dXb, s.B, s.nk, (!f32 && dk_accumulate) ? 1 : 0, st));
-        PCA_TRY(rowgemm256_dx(w.dVp, w.WvTP, dXb, s.B, s.nk, 1, st));
+        PCA_TRY(rowstream256_dx2(w.dKp, w.dVp, w.WkTP, w.WvTP, dXb, s.B, s.nk,
+                                 (!f32 && dk_accumulate) ? 1 : 0, st));
       }
       if (f32)
         PCA_TRY(cvt_bf16_f32(dXb, reinterpret_cast<float*>(dX), M * D, dk_accumulate ? 1 : 0, st));

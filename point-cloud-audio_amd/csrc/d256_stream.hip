@@ -5,10 +5,10 @@
 //     DX2     dX (+)= dKp Wk + dVp Wv                     (their adjoint w.r.t. the keys; one pass)
 //     DX1     dX = dQp Wq                                 (adjoint of fc_q, modules.py:20)
 //     DX3     dX = dQp Wq + dKp Wk + dVp Wv               (both of the above for one ISAB input)
-// k_rowgemm (d256_bf16.hip) keeps the 128 KiB weight image in LDS, which leaves 32 KiB for
-// activations: 32 KiB in flight per CU is 4 TB/s by Little's law, and that is what it measured
-// (3.3 TB/s; PROJ and the dKp / dVp adjoint also ran as two launches each, reading X / re-reading
-// dX twice).  Here, as in k_isab1_fwd256, wave j of 8 owns output features 32 j .. 32 j + 31 and
+// (k_rowgemm, which these replaced and which is gone, kept the 128 KiB weight image in LDS, which
+// left 32 KiB for activations: 32 KiB in flight per CU is 4 TB/s by Little's law, and that is what it
+// measured - 3.3 TB/s; PROJ and the dKp / dVp adjoint also ran as two launches each, reading X /
+// re-reading dX twice.)  Here, as in k_isab1_fwd256, wave j of 8 owns output features 32 j .. 32 j + 31 and
 // holds its [32 x 256] slice of each weight as MFMA A operands (64 registers per weight); LDS holds
 // only [32 points][256] activation tiles: a ring of NBUF tiles per input stream filled by
 // global_load_lds_dwordx4 (1 KiB per wave instruction, swizzled at the source), NBUF - 1 tiles
@@ -37,10 +37,6 @@ struct RowStreamArgs {
   int B, N, tiles_per_set, units_per_wg;
 };
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-__device__ __forceinline__ f32x4 tof(bf16x4 v) {
-  return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-}
 
 #define PCA_WAIT_VM_CASE(n) case n: asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory"); break;
 __device__ __forceinline__ void wait_vm(int n) {

@@ -51,55 +51,6 @@ void ProfScope::end() {
   slot = -1;
 }
 
-// ---- helper stream (see pca_common.h) ------------------------------------------------
-namespace {
-struct SideCtx {
-  bool enabled = false;
-  bool forked = false;
-  hipStream_t side = nullptr;
-  hipEvent_t ev[32] = {};
-  int k = 0;
-  bool init() {          // everything is created on first use (an eager call), never mid-capture
-    if (side != nullptr) return true;
-    if (hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) return false;
-    for (auto& e : ev)
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return false;
-    return true;
-  }
-  hipEvent_t next() {
-    hipEvent_t e = ev[k];
-    k = (k + 1) % 32;
-    return e;
-  }
-};
-thread_local SideCtx g_side;
-}  // namespace
-
-void terminal_enable(bool on) {
-  // the helper stream stays OFF: measured slower on MI355X at every size tried (DESIGN.md 4.4, 4.5;
-  // round 4: the [B*N]-row weight gradients of enc.1 under enc.0's backward, 0.285 against 0.260 ms)
-  constexpr bool allowed = false;
-  g_side.enabled = on && allowed;
-}
-
-hipStream_t terminal_stream(hipStream_t main) {
-  if (!g_side.enabled) return main;
-  if (!g_side.init()) return main;
-  hipEvent_t e = g_side.next();
-  if (hipEventRecord(e, main) != hipSuccess || hipStreamWaitEvent(g_side.side, e, 0) != hipSuccess)
-    return main;
-  g_side.forked = true;
-  return g_side.side;
-}
-
-void terminal_join(hipStream_t main) {
-  if (!g_side.forked) return;
-  hipEvent_t e = g_side.next();
-  (void)hipEventRecord(e, g_side.side);
-  (void)hipStreamWaitEvent(main, e, 0);
-  g_side.forked = false;
-}
-
 namespace {
 
 // ---- sub-wave reductions over G consecutive lanes (G power of two <= 64) ------

@@ -34,22 +34,6 @@ namespace pca {
 
 namespace {
 
-__device__ __forceinline__ int tr_off(int row, int ch) {
-  return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-__device__ __forceinline__ bf16x8 tr_frag(const char* img, int t, int lane) {
-  const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-  const int a0 = tr_off(4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
-  const int a1 = tr_off(16 + 4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a1));
-  const bf16x4 l4 = __builtin_bit_cast(bf16x4, lo), h4 = __builtin_bit_cast(bf16x4, hi);
-  bf16x8 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { r[e] = l4[e]; r[4 + e] = h4[e]; }
-  return r;
-}
 
 // ---------------------------------------------------------------------------------
 // Query-side preparation of up to 3 MABs in ONE launch (they only depend on parameters):

@@ -29,22 +29,6 @@ namespace pca {
 
 namespace {
 
-__device__ __forceinline__ int tr_off(int row, int ch) {
-  return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-__device__ __forceinline__ bf16x8 tr_frag(const char* img, int t, int lane) {
-  const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-  const int a0 = tr_off(4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
-  const int a1 = tr_off(16 + 4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a1));
-  const bf16x4 l4 = __builtin_bit_cast(bf16x4, lo), h4 = __builtin_bit_cast(bf16x4, hi);
-  bf16x8 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { r[e] = l4[e]; r[4 + e] = h4[e]; }
-  return r;
-}
 // [rows][RP] bf16 image (RP*2 bytes per row), 16-byte chunks XOR-swizzled by the row
 template <int RP>
 __device__ __forceinline__ int rp_off(int row, int ch) {
@@ -842,8 +826,8 @@ int pma_head_launch(const pca_mab_shape& s, const pca_mab_params& p, void* saved
   const size_t l3 = (2 * (size_t)m * d + (size_t)Rp + (size_t)d) * sizeof(float);
   lds = lds > l2 ? lds : l2;
   lds = lds > l3 ? lds : l3;
-  constexpr bool v1 = false;       // (the generic k_pma_head serves the shapes k_pma_head1 does not)
-  if (!v1 && d == 128 && dk == 128 && h == 4 && m == 1 && C <= 64 && a.S >= 1 && a.S <= 8)
+  // (the generic k_pma_head serves the shapes k_pma_head1 does not)
+  if (d == 128 && dk == 128 && h == 4 && m == 1 && C <= 64 && a.S >= 1 && a.S <= 8)
     hipLaunchKernelGGL(k_pma_head1, dim3(s.B), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(k_pma_head, dim3(s.B), dim3(256), lds, st, a);
@@ -871,10 +855,9 @@ int terminal_launch(const BwdDefer& D, hipStream_t st, const SlabSumJobs* late_i
     const int need = (int)cdiv(late.j[i].n, 256);
     gx = need > gx ? need : gx;
   }
-  hipStream_t ts = terminal_stream(st);
   hipLaunchKernelGGL(k_terminal1,
                      dim3(gx, J.n + (D.has_cls ? 1 : 0) + (D.has_sw ? 1 : 0) + late.n),
-                     dim3(256), 0, ts, J, D.cls, D.has_cls ? 1 : 0, D.sw, D.has_sw ? 1 : 0, late);
+                     dim3(256), 0, st, J, D.cls, D.has_cls ? 1 : 0, D.sw, D.has_sw ? 1 : 0, late);
   PCA_TRY(check_launch("k_terminal1"));
   // the layer-1 fc_v partials k_terminal1 wrote (slab mode) are summed by rider rows of post 2
   SlabSumJobs late2{};
@@ -883,7 +866,7 @@ int terminal_launch(const BwdDefer& D, hipStream_t st, const SlabSumJobs* late_i
     late2.j[late2.n++] = SlabSumJob{D.sw.slab, D.sw.dW, nwg, n1, 1, stride};
     if (D.sw.db != nullptr) late2.j[late2.n++] = SlabSumJob{D.sw.slab + n1, D.sw.db, nwg, 128, 1, stride};
   }
-  if (J.n == 0) return slab_sum_jobs(late2, ts);
+  if (J.n == 0) return slab_sum_jobs(late2, st);
   int n2 = 0;
   for (int i = 0; i < J.n; ++i) {
     const Mab0PostJob& a = J.j[i];
@@ -891,7 +874,7 @@ int terminal_launch(const BwdDefer& D, hipStream_t st, const SlabSumJobs* late_i
     n2 = e2 > n2 ? e2 : n2;
   }
   for (int i = 0; i < late2.n; ++i) n2 = late2.j[i].n > n2 ? late2.j[i].n : n2;
-  hipLaunchKernelGGL(k_mab0_post2, dim3((unsigned)cdiv(n2, 256), J.n + late2.n), dim3(256), 0, ts, J,
+  hipLaunchKernelGGL(k_mab0_post2, dim3((unsigned)cdiv(n2, 256), J.n + late2.n), dim3(256), 0, st, J,
                      late2);
   return check_launch("k_mab0_post2");
 }
@@ -905,10 +888,9 @@ int mab0_post_launch(const Mab0PostJobs& J, hipStream_t st) {
     n1 = e1 > n1 ? e1 : n1;
     n2 = e2 > n2 ? e2 : n2;
   }
-  hipStream_t ts = terminal_stream(st);     // off the critical path
-  hipLaunchKernelGGL(k_mab0_post1, dim3((unsigned)cdiv(n1, 256), J.n), dim3(256), 0, ts, J);
+  hipLaunchKernelGGL(k_mab0_post1, dim3((unsigned)cdiv(n1, 256), J.n), dim3(256), 0, st, J);
   PCA_TRY(check_launch("k_mab0_post1"));
-  hipLaunchKernelGGL(k_mab0_post2, dim3((unsigned)cdiv(n2, 256), J.n), dim3(256), 0, ts, J,
+  hipLaunchKernelGGL(k_mab0_post2, dim3((unsigned)cdiv(n2, 256), J.n), dim3(256), 0, st, J,
                      SlabSumJobs{});
   return check_launch("k_mab0_post2");
 }
@@ -1086,10 +1068,9 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
         jobs.j[jobs.n++] = WgradJob{w.dO, w.Th + (int64_t)j * Bm * dk, gr.wv,
                                     j == 0 ? gr.bv : nullptr, Bm, j * dh, (j + 1) * dh};
     }
-    hipStream_t ts = terminal_stream(st);
-    PCA_TRY(wgrad128_defer(defer, jobs, false, 64, ts));
+    PCA_TRY(wgrad128_defer(defer, jobs, false, 64, st));
     if (small)
-      PCA_TRY(wgrad_small_f32_launch(w.dO, w.Th, Bm, dk, (int64_t)Bm * dk, gr.wv, gr.bv, ts));
+      PCA_TRY(wgrad_small_f32_launch(w.dO, w.Th, Bm, dk, (int64_t)Bm * dk, gr.wv, gr.bv, st));
   }
   // (the sum of dO over the sets is taken inside k_mab0_post1)
   // k_mid_bwd / k_mab0_epi_bwd left dO per set, the post kernel sums it

@@ -848,11 +848,6 @@ int weight_image2(const float* src0, __bf16** dst0, int mode0, const float* src1
   return PCA_OK;
 }
 
-// PCA_D256_FUSED=0: the two-launch form (Q phase + row-GEMM O phase) for A/B measurements
-static bool fused256_on() {
-  return true;        // (the two-launch Q + O form of round 1 still serves fp32 activations)
-}
-
 // Does the training forward save the projected queries?  Not at layer 1 (two or three input
 // columns): there the backward recomputes them from the points - k_mab1_bwd<.., FUSE_WQ> at d = 128,
 // k_attn1_bwd3<256, SMALLQ> at d = 256 with bf16 activations (the fc_o-fused backward).
@@ -864,7 +859,7 @@ bool mab1_saves_qp(const pca_mab_shape& s) {
 }
 
 int mab1_fwd_wo_mode(const pca_mab_shape& s) {
-  return (s.d == 256 && s.y_dtype == PCA_BF16 && fused256_on()) ? 0 : 1;
+  return (s.d == 256 && s.y_dtype == PCA_BF16) ? 0 : 1;
 }
 
 bool mab1_bf16_supported(const pca_mab_shape& s, bool inference) {
@@ -934,17 +929,14 @@ int mab1_bf16_fwd_ex(const pca_mab_shape& s, const void* X, const float* H,
   const bool f8 = s.mode == PCA_MODE_FP8;
   // Which projections take fp8 operands.  Measured on the reference-trained cfg1 model (10 000
   // sets, argmax agreement with the reference's fp32 logits; bf16 mode: 99.97 %):
-  //   fc_o only       99.83 %   <- default: meets the 99.8 % bar of SURVEY.md 8d
-  //   fc_q and fc_o   99.39 %   (PCA_FP8_PROJ=qo): the 4 significant bits of e4m3 on the projected
-  //                             queries perturb the softmax logits of every head
-  constexpr bool f8_q = false;      // (fc_q in fp8 as well fails the 99.8 % bar: not selectable any more)
-  // d = 256, bf16 activations, fc_o in fp8 (the default split): the single-launch kernel
-  const bool f8_fused = f8 && !f8_q && d == 256 && s.y_dtype == PCA_BF16 && fused256_on();
+  //   fc_o only       99.83 %   <- what runs: meets the 99.8 % bar of SURVEY.md 8d
+  //   fc_q and fc_o   99.39 %   the 4 significant bits of e4m3 on the projected queries perturb the
+  //                             softmax logits of every head: fails the bar, not built
+  // d = 256, bf16 activations, fc_o in fp8: the single-launch kernel
+  const bool f8_fused = f8 && d == 256 && s.y_dtype == PCA_BF16;
   if (f8) {
-    // fp8 images of s * Wq (natural) and s * Wo (K-permuted; natural for the single-launch kernel);
-    // bf16 image of Wq when it stays bf16
-    if (!small && f8_q) PCA_TRY(prep_weight_f8(p.wq, WqB, d, d, 0, invs, st));
-    else if (!small) PCA_TRY(weight_image1(p.wq, &WqB, d, d, 0, st));
+    // bf16 image of Wq; fp8 image of s * Wo (K-permuted; natural for the single-launch kernel)
+    if (!small) PCA_TRY(weight_image1(p.wq, &WqB, d, d, 0, st));
     if (f8_fused) {          // (the single-launch kernel takes its inverse scale by pointer: the engine's
                              //  one-launch image of the step, when there is one)
       void* wo8 = WoP;
@@ -1003,17 +995,14 @@ int mab1_bf16_fwd_ex(const pca_mab_shape& s, const void* X, const float* H,
   if (s.nk == 16 && f8) {
     if (small) return abf ? launch_fwd<128, 16, true, true, 0, 2>(a, st)
                           : launch_fwd<128, 16, true, false, 0, 2>(a, st);
-    if (f8_q) return abf ? launch_fwd<128, 16, false, true, 0, 3>(a, st)
-                         : launch_fwd<128, 16, false, false, 0, 3>(a, st);
     return abf ? launch_fwd<128, 16, false, true, 0, 2>(a, st)
                : launch_fwd<128, 16, false, false, 0, 2>(a, st);
   }
   if (s.nk == 16) {
-    // PCA_D128_FUSED=0: the LDS-resident-weight kernel (k_mab1_fwd) instead of the wave = head one
-    constexpr bool fused128 = true;
-    // (d -> d blocks only: at layer 1 - two or three input columns, no X tile to stream - the
-    //  wave = head kernel measured 17.6 us against 17.0)
-    if (abf && fused128 && !small)
+    // d -> d blocks with bf16 activations: the wave = head kernel (d128_fused.hip).  Layer 1 - two or
+    // three input columns, no X tile to stream - stays on k_mab1_fwd: the wave = head kernel measured
+    // 17.6 us against 17.0 there
+    if (abf && !small)
       return isab1_fwd128_fused(X, s.dq, WqB, p.wq, p.bq, v.KpP, v.Vt, WoP, p.bo,
                                 reinterpret_cast<__bf16*>(Y), a.QpS, a.OS, a.mask, s.B, s.nq, st);
     if (abf) return small ? launch_fwd<128, 16, true, true>(a, st)
@@ -1021,36 +1010,21 @@ int mab1_bf16_fwd_ex(const pca_mab_shape& s, const void* X, const float* H,
     return small ? launch_fwd<128, 16, true, false>(a, st)
                  : launch_fwd<128, 16, false, false>(a, st);
   }
-  if (d == 256) {          // Q phase + O phase: O meets in the saved / scratch block
+  if (d == 256) {
     if (small && !abf) return launch_fwd<256, 32, true, false>(a, st);
     a.OS = v.OS;
-    const bool fused256 = fused256_on();
     if (f8_fused)
       return isab1_fwd256_fused(X, s.dq, WqB, p.wq, p.bq, v.KpP, v.Vt, WoP, p.bo,
                                 reinterpret_cast<__bf16*>(Y), a.QpS, training ? v.OS : nullptr,
                                 a.mask, s.B, s.nq, st, inv_o);
-    if (abf && !f8 && fused256) {
+    if (abf) {
       // one launch: wave = head, both weight slices in registers (d256_fused.hip)
       if (img != nullptr) PCA_TRY(prep_weight(p.wo, WoP, d, d, 0, st));   // natural image for this kernel
       return isab1_fwd256_fused(X, s.dq, WqB, p.wq, p.bq, v.KpP, v.Vt, WoP, p.bo,
                                 reinterpret_cast<__bf16*>(Y), a.QpS, training ? v.OS : nullptr,
                                 a.mask, s.B, s.nq, st);
     }
-    if (abf) {
-      // bf16 activations: the O phase is the row-GEMM kernel of d256_bf16.hip (full-line I/O);
-      // layer 1 runs its Q phase without any weight image (8 waves, 32 KiB of LDS)
-      if (small) PCA_TRY((launch_fwd<256, 32, true, true, 1>(a, st)));
-      else if (f8 && f8_q) PCA_TRY((launch_fwd<256, 32, false, true, 1, 1>(a, st)));
-      else PCA_TRY((launch_fwd<256, 32, false, true, 1>(a, st)));
-      const double pts = (double)s.B * s.nq;
-      ProfScope ps(PCA_K_MAB1_FWD, st, 2.0 * pts * d * d, pts * 4.0 * d);
-      const int rc = f8 ? rowgemm256_fwd_o_f8(v.OS, WoP, invs + 1, p.bo, reinterpret_cast<__bf16*>(Y),
-                                              a.mask, s.B, s.nq, st)
-                        : rowgemm256_fwd_o(v.OS, WoP, p.bo, reinterpret_cast<__bf16*>(Y), a.mask,
-                                           s.B, s.nq, st);
-      ps.end();
-      return rc;
-    }
+    // fp32 activations, d -> d: Q phase + O phase, O meets in the saved / scratch block
     PCA_TRY((launch_fwd<256, 32, false, false, 1>(a, st)));
     return launch_fwd<256, 32, false, false, 2>(a, st);
   }

@@ -56,22 +56,6 @@ struct Mab1BwdArgs {
   int dbg_wg;               // PCA_DEBUG_CLOCKS builds: the workgroup whose phase stamps are kept
 };
 
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-// transposed fragment (k = the 32 points of a wave tile) from a small row-major bf16 image
-// with `rb` bytes per row, for the 16 columns starting at col0
-__device__ __forceinline__ bf16x8 tr_frag_small(const char* img, int rb, int col0, int lane) {
-  const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-  const int a0 = (4 * g + q) * rb + (col0 + 4 * p) * 2;
-  const int a1 = (16 + 4 * g + q) * rb + (col0 + 4 * p) * 2;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a1));
-  const bf16x4 l4 = __builtin_bit_cast(bf16x4, lo), h4 = __builtin_bit_cast(bf16x4, hi);
-  bf16x8 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { r[e] = l4[e]; r[4 + e] = h4[e]; }
-  return r;
-}
 
 #ifdef PCA_DEBUG_CLOCKS
 // (kept in scalar registers and written once at the end: a store per stamp would sit in vmcnt and be
@@ -536,27 +520,6 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
 // ---------------------------------------------------------------------------------
 // dW[DG x DA] += G[rows, DG]^T . A[rows, DA]  (+ db[DG] += column sums of G)
 // ---------------------------------------------------------------------------------
-// LDS image of a 32-row tile with 256-byte rows; 16-byte chunk ch of row `row` sits at
-// (cdna_hip_programming.md T10, image (b)): serves the transposed reads conflict-free
-__device__ __forceinline__ int tr_off(int row, int ch) {
-  return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
-
-
-// A/B fragment with k = the 32 points of the tile (k-slot (g, j): j<4 -> point 4g+j,
-// else 16+4g+j-4) for the 16 features of tile t
-__device__ __forceinline__ bf16x8 tr_frag(const char* img, int t, int lane) {
-  const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-  const int a0 = tr_off(4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
-  const int a1 = tr_off(16 + 4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a1));
-  const bf16x4 l4 = __builtin_bit_cast(bf16x4, lo), h4 = __builtin_bit_cast(bf16x4, hi);
-  bf16x8 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { r[e] = l4[e]; r[4 + e] = h4[e]; }
-  return r;
-}
 
 __device__ __forceinline__ bf16x8 load8(const __bf16* p) {
   return *reinterpret_cast<const bf16x8*>(p);
@@ -969,11 +932,9 @@ int wgrad128_defer(BwdDefer* defer, const WgradJobs& jobs, bool bf16, int rows_p
 }
 
 bool wgrad_slabs_on() {          // (read per call: a test switches it between two engines)
-  const char* e = getenv("PCA_WGRAD_SLABS");
-  return !(e != nullptr && e[0] == '0');
+  return env_not_zero("PCA_WGRAD_SLABS");
 }
 int bwd_defer_flush(BwdDefer& D, hipStream_t st) {
-  hipStream_t ts = terminal_stream(st);
   // The sums the post stages read (D.sums: dG of the few-queries blocks) ride in the first
   // weight-gradient launch as extra workgroup rows.  Slab mode (the default when the caller lent
   // room; PCA_WGRAD_SLABS=0 switches back to fp32 atomics): the weight gradients themselves use no
@@ -988,14 +949,14 @@ int bwd_defer_flush(BwdDefer& D, hipStream_t st) {
   if (D.wg_bf16.n > 0) {
     double rows = 0;
     for (int i = 0; i < D.wg_bf16.n; ++i) rows += (double)D.wg_bf16.j[i].M;
-    ProfScope ps(PCA_K_WGRAD, ts, 2.0 * rows * 128 * 128, 4.0 * rows * 128);
+    ProfScope ps(PCA_K_WGRAD, st, 2.0 * rows * 128 * 128, 4.0 * rows * 128);
     // every workgroup costs a 64 KiB slab (16384 atomics without the slabs): aim at ~200
     // workgroups over all jobs (512 rows for one B*N-row job, 1024 for three, ...)
     // (measured at 3 x 65536 rows: 512 -> 41 us, 768 -> 41, 1024 -> 31, 1536 -> 31, 2048 -> 39)
     int rpw = 512 * (int)((rows + 98303.0) / 98304.0);
     rpw = rpw < 512 ? 512 : (rpw > 1024 ? 1024 : rpw);
     WgradSlabs sl{slab_mode ? D.slab_ws : nullptr, D.slab_cap * 3 / 4, &late, &D.sums, 0};
-    PCA_TRY(wgrad128_launch(D.wg_bf16, true, true, rpw, ts, &sl));
+    PCA_TRY(wgrad128_launch(D.wg_bf16, true, true, rpw, st, &sl));
     used = (sl.used + 255) & ~(size_t)255;
     ps.end();
     D.wg_bf16.n = 0;
@@ -1005,13 +966,13 @@ int bwd_defer_flush(BwdDefer& D, hipStream_t st) {
     // 64: 18.7 us, 128: 14.2, 256: 15.3
     WgradSlabs sl{slab_mode ? D.slab_ws + used / sizeof(float) : nullptr, D.slab_cap - used, &late,
                   &D.sums, 0};
-    PCA_TRY(wgrad128_launch(D.wg_f32, false, false, 128, ts, &sl));
+    PCA_TRY(wgrad128_launch(D.wg_f32, false, false, 128, st, &sl));
     used += (sl.used + 255) & ~(size_t)255;
     D.wg_f32.n = 0;
     D.sums.n = 0;
   }
-  if (D.wg256_n > 0) PCA_TRY(wgrad256_flush_deferred(D, ts));
-  PCA_TRY(slab_sum_jobs(D.sums, ts));        // (nobody carried them)
+  if (D.wg256_n > 0) PCA_TRY(wgrad256_flush_deferred(D, st));
+  PCA_TRY(slab_sum_jobs(D.sums, st));        // (nobody carried them)
   D.sums.n = 0;
   for (int i = 0; i < D.late.n; ++i) {
     PCA_REQUIRE(late.n < 40, "bwd_defer_flush: slab-sum table full");
@@ -1090,7 +1051,7 @@ int mab1_bf16_bwd_ex(const pca_mab_shape& s, const void* X, const float* H,
   // dZ = dY . [Z > 0] is read by the fc_o weight-gradient job only: with bf16 gradients and whole
   // 128-point mask blocks per set that job takes dY and the mask words (WgradJob::mask) and dZ is
   // never written (PCA_D128_DZ_MASK=0: the materialised form)
-  static const bool dzm_on = [] { const char* e = getenv("PCA_D128_DZ_MASK"); return !(e && e[0] == '0'); }();
+  static const bool dzm_on = env_not_zero("PCA_D128_DZ_MASK");
   const bool dz_masked = dzm_on && abf && MI == 16 && s.nq % 128 == 0;
   Mab1BwdArgs a{};
   a.dY = dY; a.QpS = v.QpS; a.mask = v.mask; a.KpP = v.KpP; a.VpP = v.VpP; a.Kt = v.Kt;
@@ -1180,12 +1141,11 @@ int mab1_bf16_bwd_ex(const pca_mab_shape& s, const void* X, const float* H,
     else
       jobs.j[jobs.n++] = WgradJob{w.dZ, v.OS, gr.wo, gr.bo, M, 0, 128};
     if (wq_big && abf) jobs.j[jobs.n++] = WgradJob{w.dQp, X, gr.wq, gr.bq, M, 0, 128};
-    hipStream_t ts = terminal_stream(st);
     if (defer != nullptr) {
-      PCA_TRY(wgrad128_defer(defer, jobs, true, rows_per_wg, ts));
+      PCA_TRY(wgrad128_defer(defer, jobs, true, rows_per_wg, st));
     } else {
-      ProfScope ps(PCA_K_WGRAD, ts, 2.0 * jobs.n * M * d * d, 4.0 * jobs.n * M * d);
-      PCA_TRY(wgrad128_launch(jobs, true, true, rows_per_wg, ts));
+      ProfScope ps(PCA_K_WGRAD, st, 2.0 * jobs.n * M * d * d, 4.0 * jobs.n * M * d);
+      PCA_TRY(wgrad128_launch(jobs, true, true, rows_per_wg, st));
       ps.end();
     }
   }
@@ -1200,9 +1160,8 @@ int mab1_bf16_bwd_ex(const pca_mab_shape& s, const void* X, const float* H,
     WgradJobs jobs{};
     jobs.j[0] = WgradJob{w.dQp, X, gr.wq, gr.bq, M, 0, 128};
     jobs.n = 1;
-    hipStream_t ts = terminal_stream(st);
-    ProfScope ps(PCA_K_WGRAD, ts, 2.0 * M * d * d, 6.0 * M * d);
-    PCA_TRY(wgrad128_launch(jobs, true, false, rows_per_wg, ts));
+    ProfScope ps(PCA_K_WGRAD, st, 2.0 * M * d * d, 6.0 * M * d);
+    PCA_TRY(wgrad128_launch(jobs, true, false, rows_per_wg, st));
     ps.end();
   }
   if (!fuse) {

@@ -47,6 +47,58 @@ __device__ __forceinline__ bf16x4 pack4(f32x4 v) {
   return r;
 }
 
+__device__ __forceinline__ bf16x8 cat8(bf16x4 lo, bf16x4 hi) {
+  bf16x8 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { r[e] = lo[e]; r[4 + e] = hi[e]; }
+  return r;
+}
+__device__ __forceinline__ f32x4 tof(bf16x4 v) {
+  return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+}
+// 8 consecutive bf16 of global memory (16-byte aligned) as one operand
+__device__ __forceinline__ bf16x8 gload8(const __bf16* p) {
+  return *reinterpret_cast<const bf16x8*>(p);
+}
+
+// ---- LDS pointers (address space 3) and the transposing LDS read ------------------------------------
+typedef __attribute__((address_space(3))) void lds_void_t;       // destination of an LDS-DMA
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;       // operand of ds_read_tr16_b64
+
+// LDS image of a 32-row tile with 256-byte rows; 16-byte chunk ch of row `row` sits at
+// (cdna_hip_programming.md T10, image (b)): serves the transposed reads conflict-free
+__device__ __forceinline__ int tr_off(int row, int ch) {
+  return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
+}
+// A/B fragment with k = the 32 points of the tile (k-slot (g, j): j<4 -> point 4g+j,
+// else 16+4g+j-4, i.e. perm32(8g + j)) for the 16 features of tile t of a tr_off image
+__device__ __forceinline__ bf16x8 tr_frag(const char* img, int t, int lane) {
+  const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
+  const int a0 = tr_off(4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
+  const int a1 = tr_off(16 + 4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a0));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a1));
+  const bf16x4 l4 = __builtin_bit_cast(bf16x4, lo), h4 = __builtin_bit_cast(bf16x4, hi);
+  bf16x8 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { r[e] = l4[e]; r[4 + e] = h4[e]; }
+  return r;
+}
+// the same fragment from a small row-major bf16 image with `rb` bytes per row (no swizzle), for the
+// 16 columns from col0
+__device__ __forceinline__ bf16x8 tr_frag_small(const char* img, int rb, int col0, int lane) {
+  const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
+  const int a0 = (4 * g + q) * rb + (col0 + 4 * p) * 2;
+  const int a1 = (16 + 4 * g + q) * rb + (col0 + 4 * p) * 2;
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a0));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a1));
+  const bf16x4 l4 = __builtin_bit_cast(bf16x4, lo), h4 = __builtin_bit_cast(bf16x4, hi);
+  bf16x8 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { r[e] = l4[e]; r[4 + e] = h4[e]; }
+  return r;
+}
+
 // ---- fp8 (OCP e4m3) operands: same 16x16x32 shape and (g, j) k-slot structure as bf16, 8 values
 // per lane in two VGPRs (element j = byte j) --------------------------------------------------
 typedef long f8x8;

@@ -22,9 +22,6 @@ namespace {
 
 constexpr int D = 128, MQ = 16, ROWB = 256;
 
-__device__ __forceinline__ bf16x8 gload8(const __bf16* p) {
-  return *reinterpret_cast<const bf16x8*>(p);
-}
 // write one accumulator tile (rows = features 16t+4g+e, col = query r) into a [query][feature]
 // bf16 image
 __device__ __forceinline__ void put_tile(char* img, int t, int r, int g, f32x4 v) {

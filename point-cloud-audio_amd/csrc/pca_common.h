@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <stdarg.h>
 
 #include "pca_hip.h"
@@ -41,6 +42,14 @@ inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// A/B switch read from the environment: on unless the variable starts with '0'.  Callers that read a
+// switch once per process keep the result in a `static const bool`; the ones tests flip in-process call
+// this every time.
+inline bool env_not_zero(const char* name) {
+  const char* e = getenv(name);
+  return !(e != nullptr && e[0] == '0');
+}
+
 // bump allocator over a caller-provided block
 struct Carver {
   char* base;
@@ -62,17 +71,6 @@ struct ProfScope {
   ProfScope(int kernel_id, hipStream_t stream, double flops, double bytes);
   void end();
 };
-
-// ---- helper stream for work that is off the critical path ------------------------------
-// While enabled (by the ST engine, per calling thread), launch sites of terminal gradient
-// reductions call terminal_stream(main): it makes the helper stream wait for everything
-// enqueued on `main` so far (event fork) and returns the helper stream, so the reduction
-// overlaps whatever `main` does next.  terminal_join(main) makes `main` wait for the helper
-// stream.  Both are plain event record / wait operations, so a stream capture of `main`
-// captures the fork and the join as graph edges.  Disabled: returns `main` itself.
-void terminal_enable(bool on);
-hipStream_t terminal_stream(hipStream_t main);
-void terminal_join(hipStream_t main);
 
 // ---- per-thread hand-off state (documented in include/pca_hip.h, "Per-thread state") ----------------
 // Every hand-off between two internal calls of ONE public entry (the step's weight-image table, the

@@ -53,7 +53,6 @@ constexpr int D = 128, MQ = 16, ROWB = 256, NT = 1024;
 __device__ __forceinline__ int y_off(int row, int ch) {
   return 256 * row + 16 * (ch ^ ((((row << 1) & 14) | ((row >> 3) & 1)) ^ (row & 8)));
 }
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 // B operand [k = point (k-slot order of pack8 of two score tiles)][col = feature 16 t + (lane & 15)] of
 // the 32-row image `img`, through the transposing LDS read
 __device__ __forceinline__ bf16x8 y_tr_frag(const char* img, int t, int lane) {
@@ -68,9 +67,6 @@ __device__ __forceinline__ bf16x8 y_tr_frag(const char* img, int t, int lane) {
   for (int e = 0; e < 4; ++e) { r[e] = l4[e]; r[4 + e] = h4[e]; }
   return r;
 }
-__device__ __forceinline__ bf16x8 gload8(const __bf16* p) {
-  return *reinterpret_cast<const bf16x8*>(p);
-}
 // accumulator tile (rows = features 16 t + 4 g + e, col = query r) -> [query][feature] bf16 image
 __device__ __forceinline__ void put_tile(char* img, int t, int r, int g, f32x4 v) {
   *reinterpret_cast<bf16x4*>(img + swz(r, 2 * t + (g >> 1), ROWB) + 8 * (g & 1)) = pack4(v);
@@ -82,11 +78,10 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 }
-// max as ONE instruction (v_med3_f32 with +inf; fmaxf costs a canonicalising v_max x, x in front).
-// A builtin, NOT inline asm: hipcc's hazard recognizer does not look inside asm, and a VALU
-// instruction reading an MFMA result needs wait states it would not insert (the first version of this
-// kernel read the accumulators of the mid stage one instruction after the MFMA - and got the old value)
-__device__ __forceinline__ float maxf(float x, float y) { return __builtin_amdgcn_fmed3f(x, y, INFINITY); }
+// max0 (as max_nn of mfma_common.hpp): ONE instruction (v_med3_f32 with +inf; fmaxf costs a canonicalising
+// v_max x, x in front).  A builtin, NOT inline asm: hipcc's hazard recognizer does not look inside asm, and
+// a VALU instruction reading an MFMA result needs wait states it would not insert (the first version of
+// this kernel read the accumulators of the mid stage one instruction after the MFMA - and got the old value)
 __device__ __forceinline__ float max0(float x) { return __builtin_amdgcn_fmed3f(x, 0.f, INFINITY); }
 // bits = 2 bits + (z > 0)
 __device__ __forceinline__ uint32_t push_gt0(uint32_t bits, float z) {
@@ -374,7 +369,7 @@ __device__ __forceinline__ void mab1_phase(const Set128Layer& L, const Ctx& c, c
       const bf16x8 qb = pack8(acc[0][nb], acc[1][nb]);
       const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
       f32x4 s0 = mfma32(kpa, qb, z4);            // [key 4 g + e][point r]
-      float mx = maxf(maxf(s0[0], s0[1]), maxf(s0[2], s0[3]));
+      float mx = max_nn(max_nn(s0[0], s0[1]), max_nn(s0[2], s0[3]));
       mx = wave16_max(mx);
       float sum = 0.f;
 #pragma unroll
@@ -452,7 +447,7 @@ __device__ __forceinline__ void mab1_phase(const Set128Layer& L, const Ctx& c, c
         for (int e = 3; e >= 0; --e) {
           const float zz = acc[t][nb][e], of = (float)o4[e];
           bits = push_gt0(bits, zz);
-          y[t][e] = maxf(of + zz, of);
+          y[t][e] = max_nn(of + zz, of);
         }
       }
 #pragma unroll
@@ -1021,7 +1016,7 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
       f32x2 sv = gk[0] * *reinterpret_cast<const f32x2*>(px);
 #pragma unroll
       for (int cc = 1; cc < DIN; ++cc) sv += gk[cc] * *reinterpret_cast<const f32x2*>(px + 2 * cc);
-      m = maxf(m, maxf(sv[0], sv[1]));
+      m = max_nn(m, max_nn(sv[0], sv[1]));
     }
     f32x2 l2 = {0.f, 0.f}, t2[DIN];
 #pragma unroll
@@ -1059,7 +1054,7 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
     if (c.wave == 0) {
       float M = -INFINITY;
 #pragma unroll 4
-      for (int p = 0; p < 16; ++p) M = maxf(M, sM[p * 64 + lane]);
+      for (int p = 0; p < 16; ++p) M = max_nn(M, sM[p * 64 + lane]);
       float Ls = 0.f, tt[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
       for (int p = 0; p < 16; ++p) {
@@ -1122,9 +1117,9 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
 #pragma unroll
       for (int pb = 0; pb < 2; ++pb)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) mt = maxf(mt, s[pb][e]);
+        for (int e = 0; e < 4; ++e) mt = max_nn(mt, s[pb][e]);
       mt = wave16_max(mt);
-      const float mnew = maxf(mrow, mt);
+      const float mnew = max_nn(mrow, mt);
       const float alpha = __builtin_amdgcn_exp2f(mrow - mnew);
       float ls = 0.f;
 #pragma unroll
@@ -1158,7 +1153,7 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
     };
     auto take_partial = [&](int slot, int from_wave) {
       const float2 ml = *reinterpret_cast<const float2*>(sML + (from_wave * 16 + r) * 2);
-      const float mn = maxf(mrow, ml.x);
+      const float mn = max_nn(mrow, ml.x);
       const float f1 = __builtin_amdgcn_exp2f(mrow - mn), f2 = __builtin_amdgcn_exp2f(ml.x - mn);
       lrow = lrow * f1 + ml.y * f2;
       mrow = mn;
@@ -1299,7 +1294,7 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
 #pragma unroll
       for (int pb = 0; pb < 2; ++pb)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) mt = maxf(mt, s[pb][e]);
+        for (int e = 0; e < 4; ++e) mt = max_nn(mt, s[pb][e]);
       mrow = wave16_max(mt);
       float ls = 0.f;
 #pragma unroll

@@ -124,9 +124,8 @@ inline bool pma_head_ok(const Shapes& s) { return mab_kind(s.pma) == 2 && s.pma.
 // the set-resident forward (set128_fwd.hip) takes a training step whose blocks are all on the fused
 // d = 128 kernels, whose sets fit one workgroup's LDS and are dense (PCA_SET128=0: the per-block launches)
 inline bool set128_on(const pca_st_config& c, const Shapes& s) {
-  const char* e = getenv("PCA_SET128");          // (read per call: tests compare the two forms in-process)
-  const bool off = e != nullptr && e[0] == '0';
-  return !off && c.mode == PCA_MODE_BF16 && s.act_bf16 &&
+  // (read per call: tests compare the two forms in-process)
+  return env_not_zero("PCA_SET128") && c.mode == PCA_MODE_BF16 && s.act_bf16 &&
          set128_shape_ok(c.B, c.N, c.din, c.d, c.h, c.m, c.k) &&
          isab_bf16_supported(s.m0[0], s.m1[0]) && isab_bf16_supported(s.m0[1], s.m1[1]) &&
          pma_head_ok(s) && s.pma.k_lengths == nullptr;
@@ -137,8 +136,9 @@ struct Ws {
   float *H[2], *Y[2], *P, *logits, *dlogits;
   float *dP, *dY2, *dY1, *dH, *clsws;
   void* scratch;             // forward + PMA backward
-  void* scratch_bw[2];       // backward of enc.0 / enc.1: separate, because their terminal
-                             // reductions run on the helper stream while the main stream moves on
+  void* scratch_bw[2];       // backward of enc.0 / enc.1: separate, because the deferred reductions and
+                             // post stages read each block's operands at the end of the step
+                             // (bwd_defer_flush), after the other layer's backward has run
   void* scratch_pma;         // d = 256: the PMA's backward workspace, kept until the deferred post
                              // stages of all three few-queries blocks have run (else = scratch)
   IsabImg img[2];            // weight images of the two ISABs (fused bf16 path)
@@ -249,13 +249,13 @@ inline int images256_prepare(const pca_st_config& c, const Layout& L, const Shap
       const bool small = s.m1[li].dq <= 4;
       add(pm.wo, mab1_fwd_wo_mode(s.m1[li]));                 // forward: fc_o (and fc_q of a d -> d block)
       if (!small) add(pm.wq, 0);
-      add(pm.wo, d256_bwd_wo_mode());                        // backward
-      if (!small) add(pm.wq, d256_bwd_wq_mode());
+      add(pm.wo, D256_BWD_WMODE);                             // backward
+      if (!small) add(pm.wq, D256_BWD_WMODE);
     }
     if (mab_kind(s.m0[li]) == 2 && s.m0[li].d == 256 && s.m0[li].dk == 256) {
       const pca_mab_params pk = params_at(p, L.mab0[li]);
       add(pk.wk, 0); add(pk.wv, 0);                          // forward: fc_k / fc_v over the keys
-      add(pk.wk, d256_bwd_kv_mode()); add(pk.wv, d256_bwd_kv_mode());
+      add(pk.wk, D256_BWD_WMODE); add(pk.wv, D256_BWD_WMODE);
     }
   }
   // fp8 mode: the e4m3 images of the forward projections (fc_o of the many-queries blocks, fc_k / fc_v of
@@ -284,9 +284,6 @@ inline int images256_prepare(const pca_st_config& c, const Layout& L, const Shap
   else PCA_TRY(prep_jobs_launch(J, st));
   return prep_f8_jobs_launch(F, st);
 }
-
-// the d = 256 few-queries blocks' post stages: one deferred launch pair per step (per block in round 2)
-inline bool defer256_on() { return true; }
 
 int validate(const pca_st_config* c) {
   PCA_REQUIRE(c != nullptr, "st: null config");
@@ -515,14 +512,6 @@ static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, co
   const float* p = params;
   float* g = grads;
   if (logits != nullptr) w.logits = logits;
-  // terminal gradient reductions overlap the critical path on the helper stream; the guard
-  // joins it back into `st` on every exit path
-  struct SideGuard {
-    hipStream_t st;
-    explicit SideGuard(hipStream_t s) : st(s) { pca::terminal_enable(true); }
-    ~SideGuard() { pca::terminal_join(st); pca::terminal_enable(false); }
-  } side_guard(st);
-
   // shared-query gradients of the fused blocks of this call: one pair of launches at the end
   // (their inputs live in per-block workspaces, which stay untouched until then)
   pca::BwdDefer posts{};
@@ -542,16 +531,14 @@ static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, co
   // needs every block's operands in place until then: the hand-over form of enc.1 (its few-queries
   // block works in w.scratch) and a workspace of its own for enc.0's few-queries block
   const bool hand1 = s.m1[1].d == 256 && pca::mab_kind(s.m1[1]) == 1 && pca::mab_kind(s.m0[1]) == 2;
-  const bool defer_wg = w.wg256_def != nullptr && hand1 && pca::defer256_on() &&
+  const bool defer_wg = w.wg256_def != nullptr && hand1 &&
                         pca::mab_kind(s.pma) == 2 && s.pma.d == 256;
   if (defer_wg) posts.wg256_ws = w.wg256_def;
   if (phase != 1) {
     // the set-resident forward runs the head stages in its own tail (PCA_SET128_HEAD=0: as a launch)
-    const char* he = getenv("PCA_SET128_HEAD");
-    const bool fuse_head = pca::set128_on(*c, s) && c->C <= 64 && !(he != nullptr && he[0] == '0');
+    const bool fuse_head = pca::set128_on(*c, s) && c->C <= 64 && pca::env_not_zero("PCA_SET128_HEAD");
     // ... and then the PMA's attention backward too (PCA_SET128_PMABWD=0: k_mab0_bwd, as a launch)
-    const char* pe = getenv("PCA_SET128_PMABWD");
-    const bool pma_bwd = fuse_head && !(pe != nullptr && pe[0] == '0');
+    const bool pma_bwd = fuse_head && pca::env_not_zero("PCA_SET128_PMABWD");
     pca::PmaHeadArgs head{};
     if (fuse_head)
       PCA_TRY(pca::pma_head_args(s.pma, pca::params_at(p, L.pma), w.saved[4], w.scratch, w.P,
@@ -576,7 +563,7 @@ static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, co
     PCA_TRY(pca::cls_train_head(w.P, p + L.wc, p + L.bc, labels, c->B, c->d, c->C, grad_scale,
                                 w.logits, w.dlogits, w.dP, g + L.wc, g + L.bc, loss_out, stats,
                                 w.clsws, st, &posts));
-    if (s.pma.d == 256 && pca::mab_kind(s.pma) == 2 && pca::defer256_on())   // post stages deferred
+    if (s.pma.d == 256 && pca::mab_kind(s.pma) == 2)   // post stages deferred
       PCA_TRY(pca::mab0_bf16_bwd_ex(s.pma, p + L.S, w.Y[1], pca::params_at(p, L.pma), w.saved[4],
                                     w.dP, g + L.S, w.dY2, 0, pca::grads_at(g, L.pma),
                                     w.scratch_pma, 0, st, &posts));
@@ -610,7 +597,7 @@ static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, co
     PCA_TRY(pca::mab_bwd_any(s.m1[1], w.Y[0], w.H[1], pca::params_at(p, L.mab1[1]),
                              w.saved[3], w.dY2, w.dY1, w.dH, 0, pca::grads_at(g, L.mab1[1]),
                              w.scratch_bw[1], st));
-    if (hand && pca::defer256_on())   // (its post stage waits for the flush: w.scratch stays untouched)
+    if (hand)   // (its post stage waits for the flush: w.scratch stays untouched)
       PCA_TRY(pca::mab0_bf16_bwd_ex(s.m0[1], p + L.I[1], w.Y[0], pca::params_at(p, L.mab0[1]),
                                     w.saved[2], w.dH, g + L.I[1], w.dY1, 1,
                                     pca::grads_at(g, L.mab0[1]), w.scratch, 0, st, &posts));
@@ -639,7 +626,7 @@ static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, co
     PCA_TRY(pca::mab_bwd_any(s.m1[0], X, w.H[0], pca::params_at(p, L.mab1[0]), w.saved[1],
                              w.dY1, nullptr, w.dH, 0, pca::grads_at(g, L.mab1[0]),
                              w.scratch_bw[0], st));
-    if (s.m0[0].d == 256 && pca::mab_kind(s.m0[0]) == 2 && pca::defer256_on())
+    if (s.m0[0].d == 256 && pca::mab_kind(s.m0[0]) == 2)
       PCA_TRY(pca::mab0_bf16_bwd_ex(s.m0[0], p + L.I[0], X, pca::params_at(p, L.mab0[0]),
                                     w.saved[0], w.dH, g + L.I[0], nullptr, 0,
                                     pca::grads_at(g, L.mab0[0]),

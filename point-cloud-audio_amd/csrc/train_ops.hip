@@ -208,8 +208,8 @@ int cls_train_head(const float* P, const float* Wc, const float* bc, const int64
     defer->has_cls = 1;
     return PCA_OK;
   }
-  hipLaunchKernelGGL(k_cls_wgrad, dim3(C), dim3(128), 0, terminal_stream(st), dlogits, P, lossv,
-                     corrv, B, d, C, dWc, dbc, loss_out, stats);
+  hipLaunchKernelGGL(k_cls_wgrad, dim3(C), dim3(128), 0, st, dlogits, P, lossv, corrv, B, d, C,
+                     dWc, dbc, loss_out, stats);
   return check_launch("k_cls_wgrad");
 }
 

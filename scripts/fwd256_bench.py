@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """The many-queries block forward at the north-star shape (d=256, 8 heads, m=32 keys), bf16
-activations at the ABI, B=128 sets: the single-launch wave-per-head kernel (PCA_D256_FUSED=0: the
-Q phase + O phase pair).  FLOPs in the reference formulation.  GPU box; used
+activations at the ABI, B=128 sets: the single-launch wave-per-head kernel.  FLOPs in the reference formulation.  GPU box; used
 under rocprofv3 for the kernel-trace / PMC summaries in profiles/."""
 import ctypes as C
 import os

@@ -43,11 +43,10 @@ for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY" "SQ_ACTI
 done
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/sqcfg2/trace -- python3 $R/bench.py --steps 20 --warmup 3 --windows 1 --no-cpu-baseline --no-roofline --no-graph > $O/sqcfg2_trace.log 2>&1
 echo "cfg2 SQ passes done"
-# --- SQ counters: the d=256 forward (single launch, and the two-launch pair it replaced) ---
-for v in fused pair; do
+# --- SQ counters: the d=256 forward (single launch; the two-launch pair it replaced is gone) ---
+for v in fused; do
   D=$O/fwd256_$v
   mkdir -p $D
-  if [ $v = pair ]; then export PCA_D256_FUSED=0; else unset PCA_D256_FUSED; fi
   NS=2048,4096 REPS=10 rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -- python3 $R/scripts/fwd256_bench.py > $D/bench.log 2>&1
   i=0
   for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY" "SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES" "SQ_INSTS_MFMA SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT"; do
@@ -55,5 +54,4 @@ for v in fused pair; do
     NS=2048 REPS=2 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $D/sq_$i -- python3 $R/scripts/fwd256_bench.py > $D/sq_$i.log 2>&1 || echo "fwd256 $v group $i failed"
   done
 done
-unset PCA_D256_FUSED
 echo "all done"

@@ -13,7 +13,10 @@ logits, the loss and the 45 gradients.
   its fused head stages against the per-block launches) in tests/test_gpu_set128.py.
 
 Round 4 removed every other ``PCA_*`` switch of the library (22 of them: the defaults had been the measured
-winners for a round or more; ``k_attn1_bwd`` went with its switch).  What is left, all covered by a test:
+winners for a round or more).  The kernels only those switches could select went with them:
+``k_attn1_bwd`` and ``k_attn1_bwd2``, every ``k_rowgemm`` instantiation (four modes, two wave counts, fp8),
+``k_fq_attn_fwd<256, 2>`` / ``k_fq_attn_bwd<256, 2>``, and the ``k_mab1_fwd`` instantiations for bf16
+activations at d = 256 and for fc_q in fp8.  What is left, all covered by a test:
 PCA_SET128, PCA_SET128_HEAD, PCA_WGRAD_SLABS, PCA_D128_DZ_MASK, PCA_D256_DZ_MASK, PCA_WGRAD256_DMA,
 PCA_D256_MID, PCA_D256_AB (+ PCA_PACK_DEFER in the Python trainer).  PCA_AB_ABLATE / PCA_AB_STAMPSEL /
 PCA_AB_ABREAST / PCA_DBG_WG exist in the diagnostic builds of scripts/experiments only (#ifdef).
