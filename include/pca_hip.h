@@ -66,14 +66,7 @@ enum { PCA_MODE_F32 = 0, PCA_MODE_BF16 = 1, PCA_MODE_FP8 = 2 };
  *   - a deferred pack (pca_pack_defer): armed by the caller, filled by the next cursor pack, consumed by
  *     the next pca_st_forward / pca_st_train_fwd_bwd of the same thread AND stream, or dropped - with an
  *     error - by pca_pack_defer(0);
- *   - the measurement hook (pca_prof_start / pca_prof_stop).
- * Inside one public call the engine hands a few things from one internal stage to the next through
- * thread-local slots (the step's weight-image table, the d = 256 mid-stage arm / ready flags, the
- * query-side "prepared" flag, a weight-gradient job hand-over); they are set and cleared within that
- * call.  pca_mab_fwd / pca_mab_bwd / pca_st_forward / pca_st_train_fwd_bwd check at entry AND at exit
- * that every such slot is empty (PCA_EINVAL naming the slot otherwise), so a forward on the main thread
- * and a backward on the autograd worker thread (SURVEY.md 8b "Threading") can never pick up each
- * other's - or a failed call's - leftovers. */
+ *   - the measurement hook (pca_prof_start / pca_prof_stop). */
 int pca_abi_version(void);
 /* Test aid (no reference counterpart): overwrites the LDS of every CU with NaN bit patterns.
  * The parity tests call it before each case so that a kernel reading LDS it has not written

@@ -53,23 +53,23 @@ size_t mab_bwd_ws_bytes_any(const pca_mab_shape& s) {
                                                      : mab_f32_bwd_ws_bytes(s);
 }
 int mab_fwd_any(const pca_mab_shape& s, const void* Q, const void* K, const pca_mab_params& p,
-                void* Y, void* saved, void* ws, hipStream_t st) {
+                void* Y, void* saved, void* ws, hipStream_t st, int flags, StepCtx* ctx) {
   const int k = mab_kind(s, saved == nullptr);
   if (k == 3) return sd64_fwd(s, (const float*)Q, (const float*)K, p, (float*)Y, ws, st);
-  if (k == 1) return mab1_bf16_fwd(s, Q, (const float*)K, p, Y, saved, ws, st);
-  if (k == 2) return mab0_bf16_fwd(s, (const float*)Q, K, p, (float*)Y, saved, ws, st);
+  if (k == 1) return mab1_bf16_fwd_ex(s, Q, (const float*)K, p, Y, saved, ws, flags, st, nullptr, ctx);
+  if (k == 2) return mab0_bf16_fwd_ex(s, (const float*)Q, K, p, (float*)Y, saved, ws, flags, st, ctx);
   return mab_f32_fwd(s, (const float*)Q, (const float*)K, p, (float*)Y, saved ? saved : ws, st);
 }
 int mab_bwd_any(const pca_mab_shape& s, const void* Q, const void* K, const pca_mab_params& p,
                 const void* saved, const void* dY, void* dQ, void* dK, int dk_accumulate,
-                const pca_mab_grads& g, void* ws, hipStream_t st) {
+                const pca_mab_grads& g, void* ws, hipStream_t st, StepCtx* ctx) {
   const int k = mab_kind(s);
   if (k == 2)
-    return mab0_bf16_bwd(s, (const float*)Q, K, p, saved, (const float*)dY, (float*)dQ, dK,
-                         dk_accumulate, g, ws, st);
+    return mab0_bf16_bwd_ex(s, (const float*)Q, K, p, saved, (const float*)dY, (float*)dQ, dK,
+                            dk_accumulate, g, ws, 0, st, ctx);
   if (k == 1)
-    return mab1_bf16_bwd(s, Q, (const float*)K, p, saved, dY, dQ, (float*)dK, dk_accumulate, g,
-                         ws, st);
+    return mab1_bf16_bwd_ex(s, Q, (const float*)K, p, saved, dY, dQ, (float*)dK, dk_accumulate, g,
+                            ws, 0, st, nullptr, nullptr, 0, nullptr, ctx);
   return mab_f32_bwd(s, (const float*)Q, (const float*)K, p, saved, (const float*)dY,
                      (float*)dQ, (float*)dK, dk_accumulate, g, ws, st);
 }
@@ -99,12 +99,7 @@ static size_t abi_bwd_ws_bytes(const pca_mab_shape& s) {
 }  // namespace pca
 
 namespace pca {
-int handoffs_empty(const char* where, bool pack_allowed) {
-  PCA_REQUIRE(!mid256_pending(), "%s: a d = 256 mid-stage hand-off is pending on this thread", where);
-  PCA_REQUIRE(!mab0_d256_prep_pending(), "%s: a query-side preparation flag is pending on this thread", where);
-  PCA_REQUIRE(!weight_images_active(), "%s: a weight-image table is still registered on this thread", where);
-  PCA_REQUIRE(!wgrad256_handoff_pending(), "%s: a weight-gradient job hand-over is pending on this thread",
-              where);
+int no_stale_pack(const char* where, bool pack_allowed) {
   PCA_REQUIRE(pack_allowed || !pack_pending(),
               "%s: a deferred pack is pending on this thread (only pca_st_forward / pca_st_train_fwd_bwd "
               "consume it)", where);
@@ -144,13 +139,13 @@ size_t pca_mab_bwd_ws_bytes(const pca_mab_shape* s) {
 }
 
 
-// runs the body, then re-checks the hand-offs: nothing may be left behind by this call either
-#define PCA_WITH_HANDOFF_CHECK(where, pack_allowed, call)            \
+// runs the body between two checks that no deferred pack is pending: these calls do not consume one
+#define PCA_WITH_PACK_CHECK(where, call)                             \
   do {                                                               \
-    PCA_TRY(pca::handoffs_empty(where, pack_allowed));              \
+    PCA_TRY(pca::no_stale_pack(where, false));                       \
     const int rc_ = (call);                                          \
     if (rc_ != PCA_OK) return rc_;                                   \
-    return pca::handoffs_empty(where " (exit)", false);             \
+    return pca::no_stale_pack(where " (exit)", false);               \
   } while (0)
 
 int pca_mab_fwd(const pca_mab_shape* s, const void* Q, const void* K,
@@ -165,11 +160,11 @@ int pca_mab_fwd(const pca_mab_shape* s, const void* Q, const void* K,
   PCA_REQUIRE(ws != nullptr || (saved != nullptr && (kind == 0 || kind == 4)),
               "mab_fwd: scratch block required");
   if (kind == 4)
-    PCA_WITH_HANDOFF_CHECK("pca_mab_fwd", false,
-                           pca::mab_f32_fwd(*s, (const float*)Q, (const float*)K, *p, (float*)Y,
-                                            saved ? saved : ws, pca::as_stream(stream), true));
-  PCA_WITH_HANDOFF_CHECK("pca_mab_fwd", false,
-                         pca::mab_fwd_any(*s, Q, K, *p, Y, saved, ws, pca::as_stream(stream)));
+    PCA_WITH_PACK_CHECK("pca_mab_fwd",
+                        pca::mab_f32_fwd(*s, (const float*)Q, (const float*)K, *p, (float*)Y,
+                                         saved ? saved : ws, pca::as_stream(stream), true));
+  PCA_WITH_PACK_CHECK("pca_mab_fwd",
+                      pca::mab_fwd_any(*s, Q, K, *p, Y, saved, ws, pca::as_stream(stream)));
 }
 
 int pca_mab_bwd(const pca_mab_shape* s, const void* Q, const void* K,
@@ -183,13 +178,13 @@ int pca_mab_bwd(const pca_mab_shape* s, const void* Q, const void* K,
   const int kind = pca::abi_kind(*s);
   PCA_TRY(pca::check_f32(s, kind));
   if (kind == 4)
-    PCA_WITH_HANDOFF_CHECK("pca_mab_bwd", false,
-                           pca::mab_f32_bwd(*s, (const float*)Q, (const float*)K, *p, saved, (const float*)dY,
-                                            (float*)dQ, (float*)dK, dk_accumulate, *g, ws,
-                                            pca::as_stream(stream), true));
-  PCA_WITH_HANDOFF_CHECK("pca_mab_bwd", false,
-                         pca::mab_bwd_any(*s, Q, K, *p, saved, dY, dQ, dK, dk_accumulate, *g, ws,
-                                          pca::as_stream(stream)));
+    PCA_WITH_PACK_CHECK("pca_mab_bwd",
+                        pca::mab_f32_bwd(*s, (const float*)Q, (const float*)K, *p, saved, (const float*)dY,
+                                         (float*)dQ, (float*)dK, dk_accumulate, *g, ws,
+                                         pca::as_stream(stream), true));
+  PCA_WITH_PACK_CHECK("pca_mab_bwd",
+                      pca::mab_bwd_any(*s, Q, K, *p, saved, dY, dQ, dK, dk_accumulate, *g, ws,
+                                       pca::as_stream(stream)));
 }
 
 int pca_linear_fwd(const float* X, const float* W, const float* b, float* Y, int64_t M,

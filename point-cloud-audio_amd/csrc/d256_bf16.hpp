@@ -37,30 +37,46 @@ bool wgrad256_masked_ok(int64_t rows_per_set);
 int mid256_fwd(const float* O, const float* Wo, const float* bo, const float* Wk, const float* bk,
                const float* Wv, const float* bv, float* Z, float* H, __bf16* KpP, __bf16* VpP,
                __bf16* Kt, __bf16* Vt, int B, hipStream_t st);
-// Armed by the engine around an ISAB's two forward calls (training): the few-queries block then
-// ends in mid256_fwd, which also writes the K / V images of the many-queries block described by
-// (s1, p1, saved1), and that block's forward skips its own projection of H (mid256_kv_ready()).
-void mid256_arm(const pca_mab_shape* s1, const pca_mab_params* p1, void* saved1);
-bool mid256_kv_ready();
-int mab0_d256_prep_all(int n, const pca_mab_shape* const* shapes, const float* const* I,
-                       const pca_mab_params* params, void* const* saved, hipStream_t st);
-// ... or only collected into `out`, for a launch the caller makes together with other preparation jobs
+// The query side (Qp, G: parameters only) of several few-queries blocks collected into `out`, for ONE
+// launch the caller makes together with its other preparation jobs; the blocks' forward calls then take
+// PCA_F_PREP_DONE (training only: the saved blocks must exist)
 struct Mab0PrepJobs;
 void mab0_d256_prep_collect(int n, const pca_mab_shape* const* shapes, const float* const* I,
                             const pca_mab_params* params, void* const* saved, Mab0PrepJobs* out);
-void mab0_d256_prep_done(bool on);
 // image mode (prep_weight) of every weight the d = 256 backward takes - fc_o / fc_q of the many-queries
 // block, fc_k / fc_v of the few-queries block: the transposed natural image the register-resident
 // kernels (k_attn1_bwd3, k_rowstream) read
 constexpr int D256_BWD_WMODE = 3;
-void wgrad256_handoff_arm(bool on);
-bool wgrad256_handoff_pending();
 struct DxHandoff {            // mab1's dX = dQp Wq, deferred into the few-queries block's DX launch
   const __bf16 *dQp, *WqT;
   __bf16* dX;
   int B, N;
 };
-int wgrad256_handoff_flush(void* ws, hipStream_t st);
+// What one engine call (pca_st_train_fwd_bwd, pca_st_forward) hands from one internal stage to the next.
+// It lives on that call's stack and goes down as a nullable pointer: null is a stand-alone block call
+// (pca_mab_fwd / pca_mab_bwd), which converts every image itself, defers nothing and hands nothing over.
+struct StepCtx {
+  const WeightImages* images;   // the step's ready-made weight images (null: converted on the spot)
+  BwdDefer* defer;              // where the block queues its terminal reductions (null: it launches them)
+  // d = 256 training forward, set around an ISAB's few-queries block (saved1 null: not set): that block
+  // then ends in mid256_fwd, which also writes the K / V images of the many-queries block (s1, p1,
+  // saved1), and says so in mid_done; the caller passes PCA_F_KV_READY to that block's forward
+  pca_mab_shape s1;
+  pca_mab_params p1;
+  void* saved1;
+  bool mid_done;
+  // d = 256 backward, armed around an ISAB's pair of calls with separate workspaces for the two blocks
+  // (dQp must outlive mab1's call): mab1's fc_q weight-gradient job {dQp, X} goes to the few-queries
+  // block, whose two jobs {dKp, X}, {dVp, X} read the same X - launched together, the three share each
+  // X tile through the XCD's L2 (k_wgrad256's shared-operand order) - and its dX = dQp Wq likewise
+  bool armed, has, has_dx;
+  Wgrad256Job job;
+  DxHandoff dx;
+};
+inline BwdDefer* defer_of(const StepCtx* c) { return c != nullptr ? c->defer : nullptr; }
+inline const WeightImages* images_of(const StepCtx* c) { return c != nullptr ? c->images : nullptr; }
+// a handed-over job / dX nobody took (the following block was not the projected-keys few-queries one)
+int wgrad256_handoff_flush(StepCtx* ctx, void* ws, hipStream_t st);
 size_t wgrad256_ws_bytes(int njobs, int64_t maxM);
 int wgrad256_launch(const Wgrad256Jobs& jobs, void* ws, hipStream_t st);
 int wgrad256_launch_t(const Wgrad256Jobs& jobs, void* ws, bool f32_operands, hipStream_t st);

@@ -33,48 +33,11 @@ struct Mab1D256Ws {
   float *dKp, *dVp, *dKpPart, *dVpPart;
   void* wg;
 };
-// Hand-over of mab1's fc_q weight-gradient job ({dQp, X}) to the few-queries block of the same ISAB,
-// whose two jobs ({dKp, X}, {dVp, X}) read the same X: launched together, the three share each X tile
-// through the XCD's L2 (k_wgrad256's shared-operand order).  Armed by the engine only, around the
-// pair of calls, with separate workspaces for the two blocks (dQp must outlive mab1's call).
-namespace {
-struct WgHandoff {
-  bool armed = false, has = false, has_dx = false;
-  Wgrad256Job job{};
-  DxHandoff dx{};
-};
-thread_local WgHandoff g_handoff;
-}  // namespace
-namespace {
-struct Mid256Handoff {
-  bool armed = false, ready = false;
-  pca_mab_shape s1{};
-  pca_mab_params p1{};
-  void* saved1 = nullptr;
-};
-thread_local Mid256Handoff g_mid256;
-}  // namespace
-void mid256_arm(const pca_mab_shape* s1, const pca_mab_params* p1, void* saved1) {
-  g_mid256.ready = false;
-  g_mid256.armed = s1 != nullptr && p1 != nullptr && saved1 != nullptr;
-  if (g_mid256.armed) { g_mid256.s1 = *s1; g_mid256.p1 = *p1; g_mid256.saved1 = saved1; }
-}
-bool mid256_pending() { return g_mid256.armed || g_mid256.ready; }
-bool mid256_kv_ready() {
-  const bool r = g_mid256.ready;
-  g_mid256.ready = false;
-  return r;
-}
 // PCA_D256_MID=0: the five-launch form of round 2 (A/B measurements)
 static bool mid256_on() {
   static const bool on = env_not_zero("PCA_D256_MID");
   return on;
 }
-void wgrad256_handoff_arm(bool on) {
-  g_handoff.armed = on;
-  if (!on) { g_handoff.has = false; g_handoff.has_dx = false; }
-}
-bool wgrad256_handoff_pending() { return g_handoff.has || g_handoff.has_dx; }
 
 static size_t mab1_d256_carve(const pca_mab_shape& s, Mab1D256Ws* out, void* base) {
   Carver c(base);
@@ -108,20 +71,18 @@ static size_t mab1_d256_carve(const pca_mab_shape& s, Mab1D256Ws* out, void* bas
   if (out) *out = w;
   return c.off;
 }
-// mab1's deferred dX = dQp Wq, written (not accumulated) now
-static int wgrad256_handoff_flush_dx(hipStream_t st) {
-  if (!g_handoff.has_dx) return PCA_OK;
-  g_handoff.has_dx = false;
-  return rowstream256_dx1(g_handoff.dx.dQp, g_handoff.dx.WqT, g_handoff.dx.dX, g_handoff.dx.B,
-                          g_handoff.dx.N, st);
+// mab1's handed-over dX = dQp Wq, written (not accumulated) now
+static int wgrad256_handoff_flush_dx(StepCtx* ctx, hipStream_t st) {
+  if (!ctx->has_dx) return PCA_OK;
+  ctx->has_dx = false;
+  return rowstream256_dx1(ctx->dx.dQp, ctx->dx.WqT, ctx->dx.dX, ctx->dx.B, ctx->dx.N, st);
 }
-// a handed-over job nobody took (the following block was not the projected-keys few-queries one)
-int wgrad256_handoff_flush(void* ws, hipStream_t st) {
-  PCA_TRY(wgrad256_handoff_flush_dx(st));
-  if (!g_handoff.has) return PCA_OK;
+int wgrad256_handoff_flush(StepCtx* ctx, void* ws, hipStream_t st) {
+  PCA_TRY(wgrad256_handoff_flush_dx(ctx, st));
+  if (!ctx->has) return PCA_OK;
   Wgrad256Jobs jobs{};
-  jobs.j[jobs.n++] = g_handoff.job;
-  g_handoff.has = false;
+  jobs.j[jobs.n++] = ctx->job;
+  ctx->has = false;
   return wgrad256_launch(jobs, ws, st);
 }
 
@@ -149,7 +110,7 @@ int wgrad256_flush_deferred(BwdDefer& D, hipStream_t st) {
 
 int mab1_d256_bwd(const pca_mab_shape& s, const void* X, const float* Hk, const pca_mab_params& p,
                   const void* saved, const void* dY, void* dX, float* dH, int dk_accumulate,
-                  const pca_mab_grads& gr, void* ws, hipStream_t st, BwdDefer* defer) {
+                  const pca_mab_grads& gr, void* ws, hipStream_t st, StepCtx* ctx) {
   PCA_REQUIRE(s.d == D && s.nk == 32 && s.h == H8, "mab1_d256_bwd: shape");
   Bf16OperandScope ops(1);             // the [B*m]-row GEMMs of the K / V tail: MFMA
   Mab1Saved v;
@@ -159,14 +120,16 @@ int mab1_d256_bwd(const pca_mab_shape& s, const void* X, const float* Hk, const 
   const int64_t M = (int64_t)s.B * s.nq;
   const bool small = s.dq <= 4, abf = s.y_dtype == PCA_BF16;
   const bool want_dx = dX != nullptr;
+  const bool hand = ctx != nullptr && ctx->armed && abf;       // fc_q's job and dX are handed over (StepCtx)
   if (want_dx && small) {
     set_error("mab1_bf16_bwd: dQ for dq <= 4 is not built");
     return PCA_EUNSUPPORTED;
   }
   if (want_dx)
-    PCA_TRY(weight_image2(p.wo, &w.WoTP, D256_BWD_WMODE, p.wq, &w.WqTP, D256_BWD_WMODE, D, D, st));
+    PCA_TRY(weight_image2(images_of(ctx), p.wo, &w.WoTP, D256_BWD_WMODE, p.wq, &w.WqTP, D256_BWD_WMODE,
+                          D, D, st));
   else
-    PCA_TRY(weight_image1(p.wo, &w.WoTP, D, D, D256_BWD_WMODE, st));
+    PCA_TRY(weight_image1(images_of(ctx), p.wo, &w.WoTP, D, D, D256_BWD_WMODE, st));
   const __bf16* dYb = reinterpret_cast<const __bf16*>(dY);
   const __bf16* Xb = small ? nullptr : reinterpret_cast<const __bf16*>(X);
   if (!abf) {
@@ -194,10 +157,10 @@ int mab1_d256_bwd(const pca_mab_shape& s, const void* X, const float* Hk, const 
   ps.end();
   if (want_dx) {
     __bf16* dXb = abf ? reinterpret_cast<__bf16*>(dX) : w.dXb;
-    if (g_handoff.armed && abf) {
+    if (hand) {
       // deferred: the few-queries block of this ISAB adds its dKp Wk + dVp Wv in the same pass (DX3)
-      g_handoff.dx = DxHandoff{w.dQp, w.WqTP, dXb, s.B, s.nq};
-      g_handoff.has_dx = true;
+      ctx->dx = DxHandoff{w.dQp, w.WqTP, dXb, s.B, s.nq};
+      ctx->has_dx = true;
     } else {
       PCA_TRY(rowstream256_dx1(w.dQp, w.WqTP, dXb, s.B, s.nq, st));
     }
@@ -209,9 +172,9 @@ int mab1_d256_bwd(const pca_mab_shape& s, const void* X, const float* Hk, const 
   else jobs.j[jobs.n++] = Wgrad256Job{w.dZ, v.OS, gr.wo, gr.bo, M};
   if (!small) {
     const Wgrad256Job jq{w.dQp, Xb, gr.wq, gr.bq, M};
-    if (g_handoff.armed && abf) {          // launched by the few-queries block with its own two jobs
-      g_handoff.job = jq;
-      g_handoff.has = true;
+    if (hand) {                            // launched by the few-queries block with its own two jobs
+      ctx->job = jq;
+      ctx->has = true;
     } else {
       jobs.j[jobs.n++] = jq;
     }
@@ -225,7 +188,7 @@ int mab1_d256_bwd(const pca_mab_shape& s, const void* X, const float* Hk, const 
     Wgrad256Jobs kv{};
     kv.j[kv.n++] = Wgrad256Job{w.dKp, Hk, gr.wk, gr.bk, Mk};
     kv.j[kv.n++] = Wgrad256Job{w.dVp, Hk, gr.wv, gr.bv, Mk};
-    PCA_TRY(wgrad256_short(kv, w.wg, defer, st));
+    PCA_TRY(wgrad256_short(kv, w.wg, defer_of(ctx), st));
   }
   if (dH != nullptr) {
     PCA_TRY(linear_dx_acc_f32(w.dKp, p.wk, dH, Mk, D, D, dk_accumulate ? 1 : 0, st));
@@ -311,20 +274,6 @@ static Mab0PrepJob fq_prep_job(const pca_mab_shape& s, const float* I, const pca
   a.Gb = fq_path(s) == FQ_PMA ? v.Gb : nullptr;
   return a;
 }
-// The query side of every few-queries block of a training step (Qp, G: parameters only) in ONE
-// launch at the start of the forward instead of one ~20 us dependent chain per block; the blocks'
-// own forward calls then skip it (engine only: the saved blocks must exist, i.e. training).
-static thread_local bool g_prep256_done = false;
-int mab0_d256_prep_all(int n, const pca_mab_shape* const* shapes, const float* const* I,
-                       const pca_mab_params* params, void* const* saved, hipStream_t st) {
-  Mab0PrepJobs J{};
-  for (int i = 0; i < n; ++i) {
-    Fq256Saved v;
-    fq_carve_saved(*shapes[i], &v, saved[i]);
-    J.j[J.n++] = fq_prep_job(*shapes[i], I[i], params[i], v);
-  }
-  return mab0_prep_launch(J, st);
-}
 void mab0_d256_prep_collect(int n, const pca_mab_shape* const* shapes, const float* const* I,
                             const pca_mab_params* params, void* const* saved, Mab0PrepJobs* out) {
   for (int i = 0; i < n; ++i) {
@@ -333,23 +282,16 @@ void mab0_d256_prep_collect(int n, const pca_mab_shape* const* shapes, const flo
     out->j[out->n++] = fq_prep_job(*shapes[i], I[i], params[i], v);
   }
 }
-void mab0_d256_prep_done(bool on) { g_prep256_done = on; }
-bool mab0_d256_prep_pending() { return g_prep256_done; }
 
-// operand mode of fc_o (and its adjoint) on the [B*m] query rows of a few-queries block:
-// 2 (default) hi + lo bf16 pairs on the MFMA - fp32-level Z, so the ReLU mask is the exact one;
-// PCA_FQ_EPI=bf16: single bf16 operands (round 2; 0.3-0.85 % of dQ elements then differ from the
-// emulation through flipped pre-activations); PCA_FQ_EPI_F32=1: the exact fp32 GEMM (22 us a call)
-static int fq_epi_bf16() {
-  return 2;
-}
+// fc_o (and its adjoint) on the [B*m] query rows: hi + lo bf16 operand pairs - fp32-level Z, exact ReLU mask
+constexpr int FQ_EPI_OPERANDS = 2;
 int mab0_d256_fwd(const pca_mab_shape& s, const float* I, const void* X, const pca_mab_params& p,
-                  float* Hout, void* saved, void* ws, hipStream_t st) {
+                  float* Hout, void* saved, void* ws, int flags, hipStream_t st, StepCtx* ctx) {
   PCA_REQUIRE(mab0_d256_supported(s), "mab0_d256_fwd: unsupported shape");
   PCA_REQUIRE(ws != nullptr, "mab0_d256_fwd: scratch required");
   // fc_o on the [B*m] query rows with bf16 MFMA operands (fp32 accumulation and I/O), as the
   // d = 128 path's k_mid_fwd does: the exact fp32 GEMM was 22 us per call for 0.5 GFLOP
-  Bf16OperandScope ops(fq_epi_bf16());
+  Bf16OperandScope ops(FQ_EPI_OPERANDS);
   Carver cw(ws);
   __bf16* WkP = cw.take<__bf16>((size_t)D * D);
   __bf16* WvP = cw.take<__bf16>((size_t)D * D);
@@ -358,7 +300,7 @@ int mab0_d256_fwd(const pca_mab_shape& s, const float* I, const void* X, const p
   fq_carve_saved(s, &v, saved != nullptr ? saved : (void*)(cw.base + cw.off));
   const int m = s.nq;
   const int64_t Bm = (int64_t)s.B * m, M = (int64_t)s.B * s.nk;
-  if (!g_prep256_done) {   // Qp = I Wq^T + bq (and, layer 1, G = sl2e Qp_h Wk_h): batch invariant
+  if (!(flags & PCA_F_PREP_DONE)) {   // Qp = I Wq^T + bq (and, layer 1, G = sl2e Qp_h Wk_h): batch invariant
     Mab0PrepJobs J{};
     J.j[J.n++] = fq_prep_job(s, I, p, v);
     PCA_TRY(mab0_prep_launch(J, st));
@@ -391,14 +333,14 @@ int mab0_d256_fwd(const pca_mab_shape& s, const float* I, const void* X, const p
       if (f8) {              // (the engine's one-launch images of the step, when there are any)
         void *wk8 = WkP, *wv8 = WvP;
         float *ik = invs, *iv = invs + 1;
-        PCA_TRY(weight_image_f8(p.wk, &wk8, D, D, 0, &ik, st));
-        PCA_TRY(weight_image_f8(p.wv, &wv8, D, D, 0, &iv, st));
+        PCA_TRY(weight_image_f8(images_of(ctx), p.wk, &wk8, D, D, 0, &ik, st));
+        PCA_TRY(weight_image_f8(images_of(ctx), p.wv, &wv8, D, D, 0, &iv, st));
         PCA_REQUIRE(iv == ik + 1, "mab0_d256_fwd: fp8 inverse scales of fc_k / fc_v must be adjacent");
         WkP = reinterpret_cast<decltype(WkP)>(wk8);
         WvP = reinterpret_cast<decltype(WvP)>(wv8);
         inv_kv = ik;
       } else {
-        PCA_TRY(weight_image2(p.wk, &WkP, 0, p.wv, &WvP, 0, D, D, st));
+        PCA_TRY(weight_image2(images_of(ctx), p.wk, &WkP, 0, p.wv, &WvP, 0, D, D, st));
       }
       const double pts = (double)M;
       ProfScope ps(PCA_K_MAB0_FWD, st, 2.0 * pts * (2.0 * D * D + 2.0 * m * D), pts * 2.0 * D);
@@ -413,7 +355,7 @@ int mab0_d256_fwd(const pca_mab_shape& s, const float* I, const void* X, const p
         PCA_TRY(prep_weight_f8(p.wv, WvP, D, D, 0, invs + 1, st));
         PCA_TRY(rowstream256_proj2_f8(Xb, WkP, WvP, invs, p.bk, p.bv, v.Kp, v.Vp, s.B, s.nk, st));
       } else {
-        PCA_TRY(weight_image2(p.wk, &WkP, 0, p.wv, &WvP, 0, D, D, st));
+        PCA_TRY(weight_image2(images_of(ctx), p.wk, &WkP, 0, p.wv, &WvP, 0, D, D, st));
         PCA_TRY(rowstream256_proj2(Xb, WkP, WvP, p.bk, p.bv, v.Kp, v.Vp, s.B, s.nk, st));   // modules.py:21
       }
       const double pts = (double)M;
@@ -427,15 +369,15 @@ int mab0_d256_fwd(const pca_mab_shape& s, const float* I, const void* X, const p
                                    s.dk, v.T, v.LSE, s.k_lengths, st));
     PCA_TRY(epi_small_fwd256(v.T, v.Qp, p.wv, p.bv, s.B, m, s.dk, v.O, st));
   }
-  if (g_mid256.armed && mid256_on() && m == 32 && g_mid256.s1.nk == 32 && g_mid256.s1.d == D &&
-      g_mid256.s1.B == s.B && fq_epi_bf16() == 2) {
+  if (ctx != nullptr && ctx->saved1 != nullptr && mid256_on() && m == 32 && ctx->s1.nk == 32 &&
+      ctx->s1.d == D && ctx->s1.B == s.B) {
     // epilogue + the next block's K / V projections and images in one launch per set (mid256.hip)
     Mab1Saved v1;
-    mab1_carve_saved(g_mid256.s1, &v1, g_mid256.saved1);
-    const pca_mab_params& p1 = g_mid256.p1;
+    mab1_carve_saved(ctx->s1, &v1, ctx->saved1);
+    const pca_mab_params& p1 = ctx->p1;
     PCA_TRY(mid256_fwd(v.O, p.wo, p.bo, p1.wk, p1.bk, p1.wv, p1.bv, v.Z, Hout, v1.KpP, v1.VpP, v1.Kt,
                        v1.Vt, s.B, st));
-    g_mid256.ready = true;
+    ctx->mid_done = true;
     return PCA_OK;
   }
   PCA_TRY(linear_fwd_f32(v.O, p.wo, p.bo, v.Z, Bm, D, D, st));              // :31
@@ -496,12 +438,13 @@ size_t mab0_d256_bwd_ws_bytes(const pca_mab_shape& s) { return fq_carve_bwd(s, n
 // dQ -> dI [m, dq] (ACCUMULATED, may be null), dK -> dX [B, N, dk] (written or accumulated)
 int mab0_d256_bwd(const pca_mab_shape& s, const float* I, const void* X, const pca_mab_params& p,
                   const void* saved, const float* dH, float* dI, void* dX, int dk_accumulate,
-                  const pca_mab_grads& gr, void* ws, hipStream_t st, BwdDefer* defer) {
+                  const pca_mab_grads& gr, void* ws, hipStream_t st, StepCtx* ctx) {
+  BwdDefer* const defer = defer_of(ctx);
   Fq256Saved v;
   fq_carve_saved(s, &v, const_cast<void*>(saved));
   Fq256BwdWs w;
   fq_carve_bwd(s, &w, ws);
-  Bf16OperandScope ops(fq_epi_bf16());       // dO = dH + dZ Wo on the MFMA (see mab0_d256_fwd)
+  Bf16OperandScope ops(FQ_EPI_OPERANDS);     // dO = dH + dZ Wo on the MFMA (see mab0_d256_fwd)
   const int m = s.nq, R = s.h * m;
   const int64_t Bm = (int64_t)s.B * m, M = (int64_t)s.B * s.nk;
   if (s.dk != D && dX != nullptr) {
@@ -563,18 +506,20 @@ int mab0_d256_bwd(const pca_mab_shape& s, const float* I, const void* X, const p
       const bool f32 = s.k_dtype == PCA_F32;
       __bf16* dXb = f32 ? w.dXb : reinterpret_cast<__bf16*>(dX);
       // dKp Wk + dVp Wv in one pass, weights in registers
-      PCA_TRY(weight_image2(p.wk, &w.WkTP, D256_BWD_WMODE, p.wv, &w.WvTP, D256_BWD_WMODE, D, D, st));
-      if (g_handoff.has_dx && !f32 && dk_accumulate && g_handoff.dx.dX == dXb &&
-          g_handoff.dx.B == s.B && g_handoff.dx.N == s.nk) {
+      PCA_TRY(weight_image2(images_of(ctx), p.wk, &w.WkTP, D256_BWD_WMODE, p.wv, &w.WvTP, D256_BWD_WMODE,
+                            D, D, st));
+      const bool has_dx = ctx != nullptr && ctx->has_dx;
+      if (has_dx && !f32 && dk_accumulate && ctx->dx.dX == dXb && ctx->dx.B == s.B &&
+          ctx->dx.N == s.nk) {
         // ... and mab1's dQp Wq (it would have written dX first; nothing to accumulate onto)
-        g_handoff.has_dx = false;
-        PCA_TRY(rowstream256_dx3(g_handoff.dx.dQp, w.dKp, w.dVp, g_handoff.dx.WqT, w.WkTP, w.WvTP,
-                                 dXb, s.B, s.nk, st));
+        ctx->has_dx = false;
+        PCA_TRY(rowstream256_dx3(ctx->dx.dQp, w.dKp, w.dVp, ctx->dx.WqT, w.WkTP, w.WvTP, dXb, s.B,
+                                 s.nk, st));
       } else {
         // a pending hand-over that cannot be fused here: mab1's dX has to exist before anything
         // is accumulated onto it (it used to be written by the later flush,
         // over this block's sum)
-        if (g_handoff.has_dx) PCA_TRY(wgrad256_handoff_flush_dx(st));
+        if (has_dx) PCA_TRY(wgrad256_handoff_flush_dx(ctx, st));
         PCA_TRY(rowstream256_dx2(w.dKp, w.dVp, w.WkTP, w.WvTP, dXb, s.B, s.nk,
                                  (!f32 && dk_accumulate) ? 1 : 0, st));
       }
@@ -584,9 +529,9 @@ int mab0_d256_bwd(const pca_mab_shape& s, const float* I, const void* X, const p
     Wgrad256Jobs jobs{};
     jobs.j[jobs.n++] = Wgrad256Job{w.dKp, Xb, gr.wk, nullptr, M};
     jobs.j[jobs.n++] = Wgrad256Job{w.dVp, Xb, gr.wv, nullptr, M};
-    if (g_handoff.has && g_handoff.job.A == Xb && g_handoff.job.M == M) {     // mab1's {dQp, X}
-      jobs.j[jobs.n++] = g_handoff.job;
-      g_handoff.has = false;
+    if (ctx != nullptr && ctx->has && ctx->job.A == Xb && ctx->job.M == M) {     // mab1's {dQp, X}
+      jobs.j[jobs.n++] = ctx->job;
+      ctx->has = false;
     }
     PCA_TRY(wgrad256_launch(jobs, w.wg, st));
     pj.DG = nullptr;

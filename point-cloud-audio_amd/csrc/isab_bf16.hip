@@ -2,7 +2,7 @@
 //   forward   mab0 attention partials -> k_mid_fwd (epilogue of mab0 + K/V of mab1) -> mab1
 //   backward  mab1 chain (dX, dKp, dVp) -> batched wgrad -> k_mid_bwd -> mab0 backward
 // Only host code here; kernels live in mab0_*, mab1_*, mid_bf16.hip.
-#include "mab1_bf16.hpp"
+#include "d256_bf16.hpp"
 
 namespace pca {
 
@@ -102,9 +102,11 @@ int isab_bf16_bwd(const pca_mab_shape& s0, const pca_mab_shape& s1, const float*
   Mab0Saved v0;
   mab0_carve_saved(s0, &v0, const_cast<void*>(saved0));
 
+  StepCtx ctx{};
+  ctx.defer = defer;
   int nparts = 0;
   PCA_TRY(mab1_bf16_bwd_ex(s1, X, H, p1, saved1, dY, dX, nullptr, 0, g1, ws1,
-                           PCA_F_SKIP_KV_TAIL, st, &im, nullptr, 0, &nparts, defer));
+                           PCA_F_SKIP_KV_TAIL, st, &im, nullptr, 0, &nparts, &ctx));
   const int64_t Bm = (int64_t)s0.B * m;
   const int Rp = 64;
   MidBwdLaunch L{};
@@ -133,7 +135,7 @@ int isab_bf16_bwd(const pca_mab_shape& s0, const pca_mab_shape& s1, const float*
                                      defer));
   }
   return mab0_bf16_bwd_ex(s0, I, X, p0, saved0, nullptr, dI, dX, dX != nullptr ? 1 : 0, g0, ws0,
-                          PCA_F_SKIP_HEAD | PCA_F_SKIP_WGRAD, st, defer);
+                          PCA_F_SKIP_HEAD | PCA_F_SKIP_WGRAD, st, &ctx);
 }
 
 }  // namespace pca

@@ -907,14 +907,10 @@ size_t mab0_bf16_fwd_ws_bytes(const pca_mab_shape& s) {
   return mab0_carve_saved(s, nullptr, nullptr);
 }
 
-int mab0_bf16_fwd(const pca_mab_shape& s, const float* I, const void* X,
-                  const pca_mab_params& p, float* H, void* saved, void* ws, hipStream_t st) {
-  return mab0_bf16_fwd_ex(s, I, X, p, H, saved, ws, 0, st);
-}
 int mab0_bf16_fwd_ex(const pca_mab_shape& s, const float* I, const void* X,
                      const pca_mab_params& p, float* H, void* saved, void* ws, int flags,
-                     hipStream_t st) {
-  if (s.d == 256) return mab0_d256_fwd(s, I, X, p, H, saved, ws, st);
+                     hipStream_t st, StepCtx* ctx) {
+  if (s.d == 256) return mab0_d256_fwd(s, I, X, p, H, saved, ws, flags, st, ctx);
   PCA_REQUIRE(mab0_bf16_supported(s), "mab0_bf16_fwd: unsupported shape");
   const bool training = saved != nullptr;
   PCA_REQUIRE(training || ws != nullptr, "mab0_bf16_fwd: scratch required");

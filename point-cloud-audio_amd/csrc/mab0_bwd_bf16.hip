@@ -15,7 +15,7 @@
 //   parameter gradients of the epilogue (dWo, dWv, dbo, dbv) are [B*m]-row reductions done with
 //   the fp32 GEMM; k_mab0_post turns sum_b dO and dG into dWk, dWq, dbq, dI.  d(bk) is
 //   identically zero (softmax shift invariance) and is left untouched.
-#include "mab1_bf16.hpp"
+#include "d256_bf16.hpp"
 #include "terminal_bodies.hpp"
 #include "pma_head_bodies.hpp"
 #include "slab_sum_body.hpp"
@@ -939,18 +939,13 @@ size_t mab0_bf16_bwd_ws_bytes(const pca_mab_shape& s) {
 }
 
 // dQ -> dI [m, dq] (ACCUMULATED, may be null), dK -> dX [B, N, dk] (written or accumulated)
-int mab0_bf16_bwd(const pca_mab_shape& s, const float* I, const void* X,
-                  const pca_mab_params& p, const void* saved, const float* dH, float* dI,
-                  void* dX, int dk_accumulate, const pca_mab_grads& gr, void* ws,
-                  hipStream_t st) {
-  return mab0_bf16_bwd_ex(s, I, X, p, saved, dH, dI, dX, dk_accumulate, gr, ws, 0, st);
-}
 int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
                      const pca_mab_params& p, const void* saved, const float* dH, float* dI,
                      void* dX, int dk_accumulate, const pca_mab_grads& gr, void* ws, int flags,
-                     hipStream_t st, BwdDefer* defer) {
+                     hipStream_t st, StepCtx* ctx) {
   if (s.d == 256)
-    return mab0_d256_bwd(s, I, X, p, saved, dH, dI, dX, dk_accumulate, gr, ws, st, defer);
+    return mab0_d256_bwd(s, I, X, p, saved, dH, dI, dX, dk_accumulate, gr, ws, st, ctx);
+  BwdDefer* const defer = defer_of(ctx);
   Mab0Saved v;
   mab0_carve_saved(s, &v, const_cast<void*>(saved));
   Mab0BwdWs w;

@@ -798,13 +798,10 @@ int prep_weight(const float* src, __bf16* dst, int rows, int cols, int mode, hip
   return check_launch("k_prep_weight");
 }
 
-static thread_local const WeightImages* t_images = nullptr;
-void weight_images_use(const WeightImages* t) { t_images = t; }
-bool weight_images_active() { return t_images != nullptr; }
-static __bf16* image_of(const float* src, int mode, int rows, int cols) {
-  if (t_images == nullptr) return nullptr;
-  for (int i = 0; i < t_images->n; ++i) {
-    const WeightImages::E& e = t_images->e[i];
+static __bf16* image_of(const WeightImages* t, const float* src, int mode, int rows, int cols) {
+  if (t == nullptr) return nullptr;
+  for (int i = 0; i < t->n; ++i) {
+    const WeightImages::E& e = t->e[i];
     if (e.src == src && e.mode == mode && e.rows == rows && e.cols == cols) return e.img;
   }
   return nullptr;
@@ -820,11 +817,11 @@ int prep_f8_jobs_launch(const PrepF8Jobs& J, hipStream_t st) {
                      0, st, J);
   return check_launch("k_prep_weight_f8_jobs");
 }
-int weight_image_f8(const float* src, void** dst, int rows, int cols, int mode, float** inv,
-                    hipStream_t st) {
-  if (t_images != nullptr)
-    for (int i = 0; i < t_images->nf8; ++i) {
-      const WeightImages::F8& e = t_images->f8[i];
+int weight_image_f8(const WeightImages* t, const float* src, void** dst, int rows, int cols, int mode,
+                    float** inv, hipStream_t st) {
+  if (t != nullptr)
+    for (int i = 0; i < t->nf8; ++i) {
+      const WeightImages::F8& e = t->f8[i];
       if (e.src == src && e.mode == mode && e.rows == rows && e.cols == cols) {
         *dst = e.img;
         *inv = e.inv;
@@ -833,14 +830,15 @@ int weight_image_f8(const float* src, void** dst, int rows, int cols, int mode, 
     }
   return prep_weight_f8(src, *dst, rows, cols, mode, *inv, st);
 }
-int weight_image1(const float* src, __bf16** dst, int rows, int cols, int mode, hipStream_t st) {
-  if (__bf16* im = image_of(src, mode, rows, cols)) { *dst = im; return PCA_OK; }
+int weight_image1(const WeightImages* t, const float* src, __bf16** dst, int rows, int cols, int mode,
+                  hipStream_t st) {
+  if (__bf16* im = image_of(t, src, mode, rows, cols)) { *dst = im; return PCA_OK; }
   return prep_weight(src, *dst, rows, cols, mode, st);
 }
-int weight_image2(const float* src0, __bf16** dst0, int mode0, const float* src1, __bf16** dst1,
-                  int mode1, int rows, int cols, hipStream_t st) {
-  __bf16* i0 = image_of(src0, mode0, rows, cols);
-  __bf16* i1 = image_of(src1, mode1, rows, cols);
+int weight_image2(const WeightImages* t, const float* src0, __bf16** dst0, int mode0, const float* src1,
+                  __bf16** dst1, int mode1, int rows, int cols, hipStream_t st) {
+  __bf16* i0 = image_of(t, src0, mode0, rows, cols);
+  __bf16* i1 = image_of(t, src1, mode1, rows, cols);
   if (i0 == nullptr && i1 == nullptr)
     return prep_weight2(src0, *dst0, mode0, src1, *dst1, mode1, rows, cols, st);
   if (i0 != nullptr) *dst0 = i0; else PCA_TRY(prep_weight(src0, *dst0, rows, cols, mode0, st));
@@ -902,14 +900,11 @@ size_t mab1_bf16_fwd_ws_bytes(const pca_mab_shape& s) {
 }
 
 // Q = X [B, nq, dq] fp32, K = H [B, nk, d] fp32 -> Y [B, nq, d] fp32
-int mab1_bf16_fwd(const pca_mab_shape& s, const void* X, const float* H,
-                  const pca_mab_params& p, void* Y, void* saved, void* ws, hipStream_t st) {
-  return mab1_bf16_fwd_ex(s, X, H, p, Y, saved, ws, 0, st);
-}
 int mab1_bf16_fwd_ex(const pca_mab_shape& s, const void* X, const float* H,
                      const pca_mab_params& p, void* Y, void* saved, void* ws, int flags,
-                     hipStream_t st, const IsabImg* img) {
+                     hipStream_t st, const IsabImg* img, const StepCtx* ctx) {
   PCA_REQUIRE(mab1_bf16_supported(s, saved == nullptr), "mab1_bf16_fwd: unsupported shape");
+  const WeightImages* const images = images_of(ctx);
   PCA_REQUIRE(ws != nullptr, "mab1_bf16_fwd: scratch required");
   Carver cw(ws);
   __bf16* WqB = cw.take<__bf16>((size_t)s.d * s.d);
@@ -936,11 +931,11 @@ int mab1_bf16_fwd_ex(const pca_mab_shape& s, const void* X, const float* H,
   const bool f8_fused = f8 && d == 256 && s.y_dtype == PCA_BF16;
   if (f8) {
     // bf16 image of Wq; fp8 image of s * Wo (K-permuted; natural for the single-launch kernel)
-    if (!small) PCA_TRY(weight_image1(p.wq, &WqB, d, d, 0, st));
+    if (!small) PCA_TRY(weight_image1(images, p.wq, &WqB, d, d, 0, st));
     if (f8_fused) {          // (the single-launch kernel takes its inverse scale by pointer: the engine's
                              //  one-launch image of the step, when there is one)
       void* wo8 = WoP;
-      PCA_TRY(weight_image_f8(p.wo, &wo8, d, d, 0, &inv_o, st));
+      PCA_TRY(weight_image_f8(images, p.wo, &wo8, d, d, 0, &inv_o, st));
       WoP = reinterpret_cast<decltype(WoP)>(wo8);
     } else {
       PCA_TRY(prep_weight_f8(p.wo, WoP, d, d, 1, invs + 1, st));
@@ -951,10 +946,9 @@ int mab1_bf16_fwd_ex(const pca_mab_shape& s, const void* X, const float* H,
   } else {
     // (d = 256 with bf16 activations runs k_isab1_fwd256, which takes Wo as a natural image too)
     const int wo_mode = mab1_fwd_wo_mode(s);
-    if (!small) PCA_TRY(weight_image2(p.wq, &WqB, 0, p.wo, &WoP, wo_mode, d, d, st));
-    else PCA_TRY(weight_image1(p.wo, &WoP, d, d, wo_mode, st));
+    if (!small) PCA_TRY(weight_image2(images, p.wq, &WqB, 0, p.wo, &WoP, wo_mode, d, d, st));
+    else PCA_TRY(weight_image1(images, p.wo, &WoP, d, d, wo_mode, st));
   }
-  if (d > 128 && training && mid256_kv_ready()) flags |= PCA_F_KV_READY;   // images written by mid256_fwd
   if (!(flags & PCA_F_KV_READY) && d > 128) {
     // Kp = H Wk^T + bk, Vp = H Wv^T + bv as MFMA products (fp32 accumulation; the operand
     // rounding is an order of magnitude below the bf16 rounding of the images), then the images

@@ -144,9 +144,9 @@ struct PrepJobs {
 int prep_jobs_launch(const PrepJobs& jobs, hipStream_t st);
 // Weight images prepared ahead by the caller (the ST engine: every bf16 image the d = 256 blocks of a
 // training step will ask for, in ONE launch at the start of the step instead of one ~5 us launch per
-// block and direction).  While a table is in use on the calling thread, weight_image1 / 2 redirect
-// *dst to a registered image of (src, mode, rows, cols) instead of converting into *dst; anything
-// not registered is converted as before, so a table can only save launches, never change results.
+// block and direction).  Given a table, weight_image1 / 2 redirect *dst to a registered image of
+// (src, mode, rows, cols) instead of converting into *dst; anything not registered - everything, with a
+// null table - is converted as before, so a table can only save launches, never change results.
 struct WeightImages {
   struct E { const float* src; int mode, rows, cols; __bf16* img; } e[24];
   int n;
@@ -161,12 +161,12 @@ struct PrepF8Jobs {
 int prep_f8_jobs_launch(const PrepF8Jobs& J, hipStream_t st);
 // the registered fp8 image of (src, mode) - *dst and *inv are redirected to it - or a conversion into
 // *dst / *inv on the spot
-int weight_image_f8(const float* src, void** dst, int rows, int cols, int mode, float** inv,
-                    hipStream_t st);
-void weight_images_use(const WeightImages* t);       // thread-local; nullptr ends the scope
-int weight_image1(const float* src, __bf16** dst, int rows, int cols, int mode, hipStream_t st);
-int weight_image2(const float* src0, __bf16** dst0, int mode0, const float* src1, __bf16** dst1,
-                  int mode1, int rows, int cols, hipStream_t st);
+int weight_image_f8(const WeightImages* t, const float* src, void** dst, int rows, int cols, int mode,
+                    float** inv, hipStream_t st);
+int weight_image1(const WeightImages* t, const float* src, __bf16** dst, int rows, int cols, int mode,
+                  hipStream_t st);
+int weight_image2(const WeightImages* t, const float* src0, __bf16** dst0, int mode0, const float* src1,
+                  __bf16** dst1, int mode1, int rows, int cols, hipStream_t st);
 int mab1_fwd_wo_mode(const pca_mab_shape& s);        // image mode of fc_o the mab1 forward asks for
 // the weight images AND the query-side tensors of a step in ONE launch (both depend on the
 // parameters only; blockIdx.y selects the job, the two kinds share the grid)
@@ -190,7 +190,7 @@ size_t mab0_carve_bwd_ws(const pca_mab_shape& s, Mab0BwdWs* out, void* base);
 // flags of the *_ex host entry points used by the fused ISAB path
 enum {
   PCA_F_SKIP_EPILOGUE = 1,   // mab0 fwd: stop after the attention partials (mid_fwd follows)
-  PCA_F_KV_READY = 2,        // mab1 fwd: Kp/Vp images already written (by mid_fwd)
+  PCA_F_KV_READY = 2,        // mab1 fwd: Kp/Vp images already written (by mid_fwd / mid256_fwd)
   PCA_F_SKIP_KV_TAIL = 4,    // mab1 bwd: stop after dKp/dVp (mid_bwd + batched wgrad follow)
   PCA_F_SKIP_HEAD = 8,       // mab0 bwd: dT/Delta images, dZ, dO, dQs already produced
   PCA_F_IMAGES_READY = 16,   // weight images were prepared by the caller (IsabImg)
@@ -316,35 +316,25 @@ bool mab1_bf16_supported(const pca_mab_shape& s, bool inference = false);
 size_t mab1_bf16_saved_bytes(const pca_mab_shape& s);
 size_t mab1_bf16_fwd_ws_bytes(const pca_mab_shape& s);
 size_t mab1_bf16_bwd_ws_bytes(const pca_mab_shape& s);
-int mab1_bf16_fwd(const pca_mab_shape& s, const void* X, const float* H,
-                  const pca_mab_params& p, void* Y, void* saved, void* ws, hipStream_t st);
+// (ctx: what the engine call this block belongs to hands from stage to stage - StepCtx, d256_bf16.hpp;
+//  null in a stand-alone call)
+struct StepCtx;
 int mab1_bf16_fwd_ex(const pca_mab_shape& s, const void* X, const float* H,
                      const pca_mab_params& p, void* Y, void* saved, void* ws, int flags,
-                     hipStream_t st, const IsabImg* img = nullptr);
-int mab1_bf16_bwd(const pca_mab_shape& s, const void* X, const float* H,
-                  const pca_mab_params& p, const void* saved, const void* dY, void* dX,
-                  float* dH, int dk_accumulate, const pca_mab_grads& gr, void* ws,
-                  hipStream_t st);
-struct BwdDefer;
+                     hipStream_t st, const IsabImg* img = nullptr, const StepCtx* ctx = nullptr);
 int mab1_bf16_bwd_ex(const pca_mab_shape& s, const void* X, const float* H,
                      const pca_mab_params& p, const void* saved, const void* dY, void* dX,
                      float* dH, int dk_accumulate, const pca_mab_grads& gr, void* ws, int flags,
                      hipStream_t st, const IsabImg* img = nullptr, float* zero_ptr = nullptr,
-                     int zero_n = 0, int* nparts_out = nullptr, BwdDefer* defer = nullptr);
+                     int zero_n = 0, int* nparts_out = nullptr, StepCtx* ctx = nullptr);
 // fused mab0 / PMA (few shared queries I, many keys X).  X / dX fp32 or bf16 per k_dtype
 bool mab0_bf16_supported(const pca_mab_shape& s);
 size_t mab0_bf16_saved_bytes(const pca_mab_shape& s);
 size_t mab0_bf16_fwd_ws_bytes(const pca_mab_shape& s);
 size_t mab0_bf16_bwd_ws_bytes(const pca_mab_shape& s);
-int mab0_bf16_fwd(const pca_mab_shape& s, const float* I, const void* X,
-                  const pca_mab_params& p, float* H, void* saved, void* ws, hipStream_t st);
 int mab0_bf16_fwd_ex(const pca_mab_shape& s, const float* I, const void* X,
                      const pca_mab_params& p, float* H, void* saved, void* ws, int flags,
-                     hipStream_t st);
-int mab0_bf16_bwd(const pca_mab_shape& s, const float* I, const void* X,
-                  const pca_mab_params& p, const void* saved, const float* dH, float* dI,
-                  void* dX, int dk_accumulate, const pca_mab_grads& gr, void* ws,
-                  hipStream_t st);
+                     hipStream_t st, StepCtx* ctx = nullptr);
 struct ClsWgradArgs {
   const float *dlogits, *P, *lossv, *corrv;
   int B, d, C;
@@ -463,41 +453,42 @@ int terminal_launch(const BwdDefer& D, hipStream_t st, const SlabSumJobs* late =
 // launch `jobs` now, or append them to the matching list of `defer`
 int wgrad128_defer(BwdDefer* defer, const WgradJobs& jobs, bool bf16, int rows_per_wg,
                    hipStream_t st);
-// `defer` non-null: the post job is appended there instead of being launched
+// ctx->defer non-null: the post job is appended there instead of being launched
 int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
                      const pca_mab_params& p, const void* saved, const float* dH, float* dI,
                      void* dX, int dk_accumulate, const pca_mab_grads& gr, void* ws, int flags,
-                     hipStream_t st, BwdDefer* defer = nullptr);
+                     hipStream_t st, StepCtx* ctx = nullptr);
 // d = 256 / 8 heads (d256_host.hip): the many-queries backward and the few-queries block
 size_t mab1_d256_bwd_ws_bytes(const pca_mab_shape& s);
 int mab1_d256_bwd(const pca_mab_shape& s, const void* X, const float* H, const pca_mab_params& p,
                   const void* saved, const void* dY, void* dX, float* dH, int dk_accumulate,
-                  const pca_mab_grads& gr, void* ws, hipStream_t st, BwdDefer* defer = nullptr);
+                  const pca_mab_grads& gr, void* ws, hipStream_t st, StepCtx* ctx);
 bool mab0_d256_supported(const pca_mab_shape& s);
 size_t mab0_d256_saved_bytes(const pca_mab_shape& s);
 size_t mab0_d256_fwd_ws_bytes(const pca_mab_shape& s);
 size_t mab0_d256_bwd_ws_bytes(const pca_mab_shape& s);
 int mab0_d256_fwd(const pca_mab_shape& s, const float* I, const void* X, const pca_mab_params& p,
-                  float* H, void* saved, void* ws, hipStream_t st);
+                  float* H, void* saved, void* ws, int flags, hipStream_t st, StepCtx* ctx);
 int mab0_d256_bwd(const pca_mab_shape& s, const float* I, const void* X, const pca_mab_params& p,
                   const void* saved, const float* dH, float* dI, void* dX, int dk_accumulate,
-                  const pca_mab_grads& gr, void* ws, hipStream_t st, BwdDefer* defer);
+                  const pca_mab_grads& gr, void* ws, hipStream_t st, StepCtx* ctx);
 int small_row_split(int B, int R);
 int mab0_attn_small_launch(const float* X, const float* Gf, int B, int N, int R, int dk, float* T,
                            float* LSE, const int32_t* lengths, hipStream_t st);
 int mab0_bwd_small_launch(const float* X, const float* Gf, const float* dTf, const float* LSE,
                           const float* Delta, int B, int N, int R, int Rp, int dk, float* DG,
                           const int32_t* lengths, hipStream_t st, float* slabs = nullptr);
-// per-block dispatch (api_mab.hip): kind 0 exact fp32, 1 fused mab1, 2 fused mab0
+// per-block dispatch (api_mab.hip): kind 0 exact fp32, 1 fused mab1, 2 fused mab0; flags / ctx go to the
+// fused kinds' *_ex entry points
 int mab_kind(const pca_mab_shape& s, bool inference = false);
 size_t mab_saved_bytes_any(const pca_mab_shape& s);
 size_t mab_fwd_ws_bytes_any(const pca_mab_shape& s);
 size_t mab_bwd_ws_bytes_any(const pca_mab_shape& s);
 int mab_fwd_any(const pca_mab_shape& s, const void* Q, const void* K, const pca_mab_params& p,
-                void* Y, void* saved, void* ws, hipStream_t st);
+                void* Y, void* saved, void* ws, hipStream_t st, int flags = 0, StepCtx* ctx = nullptr);
 int mab_bwd_any(const pca_mab_shape& s, const void* Q, const void* K, const pca_mab_params& p,
                 const void* saved, const void* dY, void* dQ, void* dK, int dk_accumulate,
-                const pca_mab_grads& g, void* ws, hipStream_t st);
+                const pca_mab_grads& g, void* ws, hipStream_t st, StepCtx* ctx = nullptr);
 // fused ISAB (isab_bf16.hip)
 bool isab_bf16_supported(const pca_mab_shape& s0, const pca_mab_shape& s1);
 size_t isab_bf16_fwd_ws_bytes(const pca_mab_shape& s0, const pca_mab_shape& s1);

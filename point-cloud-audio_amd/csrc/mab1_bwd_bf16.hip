@@ -13,7 +13,7 @@
 //                (bias gradients) ride along.
 //   k_kv_grad    per (set, head): dKp = dS^T.Qp, dVp = P^T.dO (m x 32 outputs, N-long sums).
 // The tiny [B*m, d] projections of H (fc_k, fc_v) are differentiated with the fp32 GEMMs.
-#include "mab1_bf16.hpp"
+#include "d256_bf16.hpp"
 #include "terminal_bodies.hpp"
 #include "slab_sum_body.hpp"
 
@@ -1012,19 +1012,14 @@ int kv_dh_launch(const float* dKp, const float* dVp, const float* Wk, const floa
 }
 
 // dQ -> dX [B, nq, dq] (written; may be null), dK -> dH [B, nk, d] (written or accumulated)
-int mab1_bf16_bwd(const pca_mab_shape& s, const void* X, const float* H,
-                  const pca_mab_params& p, const void* saved, const void* dY, void* dX,
-                  float* dH, int dk_accumulate, const pca_mab_grads& gr, void* ws,
-                  hipStream_t st) {
-  return mab1_bf16_bwd_ex(s, X, H, p, saved, dY, dX, dH, dk_accumulate, gr, ws, 0, st);
-}
 int mab1_bf16_bwd_ex(const pca_mab_shape& s, const void* X, const float* H,
                      const pca_mab_params& p, const void* saved, const void* dY, void* dX,
                      float* dH, int dk_accumulate, const pca_mab_grads& gr, void* ws, int flags,
                      hipStream_t st, const IsabImg* img, float* zero_ptr, int zero_n,
-                     int* nparts_out, BwdDefer* defer) {
+                     int* nparts_out, StepCtx* ctx) {
   if (s.d == 256)       // three launches + the 256-wide weight-gradient reduction (d256_host.hip)
-    return mab1_d256_bwd(s, X, H, p, saved, dY, dX, dH, dk_accumulate, gr, ws, st, defer);
+    return mab1_d256_bwd(s, X, H, p, saved, dY, dX, dH, dk_accumulate, gr, ws, st, ctx);
+  BwdDefer* const defer = defer_of(ctx);
   Mab1Saved v;
   mab1_carve_saved(s, &v, const_cast<void*>(saved));
   Mab1BwdWs w;

@@ -298,17 +298,13 @@ int validate(const pca_st_config* c) {
 }
 
 int forward(const pca_st_config& c, const Layout& L, const Shapes& s, const float* p,
-            const float* X, Ws& w, bool training, hipStream_t st, const PrepJobs* image_jobs = nullptr,
-            const PmaHeadArgs* head = nullptr, bool pma_bwd = false) {
+            const float* X, Ws& w, bool training, hipStream_t st, StepCtx* ctx,
+            const PrepJobs* image_jobs = nullptr, const PmaHeadArgs* head = nullptr, bool pma_bwd = false) {
   const void* in = X;
   // d = 256: the query side of all three few-queries blocks in the same launch (mab0_d256_prep_collect)
   const bool prep256 = training && s.m0[0].d == 256 && mab_kind(s.m0[0]) == 2 &&
                        mab_kind(s.m0[1]) == 2 && mab_kind(s.pma) == 2 && !pma_head_ok(s);
-  struct PrepGuard {
-    bool on;
-    explicit PrepGuard(bool o) : on(o) {}
-    ~PrepGuard() { if (on) mab0_d256_prep_done(false); }
-  } prep_guard(prep256);
+  const int prep_flag = prep256 ? PCA_F_PREP_DONE : 0;
   if (training) {               // all weight images of the step in ONE launch
     PrepJobs J{};
     if (image_jobs != nullptr) J = *image_jobs;      // (d = 256: the step's image table, images256_prepare)
@@ -344,7 +340,6 @@ int forward(const pca_st_config& c, const Layout& L, const Shapes& s, const floa
       mab0_d256_prep_collect(3, sh, Iq, pr, sv, &MJ);
     }
     PCA_TRY(prep_all_launch(J, MJ, st));    // (takes a deferred pack along: pca_pack_defer)
-    if (prep256) mab0_d256_prep_done(true);
   }
   PCA_TRY(pack_flush(st));                  // a deferred pack nobody took runs now, before X is read
   if (training && set128_on(c, s)) {
@@ -403,14 +398,13 @@ int forward(const pca_st_config& c, const Layout& L, const Shapes& s, const floa
     // the K / V images of the many-queries block (mid256.hip; the blocks' saved areas are disjoint)
     const pca_mab_params p1 = params_at(p, L.mab1[li]);
     const bool mid = training && s.m0[li].d == 256 && mab_kind(s.m0[li]) == 2 && mab_kind(s.m1[li]) == 1;
-    if (mid) mid256_arm(&s.m1[li], &p1, sv1);
-    const int rc0 = mab_fwd_any(s.m0[li], p + L.I[li], in, params_at(p, L.mab0[li]), w.H[li], sv0,
-                                w.scratch, st);                     // modules.py:52
-    const int rc1 = rc0 != PCA_OK ? rc0
-                                  : mab_fwd_any(s.m1[li], in, w.H[li], p1, w.Y[li], sv1, w.scratch,
-                                                st);                // modules.py:53
-    if (mid) mid256_arm(nullptr, nullptr, nullptr);
-    PCA_TRY(rc1);
+    ctx->mid_done = false;
+    if (mid) { ctx->s1 = s.m1[li]; ctx->p1 = p1; ctx->saved1 = sv1; }
+    PCA_TRY(mab_fwd_any(s.m0[li], p + L.I[li], in, params_at(p, L.mab0[li]), w.H[li], sv0, w.scratch,
+                        st, prep_flag, ctx));                       // modules.py:52
+    ctx->saved1 = nullptr;
+    PCA_TRY(mab_fwd_any(s.m1[li], in, w.H[li], p1, w.Y[li], sv1, w.scratch, st,
+                        ctx->mid_done ? PCA_F_KV_READY : 0, ctx));  // modules.py:53
     in = w.Y[li];
   }
   if (training && pma_head_ok(s))                                         // modules.py:63
@@ -420,7 +414,7 @@ int forward(const pca_st_config& c, const Layout& L, const Shapes& s, const floa
                              st));
   else
     PCA_TRY(mab_fwd_any(s.pma, p + L.S, w.Y[1], params_at(p, L.pma), w.P,
-                        training ? w.saved[4] : nullptr, w.scratch, st));
+                        training ? w.saved[4] : nullptr, w.scratch, st, prep_flag, ctx));
   if (!training)
     PCA_TRY(linear_fwd_f32(w.P, p + L.wc, p + L.bc, w.logits, (int64_t)c.B * c.k, c.d, c.C,
                            st));                                    // models.py:40
@@ -484,14 +478,15 @@ static int st_forward_impl(const pca_st_config* c, const float* params, const fl
   float* own = w.logits;
   w.logits = logits;
   (void)own;
-  return pca::forward(*c, L, s, params, X, w, false, st);
+  pca::StepCtx ctx{};
+  return pca::forward(*c, L, s, params, X, w, false, st, &ctx);
 }
 
 int pca_st_forward(const pca_st_config* c, const float* params, const float* X,
                    const int32_t* lengths, float* logits, void* ws, void* stream) {
-  PCA_TRY(pca::handoffs_empty("pca_st_forward", true));
+  PCA_TRY(pca::no_stale_pack("pca_st_forward", true));
   const int rc = st_forward_impl(c, params, X, lengths, logits, ws, stream);
-  return rc != PCA_OK ? rc : pca::handoffs_empty("pca_st_forward (exit)", false);
+  return rc != PCA_OK ? rc : pca::no_stale_pack("pca_st_forward (exit)", false);
 }
 
 static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, const float* X,
@@ -520,13 +515,13 @@ static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, co
   // d = 256: all weight images of the step in one launch (phase 1 of a split step finds the images
   // of phase 0 still in place: the parameters do not change in between)
   pca::WeightImages images{};
-  struct ImagesGuard {
-    explicit ImagesGuard(const pca::WeightImages* t) { pca::weight_images_use(t); }
-    ~ImagesGuard() { pca::weight_images_use(nullptr); }
-  };
   pca::PrepJobs image_jobs{};
   PCA_TRY(pca::images256_prepare(*c, L, s, p, w, &images, phase != 1, st, &image_jobs));
-  ImagesGuard images_guard(images.n > 0 ? &images : nullptr);
+  // what this call hands from block to block (StepCtx); a block queues its terminal reductions in `posts`
+  // when its call is given deferring(true), and launches them itself otherwise
+  pca::StepCtx ctx{};
+  ctx.images = images.n > 0 ? &images : nullptr;
+  auto deferring = [&](bool on) { ctx.defer = on ? &posts : nullptr; return &ctx; };
   // d = 256: the [B*m]-row weight-gradient jobs of all five blocks in one launch at the flush -
   // needs every block's operands in place until then: the hand-over form of enc.1 (its few-queries
   // block works in w.scratch) and a workspace of its own for enc.0's few-queries block
@@ -544,7 +539,8 @@ static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, co
       PCA_TRY(pca::pma_head_args(s.pma, pca::params_at(p, L.pma), w.saved[4], w.scratch, w.P,
                                  p + L.wc, p + L.bc, labels, c->C, grad_scale, w.logits, w.dlogits,
                                  w.dP, g + L.wc, g + L.bc, loss_out, stats, w.clsws, &posts, &head));
-    PCA_TRY(pca::forward(*c, L, s, p, X, w, true, st, &image_jobs, fuse_head ? &head : nullptr, pma_bwd));
+    PCA_TRY(pca::forward(*c, L, s, p, X, w, true, st, &ctx, &image_jobs, fuse_head ? &head : nullptr,
+                         pma_bwd));
     if (pca::pma_head_ok(s)) {
       // dec.0 epilogue + dec.1 (Linear) + mean cross-entropy forward and backward + dec.0
       // backward epilogue: one launch, one workgroup per set
@@ -557,20 +553,16 @@ static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, co
                                     w.saved[4], w.dP, g + L.S, w.dY2, 0,
                                     pca::grads_at(g, L.pma), w.scratch,
                                     pca::PCA_F_SKIP_HEAD | (pma_bwd ? pca::PCA_F_ATTN_DONE : 0), st,
-                                    &posts));
+                                    deferring(true)));
     } else {
     // dec.1 (Linear) + mean cross-entropy, forward and backward
     PCA_TRY(pca::cls_train_head(w.P, p + L.wc, p + L.bc, labels, c->B, c->d, c->C, grad_scale,
                                 w.logits, w.dlogits, w.dP, g + L.wc, g + L.bc, loss_out, stats,
                                 w.clsws, st, &posts));
-    if (s.pma.d == 256 && pca::mab_kind(s.pma) == 2)   // post stages deferred
-      PCA_TRY(pca::mab0_bf16_bwd_ex(s.pma, p + L.S, w.Y[1], pca::params_at(p, L.pma), w.saved[4],
-                                    w.dP, g + L.S, w.dY2, 0, pca::grads_at(g, L.pma),
-                                    w.scratch_pma, 0, st, &posts));
-    else
+    const bool pma256 = s.pma.d == 256 && pca::mab_kind(s.pma) == 2;   // post stages deferred
     PCA_TRY(pca::mab_bwd_any(s.pma, p + L.S, w.Y[1], pca::params_at(p, L.pma), w.saved[4],
-                             w.dP, g + L.S, w.dY2, 0, pca::grads_at(g, L.pma), w.scratch,
-                             st));
+                             w.dP, g + L.S, w.dY2, 0, pca::grads_at(g, L.pma),
+                             pma256 ? w.scratch_pma : w.scratch, st, deferring(pma256)));
     }
     // enc.1: mab1(Y1, H2) then mab0(I2, Y1); Y1 feeds both, so dY1 accumulates
     if (w.fused[1]) {
@@ -581,32 +573,18 @@ static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, co
                                  w.scratch_bw[1], w.img[1], st, &posts));
     } else {
     // d = 256: mab1's fc_q weight-gradient job is handed to the few-queries block, whose two jobs
-    // read the same Y1 (wgrad256_handoff, d256_host.hip); the two blocks then need separate
-    // workspaces - mab0 takes the forward / PMA scratch, which is free by now
-    const bool hand = s.m1[1].d == 256 && pca::mab_kind(s.m1[1]) == 1 && pca::mab_kind(s.m0[1]) == 2;
-    struct HandGuard {
-      bool on;
-      explicit HandGuard(bool o) : on(o) { if (on) pca::wgrad256_handoff_arm(true); }
-      ~HandGuard() { if (on) pca::wgrad256_handoff_arm(false); }
-    } hand_guard(hand);
-    if (defer_wg)
-      PCA_TRY(pca::mab1_bf16_bwd_ex(s.m1[1], w.Y[0], w.H[1], pca::params_at(p, L.mab1[1]),
-                                    w.saved[3], w.dY2, w.dY1, w.dH, 0, pca::grads_at(g, L.mab1[1]),
-                                    w.scratch_bw[1], 0, st, nullptr, nullptr, 0, nullptr, &posts));
-    else
+    // read the same Y1 (StepCtx::armed); the two blocks then need separate workspaces - mab0 takes the
+    // forward / PMA scratch, which is free by now
+    ctx.armed = hand1;
     PCA_TRY(pca::mab_bwd_any(s.m1[1], w.Y[0], w.H[1], pca::params_at(p, L.mab1[1]),
                              w.saved[3], w.dY2, w.dY1, w.dH, 0, pca::grads_at(g, L.mab1[1]),
-                             w.scratch_bw[1], st));
-    if (hand)   // (its post stage waits for the flush: w.scratch stays untouched)
-      PCA_TRY(pca::mab0_bf16_bwd_ex(s.m0[1], p + L.I[1], w.Y[0], pca::params_at(p, L.mab0[1]),
-                                    w.saved[2], w.dH, g + L.I[1], w.dY1, 1,
-                                    pca::grads_at(g, L.mab0[1]), w.scratch, 0, st, &posts));
-    else
+                             w.scratch_bw[1], st, deferring(defer_wg)));
+    // (hand1: its post stage waits for the flush - w.scratch stays untouched)
     PCA_TRY(pca::mab_bwd_any(s.m0[1], p + L.I[1], w.Y[0], pca::params_at(p, L.mab0[1]),
-                             w.saved[2], w.dH, g + L.I[1], w.dY1, 1,
-                             pca::grads_at(g, L.mab0[1]), hand ? w.scratch : w.scratch_bw[1], st));
-    if (hand && pca::wgrad256_handoff_pending())        // (nobody took it: run it on its own)
-      PCA_TRY(pca::wgrad256_handoff_flush(w.scratch, st));
+                             w.saved[2], w.dH, g + L.I[1], w.dY1, 1, pca::grads_at(g, L.mab0[1]),
+                             hand1 ? w.scratch : w.scratch_bw[1], st, deferring(hand1)));
+    ctx.armed = false;
+    PCA_TRY(pca::wgrad256_handoff_flush(&ctx, w.scratch, st));   // (what nobody took runs on its own)
     }
   }
   if (phase != 0) {
@@ -618,23 +596,13 @@ static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, co
                                  pca::grads_at(g, L.mab0[0]), pca::grads_at(g, L.mab1[0]),
                                  w.scratch_bw[0], w.img[0], st, &posts));
     } else {
-    if (defer_wg)
-      PCA_TRY(pca::mab1_bf16_bwd_ex(s.m1[0], X, w.H[0], pca::params_at(p, L.mab1[0]), w.saved[1],
-                                    w.dY1, nullptr, w.dH, 0, pca::grads_at(g, L.mab1[0]),
-                                    w.scratch_bw[0], 0, st, nullptr, nullptr, 0, nullptr, &posts));
-    else
     PCA_TRY(pca::mab_bwd_any(s.m1[0], X, w.H[0], pca::params_at(p, L.mab1[0]), w.saved[1],
                              w.dY1, nullptr, w.dH, 0, pca::grads_at(g, L.mab1[0]),
-                             w.scratch_bw[0], st));
-    if (s.m0[0].d == 256 && pca::mab_kind(s.m0[0]) == 2)
-      PCA_TRY(pca::mab0_bf16_bwd_ex(s.m0[0], p + L.I[0], X, pca::params_at(p, L.mab0[0]),
-                                    w.saved[0], w.dH, g + L.I[0], nullptr, 0,
-                                    pca::grads_at(g, L.mab0[0]),
-                                    defer_wg ? w.scratch_m0 : w.scratch_bw[0], 0, st, &posts));
-    else
+                             w.scratch_bw[0], st, deferring(defer_wg)));
+    const bool fq256 = s.m0[0].d == 256 && pca::mab_kind(s.m0[0]) == 2;
     PCA_TRY(pca::mab_bwd_any(s.m0[0], p + L.I[0], X, pca::params_at(p, L.mab0[0]),
-                             w.saved[0], w.dH, g + L.I[0], nullptr, 0,
-                             pca::grads_at(g, L.mab0[0]), w.scratch_bw[0], st));
+                             w.saved[0], w.dH, g + L.I[0], nullptr, 0, pca::grads_at(g, L.mab0[0]),
+                             fq256 && defer_wg ? w.scratch_m0 : w.scratch_bw[0], st, deferring(fq256)));
     }
   }
   return pca::bwd_defer_flush(posts, st);
@@ -646,9 +614,9 @@ int pca_st_train_fwd_bwd(const pca_st_config* c, const float* params, const floa
                          float* logits, float grad_scale, int phase, void* ws,
                          void* stream) {
   // phase 1 of a split step reads X again: the pack was consumed by phase 0
-  PCA_TRY(pca::handoffs_empty("pca_st_train_fwd_bwd", phase != 1));
+  PCA_TRY(pca::no_stale_pack("pca_st_train_fwd_bwd", phase != 1));
   const int rc = st_train_fwd_bwd_impl(c, params, X, lengths, labels, grads, loss_out, stats, logits,
                                        grad_scale, phase, ws, stream);
-  return rc != PCA_OK ? rc : pca::handoffs_empty("pca_st_train_fwd_bwd (exit)", false);
+  return rc != PCA_OK ? rc : pca::no_stale_pack("pca_st_train_fwd_bwd (exit)", false);
 }
 }
