@@ -130,6 +130,28 @@ int pca_stft_logmag_batch_norm(const float* waves, const int64_t* wave_off,
                                float* out, int64_t stride_f, int64_t stride_t, double norm,
                                void* stream);
 
+/* Leading / trailing silence of a whole corpus: the (start, end) of librosa.effects.trim
+ * replaces: Code/settransformer.py:48, Code/pceval.py:74,127 and the same line of every other train /
+ *           eval script (x, index = librosa.effects.trim(x, top_db = trim_dB); librosa 0.8 semantics
+ *           restated - librosa is third-party and not vendored, and the reference holds no trimmed
+ *           fixture: "parity unpinned", as the resampler)
+ * waves / wave_off[n_clips + 1] / max_len / min_len: as for the batched STFT above.  Per clip of L samples:
+ * frames t < 1 + L / hop_length of frame_length samples (even, <= 8192) from the signal reflect-padded by
+ * frame_length / 2 (so every clip must be longer than that); mse[t] = mean of the squares (fp64);
+ * db[t] = 10 log10(max(1e-10, mse[t])) - 10 log10(max(1e-10, max_t mse[t])); with first / last the first
+ * and last frame whose db[t] > -top_db: bounds[c] = (first * hop_length, min(L, (last + 1) * hop_length)),
+ * or (0, 0) when no frame qualifies.  bounds[n_clips][2] int64 (device); the caller slices.
+ * Two launches: sums of squares per segment of the padded signal into ws - every sample read once when
+ * hop_length divides frame_length / 2, a frame being frame_length / hop_length adjacent segments; whole
+ * frames otherwise - then one workgroup per clip for the maximum and the first / last scan.  Fixed-order
+ * fp64 sums, no atomics: the same call gives the same bits.
+ * ws: the trim workspace query's bytes for total_len = wave_off[n_clips] samples (0 for arguments the
+ * launch would refuse). */
+size_t pca_trim_ws_bytes(int64_t total_len, int n_clips, int frame_length, int hop_length);
+int pca_trim_bounds(const float* waves, const int64_t* wave_off, int n_clips, int64_t max_len,
+                    int64_t min_len, int frame_length, int hop_length, double top_db,
+                    int64_t* bounds, void* ws, void* stream);
+
 /* 2-D point sets for a batch of frames
  * replaces: Code/dataset.py:50-54  ESC_pc.__getitem__ (+ default_collate)
  * spec element (f, t) at spec[f*stride_f + t*stride_t]; farr[F] float32 (the

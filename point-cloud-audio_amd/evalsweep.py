@@ -14,8 +14,13 @@ band-limited sinc interpolation with resampy's documented ``kaiser_fast`` design
 third-party, not vendored and not installed here, and the reference holds no resampled fixture, so this
 axis is **parity unpinned** (SURVEY.md 8c); the kernel is checked against the CPU restatement of the
 same algorithm (tests/test_resample.py).
-Not covered: ``librosa.load`` / ``effects.trim`` (file decoding and silence trimming: the clips passed
-in are waveforms already).
+The silence trim that precedes it (``x, index = librosa.effects.trim(x, top_db=trim_dB)``,
+``Code/pceval.py:39,74``) runs on the device as well: the four re-framing sweeps take ``trim_dB`` (the
+value a run's config file carries, ``trim_dB_of``) and trim every clip once, up front and before any
+resampling, with ``pca_hip.trim_batch`` (librosa 0.8 semantics restated, default frame 2048 / hop 512;
+**parity unpinned** for the same reason: checked against the numpy restatement tests/trim_ref.py).
+``trim_dB=None`` (the default) leaves the clips as they are.
+Not covered: ``librosa.load`` (file decoding is I/O: the clips passed in are waveforms already).
 
 The other set-model experiments run here at batch scale too:
 
@@ -52,7 +57,38 @@ from pca_hip.trainer import STEngine, st_config
 __all__ = ["reframe_sweep", "framewise_dataset", "default_list_K", "sweep_draw", "subsample_sweep",
            "importance_sweep", "chunk_plan", "temporal_axes", "temporal_dataset",
            "reframe_sweep_temporal", "baseline_subsample_sweep", "baseline_frames",
-           "baseline_chunks", "baseline_reframe_sweep", "baseline_reframe_sweep_temporal"]
+           "baseline_chunks", "baseline_reframe_sweep", "baseline_reframe_sweep_temporal",
+           "trim_dB_of", "trim_clips"]
+
+
+def trim_dB_of(config: Dict) -> Optional[float]:
+    """The ``trim_dB`` of a run's config (``runfiles.load_run``; ``tDb = dict_params['trim_dB']``,
+    Code/pceval.py:39) for the sweeps' ``trim_dB`` argument; None when the config has none."""
+    v = config.get("trim_dB")
+    return None if v is None else float(v)
+
+
+def trim_clips(clips: Sequence[torch.Tensor], trim_dB: float, n_fft: int,
+               ratios: Iterable[float] = (1.0,)) -> List[torch.Tensor]:
+    """``librosa.effects.trim(x, top_db=trim_dB)`` of every clip (Code/pceval.py:74) in one
+    pca_hip.trim_batch call; the results are views of ``clips``.  A clip whose trimmed length - at any
+    of the resampling ``ratios`` (new rate / recorded rate) applied afterwards - is at or below the
+    STFT's minimum n_fft / 2 raises ValueError: it would yield no spectrum, and the reference never
+    drops a clip."""
+    out, bounds = pca_hip.trim_batch(list(clips), top_db=trim_dB)
+    need = int(n_fft) // 2
+    for c, (s, e) in enumerate(bounds.tolist()):
+        n = min(int(math.ceil((e - s) * float(r))) for r in ratios)
+        if n <= need:
+            raise ValueError(f"clip {c}: trim_dB={trim_dB:g} keeps samples [{s}, {e}) of "
+                             f"{clips[c].numel()}, {n} samples for the STFT, which needs more than "
+                             f"n_fft/2 = {need}")
+    return out
+
+
+def _pow2_fft(list_N) -> int:
+    """The largest n_fft = 2**ceil(log2 N) of the set-model re-framing loops."""
+    return max(1 << int(math.ceil(math.log2(n))) for n in list_N)
 
 
 def framewise_dataset(clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float, N: int,
@@ -77,15 +113,21 @@ def framewise_dataset(clips: Sequence[torch.Tensor], labels: Sequence[int], fs: 
 def reframe_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float,
                   list_N: Iterable[int], hf: float = 0.5, batch_size: int = 8,
                   mode: int = _lib.MODE_F32, json_file: Optional[str] = None,
-                  list_Fs: Optional[Iterable[float]] = None) -> Dict:
+                  list_Fs: Optional[Iterable[float]] = None,
+                  trim_dB: Optional[float] = None) -> Dict:
     """Accuracy of ``model`` for every analysis length in ``list_N`` - and, with ``list_Fs``, for every
     sampling rate the clips (recorded at ``fs``) are resampled to first, as the double loop of
     ``Code/pceval.py:61-98`` does; returns (and optionally writes) the dictionary
     ``Code/pceval.py:57-59,99-104`` stores: ``{"data": {Fs: [acc per N]}, "list_Fs": [...],
-    "list_N": [...]}``."""
+    "list_N": [...]}``.  ``trim_dB``: trim every clip first (trim_clips; Code/pceval.py:74 trims, then
+    resamples); None: the clips as given."""
     list_N = [int(n) for n in list_N]
     if list_Fs is not None:
         list_Fs = list(list_Fs)
+    if trim_dB is not None:
+        clips = trim_clips(clips, trim_dB, _pow2_fft(list_N),
+                           (1.0,) if list_Fs is None else [F / fs for F in list_Fs])
+    if list_Fs is not None:
         data = {}
         for F in list_Fs:
             rs = [pca_hip.resample(x, fs, F, scale=True) for x in clips]     # pceval.py:74
@@ -420,15 +462,21 @@ def reframe_sweep_temporal(model, clips: Sequence[torch.Tensor], labels: Sequenc
                            list_N: Iterable[int], Ntemp: int = 10, hf: float = 0.5,
                            list_Fs: Optional[Iterable[float]] = None,
                            json_file: Optional[str] = None, batch_size: int = 8,
-                           mode: int = _lib.MODE_F32, sets_per_call: Optional[int] = None) -> Dict:
+                           mode: int = _lib.MODE_F32, sets_per_call: Optional[int] = None,
+                           trim_dB: Optional[float] = None) -> Dict:
     """Experiment 1 of Code/pc_temp3d_eval.py:56-107: accuracy of the 3ST ``model`` for every analysis
     length in ``list_N`` (temporal_dataset) and, with ``list_Fs``, every sampling rate the clips
     (recorded at ``fs``) are resampled to first (pca_hip.resample: parity unpinned, as in
     reframe_sweep).  Returns (and optionally writes) ``{"data": {Fs: [acc per N]}, "list_Fs": [...],
-    "list_N": [...]}``; one host read per N."""
+    "list_N": [...]}``; one host read per N.  ``trim_dB``: trim every clip first (trim_clips;
+    Code/pc_temp3d_eval.py:73), before any resampling; None: the clips as given."""
     list_N = [int(n) for n in list_N]
     if list_Fs is not None:
         list_Fs = list(list_Fs)
+    if trim_dB is not None:
+        clips = trim_clips(clips, trim_dB, _pow2_fft(list_N),
+                           (1.0,) if list_Fs is None else [F / fs for F in list_Fs])
+    if list_Fs is not None:
         data = {}
         for F in list_Fs:
             rs = [pca_hip.resample(x, fs, F, scale=True) for x in clips]    # pc_temp3d_eval.py:74
@@ -591,13 +639,17 @@ def baseline_chunks(clips: Sequence[torch.Tensor], labels: Sequence[int], N: int
 
 @torch.no_grad()
 def _baseline_reframe(model, clips, labels, fs, list_N, hf, list_Fs, json_file, n_fft, Ntemp,
-                      sets_per_call):
+                      sets_per_call, trim_dB=None):
     eng = _baseline_engine(model)
     list_N = [int(n) for n in list_N]
     if n_fft is None:
         n_fft = 2 * eng.Nf if eng.cnn else 2 * (eng.layer_dims[0] - 1)
     if list_Fs is not None:
         list_Fs = list(list_Fs)
+    if trim_dB is not None:                      # Code/baseline_eval.py:74: trim, then resample
+        clips = trim_clips(clips, trim_dB, n_fft,
+                           (1.0,) if list_Fs is None else [F / fs for F in list_Fs])
+    if list_Fs is not None:
         data = {}
         for F in list_Fs:
             rs = [pca_hip.resample(x, fs, F, scale=True) for x in clips]
@@ -630,28 +682,31 @@ def baseline_reframe_sweep(model, clips: Sequence[torch.Tensor], labels: Sequenc
                            list_N: Iterable[int], hf: float = 0.5,
                            list_Fs: Optional[Iterable[float]] = None,
                            json_file: Optional[str] = None, n_fft: Optional[int] = None,
-                           sets_per_call: Optional[int] = None) -> Dict:
+                           sets_per_call: Optional[int] = None,
+                           trim_dB: Optional[float] = None) -> Dict:
     """Experiment 1 of Code/baseline_eval.py:50-103 (FB): accuracy for every analysis length N in
     ``list_N`` (baseline_frames: n_fft = the model's window 2 * (layer_dims[0] - 1) unless given,
     divisor n_fft, every frame counts) and, with ``list_Fs``, every sampling rate the clips
     (recorded at ``fs``) are resampled to first (pca_hip.resample: parity unpinned).  Returns (and
-    optionally writes) ``{"data": {Fs: [acc per N]}, "list_Fs", "list_N"}`` (FB_expt1.json)."""
+    optionally writes) ``{"data": {Fs: [acc per N]}, "list_Fs", "list_N"}`` (FB_expt1.json).
+    ``trim_dB``: trim every clip first (trim_clips; Code/baseline_eval.py:74); None: as given."""
     eng = _baseline_engine(model)
     assert not eng.cnn, "baseline_reframe_sweep takes an FB model (CNN_temp: _temporal)"
     return _baseline_reframe(eng, clips, labels, fs, list_N, hf, list_Fs, json_file, n_fft, None,
-                             sets_per_call)
+                             sets_per_call, trim_dB)
 
 
 def baseline_reframe_sweep_temporal(model, clips: Sequence[torch.Tensor], labels: Sequence[int],
                                     fs: float, list_N: Iterable[int], hf: float = 0.5,
                                     list_Fs: Optional[Iterable[float]] = None,
                                     json_file: Optional[str] = None, n_fft: Optional[int] = None,
-                                    sets_per_call: Optional[int] = None) -> Dict:
+                                    sets_per_call: Optional[int] = None,
+                                    trim_dB: Optional[float] = None) -> Dict:
     """Experiment 1 of Code/baseline_temp_eval.py:51-107 (CNN_temp): as baseline_reframe_sweep on
     the model's Nt-frame chunks (baseline_chunks: n_fft = 2 * Nf unless given, Nyquist dropped,
     divisor n_fft, short tail dropped, a trailing one-set batch of 2 skipped).  Writes the layout of
-    CNNTemp_expt1.json."""
+    CNNTemp_expt1.json.  ``trim_dB``: as in baseline_reframe_sweep (Code/baseline_temp_eval.py:72)."""
     eng = _baseline_engine(model)
     assert eng.cnn, "baseline_reframe_sweep_temporal takes a CNN_temp model"
     return _baseline_reframe(eng, clips, labels, fs, list_N, hf, list_Fs, json_file, n_fft, eng.Nt,
-                             sets_per_call)
+                             sets_per_call, trim_dB)

@@ -65,6 +65,9 @@ SIGNATURES = {
     "pca_stft_logmag_batch_norm": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64,
                                              C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, c_fp,
                                              C.c_int64, C.c_int64, C.c_double, c_vp]),
+    "pca_trim_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "pca_trim_bounds": (C.c_int, [c_fp, c_i64p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                  C.c_double, c_i64p, c_vp, c_vp]),
     "pca_resample": (C.c_int, [c_fp, C.c_int64, C.c_double, c_vp, c_vp, C.c_int, C.c_int, C.c_float, c_fp,
                                C.c_int64, c_vp]),
     "pca_pack_points_2d": (C.c_int, [c_fp, C.c_int64, C.c_int64, c_fp, c_i64p, C.c_int,

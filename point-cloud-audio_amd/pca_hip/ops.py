@@ -407,6 +407,46 @@ def resample(wave: torch.Tensor, fs_old: float, fs_new: float, scale: bool = Tru
     return out
 
 
+# ---- silence trimming (librosa.effects.trim, the step before resampling / STFT in every script) ------
+def trim_batch(waves, top_db: float = 60, frame_length: int = 2048, hop_length: int = 512):
+    """Leading / trailing silence of a list of 1-D float32 device waveforms, as
+    ``librosa.effects.trim(x, top_db, frame_length=, hop_length=)`` (Code/pceval.py:74; librosa 0.8
+    semantics restated, "parity unpinned": librosa is not available and the reference holds no trimmed
+    fixture).  One pca_trim_bounds call and one host read of the bounds for the whole list.
+    Returns (clips, bounds): clips[c] = waves[c][start:end], a view of the input (no copy), and
+    bounds the int64 ndarray [n, 2] of (start, end)."""
+    waves = list(waves)
+    assert len(waves) > 0
+    _need_cuda(*waves)
+    for w in waves:
+        if w.dim() != 1 or w.dtype != torch.float32:
+            raise _lib.PcaHipError(f"trim: 1-D float32 waveforms, got {tuple(w.shape)} {w.dtype}")
+    dev = waves[0].device
+    lens = [int(w.numel()) for w in waves]
+    woff = [0]
+    for n in lens:
+        woff.append(woff[-1] + n)
+    L = lib()
+    with torch.cuda.device(dev):
+        cat = waves[0].contiguous() if len(waves) == 1 else torch.cat(waves)
+        woff_d = torch.tensor(woff, dtype=torch.int64, device=dev)
+        bounds = torch.empty((len(waves), 2), dtype=torch.int64, device=dev)
+        ws = _bytes(L.pca_trim_ws_bytes(woff[-1], len(waves), frame_length, hop_length), cat)
+        check(L.pca_trim_bounds(_ptr(cat), _ptr(woff_d), len(waves), max(lens), min(lens),
+                                frame_length, hop_length, float(top_db), _ptr(bounds), _ptr(ws),
+                                _stream(cat)), "pca_trim_bounds")
+        b = bounds.cpu().numpy()                               # the one host read
+    return [w[int(s):int(e)] for w, (s, e) in zip(waves, b)], b
+
+
+def trim(wave: torch.Tensor, top_db: float = 60, frame_length: int = 2048,
+         hop_length: int = 512):
+    """``librosa.effects.trim`` of one 1-D float32 device waveform: (wave[start:end] as a view,
+    (start, end)).  See trim_batch."""
+    clips, b = trim_batch([wave], top_db, frame_length, hop_length)
+    return clips[0], (int(b[0, 0]), int(b[0, 1]))
+
+
 def stft_logmag_batch(waves, n_fft: int, win_length: Optional[int] = None,
                       hop: Optional[int] = None, drop_nyquist: bool = False,
                       frame_major: bool = False, norm: Optional[float] = None,
