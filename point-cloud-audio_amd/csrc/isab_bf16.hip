@@ -1,8 +1,11 @@
 // ISAB-level orchestration of the fused bf16 path (set_transformer-master/modules.py:51-53):
 //   forward   mab0 attention partials -> k_mid_fwd (epilogue of mab0 + K/V of mab1) -> mab1
-//   backward  mab1 chain (dX, dKp, dVp) -> batched wgrad -> k_mid_bwd -> mab0 backward
+//   backward  mab1 chain (dX, dKp, dVp) -> k_mid_bwd -> batched wgrad -> mab0 backward
+//             (the mid chain runs inside the mab0 backward's launch unless PCA_D128_MIDFUSE=0)
 // Only host code here; kernels live in mab0_*, mab1_*, mid_bf16.hip.
 #include "d256_bf16.hpp"
+
+#include <stdlib.h>
 
 namespace pca {
 
@@ -15,6 +18,17 @@ bool isab_bf16_supported(const pca_mab_shape& s0, const pca_mab_shape& s1) {
 
 namespace {
 constexpr size_t DD = 128 * 128;
+
+// PCA_D128_MIDFUSE: 0 = k_mid_bwd as a launch in both layers, 1 = fused in both, "wide" / "small" =
+// fused in that form only (layer 2, dk = 128 / layer 1, dk <= 4); unset = each layer's measured winner
+constexpr bool MIDFUSE_DEFAULT_WIDE = true, MIDFUSE_DEFAULT_SMALL = true;
+bool midfuse_on(bool small) {
+  const char* e = getenv("PCA_D128_MIDFUSE");
+  if (e == nullptr || e[0] == 0) return small ? MIDFUSE_DEFAULT_SMALL : MIDFUSE_DEFAULT_WIDE;
+  if (e[0] == 'w') return !small;
+  if (e[0] == 's') return small;
+  return e[0] != '0';
+}
 }  // namespace
 
 // images of one ISAB: 13 bf16 [128][128] blocks
@@ -105,10 +119,16 @@ int isab_bf16_bwd(const pca_mab_shape& s0, const pca_mab_shape& s1, const float*
   StepCtx ctx{};
   ctx.defer = defer;
   int nparts = 0;
-  PCA_TRY(mab1_bf16_bwd_ex(s1, X, H, p1, saved1, dY, dX, nullptr, 0, g1, ws1,
-                           PCA_F_SKIP_KV_TAIL, st, &im, nullptr, 0, &nparts, &ctx));
   const int64_t Bm = (int64_t)s0.B * m;
   const int Rp = 64;
+  // the per-set mid chain as the prologue of the few-queries backward (every workgroup of a set runs
+  // it for itself) instead of a launch between the two point-sized kernels; read per call so that one
+  // process can compare both forms
+  const bool fuse_mid = midfuse_on(dk <= 4);
+  // (fused: nothing runs between the two kernels, so the first one clears DG for the second)
+  PCA_TRY(mab1_bf16_bwd_ex(s1, X, H, p1, saved1, dY, dX, nullptr, 0, g1, ws1,
+                           PCA_F_SKIP_KV_TAIL, st, &im, fuse_mid ? w0.DG : nullptr,
+                           fuse_mid ? Rp * dk : 0, &nparts, &ctx));
   MidBwdLaunch L{};
   L.B = s0.B; L.dk = dk;
   L.dKpPart = w1.dKpPart; L.dVpPart = w1.dVpPart; L.nparts = nparts;
@@ -119,7 +139,13 @@ int isab_bf16_bwd(const pca_mab_shape& s0, const pca_mab_shape& s1, const float*
   L.Wv0f = p0.wv;
   L.dZ = w0.dZ; L.dO = w0.dO; L.Th = w0.Th; L.dQs = w0.dQs; L.dTf = w0.dTf; L.dTb = w0.dTb;
   L.dTt = w0.dTt; L.Delta = w0.Delta; L.LSEp = w0.LSEp;
-  PCA_TRY(mid_bwd_launch(L, st));
+  if (fuse_mid) {
+    // dKp, dVp, dZ, dO and Th are written by that launch: the weight-gradient jobs follow it
+    PCA_TRY(mab0_bf16_bwd_ex(s0, I, X, p0, saved0, nullptr, dI, dX, dX != nullptr ? 1 : 0, g0, ws0,
+                             PCA_F_SKIP_HEAD | PCA_F_SKIP_WGRAD, st, &ctx, &L));
+  } else {
+    PCA_TRY(mid_bwd_launch(L, st));
+  }
   {   // every [B*m]-row weight gradient of the ISAB in ONE launch
     WgradJobs jobs{};
     jobs.j[jobs.n++] = WgradJob{w1.dKp, H, g1.wk, g1.bk, Bm, 0, 128};
@@ -134,6 +160,7 @@ int isab_bf16_bwd(const pca_mab_shape& s0, const pca_mab_shape& s1, const float*
       PCA_TRY(wgrad_small_f32_launch(w0.dO, w0.Th, Bm, dk, (int64_t)Bm * dk, g0.wv, g0.bv, st,
                                      defer));
   }
+  if (fuse_mid) return PCA_OK;
   return mab0_bf16_bwd_ex(s0, I, X, p0, saved0, nullptr, dI, dX, dX != nullptr ? 1 : 0, g0, ws0,
                           PCA_F_SKIP_HEAD | PCA_F_SKIP_WGRAD, st, &ctx);
 }

@@ -19,6 +19,7 @@
 #include "terminal_bodies.hpp"
 #include "pma_head_bodies.hpp"
 #include "slab_sum_body.hpp"
+#include "mid_bwd_body.hpp"
 
 #include <math.h>
 #include <stdlib.h>
@@ -83,6 +84,36 @@ struct Mab0BwdArgs {
   const int32_t* lengths;   // [B] valid points per set, or null
   int R;                    // real score rows (<= RP): only these rows of dG are non-zero
   float* slabs;             // [B*S][R][128]: per-workgroup dG (summed in a fixed order afterwards)
+  // fuse_mid (RP == 64, an ISAB's few-queries block): dTb / dTt / LSEp / Delta are not read; every
+  // workgroup of a set runs the set's mid chain (mid_bwd_body.hpp) and keeps the images in LDS
+  int fuse_mid;
+  MidBwdArgs mid;
+};
+
+// sinks of the mid chain run in a prologue: the images in the layout the main loop reads them in
+struct MidSinkWide {
+  char *sdT, *sdTt;
+  float *sLSE, *sDel;
+  __device__ __forceinline__ void dTb(int row, int ct, int g, bf16x4 v) const {
+    *reinterpret_cast<bf16x4*>(sdT + tr_off(row, 2 * ct + (g >> 1)) + 8 * (g & 1)) = v;
+  }
+  __device__ __forceinline__ void dTt(int ct, int r, int w, int g, bf16x4 v) const {
+    *reinterpret_cast<bf16x4*>(sdTt + rp_off<64>(16 * ct + r, 4 * (w >> 1) + g) + 8 * (w & 1)) = v;
+  }
+  __device__ __forceinline__ void dTf(int, int, float) const {}
+  __device__ __forceinline__ void stat(int row, float delta, float lse) const {
+    sDel[row] = delta;
+    sLSE[row] = lse;
+  }
+};
+constexpr int MID_SMALL_FUSE_IMG = (64 * 4 + 64) * 4;       // dTf [64][4] + Delta [64]
+constexpr int MID_SMALL_FUSE_LDS = MID_SMALL_FUSE_IMG + MID_BWD_SMALL_LDS + 2 * MID_BWD_W_LDS;
+struct MidSinkSmall {
+  float *sdTf, *sDel;       // [64][4], [64]
+  __device__ __forceinline__ void dTb(int, int, int, bf16x4) const {}
+  __device__ __forceinline__ void dTt(int, int, int, int, bf16x4) const {}
+  __device__ __forceinline__ void dTf(int row, int c, float v) const { sdTf[row * 4 + c] = v; }
+  __device__ __forceinline__ void stat(int row, float delta, float) const { sDel[row] = delta; }
 };
 
 template <int RP, bool ABF>
@@ -108,51 +139,6 @@ __global__ __launch_bounds__(256, 1) void k_mab0_bwd(const Mab0BwdArgs a) {
   int len = a.N;
   if (a.lengths != nullptr) len = a.lengths[b] < a.N ? a.lengths[b] : a.N;
 
-  {
-    // all image chunks of this thread are fetched before the first LDS store: one round trip
-    // instead of one per loop iteration (the stores would order the loads behind them)
-    constexpr int NA = RP * 16 / 256, NB2 = DK * (RP / 8) / 256;
-    uint4 g1[NA], t1[NA], g2[NB2], t2[NB2];
-#pragma unroll
-    for (int e = 0; e < NA; ++e) {
-      const int c = tid + 256 * e, row = c >> 4, ch = c & 15;
-      g1[e] = *reinterpret_cast<const uint4*>(a.Gb + (int64_t)row * DK + ch * 8);
-      t1[e] = *reinterpret_cast<const uint4*>(a.dTb + ((int64_t)b * RP + row) * DK + ch * 8);
-    }
-#pragma unroll
-    for (int e = 0; e < NB2; ++e) {
-      const int c = tid + 256 * e, row = c / (RP / 8), ch = c % (RP / 8);
-      g2[e] = *reinterpret_cast<const uint4*>(a.GtP + (int64_t)row * RP + ch * 8);
-      t2[e] = *reinterpret_cast<const uint4*>(a.dTt + ((int64_t)b * DK + row) * RP + ch * 8);
-    }
-#pragma unroll
-    for (int e = 0; e < NA; ++e) {
-      const int c = tid + 256 * e, row = c >> 4, ch = c & 15;
-      *reinterpret_cast<uint4*>(sG + tr_off(row, ch)) = g1[e];
-      *reinterpret_cast<uint4*>(sdT + tr_off(row, ch)) = t1[e];
-    }
-#pragma unroll
-    for (int e = 0; e < NB2; ++e) {
-      const int c = tid + 256 * e, row = c / (RP / 8), ch = c % (RP / 8);
-      *reinterpret_cast<uint4*>(sGt + rp_off<RP>(row, ch)) = g2[e];
-      *reinterpret_cast<uint4*>(sdTt + rp_off<RP>(row, ch)) = t2[e];
-    }
-  }
-  for (int i = tid; i < RP; i += 256) {
-    sLSE[i] = a.LSEp[(int64_t)b * RP + i];
-    sDel[i] = a.Delta[(int64_t)b * RP + i];
-  }
-  __syncthreads();
-
-  char* myX = sX + wave * 32 * 256;
-  char* myDS = sDS + wave * 32 * 256;
-  f32x4 dG[RB][FT];
-#pragma unroll
-  for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-    for (int ft = 0; ft < FT; ++ft) dG[rb][ft] = f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr float LN2 = 0.6931471805599453f;
-
   // the wave's next X tile is fetched into registers while the current one is worked on (the kernel
   // runs one wave per SIMD: registers are free, and every tile used to start with an exposed round trip)
   bf16x8 nx[8];
@@ -165,7 +151,87 @@ __global__ __launch_bounds__(256, 1) void k_mab0_bwd(const Mab0BwdArgs a) {
                   : ld_x8_guard<ABF>(a.X, (int64_t)b * a.N, n0 + (c >> 4), n_hi, DK, c & 15);
     }
   };
-  if (n_lo + wave * 32 < n_hi) fetch_tile(n_lo + wave * 32);
+  bool fuse = false;
+  if constexpr (RP == 64) fuse = a.fuse_mid != 0;
+  if constexpr (RP == 64) if (fuse) {
+    // the shared images and the first X tile are in flight while the set's mid chain runs: Wk1^T /
+    // Wv1^T are staged where the X and dS tiles will live (free until the main loop), the chain's small
+    // images behind the statistics, and dT / dT^T / Delta / LSE land where the loop reads them
+    constexpr int NA = RP * 16 / 256, NB2 = DK * (RP / 8) / 256;
+    bf16x8 g1[NA], g2[NB2];
+#pragma unroll
+    for (int e = 0; e < NA; ++e) {
+      const int c = tid + 256 * e, row = c >> 4, ch = c & 15;
+      g1[e] = gload8(a.Gb + (int64_t)row * DK + ch * 8);
+    }
+#pragma unroll
+    for (int e = 0; e < NB2; ++e) {
+      const int c = tid + 256 * e, row = c / (RP / 8), ch = c % (RP / 8);
+      g2[e] = gload8(a.GtP + (int64_t)row * RP + ch * 8);
+    }
+    if (n_lo + wave * 32 < n_hi) fetch_tile(n_lo + wave * 32);
+    char* const tail = reinterpret_cast<char*>(sDel + RP);
+    const MidBwdLds m{tail, tail + 16 * 256, tail + 2 * 16 * 256, sX, sDS};
+    mid_bwd_body<false>(a.mid, b, m, sp == 0, MidSinkWide{sdT, sdTt, sLSE, sDel});
+#pragma unroll
+    for (int e = 0; e < NA; ++e) {
+      const int c = tid + 256 * e, row = c >> 4, ch = c & 15;
+      *reinterpret_cast<bf16x8*>(sG + tr_off(row, ch)) = g1[e];
+    }
+#pragma unroll
+    for (int e = 0; e < NB2; ++e) {
+      const int c = tid + 256 * e, row = c / (RP / 8), ch = c % (RP / 8);
+      *reinterpret_cast<bf16x8*>(sGt + rp_off<RP>(row, ch)) = g2[e];
+    }
+  }
+  if (!fuse) {
+    // all image chunks of this thread are fetched before the first LDS store: one round trip
+    // instead of one per loop iteration (the stores would order the loads behind them)
+    constexpr int NA = RP * 16 / 256, NB2 = DK * (RP / 8) / 256;
+    // (bf16x8, not uint4: copies of that struct type are memcpys, which kept these arrays in scratch
+    //  memory once the mid chain was inlined above)
+    bf16x8 g1[NA], t1[NA], g2[NB2], t2[NB2];
+#pragma unroll
+    for (int e = 0; e < NA; ++e) {
+      const int c = tid + 256 * e, row = c >> 4, ch = c & 15;
+      g1[e] = gload8(a.Gb + (int64_t)row * DK + ch * 8);
+      t1[e] = gload8(a.dTb + ((int64_t)b * RP + row) * DK + ch * 8);
+    }
+#pragma unroll
+    for (int e = 0; e < NB2; ++e) {
+      const int c = tid + 256 * e, row = c / (RP / 8), ch = c % (RP / 8);
+      g2[e] = gload8(a.GtP + (int64_t)row * RP + ch * 8);
+      t2[e] = gload8(a.dTt + ((int64_t)b * DK + row) * RP + ch * 8);
+    }
+#pragma unroll
+    for (int e = 0; e < NA; ++e) {
+      const int c = tid + 256 * e, row = c >> 4, ch = c & 15;
+      *reinterpret_cast<bf16x8*>(sG + tr_off(row, ch)) = g1[e];
+      *reinterpret_cast<bf16x8*>(sdT + tr_off(row, ch)) = t1[e];
+    }
+#pragma unroll
+    for (int e = 0; e < NB2; ++e) {
+      const int c = tid + 256 * e, row = c / (RP / 8), ch = c % (RP / 8);
+      *reinterpret_cast<bf16x8*>(sGt + rp_off<RP>(row, ch)) = g2[e];
+      *reinterpret_cast<bf16x8*>(sdTt + rp_off<RP>(row, ch)) = t2[e];
+    }
+    for (int i = tid; i < RP; i += 256) {
+      sLSE[i] = a.LSEp[(int64_t)b * RP + i];
+      sDel[i] = a.Delta[(int64_t)b * RP + i];
+    }
+  }
+  __syncthreads();
+
+  char* myX = sX + wave * 32 * 256;
+  char* myDS = sDS + wave * 32 * 256;
+  f32x4 dG[RB][FT];
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+    for (int ft = 0; ft < FT; ++ft) dG[rb][ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+  constexpr float LN2 = 0.6931471805599453f;
+
+  if (!fuse && n_lo + wave * 32 < n_hi) fetch_tile(n_lo + wave * 32);
   for (int n0 = n_lo + wave * 32; n0 < n_hi; n0 += 128) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -346,13 +412,19 @@ __global__ __launch_bounds__(256, 1) void k_mab0_bwd(const Mab0BwdArgs a) {
 
 // layer 1 (dk <= 4): thread = (query row r, point partition); accumulates DG only.  The
 // set's points are staged in LDS chunk by chunk (coalesced) and re-read from there.
+// MID (R == 64, an ISAB's first few-queries block): dTf / Delta are not read; every workgroup of a set
+// runs the set's mid chain in the dynamic LDS block (MID_SMALL_FUSE_LDS bytes).  An instance of its own,
+// so that the plain kernel does not carry the chain's registers.
+template <bool MID>
 __global__ __launch_bounds__(256) void k_mab0_bwd_small(
     const float* __restrict__ X, const float* __restrict__ Gf, const float* __restrict__ dTf,
     const float* __restrict__ LSE, const float* __restrict__ Delta, int N, int R, int Rp, int dk,
-    float* __restrict__ DG, const int32_t* __restrict__ lengths, float* __restrict__ slabs) {
+    float* __restrict__ DG, const int32_t* __restrict__ lengths, float* __restrict__ slabs,
+    const MidBwdArgs mid) {
   constexpr int CH = PCA_POINT_CHUNK;
   __shared__ float sD[256][4];
   __shared__ __attribute__((aligned(16))) float sX[CH * 4];
+  extern __shared__ __attribute__((aligned(16))) char smid[];
   const int b = blockIdx.x, tid = threadIdx.x;
   // gridDim.y workgroups share the rows of a set: this one owns rows [row0, row0 + Rb)
   const int Rb = R / gridDim.y, row0 = blockIdx.y * Rb;
@@ -362,16 +434,36 @@ __global__ __launch_bounds__(256) void k_mab0_bwd_small(
   constexpr float LN2 = 0.6931471805599453f;
   float gk[4], dt[4], acc[4];
   f32x2 acc2[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    gk[c] = c < dk ? Gf[r * dk + c] : 0.f;
-    dt[c] = c < dk ? dTf[((int64_t)b * R + r) * dk + c] : 0.f;
-  }
-  const float lse = LSE[(int64_t)b * R + r], del = Delta[(int64_t)b * Rp + r];
   int len = N;
   if (lengths != nullptr) len = lengths[b] < N ? lengths[b] : N;
   float xr[16];
-  if (len > 0) fetch_points(X + (int64_t)b * N * dk, len < CH ? len : CH, dk, xr);
+  float lse, del;
+  if constexpr (MID) {
+    // the first chunk of points, G and the statistics are in flight while the mid chain runs
+#pragma unroll
+    for (int c = 0; c < 4; ++c) gk[c] = c < dk ? Gf[r * dk + c] : 0.f;
+    lse = LSE[(int64_t)b * R + r];
+    if (len > 0) fetch_points(X + (int64_t)b * N * dk, len < CH ? len : CH, dk, xr);
+    float* const sdTf = reinterpret_cast<float*>(smid);
+    float* const sDelta = sdTf + 64 * 4;
+    char* const base = smid + MID_SMALL_FUSE_IMG;
+    const MidBwdLds m{base, base + 16 * 256, base + 2 * 16 * 256, base + MID_BWD_SMALL_LDS,
+                      base + MID_BWD_SMALL_LDS + MID_BWD_W_LDS};
+    mid_bwd_body<true>(mid, b, m, blockIdx.y == 0, MidSinkSmall{sdTf, sDelta});
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 4; ++c) dt[c] = c < dk ? sdTf[r * 4 + c] : 0.f;
+    del = sDelta[r];
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      gk[c] = c < dk ? Gf[r * dk + c] : 0.f;
+      dt[c] = c < dk ? dTf[((int64_t)b * R + r) * dk + c] : 0.f;
+    }
+    lse = LSE[(int64_t)b * R + r];
+    del = Delta[(int64_t)b * Rp + r];
+    if (len > 0) fetch_points(X + (int64_t)b * N * dk, len < CH ? len : CH, dk, xr);
+  }
   for (int n0 = 0; n0 < len; n0 += CH) {
     const int cn = (len - n0 < CH) ? len - n0 : CH;
     // [pair of points][component][2] (as k_mab0_attn_small): two points per packed-fp32 instruction;
@@ -899,8 +991,8 @@ int mab0_bwd_small_launch(const float* X, const float* Gf, const float* dTf, con
                           const float* Delta, int B, int N, int R, int Rp, int dk, float* DG,
                           const int32_t* lengths, hipStream_t st, float* slabs) {
   PCA_REQUIRE(R == 64 || R == 128 || R == 256, "mab0_bwd_small: %d score rows", R);
-  hipLaunchKernelGGL(k_mab0_bwd_small, dim3(B, small_row_split(B, R)), dim3(256), 0, st, X, Gf, dTf,
-                     LSE, Delta, N, R, Rp, dk, DG, lengths, slabs);
+  hipLaunchKernelGGL(k_mab0_bwd_small<false>, dim3(B, small_row_split(B, R)), dim3(256), 0, st, X, Gf,
+                     dTf, LSE, Delta, N, R, Rp, dk, DG, lengths, slabs, MidBwdArgs{});
   return check_launch("k_mab0_bwd_small");
 }
 
@@ -942,7 +1034,10 @@ size_t mab0_bf16_bwd_ws_bytes(const pca_mab_shape& s) {
 int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
                      const pca_mab_params& p, const void* saved, const float* dH, float* dI,
                      void* dX, int dk_accumulate, const pca_mab_grads& gr, void* ws, int flags,
-                     hipStream_t st, StepCtx* ctx) {
+                     hipStream_t st, StepCtx* ctx, const MidBwdLaunch* mid) {
+  PCA_REQUIRE(mid == nullptr || (s.d == 128 && s.nq == 16 && s.h == 4 && (flags & PCA_F_SKIP_HEAD) &&
+                                 !(flags & PCA_F_ATTN_DONE)),
+              "mab0_bf16_bwd: the mid chain fuses into an ISAB's few-queries block only");
   if (s.d == 256)
     return mab0_d256_bwd(s, I, X, p, saved, dH, dI, dX, dk_accumulate, gr, ws, st, ctx);
   BwdDefer* const defer = defer_of(ctx);
@@ -962,7 +1057,8 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
 
   const size_t el = (2 * (size_t)m * d + (size_t)Rp + (size_t)d) * sizeof(float);   // + split scratch
   if (head_done) {
-    // dZ, dO, Th, dT images, Delta, LSEp and dQs come from k_mid_bwd
+    // dZ, dO, Th, dT images, Delta, LSEp and dQs come from k_mid_bwd, or (mid != null) from the
+    // mid chain in the prologue of the launch below
   } else if (m > 2)
     hipLaunchKernelGGL((k_mab0_epi_bwd<8>), dim3(s.B), dim3(256), el, st, dH, v.Z, v.T, v.LSE, p.wo,
                        p.wv, m, d, dk, h, Rp, w.dZ, w.dO, w.Th, small ? w.dTf : nullptr,
@@ -979,9 +1075,22 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
   if (small) {
     // slab mode: per-set partials [B][R][dk] instead of atomics, summed in a fixed order
     float* sl = (wgrad_slabs_on() && (R * dk) % 4 == 0) ? w.slabs : nullptr;
-    hipLaunchKernelGGL(k_mab0_bwd_small, dim3(s.B, (R % 64 == 0 && R <= 512) ? 2 : 1), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(X), v.Gf, w.dTf, v.LSE,
-                       w.Delta, s.nk, R, Rp, dk, w.DG, s.k_lengths, sl);
+    const dim3 sgrid(s.B, (R % 64 == 0 && R <= 512) ? 2 : 1);
+    if (mid != nullptr) {
+      PCA_REQUIRE(R == 64, "mab0_bf16_bwd: fused mid chain with %d score rows", R);
+      static std::once_flag once_small;
+      std::call_once(once_small, [] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_mab0_bwd_small<true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, MID_SMALL_FUSE_LDS);
+      });
+      hipLaunchKernelGGL(k_mab0_bwd_small<true>, sgrid, dim3(256), MID_SMALL_FUSE_LDS, st,
+                         reinterpret_cast<const float*>(X), v.Gf, w.dTf, v.LSE, w.Delta, s.nk, R, Rp, dk,
+                         w.DG, s.k_lengths, sl, mid_bwd_args(*mid));
+    } else {
+      hipLaunchKernelGGL(k_mab0_bwd_small<false>, sgrid, dim3(256), 0, st,
+                         reinterpret_cast<const float*>(X), v.Gf, w.dTf, v.LSE, w.Delta, s.nk, R, Rp, dk,
+                         w.DG, s.k_lengths, sl, MidBwdArgs{});
+    }
     PCA_TRY(check_launch("k_mab0_bwd_small"));
     if (sl != nullptr) {
       // (only the first R * dk floats of the [Rp][dk] block are read by the post stage)
@@ -1011,9 +1120,15 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
   } else {
     const int S = mab0_bwd_splits(s);
     Mab0BwdArgs a{X, v.Gb, v.GtP, w.dTb, w.dTt, w.LSEp, w.Delta, dX, w.DG, s.B, s.nk,
-                  dk_accumulate ? 1 : 0, S, s.k_lengths, R, w.slabs};
+                  dk_accumulate ? 1 : 0, S, s.k_lengths, R, w.slabs, 0, MidBwdArgs{}};
     size_t lds = 2 * (size_t)Rp * 256 + 2 * (size_t)128 * Rp * 2 + 2 * 4 * 32 * 256 +
                  2 * Rp * sizeof(float);
+    if (mid != nullptr) {
+      PCA_REQUIRE(Rp == 64, "mab0_bf16_bwd: fused mid chain with %d score rows", Rp);
+      a.fuse_mid = 1;
+      a.mid = mid_bwd_args(*mid);
+      lds += MID_BWD_SMALL_LDS;       // dKp / dVp / dO_j images of the chain, behind the statistics
+    }
     if (lds < (size_t)4 * Rp * 128 * 4) lds = (size_t)4 * Rp * 128 * 4;     // merge slabs
     static std::once_flag once;
     std::call_once(once, [] {

@@ -454,10 +454,13 @@ int terminal_launch(const BwdDefer& D, hipStream_t st, const SlabSumJobs* late =
 int wgrad128_defer(BwdDefer* defer, const WgradJobs& jobs, bool bf16, int rows_per_wg,
                    hipStream_t st);
 // ctx->defer non-null: the post job is appended there instead of being launched
+// mid non-null (an ISAB's few-queries block, with PCA_F_SKIP_HEAD): the per-set mid chain of
+// mid_bwd_launch runs in the prologue of the attention backward instead of as a launch before it;
+// its zero_ptr is ignored (the caller has the accumulator cleared by an earlier launch)
 int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
                      const pca_mab_params& p, const void* saved, const float* dH, float* dI,
                      void* dX, int dk_accumulate, const pca_mab_grads& gr, void* ws, int flags,
-                     hipStream_t st, StepCtx* ctx = nullptr);
+                     hipStream_t st, StepCtx* ctx = nullptr, const MidBwdLaunch* mid = nullptr);
 // d = 256 / 8 heads (d256_host.hip): the many-queries backward and the few-queries block
 size_t mab1_d256_bwd_ws_bytes(const pca_mab_shape& s);
 int mab1_d256_bwd(const pca_mab_shape& s, const void* X, const float* H, const pca_mab_params& p,
