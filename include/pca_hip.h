@@ -393,6 +393,30 @@ int pca_cross_entropy(const float* logits, const int64_t* labels, int B, int C,
 int pca_eval_tally(const float* logits, const int64_t* labels, int B, int C, int64_t* counts,
                    int slot, void* stream);
 
+/* Clip-level aggregation of frame (or chunk) logits: per clip the mean log-probability, the votes of
+ * its frames and the two predictions the audio-classification literature reports
+ * replaces: nothing.  Code/pceval.py:95 (and the lines pca_eval_tally names) score frames; the
+ *           reference never aggregates over the frames of a clip.  ESC-50 / UrbanSound8K label clips.
+ * logits[n_sets, C] fp32; clip_offsets[n_clips + 1] int64, non-decreasing: clip c owns rows
+ * [off[c], off[c + 1]) (clamped to [0, n_sets], so a bad offset cannot read outside logits).  Per row:
+ * log_softmax (fp32, row maximum and log-sum-exp) summed over the clip, and the row's argmax - as
+ * torch.argmax: the first maximum wins, NaN counts as the maximum - added to a histogram.
+ * Outputs, each nullable:
+ *   mean_logprob[n_clips, C] fp32 = sum of log_softmax / number of rows;
+ *   votes[n_clips, C] int32       = rows whose argmax is the class;
+ *   pred[n_clips, 2] int64        = [0] vote rule: most votes, ties to the higher mean log-prob (ordered
+ *                                   as the argmax orders values), then to the lower class;
+ *                                   [1] mean rule: argmax of mean_logprob, first maximum.
+ * A clip without rows writes zeros and pred = -1 and is not tallied.
+ * labels[n_clips] int64 and counts int64, both or neither:
+ *   counts[2 * slot + r] += #{c : pred[c, r] == labels[c]}.
+ * One workgroup per clip; its four waves walk the rows four apart and their partial sums are merged in
+ * wave order.  No floating-point atomics: the same call gives the same bits; the counts are integer
+ * adds.  Each logit is read once. */
+int pca_clip_aggregate(const float* logits, int64_t n_sets, int C, const int64_t* clip_offsets,
+                       int n_clips, const int64_t* labels, float* mean_logprob, int32_t* votes,
+                       int64_t* pred, int64_t* counts, int slot, void* stream);
+
 /* torch.optim.Adam(lr, betas, eps, weight_decay) with COUPLED L2, one fused pass
  * over a flat parameter vector.  replaces: Code/settransformer.py:89-91,106,108
  * (optimizer.zero_grad + optimizer.step).

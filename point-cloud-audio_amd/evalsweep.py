@@ -28,6 +28,9 @@ The other set-model experiments run here at batch scale too:
   sets) and Code/pc_temp3d_eval.py:109-201 (3ST, per-chunk point sets);
 * ``importance_sweep``: importance-sampled sets, Code/rebut_expts.py:55-149;
 * ``reframe_sweep_temporal``: the (Fs, N) re-framing of the 3ST, Code/pc_temp3d_eval.py:56-107.
+* ``clip_accuracy``: the clip-level scores the datasets' literature reports (majority vote and mean
+  log-probability over a clip's frames or chunks, ``pca_hip.clip_aggregate``) next to the frame score;
+  no reference counterpart - Code/pceval.py:95 scores frames.
 * ``baseline_subsample_sweep``, ``baseline_reframe_sweep``, ``baseline_reframe_sweep_temporal``: the
   same experiments for the fixed-input baselines FB and CNN_temp (Code/baseline_eval.py,
   Code/baseline_temp_eval.py) on pca_hip.BaselineEngine, the selection fused into the forward launch.
@@ -58,7 +61,7 @@ __all__ = ["reframe_sweep", "framewise_dataset", "default_list_K", "sweep_draw",
            "importance_sweep", "chunk_plan", "temporal_axes", "temporal_dataset",
            "reframe_sweep_temporal", "baseline_subsample_sweep", "baseline_frames",
            "baseline_chunks", "baseline_reframe_sweep", "baseline_reframe_sweep_temporal",
-           "trim_dB_of", "trim_clips"]
+           "trim_dB_of", "trim_clips", "clip_accuracy"]
 
 
 def trim_dB_of(config: Dict) -> Optional[float]:
@@ -504,6 +507,94 @@ def reframe_sweep_temporal(model, clips: Sequence[torch.Tensor], labels: Sequenc
                     [(0, 0, 0, full)], select, counts)
         accs.append(int(counts.item()) / full)                # the one host sync of this N
     out = {"data": {fs: accs}, "list_Fs": [fs], "list_N": list_N}
+    _write_json(out, json_file)
+    return out
+
+
+# ---- clip-level evaluation (no reference counterpart: Code/pceval.py:95 scores frames) ---------------
+@torch.no_grad()
+def clip_accuracy(model, clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float, N: int,
+                  Ntemp: Optional[int] = None, n_fft: Optional[int] = None,
+                  trim_dB: Optional[float] = None, mode: int = _lib.MODE_F32,
+                  batch_size: Optional[int] = None, json_file: Optional[str] = None,
+                  hf: float = 0.5) -> Dict:
+    """Frame-level and clip-level accuracy of ``model`` on ``clips`` analysed with window length N:
+    every frame of every clip (framewise_dataset, an FST model) or, with ``Ntemp``, every whole
+    Ntemp-frame chunk (temporal_dataset, a 3ST model) is one set, and a clip's prediction is taken
+    over its sets by majority vote and by mean log-probability (pca_hip.clip_aggregate).
+
+    Unlike the re-framing sweeps every set counts (a clip's score needs all of its sets, so no short
+    batch is dropped).  The engine runs ``batch_size`` sets per call (default: SETS_PER_CALL, halved
+    until the workspace fits WS_BUDGET) and its logits are kept in one device [n_sets, C] buffer;
+    one clip_aggregate call and one pca_eval_tally call score it, and the host reads the three
+    counters once, at the end - nothing waits for the device per batch.
+    ``trim_dB``: trim every clip first (pca_hip.trim_batch: its read of the bounds is one more host
+    read for the whole corpus, before any set is evaluated).  A clip that yields no set - n_fft / 2
+    samples or fewer (after the trim), where the STFT has no frame to centre, or fewer than Ntemp
+    frames - is counted in ``n_empty`` and left out of the clip scores, not refused.
+    ``n_fft``: the datasets analyse with 2**ceil(log2 N); a value given must be that one.
+
+    Returns (and optionally writes) ``{"frame", "clip_vote", "clip_mean", "n_sets", "n_clips",
+    "n_empty"}``: correct sets / n_sets - what pca_eval_tally counts on the same logits - and correct
+    clips / (n_clips - n_empty) under the two rules; NaN where the denominator is 0."""
+    N = int(N)
+    pow2 = _pow2_fft([N])
+    if n_fft is not None and int(n_fft) != pow2:
+        raise ValueError(f"n_fft={n_fft}: the datasets analyse N={N} with n_fft={pow2}")
+    assert len(clips) == len(labels)
+    clips = list(clips)
+    if trim_dB is not None and clips:
+        clips, _ = pca_hip.trim_batch(clips, top_db=trim_dB)
+    hop = int(N * hf)
+    L = _lib.lib()
+    keep = [c for c, x in enumerate(clips) if int(x.numel()) > pow2 // 2]
+    sets_of = [0] * len(clips)                     # sets per clip, in corpus order
+    for c in keep:
+        t = int(L.pca_stft_num_frames(int(clips[c].numel()), hop))
+        sets_of[c] = t if Ntemp is None else t // int(Ntemp)
+    n_sets, n_clips = sum(sets_of), len(clips)
+    n_empty = sum(1 for n in sets_of if n == 0)
+    nan = float("nan")
+    out = {"frame": nan, "clip_vote": nan, "clip_mean": nan, "n_sets": n_sets, "n_clips": n_clips,
+           "n_empty": n_empty}
+    if n_sets == 0:
+        _write_json(out, json_file)
+        return out
+    kept, klab = [clips[c] for c in keep], [int(labels[c]) for c in keep]
+    if Ntemp is None:
+        ds, ids, din = framewise_dataset(kept, klab, fs, N, hf), None, 2
+        assert len(ds) == n_sets, (len(ds), n_sets)
+    else:
+        (ds, ids), din = temporal_dataset(kept, klab, fs, N, int(Ntemp), hf), 3
+        assert ids.numel() == n_sets, (ids.numel(), n_sets)
+    dev = _model_device(model)
+    npts = ds.num_points
+    cap = min(_sets_per_call(model, npts, mode, batch_size), n_sets)
+    offs = np.concatenate([[0], np.cumsum(sets_of)]).astype(np.int64)
+    offs_d = torch.as_tensor(offs).to(dev)
+    clip_lab = torch.as_tensor(np.asarray([int(y) for y in labels], dtype=np.int64)).to(dev)
+    set_lab = torch.empty(n_sets, dtype=torch.int64, device=dev)
+    X = torch.empty((cap, npts, din), dtype=torch.float32, device=dev)
+    logits, engines, done = None, {}, 0
+    while done < n_sets:
+        b = min(cap, n_sets - done)
+        if b not in engines:
+            engines[b] = STEngine(model, b, npts, mode, training=False)
+            assert engines[b].cfg.k == 1, "one prediction per set (PMA with one seed)"
+        eng = engines[b]
+        if logits is None:
+            logits = torch.empty((n_sets, eng.cfg.C), dtype=torch.float32, device=dev)
+        pos = torch.arange(done, done + b, dtype=torch.int64, device=dev)
+        ds.batch(pos if ids is None else ids[pos], out=X[:b], labels_out=set_lab[done:done + b])
+        logits[done:done + b].copy_(eng.forward(X[:b]))
+        done += b
+    counts = torch.zeros(3, dtype=torch.int64, device=dev)
+    pca_hip.clip_aggregate(logits, offs_d, clip_lab, counts, 0)      # counts[0], counts[1]
+    pca_hip.eval_tally(logits, set_lab, counts, 2)
+    vote, mean, frame = counts.tolist()                               # the one host read
+    out["frame"] = frame / n_sets
+    out["clip_vote"] = vote / (n_clips - n_empty)
+    out["clip_mean"] = mean / (n_clips - n_empty)
     _write_json(out, json_file)
     return out
 

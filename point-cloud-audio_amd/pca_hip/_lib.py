@@ -98,6 +98,8 @@ SIGNATURES = {
     "pca_cross_entropy": (C.c_int, [c_fp, c_i64p, C.c_int, C.c_int, C.c_float, c_fp, c_fp,
                                     c_fp, c_vp]),
     "pca_eval_tally": (C.c_int, [c_fp, c_i64p, C.c_int, C.c_int, c_i64p, C.c_int, c_vp]),
+    "pca_clip_aggregate": (C.c_int, [c_fp, C.c_int64, C.c_int, c_i64p, C.c_int, c_i64p, c_fp, c_vp,
+                                     c_i64p, c_i64p, C.c_int, c_vp]),
     "pca_debug_poison_lds": (C.c_int, [c_vp]),
     "pca_subsample_points": (C.c_int, [c_fp, C.c_int64, C.c_int64, C.c_int64, c_fp, c_fp, c_vp,
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

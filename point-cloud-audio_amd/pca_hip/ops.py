@@ -330,6 +330,40 @@ def eval_tally(logits: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor,
     return counts
 
 
+def clip_aggregate(logits: torch.Tensor, offsets: torch.Tensor,
+                   labels: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                   slot: int = 0):
+    """Per-clip aggregation of frame (or chunk) logits on the device (pca_clip_aggregate): no host
+    sync.  logits [n_sets, C] float32; offsets int64[n_clips + 1], non-decreasing: clip c owns rows
+    offsets[c] : offsets[c + 1].  Returns (pred, mean_logprob, votes):
+    mean_logprob [n_clips, C] float32, the mean of log_softmax over the clip's rows; votes
+    [n_clips, C] int32, the rows whose argmax (as torch.argmax) is the class; pred int64
+    [n_clips, 2], column 0 by votes (ties to the higher mean log-prob, then the lower class),
+    column 1 by mean log-prob.  A clip without rows gets zeros and pred -1.
+    With ``labels`` int64[n_clips] and ``counts`` int64 (both or neither):
+    counts[2 * slot] += clips the vote rule gets right, counts[2 * slot + 1] += the mean rule's."""
+    _need_cuda(logits, offsets, labels, counts)
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
+    assert offsets.dim() == 1 and offsets.dtype == torch.int64 and offsets.is_contiguous()
+    assert offsets.numel() >= 1 and logits.shape[1] >= 1
+    n_sets, Cc = logits.shape
+    n_clips = offsets.numel() - 1
+    assert (labels is None) == (counts is None), "labels and counts go together"
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == n_clips
+        assert counts.dtype == torch.int64 and counts.is_contiguous()
+        assert 0 <= slot and 2 * slot + 1 < counts.numel()
+    with torch.cuda.device(logits.device):
+        mean = torch.empty((n_clips, Cc), dtype=torch.float32, device=logits.device)
+        votes = torch.empty((n_clips, Cc), dtype=torch.int32, device=logits.device)
+        pred = torch.empty((n_clips, 2), dtype=torch.int64, device=logits.device)
+        check(lib().pca_clip_aggregate(_ptr(logits), n_sets, Cc, _ptr(offsets), n_clips,
+                                       _ptr(labels), _ptr(mean), _ptr(votes), _ptr(pred),
+                                       _ptr(counts), int(slot), _stream(logits)),
+              "pca_clip_aggregate")
+    return pred, mean, votes
+
+
 # --------------------------------------------------------------------------- #
 # feature extraction                                                           #
 # --------------------------------------------------------------------------- #
