@@ -417,6 +417,32 @@ int pca_clip_aggregate(const float* logits, int64_t n_sets, int C, const int64_t
                        int n_clips, const int64_t* labels, float* mean_logprob, int32_t* votes,
                        int64_t* pred, int64_t* counts, int slot, void* stream);
 
+/* Held-out metrics of a whole logit buffer: loss, top-1 / top-k, the confusion matrix and per-row results
+ * replaces: Code/settransformer.py:121-130 (and settransformertemp.py's twin): per test batch
+ *           criterion(preds, lbls).item(), preds.argmax(dim=1), the compare, the sum and its .item().
+ * logits[n_rows, C] fp32, labels[n_rows] int64, topk >= 1.  Per row:
+ *   loss = logsumexp(row) - row[label], the row maximum and the sum of exponentials in fp32;
+ *   pred = argmax as torch.argmax (pca_eval_tally, pca_clip_aggregate): the first maximum wins, NaN
+ *          counts as the maximum;
+ *   rank = number of classes that come before the label's class in that same order: 0 exactly when
+ *          pred == label; the row is top-k correct when rank < topk.
+ * A row whose label is outside [0, C) is skipped: it is counted as skipped and as nothing else, adds no
+ * loss and no confusion cell, and writes row_loss 0, its argmax and row_rank -1.
+ * Outputs, each nullable:
+ *   row_loss[n_rows] fp32, row_pred[n_rows] int64, row_rank[n_rows] int32;
+ *   counts int64: counts[4 * slot + {0, 1, 2, 3}] += {rows scored, top-1 correct, top-k correct, rows
+ *                 skipped} (integer adds);
+ *   confusion[C, C] int64: confusion[label, pred] += 1 per scored row (integer adds);
+ *   loss_sum double[1]: += the sum of the scored rows' losses, accumulated in fp64 in a fixed order
+ *                 (fixed row blocks per workgroup, partials merged in index order).
+ * No floating-point atomics: the same call gives the same bits, eagerly and under graph replay.
+ * ws: pca_eval_metrics_ws_bytes(n_rows) bytes, needed with counts or loss_sum; the library never
+ * allocates.  C <= 64: a lane per row over rows staged in LDS; wider rows: a wave per row.  Enqueues only. */
+int pca_eval_metrics(const float* logits, const int64_t* labels, int64_t n_rows, int C, int topk,
+                     float* row_loss, int64_t* row_pred, int32_t* row_rank, int64_t* counts, int slot,
+                     int64_t* confusion, double* loss_sum, void* ws, void* stream);
+size_t pca_eval_metrics_ws_bytes(int64_t n_rows);
+
 /* torch.optim.Adam(lr, betas, eps, weight_decay) with COUPLED L2, one fused pass
  * over a flat parameter vector.  replaces: Code/settransformer.py:89-91,106,108
  * (optimizer.zero_grad + optimizer.step).

@@ -100,7 +100,10 @@ SIGNATURES = {
     "pca_eval_tally": (C.c_int, [c_fp, c_i64p, C.c_int, C.c_int, c_i64p, C.c_int, c_vp]),
     "pca_clip_aggregate": (C.c_int, [c_fp, C.c_int64, C.c_int, c_i64p, C.c_int, c_i64p, c_fp, c_vp,
                                      c_i64p, c_i64p, C.c_int, c_vp]),
-    "pca_debug_poison_lds": (C.c_int, [c_vp]),
+    "pca_eval_metrics": (C.c_int, [c_fp, c_i64p, C.c_int64, C.c_int, C.c_int, c_fp, c_i64p, c_vp,
+                                   c_i64p, C.c_int, c_i64p, c_vp, c_vp, c_vp]),
+    "pca_eval_metrics_ws_bytes": (C.c_size_t, [C.c_int64]),
+    "pca_debug_poison_lds":(C.c_int, [c_vp]),
     "pca_subsample_points": (C.c_int, [c_fp, C.c_int64, C.c_int64, C.c_int64, c_fp, c_fp, c_vp,
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_uint64, C.c_uint64, c_vp, c_fp, c_vp, c_vp, c_vp,

@@ -364,6 +364,50 @@ def clip_aggregate(logits: torch.Tensor, offsets: torch.Tensor,
     return pred, mean, votes
 
 
+def eval_metrics(logits: torch.Tensor, labels: torch.Tensor, topk: int = 5,
+                 counts: Optional[torch.Tensor] = None, slot: int = 0,
+                 confusion: Optional[torch.Tensor] = None,
+                 loss_sum: Optional[torch.Tensor] = None, rows: bool = False):
+    """Held-out metrics of a whole logit buffer on the device (pca_eval_metrics): no host sync.
+    logits [n_rows, C] float32, labels int64[n_rows].  Per row: loss = logsumexp - logit of the label,
+    pred = argmax as torch.argmax, rank = classes ordered before the label's (top-k correct when
+    rank < topk); a row whose label is outside [0, C) is skipped and counted as skipped.
+    Accumulated into the caller's device tensors, each optional:
+    counts int64: counts[4 * slot + {0, 1, 2, 3}] += {scored, top-1 correct, top-k correct, skipped};
+    confusion int64 [C, C]: confusion[label, pred] += 1; loss_sum float64[1] += sum of the losses
+    (fp64, fixed order: bit-reproducible).
+    Returns (row_loss float32, row_pred int64, row_rank int32) with ``rows``, else None."""
+    _need_cuda(logits, labels, counts, confusion, loss_sum)
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
+    assert labels.dtype == torch.int64 and labels.is_contiguous()
+    n, Cc = logits.shape
+    assert labels.numel() == n and Cc >= 1 and topk >= 1
+    if counts is not None:
+        assert counts.dtype == torch.int64 and counts.is_contiguous()
+        assert 0 <= slot and 4 * slot + 3 < counts.numel()
+    if confusion is not None:
+        assert confusion.dtype == torch.int64 and confusion.is_contiguous()
+        assert tuple(confusion.shape) == (Cc, Cc)
+    if loss_sum is not None:
+        assert loss_sum.dtype == torch.float64 and loss_sum.numel() >= 1
+    L = lib()
+    dev = logits.device
+    with torch.cuda.device(dev):
+        out = (None, None, None)
+        if rows:
+            out = (torch.empty(n, dtype=torch.float32, device=dev),
+                   torch.empty(n, dtype=torch.int64, device=dev),
+                   torch.empty(n, dtype=torch.int32, device=dev))
+        ws = None
+        if counts is not None or loss_sum is not None:
+            ws = _bytes(L.pca_eval_metrics_ws_bytes(n), logits)
+        check(L.pca_eval_metrics(_ptr(logits), _ptr(labels), n, Cc, int(topk), _ptr(out[0]),
+                                 _ptr(out[1]), _ptr(out[2]), _ptr(counts), int(slot),
+                                 _ptr(confusion), _ptr(loss_sum), _ptr(ws), _stream(logits)),
+              "pca_eval_metrics")
+    return out if rows else None
+
+
 # --------------------------------------------------------------------------- #
 # feature extraction                                                           #
 # --------------------------------------------------------------------------- #

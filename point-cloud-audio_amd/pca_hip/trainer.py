@@ -96,15 +96,30 @@ class ShardedIndexStream:
     def per_rank(self) -> int:
         return self.n // self.world
 
+    def _share(self, epoch: int) -> torch.Tensor:
+        """This rank's share of the permutation of ``epoch``: a function of (seed, epoch) alone."""
+        per = self.per_rank()
+        if self.shuffle:
+            g = torch.Generator(device="cpu").manual_seed(self.seed + epoch)
+            perm = torch.randperm(self.n, generator=g)
+        else:
+            perm = torch.arange(self.n)
+        return perm[self.rank:per * self.world:self.world].contiguous().to(self.device)
+
+    def state(self) -> dict:
+        """(seed, epoch, cursor): all it takes to hand out the remaining batches again."""
+        return dict(seed=int(self.seed), epoch=int(self.epoch), cursor=int(self._cursor))
+
+    def load_state(self, state: dict) -> None:
+        """Continue where ``state()`` was taken; the current permutation is re-derived, not stored."""
+        self.seed, self.epoch = int(state["seed"]), int(state["epoch"])
+        self._cursor = int(state["cursor"])
+        self._perm = self._share(self.epoch - 1) if self.epoch > 0 else None
+
     def next(self) -> torch.Tensor:
         per = self.per_rank()
         if self._perm is None or self._cursor + self.B > per:
-            if self.shuffle:
-                g = torch.Generator(device="cpu").manual_seed(self.seed + self.epoch)
-                perm = torch.randperm(self.n, generator=g)
-            else:
-                perm = torch.arange(self.n)
-            self._perm = perm[self.rank:per * self.world:self.world].contiguous().to(self.device)
+            self._perm = self._share(self.epoch)
             self._cursor = 0
             self.epoch += 1
         out = self._perm[self._cursor:self._cursor + self.B]
@@ -198,15 +213,23 @@ class STEngine:
         assert tuple(lengths.shape) == (B,), lengths.shape
         return lengths.data_ptr()
 
-    def forward(self, X: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """lengths (optional, device int32[B]): valid points per set of a padded batch."""
+    def forward(self, X: torch.Tensor, lengths: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """lengths (optional, device int32[B]): valid points per set of a padded batch.
+        out (optional, device float32 [B * k, C], contiguous): where the logits go instead of the
+        engine's own buffer (e.g. a slice of the buffer that holds a whole pass)."""
         assert X.is_cuda and X.dtype == torch.float32 and X.is_contiguous()
         assert tuple(X.shape) == (self.cfg.B, self.cfg.N, self.cfg.din), X.shape
+        if out is None:
+            out = self.logits
+        else:
+            assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+            assert tuple(out.shape) == tuple(self.logits.shape), out.shape
         check(lib().pca_st_forward(C.byref(self.cfg), self.flat.data_ptr(), X.data_ptr(),
-                                   self._len_ptr(lengths, self.cfg.B), self.logits.data_ptr(),
+                                   self._len_ptr(lengths, self.cfg.B), out.data_ptr(),
                                    self.ws.data_ptr(), self._stream()),
               "pca_st_forward")
-        return self.logits
+        return out
 
     def fwd_bwd(self, X: torch.Tensor, labels: torch.Tensor, phase: int = -1,
                 grad_scale: float = 1.0, lengths: Optional[torch.Tensor] = None) -> None:
@@ -282,6 +305,8 @@ class Trainer:
         self._cursor_mode = callable(getattr(dataset, "batch_seq", None))
         self._k = 0                       # optimiser steps issued so far (host copy)
         self.g0 = self.g1 = self.g2 = None
+        self._draw_frozen = None          # see _capture
+        self._evaluator = None            # fit's held-out pass, built once
         self.indices = ShardedIndexStream(len(dataset), self.B, self.rank, self.world, seed,
                                           shuffle, self.dev)
         if self.world > 1:      # identical initial weights on every rank (rank 0's)
@@ -424,6 +449,8 @@ class Trainer:
                 self._seg1()
             with torch.cuda.graph(self.g2, pool=self.g0.pool(), **mode):
                 self._seg2()
+        # a stochastic dataset's host draw number is a by-value argument: the capture froze this one
+        self._draw_frozen = getattr(self.ds, "_draw", None)
         for dst, src in zip((self.eng.flat, self.m, self.v, self.step_count, self.eng.stats),
                             snap):
             dst.copy_(src)
@@ -441,6 +468,7 @@ class Trainer:
             self._k += 1
         else:
             self.idx.copy_(self._next_indices(), non_blocking=True)
+            self._k += 1
         if self.use_graph and self.g0 is None:
             self._capture()
         main = torch.cuda.current_stream(self.dev)
@@ -487,6 +515,98 @@ class Trainer:
             self.eng.stats.zero_()
         return float(out[0]), float(out[1])
 
+    # ---- exact resume ----------------------------------------------------------------
+    def state_dict(self) -> dict:
+        """Everything the next step depends on, as CPU tensors and plain values (one host sync): legal
+        at any step boundary, mid-epoch included.  The staged epoch sequence and the current
+        permutation are not stored: ``load_state_dict`` re-derives them from (seed, epoch)."""
+        cpu = lambda t: t.detach().to("cpu").clone()
+        return dict(format=1, B=self.B, N=self.N, mode=int(self.eng.cfg.mode), world=int(self.world),
+                    flat=cpu(self.eng.flat), m=cpu(self.m), v=cpu(self.v),
+                    step_count=int(self.step_count[0].item()), k=int(self._k),
+                    epoch_base=int(self.epoch_base.item()), stats=cpu(self.eng.stats),
+                    stream=self.indices.state(),
+                    # stochastic datasets: the host half of the draw number (the device half is
+                    # step_count); a captured step froze draw_frozen
+                    draw=getattr(self.ds, "_draw", None), draw_frozen=self._draw_frozen)
+
+    def load_state_dict(self, state: dict) -> None:
+        """Continue a run bit for bit from ``state_dict()``.  B, N, mode and world must be this
+        trainer's (a mismatch raises and names the field).  Captured graphs are dropped: the next
+        step re-captures."""
+        mine = dict(B=self.B, N=self.N, mode=int(self.eng.cfg.mode), world=int(self.world))
+        for name, have in mine.items():
+            if int(state[name]) != have:
+                raise ValueError(f"checkpoint mismatch: {name} is {state[name]} in the checkpoint, "
+                                 f"{have} in this trainer")
+        if state["flat"].numel() != self.eng.flat.numel():
+            raise ValueError(f"checkpoint mismatch: parameters is {state['flat'].numel()} in the "
+                             f"checkpoint, {self.eng.flat.numel()} in this trainer")
+        torch.cuda.synchronize(self.dev)
+        self.g0 = self.g1 = self.g2 = None
+        # into the vectors the engines (and the module's parameters) are views of, never a re-bind
+        self.eng.flat.copy_(state["flat"])
+        self.m.copy_(state["m"])
+        self.v.copy_(state["v"])
+        self.eng.stats.copy_(state["stats"])
+        self.step_count.zero_()
+        self.step_count[0] = int(state["step_count"])
+        self.epoch_base.fill_(int(state["epoch_base"]))
+        self._k = int(state["k"])
+        self.indices.load_state(state["stream"])
+        if self._cursor_mode and self.indices.epoch > 0:
+            # the epoch in progress: its index batches as next_epoch() staged them
+            spe = self.indices.steps_per_epoch()
+            if self.seq is None:
+                self.seq = torch.empty(spe * self.B, dtype=torch.int64, device=self.dev)
+            self.seq.copy_(self.indices._perm[:spe * self.B])
+        if state.get("draw") is not None and hasattr(self.ds, "_draw"):
+            frozen = state.get("draw_frozen")
+            # the re-capture (one eager warm-up, one recorded call) must freeze the same number
+            self.ds._draw = int(frozen) - 2 if (self.use_graph and frozen is not None) \
+                else int(state["draw"])
+        self._draw_frozen = None
+
+    # ---- the reference's epoch loop --------------------------------------------------------
+    def fit(self, epochs: int, test_dataset=None, eval_every: int = 10,
+            checkpoint_path: Optional[str] = None, checkpoint_every: Optional[int] = None,
+            log=print) -> list:
+        """Code/settransformer.py:96-131: ``steps_per_epoch`` steps per epoch, the train loss and
+        accuracy of the epoch (one ``read_stats``), the held-out pass over ``test_dataset`` at
+        ``epoch % eval_every == 0`` (one ``Evaluator.run``), the reference's two lines through ``log``.
+        Starts at the epoch this trainer is in (0, or where a loaded state stopped; an epoch in
+        progress is finished first) and runs up to epoch ``epochs - 1``.  With ``checkpoint_path`` a
+        checkpoint (runfiles.save_checkpoint) is written every ``checkpoint_every`` epochs (default:
+        every epoch) and after the last.  The only host syncs are those reads (and a checkpoint's).
+        Returns one dict per epoch run: epoch, train_loss, train_acc and, where the held-out pass
+        ran, test_loss, test_acc, test_topk_acc."""
+        spe = self.indices.steps_per_epoch()
+        if test_dataset is not None and (self._evaluator is None
+                                         or self._evaluator.ds is not test_dataset):
+            self._evaluator = Evaluator(self.eng.model, test_dataset, self.B,
+                                        int(self.eng.cfg.mode), process_group=self.pg)
+        history = []
+        first = self._k // spe
+        for epoch in range(first, int(epochs)):
+            for _ in range(spe - (self._k - epoch * spe)):
+                self.step()
+            loss_sum, correct = self.read_stats()
+            seen = spe * self.B * self.world
+            entry = dict(epoch=epoch, train_loss=loss_sum / seen, train_acc=correct / seen)
+            log(f"Epoch {epoch}: train loss {entry['train_loss']:.3f} train acc "
+                f"{entry['train_acc']:.3f}")
+            if test_dataset is not None and epoch % eval_every == 0:
+                res = self._evaluator.run()
+                entry.update(test_loss=res["loss"], test_acc=res["acc"],
+                             test_topk_acc=res["topk_acc"])
+                log(f"Epoch {epoch}: test loss {res['loss']:.3f} test acc {res['acc']:.3f}")
+            history.append(entry)
+            if checkpoint_path is not None and self.rank == 0 and (
+                    (epoch + 1) % (checkpoint_every or 1) == 0 or epoch + 1 == int(epochs)):
+                import runfiles
+                runfiles.save_checkpoint(checkpoint_path, self)
+        return history
+
 
 @torch.no_grad()
 def evaluate(model, dataset, batch_size: int, mode: int = _lib.MODE_F32
@@ -508,3 +628,91 @@ def evaluate(model, dataset, batch_size: int, mode: int = _lib.MODE_F32
             correct += (logits.argmax(1) == lab).sum()
             done += b
     return float(correct) / max(n, 1), n
+
+
+class Evaluator:
+    """The held-out pass of Code/settransformer.py:117-131 as a persistent object.
+
+    Built once: one ``STEngine`` for full batches and one for the tail of this rank's shard, on the
+    flat parameter vector the model already has (``flatten_parameters`` is idempotent, so after a
+    ``Trainer`` was built on ``model`` these engines read the very vector its Adam step updates: no
+    copy, and a ``run()`` after a ``step()`` sees the new weights).  Rank r of ``process_group``
+    scores the contiguous shard [r * n // world, (r + 1) * n // world) in order; nothing is dropped.
+
+    ``run()``: every batch's logits go into one device buffer, one ``pca_eval_metrics`` call scores
+    it, the int64 counters and confusion matrix are all-reduced in one message and the fp64 loss in
+    another, and the host reads once.  Nothing waits on the device per batch.
+    """
+
+    def __init__(self, model, dataset, batch_size: int, mode: int = _lib.MODE_F32, topk: int = 5,
+                 process_group=None):
+        self.ds, self.topk, self.pg = dataset, int(topk), process_group
+        self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(process_group) if dist.is_initialized() else 0
+        self.n = len(dataset)
+        lo, hi = self.rank * self.n // self.world, (self.rank + 1) * self.n // self.world
+        self.n_local = hi - lo
+        self.B = max(1, min(int(batch_size), self.n_local))
+        N = int(dataset.num_points)
+        varlen = bool(getattr(dataset, "variable_length", False))
+        flat = flatten_parameters(model)
+        _need_cuda(flat)
+        self.dev = flat.device
+        self.engines = []                 # (engine, X, lengths), full batches first
+        for b in (self.B if self.n_local else 0, self.n_local % self.B):
+            if b:
+                eng = STEngine(model, b, N, mode, training=False)
+                assert eng.flat.data_ptr() == flat.data_ptr()
+                if eng.cfg.k != 1:
+                    raise _lib.PcaHipError(f"Evaluator scores one logit row per set; the model has "
+                                           f"{eng.cfg.k} outputs per set")
+                with torch.cuda.device(self.dev):
+                    X = torch.empty((b, N, eng.cfg.din), dtype=torch.float32, device=self.dev)
+                    ln = torch.zeros(b, dtype=torch.int32, device=self.dev) if varlen else None
+                self.engines.append((eng, X, ln))
+        self.C = int(st_config(model, 1, N, mode).C)
+        with torch.cuda.device(self.dev):
+            self.idx = torch.arange(lo, hi, dtype=torch.int64, device=self.dev)
+            self.logits = torch.empty((self.n_local, self.C), dtype=torch.float32, device=self.dev)
+            self.labels = torch.zeros(self.n_local, dtype=torch.int64, device=self.dev)
+            # [4 counters | C x C confusion | the fp64 loss sum's bits]: one buffer, one host read
+            self.acc = torch.zeros(4 + self.C * self.C + 1, dtype=torch.int64, device=self.dev)
+        self.counts = self.acc[:4]
+        self.confusion = self.acc[4:4 + self.C * self.C].view(self.C, self.C)
+        self.loss_sum = self.acc[4 + self.C * self.C:].view(torch.float64)
+
+    def _enqueue(self) -> None:
+        """The whole pass on the current stream: packs, forwards, one metrics call.  No host sync."""
+        from .ops import eval_metrics
+        done = 0
+        for eng, X, ln in self.engines:
+            b = eng.cfg.B
+            while done + b <= self.n_local:
+                kw = dict(lengths_out=ln) if ln is not None else {}
+                self.ds.batch(self.idx[done:done + b], out=X,
+                              labels_out=self.labels[done:done + b], **kw)
+                eng.forward(X, ln, out=self.logits[done:done + b])
+                done += b
+        assert done == self.n_local
+        self.acc.zero_()
+        if self.n_local:
+            eval_metrics(self.logits, self.labels, self.topk, self.counts, 0, self.confusion,
+                         self.loss_sum)
+
+    @torch.no_grad()
+    def run(self) -> dict:
+        """{"loss": per-sample mean, "acc", "topk_acc", "n": rows scored, "n_skipped",
+        "per_class_acc": float64 [C] (NaN for a class without rows), "confusion": int64 [C, C]
+        indexed [label, prediction]}, summed over the ranks.  One host read."""
+        self._enqueue()
+        if self.world > 1:
+            dist.all_reduce(self.acc[:-1], group=self.pg)
+            dist.all_reduce(self.loss_sum, group=self.pg)
+        host = self.acc.cpu()
+        scored, top1, topk, skipped = (int(v) for v in host[:4])
+        conf = host[4:-1].view(self.C, self.C).clone()
+        loss_sum = float(host[-1:].view(torch.float64)[0])
+        per_class = conf.diagonal().double() / conf.sum(1).double()
+        d = max(scored, 1)
+        return dict(loss=loss_sum / d, acc=top1 / d, topk_acc=topk / d, n=scored, n_skipped=skipped,
+                    per_class_acc=per_class, confusion=conf)

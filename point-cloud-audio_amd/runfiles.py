@@ -12,6 +12,11 @@ The key set and key order of the JSON follow the shipped files
 (``Code/model_saves/FST(...)_config.json``: ``numpy_seed``; ``3ST(...)_config.json``: ``Ntemp`` after
 ``trim_dB`` and ``np_seed``), so either side of the pair can be swapped with the reference's.
 Weights are read with ``torch.load(weights_only=True)`` only.
+
+A run file holds what evaluation needs.  A *checkpoint* (``save_checkpoint`` / ``load_checkpoint``, no
+reference counterpart) holds what the next training step needs - ``Trainer.state_dict()``: parameters,
+Adam moments, step counters, the index stream's position, the running statistics - so that a run that
+ends early continues bit for bit.
 """
 import json
 import os
@@ -23,7 +28,8 @@ from torch import nn
 
 from models import ST
 
-__all__ = ["ARCHITECTURES", "run_config", "save_run", "load_run"]
+__all__ = ["ARCHITECTURES", "run_config", "save_run", "load_run", "save_checkpoint",
+           "load_checkpoint"]
 
 ARCHITECTURES = {
     "FST": "FST (Framewise Set Transformer)",
@@ -107,3 +113,25 @@ def load_run(json_path: str, pth_path: Optional[str] = None, device=None,
     model = nn.DataParallel(model)
     model.load_state_dict(sd)
     return model, config
+
+
+def save_checkpoint(path: str, trainer, config: Optional[Dict] = None) -> str:
+    """Write ``trainer.state_dict()`` (and the run's config dict, if given) to ``path`` with
+    ``torch.save``: tensors and plain values only.  Written to a sibling file first and renamed, so a
+    run that is stopped while writing leaves the previous checkpoint whole.  Returns ``path``."""
+    state = dict(trainer=trainer.state_dict(), config=config)
+    directory = os.path.dirname(os.path.abspath(path))
+    os.makedirs(directory, exist_ok=True)
+    tmp = path + ".part"
+    torch.save(state, tmp)
+    os.replace(tmp, path)
+    return path
+
+
+def load_checkpoint(path: str, trainer) -> Optional[Dict]:
+    """Put ``trainer`` where the checkpoint's run stopped (``Trainer.load_state_dict``: a mismatch of
+    batch size, set size, mode or world size raises and names the field).  Read with
+    ``torch.load(weights_only=True)``.  Returns the config stored with it, or None."""
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    trainer.load_state_dict(state["trainer"])
+    return state.get("config")
