@@ -38,8 +38,6 @@
 
 #include <math.h>
 
-#include <mutex>
-
 namespace pca {
 
 namespace {
@@ -561,11 +559,6 @@ __global__ __launch_bounds__(64 * NW, 4) void k_attnc_bwd_kv(const AttnCoreArgs 
 // Staging: 4 d items of 4 rows x 4 features per chunk, 2 d threads (h = d / 32 waves): two items each.
 constexpr int T32 = 4;         // 16-row tiles per wave and group
 
-// 8 features of a [rows][d] fp32 row as a bf16 operand (p: the first of them; 32-byte aligned)
-__device__ __forceinline__ bf16x8 ld8_bf16(const float* p) {
-  const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
-  return pack8(f32x4{lo.x, lo.y, lo.z, lo.w}, f32x4{hi.x, hi.y, hi.z, hi.w});
-}
 // row form: streamed row `row`, head features 8 g .. 8 g + 7 (the A operand of a score product)
 __device__ __forceinline__ bf16x8 rd_row(const __bf16* Rw, int row, int d, int f0) {
   const __bf16* p = Rw + row * (d + 4) + f0;
@@ -619,7 +612,7 @@ __global__ __launch_bounds__(512) void k_attn32_fwd(const AttnCoreArgs a) {
 #pragma unroll
     for (int i = 0; i < T32; ++i) {
       const int qi = q0 + 16 * i + r < nq ? q0 + 16 * i + r : nq - 1;
-      qo[i] = ld8_bf16(Qb + (int64_t)qi * d + 8 * g);
+      qo[i] = gload8(Qb + (int64_t)qi * d + 8 * g);
       m[i] = -INFINITY; l[i] = 0.f;
       acc[i][0] = z4; acc[i][1] = z4;
     }
@@ -748,8 +741,8 @@ __global__ __launch_bounds__(512) void k_attn32_bwd_q(const AttnCoreArgs a) {
         dl += d4.x * (o4.x - q4.x) + d4.y * (o4.y - q4.y) + d4.z * (o4.z - q4.z) + d4.w * (o4.w - q4.w);
       }
       const float delta = wave16_sum(dl);
-      qo[i] = ld8_bf16(qp);
-      dob[i] = ld8_bf16(a.dO + orow);
+      qo[i] = gload8(qp);
+      dob[i] = gload8(a.dO + orow);
       nlse[i] = -a.LSE[((int64_t)b * a.h + j) * nq + qi];
       nds[i] = -delta * a.scale;
       acc[i][0] = z4; acc[i][1] = z4;
@@ -852,8 +845,8 @@ __global__ __launch_bounds__(512) void k_attn32_bwd_kv(const AttnCoreArgs a) {
     for (int i = 0; i < T32; ++i) {
       const int ki = k0 + 16 * i + r < nk ? k0 + 16 * i + r : nk - 1;
       const int64_t o = ((int64_t)b * nk + ki) * d + j * 32 + 8 * g;
-      kb[i] = ld8_bf16(a.Kp + o);
-      vb[i] = ld8_bf16(a.Vp + o);
+      kb[i] = gload8(a.Kp + o);
+      vb[i] = gload8(a.Vp + o);
       dead[i] = k0 + 16 * i + r >= len;                // masked keys: P = 0, zero gradient rows
       dk[i][0] = dk[i][1] = dv[i][0] = dv[i][1] = z4;
     }
@@ -939,7 +932,7 @@ inline AttnCoreArgs core_args(const pca_mab_shape& s, const Plan& p) {
   a.B = s.B; a.nq = s.nq; a.nk = s.nk; a.d = s.d; a.dh = s.d / s.h; a.h = s.h;
   a.qb = s.q_shared ? 0 : (int64_t)s.nq * s.d;
   a.scale = 1.0f / sqrtf((float)s.d);                 // modules.py:28: sqrt(dim_V)
-  a.c = a.scale * 1.4426950408889634f;
+  a.c = a.scale * LOG2E;
   a.lengths = s.k_lengths;
   a.nt = p.nt; a.gt = p.gt; a.S = p.S; a.cps = p.cps;
   return a;
@@ -958,14 +951,7 @@ inline Plan core_plan(const pca_mab_shape& s, int reg_rows, int str_rows) {
 // dynamic LDS above 64 KB: the d = 256 images of the head-dim-32 kernels (up to 146 KB), the d = 128
 // images of the small core's k_attnc_bwd_kv (78 KB at 8 heads of dim 16, 82 KB at 16 heads of dim 8)
 void allow_big_lds() {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    const void* ks[] = {reinterpret_cast<const void*>(k_attn32_fwd), reinterpret_cast<const void*>(k_attn32_bwd_q),
-                        reinterpret_cast<const void*>(k_attn32_bwd_kv),
-                        reinterpret_cast<const void*>(k_attnc_bwd_kv<8>),
-                        reinterpret_cast<const void*>(k_attnc_bwd_kv<16>)};
-    for (const void* k : ks) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  allow_lds160<k_attn32_fwd, k_attn32_bwd_q, k_attn32_bwd_kv, k_attnc_bwd_kv<8>, k_attnc_bwd_kv<16>>();
 }
 
 }  // namespace

@@ -17,8 +17,6 @@
 
 #include <math.h>
 
-#include <mutex>
-
 namespace pca {
 
 namespace {
@@ -101,12 +99,6 @@ __global__ __launch_bounds__(64 * (D / 32), 2) void k_isab1_fwd_t(const Fused128
     const float4 q4 = *reinterpret_cast<const float4*>(sBias + which * D + 32 * j + 16 * t + 4 * g);
     return f32x4{q4.x, q4.y, q4.z, q4.w};
   };
-  // workgroup barrier that orders LDS traffic only (no vmcnt(0): see k_isab1_fwd256)
-  auto lds_barrier = [] {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     if (SMALL) {
@@ -132,12 +124,7 @@ __global__ __launch_bounds__(64 * (D / 32), 2) void k_isab1_fwd_t(const Fused128
       const int ch = (slot & ~15) | ((slot ^ row) & 15);
       const int n = n0 + row < a.N ? n0 + row : a.N - 1;
       const __bf16* src = reinterpret_cast<const __bf16*>(a.X) + ((int64_t)b * a.N + n) * D + ch * 8;
-      const unsigned ldst = __builtin_amdgcn_readfirstlane(
-          (unsigned)(uintptr_t)(lds_void_t*)(dst + (DMA_PER_WAVE * j + i) * 1024));
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                   "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "v"(src), "s"(ldst) : "memory");
+      lds_dma16(src, dst + (DMA_PER_WAVE * j + i) * 1024);
     }
   };
   if (!SMALL) {
@@ -397,20 +384,14 @@ int isab1_fwd128_fused(const void* X, int dq, const __bf16* WqB, const float* Wq
   a.Y = Y; a.QpS = QpS; a.OS = OS; a.mask = mask;
   a.B = B; a.N = N; a.dq = dq;
   a.tiles_per_set = (int)cdiv(N, P);
-  a.scale_log2e = 1.4426950408889634f / sqrtf((float)D);
+  a.scale_log2e = LOG2E / sqrtf((float)D);
   const int total = B * a.tiles_per_set;
   int grid = total < 512 ? total : 512;                  // two workgroups per CU
   a.units_per_wg = (int)cdiv(total, grid);
   grid = (int)cdiv(total, a.units_per_wg);
   const size_t lds = (XB + 4) * (size_t)(P * D * 2) + 2 * NBK * (D / 128) * 64 * sizeof(uint32_t) +
                      2 * D * sizeof(float);
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_isab1_fwd_t<D, MI, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_isab1_fwd_t<D, MI, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  allow_lds160<k_isab1_fwd_t<D, MI, false>, k_isab1_fwd_t<D, MI, true>>();
   const double pts = (double)B * N;
   ProfScope ps(PCA_K_MAB1_FWD, st, 2.0 * pts * ((double)dq * D + (double)D * D + 2.0 * MI * D),
                pts * ((dq <= 4 ? 4.0 : 2.0) * dq + 2.0 * D));

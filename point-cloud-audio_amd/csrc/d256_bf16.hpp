@@ -1,4 +1,38 @@
-// Launchers of the d = 256 training kernels (d256_bf16.hip); all activations bf16 [rows][256].
+// Launchers of the d = 256 training kernels; all activations bf16 [rows][256].  The one declaration point of
+// attn1_pma256.hip, wgrad256.hip, fq256.hip, small256.hip, slab_sum.hip, d256_stream.hip,
+// d256_fused.hip, d128_fused.hip and mid256.hip.
+//
+// Map of the d = 256 / 8-head / m = 32 Set Transformer's training step (BASELINE configs[3], the
+// north-star shape): the pieces of the MAB adjoint (set_transformer-master/
+// modules.py:19-33 backwards) that the d = 128 kernels hold in ONE launch do not fit a CU at
+// d = 256 (two 128 KiB weight images), so the backward of the many-queries block runs as
+//
+//   k_attn1_bwd3         dZ = dY.[Z>0] ; dO = dY + dZ Wo (the wave's slice of Wo^T in registers), then
+//   (attn1_pma256.hip)   per head: P recomputed, dA, dS, dQp = dO + dS Kp ; dKp, dVp of the set
+//                        (WAVE = HEAD: a wave owns the 32 features of one head of its 32-point
+//                        tiles), k_sum_parts256 sums the per-range dKp / dVp partials
+//   k_rowstream DX1/DX3  dX = dQp Wq (+ dKp Wk + dVp Wv)            (d256_stream.hip)
+//   k_wgrad256(_dma)     dW[256 x 256] = G^T A over the B*N rows, deterministic two-stage sum
+//   (wgrad256.hip)
+//
+// and the few-queries block (ISAB mab0 at dk = 256) in the reference's own formulation
+// (modules.py:21: the N keys ARE projected) because the four 128 KiB operand images of the
+// reassociated backward exceed the register file + LDS of a CU (fq256.hip):
+//
+//   k_fq_proj_fwd        m = 32: Kp / Vp = X Wk^T + bk (bf16, [B*N, 256]) and the flash attention of
+//                        the m shared queries over the set's keys in one pass over X (wave = head,
+//                        head dim 32): online softmax, O partials per range, k_fq_merge joins them
+//   k_rowstream PROJ2 +  m <= 16: the projection (d256_stream.hip) and the attention as two launches
+//   k_fq_attn_fwd<256,1>
+//   k_fq_attn_bwd2       dKp, dVp (bf16) and the set's dQp; both score orientations are
+//   (m <= 16: _bwd<256,1>) recomputed on the MFMA (one extra 16x16x32 each) instead of transposed
+//   k_rowstream DX2/DX3  dX (+)= dKp Wk + dVp Wv                    (d256_stream.hip)
+//
+// plus the PMA at dk = 256 in the reassociated form (k_pma_*256, attn1_pma256.hip), the small per-set / layer-1
+// kernels (small256.hip) and the stand-alone fixed-order slab sum (slab_sum.hip).
+//
+// All activations cross these kernels in bf16 ([rows][256], row-major); accumulation, softmax
+// statistics, biases and residuals are fp32.  Layout conventions: mfma_common.hpp.
 #pragma once
 #include "mab1_bf16.hpp"
 
@@ -83,8 +117,6 @@ int wgrad256_launch_t(const Wgrad256Jobs& jobs, void* ws, bool f32_operands, hip
 
 int cvt_f32_bf16(const float* s, __bf16* d, int64_t n, hipStream_t st);            // n % 4 == 0
 int cvt_bf16_f32(const __bf16* s, float* d, int64_t n, int accumulate, hipStream_t st);
-int kv_proj_small256(const float* X, int64_t M, int dk, const float* Wk, const float* bk,
-                     const float* Wv, const float* bv, __bf16* Kp, __bf16* Vp, hipStream_t st);
 
 // layer 1 (inputs of dq <= 4 columns)
 // d256_stream.hip: streaming row-GEMMs with the weights in registers
@@ -142,7 +174,8 @@ int pma_attn_bwd256(const __bf16* X, const __bf16* Gb, const __bf16* dTb, const 
 size_t pma_bwd256_slab_bytes(int B);
 int slab_sum(const float* slabs, int S, int n, float* out, int accumulate, hipStream_t st);
 
-// few shared queries (m <= 32) over projected keys, head dim 32
+// few shared queries over projected keys, head dim 32 (fq_attn_fwd256: m <= 16; m = 32 projects the keys in
+// the same pass: fq_proj_attn_fwd256)
 int fq_splits256(int B, int N);
 // Op [B][S][m][256], Mp / Lp [B][S][8][MQ] scratch; O = Qp + A Vp [B][m][256]; LSE [B][8][MQ]
 int fq_attn_fwd256(const __bf16* Kp, const __bf16* Vp, const float* Qp, int B, int N, int m,

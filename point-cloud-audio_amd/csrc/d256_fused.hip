@@ -19,8 +19,6 @@
 
 #include <math.h>
 
-#include <mutex>
-
 namespace pca {
 
 namespace {
@@ -123,14 +121,6 @@ __global__ __launch_bounds__(512, 2) void k_isab1_fwd256(const FusedFwdArgs a) {
     const float4 q4 = *reinterpret_cast<const float4*>(sBias + which * D + 32 * j + 16 * t + 4 * g);
     return f32x4{q4.x, q4.y, q4.z, q4.w};
   };
-  // workgroup barrier that orders LDS traffic only: __syncthreads() would also wait for every
-  // outstanding global store and LDS-DMA (vmcnt(0)), i.e. expose a full memory round trip three
-  // times per tile
-  auto lds_barrier = [] {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     if (SMALL) {
@@ -165,12 +155,7 @@ __global__ __launch_bounds__(512, 2) void k_isab1_fwd256(const FusedFwdArgs a) {
       // for at once.  Hidden from the compiler, the transfer is ordered by the counted vmcnt in the
       // loop (hidden VMEM operations can only make hipcc's own counted waits stricter: the counter
       // retires in order).  M0 = wave-uniform LDS base, written in the statement that uses it.
-      const unsigned ldst = __builtin_amdgcn_readfirstlane(
-          (unsigned)(uintptr_t)(lds_void_t*)(dst + (DMA_PER_WAVE * j + i) * 1024));
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                   "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "v"(src), "s"(ldst) : "memory");
+      lds_dma16(src, dst + (DMA_PER_WAVE * j + i) * 1024);
     }
   };
   int cb = u0 / a.tiles_per_set, ct = u0 - cb * a.tiles_per_set;      // current unit
@@ -1101,7 +1086,7 @@ int isab1_fwd256_fused(const void* X, int dq, const __bf16* WqB, const float* Wq
   a.Y = Y; a.QpS = QpS; a.OS = OS; a.mask = mask;
   a.B = B; a.N = N; a.dq = dq;
   a.tiles_per_set = (int)cdiv(N, P);
-  a.scale_log2e = 1.4426950408889634f / sqrtf((float)D);
+  a.scale_log2e = LOG2E / sqrtf((float)D);
 #if defined(PCA_FWD_ABLATE) || defined(PCA_FWD_STAMPS)      // diagnostic builds only (scripts/experiments)
   a.ablate = (getenv("PCA_AB_ABLATE") ? atoi(getenv("PCA_AB_ABLATE")) : 0) |
              ((getenv("PCA_AB_STAMPSEL") ? atoi(getenv("PCA_AB_STAMPSEL")) : 15) << 16);
@@ -1113,17 +1098,8 @@ int isab1_fwd256_fused(const void* X, int dq, const __bf16* WqB, const float* Wq
   a.units_per_wg = (int)cdiv(total, grid);
   grid = (int)cdiv(total, a.units_per_wg);
   const size_t lds = 8 * (size_t)TILEB + 2 * NBK * 2 * 64 * sizeof(uint32_t) + 2 * D * sizeof(float);
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_isab1_fwd256<false, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_isab1_fwd256<true, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_isab1_fwd256<false, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_isab1_fwd256<true, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  allow_lds160<k_isab1_fwd256<false, false>, k_isab1_fwd256<true, false>, k_isab1_fwd256<false, true>,
+               k_isab1_fwd256<true, true>>();
   const double pts = (double)B * N;
   ProfScope ps(PCA_K_MAB1_FWD, st, 2.0 * pts * ((double)dq * D + (double)D * D + 2.0 * MI * D),
                pts * ((dq <= 4 ? 4.0 : 2.0) * dq + 2.0 * D));
@@ -1140,11 +1116,7 @@ int isab1_fwd256_fused(const void* X, int dq, const __bf16* WqB, const float* Wq
         ;
 #define PCA_AB_LAUNCH(S, F, T)                                                                   \
   do {                                                                                           \
-    static std::once_flag o2;                                                                    \
-    std::call_once(o2, [] {                                                                      \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_isab1_fwd256_ab<S, F, T>),       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);        \
-    });                                                                                          \
+    allow_lds160<k_isab1_fwd256_ab<S, F, T>>();                                                  \
     hipLaunchKernelGGL((k_isab1_fwd256_ab<S, F, T>), dim3(grid), dim3(1024), lds2, st, a);       \
   } while (0)
     const bool sm = dq <= 4, f8 = inv_o != nullptr;
@@ -1156,11 +1128,7 @@ int isab1_fwd256_fused(const void* X, int dq, const __bf16* WqB, const float* Wq
     constexpr bool abreast = false;
 #endif
     if (abreast && !sm && !f8 && !train) {
-      static std::once_flag o3;
-      std::call_once(o3, [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_isab1_fwd256_ab<false, false, false, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      });
+      allow_lds160<k_isab1_fwd256_ab<false, false, false, true>>();
       hipLaunchKernelGGL((k_isab1_fwd256_ab<false, false, false, true>), dim3(grid), dim3(1024), lds2,
                          st, a);
       ps.end();

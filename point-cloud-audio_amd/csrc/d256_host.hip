@@ -1,4 +1,5 @@
-// Host orchestration of the d = 256 / 8-head training blocks (kernels: d256_bf16.hip).
+// Host orchestration of the d = 256 / 8-head training blocks (kernels: attn1_pma256.hip, wgrad256.hip,
+// fq256.hip, small256.hip; map: d256_bf16.hpp).
 //   mab1_d256_bwd     adjoint of ISAB's mab1(X, H) (modules.py:53 / 19-33): three row-GEMM /
 //                     attention launches + the 256-wide weight-gradient reduction
 //   mab0_d256_*       the few-shared-queries block (ISAB mab0, PMA; modules.py:52,63):
@@ -269,7 +270,7 @@ static Mab0PrepJob fq_prep_job(const pca_mab_shape& s, const float* I, const pca
   const int m = s.nq;
   a.I = I; a.Wq = p.wq; a.bq = p.bq; a.Wk = p.wk;
   a.m = m; a.d = D; a.dq = s.dq; a.dk = s.dk; a.h = s.h; a.Rp = (int)cdiv(s.h * m, 32) * 32;
-  a.sl2e = 1.4426950408889634f / sqrtf((float)D);
+  a.sl2e = LOG2E / sqrtf((float)D);
   a.Qp = v.Qp; a.Gf = fq_path(s) == FQ_PROJ ? nullptr : v.Gf;
   a.Gb = fq_path(s) == FQ_PMA ? v.Gb : nullptr;
   return a;
@@ -459,7 +460,7 @@ int mab0_d256_bwd(const pca_mab_shape& s, const float* I, const void* X, const p
     PCA_TRY(wgrad256_short(ej, w.wg, defer, st));
   }
   PCA_TRY(linear_dx_acc_f32(w.dZ, p.wo, w.dO, Bm, D, D, 1, st));
-  const float sl2e = 1.4426950408889634f / sqrtf((float)D);
+  const float sl2e = LOG2E / sqrtf((float)D);
   Mab0PostJob pj{};
   pj.Qp = v.Qp; pj.Wk = p.wk; pj.I = I; pj.Wq = p.wq;
   pj.dWk = gr.wk; pj.dQp = w.dQp; pj.dWq = gr.wq; pj.dbq = gr.bq; pj.dI = dI;

@@ -18,8 +18,6 @@
 
 #include <math.h>
 
-#include <mutex>
-
 namespace pca {
 
 namespace {
@@ -117,11 +115,6 @@ __global__ __launch_bounds__(512, 2) void k_rowstream(const RowStreamArgs a) {
 #pragma unroll
   for (int t = 0; t < 2; ++t) oD[t] = swz(r, 4 * j + 2 * t + (g >> 1), ROWB) + 8 * (g & 1);
   const int oC = swz(tid >> 5, tid & 31, ROWB);
-  auto lds_barrier = [] {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
   // LDS-DMA of tile k of every stream (2 pieces of 1 KiB per wave and stream; issued from inline
   // asm so that hipcc does not serialise it against the ds_reads: see k_isab1_fwd256)
   auto dma = [&](int k) {
@@ -138,12 +131,7 @@ __global__ __launch_bounds__(512, 2) void k_rowstream(const RowStreamArgs a) {
         const int ch = (slot & ~15) | ((slot ^ row) & 15);
         const int n = n0 + row < a.N ? n0 + row : a.N - 1;
         const __bf16* src = base + ((int64_t)b * a.N + n) * D + ch * 8;
-        const unsigned ldst = __builtin_amdgcn_readfirstlane(
-            (unsigned)(uintptr_t)(lds_void_t*)(dst + (2 * j + i) * 1024));
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(src), "s"(ldst) : "memory");
+        lds_dma16(src, dst + (2 * j + i) * 1024);
       }
     }
   };
@@ -238,11 +226,7 @@ int launch_rowstream(RowStreamArgs a, hipStream_t st) {
   constexpr int NS = NIN + (ACC ? 1 : 0);
   const size_t lds = (size_t)(NS * NBUF + NOUT) * TILEB;
   static_assert((NS * NBUF + NOUT) * TILEB <= 160 * 1024, "LDS");
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_rowstream<NIN, NOUT, ACC, NBUF, F8>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  allow_lds160<k_rowstream<NIN, NOUT, ACC, NBUF, F8>>();
   hipLaunchKernelGGL((k_rowstream<NIN, NOUT, ACC, NBUF, F8>), dim3(grid), dim3(512), lds, st, a);
   return check_launch("k_rowstream");
 }

@@ -434,24 +434,6 @@ __global__ void k_fill_zero(float* __restrict__ dst, int64_t n) {
   }
 }
 
-__global__ void k_add_inplace(float* __restrict__ dst, const float* __restrict__ src,
-                              int64_t n, int vec) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (vec) {
-    float4* d4 = reinterpret_cast<float4*>(dst);
-    const float4* s4 = reinterpret_cast<const float4*>(src);
-    for (; i < (n >> 2); i += stride) {
-      float4 d = d4[i];
-      const float4 t = s4[i];
-      d.x += t.x; d.y += t.y; d.z += t.z; d.w += t.w;
-      d4[i] = d;
-    }
-    return;
-  }
-  for (; i < n; i += stride) dst[i] += src[i];
-}
-
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // float4 kernels: one or two vectors per thread (a long grid-stride loop of 16-byte accesses
@@ -586,7 +568,7 @@ int colsum(const float* X, int64_t rows, int cols, float* out, int accumulate,
 }
 
 // Deterministic column sums of a tall fp32 matrix (cols % 4 == 0, 16-byte aligned rows): per-block
-// partials [cdiv(rows, 512)][cols] into `part`; the caller reduces them (slab_sum, d256_bf16.hip).
+// partials [cdiv(rows, 512)][cols] into `part`; the caller reduces them (slab_sum, slab_sum.hip).
 // Returns the number of partials through *nparts.
 int colsum_parts(const float* X, int64_t rows, int cols, float* part, int* nparts, hipStream_t st) {
   PCA_REQUIRE(X && part && nparts && cols % 4 == 0 && al16(X) && al16(part) && rows > 0,
@@ -632,13 +614,6 @@ int copy_rows(const float* src, int64_t src_rows, float* dst, int64_t rows, int6
   return check_launch("k_copy_rows");
 }
 
-int add_inplace(float* dst, const float* src, int64_t n, hipStream_t st) {
-  if (n <= 0) return PCA_OK;
-  const int vec = n % 4 == 0 && al16(dst) && al16(src);
-  hipLaunchKernelGGL(k_add_inplace, dim3(vec ? ew_blocks_v4(n / 4) : ew_blocks(n)), dim3(256), 0, st, dst, src, n, vec);
-  return check_launch("k_add_inplace");
-}
-
 }  // namespace pca
 
 extern "C" {
@@ -646,11 +621,7 @@ extern "C" {
 int pca_abi_version(void) { return PCA_ABI_VERSION; }
 
 int pca_debug_poison_lds(void* stream) {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pca::k_poison_lds),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  pca::allow_lds160<pca::k_poison_lds>();
   // one 160 KiB workgroup per CU at a time; 4 rounds over 256 CUs reach every CU
   hipLaunchKernelGGL(pca::k_poison_lds, dim3(1024), dim3(256), 160 * 1024,
                      pca::as_stream(stream));

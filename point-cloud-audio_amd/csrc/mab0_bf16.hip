@@ -28,8 +28,6 @@
 
 #include <math.h>
 
-#include <mutex>
-
 namespace pca {
 
 namespace {
@@ -795,7 +793,7 @@ void mab0_collect_prep(const pca_mab_shape& s, const float* I, const pca_mab_par
   a.I = I; a.Wq = p.wq; a.bq = p.bq; a.Wk = p.wk;
   a.m = s.nq; a.d = s.d; a.dq = s.dq; a.dk = s.dk; a.h = s.h;
   a.Rp = (int)cdiv(s.h * s.nq, 32) * 32;
-  a.sl2e = 1.4426950408889634f / sqrtf((float)s.d);
+  a.sl2e = LOG2E / sqrtf((float)s.d);
   a.Qp = v.Qp; a.Gf = v.Gf;
   a.Gb = s.dk <= 4 ? nullptr : v.Gb;
   a.GtP = (s.dk <= 4 || !training) ? nullptr : v.GtP;

@@ -1049,7 +1049,7 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
   const int d = s.d, m = s.nq, h = s.h, dk = s.dk, R = h * m, Rp = (int)cdiv(R, 32) * 32;
   const int64_t Bm = (int64_t)s.B * m;
   const bool small = dk <= 4;
-  const float sl2e = 1.4426950408889634f / sqrtf((float)d);
+  const float sl2e = LOG2E / sqrtf((float)d);
   if (small && dX != nullptr) {
     set_error("mab0_bf16_bwd: dK for dk <= 4 is not built (the set is the model input)");
     return PCA_EUNSUPPORTED;
@@ -1130,17 +1130,7 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
       lds += MID_BWD_SMALL_LDS;       // dKp / dVp / dO_j images of the chain, behind the statistics
     }
     if (lds < (size_t)4 * Rp * 128 * 4) lds = (size_t)4 * Rp * 128 * 4;     // merge slabs
-    static std::once_flag once;
-    std::call_once(once, [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_mab0_bwd<64, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_mab0_bwd<64, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_mab0_bwd<32, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_mab0_bwd<32, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
+    allow_lds160<k_mab0_bwd<64, false>, k_mab0_bwd<64, true>, k_mab0_bwd<32, false>, k_mab0_bwd<32, true>>();
     const double pts = (double)s.B * s.nk;
     const bool abf = s.k_dtype == PCA_BF16;
     // algorithmic bytes: X in, dX out (read as well when it accumulates onto mab1's dQ)

@@ -16,7 +16,6 @@
 
 #include <math.h>
 
-#include <mutex>
 #include <type_traits>
 
 namespace pca {
@@ -717,12 +716,7 @@ int launch_fwd(const Mab1FwdArgs& a, hipStream_t st) {
                      ((!DS && PHASE != 2) ? wimg_q : 0) +
                      ((!DS && PHASE == 0) ? (size_t)NW * 32 * D * 2 : 0) +
                      ((DS && (D == 128 || PHASE == 1)) ? (size_t)D * 5 * sizeof(float) : 0);
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(k_mab1_fwd<D, MI, DS, ABF, NW, PHASE, F8>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  allow_lds160<k_mab1_fwd<D, MI, DS, ABF, NW, PHASE, F8>>();
   const int total = a.B * ((a.tiles_per_set + NW / 4 - 1) / (NW / 4));
   const int cap = (DS && D == 128) ? 512 : 256;
   const int grid = total < cap ? total : cap;
@@ -984,7 +978,7 @@ int mab1_bf16_fwd_ex(const pca_mab_shape& s, const void* X, const float* H,
   a.mask = training ? v.mask : nullptr;
   a.B = s.B; a.N = s.nq; a.dq = s.dq;
   a.tiles_per_set = (int)cdiv(s.nq, TP);
-  a.scale_log2e = 1.4426950408889634f / sqrtf((float)d);
+  a.scale_log2e = LOG2E / sqrtf((float)d);
   const bool abf = s.y_dtype == PCA_BF16;
   if (s.nk == 16 && f8) {
     if (small) return abf ? launch_fwd<128, 16, true, true, 0, 2>(a, st)

@@ -20,10 +20,7 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include <mutex>
-
 namespace pca {
-
 
 namespace {
 
@@ -822,11 +819,7 @@ int launch_bwd(const Mab1BwdArgs& a, hipStream_t st, double flops, double bytes)
                (DX ? (size_t)D * D * 2 : 0) + (FUSE ? NW * (2 * 32 * 40 + 2 * 32 * 72) : 0) +
                (FWQ ? (size_t)D * sizeof(float4) : 0);
   if (FUSE && lds < (size_t)2 * NW * MI * D * 4) lds = (size_t)2 * NW * MI * D * 4;   // flush buffer
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_mab1_bwd<D, MI, DX, FUSE, FWQ, ABF>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  allow_lds160<k_mab1_bwd<D, MI, DX, FUSE, FWQ, ABF>>();
   const int total = a.B * a.tiles_per_set;
   const int grid = FUSE ? (int)cdiv(total, a.tpw) : (total < 256 ? total : 256);
   ProfScope ps(PCA_K_MAB1_BWD, st, flops, bytes);
@@ -1054,7 +1047,7 @@ int mab1_bf16_bwd_ex(const pca_mab_shape& s, const void* X, const float* H,
   a.P = w.P; a.dX = want_dx ? dX : nullptr;
   a.B = s.B; a.N = s.nq; a.tiles_per_set = (int)cdiv(s.nq, TP);
   a.scale = 1.0f / sqrtf((float)d);
-  a.scale_log2e = 1.4426950408889634f * a.scale;
+  a.scale_log2e = LOG2E * a.scale;
 #ifdef PCA_DEBUG_CLOCKS
   a.dbg_wg = getenv("PCA_DBG_WG") ? atoi(getenv("PCA_DBG_WG")) : 0;
 #else

@@ -60,10 +60,47 @@ __device__ __forceinline__ f32x4 tof(bf16x4 v) {
 __device__ __forceinline__ bf16x8 gload8(const __bf16* p) {
   return *reinterpret_cast<const bf16x8*>(p);
 }
+// the same from 8 consecutive fp32 (32-byte aligned), rounded to bf16 here
+__device__ __forceinline__ bf16x8 gload8(const float* p) {
+  const float4 lo = reinterpret_cast<const float4*>(p)[0], hi = reinterpret_cast<const float4*>(p)[1];
+  bf16x8 v;
+  v[0] = (__bf16)lo.x; v[1] = (__bf16)lo.y; v[2] = (__bf16)lo.z; v[3] = (__bf16)lo.w;
+  v[4] = (__bf16)hi.x; v[5] = (__bf16)hi.y; v[6] = (__bf16)hi.z; v[7] = (__bf16)hi.w;
+  return v;
+}
 
 // ---- LDS pointers (address space 3) and the transposing LDS read ------------------------------------
 typedef __attribute__((address_space(3))) void lds_void_t;       // destination of an LDS-DMA
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;       // operand of ds_read_tr16_b64
+
+// One 16-byte LDS-DMA: every lane's 16 bytes at `src` go to lds_dst + 16 * lane (lds_dst wave-uniform).
+// m0 carries the LDS address and is restored: the compiler keeps values of its own there.  The s_nop
+// covers the hazard between the write of m0 and the instruction that reads it.
+__device__ __forceinline__ void lds_dma16(const void* src, char* lds_dst) {
+  const unsigned ldst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_void_t*)lds_dst);
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+               "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(src), "s"(ldst) : "memory");
+}
+// workgroup barrier that orders LDS traffic only: __syncthreads() would also wait for every outstanding
+// global store and LDS-DMA (vmcnt(0)), i.e. expose a full memory round trip; the caller counts vmcnt itself
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+// two transposing reads (ds_read_tr16_b64) joined into one MFMA operand: the k-slots of p0, then of p1
+__device__ __forceinline__ bf16x8 tr_read2(const char* p0, const char* p1) {
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p1);
+  const bf16x4 l4 = __builtin_bit_cast(bf16x4, lo), h4 = __builtin_bit_cast(bf16x4, hi);
+  bf16x8 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { r[e] = l4[e]; r[4 + e] = h4[e]; }
+  return r;
+}
 
 // LDS image of a 32-row tile with 256-byte rows; 16-byte chunk ch of row `row` sits at
 // (cdna_hip_programming.md T10, image (b)): serves the transposed reads conflict-free
@@ -76,6 +113,7 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* img, int t, int lane) {
   const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
   const int a0 = tr_off(4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
   const int a1 = tr_off(16 + 4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
+  // (the tail of tr_read2 written out: through the wrapper hipcc schedules k_mab0_attn_h4 differently)
   const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a0));
   const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a1));
   const bf16x4 l4 = __builtin_bit_cast(bf16x4, lo), h4 = __builtin_bit_cast(bf16x4, hi);
@@ -90,13 +128,19 @@ __device__ __forceinline__ bf16x8 tr_frag_small(const char* img, int rb, int col
   const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
   const int a0 = (4 * g + q) * rb + (col0 + 4 * p) * 2;
   const int a1 = (16 + 4 * g + q) * rb + (col0 + 4 * p) * 2;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a1));
-  const bf16x4 l4 = __builtin_bit_cast(bf16x4, lo), h4 = __builtin_bit_cast(bf16x4, hi);
-  bf16x8 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { r[e] = l4[e]; r[4 + e] = h4[e]; }
-  return r;
+  return tr_read2(img + a0, img + a1);
+}
+
+// [32 rows][256] bf16 tile as two [32][128] halves, each a tr_off image (conflict-free ds_read_tr16_b64)
+__device__ __forceinline__ int tr_off256(int row, int ch) {
+  return (ch >> 4) * (32 * 256) + 256 * row +
+         16 * ((ch & 15) ^ (((row & 3) << 2) | ((row >> 2) & 3)));
+}
+__device__ __forceinline__ bf16x8 tr_frag256(const char* img, int t, int lane) {
+  const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
+  const int a0 = tr_off256(4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
+  const int a1 = tr_off256(16 + 4 * g + q, 2 * t + (p >> 1)) + 8 * (p & 1);
+  return tr_read2(img + a0, img + a1);
 }
 
 // ---- fp8 (OCP e4m3) operands: same 16x16x32 shape and (g, j) k-slot structure as bf16, 8 values
@@ -172,13 +216,9 @@ __device__ __forceinline__ bf16x8 ld_x8_guard(const void* X, int64_t set_row0, i
   const int64_t row = set_row0 + (ok ? n : n_hi - 1);
   bf16x8 v;
   if (ABF) {
-    v = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const __bf16*>(X) + row * DK + ch * 8);
+    v = gload8(reinterpret_cast<const __bf16*>(X) + row * DK + ch * 8);
   } else {
-    const float4* src =
-        reinterpret_cast<const float4*>(reinterpret_cast<const float*>(X) + row * DK + ch * 8);
-    const float4 lo = src[0], hi = src[1];
-    v[0] = (__bf16)lo.x; v[1] = (__bf16)lo.y; v[2] = (__bf16)lo.z; v[3] = (__bf16)lo.w;
-    v[4] = (__bf16)hi.x; v[5] = (__bf16)hi.y; v[6] = (__bf16)hi.z; v[7] = (__bf16)hi.w;
+    v = gload8(reinterpret_cast<const float*>(X) + row * DK + ch * 8);
   }
   if (!ok) {
 #pragma unroll

@@ -19,8 +19,6 @@
 //  B = 128; this one: see DESIGN.md 4.5.)
 #include "d256_bf16.hpp"
 
-#include <mutex>
-
 namespace pca {
 
 namespace {
@@ -204,11 +202,7 @@ int mid256_fwd(const float* O, const float* Wo, const float* bo, const float* Wk
                const float* Wv, const float* bv, float* Z, float* H, __bf16* KpP, __bf16* VpP,
                __bf16* Kt, __bf16* Vt, int B, hipStream_t st) {
   Mid256Args a{O, Wo, bo, Wk, bk, Wv, bv, Z, H, KpP, VpP, Kt, Vt};
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_mid256_fwd),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  allow_lds160<k_mid256_fwd>();
   hipLaunchKernelGGL(k_mid256_fwd, dim3(B), dim3(1024), (size_t)5 * TILEB, st, a);
   return check_launch("k_mid256_fwd");
 }

@@ -42,6 +42,22 @@ inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// log2(e): the softmax kernels work in the log2 domain (v_exp_f32 is 2^x)
+constexpr float LOG2E = 1.4426950408889634f;
+
+// Allow each of the kernels 160 KiB of dynamic LDS (a CU's whole LDS; HIP's default cap is 64 KiB): at the
+// first call per process, result ignored.
+// (Once per process, not per device: per-device state would change behaviour and belongs in a change of its own.)
+template <auto... Kernels>
+inline void allow_lds160() {
+  static const bool once = [] {
+    ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernels),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), ...);
+    return true;
+  }();
+  (void)once;
+}
+
 // A/B switch read from the environment: on unless the variable starts with '0'.  Callers that read a
 // switch once per process keep the result in a `static const bool`; the ones tests flip in-process call
 // this every time.
@@ -108,8 +124,6 @@ int relu_bwd_copy(const float* dY, const float* Z, float* dZ, float* dO, int64_t
 // dst[r, :] = src[(r % src_rows), :]   (broadcast copy when src_rows < rows)
 int copy_rows(const float* src, int64_t src_rows, float* dst, int64_t rows, int64_t cols,
               hipStream_t st);
-// dst += src (n elements)
-int add_inplace(float* dst, const float* src, int64_t n, hipStream_t st);
 int fill_zero(float* dst, int64_t n, hipStream_t st);
 
 }  // namespace pca

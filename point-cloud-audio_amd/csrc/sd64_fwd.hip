@@ -23,8 +23,6 @@
 
 #include <math.h>
 
-#include <mutex>
-
 namespace pca {
 
 namespace {
@@ -366,19 +364,13 @@ int sd64_fwd(const pca_mab_shape& s, const float* Q, const float* K, const pca_m
   a.Qin = Q; a.Kin = K;
   a.wq = p.wq; a.bq = p.bq; a.wk = p.wk; a.bk = p.bk; a.wv = p.wv; a.bv = p.bv; a.wo = p.wo; a.bo = p.bo;
   a.Y = Y; a.B = s.B; a.dq = s.dq; a.dk = s.dk; a.lengths = s.k_lengths;
-  a.sl2e = 1.4426950408889634f / sqrtf((float)D);
+  a.sl2e = LOG2E / sqrtf((float)D);
   if (kind == 1) {
     a.N = s.nq; a.m = s.nk;
     const dim3 grid((unsigned)s.B, (unsigned)cdiv(s.nq, 256));
     PCA_REQUIRE(grid.y <= 65535, "sd64_fwd: too many points per set (%d)", s.nq);
     const size_t lds = (size_t)(2 * MQ * D + D * 256) * sizeof(float);       // 96 KiB
-    static std::once_flag once;
-    std::call_once(once, [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_sd_mq<64>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_sd_mq<4>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
+    allow_lds160<k_sd_mq<64>, k_sd_mq<4>>();
     if (s.dq == D) hipLaunchKernelGGL(k_sd_mq<64>, grid, dim3(256), lds, st, a);
     else hipLaunchKernelGGL(k_sd_mq<4>, grid, dim3(256), lds, st, a);
     return check_launch("k_sd_mq");

@@ -33,8 +33,6 @@
 
 #include <math.h>
 
-#include <mutex>
-
 namespace pca {
 
 namespace {
@@ -1429,14 +1427,8 @@ int set128_fwd_launch(const Set128FwdArgs& a, hipStream_t st) {
               a.B, a.N, a.din);
   PCA_REQUIRE(a.Sp == 2 || a.Sp == 4, "set128_fwd: %d PMA partials", a.Sp);
   PCA_REQUIRE(a.Sp <= a.N / 128, "set128_fwd: %d PMA partials of %d points", a.Sp, a.N);
-  static std::once_flag once;
-  std::call_once(once, [] {
-    const void* ks[8] = {reinterpret_cast<const void*>(k_set128_fwd<1, 1>), reinterpret_cast<const void*>(k_set128_fwd<2, 1>),
-                         reinterpret_cast<const void*>(k_set128_fwd<3, 1>), reinterpret_cast<const void*>(k_set128_fwd<4, 1>),
-                         reinterpret_cast<const void*>(k_set128_fwd<1, 2>), reinterpret_cast<const void*>(k_set128_fwd<2, 2>),
-                         reinterpret_cast<const void*>(k_set128_fwd<3, 2>), reinterpret_cast<const void*>(k_set128_fwd<4, 2>)};
-    for (const void* k : ks) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  allow_lds160<k_set128_fwd<1, 1>, k_set128_fwd<2, 1>, k_set128_fwd<3, 1>, k_set128_fwd<4, 1>,
+               k_set128_fwd<1, 2>, k_set128_fwd<2, 2>, k_set128_fwd<3, 2>, k_set128_fwd<4, 2>>();
   const size_t lds = (size_t)512 * ROWB + 32768;
   // reference-formulation FLOPs of the three blocks this launch covers (the PMA's
   // epilogue and the classifier run in k_pma_head1), algorithmic bytes: X in, two [N, d] bf16 tensors

@@ -1,5 +1,5 @@
 // Fixed-order sum of per-workgroup partial tensors: out[n] (+)= sum_w slabs[w * stride + i].
-// Shared by the stand-alone launch (k_slab_sum_jobs, d256_bf16.hip) and by the kernels that carry
+// Shared by the stand-alone launch (k_slab_sum_jobs, slab_sum.hip) and by the kernels that carry
 // such sums as extra workgroup rows ("riders": k_wgrad128, k_terminal1) so that the reduction costs
 // no launch of its own.  Uses the first 256 threads of the workgroup; EVERY thread of the workgroup
 // must call it (one barrier inside).  `red` = 4 x 64 float4 of LDS.

@@ -346,7 +346,7 @@ int forward(const pca_st_config& c, const Layout& L, const Shapes& s, const floa
     // one launch: both ISABs and the PMA's attention partials, the set resident in one workgroup's LDS
     Set128FwdArgs a{};
     a.X = X; a.B = c.B; a.N = c.N; a.din = c.din;
-    a.scale_log2e = 1.4426950408889634f / sqrtf((float)c.d);
+    a.scale_log2e = LOG2E / sqrtf((float)c.d);
     for (int li = 0; li < 2; ++li) {
       Mab0Saved v0;
       mab0_carve_saved(s.m0[li], &v0, w.saved[2 * li]);
