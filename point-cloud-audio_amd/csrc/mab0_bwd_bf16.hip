@@ -904,15 +904,8 @@ int pma_head_args(const pca_mab_shape& s, const pca_mab_params& p, void* saved, 
   return PCA_OK;
 }
 
-int pma_head_launch(const pca_mab_shape& s, const pca_mab_params& p, void* saved, void* ws_bwd,
-                    float* P, const float* Wc, const float* bc, const int64_t* labels, int C,
-                    float grad_scale, float* logits, float* dlogits, float* dP, float* dWc,
-                    float* dbc, float* loss_out, float* stats, float* cls_ws, BwdDefer* defer,
-                    hipStream_t st) {
-  PmaHeadArgs a{};
-  PCA_TRY(pma_head_args(s, p, saved, ws_bwd, P, Wc, bc, labels, C, grad_scale, logits, dlogits, dP, dWc, dbc,
-                        loss_out, stats, cls_ws, defer, &a));
-  const int d = s.d, m = s.nq, h = s.h, dk = s.dk, R = h * m, Rp = a.Rp;
+int pma_head_launch(const PmaHeadArgs& a, hipStream_t st) {
+  const int d = a.d, m = a.m, h = a.h, dk = a.dk, R = h * m, Rp = a.Rp, C = a.C;
   size_t lds = ((size_t)R * dk + (size_t)m * d) * sizeof(float);
   const size_t l2 = (size_t)(d + C) * sizeof(float);
   const size_t l3 = (2 * (size_t)m * d + (size_t)Rp + (size_t)d) * sizeof(float);
@@ -920,9 +913,9 @@ int pma_head_launch(const pca_mab_shape& s, const pca_mab_params& p, void* saved
   lds = lds > l3 ? lds : l3;
   // (the generic k_pma_head serves the shapes k_pma_head1 does not)
   if (d == 128 && dk == 128 && h == 4 && m == 1 && C <= 64 && a.S >= 1 && a.S <= 8)
-    hipLaunchKernelGGL(k_pma_head1, dim3(s.B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_pma_head1, dim3(a.B), dim3(256), 0, st, a);
   else
-    hipLaunchKernelGGL(k_pma_head, dim3(s.B), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(k_pma_head, dim3(a.B), dim3(256), lds, st, a);
   return check_launch("k_pma_head");
 }
 

@@ -411,16 +411,9 @@ int wgrad256_flush_deferred(BwdDefer& D, hipStream_t st);       // d256_host.hip
 bool wgrad_slabs_on();       // reductions of the fused d = 128 path as slabs + fixed-order sums
                              // (PCA_WGRAD_SLABS=0: fp32 atomics)
 // PMA epilogue + classifier + cross-entropy (forward and backward) + PMA backward epilogue of the
-// train step in ONE launch per set (after mab0_bf16_fwd_ex(..., PCA_F_SKIP_EPILOGUE); followed
-// by mab0_bf16_bwd_ex(..., PCA_F_SKIP_HEAD)).  P [B, d] receives the pooled features; the
-// classifier's weight gradient is queued in `defer`.  ws_bwd is the PMA's backward workspace.
-int pma_head_launch(const pca_mab_shape& s, const pca_mab_params& p, void* saved, void* ws_bwd,
-                    float* P, const float* Wc, const float* bc, const int64_t* labels, int C,
-                    float grad_scale, float* logits, float* dlogits, float* dP, float* dWc,
-                    float* dbc, float* loss_out, float* stats, float* cls_ws, BwdDefer* defer,
-                    hipStream_t st);
-// arguments of that launch (k_pma_head / k_pma_head1; the set-resident forward runs the same stages in its
-// own tail: set128_fwd.hip)
+// train step in ONE launch per set (k_pma_head / k_pma_head1, after mab0_bf16_fwd_ex(...,
+// PCA_F_SKIP_EPILOGUE); followed by mab0_bf16_bwd_ex(..., PCA_F_SKIP_HEAD)); the set-resident forward runs
+// the same stages in its own tail (set128_fwd.hip).  Both take the arguments pma_head_args builds.
 struct PmaHeadArgs {
   // forward epilogue
   const float *Tp, *Mp, *Lp;
@@ -443,11 +436,14 @@ struct PmaHeadArgs {
   float *Delta, *LSEp, *zero_ptr;
   int zero_n;
 };
+// P [B, d] receives the pooled features; the classifier's weight gradient is queued in `defer`.  ws_bwd is
+// the PMA's backward workspace.
 int pma_head_args(const pca_mab_shape& s, const pca_mab_params& p, void* saved, void* ws_bwd,
                   float* P, const float* Wc, const float* bc, const int64_t* labels, int C,
                   float grad_scale, float* logits, float* dlogits, float* dP, float* dWc,
                   float* dbc, float* loss_out, float* stats, float* cls_ws, BwdDefer* defer,
                   PmaHeadArgs* out);
+int pma_head_launch(const PmaHeadArgs& a, hipStream_t st);
 // post stages + riders (`late`: sums nobody reads before the optimizer, e.g. weight gradients)
 int terminal_launch(const BwdDefer& D, hipStream_t st, const SlabSumJobs* late = nullptr);
 // launch `jobs` now, or append them to the matching list of `defer`

@@ -11,9 +11,6 @@
 
 namespace pca {
 
-// per-block dispatch (api_mab.hip): fused bf16 kernel where one exists for the block's shape
-// and the config asks for PCA_MODE_BF16, exact fp32 GEMM chain otherwise
-
 namespace {
 
 struct MabOff {   // element offsets of one MAB's 8 tensors in the flat vector
@@ -82,22 +79,53 @@ inline pca_mab_shape shape(const pca_st_config& c, int nq, int nk, int dq, int d
   return s;
 }
 
-struct Shapes {
-  pca_mab_shape m0[2], m1[2], pma;
-  bool act_bf16;      // hidden activations Y1, Y2 (and their gradients) travel in bf16
+// The engine-level path of one call: which fused forms run, what is deferred, what gets room.  Filled once
+// per call by plan() and read by carve(), the preparation, the forward and the backward.  (The blocks' own
+// dispatch in api_mab.hip - mab_fwd_any, mab_bwd_any, *_bytes_any - still asks per block.)  DESIGN.md 5
+struct StepPlan {
+  bool training;
+  pca_mab_shape m0[2], m1[2], pma;   // per ISAB: mab0 = MAB(I, X), mab1 = MAB(X, H); the PMA
+  int kind_m0[2], kind_m1[2], kind_pma;   // which kernel family serves each (api_mab.hip; an inference call:
+                                          // the inference kinds)
+  bool act_bf16;       // hidden activations Y1, Y2 (and their gradients) travel in bf16
+  // everything below is false in an inference call
+  bool isab128[2];     // the layer runs as ONE fused d = 128 ISAB (isab_bf16_fwd / _bwd)
+  bool isab256[2];     // d = 256, both blocks on fused kernels: the few-queries forward ends in the per-set mid
+                       // kernel (mid256.hip); [1] is also the hand-over form of enc.1's backward
+  bool img_m1[2], img_m0[2];   // d = 256: the block asks for weight images of the step's table
+  bool img256, img256_f8;      // d = 256: the table exists (bf16 images / the e4m3 ones of the fp8 mode)
+  bool prep256;        // d = 256: the query side of all three few-queries blocks in the preparation launch
+  bool pma_head;       // the PMA epilogue + classifier + loss launch (k_pma_head) exists: d = 128
+  bool pma256;         // d = 256: the PMA's post stages wait for the flush, in a workspace of its own
+  bool fq_defer[2];    // so does the post stage of the layer's few-queries block
+  bool armed[2];       // d = 256 backward: mab1's fc_q weight-gradient job and dX are handed to the few-queries
+                       // block, whose jobs read the same X (StepCtx::armed); the two blocks then need
+                       // separate workspaces
+  bool defer_wg;       // d = 256: the [B*m]-row weight-gradient jobs of all five blocks in one launch at the
+                       // flush - needs every block's operands in place until then
+  bool set128_room;    // the shape fits the set-resident launch: carve() reserves its exchange area on this alone
+  // per-call switches (environment read on every call: tests compare the two forms in-process)
+  bool set128;         // the set-resident forward (set128_fwd.hip) runs            (PCA_SET128=0: per-block launches)
+  bool fuse_head;      // ... with the head stages in its own tail                   (PCA_SET128_HEAD=0: as a launch)
+  bool pma_bwd;        // ... and then the PMA's attention backward too              (PCA_SET128_PMABWD=0: k_mab0_bwd)
 };
-inline Shapes shapes(const pca_st_config& c, bool training, const int32_t* lengths = nullptr) {
-  Shapes s;
+
+inline StepPlan plan(const pca_st_config& c, bool training, const int32_t* lengths) {
+  // `lengths` changes no answer here and no workspace size: only the q_shared blocks carry it, which
+  // mab1_bf16_supported never takes, and neither mab0_bf16_supported, mab0_d256_supported, sd64_kind's
+  // q_shared branch nor any *_bytes function reads k_lengths.  So pca_st_ws_bytes, which has no lengths,
+  // and the calls carve alike.
+  StepPlan pl{};
+  pl.training = training;
   for (int li = 0; li < 2; ++li) {
     const int din = li == 0 ? c.din : c.d;
-    s.m0[li] = shape(c, c.m, c.N, c.d, din, 1);
-    s.m1[li] = shape(c, c.N, c.m, din, c.d, 0);
+    pl.m0[li] = shape(c, c.m, c.N, c.d, din, 1);
+    pl.m1[li] = shape(c, c.N, c.m, din, c.d, 0);
   }
-  s.pma = shape(c, c.k, c.N, c.d, c.d, 1);
-  s.act_bf16 = false;
+  pl.pma = shape(c, c.k, c.N, c.d, c.d, 1);
   if (training && c.mode != PCA_MODE_F32) {
     // bf16 activations only when EVERY block runs on a fused kernel that understands them
-    Shapes t = s;
+    StepPlan t = pl;
     t.m1[0].y_dtype = PCA_BF16;
     t.m0[1].k_dtype = PCA_BF16;
     t.m1[1].q_dtype = PCA_BF16;
@@ -109,26 +137,41 @@ inline Shapes shapes(const pca_st_config& c, bool training, const int32_t* lengt
     const bool blocks256 = c.d == 256 && mab_kind(t.m0[0]) == 2 && mab_kind(t.m1[0]) == 1 &&
                            mab_kind(t.m0[1]) == 2 && mab_kind(t.m1[1]) == 1;
     if ((isab128 || blocks256) && mab_kind(t.pma) == 2) {
-      s = t;
-      s.act_bf16 = true;
+      pl = t;
+      pl.act_bf16 = true;
     }
   }
   // variable-size sets: the points are the KEYS of the three blocks that attend over them
-  s.m0[0].k_lengths = s.m0[1].k_lengths = s.pma.k_lengths = lengths;
-  return s;
-}
-
-// the PMA epilogue + classifier + loss launch (k_pma_head) exists for d = 128
-inline bool pma_head_ok(const Shapes& s) { return mab_kind(s.pma) == 2 && s.pma.d == 128; }
-
-// the set-resident forward (set128_fwd.hip) takes a training step whose blocks are all on the fused
-// d = 128 kernels, whose sets fit one workgroup's LDS and are dense (PCA_SET128=0: the per-block launches)
-inline bool set128_on(const pca_st_config& c, const Shapes& s) {
-  // (read per call: tests compare the two forms in-process)
-  return env_not_zero("PCA_SET128") && c.mode == PCA_MODE_BF16 && s.act_bf16 &&
-         set128_shape_ok(c.B, c.N, c.din, c.d, c.h, c.m, c.k) &&
-         isab_bf16_supported(s.m0[0], s.m1[0]) && isab_bf16_supported(s.m0[1], s.m1[1]) &&
-         pma_head_ok(s) && s.pma.k_lengths == nullptr;
+  pl.m0[0].k_lengths = pl.m0[1].k_lengths = pl.pma.k_lengths = lengths;
+  for (int li = 0; li < 2; ++li) {
+    pl.kind_m0[li] = mab_kind(pl.m0[li], !training);
+    pl.kind_m1[li] = mab_kind(pl.m1[li], !training);
+  }
+  pl.kind_pma = mab_kind(pl.pma, !training);
+  if (!training) return pl;
+  const bool d256 = c.d == 256;
+  for (int li = 0; li < 2; ++li) {
+    pl.isab128[li] = isab_bf16_supported(pl.m0[li], pl.m1[li]);
+    pl.isab256[li] = d256 && pl.kind_m0[li] == 2 && pl.kind_m1[li] == 1;
+    pl.img_m1[li] = d256 && pl.kind_m1[li] == 1 && pl.m1[li].nk == 32;
+    pl.img_m0[li] = d256 && pl.kind_m0[li] == 2 && pl.m0[li].dk == 256;
+  }
+  pl.img256 = d256 && (c.mode == PCA_MODE_BF16 || c.mode == PCA_MODE_FP8);
+  pl.img256_f8 = d256 && c.mode == PCA_MODE_FP8;
+  pl.prep256 = d256 && pl.kind_m0[0] == 2 && pl.kind_m0[1] == 2 && pl.kind_pma == 2;
+  pl.pma_head = c.d == 128 && pl.kind_pma == 2;
+  pl.pma256 = d256 && pl.kind_pma == 2;
+  pl.fq_defer[0] = d256 && pl.kind_m0[0] == 2;
+  pl.fq_defer[1] = pl.armed[1] = pl.isab256[1];      // (enc.0's mab1 reads the fp32 set: nothing to hand over)
+  pl.defer_wg = pl.isab256[0] && pl.isab256[1] && pl.pma256;
+  pl.set128_room = set128_shape_ok(c.B, c.N, c.din, c.d, c.h, c.m, c.k);
+  // the set-resident forward takes a step whose blocks are all on the fused d = 128 kernels, whose sets fit
+  // one workgroup's LDS and are dense
+  pl.set128 = env_not_zero("PCA_SET128") && c.mode == PCA_MODE_BF16 && pl.act_bf16 && pl.set128_room &&
+              pl.isab128[0] && pl.isab128[1] && pl.pma_head && lengths == nullptr;
+  pl.fuse_head = pl.set128 && c.C <= 64 && env_not_zero("PCA_SET128_HEAD");
+  pl.pma_bwd = pl.fuse_head && env_not_zero("PCA_SET128_PMABWD");
+  return pl;
 }
 
 struct Ws {
@@ -141,48 +184,46 @@ struct Ws {
                              // (bwd_defer_flush), after the other layer's backward has run
   void* scratch_pma;         // d = 256: the PMA's backward workspace, kept until the deferred post
                              // stages of all three few-queries blocks have run (else = scratch)
+  void* scratch_fq[2];       // backward of the layer's few-queries block (else = scratch_bw[li]).  d = 256, enc.0:
+                             // room of its own when its ISAB partner's [B*m]-row operands in scratch_bw[0] stay
+                             // in place until the deferred launch; enc.1, hand-over form: the forward / PMA
+                             // scratch, which is free by then
   IsabImg img[2];            // weight images of the two ISABs (fused bf16 path)
-  bool fused[2];
   float* wg_slabs;           // weight-gradient partials of the deferred reductions (fused d = 128)
   size_t wg_slab_bytes;
   __bf16* img256;            // d = 256: 24 weight images [256][256] prepared in one launch per step
   uint8_t* img256f8;         // d = 256, fp8 mode: e4m3 weight images of the step (one launch) ...
   float* inv256f8;           // ... and their inverse scales
   void* wg256_def;           // d = 256: slabs of the deferred [B*m]-row weight-gradient launch
-  void* scratch_m0;          // d = 256: enc.0's few-queries backward (its ISAB partner's [B*m]-row
-                             // operands in scratch_bw[0] stay in place until that launch)
   void* set128_ws;           // set-resident forward: pair flags + hand-off slots (its fused head writes the
                              // PMA's backward operands into `scratch` while other pairs still exchange)
 };
 
-inline size_t carve(const pca_st_config& c, int training, Ws* out, void* base) {
-  const Shapes s = shapes(c, training != 0);
+inline size_t carve(const pca_st_config& c, const StepPlan& pl, Ws* out, void* base) {
   Carver cv(base);
   Ws w{};
-  const pca_mab_shape* order[5] = {&s.m0[0], &s.m1[0], &s.m0[1], &s.m1[1], &s.pma};
+  const pca_mab_shape* order[5] = {&pl.m0[0], &pl.m1[0], &pl.m0[1], &pl.m1[1], &pl.pma};
   size_t max_scratch = 0;
   for (int i = 0; i < 5; ++i) {
     const size_t fb = mab_fwd_ws_bytes_any(*order[i]);
     max_scratch = fb > max_scratch ? fb : max_scratch;
-    if (training) {
+    if (pl.training) {
       const size_t bb = mab_bwd_ws_bytes_any(*order[i]);
       max_scratch = bb > max_scratch ? bb : max_scratch;
       w.saved[i] = cv.take<char>(mab_saved_bytes_any(*order[i]));
     }
   }
   for (int li = 0; li < 2; ++li) {
-    w.fused[li] = training && isab_bf16_supported(s.m0[li], s.m1[li]);
-    if (w.fused[li]) {
-      const size_t fb = isab_bf16_fwd_ws_bytes(s.m0[li], s.m1[li]);
-      const size_t bb = isab_bf16_bwd_ws_bytes(s.m0[li], s.m1[li]);
+    if (pl.isab128[li]) {
+      const size_t fb = isab_bf16_fwd_ws_bytes(pl.m0[li], pl.m1[li]);
+      const size_t bb = isab_bf16_bwd_ws_bytes(pl.m0[li], pl.m1[li]);
       max_scratch = fb > max_scratch ? fb : max_scratch;
       max_scratch = bb > max_scratch ? bb : max_scratch;
       char* ib = cv.take<char>(isab_img_bytes());
       if (base != nullptr) isab_img_carve(ib, &w.img[li]);
     }
   }
-  if (training && set128_shape_ok(c.B, c.N, c.din, c.d, c.h, c.m, c.k))
-    w.set128_ws = cv.take<char>(set128_fwd_ws_bytes(c.B));
+  if (pl.set128_room) w.set128_ws = cv.take<char>(set128_fwd_ws_bytes(c.B));   // (on the shape, not the switch)
   const size_t BN = (size_t)c.B * c.N, Bm = (size_t)c.B * c.m;
   w.H[0] = cv.take<float>(Bm * c.d);
   w.H[1] = cv.take<float>(Bm * c.d);
@@ -190,7 +231,7 @@ inline size_t carve(const pca_st_config& c, int training, Ws* out, void* base) {
   w.Y[1] = cv.take<float>(BN * c.d);
   w.P = cv.take<float>((size_t)c.B * c.k * c.d);
   w.logits = cv.take<float>((size_t)c.B * c.k * c.C);
-  if (training) {
+  if (pl.training) {
     w.dlogits = cv.take<float>((size_t)c.B * c.k * c.C);
     w.dP = cv.take<float>((size_t)c.B * c.k * c.d);
     w.dY2 = cv.take<float>(BN * c.d);
@@ -200,42 +241,39 @@ inline size_t carve(const pca_st_config& c, int training, Ws* out, void* base) {
   }
   w.scratch = cv.take<char>(max_scratch);
   for (int li = 0; li < 2; ++li)
-    w.scratch_bw[li] = training ? (void*)cv.take<char>(max_scratch) : w.scratch;
-  w.scratch_pma = w.scratch;
-  if (training && s.pma.d == 256 && mab_kind(s.pma) == 2)
-    w.scratch_pma = cv.take<char>(mab_bwd_ws_bytes_any(s.pma));
-  if ((w.fused[0] || w.fused[1]) && wgrad_slabs_on()) {
+    w.scratch_bw[li] = pl.training ? (void*)cv.take<char>(max_scratch) : w.scratch;
+  w.scratch_pma = pl.pma256 ? (void*)cv.take<char>(mab_bwd_ws_bytes_any(pl.pma)) : w.scratch;
+  if ((pl.isab128[0] || pl.isab128[1]) && wgrad_slabs_on()) {
     // two lists (B*N-row and B*m-row jobs) of up to ~600 [128 x 128 (+128)] fp32 slabs each;
     // bwd_defer_flush gives a workgroup more rows when a list would not fit
     constexpr int slab_mb = 40;
     w.wg_slab_bytes = 2 * (size_t)slab_mb * 1024 * 1024;
     w.wg_slabs = cv.take<float>(w.wg_slab_bytes / sizeof(float));
   }
-  if (training && c.d == 256 && (c.mode == PCA_MODE_BF16 || c.mode == PCA_MODE_FP8))
-    w.img256 = cv.take<__bf16>((size_t)24 * 256 * 256);
-  if (training && c.d == 256 && c.mode == PCA_MODE_FP8) {
+  if (pl.img256) w.img256 = cv.take<__bf16>((size_t)24 * 256 * 256);
+  if (pl.img256_f8) {
     w.img256f8 = cv.take<uint8_t>((size_t)8 * 256 * 256);
     w.inv256f8 = cv.take<float>(16);
   }
-  w.scratch_m0 = w.scratch_bw[0];
-  if (training && c.d == 256 && mab_kind(s.m0[0]) == 2 && mab_kind(s.m1[0]) == 1) {
+  w.scratch_fq[0] = w.scratch_bw[0];
+  w.scratch_fq[1] = pl.isab256[1] ? w.scratch : w.scratch_bw[1];
+  if (pl.isab256[0]) {
     w.wg256_def = cv.take<char>(wgrad256_ws_bytes(8, (int64_t)c.B * c.m));
-    w.scratch_m0 = cv.take<char>(mab_bwd_ws_bytes_any(s.m0[0]));
+    void* own = cv.take<char>(mab_bwd_ws_bytes_any(pl.m0[0]));
+    if (pl.defer_wg) w.scratch_fq[0] = own;
   }
   if (out) *out = w;
   return cv.off;
 }
 
 // Every bf16 weight image the d = 256 blocks of a training step ask for (weight_image1 / 2 in
-// mab1_bf16.hip, d256_host.hip), registered in `tab`; launch != 0 also converts them, all in one
-// launch.  A request this list does not foresee is converted on the spot by the block itself.
-// (jobs_out != nullptr: the bf16 image jobs are handed to the caller, who launches them together with the
-//  step's other preparation work - forward() -, instead of being launched here)
-inline int images256_prepare(const pca_st_config& c, const Layout& L, const Shapes& s, const float* p,
-                             const Ws& w, WeightImages* tab, bool launch, hipStream_t st,
-                             PrepJobs* jobs_out = nullptr) {
+// mab1_bf16.hip, d256_host.hip), registered in `tab`; launch != 0 also converts them: the bf16 image jobs
+// go to `jobs`, which the caller launches together with the step's other preparation work (prepare_step),
+// the fp8 ones run here.  A request this list does not foresee is converted on the spot by the block itself.
+inline int images256_prepare(const Layout& L, const StepPlan& pl, const float* p, const Ws& w,
+                             WeightImages* tab, bool launch, hipStream_t st, PrepJobs* jobs) {
   tab->n = 0;
-  if (w.img256 == nullptr) return PCA_OK;
+  if (!pl.img256) return PCA_OK;
   PrepJobs J{};
   auto add = [&](const float* src, int mode) {
     if (tab->n >= 24) return;
@@ -244,15 +282,15 @@ inline int images256_prepare(const pca_st_config& c, const Layout& L, const Shap
     J.j[J.n++] = PrepJob{src, img, 256, 256, mode};
   };
   for (int li = 0; li < 2; ++li) {
-    if (mab_kind(s.m1[li]) == 1 && s.m1[li].d == 256 && s.m1[li].nk == 32) {
+    if (pl.img_m1[li]) {
       const pca_mab_params pm = params_at(p, L.mab1[li]);
-      const bool small = s.m1[li].dq <= 4;
-      add(pm.wo, mab1_fwd_wo_mode(s.m1[li]));                 // forward: fc_o (and fc_q of a d -> d block)
+      const bool small = pl.m1[li].dq <= 4;
+      add(pm.wo, mab1_fwd_wo_mode(pl.m1[li]));                // forward: fc_o (and fc_q of a d -> d block)
       if (!small) add(pm.wq, 0);
       add(pm.wo, D256_BWD_WMODE);                             // backward
       if (!small) add(pm.wq, D256_BWD_WMODE);
     }
-    if (mab_kind(s.m0[li]) == 2 && s.m0[li].d == 256 && s.m0[li].dk == 256) {
+    if (pl.img_m0[li]) {
       const pca_mab_params pk = params_at(p, L.mab0[li]);
       add(pk.wk, 0); add(pk.wv, 0);                          // forward: fc_k / fc_v over the keys
       add(pk.wk, D256_BWD_WMODE); add(pk.wv, D256_BWD_WMODE);
@@ -262,7 +300,7 @@ inline int images256_prepare(const pca_st_config& c, const Layout& L, const Shap
   // the d -> d few-queries block; natural layout: a block that wants another one converts its own)
   PrepF8Jobs F{};
   tab->nf8 = 0;
-  if (c.mode == PCA_MODE_FP8 && w.img256f8 != nullptr) {
+  if (pl.img256_f8) {
     auto add8 = [&](const float* src, int slot) {       // slot: index of the inverse scale
       if (tab->nf8 >= 8) return;
       const WeightImages::F8 e{src, 0, 256, 256, w.img256f8 + (size_t)tab->nf8 * 256 * 256,
@@ -271,17 +309,15 @@ inline int images256_prepare(const pca_st_config& c, const Layout& L, const Shap
       F.j[F.n++] = e;
     };
     for (int li = 0; li < 2; ++li) {
-      if (mab_kind(s.m1[li]) == 1 && s.m1[li].d == 256 && s.m1[li].nk == 32)
-        add8(params_at(p, L.mab1[li]).wo, 4 * li + 1);                 // [., o]
-      if (mab_kind(s.m0[li]) == 2 && s.m0[li].d == 256 && s.m0[li].dk == 256) {
-        add8(params_at(p, L.mab0[li]).wk, 4 * li + 2);                 // [k, v]: adjacent
+      if (pl.img_m1[li]) add8(params_at(p, L.mab1[li]).wo, 4 * li + 1);   // [., o]
+      if (pl.img_m0[li]) {
+        add8(params_at(p, L.mab0[li]).wk, 4 * li + 2);                   // [k, v]: adjacent
         add8(params_at(p, L.mab0[li]).wv, 4 * li + 3);
       }
     }
   }
   if (!launch) return PCA_OK;
-  if (jobs_out != nullptr) *jobs_out = J;
-  else PCA_TRY(prep_jobs_launch(J, st));
+  *jobs = J;
   return prep_f8_jobs_launch(F, st);
 }
 
@@ -297,98 +333,101 @@ int validate(const pca_st_config* c) {
   return PCA_OK;
 }
 
-int forward(const pca_st_config& c, const Layout& L, const Shapes& s, const float* p,
-            const float* X, Ws& w, bool training, hipStream_t st, StepCtx* ctx,
-            const PrepJobs* image_jobs = nullptr, const PmaHeadArgs* head = nullptr, bool pma_bwd = false) {
-  const void* in = X;
-  // d = 256: the query side of all three few-queries blocks in the same launch (mab0_d256_prep_collect)
-  const bool prep256 = training && s.m0[0].d == 256 && mab_kind(s.m0[0]) == 2 &&
-                       mab_kind(s.m0[1]) == 2 && mab_kind(s.pma) == 2 && !pma_head_ok(s);
-  const int prep_flag = prep256 ? PCA_F_PREP_DONE : 0;
-  if (training) {               // all weight images of the step in ONE launch
-    PrepJobs J{};
-    if (image_jobs != nullptr) J = *image_jobs;      // (d = 256: the step's image table, images256_prepare)
-    for (int li = 0; li < 2; ++li)
-      if (w.fused[li])
-        isab_collect_prep(s.m0[li], params_at(p, L.mab0[li]), params_at(p, L.mab1[li]),
-                          w.img[li], true, li == 1, &J);
-    if (set128_on(c, s))           // the pair flags of the set-resident forward start every step at zero
-      // (not the 16-byte header in front of them: word 0 counts expired spin-waits and is the CALLER's to
-      // clear and read - pca_st_handoff_counter)
-      J.j[J.n++] = PrepJob{nullptr, reinterpret_cast<__bf16*>(static_cast<char*>(w.set128_ws) + 16), 1,
-                           (int)((set128_flag_bytes(c.B) - 16) / 2), 4};
-    // (launched together with the query-side jobs below)
-    // query-side preparation (Qp, G images) of every fused mab0 / PMA, also one launch
-    Mab0PrepJobs MJ{};
-    for (int li = 0; li < 2; ++li)
-      if (w.fused[li]) {
-        Mab0Saved v;
-        mab0_carve_saved(s.m0[li], &v, w.saved[2 * li]);
-        mab0_collect_prep(s.m0[li], p + L.I[li], params_at(p, L.mab0[li]), v, true, false, &MJ);
-      }
-    if (pma_head_ok(s)) {
+// The preparation of a training step in ONE launch: all weight images (`J` arrives with the d = 256 image
+// table's jobs, images256_prepare), the flag clear of the set-resident forward and the query side (Qp, G
+// images) of every fused mab0 / PMA.  (takes a deferred pack along: pca_pack_defer)
+int prepare_step(const pca_st_config& c, const Layout& L, const StepPlan& pl, const float* p, const Ws& w,
+                 PrepJobs J, hipStream_t st) {
+  Mab0PrepJobs MJ{};
+  for (int li = 0; li < 2; ++li)
+    if (pl.isab128[li]) {
+      isab_collect_prep(pl.m0[li], params_at(p, L.mab0[li]), params_at(p, L.mab1[li]), w.img[li], true,
+                        li == 1, &J);
       Mab0Saved v;
-      mab0_carve_saved(s.pma, &v, w.saved[4]);
-      mab0_collect_prep(s.pma, p + L.S, params_at(p, L.pma), v, true, true, &MJ);
+      mab0_carve_saved(pl.m0[li], &v, w.saved[2 * li]);
+      mab0_collect_prep(pl.m0[li], p + L.I[li], params_at(p, L.mab0[li]), v, true, false, &MJ);
     }
-    if (prep256) {
-      const pca_mab_shape* sh[3] = {&s.m0[0], &s.m0[1], &s.pma};
-      const float* Iq[3] = {p + L.I[0], p + L.I[1], p + L.S};
-      const pca_mab_params pr[3] = {params_at(p, L.mab0[0]), params_at(p, L.mab0[1]),
-                                    params_at(p, L.pma)};
-      void* sv[3] = {w.saved[0], w.saved[2], w.saved[4]};
-      mab0_d256_prep_collect(3, sh, Iq, pr, sv, &MJ);
-    }
-    PCA_TRY(prep_all_launch(J, MJ, st));    // (takes a deferred pack along: pca_pack_defer)
+  if (pl.set128)                 // the pair flags of the set-resident forward start every step at zero
+    // (not the 16-byte header in front of them: word 0 counts expired spin-waits and is the CALLER's to
+    // clear and read - pca_st_handoff_counter)
+    J.j[J.n++] = PrepJob{nullptr, reinterpret_cast<__bf16*>(static_cast<char*>(w.set128_ws) + 16), 1,
+                         (int)((set128_flag_bytes(c.B) - 16) / 2), 4};
+  if (pl.pma_head) {
+    Mab0Saved v;
+    mab0_carve_saved(pl.pma, &v, w.saved[4]);
+    mab0_collect_prep(pl.pma, p + L.S, params_at(p, L.pma), v, true, true, &MJ);
   }
-  PCA_TRY(pack_flush(st));                  // a deferred pack nobody took runs now, before X is read
-  if (training && set128_on(c, s)) {
-    // one launch: both ISABs and the PMA's attention partials, the set resident in one workgroup's LDS
-    Set128FwdArgs a{};
-    a.X = X; a.B = c.B; a.N = c.N; a.din = c.din;
-    a.scale_log2e = LOG2E / sqrtf((float)c.d);
-    for (int li = 0; li < 2; ++li) {
-      Mab0Saved v0;
-      mab0_carve_saved(s.m0[li], &v0, w.saved[2 * li]);
-      Mab1Saved v1;
-      mab1_carve_saved(s.m1[li], &v1, w.saved[2 * li + 1]);
-      const pca_mab_params p0 = params_at(p, L.mab0[li]), p1 = params_at(p, L.mab1[li]);
-      const IsabImg& im = w.img[li];
-      Set128Layer& S = a.L[li];
-      S.Gf = v0.Gf; S.Gb = v0.Gb; S.Qp0 = v0.Qp; S.Wv0 = im.Wv0; S.Wv0f = p0.wv; S.bv0 = p0.bv;
-      S.bo0 = p0.bo; S.Wo0 = im.Wo0; S.T = v0.T; S.LSE = v0.LSE; S.O0 = v0.O; S.Z0 = v0.Z; S.H = w.H[li];
-      S.Wk1 = im.Wk1; S.Wv1 = im.Wv1; S.bk1 = p1.bk; S.bv1 = p1.bv;
-      S.KpP = v1.KpP; S.VpP = v1.VpP; S.Kt = v1.Kt; S.Vt = v1.Vt;
-      S.WqB = im.WqB; S.WqF = p1.wq; S.bq1 = p1.bq; S.WoP = im.WoP; S.bo1 = p1.bo;
-      S.QpS = v1.QpS; S.OS = v1.OS; S.Y = reinterpret_cast<__bf16*>(w.Y[li]); S.mask = v1.mask;
-    }
-    if (head != nullptr && pma_bwd) {  // the PMA's attention backward in the tail: Y2 has no reader left
-      a.pma_bwd = 1;
-      a.dY2 = reinterpret_cast<__bf16*>(w.dY2);
-      Mab0BwdWs wb;
-      mab0_carve_bwd_ws(s.pma, &wb, w.scratch);
-      a.pma_slabs = wb.slabs;
-      a.pma_S = mab0_bwd_splits(s.pma);
-      a.L[1].Y = nullptr;
-    }
-    Carver cs(w.set128_ws);
-    a.flags = reinterpret_cast<uint32_t*>(cs.take<char>(set128_flag_bytes(c.B)));   // (cleared by k_prep_all)
-    a.ex2 = cs.take<float>((size_t)c.B * 2 * 9216);
-    a.exP = cs.take<float>((size_t)c.B * 2 * 528);
-    if (head != nullptr) {             // the PMA epilogue, the classifier and the loss in the same launch
-      a.fuse_head = 1;
-      a.head = *head;
-    }
-    Mab0Saved vp;
-    mab0_carve_saved(s.pma, &vp, w.saved[4]);
-    a.Gpma = vp.Gb; a.TpP = vp.Tp; a.MpP = vp.Mp; a.LpP = vp.Lp; a.Sp = mab0_splits(s.pma);
-    return set128_fwd_launch(a, st);
+  if (pl.prep256) {              // (mab0_d256_prep_collect; the blocks' forward calls take PCA_F_PREP_DONE)
+    const pca_mab_shape* sh[3] = {&pl.m0[0], &pl.m0[1], &pl.pma};
+    const float* Iq[3] = {p + L.I[0], p + L.I[1], p + L.S};
+    const pca_mab_params pr[3] = {params_at(p, L.mab0[0]), params_at(p, L.mab0[1]),
+                                  params_at(p, L.pma)};
+    void* sv[3] = {w.saved[0], w.saved[2], w.saved[4]};
+    mab0_d256_prep_collect(3, sh, Iq, pr, sv, &MJ);
   }
+  return prep_all_launch(J, MJ, st);
+}
+
+// arguments of the set-resident forward: both ISABs and the PMA's attention partials, the set resident in
+// one workgroup's LDS; `head`: the stages it runs in its tail when the plan says so
+Set128FwdArgs set128_args(const pca_st_config& c, const Layout& L, const StepPlan& pl, const float* p,
+                          const float* X, const Ws& w, const PmaHeadArgs& head) {
+  Set128FwdArgs a{};
+  a.X = X; a.B = c.B; a.N = c.N; a.din = c.din;
+  a.scale_log2e = LOG2E / sqrtf((float)c.d);
   for (int li = 0; li < 2; ++li) {
-    void* sv0 = training ? w.saved[2 * li] : nullptr;
-    void* sv1 = training ? w.saved[2 * li + 1] : nullptr;
-    if (training && w.fused[li]) {
-      PCA_TRY(isab_bf16_fwd(s.m0[li], s.m1[li], p + L.I[li], in, params_at(p, L.mab0[li]),
+    Mab0Saved v0;
+    mab0_carve_saved(pl.m0[li], &v0, w.saved[2 * li]);
+    Mab1Saved v1;
+    mab1_carve_saved(pl.m1[li], &v1, w.saved[2 * li + 1]);
+    const pca_mab_params p0 = params_at(p, L.mab0[li]), p1 = params_at(p, L.mab1[li]);
+    const IsabImg& im = w.img[li];
+    Set128Layer& S = a.L[li];
+    S.Gf = v0.Gf; S.Gb = v0.Gb; S.Qp0 = v0.Qp; S.Wv0 = im.Wv0; S.Wv0f = p0.wv; S.bv0 = p0.bv;
+    S.bo0 = p0.bo; S.Wo0 = im.Wo0; S.T = v0.T; S.LSE = v0.LSE; S.O0 = v0.O; S.Z0 = v0.Z; S.H = w.H[li];
+    S.Wk1 = im.Wk1; S.Wv1 = im.Wv1; S.bk1 = p1.bk; S.bv1 = p1.bv;
+    S.KpP = v1.KpP; S.VpP = v1.VpP; S.Kt = v1.Kt; S.Vt = v1.Vt;
+    S.WqB = im.WqB; S.WqF = p1.wq; S.bq1 = p1.bq; S.WoP = im.WoP; S.bo1 = p1.bo;
+    S.QpS = v1.QpS; S.OS = v1.OS; S.Y = reinterpret_cast<__bf16*>(w.Y[li]); S.mask = v1.mask;
+  }
+  if (pl.pma_bwd) {              // the PMA's attention backward in the tail: Y2 has no reader left
+    a.pma_bwd = 1;
+    a.dY2 = reinterpret_cast<__bf16*>(w.dY2);
+    Mab0BwdWs wb;
+    mab0_carve_bwd_ws(pl.pma, &wb, w.scratch);
+    a.pma_slabs = wb.slabs;
+    a.pma_S = mab0_bwd_splits(pl.pma);
+    a.L[1].Y = nullptr;
+  }
+  Carver cs(w.set128_ws);
+  a.flags = reinterpret_cast<uint32_t*>(cs.take<char>(set128_flag_bytes(c.B)));   // (cleared by k_prep_all)
+  a.ex2 = cs.take<float>((size_t)c.B * 2 * 9216);
+  a.exP = cs.take<float>((size_t)c.B * 2 * 528);
+  if (pl.fuse_head) {            // the PMA epilogue, the classifier and the loss in the same launch
+    a.fuse_head = 1;
+    a.head = head;
+  }
+  Mab0Saved vp;
+  mab0_carve_saved(pl.pma, &vp, w.saved[4]);
+  a.Gpma = vp.Gb; a.TpP = vp.Tp; a.MpP = vp.Mp; a.LpP = vp.Lp; a.Sp = mab0_splits(pl.pma);
+  return a;
+}
+
+// `head`: the train step's head arguments (pma_head_args; read only by the set-resident launch), null in inference
+int forward(const pca_st_config& c, const Layout& L, const StepPlan& pl, const float* p, const float* X,
+            const Ws& w, hipStream_t st, StepCtx* ctx, const PmaHeadArgs* head = nullptr) {
+  PCA_TRY(pack_flush(st));                  // a deferred pack nobody took runs now, before X is read
+  if (pl.set128) {
+    PCA_REQUIRE(head != nullptr, "st: the set-resident forward needs the head arguments");
+    return set128_fwd_launch(set128_args(c, L, pl, p, X, w, *head), st);
+  }
+  const void* in = X;
+  const int prep_flag = pl.prep256 ? PCA_F_PREP_DONE : 0;
+  for (int li = 0; li < 2; ++li) {
+    void* sv0 = pl.training ? w.saved[2 * li] : nullptr;
+    void* sv1 = pl.training ? w.saved[2 * li + 1] : nullptr;
+    if (pl.isab128[li]) {
+      PCA_TRY(isab_bf16_fwd(pl.m0[li], pl.m1[li], p + L.I[li], in, params_at(p, L.mab0[li]),
                             params_at(p, L.mab1[li]), w.H[li], w.Y[li], sv0, sv1, w.scratch,
                             w.img[li], st));
       in = w.Y[li];
@@ -397,28 +436,121 @@ int forward(const pca_st_config& c, const Layout& L, const Shapes& s, const floa
     // d = 256 training: the few-queries block ends in the per-set mid kernel, which also prepares
     // the K / V images of the many-queries block (mid256.hip; the blocks' saved areas are disjoint)
     const pca_mab_params p1 = params_at(p, L.mab1[li]);
-    const bool mid = training && s.m0[li].d == 256 && mab_kind(s.m0[li]) == 2 && mab_kind(s.m1[li]) == 1;
     ctx->mid_done = false;
-    if (mid) { ctx->s1 = s.m1[li]; ctx->p1 = p1; ctx->saved1 = sv1; }
-    PCA_TRY(mab_fwd_any(s.m0[li], p + L.I[li], in, params_at(p, L.mab0[li]), w.H[li], sv0, w.scratch,
+    if (pl.isab256[li]) { ctx->s1 = pl.m1[li]; ctx->p1 = p1; ctx->saved1 = sv1; }
+    PCA_TRY(mab_fwd_any(pl.m0[li], p + L.I[li], in, params_at(p, L.mab0[li]), w.H[li], sv0, w.scratch,
                         st, prep_flag, ctx));                       // modules.py:52
     ctx->saved1 = nullptr;
-    PCA_TRY(mab_fwd_any(s.m1[li], in, w.H[li], p1, w.Y[li], sv1, w.scratch, st,
+    PCA_TRY(mab_fwd_any(pl.m1[li], in, w.H[li], p1, w.Y[li], sv1, w.scratch, st,
                         ctx->mid_done ? PCA_F_KV_READY : 0, ctx));  // modules.py:53
     in = w.Y[li];
   }
-  if (training && pma_head_ok(s))                                         // modules.py:63
+  if (pl.pma_head)                                                        // modules.py:63
     // (its epilogue runs inside k_pma_head together with the classifier and the loss)
-    PCA_TRY(mab0_bf16_fwd_ex(s.pma, p + L.S, w.Y[1], params_at(p, L.pma), w.P, w.saved[4],
+    PCA_TRY(mab0_bf16_fwd_ex(pl.pma, p + L.S, w.Y[1], params_at(p, L.pma), w.P, w.saved[4],
                              w.scratch, PCA_F_PREP_DONE | (c.k == 1 ? PCA_F_SKIP_EPILOGUE : 0),
                              st));
   else
-    PCA_TRY(mab_fwd_any(s.pma, p + L.S, w.Y[1], params_at(p, L.pma), w.P,
-                        training ? w.saved[4] : nullptr, w.scratch, st, prep_flag, ctx));
-  if (!training)
+    PCA_TRY(mab_fwd_any(pl.pma, p + L.S, w.Y[1], params_at(p, L.pma), w.P,
+                        pl.training ? w.saved[4] : nullptr, w.scratch, st, prep_flag, ctx));
+  if (!pl.training)
     PCA_TRY(linear_fwd_f32(w.P, p + L.wc, p + L.bc, w.logits, (int64_t)c.B * c.k, c.d, c.C,
                            st));                                    // models.py:40
   return PCA_OK;
+}
+
+// a block queues its terminal reductions in `posts` when its call is given deferring(.., true), and launches
+// them itself otherwise
+inline StepCtx* deferring(StepCtx* ctx, BwdDefer* posts, bool on) {
+  ctx->defer = on ? posts : nullptr;
+  return ctx;
+}
+
+// Backward of enc.<li>: mab1(X, H) then mab0(I, X).  X feeds both blocks, so its gradient dX is written by
+// the first and accumulated by the second (null: X is the input set, which needs no gradient).
+int isab_bwd(int li, const Layout& L, const StepPlan& pl, const float* p, float* g, const void* X,
+             const void* dY, void* dX, const Ws& w, BwdDefer* posts, StepCtx* ctx, hipStream_t st) {
+  const pca_mab_params p0 = params_at(p, L.mab0[li]), p1 = params_at(p, L.mab1[li]);
+  const pca_mab_grads g0 = grads_at(g, L.mab0[li]), g1 = grads_at(g, L.mab1[li]);
+  if (pl.isab128[li])
+    return isab_bf16_bwd(pl.m0[li], pl.m1[li], p + L.I[li], X, w.H[li], p0, p1, w.saved[2 * li],
+                         w.saved[2 * li + 1], dY, g + L.I[li], dX, g0, g1, w.scratch_bw[li], w.img[li], st,
+                         posts);
+  ctx->armed = pl.armed[li];
+  PCA_TRY(mab_bwd_any(pl.m1[li], X, w.H[li], p1, w.saved[2 * li + 1], dY, dX, w.dH, 0, g1, w.scratch_bw[li],
+                      st, deferring(ctx, posts, pl.defer_wg)));
+  PCA_TRY(mab_bwd_any(pl.m0[li], p + L.I[li], X, p0, w.saved[2 * li], w.dH, g + L.I[li], dX, dX != nullptr,
+                      g0, w.scratch_fq[li], st, deferring(ctx, posts, pl.fq_defer[li])));
+  ctx->armed = false;
+  return wgrad256_handoff_flush(ctx, w.scratch, st);   // (what nobody took runs on its own; not armed: nothing)
+}
+
+int st_forward(const pca_st_config* c, const float* params, const float* X, const int32_t* lengths,
+               float* logits, void* ws, void* stream) {
+  PCA_TRY(validate(c));
+  PCA_REQUIRE(params && X && logits && ws, "st_forward: null pointer");
+  const StepPlan pl = plan(*c, false, lengths);
+  Ws w;
+  carve(*c, pl, &w, ws);
+  w.logits = logits;
+  StepCtx ctx{};
+  return forward(*c, layout(*c), pl, params, X, w, as_stream(stream), &ctx);
+}
+
+int st_train_fwd_bwd(const pca_st_config* c, const float* p, const float* X, const int32_t* lengths,
+                     const int64_t* labels, float* g, float* loss_out, float* stats, float* logits,
+                     float grad_scale, int phase, void* ws, void* stream) {
+  PCA_TRY(validate(c));
+  PCA_REQUIRE(p && X && labels && g && loss_out && ws, "st_train_fwd_bwd: null pointer");
+  PCA_REQUIRE(c->k == 1, "st_train_fwd_bwd: the train step needs k == 1 (got %d)", c->k);
+  PCA_REQUIRE(phase >= -1 && phase <= 1, "st_train_fwd_bwd: phase=%d", phase);
+  hipStream_t st = as_stream(stream);
+  const StepPlan pl = plan(*c, true, lengths);
+  Ws w;
+  carve(*c, pl, &w, ws);
+  const Layout L = layout(*c);
+  if (logits != nullptr) w.logits = logits;
+  // shared-query gradients of the fused blocks of this call: one pair of launches at the end
+  // (their inputs live in per-block workspaces, which stay untouched until then)
+  BwdDefer posts{};
+  posts.slab_ws = w.wg_slabs;
+  posts.slab_cap = w.wg_slab_bytes;
+  if (pl.defer_wg) posts.wg256_ws = w.wg256_def;
+  // d = 256: all weight images of the step in one launch (phase 1 of a split step finds the images
+  // of phase 0 still in place: the parameters do not change in between)
+  WeightImages images{};
+  PrepJobs image_jobs{};
+  PCA_TRY(images256_prepare(L, pl, p, w, &images, phase != 1, st, &image_jobs));
+  // what this call hands from block to block (StepCtx)
+  StepCtx ctx{};
+  ctx.images = images.n > 0 ? &images : nullptr;
+  if (phase != 1) {
+    PmaHeadArgs head{};
+    if (pl.pma_head)
+      PCA_TRY(pma_head_args(pl.pma, params_at(p, L.pma), w.saved[4], w.scratch, w.P, p + L.wc, p + L.bc,
+                            labels, c->C, grad_scale, w.logits, w.dlogits, w.dP, g + L.wc, g + L.bc,
+                            loss_out, stats, w.clsws, &posts, &head));
+    PCA_TRY(prepare_step(*c, L, pl, p, w, image_jobs, st));
+    PCA_TRY(forward(*c, L, pl, p, X, w, st, &ctx, &head));
+    if (pl.pma_head) {
+      // dec.0 epilogue + dec.1 (Linear) + mean cross-entropy forward and backward + dec.0
+      // backward epilogue: one launch, one workgroup per set - or the tail of the set-resident forward
+      if (!pl.fuse_head) PCA_TRY(pma_head_launch(head, st));
+      PCA_TRY(mab0_bf16_bwd_ex(pl.pma, p + L.S, w.Y[1], params_at(p, L.pma), w.saved[4], w.dP, g + L.S,
+                               w.dY2, 0, grads_at(g, L.pma), w.scratch,
+                               PCA_F_SKIP_HEAD | (pl.pma_bwd ? PCA_F_ATTN_DONE : 0), st,
+                               deferring(&ctx, &posts, true)));
+    } else {
+      // dec.1 (Linear) + mean cross-entropy, forward and backward
+      PCA_TRY(cls_train_head(w.P, p + L.wc, p + L.bc, labels, c->B, c->d, c->C, grad_scale, w.logits,
+                             w.dlogits, w.dP, g + L.wc, g + L.bc, loss_out, stats, w.clsws, st, &posts));
+      PCA_TRY(mab_bwd_any(pl.pma, p + L.S, w.Y[1], params_at(p, L.pma), w.saved[4], w.dP, g + L.S, w.dY2,
+                          0, grads_at(g, L.pma), w.scratch_pma, st, deferring(&ctx, &posts, pl.pma256)));
+    }
+    PCA_TRY(isab_bwd(1, L, pl, p, g, w.Y[0], w.dY2, w.dY1, w, &posts, &ctx, st));
+  }
+  if (phase != 0) PCA_TRY(isab_bwd(0, L, pl, p, g, X, w.dY1, nullptr, w, &posts, &ctx, st));
+  return bwd_defer_flush(posts, st);
 }
 
 }  // namespace
@@ -438,14 +570,14 @@ int64_t pca_st_bucket_split(const pca_st_config* c) {
 
 size_t pca_st_ws_bytes(const pca_st_config* c, int training) {
   if (pca::validate(c) != PCA_OK) return 0;
-  return pca::carve(*c, training, nullptr, nullptr);
+  return pca::carve(*c, pca::plan(*c, training != 0, nullptr), nullptr, nullptr);
 }
 
 int pca_st_handoff_counter(const pca_st_config* c, void* ws, uint32_t** counter) {
   PCA_TRY(pca::validate(c));
   PCA_REQUIRE(ws != nullptr && counter != nullptr, "st_handoff_counter: null pointer");
   pca::Ws w;
-  pca::carve(*c, 1, &w, ws);
+  pca::carve(*c, pca::plan(*c, true, nullptr), &w, ws);
   *counter = static_cast<uint32_t*>(w.set128_ws);      // nullptr: no set-resident launch for this shape
   return PCA_OK;
 }
@@ -455,7 +587,7 @@ int pca_st_ws_layout(const pca_st_config* c, int64_t* out) {
   PCA_REQUIRE(out != nullptr, "st_ws_layout: null pointer");
   pca::Ws w;
   char* const base = reinterpret_cast<char*>(256);      // (never dereferenced: offsets only)
-  const size_t total = pca::carve(*c, 1, &w, base);
+  const size_t total = pca::carve(*c, pca::plan(*c, true, nullptr), &w, base);
   for (int i = 0; i < 5; ++i) out[i] = reinterpret_cast<char*>(w.saved[i]) - base;
   for (int i = 0; i < 2; ++i) {
     out[5 + i] = reinterpret_cast<char*>(w.H[i]) - base;
@@ -466,146 +598,11 @@ int pca_st_ws_layout(const pca_st_config* c, int64_t* out) {
   return PCA_OK;
 }
 
-static int st_forward_impl(const pca_st_config* c, const float* params, const float* X,
-                           const int32_t* lengths, float* logits, void* ws, void* stream) {
-  PCA_TRY(pca::validate(c));
-  PCA_REQUIRE(params && X && logits && ws, "st_forward: null pointer");
-  hipStream_t st = pca::as_stream(stream);
-  pca::Ws w;
-  pca::carve(*c, 0, &w, ws);
-  const pca::Layout L = pca::layout(*c);
-  const pca::Shapes s = pca::shapes(*c, false, lengths);
-  float* own = w.logits;
-  w.logits = logits;
-  (void)own;
-  pca::StepCtx ctx{};
-  return pca::forward(*c, L, s, params, X, w, false, st, &ctx);
-}
-
 int pca_st_forward(const pca_st_config* c, const float* params, const float* X,
                    const int32_t* lengths, float* logits, void* ws, void* stream) {
   PCA_TRY(pca::no_stale_pack("pca_st_forward", true));
-  const int rc = st_forward_impl(c, params, X, lengths, logits, ws, stream);
+  const int rc = pca::st_forward(c, params, X, lengths, logits, ws, stream);
   return rc != PCA_OK ? rc : pca::no_stale_pack("pca_st_forward (exit)", false);
-}
-
-static int st_train_fwd_bwd_impl(const pca_st_config* c, const float* params, const float* X,
-                                 const int32_t* lengths, const int64_t* labels, float* grads,
-                                 float* loss_out, float* stats,
-                                 float* logits, float grad_scale, int phase, void* ws,
-                                 void* stream) {
-  PCA_TRY(pca::validate(c));
-  PCA_REQUIRE(params && X && labels && grads && loss_out && ws,
-              "st_train_fwd_bwd: null pointer");
-  PCA_REQUIRE(c->k == 1, "st_train_fwd_bwd: the train step needs k == 1 (got %d)", c->k);
-  PCA_REQUIRE(phase >= -1 && phase <= 1, "st_train_fwd_bwd: phase=%d", phase);
-  hipStream_t st = pca::as_stream(stream);
-  pca::Ws w;
-  pca::carve(*c, 1, &w, ws);
-  const pca::Layout L = pca::layout(*c);
-  const pca::Shapes s = pca::shapes(*c, true, lengths);
-  const float* p = params;
-  float* g = grads;
-  if (logits != nullptr) w.logits = logits;
-  // shared-query gradients of the fused blocks of this call: one pair of launches at the end
-  // (their inputs live in per-block workspaces, which stay untouched until then)
-  pca::BwdDefer posts{};
-  posts.slab_ws = w.wg_slabs;
-  posts.slab_cap = w.wg_slab_bytes;
-  // d = 256: all weight images of the step in one launch (phase 1 of a split step finds the images
-  // of phase 0 still in place: the parameters do not change in between)
-  pca::WeightImages images{};
-  pca::PrepJobs image_jobs{};
-  PCA_TRY(pca::images256_prepare(*c, L, s, p, w, &images, phase != 1, st, &image_jobs));
-  // what this call hands from block to block (StepCtx); a block queues its terminal reductions in `posts`
-  // when its call is given deferring(true), and launches them itself otherwise
-  pca::StepCtx ctx{};
-  ctx.images = images.n > 0 ? &images : nullptr;
-  auto deferring = [&](bool on) { ctx.defer = on ? &posts : nullptr; return &ctx; };
-  // d = 256: the [B*m]-row weight-gradient jobs of all five blocks in one launch at the flush -
-  // needs every block's operands in place until then: the hand-over form of enc.1 (its few-queries
-  // block works in w.scratch) and a workspace of its own for enc.0's few-queries block
-  const bool hand1 = s.m1[1].d == 256 && pca::mab_kind(s.m1[1]) == 1 && pca::mab_kind(s.m0[1]) == 2;
-  const bool defer_wg = w.wg256_def != nullptr && hand1 &&
-                        pca::mab_kind(s.pma) == 2 && s.pma.d == 256;
-  if (defer_wg) posts.wg256_ws = w.wg256_def;
-  if (phase != 1) {
-    // the set-resident forward runs the head stages in its own tail (PCA_SET128_HEAD=0: as a launch)
-    const bool fuse_head = pca::set128_on(*c, s) && c->C <= 64 && pca::env_not_zero("PCA_SET128_HEAD");
-    // ... and then the PMA's attention backward too (PCA_SET128_PMABWD=0: k_mab0_bwd, as a launch)
-    const bool pma_bwd = fuse_head && pca::env_not_zero("PCA_SET128_PMABWD");
-    pca::PmaHeadArgs head{};
-    if (fuse_head)
-      PCA_TRY(pca::pma_head_args(s.pma, pca::params_at(p, L.pma), w.saved[4], w.scratch, w.P,
-                                 p + L.wc, p + L.bc, labels, c->C, grad_scale, w.logits, w.dlogits,
-                                 w.dP, g + L.wc, g + L.bc, loss_out, stats, w.clsws, &posts, &head));
-    PCA_TRY(pca::forward(*c, L, s, p, X, w, true, st, &ctx, &image_jobs, fuse_head ? &head : nullptr,
-                         pma_bwd));
-    if (pca::pma_head_ok(s)) {
-      // dec.0 epilogue + dec.1 (Linear) + mean cross-entropy forward and backward + dec.0
-      // backward epilogue: one launch, one workgroup per set
-      if (!fuse_head)
-      PCA_TRY(pca::pma_head_launch(s.pma, pca::params_at(p, L.pma), w.saved[4], w.scratch, w.P,
-                                   p + L.wc, p + L.bc, labels, c->C, grad_scale, w.logits,
-                                   w.dlogits, w.dP, g + L.wc, g + L.bc, loss_out, stats,
-                                   w.clsws, &posts, st));
-      PCA_TRY(pca::mab0_bf16_bwd_ex(s.pma, p + L.S, w.Y[1], pca::params_at(p, L.pma),
-                                    w.saved[4], w.dP, g + L.S, w.dY2, 0,
-                                    pca::grads_at(g, L.pma), w.scratch,
-                                    pca::PCA_F_SKIP_HEAD | (pma_bwd ? pca::PCA_F_ATTN_DONE : 0), st,
-                                    deferring(true)));
-    } else {
-    // dec.1 (Linear) + mean cross-entropy, forward and backward
-    PCA_TRY(pca::cls_train_head(w.P, p + L.wc, p + L.bc, labels, c->B, c->d, c->C, grad_scale,
-                                w.logits, w.dlogits, w.dP, g + L.wc, g + L.bc, loss_out, stats,
-                                w.clsws, st, &posts));
-    const bool pma256 = s.pma.d == 256 && pca::mab_kind(s.pma) == 2;   // post stages deferred
-    PCA_TRY(pca::mab_bwd_any(s.pma, p + L.S, w.Y[1], pca::params_at(p, L.pma), w.saved[4],
-                             w.dP, g + L.S, w.dY2, 0, pca::grads_at(g, L.pma),
-                             pma256 ? w.scratch_pma : w.scratch, st, deferring(pma256)));
-    }
-    // enc.1: mab1(Y1, H2) then mab0(I2, Y1); Y1 feeds both, so dY1 accumulates
-    if (w.fused[1]) {
-      PCA_TRY(pca::isab_bf16_bwd(s.m0[1], s.m1[1], p + L.I[1], w.Y[0], w.H[1],
-                                 pca::params_at(p, L.mab0[1]), pca::params_at(p, L.mab1[1]),
-                                 w.saved[2], w.saved[3], w.dY2, g + L.I[1], w.dY1,
-                                 pca::grads_at(g, L.mab0[1]), pca::grads_at(g, L.mab1[1]),
-                                 w.scratch_bw[1], w.img[1], st, &posts));
-    } else {
-    // d = 256: mab1's fc_q weight-gradient job is handed to the few-queries block, whose two jobs
-    // read the same Y1 (StepCtx::armed); the two blocks then need separate workspaces - mab0 takes the
-    // forward / PMA scratch, which is free by now
-    ctx.armed = hand1;
-    PCA_TRY(pca::mab_bwd_any(s.m1[1], w.Y[0], w.H[1], pca::params_at(p, L.mab1[1]),
-                             w.saved[3], w.dY2, w.dY1, w.dH, 0, pca::grads_at(g, L.mab1[1]),
-                             w.scratch_bw[1], st, deferring(defer_wg)));
-    // (hand1: its post stage waits for the flush - w.scratch stays untouched)
-    PCA_TRY(pca::mab_bwd_any(s.m0[1], p + L.I[1], w.Y[0], pca::params_at(p, L.mab0[1]),
-                             w.saved[2], w.dH, g + L.I[1], w.dY1, 1, pca::grads_at(g, L.mab0[1]),
-                             hand1 ? w.scratch : w.scratch_bw[1], st, deferring(hand1)));
-    ctx.armed = false;
-    PCA_TRY(pca::wgrad256_handoff_flush(&ctx, w.scratch, st));   // (what nobody took runs on its own)
-    }
-  }
-  if (phase != 0) {
-    // enc.0: the set itself needs no gradient
-    if (w.fused[0]) {
-      PCA_TRY(pca::isab_bf16_bwd(s.m0[0], s.m1[0], p + L.I[0], X, w.H[0],
-                                 pca::params_at(p, L.mab0[0]), pca::params_at(p, L.mab1[0]),
-                                 w.saved[0], w.saved[1], w.dY1, g + L.I[0], nullptr,
-                                 pca::grads_at(g, L.mab0[0]), pca::grads_at(g, L.mab1[0]),
-                                 w.scratch_bw[0], w.img[0], st, &posts));
-    } else {
-    PCA_TRY(pca::mab_bwd_any(s.m1[0], X, w.H[0], pca::params_at(p, L.mab1[0]), w.saved[1],
-                             w.dY1, nullptr, w.dH, 0, pca::grads_at(g, L.mab1[0]),
-                             w.scratch_bw[0], st, deferring(defer_wg)));
-    const bool fq256 = s.m0[0].d == 256 && pca::mab_kind(s.m0[0]) == 2;
-    PCA_TRY(pca::mab_bwd_any(s.m0[0], p + L.I[0], X, pca::params_at(p, L.mab0[0]),
-                             w.saved[0], w.dH, g + L.I[0], nullptr, 0, pca::grads_at(g, L.mab0[0]),
-                             fq256 && defer_wg ? w.scratch_m0 : w.scratch_bw[0], st, deferring(fq256)));
-    }
-  }
-  return pca::bwd_defer_flush(posts, st);
 }
 
 int pca_st_train_fwd_bwd(const pca_st_config* c, const float* params, const float* X,
@@ -615,7 +612,7 @@ int pca_st_train_fwd_bwd(const pca_st_config* c, const float* params, const floa
                          void* stream) {
   // phase 1 of a split step reads X again: the pack was consumed by phase 0
   PCA_TRY(pca::no_stale_pack("pca_st_train_fwd_bwd", phase != 1));
-  const int rc = st_train_fwd_bwd_impl(c, params, X, lengths, labels, grads, loss_out, stats, logits,
+  const int rc = pca::st_train_fwd_bwd(c, params, X, lengths, labels, grads, loss_out, stats, logits,
                                        grad_scale, phase, ws, stream);
   return rc != PCA_OK ? rc : pca::no_stale_pack("pca_st_train_fwd_bwd (exit)", false);
 }

@@ -144,3 +144,33 @@ def test_handoff_timeouts_are_surfaced(dev):
         eng.check_handoffs()
     other = trainer.STEngine(net, B, 300, _lib.MODE_BF16, training=True)   # N = 300: per-block launches
     assert other._handoff_word is None
+
+
+# pca_st_ws_bytes(cfg, 1) and the 11 words of pca_st_ws_layout (saved[0..4], H[0..1], Y[0..1], scratch, total)
+# of (B, N, din, d, h, m) = (8, 256, 2, 128, 4, 16), k = 1, C = 10, bf16 on an MI355X, recorded from the
+# library of the commit before csrc/st_engine.hip got its StepPlan (profiles/r08_step_plan.txt, check C)
+SET128_WS_BYTES = 105965312
+SET128_WS_LAYOUT = (0, 221184, 1433600, 2566144, 3778560, 5476864, 5542400, 5607936, 6656512, 9877248,
+                    105965312)
+
+
+def test_set128_workspace_has_the_handoff_room(dev):
+    """On a GPU the workspace of a set-resident shape includes the exchange area of the pair hand-offs; the
+    host-side pins of tests/test_sab_host.py see a library without a device, which reserves none.  Pinned:
+    the workspace's size, the offsets of the blocks in front of and behind the area, and that the engine
+    hands out the area's counter word for this shape and none for N = 300, which has no set-resident
+    launch.  Nothing is launched."""
+    import ctypes as C
+    from pca_hip import _lib
+    L = _lib.lib()
+    cfg = _lib.StConfig(8, 256, 2, 128, 4, 16, 1, 10, _lib.MODE_BF16)
+    words = (C.c_int64 * 11)()
+    _lib.check(L.pca_st_ws_layout(C.byref(cfg), C.cast(words, C.c_void_p)), "pca_st_ws_layout")
+    assert L.pca_st_ws_bytes(C.byref(cfg), 1) == SET128_WS_BYTES
+    assert tuple(words) == SET128_WS_LAYOUT
+    for N, there in ((256, True), (300, False)):
+        cfg.N = N
+        ws = torch.empty(L.pca_st_ws_bytes(C.byref(cfg), 1), dtype=torch.uint8, device=dev)
+        ptr = C.c_void_p()
+        _lib.check(L.pca_st_handoff_counter(C.byref(cfg), ws.data_ptr(), C.byref(ptr)), "pca_st_handoff_counter")
+        assert bool(ptr.value) == there, (N, ptr.value)
