@@ -4,101 +4,100 @@
 
 namespace pca {
 
-
-
-// kind as the C entry points see it (abi_kind below)
-static int check_f32(const pca_mab_shape* s, int kind) {
-  // the GEMM chains (kinds 0 and 4) exchange fp32 only; the fused kernels validate their own dtypes
-  PCA_REQUIRE((kind != 0 && kind != 4) || (s->q_dtype == PCA_F32 && s->k_dtype == PCA_F32 &&
-                                           s->y_dtype == PCA_F32),
-              "mab: the exact fp32 path needs fp32 Q, K and Y");
-  return PCA_OK;
-}
-
-// ---- mode resolution + dispatch, shared by the C entry points and the ST engine ----
-// kind: 0 = exact fp32 chain of GEMMs, 1 = fused bf16 mab1 (many queries, few keys),
-//       2 = fused bf16 mab0 (few shared queries, many keys),
-//       3 = the shipped d = 64 / 8-head shape, fused fp32 forward (inference only: sd64_fwd.hip)
-int mab_kind(const pca_mab_shape& s, bool inference) {
-  // (a fused mab1 has the m inducing-point outputs as keys: always all of them; a caller that
-  // masks keys of such a shape gets the exact path, whose softmax honours k_lengths)
-  if (s.ln) return 0;          // LayerNorm variants: exact chain only
-  const bool fused_mode = s.mode == PCA_MODE_BF16 || s.mode == PCA_MODE_FP8;
-  if (fused_mode && s.k_lengths == nullptr && mab1_bf16_supported(s, inference)) return 1;
-  if (fused_mode && mab0_bf16_supported(s)) return 2;
-  if (fused_mode && inference && sd64_kind(s) != 0) return 3;
-  return 0;
-}
-size_t mab_saved_bytes_any(const pca_mab_shape& s) {
-  const int k = mab_kind(s);
-  return k == 1 ? mab1_bf16_saved_bytes(s) : k == 2 ? mab0_bf16_saved_bytes(s)
-                                                    : mab_f32_saved_bytes(s);
-}
-size_t mab_fwd_ws_bytes_any(const pca_mab_shape& s) {
-  // inference (saved == NULL) keeps the intermediates in the scratch block instead; a training
-  // forward of the same shape never needs more (the exact chain's scratch is its saved block)
-  const int k = mab_kind(s, true);
-  if (k != mab_kind(s, false)) {
-    const size_t a = k == 3 ? sd64_fwd_ws_bytes(s)
-                            : k == 1 ? mab1_bf16_fwd_ws_bytes(s) : mab0_bf16_fwd_ws_bytes(s);
-    const size_t b = mab_f32_saved_bytes(s);
-    return a > b ? a : b;
+// ---- the path of one block (BlockPath, mab1_bf16.hpp), decided once per call and read by everything below ----
+BlockPath block_path(const pca_mab_shape& s, bool inference, bool abi) {
+  // LayerNorm variants: the exact chain only
+  if (!s.ln && (s.mode == PCA_MODE_BF16 || s.mode == PCA_MODE_FP8)) {
+    const bool d256 = s.d == 256;
+    // (a fused mab1 has the m inducing-point outputs as keys: always all of them; a caller that
+    // masks keys of such a shape gets the exact path, whose softmax honours k_lengths)
+    if (s.k_lengths == nullptr && mab1_bf16_supported(s, inference))
+      return d256 ? BlockPath::Mab1_256 : BlockPath::Mab1_128;
+    if (d256 ? mab0_d256_supported(s) : mab0_bf16_supported(s))
+      return d256 ? BlockPath::Mab0_256 : BlockPath::Mab0_128;
+    if (inference && sd64_kind(s) != 0) return BlockPath::Sd64;
   }
-  return k == 1 ? mab1_bf16_fwd_ws_bytes(s) : k == 2 ? mab0_bf16_fwd_ws_bytes(s)
-                                                     : mab_f32_saved_bytes(s);
-}
-size_t mab_bwd_ws_bytes_any(const pca_mab_shape& s) {
-  const int k = mab_kind(s);
-  return k == 1 ? mab1_bf16_bwd_ws_bytes(s) : k == 2 ? mab0_bf16_bwd_ws_bytes(s)
-                                                     : mab_f32_bwd_ws_bytes(s);
-}
-int mab_fwd_any(const pca_mab_shape& s, const void* Q, const void* K, const pca_mab_params& p,
-                void* Y, void* saved, void* ws, hipStream_t st, int flags, StepCtx* ctx) {
-  const int k = mab_kind(s, saved == nullptr);
-  if (k == 3) return sd64_fwd(s, (const float*)Q, (const float*)K, p, (float*)Y, ws, st);
-  if (k == 1) return mab1_bf16_fwd_ex(s, Q, (const float*)K, p, Y, saved, ws, flags, st, nullptr, ctx);
-  if (k == 2) return mab0_bf16_fwd_ex(s, (const float*)Q, K, p, (float*)Y, saved, ws, flags, st, ctx);
-  return mab_f32_fwd(s, (const float*)Q, (const float*)K, p, (float*)Y, saved ? saved : ws, st);
-}
-int mab_bwd_any(const pca_mab_shape& s, const void* Q, const void* K, const pca_mab_params& p,
-                const void* saved, const void* dY, void* dQ, void* dK, int dk_accumulate,
-                const pca_mab_grads& g, void* ws, hipStream_t st, StepCtx* ctx) {
-  const int k = mab_kind(s);
-  if (k == 2)
-    return mab0_bf16_bwd_ex(s, (const float*)Q, K, p, saved, (const float*)dY, (float*)dQ, dK,
-                            dk_accumulate, g, ws, 0, st, ctx);
-  if (k == 1)
-    return mab1_bf16_bwd_ex(s, Q, (const float*)K, p, saved, dY, dQ, (float*)dK, dk_accumulate, g,
-                            ws, 0, st, nullptr, nullptr, 0, nullptr, ctx);
-  return mab_f32_bwd(s, (const float*)Q, (const float*)K, p, saved, (const float*)dY,
-                     (float*)dQ, (float*)dK, dk_accumulate, g, ws, st);
+  // a self-attention-shaped block (SAB, set_transformer-master/modules.py:35-41: per-set queries, nq = nk,
+  // dq = dk) that no fused kernel takes, in PCA_MODE_BF16 or PCA_MODE_FP8 (run alike: no fp8 operands): the
+  // bf16-operand chain of mab_f32.hip with its attention on the fused core (attn_core.hip, head dims 8 / 16 /
+  // 32), so nothing of size nq x nk is ever stored.  Only the pca_mab_* entry points ask for it (abi); the ST
+  // engine keeps its blocks as they are.
+  return abi && attn_core_sab_ok(s) ? BlockPath::ExactCore : BlockPath::Exact;
 }
 
-// kind 4 = a self-attention-shaped block (SAB, set_transformer-master/modules.py:35-41: per-set queries,
-// nq = nk, dq = dk) that kinds 1-3 do not take, in PCA_MODE_BF16 or PCA_MODE_FP8 (run alike: no fp8
-// operands): the bf16-operand chain of mab_f32.hip with its attention on the fused core (attn_core.hip,
-// head dims 8 / 16 / 32), so nothing of size nq x nk is ever stored.  Only the pca_mab_* entry points
-// select it; the ST engine dispatches on mab_kind and keeps its blocks as they are.
-static int abi_kind(const pca_mab_shape& s, bool inference = false) {
-  const int k = mab_kind(s, inference);
-  return k == 0 && attn_core_sab_ok(s) ? 4 : k;
+size_t mab_saved_bytes(BlockPath path, const pca_mab_shape& s) {
+  switch (path) {
+    case BlockPath::Mab1_128: case BlockPath::Mab1_256: return mab1_bf16_saved_bytes(s);
+    case BlockPath::Mab0_128: return mab0_bf16_saved_bytes(s);
+    case BlockPath::Mab0_256: return mab0_d256_saved_bytes(s);
+    case BlockPath::ExactCore: return mab_f32_saved_bytes(s, true);
+    case BlockPath::Exact: case BlockPath::Sd64: break;      // (Sd64: inference only, nothing is saved)
+  }
+  return mab_f32_saved_bytes(s);
 }
-static size_t abi_saved_bytes(const pca_mab_shape& s) {
-  return abi_kind(s) == 4 ? mab_f32_saved_bytes(s, true) : mab_saved_bytes_any(s);
-}
-static size_t abi_fwd_ws_bytes(const pca_mab_shape& s) {
-  const int ki = abi_kind(s, true), kt = abi_kind(s, false);
-  if (ki != 4 && kt != 4) return mab_fwd_ws_bytes_any(s);
-  // the chain's scratch is its saved block; an inference-only kernel of the shape (kind 3) needs its own
-  const size_t a = mab_f32_saved_bytes(s, true), b = ki == 3 ? sd64_fwd_ws_bytes(s) : 0;
+// The forward's scratch block serves both kinds of call: the inference path's scratch (inference, saved ==
+// NULL, keeps the intermediates there), or the exact chain's saved block (its scratch) when training and
+// inference paths differ, whichever is larger.
+size_t mab_fwd_ws_bytes(BlockPath inference, BlockPath training, const pca_mab_shape& s) {
+  size_t a = 0;
+  switch (inference) {
+    case BlockPath::Mab1_128: case BlockPath::Mab1_256: a = mab1_bf16_fwd_ws_bytes(s); break;
+    case BlockPath::Mab0_128: a = mab0_bf16_fwd_ws_bytes(s); break;
+    case BlockPath::Mab0_256: a = mab0_d256_fwd_ws_bytes(s); break;
+    case BlockPath::Sd64: a = sd64_fwd_ws_bytes(s); break;
+    case BlockPath::Exact: case BlockPath::ExactCore: a = mab_saved_bytes(inference, s); break;
+  }
+  const size_t b = training != inference ? mab_saved_bytes(training, s) : 0;
   return a > b ? a : b;
 }
-static size_t abi_bwd_ws_bytes(const pca_mab_shape& s) {
-  return abi_kind(s) == 4 ? mab_f32_bwd_ws_bytes(s, true) : mab_bwd_ws_bytes_any(s);
+size_t mab_bwd_ws_bytes(BlockPath path, const pca_mab_shape& s) {
+  switch (path) {
+    case BlockPath::Mab1_128: return mab1_bf16_bwd_ws_bytes(s);
+    case BlockPath::Mab1_256: return mab1_d256_bwd_ws_bytes(s);
+    case BlockPath::Mab0_128: return mab0_bf16_bwd_ws_bytes(s);
+    case BlockPath::Mab0_256: return mab0_d256_bwd_ws_bytes(s);
+    case BlockPath::ExactCore: return mab_f32_bwd_ws_bytes(s, true);
+    case BlockPath::Exact: case BlockPath::Sd64: break;
+  }
+  return mab_f32_bwd_ws_bytes(s);
 }
-}  // namespace pca
+int mab_fwd(BlockPath path, const pca_mab_shape& s, const void* Q, const void* K, const pca_mab_params& p,
+            void* Y, void* saved, void* ws, hipStream_t st, int flags, StepCtx* ctx) {
+  switch (path) {
+    case BlockPath::Mab1_128: case BlockPath::Mab1_256:      // (the many-queries forward serves both widths)
+      return mab1_bf16_fwd_ex(s, Q, (const float*)K, p, Y, saved, ws, flags, st, nullptr, ctx);
+    case BlockPath::Mab0_128:
+      return mab0_bf16_fwd_ex(s, (const float*)Q, K, p, (float*)Y, saved, ws, flags, st, ctx);
+    case BlockPath::Mab0_256:
+      return mab0_d256_fwd(s, (const float*)Q, K, p, (float*)Y, saved, ws, flags, st, ctx);
+    case BlockPath::Sd64:
+      return sd64_fwd(s, (const float*)Q, (const float*)K, p, (float*)Y, ws, st);
+    case BlockPath::Exact: case BlockPath::ExactCore: break;
+  }
+  return mab_f32_fwd(s, (const float*)Q, (const float*)K, p, (float*)Y, saved ? saved : ws, st,
+                     path == BlockPath::ExactCore);
+}
+int mab_bwd(BlockPath path, const pca_mab_shape& s, const void* Q, const void* K, const pca_mab_params& p,
+            const void* saved, const void* dY, void* dQ, void* dK, int dk_accumulate,
+            const pca_mab_grads& g, void* ws, hipStream_t st, StepCtx* ctx) {
+  switch (path) {
+    case BlockPath::Mab1_128:
+      return mab1_bf16_bwd_ex(s, Q, (const float*)K, p, saved, dY, dQ, (float*)dK, dk_accumulate, g,
+                              ws, 0, st, nullptr, nullptr, 0, nullptr, ctx);
+    case BlockPath::Mab1_256:      // three launches + the 256-wide weight-gradient reduction (d256_host.hip)
+      return mab1_d256_bwd(s, Q, (const float*)K, p, saved, dY, dQ, (float*)dK, dk_accumulate, g, ws, st, ctx);
+    case BlockPath::Mab0_128:
+      return mab0_bf16_bwd_ex(s, (const float*)Q, K, p, saved, (const float*)dY, (float*)dQ, dK,
+                              dk_accumulate, g, ws, 0, st, ctx);
+    case BlockPath::Mab0_256:
+      return mab0_d256_bwd(s, (const float*)Q, K, p, saved, (const float*)dY, (float*)dQ, dK,
+                           dk_accumulate, g, ws, st, ctx);
+    case BlockPath::Exact: case BlockPath::ExactCore: case BlockPath::Sd64: break;
+  }
+  return mab_f32_bwd(s, (const float*)Q, (const float*)K, p, saved, (const float*)dY, (float*)dQ,
+                     (float*)dK, dk_accumulate, g, ws, st, path == BlockPath::ExactCore);
+}
 
-namespace pca {
 int no_stale_pack(const char* where, bool pack_allowed) {
   PCA_REQUIRE(pack_allowed || !pack_pending(),
               "%s: a deferred pack is pending on this thread (only pca_st_forward / pca_st_train_fwd_bwd "
@@ -109,11 +108,19 @@ int no_stale_pack(const char* where, bool pack_allowed) {
 
 extern "C" {
 
+// the path of a pca_mab_* call: what block_path answers with the SAB chain on the fused core included
+static pca::BlockPath abi_path(const pca_mab_shape* s, bool inference = false) {
+  return pca::block_path(*s, inference, true);
+}
+static bool on_chain(pca::BlockPath path) {
+  return path == pca::BlockPath::Exact || path == pca::BlockPath::ExactCore;
+}
+
 // An explicit PCA_MODE_BF16 request must be served by a fused kernel (no silent change of
 // arithmetic at this level); callers that want "bf16 where available" query
 // pca_mab_saved_bytes() first, which returns 0 for unsupported bf16 shapes.
-static int bf16_demand(const pca_mab_shape* s, bool inference = false) {
-  if ((s->mode == PCA_MODE_BF16 || s->mode == PCA_MODE_FP8) && pca::abi_kind(*s, inference) == 0) {
+static int bf16_demand(const pca_mab_shape* s, pca::BlockPath path) {
+  if ((s->mode == PCA_MODE_BF16 || s->mode == PCA_MODE_FP8) && path == pca::BlockPath::Exact) {
     pca::set_error("mab: no bf16 / fp8 kernel for B=%d nq=%d nk=%d dq=%d dk=%d d=%d h=%d q_shared=%d",
                    s->B, s->nq, s->nk, s->dq, s->dk, s->d, s->h, s->q_shared);
     return PCA_EUNSUPPORTED;
@@ -124,20 +131,28 @@ static int bf16_demand(const pca_mab_shape* s, bool inference = false) {
   }
   return PCA_OK;
 }
+static int check_f32(const pca_mab_shape* s, pca::BlockPath path) {
+  // the GEMM chains exchange fp32 only; the fused kernels validate their own dtypes
+  PCA_REQUIRE(!on_chain(path) || (s->q_dtype == PCA_F32 && s->k_dtype == PCA_F32 && s->y_dtype == PCA_F32),
+              "mab: the exact fp32 path needs fp32 Q, K and Y");
+  return PCA_OK;
+}
 
 size_t pca_mab_saved_bytes(const pca_mab_shape* s) {
-  if (pca::validate_shape(s) != PCA_OK || bf16_demand(s) != PCA_OK) return 0;
-  return pca::abi_saved_bytes(*s);
+  if (pca::validate_shape(s) != PCA_OK) return 0;
+  const pca::BlockPath path = abi_path(s);
+  return bf16_demand(s, path) != PCA_OK ? 0 : pca::mab_saved_bytes(path, *s);
 }
 size_t pca_mab_fwd_ws_bytes(const pca_mab_shape* s) {
-  if (pca::validate_shape(s) != PCA_OK || bf16_demand(s, true) != PCA_OK) return 0;
-  return pca::abi_fwd_ws_bytes(*s);
+  if (pca::validate_shape(s) != PCA_OK) return 0;
+  const pca::BlockPath inference = abi_path(s, true);
+  return bf16_demand(s, inference) != PCA_OK ? 0 : pca::mab_fwd_ws_bytes(inference, abi_path(s), *s);
 }
 size_t pca_mab_bwd_ws_bytes(const pca_mab_shape* s) {
-  if (pca::validate_shape(s) != PCA_OK || bf16_demand(s) != PCA_OK) return 0;
-  return pca::abi_bwd_ws_bytes(*s);
+  if (pca::validate_shape(s) != PCA_OK) return 0;
+  const pca::BlockPath path = abi_path(s);
+  return bf16_demand(s, path) != PCA_OK ? 0 : pca::mab_bwd_ws_bytes(path, *s);
 }
-
 
 // runs the body between two checks that no deferred pack is pending: these calls do not consume one
 #define PCA_WITH_PACK_CHECK(where, call)                             \
@@ -154,17 +169,12 @@ int pca_mab_fwd(const pca_mab_shape* s, const void* Q, const void* K,
   PCA_REQUIRE(Q && K && p && Y, "mab_fwd: null pointer");
   PCA_REQUIRE(p->wq && p->bq && p->wk && p->bk && p->wv && p->bv && p->wo && p->bo,
               "mab_fwd: null parameter");
-  PCA_TRY(bf16_demand(s, saved == nullptr));
-  const int kind = pca::abi_kind(*s, saved == nullptr);
-  PCA_TRY(pca::check_f32(s, kind));
-  PCA_REQUIRE(ws != nullptr || (saved != nullptr && (kind == 0 || kind == 4)),
-              "mab_fwd: scratch block required");
-  if (kind == 4)
-    PCA_WITH_PACK_CHECK("pca_mab_fwd",
-                        pca::mab_f32_fwd(*s, (const float*)Q, (const float*)K, *p, (float*)Y,
-                                         saved ? saved : ws, pca::as_stream(stream), true));
+  const pca::BlockPath path = abi_path(s, saved == nullptr);
+  PCA_TRY(bf16_demand(s, path));
+  PCA_TRY(check_f32(s, path));
+  PCA_REQUIRE(ws != nullptr || (saved != nullptr && on_chain(path)), "mab_fwd: scratch block required");
   PCA_WITH_PACK_CHECK("pca_mab_fwd",
-                      pca::mab_fwd_any(*s, Q, K, *p, Y, saved, ws, pca::as_stream(stream)));
+                      pca::mab_fwd(path, *s, Q, K, *p, Y, saved, ws, pca::as_stream(stream)));
 }
 
 int pca_mab_bwd(const pca_mab_shape* s, const void* Q, const void* K,
@@ -174,17 +184,12 @@ int pca_mab_bwd(const pca_mab_shape* s, const void* Q, const void* K,
   PCA_REQUIRE(Q && K && p && saved && dY && g && ws, "mab_bwd: null pointer");
   PCA_REQUIRE(g->wq && g->bq && g->wk && g->bk && g->wv && g->bv && g->wo && g->bo,
               "mab_bwd: null gradient buffer");
-  PCA_TRY(bf16_demand(s));
-  const int kind = pca::abi_kind(*s);
-  PCA_TRY(pca::check_f32(s, kind));
-  if (kind == 4)
-    PCA_WITH_PACK_CHECK("pca_mab_bwd",
-                        pca::mab_f32_bwd(*s, (const float*)Q, (const float*)K, *p, saved, (const float*)dY,
-                                         (float*)dQ, (float*)dK, dk_accumulate, *g, ws,
-                                         pca::as_stream(stream), true));
+  const pca::BlockPath path = abi_path(s);
+  PCA_TRY(bf16_demand(s, path));
+  PCA_TRY(check_f32(s, path));
   PCA_WITH_PACK_CHECK("pca_mab_bwd",
-                      pca::mab_bwd_any(*s, Q, K, *p, saved, dY, dQ, dK, dk_accumulate, *g, ws,
-                                       pca::as_stream(stream)));
+                      pca::mab_bwd(path, *s, Q, K, *p, saved, dY, dQ, dK, dk_accumulate, *g, ws,
+                                   pca::as_stream(stream)));
 }
 
 int pca_linear_fwd(const float* X, const float* W, const float* b, float* Y, int64_t M,

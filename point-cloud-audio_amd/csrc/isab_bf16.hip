@@ -12,8 +12,8 @@ namespace pca {
 
 // s0 = mab0(I, X) shape, s1 = mab1(X, H) shape of the same ISAB
 bool isab_bf16_supported(const pca_mab_shape& s0, const pca_mab_shape& s1) {
-  return mab_kind(s0) == 2 && mab_kind(s1) == 1 && s0.nq == 16 && s1.nk == 16 && s0.h == 4 &&
-         s0.d == 128 && s0.B == s1.B && s0.nk == s1.nq;
+  return block_path(s0) == BlockPath::Mab0_128 && block_path(s1) == BlockPath::Mab1_128 && s0.nq == 16 &&
+         s1.nk == 16 && s0.h == 4 && s0.B == s1.B && s0.nk == s1.nq;
 }
 
 namespace {

@@ -775,7 +775,6 @@ __global__ __launch_bounds__(256) void k_mab0_epi(const float* __restrict__ Tp, 
 
 // ---- host side --------------------------------------------------------------------
 bool mab0_bf16_supported(const pca_mab_shape& s) {
-  if (s.d == 256) return mab0_d256_supported(s);
   const int R = s.h * s.nq;
   if (!(s.nq == 16 || s.nq <= 2)) return false;      // epilogue: 8 or 1 queries per thread
   // the keys X may be bf16 when they are a hidden tensor (dk == d)
@@ -897,18 +896,15 @@ size_t mab0_carve_saved(const pca_mab_shape& s, Mab0Saved* out, void* base) {
 }
 
 size_t mab0_bf16_saved_bytes(const pca_mab_shape& s) {
-  if (s.d == 256) return mab0_d256_saved_bytes(s);
   return mab0_carve_saved(s, nullptr, nullptr);
 }
 size_t mab0_bf16_fwd_ws_bytes(const pca_mab_shape& s) {
-  if (s.d == 256) return mab0_d256_fwd_ws_bytes(s);
   return mab0_carve_saved(s, nullptr, nullptr);
 }
 
 int mab0_bf16_fwd_ex(const pca_mab_shape& s, const float* I, const void* X,
                      const pca_mab_params& p, float* H, void* saved, void* ws, int flags,
                      hipStream_t st, StepCtx* ctx) {
-  if (s.d == 256) return mab0_d256_fwd(s, I, X, p, H, saved, ws, flags, st, ctx);
   PCA_REQUIRE(mab0_bf16_supported(s), "mab0_bf16_fwd: unsupported shape");
   const bool training = saved != nullptr;
   PCA_REQUIRE(training || ws != nullptr, "mab0_bf16_fwd: scratch required");

@@ -1019,8 +1019,16 @@ size_t mab0_carve_bwd_ws(const pca_mab_shape& s, Mab0BwdWs* out, void* base) {
 }
 
 size_t mab0_bf16_bwd_ws_bytes(const pca_mab_shape& s) {
-  if (s.d == 256) return mab0_d256_bwd_ws_bytes(s);
   return mab0_carve_bwd_ws(s, nullptr, nullptr);
+}
+
+// a fixed-order slab sum: with the other sums of the step when the caller defers them, else right away
+static int slab_sum_defer(BwdDefer* defer, const SlabSumJob& sj, hipStream_t st) {
+  SlabSumJobs one{};
+  SlabSumJobs& J = defer != nullptr ? defer->sums : one;
+  PCA_REQUIRE(J.n < 40, "mab0_bf16_bwd: slab-sum table full");
+  J.j[J.n++] = sj;
+  return defer != nullptr ? PCA_OK : slab_sum_jobs(one, st);
 }
 
 // dQ -> dI [m, dq] (ACCUMULATED, may be null), dK -> dX [B, N, dk] (written or accumulated)
@@ -1031,8 +1039,7 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
   PCA_REQUIRE(mid == nullptr || (s.d == 128 && s.nq == 16 && s.h == 4 && (flags & PCA_F_SKIP_HEAD) &&
                                  !(flags & PCA_F_ATTN_DONE)),
               "mab0_bf16_bwd: the mid chain fuses into an ISAB's few-queries block only");
-  if (s.d == 256)
-    return mab0_d256_bwd(s, I, X, p, saved, dH, dI, dX, dk_accumulate, gr, ws, st, ctx);
+  PCA_REQUIRE(s.d == 128, "mab0_bf16_bwd: d = 128 only (d = 256: mab0_d256_bwd)");
   BwdDefer* const defer = defer_of(ctx);
   Mab0Saved v;
   mab0_carve_saved(s, &v, const_cast<void*>(saved));
@@ -1087,29 +1094,13 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
     PCA_TRY(check_launch("k_mab0_bwd_small"));
     if (sl != nullptr) {
       // (only the first R * dk floats of the [Rp][dk] block are read by the post stage)
-      const SlabSumJob sj{sl, w.DG, s.B, R * dk, 0, 0};
-      if (defer != nullptr) {
-        PCA_REQUIRE(defer->sums.n < 40, "mab0_bf16_bwd: slab-sum table full");
-        defer->sums.j[defer->sums.n++] = sj;
-      } else {
-        SlabSumJobs one{};
-        one.j[one.n++] = sj;
-        PCA_TRY(slab_sum_jobs(one, st));
-      }
+      PCA_TRY(slab_sum_defer(defer, SlabSumJob{sl, w.DG, s.B, R * dk, 0, 0}, st));
     }
   } else if (flags & PCA_F_ATTN_DONE) {
     // the set-resident forward ran the attention backward and left the slabs k_mab0_bwd would have
     // written: only their fixed-order sum is left
     PCA_REQUIRE(head_done && R * dk == 512, "mab0_bf16_bwd: set-resident PMA backward with R=%d dk=%d", R, dk);
-    const SlabSumJob sj{w.slabs, w.DG, s.B * mab0_bwd_splits(s), R * dk, 0};
-    if (defer != nullptr) {
-      PCA_REQUIRE(defer->sums.n < 40, "mab0_bf16_bwd: slab-sum table full");
-      defer->sums.j[defer->sums.n++] = sj;
-    } else {
-      SlabSumJobs one{};
-      one.j[one.n++] = sj;
-      PCA_TRY(slab_sum_jobs(one, st));
-    }
+    PCA_TRY(slab_sum_defer(defer, SlabSumJob{w.slabs, w.DG, s.B * mab0_bwd_splits(s), R * dk, 0, 0}, st));
   } else {
     const int S = mab0_bwd_splits(s);
     Mab0BwdArgs a{X, v.Gb, v.GtP, w.dTb, w.dTt, w.LSEp, w.Delta, dX, w.DG, s.B, s.nk,
@@ -1139,15 +1130,7 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
     PCA_TRY(check_launch("k_mab0_bwd"));
     // dG = the workgroups' slabs added in a fixed order: with the other sums of the step when
     // the caller defers them, else right away
-    const SlabSumJob sj{w.slabs, w.DG, s.B * S, R * dk, 0};
-    if (defer != nullptr) {
-      PCA_REQUIRE(defer->sums.n < 40, "mab0_bf16_bwd: slab-sum table full");
-      defer->sums.j[defer->sums.n++] = sj;
-    } else {
-      SlabSumJobs one{};
-      one.j[one.n++] = sj;
-      PCA_TRY(slab_sum_jobs(one, st));
-    }
+    PCA_TRY(slab_sum_defer(defer, SlabSumJob{w.slabs, w.DG, s.B * S, R * dk, 0, 0}, st));
   }
 
   // ---- parameter gradients of the epilogue: [B*m]-row reductions, ONE MFMA launch ----
@@ -1169,14 +1152,11 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
   // k_mid_bwd / k_mab0_epi_bwd left dO per set, the post kernel sums it
   Mab0PostJob pj{nullptr, w.DG, v.Qp, p.wk, I, p.wq, gr.wk, w.dQp, gr.wq,
                  gr.bq, dI, m, d, dk, s.dq, h, sl2e, w.dO, s.B};
-  if (defer != nullptr) {
-    PCA_REQUIRE(defer->posts.n < 3, "mab0_bf16_bwd: post-job table full");
-    defer->posts.j[defer->posts.n++] = pj;
-    return PCA_OK;
-  }
   Mab0PostJobs one{};
-  one.j[one.n++] = pj;
-  return mab0_post_launch(one, st);
+  Mab0PostJobs& J = defer != nullptr ? defer->posts : one;      // queued like the slab sums, or run now
+  PCA_REQUIRE(J.n < 3, "mab0_bf16_bwd: post-job table full");
+  J.j[J.n++] = pj;
+  return defer != nullptr ? PCA_OK : mab0_post_launch(one, st);
 }
 
 }  // namespace pca

@@ -1,4 +1,6 @@
-// Declarations shared by the fused bf16 mab1 forward / backward translation units.
+// Host-side declarations of the attention blocks: every host entry point of the exact, d = 64 and d = 128
+// paths, the d = 256 blocks' entries, the per-block dispatch (BlockPath) and the job / workspace structures the
+// translation units hand to each other.  (Named for the first kernel family that needed a shared header.)
 #pragma once
 #include "pca_common.h"
 #include "mfma_common.hpp"
@@ -193,7 +195,6 @@ enum {
   PCA_F_KV_READY = 2,        // mab1 fwd: Kp/Vp images already written (by mid_fwd / mid256_fwd)
   PCA_F_SKIP_KV_TAIL = 4,    // mab1 bwd: stop after dKp/dVp (mid_bwd + batched wgrad follow)
   PCA_F_SKIP_HEAD = 8,       // mab0 bwd: dT/Delta images, dZ, dO, dQs already produced
-  PCA_F_IMAGES_READY = 16,   // weight images were prepared by the caller (IsabImg)
   PCA_F_PREP_DONE = 32,      // mab0 fwd: Qp / G images were prepared by the caller
   PCA_F_SKIP_WGRAD = 64,     // mab0 bwd: dWo / dWv reductions are done by the caller; DG is clear
   PCA_F_ATTN_DONE = 128      // mab0 bwd (PMA, d = 128): the caller's launch ran k_mab0_bwd's part and left
@@ -245,7 +246,7 @@ int prep_weight_f8(const float* src, void* dst, int rows, int cols, int mode, fl
 // fused attention core of the bf16-operand GEMM chain for head dims <= 16 (attn_core.hip): O = Q_ + A V_
 // and its adjoint without the [B h, nq, nk] matrix A (LSE [B][h][nq] is what is saved instead)
 bool attn_core_ok(const pca_mab_shape& s);
-// self-attention-shaped blocks (SAB) reached through the C ABI only (kind 4, api_mab.hip): the same core
+// self-attention-shaped blocks (SAB) reached through the C ABI only (BlockPath::ExactCore): the same core
 // for head dims 8 / 16 at d <= 128, and its head-dim-32 kernels for d <= 256.  Never consulted by the
 // ST engine, whose blocks keep attn_core_ok.
 bool attn_core_sab_ok(const pca_mab_shape& s);
@@ -274,7 +275,7 @@ int lin64_fc_o_bwd(const float* dY, const float* Z, const float* W, float* dZ, f
                    hipStream_t st);
 // exact fp32 path (mab_f32.hip)
 int validate_shape(const pca_mab_shape* s);
-// core / sab = true (kind 4, attn_core_sab_ok shapes): the attention runs on the fused core and the
+// core / sab = true (BlockPath::ExactCore): the attention runs on the fused core and the
 // backward's weight gradients on wgrad_rows; false: the core where attn_core_ok holds, else through the
 // materialised A, and linear_dw_db
 size_t mab_f32_saved_bytes(const pca_mab_shape& s, bool core = false);
@@ -307,7 +308,7 @@ int linear_dx_acc_f32(const float* dY, const float* W, float* dX, int64_t M, int
 // fused mab1 (many queries X, few keys H).  X / Y / dY / dX are fp32 or bf16 per the shape's
 // q_dtype / y_dtype; H and dH are fp32
 // the shipped d = 64 / 8 heads / <= 64 inducing points shape: fused fp32 forward (sd64_fwd.hip);
-// kind 1 = many queries, 2 = few shared queries, 0 = another shape
+// 1 = many queries, 2 = few shared queries, 0 = another shape
 int sd64_kind(const pca_mab_shape& s);
 size_t sd64_fwd_ws_bytes(const pca_mab_shape& s);
 int sd64_fwd(const pca_mab_shape& s, const float* Q, const float* K, const pca_mab_params& p,
@@ -477,17 +478,26 @@ int mab0_attn_small_launch(const float* X, const float* Gf, int B, int N, int R,
 int mab0_bwd_small_launch(const float* X, const float* Gf, const float* dTf, const float* LSE,
                           const float* Delta, int B, int N, int R, int Rp, int dk, float* DG,
                           const int32_t* lengths, hipStream_t st, float* slabs = nullptr);
-// per-block dispatch (api_mab.hip): kind 0 exact fp32, 1 fused mab1, 2 fused mab0; flags / ctx go to the
-// fused kinds' *_ex entry points
-int mab_kind(const pca_mab_shape& s, bool inference = false);
-size_t mab_saved_bytes_any(const pca_mab_shape& s);
-size_t mab_fwd_ws_bytes_any(const pca_mab_shape& s);
-size_t mab_bwd_ws_bytes_any(const pca_mab_shape& s);
-int mab_fwd_any(const pca_mab_shape& s, const void* Q, const void* K, const pca_mab_params& p,
-                void* Y, void* saved, void* ws, hipStream_t st, int flags = 0, StepCtx* ctx = nullptr);
-int mab_bwd_any(const pca_mab_shape& s, const void* Q, const void* K, const pca_mab_params& p,
-                const void* saved, const void* dY, void* dQ, void* dK, int dk_accumulate,
-                const pca_mab_grads& g, void* ws, hipStream_t st, StepCtx* ctx = nullptr);
+// Per-block dispatch (api_mab.hip).  The path of a block is decided once per call, by block_path, and handed
+// to the functions below; flags / ctx go to the fused paths' entry points.
+//   Exact      fp32 chain of GEMMs (mab_f32.hip), bf16 operands in the fused modes
+//   ExactCore  the same chain with a self-attention block's attention on the fused core: pca_mab_* only (abi)
+//   Mab1_*     fused many queries / few keys, d = 128 or 256 (one forward; the d = 256 backward in d256_host.hip)
+//   Mab0_*     fused few shared queries / many keys, d = 128 (mab0_*.hip) or 256 (d256_host.hip)
+//   Sd64       the d = 64 / 8-head fused fp32 forward, inference only (sd64_fwd.hip picks many / few queries
+//              from q_shared, which it needs for its argument roles anyway)
+enum class BlockPath { Exact, ExactCore, Mab1_128, Mab1_256, Mab0_128, Mab0_256, Sd64 };
+BlockPath block_path(const pca_mab_shape& s, bool inference = false, bool abi = false);
+inline bool is_mab1(BlockPath p) { return p == BlockPath::Mab1_128 || p == BlockPath::Mab1_256; }
+inline bool is_mab0(BlockPath p) { return p == BlockPath::Mab0_128 || p == BlockPath::Mab0_256; }
+size_t mab_saved_bytes(BlockPath path, const pca_mab_shape& s);
+size_t mab_fwd_ws_bytes(BlockPath inference, BlockPath training, const pca_mab_shape& s);
+size_t mab_bwd_ws_bytes(BlockPath path, const pca_mab_shape& s);
+int mab_fwd(BlockPath path, const pca_mab_shape& s, const void* Q, const void* K, const pca_mab_params& p,
+            void* Y, void* saved, void* ws, hipStream_t st, int flags = 0, StepCtx* ctx = nullptr);
+int mab_bwd(BlockPath path, const pca_mab_shape& s, const void* Q, const void* K, const pca_mab_params& p,
+            const void* saved, const void* dY, void* dQ, void* dK, int dk_accumulate,
+            const pca_mab_grads& g, void* ws, hipStream_t st, StepCtx* ctx = nullptr);
 // fused ISAB (isab_bf16.hip)
 bool isab_bf16_supported(const pca_mab_shape& s0, const pca_mab_shape& s1);
 size_t isab_bf16_fwd_ws_bytes(const pca_mab_shape& s0, const pca_mab_shape& s1);

@@ -65,7 +65,7 @@ struct BwdWsF32 {
   float *dZ, *dO, *dQp, *dA, *dKp, *dVp, *dQps;
   float* dYp;       // ln = 1: gradient w.r.t. the input of ln1
   float* Wt;        // [d][d]: a transposed weight (linear_dx of large bf16-mode problems)
-  float* wpart;     // self-attention blocks (kind 4): the slabs of the deterministic weight gradients
+  float* wpart;     // self-attention blocks (BlockPath::ExactCore): the slabs of the deterministic weight gradients
 };
 
 inline size_t bwd_ws_elems(const pca_mab_shape& s, BwdWsF32* out, void* base, bool core, bool sab) {

@@ -80,13 +80,13 @@ inline pca_mab_shape shape(const pca_st_config& c, int nq, int nk, int dq, int d
 }
 
 // The engine-level path of one call: which fused forms run, what is deferred, what gets room.  Filled once
-// per call by plan() and read by carve(), the preparation, the forward and the backward.  (The blocks' own
-// dispatch in api_mab.hip - mab_fwd_any, mab_bwd_any, *_bytes_any - still asks per block.)  DESIGN.md 5
+// per call by plan() and read by carve(), the preparation, the forward and the backward, the blocks' own
+// dispatch in api_mab.hip included: mab_fwd, mab_bwd and the *_bytes functions take the plan's path.  DESIGN.md 5
 struct StepPlan {
   bool training;
   pca_mab_shape m0[2], m1[2], pma;   // per ISAB: mab0 = MAB(I, X), mab1 = MAB(X, H); the PMA
-  int kind_m0[2], kind_m1[2], kind_pma;   // which kernel family serves each (api_mab.hip; an inference call:
-                                          // the inference kinds)
+  BlockPath path_m0[2], path_m1[2], path_pma;   // which kernel family serves each (block_path; an inference
+                                                // call: the inference paths)
   bool act_bf16;       // hidden activations Y1, Y2 (and their gradients) travel in bf16
   // everything below is false in an inference call
   bool isab128[2];     // the layer runs as ONE fused d = 128 ISAB (isab_bf16_fwd / _bwd)
@@ -134,9 +134,9 @@ inline StepPlan plan(const pca_st_config& c, bool training, const int32_t* lengt
     const bool isab128 = isab_bf16_supported(t.m0[0], t.m1[0]) &&
                          isab_bf16_supported(t.m0[1], t.m1[1]);
     // d = 256: every block has a fused kernel of its own (no ISAB-level fusion)
-    const bool blocks256 = c.d == 256 && mab_kind(t.m0[0]) == 2 && mab_kind(t.m1[0]) == 1 &&
-                           mab_kind(t.m0[1]) == 2 && mab_kind(t.m1[1]) == 1;
-    if ((isab128 || blocks256) && mab_kind(t.pma) == 2) {
+    const bool blocks256 = block_path(t.m0[0]) == BlockPath::Mab0_256 && block_path(t.m1[0]) == BlockPath::Mab1_256 &&
+                           block_path(t.m0[1]) == BlockPath::Mab0_256 && block_path(t.m1[1]) == BlockPath::Mab1_256;
+    if ((isab128 || blocks256) && is_mab0(block_path(t.pma))) {
       pl = t;
       pl.act_bf16 = true;
     }
@@ -144,24 +144,25 @@ inline StepPlan plan(const pca_st_config& c, bool training, const int32_t* lengt
   // variable-size sets: the points are the KEYS of the three blocks that attend over them
   pl.m0[0].k_lengths = pl.m0[1].k_lengths = pl.pma.k_lengths = lengths;
   for (int li = 0; li < 2; ++li) {
-    pl.kind_m0[li] = mab_kind(pl.m0[li], !training);
-    pl.kind_m1[li] = mab_kind(pl.m1[li], !training);
+    pl.path_m0[li] = block_path(pl.m0[li], !training);
+    pl.path_m1[li] = block_path(pl.m1[li], !training);
   }
-  pl.kind_pma = mab_kind(pl.pma, !training);
+  pl.path_pma = block_path(pl.pma, !training);
   if (!training) return pl;
   const bool d256 = c.d == 256;
   for (int li = 0; li < 2; ++li) {
     pl.isab128[li] = isab_bf16_supported(pl.m0[li], pl.m1[li]);
-    pl.isab256[li] = d256 && pl.kind_m0[li] == 2 && pl.kind_m1[li] == 1;
-    pl.img_m1[li] = d256 && pl.kind_m1[li] == 1 && pl.m1[li].nk == 32;
-    pl.img_m0[li] = d256 && pl.kind_m0[li] == 2 && pl.m0[li].dk == 256;
+    pl.isab256[li] = pl.path_m0[li] == BlockPath::Mab0_256 && pl.path_m1[li] == BlockPath::Mab1_256;
+    pl.img_m1[li] = pl.path_m1[li] == BlockPath::Mab1_256;      // (nk = 32: the only many-queries shape at d = 256)
+    pl.img_m0[li] = pl.path_m0[li] == BlockPath::Mab0_256 && pl.m0[li].dk == 256;
   }
   pl.img256 = d256 && (c.mode == PCA_MODE_BF16 || c.mode == PCA_MODE_FP8);
   pl.img256_f8 = d256 && c.mode == PCA_MODE_FP8;
-  pl.prep256 = d256 && pl.kind_m0[0] == 2 && pl.kind_m0[1] == 2 && pl.kind_pma == 2;
-  pl.pma_head = c.d == 128 && pl.kind_pma == 2;
-  pl.pma256 = d256 && pl.kind_pma == 2;
-  pl.fq_defer[0] = d256 && pl.kind_m0[0] == 2;
+  pl.prep256 = pl.path_m0[0] == BlockPath::Mab0_256 && pl.path_m0[1] == BlockPath::Mab0_256 &&
+               pl.path_pma == BlockPath::Mab0_256;
+  pl.pma_head = pl.path_pma == BlockPath::Mab0_128;
+  pl.pma256 = pl.path_pma == BlockPath::Mab0_256;
+  pl.fq_defer[0] = pl.path_m0[0] == BlockPath::Mab0_256;
   pl.fq_defer[1] = pl.armed[1] = pl.isab256[1];      // (enc.0's mab1 reads the fp32 set: nothing to hand over)
   pl.defer_wg = pl.isab256[0] && pl.isab256[1] && pl.pma256;
   pl.set128_room = set128_shape_ok(c.B, c.N, c.din, c.d, c.h, c.m, c.k);
@@ -203,14 +204,16 @@ inline size_t carve(const pca_st_config& c, const StepPlan& pl, Ws* out, void* b
   Carver cv(base);
   Ws w{};
   const pca_mab_shape* order[5] = {&pl.m0[0], &pl.m1[0], &pl.m0[1], &pl.m1[1], &pl.pma};
+  const BlockPath path[5] = {pl.path_m0[0], pl.path_m1[0], pl.path_m0[1], pl.path_m1[1], pl.path_pma};
   size_t max_scratch = 0;
   for (int i = 0; i < 5; ++i) {
-    const size_t fb = mab_fwd_ws_bytes_any(*order[i]);
+    // (one scratch size for both kinds of call: the inference path's block and the training one's)
+    const size_t fb = mab_fwd_ws_bytes(block_path(*order[i], true), block_path(*order[i], false), *order[i]);
     max_scratch = fb > max_scratch ? fb : max_scratch;
     if (pl.training) {
-      const size_t bb = mab_bwd_ws_bytes_any(*order[i]);
+      const size_t bb = mab_bwd_ws_bytes(path[i], *order[i]);
       max_scratch = bb > max_scratch ? bb : max_scratch;
-      w.saved[i] = cv.take<char>(mab_saved_bytes_any(*order[i]));
+      w.saved[i] = cv.take<char>(mab_saved_bytes(path[i], *order[i]));
     }
   }
   for (int li = 0; li < 2; ++li) {
@@ -242,7 +245,7 @@ inline size_t carve(const pca_st_config& c, const StepPlan& pl, Ws* out, void* b
   w.scratch = cv.take<char>(max_scratch);
   for (int li = 0; li < 2; ++li)
     w.scratch_bw[li] = pl.training ? (void*)cv.take<char>(max_scratch) : w.scratch;
-  w.scratch_pma = pl.pma256 ? (void*)cv.take<char>(mab_bwd_ws_bytes_any(pl.pma)) : w.scratch;
+  w.scratch_pma = pl.pma256 ? (void*)cv.take<char>(mab_bwd_ws_bytes(pl.path_pma, pl.pma)) : w.scratch;
   if ((pl.isab128[0] || pl.isab128[1]) && wgrad_slabs_on()) {
     // two lists (B*N-row and B*m-row jobs) of up to ~600 [128 x 128 (+128)] fp32 slabs each;
     // bwd_defer_flush gives a workgroup more rows when a list would not fit
@@ -259,7 +262,7 @@ inline size_t carve(const pca_st_config& c, const StepPlan& pl, Ws* out, void* b
   w.scratch_fq[1] = pl.isab256[1] ? w.scratch : w.scratch_bw[1];
   if (pl.isab256[0]) {
     w.wg256_def = cv.take<char>(wgrad256_ws_bytes(8, (int64_t)c.B * c.m));
-    void* own = cv.take<char>(mab_bwd_ws_bytes_any(pl.m0[0]));
+    void* own = cv.take<char>(mab_bwd_ws_bytes(pl.path_m0[0], pl.m0[0]));
     if (pl.defer_wg) w.scratch_fq[0] = own;
   }
   if (out) *out = w;
@@ -438,10 +441,10 @@ int forward(const pca_st_config& c, const Layout& L, const StepPlan& pl, const f
     const pca_mab_params p1 = params_at(p, L.mab1[li]);
     ctx->mid_done = false;
     if (pl.isab256[li]) { ctx->s1 = pl.m1[li]; ctx->p1 = p1; ctx->saved1 = sv1; }
-    PCA_TRY(mab_fwd_any(pl.m0[li], p + L.I[li], in, params_at(p, L.mab0[li]), w.H[li], sv0, w.scratch,
+    PCA_TRY(mab_fwd(pl.path_m0[li], pl.m0[li], p + L.I[li], in, params_at(p, L.mab0[li]), w.H[li], sv0, w.scratch,
                         st, prep_flag, ctx));                       // modules.py:52
     ctx->saved1 = nullptr;
-    PCA_TRY(mab_fwd_any(pl.m1[li], in, w.H[li], p1, w.Y[li], sv1, w.scratch, st,
+    PCA_TRY(mab_fwd(pl.path_m1[li], pl.m1[li], in, w.H[li], p1, w.Y[li], sv1, w.scratch, st,
                         ctx->mid_done ? PCA_F_KV_READY : 0, ctx));  // modules.py:53
     in = w.Y[li];
   }
@@ -451,7 +454,7 @@ int forward(const pca_st_config& c, const Layout& L, const StepPlan& pl, const f
                              w.scratch, PCA_F_PREP_DONE | (c.k == 1 ? PCA_F_SKIP_EPILOGUE : 0),
                              st));
   else
-    PCA_TRY(mab_fwd_any(pl.pma, p + L.S, w.Y[1], params_at(p, L.pma), w.P,
+    PCA_TRY(mab_fwd(pl.path_pma, pl.pma, p + L.S, w.Y[1], params_at(p, L.pma), w.P,
                         pl.training ? w.saved[4] : nullptr, w.scratch, st, prep_flag, ctx));
   if (!pl.training)
     PCA_TRY(linear_fwd_f32(w.P, p + L.wc, p + L.bc, w.logits, (int64_t)c.B * c.k, c.d, c.C,
@@ -477,9 +480,9 @@ int isab_bwd(int li, const Layout& L, const StepPlan& pl, const float* p, float*
                          w.saved[2 * li + 1], dY, g + L.I[li], dX, g0, g1, w.scratch_bw[li], w.img[li], st,
                          posts);
   ctx->armed = pl.armed[li];
-  PCA_TRY(mab_bwd_any(pl.m1[li], X, w.H[li], p1, w.saved[2 * li + 1], dY, dX, w.dH, 0, g1, w.scratch_bw[li],
+  PCA_TRY(mab_bwd(pl.path_m1[li], pl.m1[li], X, w.H[li], p1, w.saved[2 * li + 1], dY, dX, w.dH, 0, g1, w.scratch_bw[li],
                       st, deferring(ctx, posts, pl.defer_wg)));
-  PCA_TRY(mab_bwd_any(pl.m0[li], p + L.I[li], X, p0, w.saved[2 * li], w.dH, g + L.I[li], dX, dX != nullptr,
+  PCA_TRY(mab_bwd(pl.path_m0[li], pl.m0[li], p + L.I[li], X, p0, w.saved[2 * li], w.dH, g + L.I[li], dX, dX != nullptr,
                       g0, w.scratch_fq[li], st, deferring(ctx, posts, pl.fq_defer[li])));
   ctx->armed = false;
   return wgrad256_handoff_flush(ctx, w.scratch, st);   // (what nobody took runs on its own; not armed: nothing)
@@ -544,7 +547,7 @@ int st_train_fwd_bwd(const pca_st_config* c, const float* p, const float* X, con
       // dec.1 (Linear) + mean cross-entropy, forward and backward
       PCA_TRY(cls_train_head(w.P, p + L.wc, p + L.bc, labels, c->B, c->d, c->C, grad_scale, w.logits,
                              w.dlogits, w.dP, g + L.wc, g + L.bc, loss_out, stats, w.clsws, st, &posts));
-      PCA_TRY(mab_bwd_any(pl.pma, p + L.S, w.Y[1], params_at(p, L.pma), w.saved[4], w.dP, g + L.S, w.dY2,
+      PCA_TRY(mab_bwd(pl.path_pma, pl.pma, p + L.S, w.Y[1], params_at(p, L.pma), w.saved[4], w.dP, g + L.S, w.dY2,
                           0, grads_at(g, L.pma), w.scratch_pma, st, deferring(&ctx, &posts, pl.pma256)));
     }
     PCA_TRY(isab_bwd(1, L, pl, p, g, w.Y[0], w.dY2, w.dY1, w, &posts, &ctx, st));

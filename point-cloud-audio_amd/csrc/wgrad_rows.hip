@@ -1,5 +1,5 @@
 // Weight and bias gradients of a Linear over a tall activation, deterministic (the self-attention blocks of
-// kind 4, api_mab.hip):
+// BlockPath::ExactCore, api_mab.hip):
 //
 //     dW[dout][din] += dY[M][dout]^T X[M][din]      db[dout] += colsum(dY)          (nn.Linear's adjoint)
 //
