@@ -247,6 +247,16 @@ int pca_importance_points(const float* spec, int64_t stride_f, int64_t stride_t,
                           const int32_t* draw_dev, float* out, int32_t* sel, float* heat,
                           const int64_t* labels, int64_t* labels_out, void* stream);
 
+/* The K points of largest key of packed point sets (the key comes from outside: e.g. pca_pma_attention's)
+ * replaces: nothing (the reference sub-samples by magnitude, at random or by its heat map only).
+ * X[B, N, din] packed sets, din in {2, 3}; key[B, N] fp32; 1 <= K <= N <= 16384.
+ * out[B, K, din] = the rows of the K largest keys in descending order, by pca_subsample_points mode 0's
+ * rule: equal keys (-0 == +0) in ascending point order, NaN last.  lengths (nullable, int32[B]): the points
+ * at and beyond lengths[b] come after every valid point, in index order.  sel (nullable) [B, K] int32
+ * receives the point indices.  One workgroup per set, the sort in LDS. */
+int pca_select_points(const float* X, const float* key, const int32_t* lengths, int B, int N,
+                      int din, int K, float* out, int32_t* sel, void* stream);
+
 /* 2-D point sets from per-frame tables (the output of pc_maxK / pc_randK)
  * replaces: Code/dataset.py:76-80  ESC_pc_ss.__getitem__ (+ default_collate)
  * x_tk[T, K] values and f_tk[T, K] coordinates, frame-major; out[B, K, 2] =
@@ -361,6 +371,30 @@ int pca_mab_bwd(const pca_mab_shape* s, const void* Q, const void* K,
                 const pca_mab_params* p, const void* saved, const void* dY,
                 void* dQ, void* dK, int dk_accumulate, const pca_mab_grads* g,
                 void* ws, void* stream);
+
+/* The pooling attention of a PMA block, returned instead of dropped
+ * replaces: nothing the reference returns.  It is the `A` of set_transformer-master/modules.py:21-27 as
+ *           PMA (modules.py:55-63) reaches it: Q = fc_q(S), K = fc_k(X), head j = features
+ *           [j d/h, (j+1) d/h), A = softmax(Q_j K_j^T / sqrt(d)) over the keys - the weights of the N points
+ *           of a set in front of the classifier.  MAB.forward drops it; so do the fused kernels here.
+ * Shape: q_shared = 1, nq = k seeds, nk = N, dq = dk = d <= 256, d % h == 0, k_dtype = PCA_F32, ln = 0; any
+ *   N >= 1, any k >= 1.  `mode` is accepted and ignored: the arithmetic is fp32 in every mode (the
+ *   parameter-only projections sum in fp64 and are rounded once).  Anything else: PCA_EINVAL.
+ * S[k, d] the seeds, X[B, N, d] fp32, p: fc_q and fc_k are read (wq, bq, wk, bk), the rest is ignored.
+ * attn[B, k, h, N] fp32 (required).  The reference's own order is head-major along the batch, [h B, k, N]
+ *   (torch.cat of the head split along dim 0): reference row (j B + b, s) is attn[b, s, j, :].
+ * key[B, N] fp32 (nullable): the mean of attn over seeds and heads - the fp32 sum over rows r = s h + j in
+ *   ascending r, divided by k h - what pca_select_points sorts by.
+ * s->k_lengths: keys at and beyond k_lengths[b] take no part; their attn and key entries are written as exact
+ *   zeros and the valid prefix equals the result on the truncated set; padding rows of X are not read.
+ * The projected keys are never built: score[b, s, j, n] = X[b, n, :] . u_{s,j} + c_{s,j} with u = Wk_j^T q_j /
+ *   sqrt(d) and c = q_j . bk_j / sqrt(d).  X is read once for all heads and seeds; rows of any
+ *   length (raw scores to attn, per-tile maxima and sums, a normalising pass).  No atomics, one owner per
+ *   output element, fixed-order sums: the same call gives the same bits, eagerly and under graph replay.
+ * ws: pca_pma_attention_ws_bytes(s) bytes (0 for a shape the call would refuse).  Enqueues only. */
+size_t pca_pma_attention_ws_bytes(const pca_mab_shape* s);
+int pca_pma_attention(const pca_mab_shape* s, const float* S, const float* X,
+                      const pca_mab_params* p, float* attn, float* key, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Classifier head, loss and optimiser                                        *
@@ -504,6 +538,17 @@ int pca_st_handoff_counter(const pca_st_config* c, void* ws, uint32_t** counter)
  * set b then equal those of its first lengths[b] points alone (see pca_mab_shape). */
 int pca_st_forward(const pca_st_config* c, const float* params, const float* X,
                    const int32_t* lengths, float* logits, void* ws, void* stream);
+
+/* Logits and the pooling attention of the whole model in one call (no reference counterpart).
+ * Runs the inference forward exactly as pca_st_forward does - the same plan, the same launches: logits are
+ * bit-identical - and then pca_pma_attention's kernels on the second ISAB's output (fp32 [B, N, d], which
+ * every inference path leaves complete in the workspace) with dec.0's seeds and parameters.
+ * attn[B, k, h, N] and key[B, N]: as pca_pma_attention, with k_lengths = lengths; each nullable.
+ * ws: pca_st_pool_attention_ws_bytes(c) = pca_st_ws_bytes(c, 0) + the attention scratch.  Enqueues only. */
+size_t pca_st_pool_attention_ws_bytes(const pca_st_config* c);
+int pca_st_pool_attention(const pca_st_config* c, const float* params, const float* X,
+                          const int32_t* lengths, float* logits, float* attn, float* key,
+                          void* ws, void* stream);
 
 /* phase 0: forward, mean cross-entropy (loss_out[0]; stats += {sum loss, #correct}),
  *          backward through dec and enc.1 ; phase 1: backward through enc.0.

@@ -125,5 +125,9 @@ int relu_bwd_copy(const float* dY, const float* Z, float* dZ, float* dO, int64_t
 int copy_rows(const float* src, int64_t src_rows, float* dst, int64_t rows, int64_t cols,
               hipStream_t st);
 int fill_zero(float* dst, int64_t n, hipStream_t st);
+// the pooling attention of a q_shared block (pool_attn.hip; contracts: pca_pma_attention in pca_hip.h)
+size_t pma_attention_ws_bytes(const pca_mab_shape& s);
+int pma_attention(const pca_mab_shape& s, const float* S, const float* X, const pca_mab_params& p,
+                  float* attn, float* key, void* ws, hipStream_t st);
 
 }  // namespace pca

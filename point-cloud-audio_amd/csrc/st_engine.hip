@@ -500,6 +500,51 @@ int st_forward(const pca_st_config* c, const float* params, const float* X, cons
   return forward(*c, layout(*c), pl, params, X, w, as_stream(stream), &ctx);
 }
 
+// The attention scratch behind the inference workspace: pma_attention's own block and a home for the scores
+// when the caller wants the key alone.
+struct AttnWs {
+  void* pa;
+  float* attn;
+};
+inline size_t carve_attn(const pca_st_config& c, const StepPlan& pl, AttnWs* out, void* base) {
+  Carver cv(base);
+  AttnWs a{};
+  a.pa = cv.take<char>(pma_attention_ws_bytes(pl.pma));
+  a.attn = cv.take<float>((size_t)c.B * c.k * c.h * c.N);
+  if (out) *out = a;
+  return cv.off;
+}
+int attn_config_ok(const pca_st_config* c) {
+  PCA_REQUIRE(c->d <= 256, "st_pool_attention: d=%d (max 256)", c->d);
+  return PCA_OK;
+}
+
+int st_pool_attention(const pca_st_config* c, const float* params, const float* X, const int32_t* lengths,
+                      float* logits, float* attn, float* key, void* ws, void* stream) {
+  PCA_TRY(validate(c));
+  PCA_TRY(attn_config_ok(c));
+  PCA_REQUIRE(params && X && logits && ws, "st_pool_attention: null pointer");
+  const StepPlan pl = plan(*c, false, lengths);
+  // Y2 = w.Y[1] must be the complete fp32 [B, N, d] output of enc.1: an inference plan keeps every
+  // activation in fp32 (act_bf16 and the set-resident launch belong to training plans) and each path of the
+  // many-queries block (Mab1_128 / Mab1_256 / Sd64 / Exact) writes all B N rows of its Y.
+  if (pl.act_bf16 || pl.set128 || pl.m1[1].y_dtype != PCA_F32 || pl.pma.k_dtype != PCA_F32) {
+    set_error("st_pool_attention: this configuration's forward does not leave enc.1's output in fp32");
+    return PCA_EUNSUPPORTED;
+  }
+  Ws w;
+  const size_t fwd_bytes = carve(*c, pl, &w, ws);
+  w.logits = logits;
+  StepCtx ctx{};
+  const Layout L = layout(*c);
+  PCA_TRY(forward(*c, L, pl, params, X, w, as_stream(stream), &ctx));
+  if (attn == nullptr && key == nullptr) return PCA_OK;
+  AttnWs a;
+  carve_attn(*c, pl, &a, static_cast<char*>(ws) + fwd_bytes);
+  return pma_attention(pl.pma, params + L.S, w.Y[1], params_at(params, L.pma), attn != nullptr ? attn : a.attn,
+                       key, a.pa, as_stream(stream));
+}
+
 int st_train_fwd_bwd(const pca_st_config* c, const float* p, const float* X, const int32_t* lengths,
                      const int64_t* labels, float* g, float* loss_out, float* stats, float* logits,
                      float grad_scale, int phase, void* ws, void* stream) {
@@ -606,6 +651,20 @@ int pca_st_forward(const pca_st_config* c, const float* params, const float* X,
   PCA_TRY(pca::no_stale_pack("pca_st_forward", true));
   const int rc = pca::st_forward(c, params, X, lengths, logits, ws, stream);
   return rc != PCA_OK ? rc : pca::no_stale_pack("pca_st_forward (exit)", false);
+}
+
+size_t pca_st_pool_attention_ws_bytes(const pca_st_config* c) {
+  if (pca::validate(c) != PCA_OK || pca::attn_config_ok(c) != PCA_OK) return 0;
+  const pca::StepPlan pl = pca::plan(*c, false, nullptr);
+  return pca::carve(*c, pl, nullptr, nullptr) + pca::carve_attn(*c, pl, nullptr, nullptr);
+}
+
+int pca_st_pool_attention(const pca_st_config* c, const float* params, const float* X,
+                          const int32_t* lengths, float* logits, float* attn, float* key,
+                          void* ws, void* stream) {
+  PCA_TRY(pca::no_stale_pack("pca_st_pool_attention", true));
+  const int rc = pca::st_pool_attention(c, params, X, lengths, logits, attn, key, ws, stream);
+  return rc != PCA_OK ? rc : pca::no_stale_pack("pca_st_pool_attention (exit)", false);
 }
 
 int pca_st_train_fwd_bwd(const pca_st_config* c, const float* params, const float* X,

@@ -15,6 +15,7 @@
 // HBM traffic: N values read + K rows written per set; the sort itself never leaves LDS.
 #include "pca_common.h"
 #include "select_keys.hpp"
+#include "lds_sort.hpp"
 
 #include <stdint.h>
 
@@ -55,22 +56,7 @@ __global__ __launch_bounds__(1024) void k_subsample(
     keys[p] = k;
   }
   __syncthreads();
-  // bitonic network, ascending; every pair (i, i | j) is touched by exactly one thread
-  for (int k = 2; k <= Np; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < (Np >> 1); t += 1024) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        const int l = i | j;
-        const uint64_t a = keys[i], c = keys[l];
-        const bool up = (i & k) == 0;
-        if ((a > c) == up) {
-          keys[i] = c;
-          keys[l] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  lds_sort_asc_1024(keys, Np, tid);
   const int din = tarr != nullptr ? 3 : 2;
   for (int q = tid; q < K; q += 1024) {
     const int p = (int)(uint32_t)keys[q];
@@ -161,21 +147,7 @@ __global__ __launch_bounds__(1024) void k_importance(
       if (i < Np) lds64[i] = i < N ? (((uint64_t)hk[u] << 32) | (uint32_t)i) : ~0ull;
     }
     __syncthreads();
-    for (int k = 2; k <= Np; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int t = tid; t < (Np >> 1); t += 1024) {
-          const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-          const int l = i | j;
-          const uint64_t a = lds64[i], c = lds64[l];
-          const bool up = (i & k) == 0;
-          if ((a > c) == up) {
-            lds64[i] = c;
-            lds64[l] = a;
-          }
-        }
-        __syncthreads();
-      }
-    }
+    lds_sort_asc_1024(lds64, Np, tid);
   } else {
     // inclusive CDF of the heat map in place: per-thread chunks, then a scan of the 1024 sums
     __shared__ double part[1024];
@@ -219,6 +191,34 @@ __global__ __launch_bounds__(1024) void k_importance(
     o[1] = tarr[tq];
     o[2] = base[fq * stride_f + tq * stride_t];
     if (sel != nullptr) sel[(int64_t)b * K + q] = i;
+  }
+}
+
+// Top-K points of packed sets by an EXTERNAL key (no reference counterpart: the key is e.g. the pooling
+// attention of pca_pma_attention).  max-K's order - desc_key, equal keys in ascending point order, NaN last -
+// with the points at and beyond lengths[b] behind every valid one, in index order (they take NaN's key: a
+// valid NaN has the lower index).  HBM traffic: N keys read, K rows gathered and written per set.
+__global__ __launch_bounds__(1024) void k_select(
+    const float* __restrict__ X, const float* __restrict__ key, const int32_t* __restrict__ lengths,
+    int N, int din, int K, int Np, float* __restrict__ out, int32_t* __restrict__ sel) {
+  extern __shared__ uint64_t keys[];                 // Np = power of two >= N
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int len = lengths != nullptr ? lengths[b] : N;
+  len = len < 0 ? 0 : (len > N ? N : len);
+  const float* __restrict__ kb = key + (int64_t)b * N;
+  for (int p = tid; p < Np; p += 1024) {
+    uint64_t k = ~0ull;
+    if (p < N) k = ((uint64_t)(p < len ? desc_key(kb[p]) : 0xffffffffu) << 32) | (uint32_t)p;
+    keys[p] = k;
+  }
+  __syncthreads();
+  lds_sort_asc_1024(keys, Np, tid);
+  const float* __restrict__ xb = X + (int64_t)b * N * din;
+  for (int q = tid; q < K; q += 1024) {
+    const int p = (int)(uint32_t)keys[q];            // (K <= N: never a filler entry)
+    float* o = out + ((int64_t)b * K + q) * din;
+    for (int c = 0; c < din; ++c) o[c] = xb[(int64_t)p * din + c];
+    if (sel != nullptr) sel[(int64_t)b * K + q] = p;
   }
 }
 
@@ -271,6 +271,25 @@ int pca_subsample_points(const float* spec, int64_t stride_f, int64_t stride_t,
                      stride_t, stride_s, farr, tarr, idx, F, Nt, K, mode, seed, draw, draw_dev,
                      Np, out, sel, labels, labels_out);
   return pca::check_launch("k_subsample");
+}
+
+int pca_select_points(const float* X, const float* key, const int32_t* lengths, int B, int N,
+                      int din, int K, float* out, int32_t* sel, void* stream) {
+  PCA_REQUIRE(X && key && out, "select_points: null pointer");
+  PCA_REQUIRE(B > 0 && N > 0, "select_points: B=%d N=%d", B, N);
+  PCA_REQUIRE(din == 2 || din == 3, "select_points: din=%d (2 or 3)", din);
+  PCA_REQUIRE(N <= 16384, "select_points: %d points per set (max 16384)", N);
+  PCA_REQUIRE(K > 0 && K <= N, "select_points: K=%d outside [1, %d]", K, N);
+  int Np = 2;
+  while (Np < N) Np <<= 1;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pca::k_select),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+  });
+  hipLaunchKernelGGL(pca::k_select, dim3((unsigned)B), dim3(1024), (size_t)Np * sizeof(uint64_t),
+                     pca::as_stream(stream), X, key, lengths, N, din, K, Np, out, sel);
+  return pca::check_launch("k_select");
 }
 
 int pca_importance_points(const float* spec, int64_t stride_f, int64_t stride_t,

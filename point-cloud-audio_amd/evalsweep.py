@@ -27,6 +27,9 @@ The other set-model experiments run here at batch scale too:
 * ``subsample_sweep``: max-K / random-K sub-sampling, Code/pceval.py:107-192 (FST, per-frame point
   sets) and Code/pc_temp3d_eval.py:109-201 (3ST, per-chunk point sets);
 * ``importance_sweep``: importance-sampled sets, Code/rebut_expts.py:55-149;
+* ``attention_sweep``: sets reduced to the K points the model's own pooling attention weighs most
+  (``STEngine.attention``, ``pca_hip.select_points``); no reference counterpart - a third curve beside
+  random-K and max-K;
 * ``reframe_sweep_temporal``: the (Fs, N) re-framing of the 3ST, Code/pc_temp3d_eval.py:56-107.
 * ``clip_accuracy``: the clip-level scores the datasets' literature reports (majority vote and mean
   log-probability over a clip's frames or chunks, ``pca_hip.clip_aggregate``) next to the frame score;
@@ -58,7 +61,7 @@ from pca_hip.baseline import SEL_ALL, BaselineEngine
 from pca_hip.trainer import STEngine, st_config
 
 __all__ = ["reframe_sweep", "framewise_dataset", "default_list_K", "sweep_draw", "subsample_sweep",
-           "importance_sweep", "chunk_plan", "temporal_axes", "temporal_dataset",
+           "importance_sweep", "attention_sweep", "chunk_plan", "temporal_axes", "temporal_dataset",
            "reframe_sweep_temporal", "baseline_subsample_sweep", "baseline_frames",
            "baseline_chunks", "baseline_reframe_sweep", "baseline_reframe_sweep_temporal",
            "trim_dB_of", "trim_clips", "clip_accuracy"]
@@ -405,6 +408,93 @@ def importance_sweep(model, spec, labels, farr, tarr, list_K: Optional[Iterable[
         _write_json(out_r, json_files[0])
         _write_json(out_m, json_files[1])
     return out_r, out_m
+
+
+def _pack_sets(x, f32, t32, pos, out):
+    """The full point sets of the positions ``pos`` into ``out`` [n, N, din], as the datasets pack them:
+    (farr[f], x) for FST frames, point p = t * F + f -> (farr[f], tarr[t], x) for 3ST chunks."""
+    if t32 is None:
+        pca_hip.pack_points_2d(x, f32, pos, out=out)
+    else:
+        pca_hip.pack_points_3d(x, f32, t32, pos, out=out)
+
+
+@torch.no_grad()
+def attention_sweep(model, spec, labels, farr, tarr=None, list_K: Optional[Iterable[int]] = None,
+                    batch_size: int = 8, mode: int = _lib.MODE_F32, json_file: Optional[str] = None,
+                    sets_per_call: Optional[int] = None):
+    """Accuracy of ``model`` on point sets reduced to the K points its own pooling attention weighs most,
+    for every K in ``list_K``.  **No reference counterpart**: the reference sub-samples by magnitude, at
+    random (Code/pceval.py:107-192, Code/pc_temp3d_eval.py:109-201) or by a heat map of the input
+    (Code/rebut_expts.py); this is the same experiment with the selection read off the trained model.
+
+    Arguments and defaults as subsample_sweep: FST ``spec`` [F, T] frames with ``tarr`` None, 3ST ``spec``
+    [F, Nt, S] chunks with ``tarr`` [Nt]; default list_K default_list_K(F - 1) / default_list_K(F * Nt).
+
+    Pass 1 runs ``STEngine.attention`` over the sets that count (the first (n // batch_size) * batch_size)
+    once, at full size, and keeps ``key`` - the mean of the pooling attention over seeds and heads,
+    [n_sets, N] float32 - on the device.  Then, for every K, the sets are packed again piece by piece,
+    reduced by ``pca_hip.select_points`` to the K points of largest key (descending; equal keys in
+    ascending point order), evaluated by ``STEngine.forward`` at N = K and tallied by pca_eval_tally; one
+    host read per K.  Engine calls hold up to ``sets_per_call`` sets (default: SETS_PER_CALL halved until
+    the workspace fits WS_BUDGET, for the full-size pass and for every K).  The key is fp32 in every
+    ``mode``; ``mode`` is the arithmetic of the forwards.
+
+    Returns (and, with ``json_file``, writes) ``{"data": {K: [acc, 0]}, "list_K": [...]}``, the shape of the
+    reference's max-K dictionary (paper_plots/FST_maxK_expt2.json), so the paper's plotting code can put
+    the curve beside it."""
+    dev = _model_device(model)
+    x, lab, f32, t32 = _resident_sets(spec, labels, farr, tarr, dev)
+    if tarr is None:
+        F, n_sets = x.shape
+        npts_all, din, default_n = F, 2, F - 1
+    else:
+        F, Nt, n_sets = x.shape
+        npts_all, din, default_n = F * Nt, 3, F * Nt
+    list_K = default_list_K(default_n) if list_K is None else [int(k) for k in list_K]
+    assert all(1 <= k <= npts_all for k in list_K), (list_K, npts_all)
+    full = (n_sets // batch_size) * batch_size
+    data = {}
+    if full == 0:
+        data = {K: [float("nan"), 0] for K in list_K}
+    else:
+        # pass 1: the key of every set, resident
+        key = torch.empty((full, npts_all), dtype=torch.float32, device=dev)
+        cap = _sets_per_call(model, npts_all, mode, sets_per_call)
+        engines = {}
+        for p0 in range(0, full, cap):
+            b = min(cap, full - p0)
+            if b not in engines:
+                eng = STEngine(model, b, npts_all, mode, training=False)
+                assert eng.cfg.k == 1, "sweeps score one prediction per set (PMA with one seed)"
+                engines[b] = (eng, torch.empty((b, npts_all, din), dtype=torch.float32, device=dev))
+            eng, X = engines[b]
+            _pack_sets(x, f32, t32, torch.arange(p0, p0 + b, dtype=torch.int64, device=dev), X)
+            eng.attention(X, want_attn=False, key_out=key[p0:p0 + b])
+        del engines
+        full_buf = {}
+
+        def select_of_K(K):
+            def select(slot, draw, pos, out, labels_out):
+                n = pos.numel()
+                if n not in full_buf:          # the full-size sets of a piece and the indices kept
+                    full_buf[n] = (torch.empty((n, npts_all, din), dtype=torch.float32, device=dev),
+                                   torch.empty((n, K), dtype=torch.int32, device=dev))
+                Xf, sel = full_buf[n]
+                _pack_sets(x, f32, t32, pos, Xf)
+                pca_hip.select_points(Xf, key.index_select(0, pos), K, out=out, sel=sel)
+                torch.index_select(lab, 0, pos, out=labels_out)
+            return select
+
+        for K in list_K:
+            counts = torch.zeros(1, dtype=torch.int64, device=dev)
+            full_buf.clear()
+            _run_pieces(model, K, din, mode, _sets_per_call(model, K, mode, sets_per_call),
+                        [(0, 0, 0, full)], select_of_K(K), counts)
+            data[K] = [int(counts.item()) / full, 0]           # the one host read of this K
+    out = {"data": data, "list_K": list_K}
+    _write_json(out, json_file)
+    return out
 
 
 def chunk_plan(frames: Sequence[int], Ntemp: int):

@@ -62,6 +62,17 @@ class ST(nn.Module):
             X = isab(X, lengths)
         return self.dec[1](self.dec[0](X, lengths)).squeeze()
 
+    @torch.no_grad()
+    def attention(self, X, lengths=None):
+        """(logits, attn): ``forward``'s logits and the pooling attention [B, num_outputs, num_heads, N]
+        of ``dec[0]`` (PMA.attention) on the same encoder output - which of the N points the classifier
+        listened to.  The module route: enc, then PMA.attention, then dec; ``STEngine.attention`` is the
+        one-call form.  Not differentiable (runs under torch.no_grad())."""
+        for isab in self.enc:
+            X = isab(X, lengths)
+        attn = self.dec[0].attention(X, lengths)
+        return self.dec[1](self.dec[0](X, lengths)).squeeze(), attn
+
 
 def _mlp(dims, head_name, nclasses):
     """Linear + LeakyReLU stack ``dims[0] -> ... -> dims[-1]`` followed by a Linear named

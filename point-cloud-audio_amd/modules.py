@@ -107,3 +107,12 @@ class PMA(nn.Module):
 
     def forward(self, X, lengths=None):
         return self.mab(self.S, X, q_shared=True, key_lengths=lengths)
+
+    @torch.no_grad()
+    def attention(self, X, lengths=None):
+        """The softmax this block pools with (modules.py:28), which ``forward`` never returns:
+        [B, num_seeds, num_heads, N] float32, head j over the features [j d/h, (j+1) d/h); the
+        reference's own order [h * B, k, N] has row (j * B + b, s) = result[b, s, j].  ``lengths``
+        int[B]: points at and beyond lengths[b] take no part and are exact zeros.  fp32 in every mode.
+        Not differentiable (runs under torch.no_grad(); no LayerNorm is involved: it sits behind A)."""
+        return pca_hip.pma_attention(self.S, X, self.mab._params(), self.mab.num_heads, lengths)

@@ -91,6 +91,11 @@ SIGNATURES = {
                               c_vp, c_vp, c_vp]),
     "pca_mab_bwd": (C.c_int, [C.POINTER(MabShape), c_vp, c_vp, C.POINTER(MabParams), c_vp,
                               c_vp, c_vp, c_vp, C.c_int, C.POINTER(MabGrads), c_vp, c_vp]),
+    "pca_pma_attention_ws_bytes": (C.c_size_t, [C.POINTER(MabShape)]),
+    "pca_pma_attention": (C.c_int, [C.POINTER(MabShape), c_fp, c_fp, C.POINTER(MabParams), c_fp, c_fp,
+                                    c_vp, c_vp]),
+    "pca_select_points": (C.c_int, [c_fp, c_fp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_vp,
+                                    c_vp]),
     "pca_linear_fwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int64, C.c_int, C.c_int, c_vp]),
     "pca_linear_bwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_int64, C.c_int,
                                  C.c_int, c_vp, c_vp]),
@@ -130,6 +135,9 @@ SIGNATURES = {
     "pca_st_ws_layout": (C.c_int, [C.POINTER(StConfig), C.c_void_p]),
     "pca_st_handoff_counter": (C.c_int, [C.POINTER(StConfig), C.c_void_p, C.POINTER(C.c_void_p)]),
     "pca_st_forward": (C.c_int, [C.POINTER(StConfig), c_fp, c_fp, c_vp, c_fp, c_vp, c_vp]),
+    "pca_st_pool_attention_ws_bytes": (C.c_size_t, [C.POINTER(StConfig)]),
+    "pca_st_pool_attention": (C.c_int, [C.POINTER(StConfig), c_fp, c_fp, c_vp, c_fp, c_fp, c_fp, c_vp,
+                                        c_vp]),
     "pca_st_train_fwd_bwd": (C.c_int, [C.POINTER(StConfig), c_fp, c_fp, c_vp, c_i64p, c_fp,
                                        c_fp, c_fp, c_fp, C.c_float, C.c_int, c_vp, c_vp]),
     "pca_prof_start": (C.c_int, [C.c_int, C.c_int]),

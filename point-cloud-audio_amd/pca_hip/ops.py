@@ -251,6 +251,42 @@ def mab_infer(Q, K, params, num_heads: int, q_shared: bool = False,
     return Y
 
 
+def pma_attention(S, X, params, num_heads: int, key_lengths=None, want_key: bool = False):
+    """The pooling attention of a PMA block (pca_pma_attention): the `A` of
+    set_transformer-master/modules.py:21-27 that MAB.forward builds and drops.
+    S [k, d] or [1, k, d] the seeds, X [B, N, d] float32, ``params`` = (fc_q.weight, fc_q.bias, fc_k.weight,
+    fc_k.bias[, ...]): only the first four are read.  Returns attn [B, k, h, N] float32 - the reference's
+    own [h * B, k, N] row (j * B + b, s) is attn[b, s, j, :] - and, with ``want_key``, (attn, key): key
+    [B, N], the mean over seeds and heads that select_points sorts by.  ``key_lengths`` int[B]: keys at and
+    beyond it take no part and come out as exact zeros.  fp32 whatever the mode (set_mode is not consulted).
+    Not differentiable: a diagnostic, computed outside autograd."""
+    _need_cuda(S, X)
+    S, X = _f32c(S.detach()), _f32c(X.detach())
+    params = [_f32c(p.detach()) for p in list(params)[:4]]
+    _need_cuda(*params)
+    if X.dim() != 3:
+        raise RuntimeError(f"pma_attention: X must be [B, N, d], got {tuple(X.shape)}")
+    B, N, d = X.shape
+    S = S.reshape(-1, S.shape[-1])
+    k = S.shape[0]
+    if S.shape[1] != d or tuple(params[0].shape) != (d, d) or tuple(params[2].shape) != (d, d):
+        raise RuntimeError("pma_attention: the widths of S, X, fc_q and fc_k do not match")
+    kl = _lengths(key_lengths, B, X)
+    s = _shape(B, k, N, d, d, d, num_heads, True, k_lengths=kl)
+    L = lib()
+    with torch.cuda.device(X.device):
+        n = L.pca_pma_attention_ws_bytes(C.byref(s))
+        if n == 0:
+            raise _lib.PcaHipError("pca_pma_attention_ws_bytes: " + L.pca_last_error().decode())
+        ws = _bytes(n, X)
+        attn = torch.empty((B, k, num_heads, N), dtype=torch.float32, device=X.device)
+        key = torch.empty((B, N), dtype=torch.float32, device=X.device) if want_key else None
+        pp = MabParams(*([_ptr(p) for p in params] + [None] * 8))
+        check(L.pca_pma_attention(C.byref(s), _ptr(S), _ptr(X), C.byref(pp), _ptr(attn), _ptr(key),
+                                  _ptr(ws), _stream(X)), "pca_pma_attention")
+    return (attn, key) if want_key else attn
+
+
 class _LinearFn(torch.autograd.Function):
     """nn.Linear (Code/models.py:40) on the library's GEMM."""
 
@@ -694,6 +730,33 @@ def subsample_points(spec: torch.Tensor, farr: torch.Tensor, tarr: Optional[torc
                                          _ptr(labels), _ptr(labels_out), _stream(spec)),
               "pca_subsample_points")
     return (out, labels_out, sel) if want_sel else (out, labels_out)
+
+
+def select_points(X: torch.Tensor, key: torch.Tensor, K: int,
+                  lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                  sel: Optional[torch.Tensor] = None):
+    """The K points of largest ``key`` of every packed set (pca_select_points): X [B, N, din] float32, din
+    2 or 3, key [B, N] float32, 1 <= K <= N <= 16384.  Order: keys descending, equal keys in ascending
+    point order, NaN last (subsample_points' MAXK rule); with ``lengths`` (device int32[B]) the points at
+    and beyond lengths[b] come after every valid one.  Returns (out [B, K, din], sel int32 [B, K]); both
+    may be passed in (contiguous)."""
+    _need_cuda(X, key, lengths, out, sel)
+    assert X.dim() == 3 and X.dtype == torch.float32 and X.is_contiguous()
+    B, N, din = X.shape
+    assert key.dtype == torch.float32 and key.is_contiguous() and tuple(key.shape) == (B, N)
+    if lengths is not None:
+        assert lengths.dtype == torch.int32 and lengths.is_contiguous() and tuple(lengths.shape) == (B,)
+    K = int(K)
+    with torch.cuda.device(X.device):
+        if out is None:
+            out = torch.empty((B, K, din), dtype=torch.float32, device=X.device)
+        if sel is None:
+            sel = torch.empty((B, K), dtype=torch.int32, device=X.device)
+        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, K, din)
+        assert sel.dtype == torch.int32 and sel.is_contiguous() and tuple(sel.shape) == (B, K)
+        check(lib().pca_select_points(_ptr(X), _ptr(key), _ptr(lengths), B, N, din, K, _ptr(out),
+                                      _ptr(sel), _stream(X)), "pca_select_points")
+    return out, sel
 
 
 def pack_points_2d_ss(x_tk: torch.Tensor, f_tk: torch.Tensor, idx: torch.Tensor,

@@ -231,6 +231,42 @@ class STEngine:
               "pca_st_forward")
         return out
 
+    def attention(self, X: torch.Tensor, lengths: Optional[torch.Tensor] = None, want_key: bool = True,
+                  want_attn: bool = True, key_out: Optional[torch.Tensor] = None):
+        """(logits, attn, key) of one inference call (pca_st_pool_attention): the logits ``forward``
+        returns, bit for bit, the pooling attention attn [B, k, h, N] of dec.0 (modules.PMA.attention) and
+        key [B, N], its mean over seeds and heads (what pca_hip.select_points sorts by).  attn / key are
+        None without ``want_attn`` / ``want_key``.  The tensors are the engine's own buffers, overwritten
+        by the next call; ``key_out`` (device float32 [B, N], contiguous) receives the key instead.
+        fp32 whatever the engine's mode; not differentiable.  Needs an engine built with training=False."""
+        if self.training:
+            raise _lib.PcaHipError("STEngine.attention needs an engine built with training=False")
+        assert X.is_cuda and X.dtype == torch.float32 and X.is_contiguous()
+        cfg = self.cfg
+        assert tuple(X.shape) == (cfg.B, cfg.N, cfg.din), X.shape
+        L = lib()
+        with torch.cuda.device(self.dev):
+            if getattr(self, "_attn", None) is None:
+                n = L.pca_st_pool_attention_ws_bytes(C.byref(cfg))
+                if n == 0:
+                    raise _lib.PcaHipError("pca_st_pool_attention_ws_bytes: " + L.pca_last_error().decode())
+                # the inference workspace with the attention scratch behind it (nothing in it outlives a call)
+                self.ws = torch.empty(n, dtype=torch.uint8, device=self.dev)
+                self._attn = torch.empty((cfg.B, cfg.k, cfg.h, cfg.N), dtype=torch.float32, device=self.dev)
+                self._key = torch.empty((cfg.B, cfg.N), dtype=torch.float32, device=self.dev)
+        attn = self._attn if want_attn else None
+        key = None
+        if want_key:
+            key = self._key if key_out is None else key_out
+            assert key.is_cuda and key.dtype == torch.float32 and key.is_contiguous()
+            assert tuple(key.shape) == (cfg.B, cfg.N), key.shape
+        check(L.pca_st_pool_attention(C.byref(cfg), self.flat.data_ptr(), X.data_ptr(),
+                                      self._len_ptr(lengths, cfg.B), self.logits.data_ptr(),
+                                      None if attn is None else attn.data_ptr(),
+                                      None if key is None else key.data_ptr(),
+                                      self.ws.data_ptr(), self._stream()), "pca_st_pool_attention")
+        return self.logits, attn, key
+
     def fwd_bwd(self, X: torch.Tensor, labels: torch.Tensor, phase: int = -1,
                 grad_scale: float = 1.0, lengths: Optional[torch.Tensor] = None) -> None:
         check(lib().pca_st_train_fwd_bwd(C.byref(self.cfg), self.flat.data_ptr(), X.data_ptr(),
