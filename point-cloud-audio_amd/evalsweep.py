@@ -44,6 +44,20 @@ of the reference's 8-set batches - and of all the random draws of that K - into 
 correct predictions to device counters.  The host reads the counters once per K (or N), where the
 reference syncs after every batch (``.item()``).  As in the reference, sets are taken in order and
 only the first ``(n // batch_size) * batch_size`` count.
+
+How the sweeps are put together - a new experiment is one more caller of these, not one more copy:
+
+* ``_reframe_driver``: the (Fs, N) loop of the four re-framing sweeps - trim once, resample once per
+  rate, ``acc_of_N`` per N, the dictionary and its JSON; a sweep supplies ``acc_of_N`` only;
+* ``_run_pieces``: the engine pass of every set-model sweep, ``reframe_sweep`` included (call packing,
+  selection, forward, tally), on engines from ``_engine_cache`` (one ``STEngine`` and its buffers
+  per call size; also pass 1 of ``attention_sweep`` and ``clip_accuracy``); ``_dataset_accuracy`` is
+  one such pass over a dataset, NaN for an empty one; ``_baseline_run`` is the BaselineEngine
+  counterpart of ``_run_pieces``;
+* ``_k_passes`` / ``_two_pass_sweep``: the K loop of random runs plus one deterministic pass;
+* ``_set_contiguous`` (within ``_resident_sets``), ``_set_geometry``, ``_norm_list_K``,
+  ``_chunk_labels``, ``_two_dicts``: the set layout, its sizes, the K grid, the chunk labels and the
+  two-dictionary return that the set-model sweeps and the baselines share.
 """
 import json
 import math
@@ -97,6 +111,34 @@ def _pow2_fft(list_N) -> int:
     return max(1 << int(math.ceil(math.log2(n))) for n in list_N)
 
 
+def _write_json(out: Dict, path: Optional[str]) -> None:
+    if path is not None:
+        with open(path, "w") as f:
+            json.dump(out, f)
+
+
+def _reframe_driver(clips, labels, fs, list_N, list_Fs, trim_dB, trim_n_fft, json_file,
+                    acc_of_N) -> Dict:
+    """The (Fs, N) double loop of the re-framing sweeps (Code/pceval.py:61-104 and its counterparts):
+    trims every clip once, before any resampling, checked against ``trim_n_fft`` (None: the set
+    models' _pow2_fft(list_N)) at the ratios F / fs; resamples once per rate of ``list_Fs`` (None: the
+    clips as recorded, at ``fs``); ``acc_of_N(clips_at_rate, rate, N) -> float`` gives each entry.
+    Returns and writes ``{"data": {Fs: [acc per N]}, "list_Fs": [...], "list_N": [...]}``."""
+    list_N = [int(n) for n in list_N]
+    rates = None if list_Fs is None else list(list_Fs)
+    if trim_dB is not None:
+        clips = trim_clips(clips, trim_dB, _pow2_fft(list_N) if trim_n_fft is None else trim_n_fft,
+                           (1.0,) if rates is None else [F / fs for F in rates])
+    data = {}
+    for F in [fs] if rates is None else rates:
+        at_rate = clips if rates is None else \
+            [pca_hip.resample(x, fs, F, scale=True) for x in clips]      # pceval.py:74
+        data[F] = [acc_of_N(at_rate, F, N) for N in list_N]
+    out = {"data": data, "list_Fs": [fs] if rates is None else rates, "list_N": list_N}
+    _write_json(out, json_file)
+    return out
+
+
 def framewise_dataset(clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float, N: int,
                       hf: float = 0.5) -> ESC_pc:
     """ESC_pc over all frames of ``clips`` analysed with window length N
@@ -126,49 +168,15 @@ def reframe_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], f
     ``Code/pceval.py:61-98`` does; returns (and optionally writes) the dictionary
     ``Code/pceval.py:57-59,99-104`` stores: ``{"data": {Fs: [acc per N]}, "list_Fs": [...],
     "list_N": [...]}``.  ``trim_dB``: trim every clip first (trim_clips; Code/pceval.py:74 trims, then
-    resamples); None: the clips as given."""
-    list_N = [int(n) for n in list_N]
-    if list_Fs is not None:
-        list_Fs = list(list_Fs)
-    if trim_dB is not None:
-        clips = trim_clips(clips, trim_dB, _pow2_fft(list_N),
-                           (1.0,) if list_Fs is None else [F / fs for F in list_Fs])
-    if list_Fs is not None:
-        data = {}
-        for F in list_Fs:
-            rs = [pca_hip.resample(x, fs, F, scale=True) for x in clips]     # pceval.py:74
-            data[F] = reframe_sweep(model, rs, labels, F, list_N, hf, batch_size, mode)["data"][F]
-        out = {"data": data, "list_Fs": list_Fs, "list_N": list_N}
-        if json_file is not None:
-            with open(json_file, "w") as f:
-                json.dump(out, f)
-        return out
-    accs: List[float] = []
-    for N in list_N:
-        ds = framewise_dataset(clips, labels, fs, N, hf)
-        n = len(ds)
-        full = (n // batch_size) * batch_size          # pceval.py:88-89 skips the short batch
-        if full == 0:
-            accs.append(float("nan"))
-            continue
-        # one engine launch covers many of the reference's 8-set batches
-        chunk = batch_size * max(1, 256 // batch_size)
-        dev = ds._resident()[0].device
-        correct, done = 0, 0
-        eng, eng_b = None, 0
-        while done < full:
-            b = min(chunk, full - done)
-            if b != eng_b:
-                eng, eng_b = STEngine(model, b, ds.num_points, mode, training=False), b
-            X, lab = ds.batch(torch.arange(done, done + b, device=dev))
-            correct += int((eng.forward(X).argmax(1) == lab).sum())
-            done += b
-        accs.append(correct / full)
-    out = {"data": {fs: accs}, "list_Fs": [fs], "list_N": list_N}
-    if json_file is not None:
-        with open(json_file, "w") as f:
-            json.dump(out, f)
-    return out
+    resamples); None: the clips as given.  One engine call covers many of the reference's 8-set
+    batches (batch_size * max(1, 256 // batch_size) sets) and the host reads the count once per N;
+    like every sweep on _run_pieces it takes a model with one prediction per set (PMA, one seed)."""
+    def acc_of_N(at_rate, F, N):
+        # pceval.py:88-89 skips the short batch; the call size is fixed, not the workspace rule
+        return _dataset_accuracy(model, framewise_dataset(at_rate, labels, F, N, hf), None, 2,
+                                 batch_size, mode, batch_size * max(1, 256 // batch_size))
+
+    return _reframe_driver(clips, labels, fs, list_N, list_Fs, trim_dB, None, json_file, acc_of_N)
 
 
 # ---- batch-scale sweeps of the sub-sampling, importance and 3-D re-framing experiments ---------------
@@ -194,12 +202,6 @@ def sweep_draw(step: int, run: int, n_runs: int) -> int:
     return 1 + int(step) * int(n_runs) + int(run)
 
 
-def _write_json(out: Dict, path: Optional[str]) -> None:
-    if path is not None:
-        with open(path, "w") as f:
-            json.dump(out, f)
-
-
 def _model_device(model) -> torch.device:
     return next(getattr(model, "module", model).parameters()).device
 
@@ -218,6 +220,21 @@ def _sets_per_call(model, npts: int, mode: int, want: Optional[int]) -> int:
             break
         cap //= 2
     return cap
+
+
+def _engine_cache(model, npts: int, mode: int, dev, *bufs):
+    """get(b) -> [STEngine(model, b, npts, mode, training=False), one tensor [b, *shape] of ``dtype``
+    on ``dev`` per (shape, dtype) of ``bufs``], built once per call size b, on its first use."""
+    cache = {}
+
+    def get(b):
+        if b not in cache:
+            eng = STEngine(model, b, npts, mode, training=False)
+            assert eng.cfg.k == 1, "sweeps score one prediction per set (PMA with one seed)"
+            cache[b] = [eng] + [torch.empty((b, *shape), dtype=dtype, device=dev)
+                                for shape, dtype in bufs]
+        return cache[b]
+    return get
 
 
 def _run_pieces(model, npts: int, din: int, mode: int, cap: int, pieces, select,
@@ -240,14 +257,9 @@ def _run_pieces(model, npts: int, din: int, mode: int, cap: int, pieces, select,
     if cur:
         calls.append((cur, fill))
     dev = counts.device
-    engines = {}
+    engines = _engine_cache(model, npts, mode, dev, ((npts, din), torch.float32), ((), torch.int64))
     for parts, b in calls:
-        if b not in engines:
-            eng = STEngine(model, b, npts, mode, training=False)
-            assert eng.cfg.k == 1, "sweeps score one prediction per set (PMA with one seed)"
-            engines[b] = (eng, torch.empty((b, npts, din), dtype=torch.float32, device=dev),
-                          torch.empty(b, dtype=torch.int64, device=dev))
-        eng, X, lab = engines[b]
+        eng, X, lab = engines(b)
         for slot, draw, p0, p1, off in parts:
             pos = torch.arange(p0, p1, dtype=torch.int64, device=dev)
             select(slot, draw, pos, X[off:off + p1 - p0], lab[off:off + p1 - p0])
@@ -256,34 +268,87 @@ def _run_pieces(model, npts: int, din: int, mode: int, cap: int, pieces, select,
             pca_hip.eval_tally(logits[off:off + p1 - p0], lab[off:off + p1 - p0], counts, slot)
 
 
+def _dataset_accuracy(model, ds, ids, din: int, batch_size: int, mode: int, sets_per_call) -> float:
+    """Accuracy of ``model`` over the first (n // batch_size) * batch_size sets of ``ds`` - of the
+    sets ``ids`` (device int64) when given - in one _run_pieces pass of calls of _sets_per_call(...,
+    ``sets_per_call``) sets and one host read; NaN when there is no full batch."""
+    full = ((len(ds) if ids is None else ids.numel()) // batch_size) * batch_size
+    if full == 0:
+        return float("nan")
+    counts = torch.zeros(1, dtype=torch.int64, device=_model_device(model))
+
+    def select(slot, draw, pos, out, labels_out):
+        ds.batch(pos if ids is None else ids[pos], out=out, labels_out=labels_out)
+
+    npts = ds.num_points
+    _run_pieces(model, npts, din, mode, _sets_per_call(model, npts, mode, sets_per_call),
+                [(0, 0, 0, full)], select, counts)
+    return int(counts.item()) / full                              # the one host sync of this pass
+
+
+def _set_contiguous(spec, labels, dev, temporal: bool):
+    """(spec on ``dev`` in float32 with every set contiguous - an [F, T] view of frames, or with
+    ``temporal`` an [F, Nt, S] view of chunks -, labels int64 on ``dev``)."""
+    x = torch.as_tensor(spec).to(dev, torch.float32)
+    if temporal:
+        assert x.dim() == 3, "chunks (3ST, CNN_temp): spec is [F, Nt, S]"
+        x = x.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+    else:
+        assert x.dim() == 2, "frames (FST, FB): spec is [F, T]"
+        x = x.t().contiguous().t()
+    lab = torch.as_tensor(np.asarray(labels) if not torch.is_tensor(labels) else labels)
+    return x, lab.to(dev, torch.int64).contiguous()
+
+
 def _resident_sets(spec, labels, farr, tarr, dev):
     """spec on ``dev`` in float32 with every set contiguous: [F, T] (FST frames) or [F, Nt, S]
     (3ST chunks) views; farr / tarr rounded to float32 once, as the datasets' .float() does."""
-    x = torch.as_tensor(spec).to(dev, torch.float32)
-    if tarr is None:
-        assert x.dim() == 2, "FST: spec is [F, T]"
-        x = x.t().contiguous().t()
-    else:
-        assert x.dim() == 3, "3ST: spec is [F, Nt, S]"
-        x = x.permute(2, 1, 0).contiguous().permute(2, 1, 0)
-    lab = torch.as_tensor(np.asarray(labels) if not torch.is_tensor(labels) else labels)
-    lab = lab.to(dev, torch.int64).contiguous()
+    x, lab = _set_contiguous(spec, labels, dev, tarr is not None)
     f32 = torch.as_tensor(np.asarray(farr, dtype=np.float64)).float().to(dev)
     t32 = None if tarr is None else \
         torch.as_tensor(np.asarray(tarr, dtype=np.float64)).float().to(dev)
     return x, lab, f32, t32
 
 
-def _two_pass_sweep(model, n_sets: int, npts_of_K, din: int, list_K, n_runs: int, batch_size: int,
+def _set_geometry(x: torch.Tensor, temporal: bool):
+    """(n_sets, points or cells per set, din of the packed points, n of the default K grid
+    default_list_K(n)) of a _set_contiguous spec: frames [F, T] -> (T, F, 2, F - 1 = Nfft // 2),
+    chunks [F, Nt, S] -> (S, F * Nt, 3, F * Nt)."""
+    if not temporal:
+        F, n_sets = x.shape
+        return n_sets, F, 2, F - 1
+    F, Nt, n_sets = x.shape
+    return n_sets, F * Nt, 3, F * Nt
+
+
+def _norm_list_K(list_K, default_n: int, k_max: Optional[int] = None) -> List[int]:
+    """``list_K`` as ints (None: default_list_K(default_n)), every K at least 1 and, where given, at
+    most ``k_max``."""
+    list_K = default_list_K(default_n) if list_K is None else [int(k) for k in list_K]
+    assert all(k >= 1 and (k_max is None or k <= k_max) for k in list_K), (list_K, k_max)
+    return list_K
+
+
+def _two_dicts(rand, det, list_K, json_files):
+    """The two dictionaries of the K sweeps, ``{"data": rand, "list_K"}`` and ``{"data": det,
+    "list_K"}``, written to ``json_files`` = (randK path, maxK path) when given."""
+    out_r = {"data": rand, "list_K": list_K}
+    out_m = {"data": det, "list_K": list_K}
+    if json_files is not None:
+        _write_json(out_r, json_files[0])
+        _write_json(out_m, json_files[1])
+    return out_r, out_m
+
+
+def _two_pass_sweep(model, n_sets: int, din: int, list_K, n_runs: int, batch_size: int,
                     mode: int, sets_per_call, select_of_K, step0: int = 0):
     """{K: [mean, var]} of the n_runs random runs and {K: [acc, 0]} of the deterministic pass (slot
-    n_runs); one host read per K."""
+    n_runs) on sets of K points; one host read per K."""
     assert n_runs >= 1 and batch_size >= 1
 
     def run_K(K, pieces, counts):
-        npts = npts_of_K(K)
-        cap = _sets_per_call(model, npts, mode, sets_per_call)
-        _run_pieces(model, npts, din, mode, cap, pieces, select_of_K(K), counts)
+        cap = _sets_per_call(model, K, mode, sets_per_call)
+        _run_pieces(model, K, din, mode, cap, pieces, select_of_K(K), counts)
 
     return _k_passes((n_sets // batch_size) * batch_size, list_K, n_runs, _model_device(model),
                      run_K, step0)
@@ -336,16 +401,8 @@ def subsample_sweep(model, spec, labels, farr, tarr=None, list_K: Optional[Itera
     ``{"data": {K: [acc, 0]}, "list_K": [...]}``."""
     dev = _model_device(model)
     x, lab, f32, t32 = _resident_sets(spec, labels, farr, tarr, dev)
-    if tarr is None:
-        F, n_sets = x.shape
-        npts_all, din = F, 2
-        default_n = F - 1
-    else:
-        F, Nt, n_sets = x.shape
-        npts_all, din = F * Nt, 3
-        default_n = F * Nt
-    list_K = default_list_K(default_n) if list_K is None else [int(k) for k in list_K]
-    assert all(1 <= k <= npts_all for k in list_K), (list_K, npts_all)
+    n_sets, npts_all, din, default_n = _set_geometry(x, tarr is not None)
+    list_K = _norm_list_K(list_K, default_n, npts_all)
 
     def select_of_K(K):
         def select(slot, draw, pos, out, labels_out):
@@ -354,14 +411,9 @@ def subsample_sweep(model, spec, labels, farr, tarr=None, list_K: Optional[Itera
                                      labels_out=labels_out)
         return select
 
-    rand, det = _two_pass_sweep(model, n_sets, lambda K: K, din, list_K, n_runs, batch_size, mode,
+    rand, det = _two_pass_sweep(model, n_sets, din, list_K, n_runs, batch_size, mode,
                                 sets_per_call, select_of_K)
-    out_r = {"data": rand, "list_K": list_K}
-    out_m = {"data": det, "list_K": list_K}
-    if json_files is not None:
-        _write_json(out_r, json_files[0])
-        _write_json(out_m, json_files[1])
-    return out_r, out_m
+    return _two_dicts(rand, det, list_K, json_files)
 
 
 @torch.no_grad()
@@ -384,10 +436,9 @@ def importance_sweep(model, spec, labels, farr, tarr, list_K: Optional[Iterable[
     ``{"data": {winF: {K: [acc, 0]}}, "list_K"}``.  Default list_K: default_list_K(F * Nt)."""
     dev = _model_device(model)
     x, lab, f32, t32 = _resident_sets(spec, labels, farr, tarr, dev)
-    F, Nt, n_sets = x.shape
-    list_K = default_list_K(F * Nt) if list_K is None else [int(k) for k in list_K]
+    n_sets, _, din, default_n = _set_geometry(x, True)
+    list_K = _norm_list_K(list_K, default_n)
     list_winF = [int(w) for w in list_winF]
-    assert all(k >= 1 for k in list_K)
     rand, det = {}, {}
     for wi, winF in enumerate(list_winF):
         kern = pca_hip.importance_kernel(winF).to(dev)
@@ -399,15 +450,10 @@ def importance_sweep(model, spec, labels, farr, tarr, list_K: Optional[Iterable[
                                           out=out, labels_out=labels_out)
             return select
 
-        rand[winF], det[winF] = _two_pass_sweep(model, n_sets, lambda K: K, 3, list_K, n_runs,
-                                                batch_size, mode, sets_per_call, select_of_K,
+        rand[winF], det[winF] = _two_pass_sweep(model, n_sets, din, list_K, n_runs, batch_size,
+                                                mode, sets_per_call, select_of_K,
                                                 step0=wi * len(list_K))
-    out_r = {"data": rand, "list_K": list_K}
-    out_m = {"data": det, "list_K": list_K}
-    if json_files is not None:
-        _write_json(out_r, json_files[0])
-        _write_json(out_m, json_files[1])
-    return out_r, out_m
+    return _two_dicts(rand, det, list_K, json_files)
 
 
 def _pack_sets(x, f32, t32, pos, out):
@@ -445,14 +491,8 @@ def attention_sweep(model, spec, labels, farr, tarr=None, list_K: Optional[Itera
     the curve beside it."""
     dev = _model_device(model)
     x, lab, f32, t32 = _resident_sets(spec, labels, farr, tarr, dev)
-    if tarr is None:
-        F, n_sets = x.shape
-        npts_all, din, default_n = F, 2, F - 1
-    else:
-        F, Nt, n_sets = x.shape
-        npts_all, din, default_n = F * Nt, 3, F * Nt
-    list_K = default_list_K(default_n) if list_K is None else [int(k) for k in list_K]
-    assert all(1 <= k <= npts_all for k in list_K), (list_K, npts_all)
+    n_sets, npts_all, din, default_n = _set_geometry(x, tarr is not None)
+    list_K = _norm_list_K(list_K, default_n, npts_all)
     full = (n_sets // batch_size) * batch_size
     data = {}
     if full == 0:
@@ -461,14 +501,10 @@ def attention_sweep(model, spec, labels, farr, tarr=None, list_K: Optional[Itera
         # pass 1: the key of every set, resident
         key = torch.empty((full, npts_all), dtype=torch.float32, device=dev)
         cap = _sets_per_call(model, npts_all, mode, sets_per_call)
-        engines = {}
+        engines = _engine_cache(model, npts_all, mode, dev, ((npts_all, din), torch.float32))
         for p0 in range(0, full, cap):
             b = min(cap, full - p0)
-            if b not in engines:
-                eng = STEngine(model, b, npts_all, mode, training=False)
-                assert eng.cfg.k == 1, "sweeps score one prediction per set (PMA with one seed)"
-                engines[b] = (eng, torch.empty((b, npts_all, din), dtype=torch.float32, device=dev))
-            eng, X = engines[b]
+            eng, X = engines(b)
             _pack_sets(x, f32, t32, torch.arange(p0, p0 + b, dtype=torch.int64, device=dev), X)
             eng.attention(X, want_attn=False, key_out=key[p0:p0 + b])
         del engines
@@ -525,6 +561,19 @@ def temporal_axes(fs: float, N: int, Ntemp: int, hf: float = 0.5, F: Optional[in
     return farr, tarr
 
 
+def _chunk_labels(clips, labels, hop: int, Ntemp: int, foff, dev):
+    """(S, labels int64 [S], ids of the whole chunks in corpus order; both on ``dev``) of the S
+    Ntemp-frame chunk slots of a frame-aligned STFT (stft_logmag_batch(..., frame_align=Ntemp), frame
+    offsets ``foff`` = chunk_plan's): a whole chunk carries its clip's label, every other slot -1."""
+    frames = [int(pca_hip.lib().pca_stft_num_frames(int(x.numel()), hop)) for x in clips]
+    plan_off, ids, clip_of = chunk_plan(frames, Ntemp)
+    assert plan_off == foff, (plan_off, foff)
+    S = foff[-1] // Ntemp
+    lab = np.full(S, -1, dtype=np.int64)
+    lab[ids] = np.asarray([int(labels[c]) for c in clip_of], dtype=np.int64)
+    return S, torch.as_tensor(lab).to(dev), torch.as_tensor(np.asarray(ids, dtype=np.int64)).to(dev)
+
+
 def temporal_dataset(clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float, N: int,
                      Ntemp: int = 10, hf: float = 0.5):
     """(ESC_pc_temp over every Ntemp-frame chunk slot of the corpus, device int64 ids of the whole
@@ -537,17 +586,10 @@ def temporal_dataset(clips: Sequence[torch.Tensor], labels: Sequence[int], fs: f
     spec, foff = pca_hip.stft_logmag_batch(list(clips), n_fft, win_length=N, hop=hop,
                                            drop_nyquist=True, frame_major=True, norm=N,
                                            frame_align=Ntemp)
-    frames = [int(pca_hip.lib().pca_stft_num_frames(int(x.numel()), hop)) for x in clips]
-    plan_off, ids, clip_of = chunk_plan(frames, Ntemp)
-    assert plan_off == foff, (plan_off, foff)
+    S, lab, ids = _chunk_labels(clips, labels, hop, Ntemp, foff, spec.device)
     F = n_fft // 2
-    S = foff[-1] // Ntemp
-    lab = np.full(S, -1, dtype=np.int64)
-    lab[ids] = np.asarray([int(labels[c]) for c in clip_of], dtype=np.int64)
-    dev = spec.device
     farr, tarr = temporal_axes(fs, N, Ntemp, hf, F)
-    ds = ESC_pc_temp.from_device(spec.view(S, Ntemp, F), torch.as_tensor(lab).to(dev), farr, tarr)
-    return ds, torch.as_tensor(np.asarray(ids, dtype=np.int64)).to(dev)
+    return ESC_pc_temp.from_device(spec.view(S, Ntemp, F), lab, farr, tarr), ids
 
 
 @torch.no_grad()
@@ -563,42 +605,12 @@ def reframe_sweep_temporal(model, clips: Sequence[torch.Tensor], labels: Sequenc
     reframe_sweep).  Returns (and optionally writes) ``{"data": {Fs: [acc per N]}, "list_Fs": [...],
     "list_N": [...]}``; one host read per N.  ``trim_dB``: trim every clip first (trim_clips;
     Code/pc_temp3d_eval.py:73), before any resampling; None: the clips as given."""
-    list_N = [int(n) for n in list_N]
-    if list_Fs is not None:
-        list_Fs = list(list_Fs)
-    if trim_dB is not None:
-        clips = trim_clips(clips, trim_dB, _pow2_fft(list_N),
-                           (1.0,) if list_Fs is None else [F / fs for F in list_Fs])
-    if list_Fs is not None:
-        data = {}
-        for F in list_Fs:
-            rs = [pca_hip.resample(x, fs, F, scale=True) for x in clips]    # pc_temp3d_eval.py:74
-            data[F] = reframe_sweep_temporal(model, rs, labels, F, list_N, Ntemp, hf,
-                                             batch_size=batch_size, mode=mode,
-                                             sets_per_call=sets_per_call)["data"][F]
-        out = {"data": data, "list_Fs": list_Fs, "list_N": list_N}
-        _write_json(out, json_file)
-        return out
-    dev = _model_device(model)
-    accs: List[float] = []
-    for N in list_N:
-        ds, ids = temporal_dataset(clips, labels, fs, N, Ntemp, hf)
-        full = (ids.numel() // batch_size) * batch_size   # pc_temp3d_eval.py:93-94: no short batch
-        if full == 0:
-            accs.append(float("nan"))
-            continue
-        npts = ds.num_points
-        counts = torch.zeros(1, dtype=torch.int64, device=dev)
+    def acc_of_N(at_rate, F, N):
+        ds, ids = temporal_dataset(at_rate, labels, F, N, Ntemp, hf)
+        # pc_temp3d_eval.py:93-94: no short batch
+        return _dataset_accuracy(model, ds, ids, 3, batch_size, mode, sets_per_call)
 
-        def select(slot, draw, pos, out, labels_out):
-            ds.batch(ids[pos], out=out, labels_out=labels_out)
-
-        _run_pieces(model, npts, 3, mode, _sets_per_call(model, npts, mode, sets_per_call),
-                    [(0, 0, 0, full)], select, counts)
-        accs.append(int(counts.item()) / full)                # the one host sync of this N
-    out = {"data": {fs: accs}, "list_Fs": [fs], "list_N": list_N}
-    _write_json(out, json_file)
-    return out
+    return _reframe_driver(clips, labels, fs, list_N, list_Fs, trim_dB, None, json_file, acc_of_N)
 
 
 # ---- clip-level evaluation (no reference counterpart: Code/pceval.py:95 scores frames) ---------------
@@ -665,13 +677,10 @@ def clip_accuracy(model, clips: Sequence[torch.Tensor], labels: Sequence[int], f
     clip_lab = torch.as_tensor(np.asarray([int(y) for y in labels], dtype=np.int64)).to(dev)
     set_lab = torch.empty(n_sets, dtype=torch.int64, device=dev)
     X = torch.empty((cap, npts, din), dtype=torch.float32, device=dev)
-    logits, engines, done = None, {}, 0
+    logits, engines, done = None, _engine_cache(model, npts, mode, dev), 0
     while done < n_sets:
         b = min(cap, n_sets - done)
-        if b not in engines:
-            engines[b] = STEngine(model, b, npts, mode, training=False)
-            assert engines[b].cfg.k == 1, "one prediction per set (PMA with one seed)"
-        eng = engines[b]
+        eng = engines(b)[0]
         if logits is None:
             logits = torch.empty((n_sets, eng.cfg.C), dtype=torch.float32, device=dev)
         pos = torch.arange(done, done + b, dtype=torch.int64, device=dev)
@@ -750,20 +759,9 @@ def baseline_subsample_sweep(model, spec, labels, list_K: Optional[Iterable[int]
     ``json_files`` = (randK path, maxK path), writes) ``{"data": {K: [mean, var]}, "list_K"}`` and
     ``{"data": {K: [acc, 0]}, "list_K"}``, the layout of paper_plots/{FB,CNNTemp}_{randK,maxK}_expt2.json."""
     eng = _baseline_engine(model)
-    x = torch.as_tensor(spec).to(eng.dev, torch.float32)
-    if eng.cnn:
-        assert x.dim() == 3, "CNN_temp: spec is [F, Nt, S]"
-        x = x.permute(2, 1, 0).contiguous().permute(2, 1, 0)
-    else:
-        assert x.dim() == 2, "FB: spec is [F, T]"
-        x = x.t().contiguous().t()
-    lab = torch.as_tensor(np.asarray(labels) if not torch.is_tensor(labels) else labels)
-    lab = lab.to(eng.dev, torch.int64).contiguous()
-    n_cells = x.shape[0] * (x.shape[1] if eng.cnn else 1)
-    n_sets = x.shape[-1]
-    list_K = default_list_K(n_cells if eng.cnn else n_cells - 1) if list_K is None \
-        else [int(k) for k in list_K]
-    assert all(1 <= k <= n_cells for k in list_K), (list_K, n_cells)
+    x, lab = _set_contiguous(spec, labels, eng.dev, eng.cnn)
+    n_sets, n_cells, _, default_n = _set_geometry(x, eng.cnn)
+    list_K = _norm_list_K(list_K, default_n, n_cells)
 
     def run_K(K, pieces, counts):
         _baseline_run(eng, x, lab, None, pieces, counts, K,
@@ -771,12 +769,7 @@ def baseline_subsample_sweep(model, spec, labels, list_K: Optional[Iterable[int]
                       sets_per_call)
 
     rand, det = _k_passes(_baseline_full(eng, n_sets), list_K, n_runs, eng.dev, run_K)
-    out_r = {"data": rand, "list_K": list_K}
-    out_m = {"data": det, "list_K": list_K}
-    if json_files is not None:
-        _write_json(out_r, json_files[0])
-        _write_json(out_m, json_files[1])
-    return out_r, out_m
+    return _two_dicts(rand, det, list_K, json_files)
 
 
 def baseline_frames(clips: Sequence[torch.Tensor], labels: Sequence[int], N: int, n_fft: int,
@@ -806,57 +799,34 @@ def baseline_chunks(clips: Sequence[torch.Tensor], labels: Sequence[int], N: int
     spec, foff = pca_hip.stft_logmag_batch(list(clips), n_fft, win_length=N, hop=hop,
                                            drop_nyquist=True, frame_major=True,
                                            frame_align=Ntemp)
-    frames = [int(pca_hip.lib().pca_stft_num_frames(int(x.numel()), hop)) for x in clips]
-    plan_off, ids, clip_of = chunk_plan(frames, Ntemp)
-    assert plan_off == foff, (plan_off, foff)
-    F = n_fft // 2
-    S = foff[-1] // Ntemp
-    lab = np.full(S, -1, dtype=np.int64)
-    lab[ids] = np.asarray([int(labels[c]) for c in clip_of], dtype=np.int64)
-    dev = spec.device
-    return (spec.view(S, Ntemp, F).permute(2, 1, 0), torch.as_tensor(lab).to(dev),
-            torch.as_tensor(np.asarray(ids, dtype=np.int64)).to(dev))
+    S, lab, ids = _chunk_labels(clips, labels, hop, Ntemp, foff, spec.device)
+    return spec.view(S, Ntemp, n_fft // 2).permute(2, 1, 0), lab, ids
 
 
 @torch.no_grad()
-def _baseline_reframe(model, clips, labels, fs, list_N, hf, list_Fs, json_file, n_fft, Ntemp,
-                      sets_per_call, trim_dB=None):
-    eng = _baseline_engine(model)
-    list_N = [int(n) for n in list_N]
+def _baseline_reframe(eng: BaselineEngine, clips, labels, fs, list_N, hf, list_Fs, json_file,
+                      n_fft, sets_per_call, trim_dB):
+    """Experiment 1 of both baselines on _reframe_driver: an N is one _baseline_run pass over
+    baseline_frames (FB) or baseline_chunks (CNN_temp) and one host read."""
     if n_fft is None:
         n_fft = 2 * eng.Nf if eng.cnn else 2 * (eng.layer_dims[0] - 1)
-    if list_Fs is not None:
-        list_Fs = list(list_Fs)
-    if trim_dB is not None:                      # Code/baseline_eval.py:74: trim, then resample
-        clips = trim_clips(clips, trim_dB, n_fft,
-                           (1.0,) if list_Fs is None else [F / fs for F in list_Fs])
-    if list_Fs is not None:
-        data = {}
-        for F in list_Fs:
-            rs = [pca_hip.resample(x, fs, F, scale=True) for x in clips]
-            data[F] = _baseline_reframe(eng, rs, labels, F, list_N, hf, None, None, n_fft, Ntemp,
-                                        sets_per_call)["data"][F]
-        out = {"data": data, "list_Fs": list_Fs, "list_N": list_N}
-        _write_json(out, json_file)
-        return out
-    accs: List[float] = []
-    for N in list_N:
+
+    def acc_of_N(at_rate, F, N):
         if eng.cnn:
-            x, lab, ids = baseline_chunks(clips, labels, N, n_fft, Ntemp, hf)
+            x, lab, ids = baseline_chunks(at_rate, labels, N, n_fft, eng.Nt, hf)
             n_sets = ids.numel()
         else:
-            x, lab = baseline_frames(clips, labels, N, n_fft, hf)
+            x, lab = baseline_frames(at_rate, labels, N, n_fft, hf)
             ids, n_sets = None, x.shape[1]
         full = _baseline_full(eng, n_sets)
         if full == 0:
-            accs.append(float("nan"))
-            continue
+            return float("nan")
         counts = torch.zeros(1, dtype=torch.int64, device=eng.dev)
         _baseline_run(eng, x, lab, ids, [(0, 0, 0, full)], counts, cap=sets_per_call)
-        accs.append(int(counts.item()) / full)                # the one host sync of this N
-    out = {"data": {fs: accs}, "list_Fs": [fs], "list_N": list_N}
-    _write_json(out, json_file)
-    return out
+        return int(counts.item()) / full                      # the one host sync of this N
+
+    # Code/baseline_eval.py:74: trim, then resample; the trim is checked against the model's window
+    return _reframe_driver(clips, labels, fs, list_N, list_Fs, trim_dB, n_fft, json_file, acc_of_N)
 
 
 def baseline_reframe_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float,
@@ -873,7 +843,7 @@ def baseline_reframe_sweep(model, clips: Sequence[torch.Tensor], labels: Sequenc
     ``trim_dB``: trim every clip first (trim_clips; Code/baseline_eval.py:74); None: as given."""
     eng = _baseline_engine(model)
     assert not eng.cnn, "baseline_reframe_sweep takes an FB model (CNN_temp: _temporal)"
-    return _baseline_reframe(eng, clips, labels, fs, list_N, hf, list_Fs, json_file, n_fft, None,
+    return _baseline_reframe(eng, clips, labels, fs, list_N, hf, list_Fs, json_file, n_fft,
                              sets_per_call, trim_dB)
 
 
@@ -889,5 +859,5 @@ def baseline_reframe_sweep_temporal(model, clips: Sequence[torch.Tensor], labels
     CNNTemp_expt1.json.  ``trim_dB``: as in baseline_reframe_sweep (Code/baseline_temp_eval.py:72)."""
     eng = _baseline_engine(model)
     assert eng.cnn, "baseline_reframe_sweep_temporal takes a CNN_temp model"
-    return _baseline_reframe(eng, clips, labels, fs, list_N, hf, list_Fs, json_file, n_fft, eng.Nt,
+    return _baseline_reframe(eng, clips, labels, fs, list_N, hf, list_Fs, json_file, n_fft,
                              sets_per_call, trim_dB)

@@ -583,6 +583,17 @@ def test_reframe_sweep(dev, golden_ckpt, tmp_path):
     assert all(0.0 <= a <= 1.0 for a in out["data"][fs])
     back = json.load(open(jf))
     assert back["list_N"] == list_N and len(back["data"][str(fs)]) == len(list_N)
+    # every N against what the sweep is composed of - framewise_dataset, STEngine.forward at the
+    # sweep's own call sizes (256 sets, then the rest) and torch.argmax: the same counts, exactly
+    for N, acc in zip(list_N, out["data"][fs]):
+        d = evalsweep.framewise_dataset(clips, labels, fs, N)
+        full_N, correct = (len(d) // 8) * 8, 0
+        for p0 in range(0, full_N, 256):
+            b = min(256, full_N - p0)
+            X, lab = d.batch(torch.arange(p0, p0 + b, device=dev))
+            logits = trainer.STEngine(net, b, d.num_points, training=False).forward(X)
+            correct += int((torch.argmax(logits, 1) == lab).sum())
+        assert full_N > 0 and acc == correct / full_N, (N, acc, correct, full_N)
     # N = Nfft against a direct evaluation on the oracle's spectrogram (same skipped tail)
     import dataset
     specs = [orc.stft_logmag(w, Nfft) for w in waves]

@@ -1,8 +1,11 @@
 """Host-side pieces of the batch-scale sweeps (evalsweep.subsample_sweep / importance_sweep /
-reframe_sweep_temporal): the K grid, the JSON the reference writes, the chunk plan and the 3-D axes.
-No GPU: the engine pass is replaced by a stand-in that fills the counters."""
+reframe_sweep_temporal): the K grid, the JSON the reference writes, the chunk plan and the 3-D axes,
+the call packing of the engine pass and the (Fs, N) loop of the re-framing sweeps.
+No GPU: the engine pass is replaced by a stand-in that fills the counters, or runs on a stand-in
+engine."""
 import json
 import math
+import types
 
 import numpy as np
 import pytest
@@ -176,3 +179,159 @@ def test_temporal_axes_follow_reference(N):
     np.testing.assert_array_equal(farr, np.linspace(0, fs / 2, nbins) / fs)
     np.testing.assert_array_equal(tarr, np.linspace(0, ((hf * Nfft) / fs) * Ntemp, Ntemp))
     assert len(farr) == (1 << math.ceil(math.log2(N))) // 2
+
+
+def _rows(view):
+    """(the buffer a leading-dimension slice views, its first row, its end row)."""
+    base = view if view._base is None else view._base
+    r0 = (view.storage_offset() - base.storage_offset()) // base.stride(0)
+    return base, r0, r0 + view.shape[0]
+
+
+@pytest.mark.parametrize("cap, pieces, sizes", [
+    (5, [(0, 1, 0, 7), (1, 2, 0, 7), (2, 0, 0, 7)], [5, 5, 5, 5, 1]),
+    (8, [(0, 0, 0, 3)], [3])])
+def test_run_pieces_call_packing(cap, pieces, sizes, monkeypatch):
+    """_run_pieces cuts the pieces into engine calls of `cap` sets (the last one shorter), builds one
+    engine per call size, hands `select` every position once, and the views it passes to `select`
+    and to the tally tile each call's buffers."""
+    npts, din = 6, 2
+    built, events = [], []
+
+    class Engine:
+        def __init__(self, model, B, n, mode, training=True):
+            assert training is False
+            built.append((B, n))
+            self.cfg, self.B = types.SimpleNamespace(k=1), B
+
+        def forward(self, X):
+            assert X.shape == (self.B, npts, din) and X.dtype == torch.float32
+            events.append(("forward", X, torch.zeros(self.B, 4)))
+            return events[-1][2]
+
+    def select(slot, draw, pos, out, labels_out):
+        assert pos.dtype == torch.int64 and labels_out.dtype == torch.int64
+        events.append(("select", slot, draw, pos.tolist(), out, labels_out))
+
+    monkeypatch.setattr(evalsweep, "STEngine", Engine)
+    monkeypatch.setattr(evalsweep.pca_hip, "eval_tally",
+                        lambda logits, lab, counts, slot: events.append(("tally", slot, logits, lab)))
+    evalsweep._run_pieces(_Net(), npts, din, 0, cap, pieces, select, torch.zeros(3, dtype=torch.int64))
+    forwards = [e for e in events if e[0] == "forward"]
+    assert [e[1].shape[0] for e in forwards] == sizes
+    assert built == [(b, npts) for b in dict.fromkeys(sizes)]      # once per size, in order of use
+    for slot, draw, p0, p1 in pieces:
+        mine = [e for e in events if e[0] == "select" and e[1] == slot]
+        assert all(e[2] == draw for e in mine)
+        assert [p for e in mine for p in e[3]] == list(range(p0, p1))
+    # per call: selects, one forward, tallies; the views tile [0, B) of X, labels and logits
+    i = 0
+    for b in sizes:
+        j = i
+        while events[j][0] == "select":
+            j += 1
+        kind, X, logits = events[j]
+        assert kind == "forward" and j > i
+        sel, tal = events[i:j], events[j + 1:j + 1 + (j - i)]
+        assert [e[0] for e in tal] == ["tally"] * (j - i)
+        assert [e[1] for e in tal] == [e[1] for e in sel]            # same slots, same order
+        end, lab_bufs = 0, []
+        for s_, t_ in zip(sel, tal):
+            n = len(s_[3])
+            spans = [_rows(v) for v in (s_[4], s_[5], t_[2], t_[3])]
+            assert all((r0, r1) == (end, end + n) for _, r0, r1 in spans)
+            assert spans[0][0] is X and spans[2][0] is logits and spans[1][0] is spans[3][0]
+            lab_bufs.append(spans[1][0])
+            end += n
+        assert end == b and tuple(lab_bufs[0].shape) == (b,)
+        assert all(buf is lab_bufs[0] for buf in lab_bufs)
+        i = j + 1 + (j - i)
+    assert i == len(events)
+
+
+REFRAME_SWEEPS = ["reframe_sweep", "reframe_sweep_temporal", "baseline_reframe_sweep",
+                  "baseline_reframe_sweep_temporal"]
+
+
+@pytest.mark.parametrize("name", REFRAME_SWEEPS)
+def test_reframe_sweeps_trim_once_resample_per_rate(name, tmp_path, monkeypatch):
+    """The (Fs, N) loop of the four re-framing sweeps (Code/pceval.py:61-104 and its counterparts):
+    one trim, before any resampling; one resampling per clip and rate; the reference's dictionary,
+    rates as keys in the given order; NaN where an N leaves less than one batch."""
+    from test_baselines_host import _FakeEngine
+    fs, list_N, short_N = 44100, [1024, 600, 100], 600
+    list_Fs = [fs, fs / 2]
+    clips = [torch.zeros(8192 + c) for c in range(3)]
+    baseline, temporal = name.startswith("baseline"), name.endswith("temporal")
+    batch = (2 if temporal else 1) if baseline else 8
+    events, cur = [], {}
+    n_of = lambda N: batch - 1 if N == short_N else 16 + N % 5                # noqa: E731
+    hits = lambda L, N: (L // 1024 + N) % 7 + 1                              # noqa: E731
+
+    def trim_batch(cs, top_db):
+        events.append(("trim", [int(x.numel()) for x in cs], top_db))
+        return cs, torch.tensor([[0, int(x.numel())] for x in cs])
+
+    def resample(x, fs_in, fs_out, scale=False):
+        assert fs_in == fs and scale is True
+        events.append(("resample", int(x.numel()), fs_out))
+        return x[:int(x.numel() * fs_out / fs_in)]
+
+    class DS:
+        def __init__(self, n, npts):
+            self.n, self.num_points = n, npts
+
+        def __len__(self):
+            return self.n
+
+    def build(cs, N, rate=None):
+        assert rate is None or rate == fs * cs[0].numel() // 8192        # the clips of that rate
+        cur["hits"] = hits(cs[0].numel(), N)
+        return n_of(N)
+
+    def framewise(cs, labels, rate, N, hf=0.5):
+        return DS(build(cs, N, rate), 1 + N)
+
+    def temporal_ds(cs, labels, rate, N, Ntemp=10, hf=0.5):
+        n = build(cs, N, rate)
+        return DS(n + 3, N), torch.arange(n)
+
+    def frames(cs, labels, N, n_fft, hf=0.5):
+        n = build(cs, N)
+        return torch.zeros(1025, n), torch.zeros(n, dtype=torch.int64)
+
+    def chunks(cs, labels, N, n_fft, Ntemp=10, hf=0.5):
+        n = build(cs, N)
+        return torch.zeros(512, Ntemp, n + 3), torch.zeros(n + 3, dtype=torch.int64), torch.arange(n)
+
+    def run_pieces(model, npts, din, mode, cap, pieces, select, counts):
+        counts[0] += cur["hits"]
+
+    def baseline_run(eng, x, lab, ids, pieces, counts, K=None, sel_of_slot=None, seed=0, cap=None):
+        counts[0] += cur["hits"]
+
+    monkeypatch.setattr(evalsweep.pca_hip, "trim_batch", trim_batch)
+    monkeypatch.setattr(evalsweep.pca_hip, "resample", resample)
+    for attr, fake in (("framewise_dataset", framewise), ("temporal_dataset", temporal_ds),
+                       ("baseline_frames", frames), ("baseline_chunks", chunks),
+                       ("_run_pieces", run_pieces), ("_baseline_run", baseline_run),
+                       ("_model_device", lambda m: torch.device("cpu")),
+                       ("_sets_per_call", lambda *a: 64)):
+        monkeypatch.setattr(evalsweep, attr, fake)
+    if baseline:
+        model = _FakeEngine(temporal)
+        model.layer_dims, model.Nf, model.Nt = [1025, 513, 256], 512, 10
+    else:
+        model = _Net()
+    path = str(tmp_path / "expt1.json")
+    out = getattr(evalsweep, name)(model, clips, [0, 1, 2], fs, list_N, list_Fs=list_Fs,
+                                   trim_dB=60, json_file=path)
+    assert events[0] == ("trim", [8192, 8193, 8194], 60)
+    assert [e[0] for e in events].count("trim") == 1
+    assert events[1:] == [("resample", 8192 + c, F) for F in list_Fs for c in range(3)]
+    full = (n_of(1024) // batch) * batch, (n_of(100) // batch) * batch
+    ref = {"data": {F: [hits(int(8192 * F / fs), 1024) / full[0], float("nan"),
+                        hits(int(8192 * F / fs), 100) / full[1]] for F in list_Fs},
+           "list_Fs": list_Fs, "list_N": list_N}
+    assert open(path).read() == json.dumps(ref) and json.dumps(out) == json.dumps(ref)
+    assert list(out["data"].keys()) == list_Fs and math.isnan(out["data"][fs / 2][1])
