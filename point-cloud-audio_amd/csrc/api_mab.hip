@@ -1,10 +1,10 @@
 // extern "C" entry points for the multihead attention block: argument validation and
 // dispatch on the arithmetic mode.  (set_transformer-master/modules.py:19-33)
-#include "mab1_bf16.hpp"
+#include "blocks.hpp"
 
 namespace pca {
 
-// ---- the path of one block (BlockPath, mab1_bf16.hpp), decided once per call and read by everything below ----
+// ---- the path of one block (BlockPath, blocks.hpp), decided once per call and read by everything below ----
 BlockPath block_path(const pca_mab_shape& s, bool inference, bool abi) {
   // LayerNorm variants: the exact chain only
   if (!s.ln && (s.mode == PCA_MODE_BF16 || s.mode == PCA_MODE_FP8)) {

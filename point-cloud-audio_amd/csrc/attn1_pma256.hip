@@ -1,4 +1,4 @@
-// Two kernel families of the d = 256 / 8-head step in one translation unit (map: d256_bf16.hpp):
+// Two kernel families of the d = 256 / 8-head step in one translation unit (map: d256.hpp):
 //  - the many-queries attention adjoint: k_attn1_bwd3 runs the fc_o adjoint and the attention adjoint in one
 //    launch, WAVE = HEAD, and leaves per-range partials of the set's dKp / dVp; k_sum_parts256 adds them in
 //    a fixed order;
@@ -7,7 +7,9 @@
 // They share the unit for the compiler's sake: hipcc emits another k_pma_bwd256 (5 instructions more, other
 // registers) when the PMA is compiled without k_attn1_bwd3 or k_fq_attn_bwd2 beside it
 // (profiles/r07_split_d256.txt, check A).
-#include "d256_bf16.hpp"
+#include "d256.hpp"
+#include "bwd_defer.hpp"
+#include "mfma_common.hpp"
 
 #include <math.h>
 
@@ -774,7 +776,7 @@ __global__ __launch_bounds__(256, 1) void k_pma_bwd256(const PmaArgs a) {
 
 }  // namespace
 
-// ---- launchers (declared in d256_bf16.hpp) ------------------------------------------------
+// ---- launchers (declared in d256.hpp) ------------------------------------------------
 int attn1_bwd256_parts(int B, int N) {
   // point ranges per set so that B * parts workgroups (2 per CU) cover the chip
   int parts = 1;

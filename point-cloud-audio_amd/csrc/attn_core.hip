@@ -34,7 +34,8 @@
 // k_lengths[b] are masked (P = 0), as softmax_rows does for the chain.
 // Workgroup ids: sets b and b + 8 k sit on the same XCD (id mod 8), the workgroups of one set in
 // consecutive slots of it - what they stage comes from that XCD's L2 after the first.
-#include "mab1_bf16.hpp"
+#include "blocks.hpp"
+#include "mfma_common.hpp"
 
 #include <math.h>
 

@@ -1,0 +1,259 @@
+// The end of a backward pass: bwd_defer_flush runs everything the blocks of a step queued in their BwdDefer
+// (bwd_defer.hpp) - the weight-gradient launches (wgrad128.hip, wgrad256.hip) with the due slab sums as
+// riders, then the post stages:
+//
+//   k_mab0_post1 / k_terminal1   dWk and dQp of the shared queries (k_terminal1: the same plus the classifier's
+//                                weight gradient, the layer-1 fc_v gradient and late slab sums as extra rows)
+//   k_mab0_post2                 dWq, dbq, dI from dQp (+ the sums of the partials k_terminal1 itself wrote)
+#include "bwd_defer.hpp"
+#include "terminal_bodies.hpp"
+#include "slab_sum_body.hpp"
+
+namespace pca {
+
+namespace {
+
+// ---------------------------------------------------------------------------------
+// shared-query parameters.  dQs = sum_b dO[b] ([m][d]); DG = sum over sets of dS X in
+// "ln2 units": dG_raw = sl2e * DG.
+//   dWk[f][c]  += sum_q Qp[q][f] dG_raw[j m + q][c]            (j = head of f)
+//   dQp[q][f]   = dQs[q][f] + sum_c dG_raw[j m + q][c] Wk[f][c]
+//   dWq += dQp^T I ; dbq += colsum(dQp) ; dI += dQp Wq
+// ---------------------------------------------------------------------------------
+// dot of two strided sequences with NF independent load pairs in flight (the post kernels are a
+// few dependent L2 round trips long and nothing else: a 128-term dot is 2 trips at NF = 64, 8 at 16)
+template <int NF = 64>
+__device__ __forceinline__ float dot_strided(const float* __restrict__ a, int64_t sa,
+                                             const float* __restrict__ b, int64_t sb, int n) {
+  float acc = 0.f;
+  int i = 0;
+  for (; i + NF <= n; i += NF) {
+    float x[NF], y[NF];
+#pragma unroll
+    for (int u = 0; u < NF; ++u) { x[u] = a[(i + u) * sa]; y[u] = b[(i + u) * sb]; }
+#pragma unroll
+    for (int u = 0; u < NF; ++u) acc = fmaf(x[u], y[u], acc);
+  }
+  for (; i + 16 <= n; i += 16) {
+    float x[16], y[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) { x[u] = a[(i + u) * sa]; y[u] = b[(i + u) * sb]; }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) acc = fmaf(x[u], y[u], acc);
+  }
+  for (; i < n; ++i) acc = fmaf(a[i * sa], b[i * sb], acc);
+  return acc;
+}
+
+// stage 1 (grid-parallel): dWk and dQp = dQs + (dG_raw Wk_h^T); blockIdx.y = MAB
+__device__ __forceinline__ void post1_body(const Mab0PostJob& a, int blk) {
+  const int m = a.m, d = a.d, dk = a.dk;
+  const int dh = d / a.h;
+  const int o = blk * 256 + threadIdx.x;
+  if (o < d * dk) {
+    if (a.DG == nullptr) return;            // keys were projected: dWk comes from the GEMM path
+    const int f = o / dk, c = o - f * dk, j = f / dh;
+    a.dWk[o] += a.sl2e * dot_strided(a.Qp + f, d, a.DG + (int64_t)j * m * dk + c, dk, m);
+  } else if (o < d * dk + m * d) {
+    const int oo = o - d * dk;
+    const int q = oo / d, f = oo - q * d, j = f / dh;
+    float qs;
+    if (a.dQs != nullptr) {
+      qs = a.dQs[oo];
+    } else {                                  // sum over the sets, 16 loads in flight
+      qs = 0.f;
+      const int64_t sb = (int64_t)m * d;
+      int bb = 0;
+      for (; bb + 64 <= a.B; bb += 64) {
+        float v[64];
+#pragma unroll
+        for (int u = 0; u < 64; ++u) v[u] = a.dO[(bb + u) * sb + oo];
+#pragma unroll
+        for (int u = 0; u < 64; ++u) qs += v[u];
+      }
+      for (; bb + 16 <= a.B; bb += 16) {
+        float v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = a.dO[(bb + u) * sb + oo];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) qs += v[u];
+      }
+      for (; bb < a.B; ++bb) qs += a.dO[bb * sb + oo];
+    }
+    a.dQp[oo] = a.DG == nullptr ? qs
+                                : qs + a.sl2e * dot_strided(a.DG + (int64_t)(j * m + q) * dk, 1,
+                                                            a.Wk + (int64_t)f * dk, 1, dk);
+  }
+}
+__global__ __launch_bounds__(256) void k_mab0_post1(const Mab0PostJobs jobs) {
+  post1_body(jobs.j[blockIdx.y], blockIdx.x);
+}
+// stage 1 + riders: rows [0, J.n) of blockIdx.y are the post-1 jobs, then (when present) the
+// classifier weight gradient (one workgroup per class) and the layer-1 fc_v gradient
+__global__ __launch_bounds__(256) void k_terminal1(const Mab0PostJobs jobs, const ClsWgradArgs c,
+                                                   int has_cls, const SmallWgradArgs w,
+                                                   int has_sw, const SlabSumJobs late) {
+  const int y = blockIdx.y;
+  if (y < jobs.n) {
+    post1_body(jobs.j[y], blockIdx.x);
+  } else if (has_cls && y == jobs.n) {
+    if ((int)blockIdx.x < c.C)
+      cls_wgrad_body(c.dlogits, c.P, c.lossv, c.corrv, c.B, c.d, c.C, c.dWc, c.dbc, c.loss_out,
+                     c.stats, blockIdx.x);
+  } else if (has_sw && y == jobs.n + has_cls) {
+    if ((int64_t)blockIdx.x * w.rows_per_wg < w.M)
+      wgrad_small_body<float>(w.G, w.X, w.M, w.dq, w.rows_per_wg, w.x_head_stride, w.dW, w.db,
+                              blockIdx.x, w.slab);
+  } else {
+    // rider rows: the weight-gradient slabs of this step, added in a fixed order
+    __shared__ float4 red[4 * 64];
+    slab_sum_body(late.j[y - jobs.n - has_cls - has_sw], blockIdx.x, threadIdx.x, red);
+  }
+}
+// stage 2: dWq += dQp^T I ; dbq += colsum(dQp) ; dI += dQp Wq
+__global__ __launch_bounds__(256) void k_mab0_post2(const Mab0PostJobs jobs, const SlabSumJobs late) {
+  if ((int)blockIdx.y >= jobs.n) {       // rider rows (partials written by k_terminal1 itself)
+    __shared__ float4 red[4 * 64];
+    slab_sum_body(late.j[blockIdx.y - jobs.n], blockIdx.x, threadIdx.x, red);
+    return;
+  }
+  const Mab0PostJob a = jobs.j[blockIdx.y];
+  const int m = a.m, d = a.d, dq = a.dq;
+  const int o = blockIdx.x * 256 + threadIdx.x;
+  const int n1 = d * dq, n2 = n1 + d, n3 = n2 + (a.dI != nullptr ? m * dq : 0);
+  if (o < n1) {
+    const int f = o / dq, c = o - f * dq;
+    a.dWq[o] += dot_strided(a.dQp + f, d, a.I + c, dq, m);
+  } else if (o < n2) {
+    const int f = o - n1;
+    float acc = 0.f;
+    for (int q = 0; q < m; ++q) acc += a.dQp[q * d + f];
+    a.dbq[f] += acc;
+  } else if (o < n3) {
+    const int oo = o - n2;
+    const int q = oo / dq, c = oo - q * dq;
+    a.dI[oo] += dot_strided(a.dQp + (int64_t)q * d, 1, a.Wq + c, dq, d);
+  }
+}
+
+}  // namespace
+
+// threads the widest job needs in each post stage (one output element per thread; grid.x = cdiv(., 256))
+struct PostExtents { int n1, n2; };
+static PostExtents post_extents(const Mab0PostJobs& J) {
+  PostExtents x{0, 0};
+  for (int i = 0; i < J.n; ++i) {
+    const Mab0PostJob& a = J.j[i];
+    const int e1 = a.d * a.dk + a.m * a.d, e2 = a.d * a.dq + a.d + (a.dI ? a.m * a.dq : 0);
+    x.n1 = e1 > x.n1 ? e1 : x.n1;
+    x.n2 = e2 > x.n2 ? e2 : x.n2;
+  }
+  return x;
+}
+
+int terminal_launch(const BwdDefer& D, hipStream_t st, const SlabSumJobs* late_in) {
+  SlabSumJobs late{};
+  if (late_in != nullptr) late = *late_in;
+  if (!D.has_cls && !D.has_sw && late.n == 0) return mab0_post_launch(D.posts, st);
+  const Mab0PostJobs& J = D.posts;
+  const PostExtents x = post_extents(J);
+  int gx = (int)cdiv(x.n1, 256);
+  if (D.has_cls && D.cls.C > gx) gx = D.cls.C;
+  if (D.has_sw) {
+    const int gs = (int)cdiv(D.sw.M, D.sw.rows_per_wg);
+    gx = gs > gx ? gs : gx;
+  }
+  for (int i = 0; i < late.n; ++i) {
+    PCA_REQUIRE(slab_sum_job_ok(late.j[i]), "terminal: rider alignment");
+    const int need = (int)cdiv(late.j[i].n, 256);
+    gx = need > gx ? need : gx;
+  }
+  hipLaunchKernelGGL(k_terminal1,
+                     dim3(gx, J.n + (D.has_cls ? 1 : 0) + (D.has_sw ? 1 : 0) + late.n),
+                     dim3(256), 0, st, J, D.cls, D.has_cls ? 1 : 0, D.sw, D.has_sw ? 1 : 0, late);
+  PCA_TRY(check_launch("k_terminal1"));
+  // the layer-1 fc_v partials k_terminal1 wrote (slab mode) are summed by rider rows of post 2
+  SlabSumJobs late2{};
+  if (D.has_sw && D.sw.slab != nullptr) {
+    const int nwg = (int)cdiv(D.sw.M, D.sw.rows_per_wg), n1 = 128 * D.sw.dq, stride = n1 + 128;
+    late2.j[late2.n++] = SlabSumJob{D.sw.slab, D.sw.dW, nwg, n1, 1, stride};
+    if (D.sw.db != nullptr) late2.j[late2.n++] = SlabSumJob{D.sw.slab + n1, D.sw.db, nwg, 128, 1, stride};
+  }
+  if (J.n == 0) return slab_sum_jobs(late2, st);
+  int n2 = x.n2;
+  for (int i = 0; i < late2.n; ++i) n2 = late2.j[i].n > n2 ? late2.j[i].n : n2;
+  hipLaunchKernelGGL(k_mab0_post2, dim3((unsigned)cdiv(n2, 256), J.n + late2.n), dim3(256), 0, st, J,
+                     late2);
+  return check_launch("k_mab0_post2");
+}
+
+int mab0_post_launch(const Mab0PostJobs& J, hipStream_t st) {
+  if (J.n == 0) return PCA_OK;
+  const PostExtents x = post_extents(J);
+  hipLaunchKernelGGL(k_mab0_post1, dim3((unsigned)cdiv(x.n1, 256), J.n), dim3(256), 0, st, J);
+  PCA_TRY(check_launch("k_mab0_post1"));
+  hipLaunchKernelGGL(k_mab0_post2, dim3((unsigned)cdiv(x.n2, 256), J.n), dim3(256), 0, st, J,
+                     SlabSumJobs{});
+  return check_launch("k_mab0_post2");
+}
+
+bool wgrad_slabs_on() {          // (read per call: a test switches it between two engines)
+  return env_not_zero("PCA_WGRAD_SLABS");
+}
+int bwd_defer_flush(BwdDefer& D, hipStream_t st) {
+  // The sums the post stages read (D.sums: dG of the few-queries blocks) ride in the first
+  // weight-gradient launch as extra workgroup rows.  Slab mode (the default when the caller lent
+  // room; PCA_WGRAD_SLABS=0 switches back to fp32 atomics): the weight gradients themselves use no
+  // atomics either - per-workgroup partials, summed in a fixed order by rider rows of k_terminal1
+  // (`late`: only the optimizer reads them).  With EVERY reduction of the step in this form
+  // configs[1] measured 0.324 ms/step against 0.335 with the atomics (three same-box pairs), and the
+  // step is bit-reproducible.  (With only k_wgrad128 converted it was 0.343 ... 0.361 against 0.348,
+  // depending on where the partials happened to lie.)
+  const bool slab_mode = wgrad_slabs_on() && D.slab_ws != nullptr && D.slab_cap > 0;
+  SlabSumJobs late{};
+  size_t used = 0;          // the two lists' slabs lie back to back
+  if (D.wg_bf16.n > 0) {
+    double rows = 0;
+    for (int i = 0; i < D.wg_bf16.n; ++i) rows += (double)D.wg_bf16.j[i].M;
+    ProfScope ps(PCA_K_WGRAD, st, 2.0 * rows * 128 * 128, 4.0 * rows * 128);
+    // every workgroup costs a 64 KiB slab (16384 atomics without the slabs): aim at ~200
+    // workgroups over all jobs (512 rows for one B*N-row job, 1024 for three, ...)
+    // (measured at 3 x 65536 rows: 512 -> 41 us, 768 -> 41, 1024 -> 31, 1536 -> 31, 2048 -> 39)
+    int rpw = 512 * (int)((rows + 98303.0) / 98304.0);
+    rpw = rpw < 512 ? 512 : (rpw > 1024 ? 1024 : rpw);
+    WgradSlabs sl{slab_mode ? D.slab_ws : nullptr, D.slab_cap * 3 / 4, &late, &D.sums, 0};
+    PCA_TRY(wgrad128_launch(D.wg_bf16, true, true, rpw, st, &sl));
+    used = (sl.used + 255) & ~(size_t)255;
+    ps.end();
+    D.wg_bf16.n = 0;
+    D.sums.n = 0;
+  }
+  if (D.wg_f32.n > 0) {
+    // 64: 18.7 us, 128: 14.2, 256: 15.3
+    WgradSlabs sl{slab_mode ? D.slab_ws + used / sizeof(float) : nullptr, D.slab_cap - used, &late,
+                  &D.sums, 0};
+    PCA_TRY(wgrad128_launch(D.wg_f32, false, false, 128, st, &sl));
+    used += (sl.used + 255) & ~(size_t)255;
+    D.wg_f32.n = 0;
+    D.sums.n = 0;
+  }
+  if (D.wg256_n > 0) PCA_TRY(wgrad256_flush_deferred(D, st));
+  PCA_TRY(slab_sum_jobs(D.sums, st));        // (nobody carried them)
+  D.sums.n = 0;
+  for (int i = 0; i < D.late.n; ++i) {
+    PCA_REQUIRE(late.n < 40, "bwd_defer_flush: slab-sum table full");
+    late.j[late.n++] = D.late.j[i];
+  }
+  D.late.n = 0;
+  if (slab_mode && D.has_sw) {     // layer-1 fc_v gradient (rider of k_terminal1): slabs as well
+    const int nwg = (int)cdiv(D.sw.M, D.sw.rows_per_wg), stride = 128 * D.sw.dq + 128;
+    if ((128 * D.sw.dq) % 4 == 0 && used + (size_t)nwg * stride * 4 <= D.slab_cap)
+      D.sw.slab = D.slab_ws + used / sizeof(float);
+  }
+  PCA_TRY(terminal_launch(D, st, &late));
+  D.posts.n = 0;
+  D.has_cls = D.has_sw = 0;
+  return PCA_OK;
+}
+
+}  // namespace pca

@@ -13,7 +13,8 @@
 // bf16 tensors = 67 MB, 15 us at the 4.5 TB/s these streams reach - so a deeper X ring (tried: one
 // to three tiles ahead, same time) buys nothing; only saving less would.
 // Roofline unit: 2 (dq d + d^2 + 2 m d) FLOP per point, 2 (dq + d) bytes per point.
-#include "d256_bf16.hpp"
+#include "blocks.hpp"
+#include "mfma_common.hpp"
 
 #include <math.h>
 

@@ -1,6 +1,6 @@
 // Launchers of the d = 256 training kernels; all activations bf16 [rows][256].  The one declaration point of
-// attn1_pma256.hip, wgrad256.hip, fq256.hip, small256.hip, slab_sum.hip, d256_stream.hip,
-// d256_fused.hip, d128_fused.hip and mid256.hip.
+// attn1_pma256.hip, wgrad256.hip, fq256.hip, small256.hip, d256_stream.hip, d256_fused.hip and mid256.hip
+// (the blocks built from them: d256_host.hip, declared in blocks.hpp).
 //
 // Map of the d = 256 / 8-head / m = 32 Set Transformer's training step (BASELINE configs[3], the
 // north-star shape): the pieces of the MAB adjoint (set_transformer-master/
@@ -34,7 +34,9 @@
 // All activations cross these kernels in bf16 ([rows][256], row-major); accumulation, softmax
 // statistics, biases and residuals are fp32.  Layout conventions: mfma_common.hpp.
 #pragma once
-#include "mab1_bf16.hpp"
+#include "pca_common.h"
+#include "weight_images.hpp"
+#include "bwd_defer.hpp"
 
 namespace pca {
 
@@ -50,22 +52,6 @@ int isab1_fwd256_fused(const void* X, int dq, const __bf16* WqB, const float* Wq
                        __bf16* Y, __bf16* QpS, __bf16* OS, uint32_t* mask, int B, int N,
                        hipStream_t st, const float* inv_o = nullptr);
 
-// dW[256 x 256] += G^T A, db[256] += colsum(G) (nullable); G, A bf16 [M][256]
-struct Wgrad256Job {
-  const void* G;      // bf16, or fp32 with wgrad256_launch_t(..., f32_operands = true)
-  const void* A;
-  float* dW;
-  float* db;
-  int64_t M;
-  // optional (bf16 LDS-DMA kernel only, M % 32 == 0): ReLU mask words of the many-queries forward
-  // over the same rows (mab1_mask_index<256> with N % 128 == 0, i.e. 128 words per 16 rows); G is
-  // then used as G . [mask] - the job reads dY and the mask instead of a materialised dZ
-  const uint32_t* mask;
-};
-struct Wgrad256Jobs {
-  Wgrad256Job j[8];
-  int n;
-};
 bool wgrad256_masked_ok(int64_t rows_per_set);
 // mid256.hip: the per-set stage between the two blocks of a d = 256 ISAB in one launch
 int mid256_fwd(const float* O, const float* Wo, const float* bo, const float* Wk, const float* bk,
@@ -74,43 +60,12 @@ int mid256_fwd(const float* O, const float* Wo, const float* bo, const float* Wk
 // The query side (Qp, G: parameters only) of several few-queries blocks collected into `out`, for ONE
 // launch the caller makes together with its other preparation jobs; the blocks' forward calls then take
 // PCA_F_PREP_DONE (training only: the saved blocks must exist)
-struct Mab0PrepJobs;
 void mab0_d256_prep_collect(int n, const pca_mab_shape* const* shapes, const float* const* I,
                             const pca_mab_params* params, void* const* saved, Mab0PrepJobs* out);
 // image mode (prep_weight) of every weight the d = 256 backward takes - fc_o / fc_q of the many-queries
 // block, fc_k / fc_v of the few-queries block: the transposed natural image the register-resident
 // kernels (k_attn1_bwd3, k_rowstream) read
 constexpr int D256_BWD_WMODE = 3;
-struct DxHandoff {            // mab1's dX = dQp Wq, deferred into the few-queries block's DX launch
-  const __bf16 *dQp, *WqT;
-  __bf16* dX;
-  int B, N;
-};
-// What one engine call (pca_st_train_fwd_bwd, pca_st_forward) hands from one internal stage to the next.
-// It lives on that call's stack and goes down as a nullable pointer: null is a stand-alone block call
-// (pca_mab_fwd / pca_mab_bwd), which converts every image itself, defers nothing and hands nothing over.
-struct StepCtx {
-  const WeightImages* images;   // the step's ready-made weight images (null: converted on the spot)
-  BwdDefer* defer;              // where the block queues its terminal reductions (null: it launches them)
-  // d = 256 training forward, set around an ISAB's few-queries block (saved1 null: not set): that block
-  // then ends in mid256_fwd, which also writes the K / V images of the many-queries block (s1, p1,
-  // saved1), and says so in mid_done; the caller passes PCA_F_KV_READY to that block's forward
-  pca_mab_shape s1;
-  pca_mab_params p1;
-  void* saved1;
-  bool mid_done;
-  // d = 256 backward, armed around an ISAB's pair of calls with separate workspaces for the two blocks
-  // (dQp must outlive mab1's call): mab1's fc_q weight-gradient job {dQp, X} goes to the few-queries
-  // block, whose two jobs {dKp, X}, {dVp, X} read the same X - launched together, the three share each
-  // X tile through the XCD's L2 (k_wgrad256's shared-operand order) - and its dX = dQp Wq likewise
-  bool armed, has, has_dx;
-  Wgrad256Job job;
-  DxHandoff dx;
-};
-inline BwdDefer* defer_of(const StepCtx* c) { return c != nullptr ? c->defer : nullptr; }
-inline const WeightImages* images_of(const StepCtx* c) { return c != nullptr ? c->images : nullptr; }
-// a handed-over job / dX nobody took (the following block was not the projected-keys few-queries one)
-int wgrad256_handoff_flush(StepCtx* ctx, void* ws, hipStream_t st);
 size_t wgrad256_ws_bytes(int njobs, int64_t maxM);
 int wgrad256_launch(const Wgrad256Jobs& jobs, void* ws, hipStream_t st);
 int wgrad256_launch_t(const Wgrad256Jobs& jobs, void* ws, bool f32_operands, hipStream_t st);
@@ -141,11 +96,6 @@ int attn1_bwd256_fused(const __bf16* dY, const uint32_t* mask, const __bf16* WoT
                        __bf16* dQp, float* dKpPart, float* dVpPart, float* dKp, float* dVp, int B,
                        int N, hipStream_t st, const float* Xs = nullptr,
                        const float* WqF = nullptr, const float* bq = nullptr, int dq = 0);
-// d128_fused.hip: the same single-launch forward at d = 128 / 4 heads / m = 16
-int isab1_fwd128_fused(const void* X, int dq, const __bf16* WqB, const float* WqF, const float* bq,
-                       const __bf16* KpP, const __bf16* Vt, const __bf16* WoP, const float* bo,
-                       __bf16* Y, __bf16* QpS, __bf16* OS, uint32_t* mask, int B, int N,
-                       hipStream_t st);
 size_t wgrad_small256_ws_bytes(int64_t M);
 int wgrad_small256(const __bf16* G, const float* X, int64_t M, int dq, float* dW, float* db,
                    void* ws, hipStream_t st);
@@ -172,7 +122,6 @@ int pma_attn_bwd256(const __bf16* X, const __bf16* Gb, const __bf16* dTb, const 
                     const int32_t* lengths, __bf16* dX, int accumulate_dx, float* DG, float* DGslabs,
                     hipStream_t st);
 size_t pma_bwd256_slab_bytes(int B);
-int slab_sum(const float* slabs, int S, int n, float* out, int accumulate, hipStream_t st);
 
 // few shared queries over projected keys, head dim 32 (fq_attn_fwd256: m <= 16; m = 32 projects the keys in
 // the same pass: fq_proj_attn_fwd256)

@@ -15,7 +15,8 @@
 // between: 2 extra passes over [B*N, 256]), no weight is ever re-read, and every global access is
 // a full 128-byte line.  Roofline unit: 2 (dq d + d^2 + 2 m d) FLOP per point,
 // 2 (dq + d) bytes per point.
-#include "d256_bf16.hpp"
+#include "d256.hpp"
+#include "mfma_common.hpp"
 
 #include <math.h>
 

@@ -1,5 +1,5 @@
 // Host orchestration of the d = 256 / 8-head training blocks (kernels: attn1_pma256.hip, wgrad256.hip,
-// fq256.hip, small256.hip; map: d256_bf16.hpp).
+// fq256.hip, small256.hip; map: d256.hpp).
 //   mab1_d256_bwd     adjoint of ISAB's mab1(X, H) (modules.py:53 / 19-33): three row-GEMM /
 //                     attention launches + the 256-wide weight-gradient reduction
 //   mab0_d256_*       the few-shared-queries block (ISAB mab0, PMA; modules.py:52,63):
@@ -10,7 +10,11 @@
 //                     with the per-set [B*m]-row epilogues on the GEMM kernel.
 // Activations cross the ABI in fp32 or bf16 (shape.*_dtype); inside, every [B*N, 256] tensor is
 // bf16 - fp32 callers pay one conversion pass per tensor.
-#include "d256_bf16.hpp"
+#include "blocks.hpp"
+#include "weight_images.hpp"
+#include "bwd_defer.hpp"
+#include "step_ctx.hpp"
+#include "d256.hpp"
 
 #include <math.h>
 

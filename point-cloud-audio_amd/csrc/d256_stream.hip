@@ -14,7 +14,8 @@
 // global_load_lds_dwordx4 (1 KiB per wave instruction, swizzled at the source), NBUF - 1 tiles
 // ahead, and one tile per output that leaves in 16-byte pieces of full rows.
 // Roofline unit: 2 d^2 FLOP per point and weight, 2 d bytes per point and tensor.
-#include "d256_bf16.hpp"
+#include "d256.hpp"
+#include "mfma_common.hpp"
 
 #include <math.h>
 

@@ -1,8 +1,9 @@
 // The few-queries attention (ISAB mab0 at dk = 256) over projected keys, wave = head, head dim 32
-// (map: d256_bf16.hpp): the forward with the projection in the same pass (k_fq_proj_fwd, m = 32) or
+// (map: d256.hpp): the forward with the projection in the same pass (k_fq_proj_fwd, m = 32) or
 // after k_rowstream PROJ2 (k_fq_attn_fwd, m <= 16), the backward (k_fq_attn_bwd2 / k_fq_attn_bwd) and
 // the small kernels that join the per-range partials.
-#include "d256_bf16.hpp"
+#include "d256.hpp"
+#include "mfma_common.hpp"
 
 #include <math.h>
 
@@ -866,7 +867,7 @@ __global__ __launch_bounds__(256) void k_fq_dq_sum(const float* __restrict__ dO,
 
 }  // namespace
 
-// ---- launchers (declared in d256_bf16.hpp) ------------------------------------------------
+// ---- launchers (declared in d256.hpp) ------------------------------------------------
 int fq_splits256(int B, int N) {
   int S = 1;
   const int tiles = (int)cdiv(N, 32);

@@ -3,7 +3,10 @@
 //   backward  mab1 chain (dX, dKp, dVp) -> k_mid_bwd -> batched wgrad -> mab0 backward
 //             (the mid chain runs inside the mab0 backward's launch unless PCA_D128_MIDFUSE=0)
 // Only host code here; kernels live in mab0_*, mab1_*, mid_bf16.hip.
-#include "d256_bf16.hpp"
+#include "blocks.hpp"
+#include "weight_images.hpp"
+#include "bwd_defer.hpp"
+#include "step_ctx.hpp"
 
 #include <stdlib.h>
 

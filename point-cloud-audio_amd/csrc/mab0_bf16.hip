@@ -22,7 +22,10 @@
 //   k_mab0_attn_small   layer 1 (dk = din <= 4): exact fp32 on the vector ALU, the rows of a
 //                 set shared by two workgroups
 //   k_mab0_epi    per set: O, Z, H (fp32 VALU; 2*m*d*(dk+d) MACs)
-#include "mab1_bf16.hpp"
+#include "blocks.hpp"
+#include "weight_images.hpp"
+#include "step_ctx.hpp"
+#include "mfma_common.hpp"
 #include "pack_body.hpp"
 #include "pma_head_bodies.hpp"
 

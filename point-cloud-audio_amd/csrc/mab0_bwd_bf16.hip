@@ -12,13 +12,15 @@
 //                                              LDS tile and comes back transposed, X^T through
 //                                              ds_read_tr16_b64 of the X tile)
 //   k_mab0_bwd_small                      layer 1 (dk <= 4): fp32 VALU, no dX needed
-//   parameter gradients of the epilogue (dWo, dWv, dbo, dbv) are [B*m]-row reductions done with
-//   the fp32 GEMM; k_mab0_post turns sum_b dO and dG into dWk, dWq, dbq, dI.  d(bk) is
-//   identically zero (softmax shift invariance) and is left untouched.
-#include "d256_bf16.hpp"
-#include "terminal_bodies.hpp"
+//   parameter gradients of the epilogue (dWo, dWv, dbo, dbv) are [B*m]-row reductions: jobs of
+//   k_wgrad128 (wgrad128.hip); the post stages (k_mab0_post1 / 2, bwd_defer.hip) turn sum_b dO and dG
+//   into dWk, dWq, dbq, dI.  d(bk) is identically zero (softmax shift invariance) and is left
+//   untouched.  The PMA head launch that precedes this backward in the train step: pma_head.hip.
+#include "blocks.hpp"
+#include "bwd_defer.hpp"
+#include "step_ctx.hpp"
+#include "mfma_common.hpp"
 #include "pma_head_bodies.hpp"
-#include "slab_sum_body.hpp"
 #include "mid_bwd_body.hpp"
 
 #include <math.h>
@@ -503,482 +505,7 @@ __global__ __launch_bounds__(256) void k_mab0_bwd_small(
   }
 }
 
-// ---------------------------------------------------------------------------------
-// shared-query parameters.  dQs = sum_b dO[b] ([m][d]); DG = sum over sets of dS X in
-// "ln2 units": dG_raw = sl2e * DG.
-//   dWk[f][c]  += sum_q Qp[q][f] dG_raw[j m + q][c]            (j = head of f)
-//   dQp[q][f]   = dQs[q][f] + sum_c dG_raw[j m + q][c] Wk[f][c]
-//   dWq += dQp^T I ; dbq += colsum(dQp) ; dI += dQp Wq
-// ---------------------------------------------------------------------------------
-// dot of two strided sequences with NF independent load pairs in flight (the post kernels are a
-// few dependent L2 round trips long and nothing else: a 128-term dot is 2 trips at NF = 64, 8 at 16)
-template <int NF = 64>
-__device__ __forceinline__ float dot_strided(const float* __restrict__ a, int64_t sa,
-                                             const float* __restrict__ b, int64_t sb, int n) {
-  float acc = 0.f;
-  int i = 0;
-  for (; i + NF <= n; i += NF) {
-    float x[NF], y[NF];
-#pragma unroll
-    for (int u = 0; u < NF; ++u) { x[u] = a[(i + u) * sa]; y[u] = b[(i + u) * sb]; }
-#pragma unroll
-    for (int u = 0; u < NF; ++u) acc = fmaf(x[u], y[u], acc);
-  }
-  for (; i + 16 <= n; i += 16) {
-    float x[16], y[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) { x[u] = a[(i + u) * sa]; y[u] = b[(i + u) * sb]; }
-#pragma unroll
-    for (int u = 0; u < 16; ++u) acc = fmaf(x[u], y[u], acc);
-  }
-  for (; i < n; ++i) acc = fmaf(a[i * sa], b[i * sb], acc);
-  return acc;
-}
-
-// stage 1 (grid-parallel): dWk and dQp = dQs + (dG_raw Wk_h^T); blockIdx.y = MAB
-__device__ __forceinline__ void post1_body(const Mab0PostJob& a, int blk);
-__global__ __launch_bounds__(256) void k_mab0_post1(const Mab0PostJobs jobs) {
-  post1_body(jobs.j[blockIdx.y], blockIdx.x);
-}
-__device__ __forceinline__ void post1_body(const Mab0PostJob& a, int blk) {
-  const int m = a.m, d = a.d, dk = a.dk;
-  const int dh = d / a.h;
-  const int o = blk * 256 + threadIdx.x;
-  if (o < d * dk) {
-    if (a.DG == nullptr) return;            // keys were projected: dWk comes from the GEMM path
-    const int f = o / dk, c = o - f * dk, j = f / dh;
-    a.dWk[o] += a.sl2e * dot_strided(a.Qp + f, d, a.DG + (int64_t)j * m * dk + c, dk, m);
-  } else if (o < d * dk + m * d) {
-    const int oo = o - d * dk;
-    const int q = oo / d, f = oo - q * d, j = f / dh;
-    float qs;
-    if (a.dQs != nullptr) {
-      qs = a.dQs[oo];
-    } else {                                  // sum over the sets, 16 loads in flight
-      qs = 0.f;
-      const int64_t sb = (int64_t)m * d;
-      int bb = 0;
-      for (; bb + 64 <= a.B; bb += 64) {
-        float v[64];
-#pragma unroll
-        for (int u = 0; u < 64; ++u) v[u] = a.dO[(bb + u) * sb + oo];
-#pragma unroll
-        for (int u = 0; u < 64; ++u) qs += v[u];
-      }
-      for (; bb + 16 <= a.B; bb += 16) {
-        float v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = a.dO[(bb + u) * sb + oo];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) qs += v[u];
-      }
-      for (; bb < a.B; ++bb) qs += a.dO[bb * sb + oo];
-    }
-    a.dQp[oo] = a.DG == nullptr ? qs
-                                : qs + a.sl2e * dot_strided(a.DG + (int64_t)(j * m + q) * dk, 1,
-                                                            a.Wk + (int64_t)f * dk, 1, dk);
-  }
-}
-// stage 1 + riders: rows [0, J.n) of blockIdx.y are the post-1 jobs, then (when present) the
-// classifier weight gradient (one workgroup per class) and the layer-1 fc_v gradient
-__device__ __forceinline__ void post1_body(const Mab0PostJob& a, int blk);
-__global__ __launch_bounds__(256) void k_terminal1(const Mab0PostJobs jobs, const ClsWgradArgs c,
-                                                   int has_cls, const SmallWgradArgs w,
-                                                   int has_sw, const SlabSumJobs late) {
-  const int y = blockIdx.y;
-  if (y < jobs.n) {
-    post1_body(jobs.j[y], blockIdx.x);
-  } else if (has_cls && y == jobs.n) {
-    if ((int)blockIdx.x < c.C)
-      cls_wgrad_body(c.dlogits, c.P, c.lossv, c.corrv, c.B, c.d, c.C, c.dWc, c.dbc, c.loss_out,
-                     c.stats, blockIdx.x);
-  } else if (has_sw && y == jobs.n + has_cls) {
-    if ((int64_t)blockIdx.x * w.rows_per_wg < w.M)
-      wgrad_small_body<float>(w.G, w.X, w.M, w.dq, w.rows_per_wg, w.x_head_stride, w.dW, w.db,
-                              blockIdx.x, w.slab);
-  } else {
-    // rider rows: the weight-gradient slabs of this step, added in a fixed order
-    __shared__ float4 red[4 * 64];
-    slab_sum_body(late.j[y - jobs.n - has_cls - has_sw], blockIdx.x, threadIdx.x, red);
-  }
-}
-// stage 2: dWq += dQp^T I ; dbq += colsum(dQp) ; dI += dQp Wq
-__global__ __launch_bounds__(256) void k_mab0_post2(const Mab0PostJobs jobs, const SlabSumJobs late) {
-  if ((int)blockIdx.y >= jobs.n) {       // rider rows (partials written by k_terminal1 itself)
-    __shared__ float4 red[4 * 64];
-    slab_sum_body(late.j[blockIdx.y - jobs.n], blockIdx.x, threadIdx.x, red);
-    return;
-  }
-  const Mab0PostJob a = jobs.j[blockIdx.y];
-  const int m = a.m, d = a.d, dq = a.dq;
-  const int o = blockIdx.x * 256 + threadIdx.x;
-  const int n1 = d * dq, n2 = n1 + d, n3 = n2 + (a.dI != nullptr ? m * dq : 0);
-  if (o < n1) {
-    const int f = o / dq, c = o - f * dq;
-    a.dWq[o] += dot_strided(a.dQp + f, d, a.I + c, dq, m);
-  } else if (o < n2) {
-    const int f = o - n1;
-    float acc = 0.f;
-    for (int q = 0; q < m; ++q) acc += a.dQp[q * d + f];
-    a.dbq[f] += acc;
-  } else if (o < n3) {
-    const int oo = o - n2;
-    const int q = oo / dq, c = oo - q * dq;
-    a.dI[oo] += dot_strided(a.dQp + (int64_t)q * d, 1, a.Wq + c, dq, d);
-  }
-}
-
 }  // namespace
-namespace {
-// Everything a set needs between its attention forward and its attention backward.  The stages
-// hand over through global memory written by this very workgroup (H = pooled features, Z, T,
-// LSE, dP): a workgroup barrier makes those stores visible to the next stage.
-__global__ __launch_bounds__(256) void k_pma_head(const PmaHeadArgs a) {
-  const int b = blockIdx.x;
-  mab0_epi_body<1>(a.Tp, a.Mp, a.Lp, a.S, a.T, a.LSE, a.Qp, a.WvT, a.bv, a.WoT, a.bo, a.m, a.d,
-                   a.dk, a.h, a.H, a.Osave, a.Zsave, b);
-  __syncthreads();
-  cls_fwd_bwd_body(a.H, a.Wc, a.bc, a.labels, a.B, a.d, a.C, a.grad_scale, a.logits, a.dlogits,
-                   a.dP, a.lossv, a.corrv, b);
-  __syncthreads();
-  mab0_epi_bwd_body<1>(a.dP, a.Zsave, a.T, a.LSE, a.Wo, a.Wv, a.m, a.d, a.dk, a.h, a.Rp, a.dZ,
-                       a.dO, a.Th, a.dTf, a.dTb, a.dTt, a.Delta, a.LSEp, a.B, a.zero_ptr,
-                       a.zero_n, b);
-}
-
-// The same chain for the shape the engine actually runs it on (one seed, d = dk = 128, four heads,
-// C <= 64): every weight element a thread will need - 64 + 64 + 32 + 32 + 64 + 64 floats over the
-// six GEMV stages - is requested before the first stage, and the stages hand over through LDS
-// instead of through the global arrays they also write.  The generic bodies above spend the
-// launch in ~25 dependent L2 round trips (16 loads in flight each, one batch after the other,
-// plus the re-reads of H / Z / T / dP between stages): 25 us for ~2 us of arithmetic.  Same
-// products in the same order; Delta is reduced by shuffles instead of LDS float atomics.
-__global__ __launch_bounds__(256) void k_pma_head1(const PmaHeadArgs a) {
-  constexpr int D = 128, DK = 128, DH = 32, R = 4;        // (four heads)
-  __shared__ float sT[R * DK], sO[D], sP[D], sZ[D], sL[64], sdZ[D], sdO[D], sdP[D], part[D];
-  __shared__ float sLSE[R], sDl[2 * R], red[2];
-  __shared__ int ramax;
-  const int b = blockIdx.x, tid = threadIdx.x, f = tid & 127, half = tid >> 7;
-  const int S = a.S, C = a.C;
-
-  // ---- stage 0 loads first (they are needed first), then all the weights ----
-  float mp[2][8], lp[2][8], tp[2][8];
-  const int SS = S < 8 ? S : 8;
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int i = tid + 256 * e, r = i >> 7, c = i & 127;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const bool on = q < SS;
-      const int64_t o = ((int64_t)b * S + (on ? q : 0)) * R + r;
-      mp[e][q] = on ? a.Mp[o] : -INFINITY;
-      lp[e][q] = on ? a.Lp[o] : 0.f;
-      tp[e][q] = on ? a.Tp[o * DK + c] : 0.f;
-    }
-  }
-  const float qb = a.Qp[f] + a.bv[f], bo_f = a.bo[f];
-  float w1[64], w2[64], w5[64], w6[2][DH], w4[32];
-  float4 w3[8];
-#pragma unroll
-  for (int c = 0; c < 64; ++c) w1[c] = a.WvT[(int64_t)(half * 64 + c) * D + f];
-#pragma unroll
-  for (int c = 0; c < 64; ++c) w2[c] = a.WoT[(int64_t)(half * 64 + c) * D + f];
-  const int c3 = tid >> 2, part3 = tid & 3;
-#pragma unroll
-  for (int u = 0; u < 8; ++u)
-    w3[u] = *reinterpret_cast<const float4*>(a.Wc + (int64_t)(c3 < C ? c3 : 0) * D + part3 * 32 + 4 * u);
-  const float bc3 = a.bc[c3 < C ? c3 : 0];
-  const int c0 = half * (C / 2), c1 = half ? C : C / 2;
-#pragma unroll
-  for (int u = 0; u < 32; ++u) w4[u] = a.Wc[(int64_t)(c0 + u < c1 ? c0 + u : c0) * D + f];
-#pragma unroll
-  for (int k = 0; k < 64; ++k) w5[k] = a.Wo[(int64_t)(half * 64 + k) * D + f];
-#pragma unroll
-  for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-    for (int k = 0; k < DH; ++k)
-      w6[jj][k] = a.Wv[(int64_t)((2 * half + jj) * DH + k) * DK + f];
-  const int64_t y = a.labels[b];
-  if (a.zero_ptr != nullptr)
-    for (int i = b * 256 + tid; i < a.zero_n; i += gridDim.x * 256) a.zero_ptr[i] = 0.f;
-
-  // ---- forward epilogue: merge the S point-range partials (mab0_epi_body) ----
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int i = tid + 256 * e, r = i >> 7, c = i & 127;
-    float M = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) M = fmaxf(M, mp[e][q]);
-    float L = 0.f, t = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      if (q >= SS || mp[e][q] == -INFINITY) continue;
-      const float fs = exp2f(mp[e][q] - M);
-      L += fs * lp[e][q];
-      t += fs * tp[e][q];
-    }
-    const float v = t / L;
-    sT[i] = v;
-    a.T[(int64_t)b * R * DK + i] = v;
-    if (c == 0) {
-      const float lse = M + log2f(L);
-      a.LSE[(int64_t)b * R + r] = lse;
-      sLSE[r] = lse;
-    }
-  }
-  __syncthreads();
-  // O = Qp + T_h Wv_h^T + bv ; each half of the workgroup takes half of the contraction
-  {
-    const int j = f / DH;
-    float a1 = half == 0 ? qb : 0.f;
-#pragma unroll
-    for (int c = 0; c < 64; ++c) a1 = fmaf(sT[j * DK + half * 64 + c], w1[c], a1);
-    if (half == 1) part[f] = a1;
-    __syncthreads();
-    if (half == 0) sO[f] = a1 + part[f];
-    __syncthreads();
-  }
-  {
-    float z1 = half == 0 ? bo_f : 0.f;
-#pragma unroll
-    for (int c = 0; c < 64; ++c) z1 = fmaf(sO[half * 64 + c], w2[c], z1);
-    if (half == 1) part[f] = z1;
-    __syncthreads();
-    if (half == 0) {
-      z1 += part[f];
-      const float o1 = sO[f], hv = o1 + fmaxf(z1, 0.f);
-      const int64_t o = (int64_t)b * D + f;
-      a.H[o] = hv;
-      a.Osave[o] = o1;
-      a.Zsave[o] = z1;
-      sP[f] = hv;
-      sZ[f] = z1;
-    }
-    __syncthreads();
-  }
-  // ---- classifier + cross-entropy, forward and backward (cls_fwd_bwd_body) ----
-  {
-    float acc = 0.f;
-    if (c3 < C) {
-      const float* x = sP + part3 * 32;
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        acc += x[4 * u] * w3[u].x + x[4 * u + 1] * w3[u].y + x[4 * u + 2] * w3[u].z +
-               x[4 * u + 3] * w3[u].w;
-    }
-    acc += __shfl_xor(acc, 1, 64);
-    acc += __shfl_xor(acc, 2, 64);
-    if (c3 < C && part3 == 0) {
-      acc += bc3;
-      sL[c3] = acc;
-      a.logits[(int64_t)b * C + c3] = acc;
-    }
-  }
-  __syncthreads();
-  if (tid < 64) {
-    float m = -INFINITY;
-    int am = 0x7fffffff;
-    for (int j = tid; j < C; j += 64)
-      if (sL[j] > m) { m = sL[j]; am = j; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float om = __shfl_xor(m, o, 64);
-      const int oa = __shfl_xor(am, o, 64);
-      if (om > m || (om == m && oa < am)) { m = om; am = oa; }
-    }
-    float sm = 0.f;
-    for (int j = tid; j < C; j += 64) sm += expf(sL[j] - m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sm += __shfl_xor(sm, o, 64);
-    if (tid == 0) { red[0] = m; red[1] = sm; ramax = am; }
-  }
-  __syncthreads();
-  {
-    const float m = red[0], sm = red[1];
-    const float gs = a.grad_scale / (float)a.B;
-    if (tid == 0) {
-      a.lossv[b] = m + logf(sm) - sL[y];
-      a.corrv[b] = ramax == (int)y ? 1.f : 0.f;
-    }
-    __syncthreads();
-    for (int c = tid; c < C; c += 256) {
-      const float g = (expf(sL[c] - m) / sm - (c == y ? 1.f : 0.f)) * gs;
-      sL[c] = g;
-      a.dlogits[(int64_t)b * C + c] = g;
-    }
-    __syncthreads();
-    float acc = 0.f;
-#pragma unroll
-    for (int u = 0; u < 32; ++u)
-      if (c0 + u < c1) acc = fmaf(sL[c0 + u], w4[u], acc);
-    if (half == 1) part[f] = acc;
-    __syncthreads();
-    if (half == 0) {
-      const float dp = acc + part[f];
-      a.dP[(int64_t)b * D + f] = dp;
-      sdP[f] = dp;
-    }
-    __syncthreads();
-  }
-  // ---- backward epilogue (mab0_epi_bwd_body): dZ, dO = dP + dZ Wo, dT_h = dO_h Wv_h, Delta ----
-  if (tid < D) {
-    const float v = sZ[tid] > 0.f ? sdP[tid] : 0.f;
-    sdZ[tid] = v;
-    a.dZ[(int64_t)b * D + tid] = v;
-  }
-  __syncthreads();
-  {
-    float a5 = half == 0 ? sdP[f] : 0.f;
-#pragma unroll
-    for (int k = 0; k < 64; ++k) a5 = fmaf(sdZ[half * 64 + k], w5[k], a5);
-    if (half == 1) part[f] = a5;
-    __syncthreads();
-    if (half == 0) {
-      a5 += part[f];
-      sdO[f] = a5;
-      a.dO[(int64_t)b * D + f] = a5;
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int jj = 0; jj < 2; ++jj) {
-    const int j = 2 * half + jj;                  // head = score row r (one seed)
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < DH; ++k) acc = fmaf(sdO[j * DH + k], w6[jj][k], acc);
-    const float tv = sT[j * DK + f];
-    a.Th[((int64_t)j * a.B + b) * DK + f] = tv;
-    a.dTb[((int64_t)b * a.Rp + j) * DK + f] = (__bf16)acc;
-    int pos = 0;
-#pragma unroll
-    for (int p = 0; p < 32; ++p)
-      if (perm32(p) == j) pos = p;
-    a.dTt[((int64_t)b * DK + f) * a.Rp + pos] = (__bf16)acc;
-    // Delta[r] = sum over the 128 columns: the wave's 64 by shuffles, the two waves through LDS
-    float dl = acc * tv;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) dl += __shfl_xor(dl, o, 64);
-    if ((tid & 63) == 0) sDl[2 * j + ((tid >> 6) & 1)] = dl;
-  }
-  __syncthreads();
-  for (int r = tid; r < a.Rp; r += 256) {
-    a.Delta[(int64_t)b * a.Rp + r] = r < R ? sDl[2 * r] + sDl[2 * r + 1] : 0.f;
-    a.LSEp[(int64_t)b * a.Rp + r] = r < R ? sLSE[r] : 1.0e30f;
-  }
-  for (int o = tid; o < (a.Rp - R) * DK; o += 256) {       // padding rows / columns of the images
-    const int r = R + o / DK, cc = o % DK;
-    a.dTb[((int64_t)b * a.Rp + r) * DK + cc] = (__bf16)0.f;
-    const int rb32 = r & ~31, ro = r & 31;
-    int pos = 0;
-#pragma unroll
-    for (int p = 0; p < 32; ++p)
-      if (perm32(p) == ro) pos = p;
-    a.dTt[((int64_t)b * DK + cc) * a.Rp + rb32 + pos] = (__bf16)0.f;
-  }
-}
-}  // namespace
-
-int pma_head_args(const pca_mab_shape& s, const pca_mab_params& p, void* saved, void* ws_bwd,
-                  float* P, const float* Wc, const float* bc, const int64_t* labels, int C,
-                  float grad_scale, float* logits, float* dlogits, float* dP, float* dWc,
-                  float* dbc, float* loss_out, float* stats, float* cls_ws, BwdDefer* defer,
-                  PmaHeadArgs* out) {
-  PCA_REQUIRE(s.nq == 1 && s.dk > 4 && defer != nullptr, "pma_head: needs the fused PMA (k = 1)");
-  Mab0Saved v;
-  mab0_carve_saved(s, &v, saved);
-  Mab0BwdWs w;
-  mab0_carve_bwd_ws(s, &w, ws_bwd);
-  const int d = s.d, m = s.nq, h = s.h, dk = s.dk, R = h * m, Rp = (int)cdiv(R, 32) * 32;
-  PmaHeadArgs a{};
-  a.Tp = v.Tp; a.Mp = v.Mp; a.Lp = v.Lp; a.S = mab0_splits(s); a.T = v.T; a.LSE = v.LSE;
-  a.Qp = v.Qp; a.WvT = v.WvT; a.bv = p.bv; a.WoT = v.WoT; a.bo = p.bo;
-  a.m = m; a.d = d; a.dk = dk; a.h = h; a.H = P; a.Osave = v.O; a.Zsave = v.Z;
-  a.Wc = Wc; a.bc = bc; a.labels = labels; a.B = s.B; a.C = C; a.grad_scale = grad_scale;
-  a.logits = logits; a.dlogits = dlogits; a.dP = dP; a.lossv = cls_ws; a.corrv = cls_ws + s.B;
-  a.Wo = p.wo; a.Wv = p.wv; a.Rp = Rp; a.dZ = w.dZ; a.dO = w.dO; a.Th = w.Th; a.dTf = nullptr;
-  a.dTb = w.dTb; a.dTt = w.dTt; a.Delta = w.Delta; a.LSEp = w.LSEp;
-  a.zero_ptr = w.DG; a.zero_n = Rp * dk;
-  *out = a;
-  defer->cls = ClsWgradArgs{dlogits, P, a.lossv, a.corrv, s.B, d, C, dWc, dbc, loss_out, stats};
-  defer->has_cls = 1;
-  return PCA_OK;
-}
-
-int pma_head_launch(const PmaHeadArgs& a, hipStream_t st) {
-  const int d = a.d, m = a.m, h = a.h, dk = a.dk, R = h * m, Rp = a.Rp, C = a.C;
-  size_t lds = ((size_t)R * dk + (size_t)m * d) * sizeof(float);
-  const size_t l2 = (size_t)(d + C) * sizeof(float);
-  const size_t l3 = (2 * (size_t)m * d + (size_t)Rp + (size_t)d) * sizeof(float);
-  lds = lds > l2 ? lds : l2;
-  lds = lds > l3 ? lds : l3;
-  // (the generic k_pma_head serves the shapes k_pma_head1 does not)
-  if (d == 128 && dk == 128 && h == 4 && m == 1 && C <= 64 && a.S >= 1 && a.S <= 8)
-    hipLaunchKernelGGL(k_pma_head1, dim3(a.B), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL(k_pma_head, dim3(a.B), dim3(256), lds, st, a);
-  return check_launch("k_pma_head");
-}
-
-int terminal_launch(const BwdDefer& D, hipStream_t st, const SlabSumJobs* late_in) {
-  SlabSumJobs late{};
-  if (late_in != nullptr) late = *late_in;
-  if (!D.has_cls && !D.has_sw && late.n == 0) return mab0_post_launch(D.posts, st);
-  const Mab0PostJobs& J = D.posts;
-  int n1 = 0;
-  for (int i = 0; i < J.n; ++i) {
-    const int e1 = J.j[i].d * J.j[i].dk + J.j[i].m * J.j[i].d;
-    n1 = e1 > n1 ? e1 : n1;
-  }
-  int gx = (int)cdiv(n1, 256);
-  if (D.has_cls && D.cls.C > gx) gx = D.cls.C;
-  if (D.has_sw) {
-    const int gs = (int)cdiv(D.sw.M, D.sw.rows_per_wg);
-    gx = gs > gx ? gs : gx;
-  }
-  for (int i = 0; i < late.n; ++i) {
-    PCA_REQUIRE(slab_sum_job_ok(late.j[i]), "terminal: rider alignment");
-    const int need = (int)cdiv(late.j[i].n, 256);
-    gx = need > gx ? need : gx;
-  }
-  hipLaunchKernelGGL(k_terminal1,
-                     dim3(gx, J.n + (D.has_cls ? 1 : 0) + (D.has_sw ? 1 : 0) + late.n),
-                     dim3(256), 0, st, J, D.cls, D.has_cls ? 1 : 0, D.sw, D.has_sw ? 1 : 0, late);
-  PCA_TRY(check_launch("k_terminal1"));
-  // the layer-1 fc_v partials k_terminal1 wrote (slab mode) are summed by rider rows of post 2
-  SlabSumJobs late2{};
-  if (D.has_sw && D.sw.slab != nullptr) {
-    const int nwg = (int)cdiv(D.sw.M, D.sw.rows_per_wg), n1 = 128 * D.sw.dq, stride = n1 + 128;
-    late2.j[late2.n++] = SlabSumJob{D.sw.slab, D.sw.dW, nwg, n1, 1, stride};
-    if (D.sw.db != nullptr) late2.j[late2.n++] = SlabSumJob{D.sw.slab + n1, D.sw.db, nwg, 128, 1, stride};
-  }
-  if (J.n == 0) return slab_sum_jobs(late2, st);
-  int n2 = 0;
-  for (int i = 0; i < J.n; ++i) {
-    const Mab0PostJob& a = J.j[i];
-    const int e2 = a.d * a.dq + a.d + (a.dI ? a.m * a.dq : 0);
-    n2 = e2 > n2 ? e2 : n2;
-  }
-  for (int i = 0; i < late2.n; ++i) n2 = late2.j[i].n > n2 ? late2.j[i].n : n2;
-  hipLaunchKernelGGL(k_mab0_post2, dim3((unsigned)cdiv(n2, 256), J.n + late2.n), dim3(256), 0, st, J,
-                     late2);
-  return check_launch("k_mab0_post2");
-}
-
-int mab0_post_launch(const Mab0PostJobs& J, hipStream_t st) {
-  if (J.n == 0) return PCA_OK;
-  int n1 = 0, n2 = 0;
-  for (int i = 0; i < J.n; ++i) {
-    const Mab0PostJob& a = J.j[i];
-    const int e1 = a.d * a.dk + a.m * a.d, e2 = a.d * a.dq + a.d + (a.dI ? a.m * a.dq : 0);
-    n1 = e1 > n1 ? e1 : n1;
-    n2 = e2 > n2 ? e2 : n2;
-  }
-  hipLaunchKernelGGL(k_mab0_post1, dim3((unsigned)cdiv(n1, 256), J.n), dim3(256), 0, st, J);
-  PCA_TRY(check_launch("k_mab0_post1"));
-  hipLaunchKernelGGL(k_mab0_post2, dim3((unsigned)cdiv(n2, 256), J.n), dim3(256), 0, st, J,
-                     SlabSumJobs{});
-  return check_launch("k_mab0_post2");
-}
 
 int mab0_bwd_small_launch(const float* X, const float* Gf, const float* dTf, const float* LSE,
                           const float* Delta, int B, int N, int R, int Rp, int dk, float* DG,

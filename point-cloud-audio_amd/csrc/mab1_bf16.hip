@@ -11,8 +11,11 @@
 // fp32 softmax / bias / residual.
 //
 // Roofline unit: per point 2*(2 d^2 + 2 m d) FLOP forward.
-#include "mab1_bf16.hpp"
-#include "d256_bf16.hpp"
+#include "blocks.hpp"
+#include "weight_images.hpp"
+#include "step_ctx.hpp"
+#include "d256.hpp"
+#include "mfma_common.hpp"
 
 #include <math.h>
 

@@ -7,7 +7,8 @@
 // projection, so no head-major copy is ever made.  The learned query of ISAB / PMA
 // (modules.py:52,63 `I.repeat(B,1,1)`) is projected once (q_shared) and broadcast through
 // a zero batch stride.
-#include "mab1_bf16.hpp"
+#include "blocks.hpp"
+#include "weight_images.hpp"
 
 #include <math.h>
 

@@ -282,4 +282,41 @@ __device__ __forceinline__ void commit_points(const float (&v)[16], int cn, int 
   __syncthreads();
 }
 
+// ---- the many-queries kernels' point tiling and the layout of their saved ReLU mask -------------------
+constexpr int M1_TP = 128;     // points per workgroup tile (4 waves x 32)
+constexpr int M1_NB = 2;       // 16-point blocks per wave
+
+// one 32-bit word per lane covers 8 feature tiles (4 bits each)
+template <int D>
+__host__ __device__ __forceinline__ int64_t mab1_mask_index(int b, int tiles_per_set, int tile,
+                                                            int wave, int nb, int w, int lane) {
+  const int64_t pb = ((int64_t)b * tiles_per_set + tile) * (M1_TP / 16) + wave * M1_NB + nb;
+  return (pb * (D / 128) + w) * 64 + lane;
+}
+
+// ---- per-set row GEMM on the VALU --------------------------------------------------------------------
+// acc[q] += sum_c sX[q*ldx + c] * WT[c*ldw + f]   for q < MQ : thread-owned output column f,
+// activations broadcast from LDS, weights read coalesced (consecutive threads = consecutive f)
+template <int MQ>
+__device__ __forceinline__ void col_gemm(const float* sX, int ldx, const float* __restrict__ WT,
+                                         int ldw, int K, int f, float (&acc)[MQ]) {
+  // 16 independent weight loads in flight per thread: these per-set kernels run at one
+  // workgroup per set and are otherwise bound by L2 latency, not bandwidth
+  int c = 0;
+  for (; c + 16 <= K; c += 16) {
+    float w[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) w[u] = WT[(int64_t)(c + u) * ldw + f];
+#pragma unroll
+    for (int u = 0; u < 16; ++u)
+#pragma unroll
+      for (int q = 0; q < MQ; ++q) acc[q] = fmaf(sX[q * ldx + c + u], w[u], acc[q]);
+  }
+  for (; c < K; ++c) {
+    const float w = WT[(int64_t)c * ldw + f];
+#pragma unroll
+    for (int q = 0; q < MQ; ++q) acc[q] = fmaf(sX[q * ldx + c], w, acc[q]);
+  }
+}
+
 }  // namespace pca

@@ -17,7 +17,8 @@
 // the waves through bf16 LDS tiles ([32][256], 16-byte chunks XOR-swizzled by row).
 // (First version: 8 waves x 32 features, a batch loaded and then consumed: 32.1 us per launch at
 //  B = 128; this one: see DESIGN.md 4.5.)
-#include "d256_bf16.hpp"
+#include "d256.hpp"
+#include "mfma_common.hpp"
 
 namespace pca {
 

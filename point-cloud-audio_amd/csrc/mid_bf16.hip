@@ -12,7 +12,8 @@
 // One workgroup per set, wave w = head w.  Each wave needs every weight fragment exactly
 // once, so fragments are read straight from L2 (no LDS staging); activations cross waves
 // through small bf16 LDS images.
-#include "mab1_bf16.hpp"
+#include "blocks.hpp"
+#include "mfma_common.hpp"
 #include "mid_bwd_body.hpp"
 
 #include <math.h>

@@ -7,7 +7,8 @@
 // on the same operands in the same summation order wherever it runs; only the sink of the images
 // differs.  256 threads, wave w = head w; ONE workgroup barrier inside (every thread must call it).
 #pragma once
-#include "mab1_bf16.hpp"
+#include "blocks.hpp"
+#include "mfma_common.hpp"
 
 namespace pca {
 

@@ -1,10 +1,10 @@
 // The three per-set stages around the classifier of the train step, as device functions: the
 // PMA forward epilogue, the classifier + cross-entropy (forward and backward) and the PMA backward
 // epilogue.  Stand-alone they are the kernels k_mab0_epi / k_cls_fwd_bwd / k_mab0_epi_bwd; the
-// engine runs them back to back inside ONE launch (k_pma_head, mab0_bwd_bf16.hip): each is a
+// engine runs them back to back inside ONE launch (k_pma_head, pma_head.hip): each is a
 // chain of dependent L2 round trips for one set, so two launches less is ~10 us of a 0.4 ms step.
 #pragma once
-#include "mab1_bf16.hpp"
+#include "mfma_common.hpp"
 
 #include <math.h>
 

@@ -19,7 +19,7 @@
 //   k_sd_mq      many queries (ISAB mab1): the workgroup projects the set's m keys (Kp, Vp: 2 x 16
 //                KiB of LDS) once, then lane = point: Qp = Wq x + bq, per head 64 scores in
 //                registers, softmax, O_h = Qp_h + P V_h, Z = Wo O + bo, Y = O + relu(Z).
-#include "mab1_bf16.hpp"
+#include "blocks.hpp"
 
 #include <math.h>
 

@@ -3,7 +3,7 @@
 // modules.py:51-53, 62-63 with :19-33 inside; Code/models.py:34-44), each its half of the set's
 // [N, 128] activations resident in LDS.  Declarations shared by set128_fwd.hip and the ST engine.
 #pragma once
-#include "mab1_bf16.hpp"
+#include "bwd_defer.hpp"
 
 namespace pca {
 

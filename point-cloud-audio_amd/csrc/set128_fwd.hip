@@ -30,6 +30,7 @@
 // Roofline unit: MACs_fwd / set = N (3 din d + 7 d^2 + 8 m d + 2 k d) + 6 m d^2 (the
 // PMA epilogue and the classifier run in k_pma_head1); algorithmic bytes 4 N din + 4 (2 N d) per set.
 #include "set128.hpp"
+#include "mfma_common.hpp"
 
 #include <math.h>
 
@@ -474,7 +475,7 @@ __device__ __forceinline__ void mab1_phase(const Set128Layer& L, const Ctx& c, c
 
 // ---------------------------------------------------------------------------------------------
 // The per-set stages between the PMA's attention forward and its attention backward (k_pma_head1,
-// mab0_bwd_bf16.hip, on 1024 threads): PMA epilogue O = Qp + T_h Wv_h^T + bv, P = O + relu(O Wo^T + bo)
+// pma_head.hip, on 1024 threads): PMA epilogue O = Qp + T_h Wv_h^T + bv, P = O + relu(O Wo^T + bo)
 // (modules.py:29-31), classifier + mean cross-entropy forward and backward (Code/models.py:40,
 // Code/settransformer.py:104), and the adjoint of the epilogue: dZ, dO = dP + dZ Wo, dT_h = dO_h Wv_h,
 // Delta = rowdot(dT, T).  Products over the INPUT index take 8 (16) adjacent lanes per output and a

@@ -1,6 +1,6 @@
 // Stand-alone launch of the fixed-order slab sum (slab_sum_body.hpp): out[i] (+)= sum_s slabs[s][i], the
 // replacement of fp32 atomics wherever workgroups reduce into one small tensor.
-#include "d256_bf16.hpp"
+#include "bwd_defer.hpp"
 #include "slab_sum_body.hpp"
 
 namespace pca {

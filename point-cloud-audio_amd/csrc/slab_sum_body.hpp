@@ -4,7 +4,7 @@
 // no launch of its own.  Uses the first 256 threads of the workgroup; EVERY thread of the workgroup
 // must call it (one barrier inside).  `red` = 4 x 64 float4 of LDS.
 #pragma once
-#include "mab1_bf16.hpp"
+#include "bwd_defer.hpp"
 
 namespace pca {
 

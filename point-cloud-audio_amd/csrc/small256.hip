@@ -1,6 +1,7 @@
-// The small kernels of the d = 256 step (map: d256_bf16.hpp): fp32 <-> bf16 conversion, the layer-1
+// The small kernels of the d = 256 step (map: d256.hpp): fp32 <-> bf16 conversion, the layer-1
 // weight gradient (inputs of dq <= 4 columns) and the per-set epilogues of the few-queries block.
-#include "d256_bf16.hpp"
+#include "d256.hpp"
+#include "mfma_common.hpp"
 
 #include <math.h>
 
@@ -249,7 +250,7 @@ __global__ __launch_bounds__(256) void k_epi_small_wv(const float* __restrict__ 
 
 }  // namespace
 
-// ---- launchers (declared in d256_bf16.hpp) ------------------------------------------------
+// ---- launchers (declared in d256.hpp) ------------------------------------------------
 int cvt_f32_bf16(const float* s, __bf16* d, int64_t n, hipStream_t st) {
   hipLaunchKernelGGL(k_cvt_f32_bf16, dim3((unsigned)cdiv(n / 4, 256)), dim3(256), 0, st, s, d,
                      n / 4);

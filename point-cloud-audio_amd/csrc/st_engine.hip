@@ -4,9 +4,12 @@
 // in state_dict order.  No Python, autograd or allocator sits between the kernels, so the
 // caller can capture the call in a hipGraph.
 #include <stdlib.h>
-#include "mab1_bf16.hpp"
+#include "blocks.hpp"
+#include "weight_images.hpp"
+#include "bwd_defer.hpp"
+#include "step_ctx.hpp"
+#include "d256.hpp"
 #include "pack_body.hpp"
-#include "d256_bf16.hpp"
 #include "set128.hpp"
 
 namespace pca {

@@ -1,9 +1,10 @@
 // Terminal reductions that are small enough to share ONE launch at the end of a backward phase
-// (k_terminal1 in mab0_bwd_bf16.hip): the classifier's weight gradient + loss counters and the
+// (k_terminal1 in bwd_defer.hip): the classifier's weight gradient + loss counters and the
 // layer-1 fc_v gradient, next to the shared-query gradients.  The bodies are device functions
 // so that the stand-alone kernels (k_cls_wgrad, k_wgrad_small) stay thin wrappers.
 #pragma once
-#include "mab1_bf16.hpp"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace pca {
 

@@ -2,7 +2,8 @@
 // nn.CrossEntropyLoss (mean) forward+gradient in one launch, and torch.optim.Adam with
 // coupled weight decay as one fused pass over a flat parameter vector.  Also the correct-count
 // tally of the evaluation sweeps (Code/pceval.py:95, (preds.argmax(dim=1) == lbls).sum()).
-#include "mab1_bf16.hpp"
+#include "blocks.hpp"
+#include "bwd_defer.hpp"
 #include "terminal_bodies.hpp"
 #include "pma_head_bodies.hpp"
 

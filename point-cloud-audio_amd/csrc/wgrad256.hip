@@ -1,8 +1,10 @@
-// The [256 x 256] weight gradients of the d = 256 blocks (map: d256_bf16.hpp): dW = G^T A over the B*N
+// The [256 x 256] weight gradients of the d = 256 blocks (map: d256.hpp): dW = G^T A over the B*N
 // (or B*m) rows as per-workgroup fp32 slabs - k_wgrad256_dma (operand tiles by LDS-DMA) or k_wgrad256
 // (register staged: fp32 operands, PCA_WGRAD256_DMA=0) - and k_wgrad256_sum, which adds the slabs of
 // a job into dW / db in a fixed order.  Tile layout: tr_off256 / tr_frag256 (mfma_common.hpp).
-#include "d256_bf16.hpp"
+#include "d256.hpp"
+#include "bwd_defer.hpp"
+#include "mfma_common.hpp"
 #include "slab_sum_body.hpp"
 
 #include <math.h>
@@ -331,7 +333,7 @@ __global__ __launch_bounds__(256) void k_wgrad256_sum(const Wgrad256Jobs jobs, i
 
 }  // namespace
 
-// ---- launchers (declared in d256_bf16.hpp) ------------------------------------------------
+// ---- launchers (declared in d256.hpp) ------------------------------------------------
 // workgroups per job: enough to stream from every CU, few enough that the slab pass (256 KiB per
 // workgroup written + read) stays small against the 1 KiB per row the job reads
 int wgrad256_nwg(int64_t maxM) {

@@ -17,7 +17,7 @@
 #include "pca_common.h"
 
 #include <stdint.h>
-#include "mab1_bf16.hpp"
+#include "blocks.hpp"
 #include "mfma_common.hpp"
 
 namespace pca {

@@ -16,7 +16,8 @@
 //   k_wgrad_reduce   dW += sum of the slabs, db += sum of the column-sum slabs, in a fixed order (8 threads per
 //                    element over contiguous slab ranges, their sums added in range order).
 // The result is bitwise reproducible, and does not depend on how the launch is captured or replayed.
-#include "mab1_bf16.hpp"
+#include "blocks.hpp"
+#include "mfma_common.hpp"
 
 namespace pca {
 
