@@ -1,6 +1,6 @@
 // The end of a backward pass: bwd_defer_flush runs everything the blocks of a step queued in their BwdDefer
-// (bwd_defer.hpp) - the weight-gradient launches (wgrad128.hip, wgrad256.hip) with the due slab sums as
-// riders, then the post stages:
+// (bwd_defer.hpp) - the weight-gradient launch (wgrad128.hip: both d = 128 lists in one; wgrad256.hip) with
+// the due slab sums as riders, then the post stages:
 //
 //   k_mab0_post1 / k_terminal1   dWk and dQp of the shared queries (k_terminal1: the same plus the classifier's
 //                                weight gradient, the layer-1 fc_v gradient and late slab sums as extra rows)
@@ -200,6 +200,9 @@ int mab0_post_launch(const Mab0PostJobs& J, hipStream_t st) {
 bool wgrad_slabs_on() {          // (read per call: a test switches it between two engines)
   return env_not_zero("PCA_WGRAD_SLABS");
 }
+bool wgrad_fold_on() {           // (read per call, like the switch above)
+  return env_not_zero("PCA_WGRAD_FOLD");
+}
 int bwd_defer_flush(BwdDefer& D, hipStream_t st) {
   // The sums the post stages read (D.sums: dG of the few-queries blocks) ride in the first
   // weight-gradient launch as extra workgroup rows.  Slab mode (the default when the caller lent
@@ -212,16 +215,41 @@ int bwd_defer_flush(BwdDefer& D, hipStream_t st) {
   const bool slab_mode = wgrad_slabs_on() && D.slab_ws != nullptr && D.slab_cap > 0;
   SlabSumJobs late{};
   size_t used = 0;          // the two lists' slabs lie back to back
+  double rows = 0, rows_f32 = 0;
+  for (int i = 0; i < D.wg_bf16.n; ++i) rows += (double)D.wg_bf16.j[i].M;
+  for (int i = 0; i < D.wg_f32.n; ++i) rows_f32 += (double)D.wg_f32.j[i].M;
+  // every workgroup costs a 64 KiB slab (16384 atomics without the slabs): aim at ~200
+  // workgroups over all bf16 jobs (512 rows for one B*N-row job, 1024 for three, ...); the fp32
+  // jobs ([B*m] rows) take 128 rows per workgroup.  (Swept before k_wgrad128 kept several tiles in
+  // flight, and kept because the partition fixes the summation order: 1024 beat 512 / 768 and 2048
+  // at 3 x 65536 rows, 128 beat 64 and 256 for the fp32 list.)
+  int rpw = 512 * (int)((rows + 98303.0) / 98304.0);
+  rpw = rpw < 512 ? 512 : (rpw > 1024 ? 1024 : rpw);
+  int rpw_f32 = 128;
+  const size_t cap_bf16 = D.slab_cap * 3 / 4;
+  if (rows > 0 && rows_f32 > 0 && wgrad_fold_on()) {
+    // ONE launch (k_wgrad128_step): the fp32 jobs run beside the bf16 rows (which leave a quarter of
+    // the compute units idle) instead of paying a launch boundary and a ramp of their own: 32 us
+    // against 25 + 9.5.  Same partition, same slabs, same order of the slab sums as the two launches
+    // below: the same bits.
+    WgradJobs bf = D.wg_bf16, f32 = D.wg_f32;
+    ProfScope ps(PCA_K_WGRAD, st, 2.0 * (rows + rows_f32) * 128 * 128,
+                 4.0 * rows * 128 + 8.0 * rows_f32 * 128);
+    WgradSlabs sl{slab_mode ? D.slab_ws : nullptr, cap_bf16, &late, nullptr, 0};
+    PCA_TRY(wgrad128_place(bf, rpw, &sl));
+    used = (sl.used + 255) & ~(size_t)255;
+    WgradSlabs sf{slab_mode ? D.slab_ws + used / sizeof(float) : nullptr, D.slab_cap - used, &late,
+                  nullptr, 0};
+    PCA_TRY(wgrad128_place(f32, rpw_f32, &sf));
+    used += (sf.used + 255) & ~(size_t)255;
+    PCA_TRY(wgrad128_launch_step(bf, rpw, f32, rpw_f32, D.sums, st));
+    ps.end();
+    D.wg_bf16.n = D.wg_f32.n = 0;
+    D.sums.n = 0;
+  }
   if (D.wg_bf16.n > 0) {
-    double rows = 0;
-    for (int i = 0; i < D.wg_bf16.n; ++i) rows += (double)D.wg_bf16.j[i].M;
     ProfScope ps(PCA_K_WGRAD, st, 2.0 * rows * 128 * 128, 4.0 * rows * 128);
-    // every workgroup costs a 64 KiB slab (16384 atomics without the slabs): aim at ~200
-    // workgroups over all jobs (512 rows for one B*N-row job, 1024 for three, ...)
-    // (measured at 3 x 65536 rows: 512 -> 41 us, 768 -> 41, 1024 -> 31, 1536 -> 31, 2048 -> 39)
-    int rpw = 512 * (int)((rows + 98303.0) / 98304.0);
-    rpw = rpw < 512 ? 512 : (rpw > 1024 ? 1024 : rpw);
-    WgradSlabs sl{slab_mode ? D.slab_ws : nullptr, D.slab_cap * 3 / 4, &late, &D.sums, 0};
+    WgradSlabs sl{slab_mode ? D.slab_ws : nullptr, cap_bf16, &late, &D.sums, 0};
     PCA_TRY(wgrad128_launch(D.wg_bf16, true, true, rpw, st, &sl));
     used = (sl.used + 255) & ~(size_t)255;
     ps.end();
@@ -229,10 +257,9 @@ int bwd_defer_flush(BwdDefer& D, hipStream_t st) {
     D.sums.n = 0;
   }
   if (D.wg_f32.n > 0) {
-    // 64: 18.7 us, 128: 14.2, 256: 15.3
     WgradSlabs sl{slab_mode ? D.slab_ws + used / sizeof(float) : nullptr, D.slab_cap - used, &late,
                   &D.sums, 0};
-    PCA_TRY(wgrad128_launch(D.wg_f32, false, false, 128, st, &sl));
+    PCA_TRY(wgrad128_launch(D.wg_f32, false, false, rpw_f32, st, &sl));
     used += (sl.used + 255) & ~(size_t)255;
     D.wg_f32.n = 0;
     D.sums.n = 0;

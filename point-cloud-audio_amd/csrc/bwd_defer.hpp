@@ -57,6 +57,13 @@ struct WgradSlabs {          // optional slab mode of wgrad128_launch
 // g_bf16 / a_bf16: element type of every job's G / A (bf16 or fp32)
 int wgrad128_launch(const WgradJobs& jobs, bool g_bf16, bool a_bf16, int rows_per_wg,
                     hipStream_t st, WgradSlabs* slabs = nullptr);
+// The two halves of wgrad128_launch for a caller that puts two lists into one launch: wgrad128_place
+// gives every job of a list its slabs (slab mode; rows_per_wg doubles until they fit `slabs->cap`) and
+// appends their sum jobs; wgrad128_launch_step runs a placed bf16 list (G, A bf16) and a placed fp32
+// list, each with its own rows per workgroup (>= 128), and the riders as ONE launch (k_wgrad128_step).
+int wgrad128_place(WgradJobs& jobs, int& rows_per_wg, WgradSlabs* slabs);
+int wgrad128_launch_step(const WgradJobs& bf16_jobs, int rows_per_wg_bf16, const WgradJobs& f32_jobs,
+                         int rows_per_wg_f32, const SlabSumJobs& riders, hipStream_t st);
 
 // ---- the d = 256 job (wgrad256.hip; launchers in d256.hpp) ------------------
 // dW[256 x 256] += G^T A, db[256] += colsum(G) (nullable); G, A bf16 [M][256]
@@ -111,8 +118,8 @@ int mab0_post_launch(const Mab0PostJobs& J, hipStream_t st);
 // ---- what a step collects, and its flush (bwd_defer.hip) ------------------
 // Terminal reductions of a backward pass (only the optimiser / the all-reduce reads their
 // results): a caller that runs several blocks collects them and flushes ONCE at the end of the
-// phase - one bf16 and one fp32 weight-gradient launch (job tables) and one pair of post
-// launches instead of one set per block.  Their operands live in per-block workspaces that
+// phase - one weight-gradient launch over the bf16 and the fp32 job table (PCA_WGRAD_FOLD=0: one
+// launch each) and one pair of post launches instead of one set per block.  Their operands live in per-block workspaces that
 // stay untouched until then.
 struct BwdDefer {
   SlabSumJobs sums;       // partial sums the post stages read: run before them
@@ -126,8 +133,8 @@ struct BwdDefer {
   float* slab_ws;         // room for the weight-gradient partials of the two deferred lists
   size_t slab_cap;        // (bytes; null / 0: those reductions use fp32 atomics)
   Mab0PostJobs posts;
-  WgradJobs wg_bf16;      // G, A bf16, M = B*N rows   (512 rows per workgroup)
-  WgradJobs wg_f32;       // G, A fp32, M = B*m rows   (64 rows per workgroup)
+  WgradJobs wg_bf16;      // G, A bf16, M = B*N rows   (512 ... 1024 rows per workgroup: bwd_defer_flush)
+  WgradJobs wg_f32;       // G, A fp32, M = B*m rows   (128 rows per workgroup)
   // classifier weight gradient + loss counters, layer-1 fc_v gradient: they ride in the first
   // post launch (k_terminal1) as extra job rows
   ClsWgradArgs cls;
@@ -140,6 +147,7 @@ int terminal_launch(const BwdDefer& D, hipStream_t st, const SlabSumJobs* late =
 int wgrad256_flush_deferred(BwdDefer& D, hipStream_t st);       // d256_host.hip
 bool wgrad_slabs_on();       // reductions of the fused d = 128 path as slabs + fixed-order sums
                              // (PCA_WGRAD_SLABS=0: fp32 atomics)
+bool wgrad_fold_on();        // the two deferred d = 128 lists in one launch (PCA_WGRAD_FOLD=0: two)
 // launch `jobs` now, or append them to the matching list of `defer`
 int wgrad128_defer(BwdDefer* defer, const WgradJobs& jobs, bool bf16, int rows_per_wg,
                    hipStream_t st);

@@ -5,11 +5,13 @@
 //                  ds_read_tr16_b64 (hardware transpose); the result leaves as a per-workgroup slab summed in
 //                  a fixed order afterwards, or as fp32 atomics; column sums of G (bias gradients) ride along,
 //                  and so do slab sums that are due now (rider rows).
+//   k_wgrad128_step  the same body over the two deferred lists of a step (bf16 and fp32 operands) in one launch.
 //   k_wgrad_small  layer 1: dW[128 x dq] += G^T.X with dq <= 4 (body: terminal_bodies.hpp).
 #include "bwd_defer.hpp"
 #include "mfma_common.hpp"
 #include "terminal_bodies.hpp"
 #include "slab_sum_body.hpp"
+#include <type_traits>
 
 namespace pca {
 
@@ -19,38 +21,62 @@ namespace {
 // dW[DG x DA] += G[rows, DG]^T . A[rows, DA]  (+ db[DG] += column sums of G)
 // ---------------------------------------------------------------------------------
 
-__device__ __forceinline__ bf16x8 load8(const __bf16* p) {
-  return *reinterpret_cast<const bf16x8*>(p);
+// eight consecutive elements of an operand row as they were loaded: converted to bf16 only when the
+// tile goes to LDS, so that a fetch is requests and nothing else and stays in flight until then
+template <typename T> struct Raw8;
+template <> struct Raw8<__bf16> { bf16x8 v; };
+template <> struct Raw8<float> { float4 lo, hi; };
+__device__ __forceinline__ void load_raw(Raw8<__bf16>& r, const __bf16* p) {
+  r.v = *reinterpret_cast<const bf16x8*>(p);
 }
-__device__ __forceinline__ bf16x8 load8(const float* p) {
-  const float4 lo = reinterpret_cast<const float4*>(p)[0], hi = reinterpret_cast<const float4*>(p)[1];
+__device__ __forceinline__ void load_raw(Raw8<float>& r, const float* p) {
+  r.lo = reinterpret_cast<const float4*>(p)[0];
+  r.hi = reinterpret_cast<const float4*>(p)[1];
+}
+__device__ __forceinline__ void zero_raw(Raw8<__bf16>& r) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) r.v[k] = (__bf16)0.f;
+}
+__device__ __forceinline__ void zero_raw(Raw8<float>& r) {
+  r.lo = float4{0.f, 0.f, 0.f, 0.f};
+  r.hi = float4{0.f, 0.f, 0.f, 0.f};
+}
+__device__ __forceinline__ bf16x8 to_bf16(const Raw8<__bf16>& r) { return r.v; }
+__device__ __forceinline__ bf16x8 to_bf16(const Raw8<float>& r) {
   bf16x8 v;
-  v[0] = (__bf16)lo.x; v[1] = (__bf16)lo.y; v[2] = (__bf16)lo.z; v[3] = (__bf16)lo.w;
-  v[4] = (__bf16)hi.x; v[5] = (__bf16)hi.y; v[6] = (__bf16)hi.z; v[7] = (__bf16)hi.w;
+  v[0] = (__bf16)r.lo.x; v[1] = (__bf16)r.lo.y; v[2] = (__bf16)r.lo.z; v[3] = (__bf16)r.lo.w;
+  v[4] = (__bf16)r.hi.x; v[5] = (__bf16)r.hi.y; v[6] = (__bf16)r.hi.z; v[7] = (__bf16)r.hi.w;
   return v;
 }
+// one thread's share of a fetched 32-row tile pair: two 8-element chunks of G and of A, and the ReLU
+// mask words of the G chunks (job.mask)
+template <typename GT, typename AT>
+struct WgradStage {
+  Raw8<GT> g[2];
+  Raw8<AT> a[2];
+  uint32_t mk[2][2];
+};
 
-// Software-pipelined: the next 32-row tile is fetched into registers while the current one is
-// consumed from LDS; two LDS buffers -> one barrier per tile.  blockIdx.y selects the job.
+// One job's row range [blockIdx.x * rows_per_wg, ...) of dW += G^T.A (the body of k_wgrad128 and of the
+// job rows of k_wgrad128_step).  `lds`: 64 KiB - 2 x 2 staging tiles per group during the loop, the fp32
+// [128][128] result afterwards.
+// Software-pipelined: DEPTH 32-row tile pairs per group are in flight as loads into register sets that
+// rotate (unrolled by DEPTH: the sets are named statically) while the current one is consumed from
+// LDS; two LDS buffers -> one barrier per tile.  A tile's wait is the counted one the compiler derives
+// from the program order of the loads (the DEPTH - 1 later tiles stay in flight across the barrier),
+// which is why the steady loop below holds no conditional load: steps whose tiles lie wholly inside
+// the range for every group fetch unguarded (one uniform test per tile), and only the last steps of a
+// range and a ragged last tile go through the guarded fetch with its zero fill.
 // NG row groups of four waves each (NG = 2 for the long B*N-row jobs: twice the loads in flight
-// per CU; the kernel runs on at most half the CUs because every workgroup costs 16384 atomics):
-// group q takes the 32-row tiles q, q + NG, ...; the groups' [128][128] blocks are summed in LDS.
-template <typename GT, typename AT, int NG>
-__global__ __launch_bounds__(256 * NG) void k_wgrad128(const WgradJobs jobs, int rows_per_wg,
-                                                       const SlabSumJobs riders) {
+// per CU): group q takes the 32-row tiles q, q + NG, ...; the groups' [128][128] blocks are summed in
+// LDS.
+template <typename GT, typename AT, int NG, int DEPTH>
+__device__ __forceinline__ void wgrad128_body(const WgradJob& job, int rows_per_wg, char* lds) {
   constexpr int D = 128, NT = 256 * NG;
-  // 64 KiB: 2 x 2 staging tiles per group during the loop, the fp32 [128][128] result afterwards
-  __shared__ __attribute__((aligned(16))) char lds[4 * 32 * 256 * 2];
-  if ((int)blockIdx.y >= jobs.n) {          // rider rows: partial sums that are due now
-    slab_sum_body(riders.j[blockIdx.y - jobs.n], blockIdx.x, threadIdx.x,
-                  reinterpret_cast<float4*>(lds));
-    return;
-  }
   const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) & 3, grp = tid >> 8;
   const int gtid = tid & 255;
   char (*sG)[32 * 256] = reinterpret_cast<char (*)[32 * 256]>(lds + grp * (4 * 32 * 256));
   char (*sA)[32 * 256] = reinterpret_cast<char (*)[32 * 256]>(lds + grp * (4 * 32 * 256) + 2 * 32 * 256);
-  const WgradJob job = jobs.j[blockIdx.y];
   const GT* __restrict__ G = reinterpret_cast<const GT*>(job.G);
   const AT* __restrict__ A = reinterpret_cast<const AT*>(job.A);
   const int64_t M = job.M;
@@ -58,6 +84,10 @@ __global__ __launch_bounds__(256 * NG) void k_wgrad128(const WgradJobs jobs, int
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_wg;
   if (r0 >= M) return;
   const int64_t r1 = (r0 + rows_per_wg < M) ? r0 + rows_per_wg : M;
+  // steps (uniform over the groups: a group whose tile lies beyond r1 multiplies zeros), and how many
+  // of them have every group's tile wholly inside [r0, r1)
+  const int nrows = (int)(r1 - r0);
+  const int nt = (nrows + 32 * NG - 1) / (32 * NG), nfull = nrows / (32 * NG);
   // wave w owns the 64 x 64 output block (G features 64*(w>>1).., A features 64*(w&1)..):
   // 4 + 4 transposed fragments feed 16 MFMAs per 32-row tile
   const int gt0 = 4 * (wave >> 1), at0 = 4 * (wave & 1);
@@ -68,67 +98,118 @@ __global__ __launch_bounds__(256 * NG) void k_wgrad128(const WgradJobs jobs, int
     for (int t = 0; t < 4; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
   float bs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // column sums of G, columns 8*(tid&15)..
 
-  bf16x8 vg[2], va[2];
-  uint32_t mk[2][2] = {{~0u, ~0u}, {~0u, ~0u}};       // ReLU mask words of the fetched chunks (job.mask)
-  auto fetch = [&](int64_t base) {          // rows at and beyond r1 read as zeros
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int c = gtid + e * 256;
-      const int row = c >> 4, ch = c & 15;
-      if (base + row < r1) {          // (guarded on purpose: the unconditional form measured +18 %)
-        vg[e] = load8(G + (base + row) * D + ch * 8);
-        va[e] = load8(A + (base + row) * D + ch * 8);
-        if (job.mask != nullptr) {
-          // features 8 ch .. 8 ch + 7 of row R: two nibbles (bit 4 t + e of lane (r, g) <-> feature
-          // 16 t + 4 g + e, t = ch / 2) of the words of lanes g0 = 2 (ch & 1) and g0 + 1.  Only
-          // requested here; applied when the tile goes to LDS (the loads stay in flight meanwhile)
-          const int64_t R = base + row;
-          const uint32_t* mw = job.mask + (R >> 4) * 64 + (R & 15) + 32 * (ch & 1);
-          mk[e][0] = mw[0];
-          mk[e][1] = mw[16];
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { vg[e][k] = (__bf16)0.f; va[e][k] = (__bf16)0.f; }
+  // the loop, once per kind of job (with / without mask words: a load that only one kind issues
+  // would make the other kind's counted waits count it too)
+  auto run = [&](auto has_mask) {
+    constexpr bool MASK = decltype(has_mask)::value;
+    using Stage = WgradStage<GT, AT>;
+    // features 8 ch .. 8 ch + 7 of row R: two nibbles (bit 4 t + e of lane (r, g) <-> feature
+    // 16 t + 4 g + e, t = ch / 2) of the words of lanes g0 = 2 (ch & 1) and g0 + 1.  Only
+    // requested with the tile; applied when the tile goes to LDS (the loads stay in flight meanwhile)
+    auto fetch_row = [&](Stage& s, int e, int64_t R, int ch) {
+      load_raw(s.g[e], G + R * D + ch * 8);
+      load_raw(s.a[e], A + R * D + ch * 8);
+      if (MASK) {
+        const uint32_t* mw = job.mask + (R >> 4) * 64 + (R & 15) + 32 * (ch & 1);
+        s.mk[e][0] = mw[0];
+        s.mk[e][1] = mw[16];
       }
+    };
+    auto fetch_full = [&](Stage& s, int t) {          // step t < nfull: every row exists
+      const int64_t base = r0 + 32 * ((int64_t)t * NG + grp);
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int c = gtid + e * 256;
+        fetch_row(s, e, base + (c >> 4), c & 15);
+      }
+    };
+    auto fetch_any = [&](Stage& s, int t) {           // rows at and beyond r1 read as zeros
+      if (t < nfull) {
+        fetch_full(s, t);
+      } else if (t < nt) {
+        const int64_t base = r0 + 32 * ((int64_t)t * NG + grp);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const int c = gtid + e * 256;
+          if (base + (c >> 4) < r1) {
+            fetch_row(s, e, base + (c >> 4), c & 15);
+          } else {
+            zero_raw(s.g[e]);
+            zero_raw(s.a[e]);
+          }
+        }
+      }
+    };
+    int buf = 0;
+    // step t: set s (tile t) goes to LDS, then takes the loads of tile t + DEPTH
+    auto step = [&](Stage& s, int t, auto full) {
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int c = gtid + e * 256;
+        const int row = c >> 4, ch = c & 15;
+        bf16x8 vg = to_bf16(s.g[e]);
+        const bf16x8 va = to_bf16(s.a[e]);
+        if (MASK) {
+          const uint32_t n0 = s.mk[e][0] >> (4 * (ch >> 1)), n1 = s.mk[e][1] >> (4 * (ch >> 1));
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            if (!((n0 >> k) & 1u)) vg[k] = (__bf16)0.f;
+            if (!((n1 >> k) & 1u)) vg[4 + k] = (__bf16)0.f;
+          }
+        }
+        *reinterpret_cast<bf16x8*>(sG[buf] + tr_off(row, ch)) = vg;
+        *reinterpret_cast<bf16x8*>(sA[buf] + tr_off(row, ch)) = va;
+        if (job.db != nullptr) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) bs[k] += (float)vg[k];
+        }
+      }
+      __syncthreads();
+      if (decltype(full)::value) fetch_full(s, t + DEPTH);
+      else fetch_any(s, t + DEPTH);
+      __builtin_amdgcn_sched_barrier(0);      // the requests leave before this step's LDS reads and MFMAs
+      bf16x8 ga[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ga[i] = tr_frag(sG[buf], gt0 + i, lane);
+#pragma unroll
+      for (int tt = 0; tt < 4; ++tt) {
+        const bf16x8 ab = tr_frag(sA[buf], at0 + tt, lane);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i][tt] = mfma32(ga[i], ab, acc[i][tt]);
+      }
+      buf ^= 1;
+    };
+    Stage st[DEPTH];
+#pragma unroll
+    for (int u = 0; u < DEPTH; ++u)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) st[u].mk[e][0] = st[u].mk[e][1] = ~0u;
+    int t = 0;
+    if (2 * DEPTH <= nfull) {
+      // steady: the prologue and every fetch of the loop are full tiles, so the loop is entered
+      // with all DEPTH sets requested in order and its waits count exactly
+#pragma unroll
+      for (int u = 0; u < DEPTH; ++u) {
+        fetch_full(st[u], u);
+        __builtin_amdgcn_sched_barrier(0);    // (the scheduler would request the first tile last)
+      }
+      for (; t + 2 * DEPTH <= nfull; t += DEPTH) {
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) step(st[u], t + u, std::true_type{});
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < DEPTH; ++u) fetch_any(st[u], u);
+    }
+    for (; t < nt; t += DEPTH) {                      // the last steps and the ragged tile
+#pragma unroll
+      for (int u = 0; u < DEPTH; ++u)
+        if (t + u < nt) step(st[u], t + u, std::false_type{});
     }
   };
-  fetch(r0 + 32 * grp);
-  int buf = 0;
-  // uniform trip count for all groups (a group whose tile lies beyond r1 multiplies zeros)
-  for (int64_t base0 = r0; base0 < r1; base0 += 32 * NG, buf ^= 1) {
-    const int64_t base = base0 + 32 * grp;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int c = gtid + e * 256;
-      const int row = c >> 4, ch = c & 15;
-      if (job.mask != nullptr) {
-        const uint32_t n0 = mk[e][0] >> (4 * (ch >> 1)), n1 = mk[e][1] >> (4 * (ch >> 1));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if (!((n0 >> k) & 1u)) vg[e][k] = (__bf16)0.f;
-          if (!((n1 >> k) & 1u)) vg[e][4 + k] = (__bf16)0.f;
-        }
-      }
-      *reinterpret_cast<bf16x8*>(sG[buf] + tr_off(row, ch)) = vg[e];
-      *reinterpret_cast<bf16x8*>(sA[buf] + tr_off(row, ch)) = va[e];
-      if (job.db != nullptr) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) bs[k] += (float)vg[e][k];
-      }
-    }
-    __syncthreads();
-    if (base0 + 32 * NG < r1) fetch(base + 32 * NG);
-    bf16x8 ga[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ga[i] = tr_frag(sG[buf], gt0 + i, lane);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const bf16x8 ab = tr_frag(sA[buf], at0 + t, lane);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i][t] = mfma32(ga[i], ab, acc[i][t]);
-    }
-  }
+  if (job.mask != nullptr) run(std::true_type{});
+  else run(std::false_type{});
+
   // The atomics cost per cache-line transaction, not per lane: stage the [128][128] block in
   // LDS and add it with fully coalesced instructions (64 consecutive floats per wave) instead
   // of 16-float row fragments straight from the accumulator layout.
@@ -177,6 +258,45 @@ __global__ __launch_bounds__(256 * NG) void k_wgrad128(const WgradJobs jobs, int
   }
 }
 
+// tile pairs in flight per row group: three for bf16 operands (96 KB per 512-thread workgroup beside
+// the 64 accumulator registers), one for fp32 ones (their register sets are twice as large, and the
+// fp32 jobs of a step are two steps long: two in flight measured the same k_wgrad128_step time)
+template <typename GT, typename AT>
+constexpr int wgrad128_depth() {
+  return std::is_same<GT, __bf16>::value && std::is_same<AT, __bf16>::value ? 3 : 1;
+}
+
+// blockIdx.y selects the job; the rows beyond the jobs are rider rows
+template <typename GT, typename AT, int NG>
+__global__ __launch_bounds__(256 * NG) void k_wgrad128(const WgradJobs jobs, int rows_per_wg,
+                                                       const SlabSumJobs riders) {
+  __shared__ __attribute__((aligned(16))) char lds[4 * 32 * 256 * 2];
+  if ((int)blockIdx.y >= jobs.n) {          // rider rows: partial sums that are due now
+    slab_sum_body(riders.j[blockIdx.y - jobs.n], blockIdx.x, threadIdx.x,
+                  reinterpret_cast<float4*>(lds));
+    return;
+  }
+  wgrad128_body<GT, AT, NG, wgrad128_depth<GT, AT>()>(jobs.j[blockIdx.y], rows_per_wg, lds);
+}
+
+// The two deferred lists of a step in one launch: rows [0, bf.n) of blockIdx.y are the bf16 jobs (the
+// long ones, so they are placed first), then the fp32 jobs, then the rider rows.  Each list has its own
+// rows per workgroup; a row whose blockIdx.x lies beyond its range leaves at once.  The operand type
+// is uniform per workgroup, and both lists run two row groups.
+__global__ __launch_bounds__(512) void k_wgrad128_step(const WgradJobs bf, int rpw_bf,
+                                                       const WgradJobs f32, int rpw_f32,
+                                                       const SlabSumJobs riders) {
+  __shared__ __attribute__((aligned(16))) char lds[4 * 32 * 256 * 2];
+  const int y = blockIdx.y;
+  if (y < bf.n) {
+    wgrad128_body<__bf16, __bf16, 2, wgrad128_depth<__bf16, __bf16>()>(bf.j[y], rpw_bf, lds);
+  } else if (y < bf.n + f32.n) {
+    wgrad128_body<float, float, 2, wgrad128_depth<float, float>()>(f32.j[y - bf.n], rpw_f32, lds);
+  } else {
+    slab_sum_body(riders.j[y - bf.n - f32.n], blockIdx.x, threadIdx.x, reinterpret_cast<float4*>(lds));
+  }
+}
+
 // layer 1: dW[D x dq] += dQp^T . X with dq <= 4 (fp32 X), db += colsum(dQp).
 // 256 threads = 128 features x 2 row phases; 128 rows per workgroup, loads unrolled.
 template <typename GT>
@@ -191,45 +311,60 @@ __global__ __launch_bounds__(256) void k_wgrad_small(const GT* __restrict__ G,
 
 }  // namespace
 
-int wgrad128_launch(const WgradJobs& jobs_in, bool g_bf16, bool a_bf16, int rows_per_wg,
-                    hipStream_t st, WgradSlabs* sl) {
-  WgradJobs jobs = jobs_in;
-  int64_t maxM = 0;
-  for (int i = 0; i < jobs.n; ++i) maxM = jobs.j[i].M > maxM ? jobs.j[i].M : maxM;
-  SlabSumJobs riders{};
-  if (sl != nullptr && sl->riders != nullptr) riders = *sl->riders;
-  if (maxM == 0 || jobs.n == 0) return slab_sum_jobs(riders, st);
-  if (sl != nullptr && sl->ws != nullptr) {
-    // one slab per workgroup and job; more rows per workgroup until they fit
-    for (;;) {
-      size_t need = 0;
-      for (int i = 0; i < jobs.n; ++i) {
-        const WgradJob& j = jobs.j[i];
-        need += (size_t)cdiv(j.M, rows_per_wg) * ((j.g_hi - j.g_lo) * 128 + (j.db ? 128 : 0)) * 4;
-      }
-      if (need <= sl->cap) break;
-      rows_per_wg *= 2;
-    }
-    float* at = sl->ws;
+static int64_t max_rows(const WgradJobs& jobs) {
+  int64_t m = 0;
+  for (int i = 0; i < jobs.n; ++i) m = jobs.j[i].M > m ? jobs.j[i].M : m;
+  return m;
+}
+
+int wgrad128_place(WgradJobs& jobs, int& rows_per_wg, WgradSlabs* sl) {
+  if (sl == nullptr || sl->ws == nullptr) return PCA_OK;
+  // one slab per workgroup and job; more rows per workgroup until they fit
+  for (;;) {
+    size_t need = 0;
     for (int i = 0; i < jobs.n; ++i) {
-      WgradJob& j = jobs.j[i];
-      if (j.M <= 0) continue;
-      const int nwg = (int)cdiv(j.M, rows_per_wg), n1 = (j.g_hi - j.g_lo) * 128;
-      const int stride = n1 + (j.db ? 128 : 0);
-      j.slab = at;
-      PCA_REQUIRE(sl->sums_out->n + 2 <= 40, "wgrad128: slab-sum table full");
-      sl->sums_out->j[sl->sums_out->n++] = SlabSumJob{at, j.dW + (int64_t)j.g_lo * 128, nwg, n1, 1, stride};
-      if (j.db) sl->sums_out->j[sl->sums_out->n++] = SlabSumJob{at + n1, j.db, nwg, 128, 1, stride};
-      at += (size_t)nwg * stride;
+      const WgradJob& j = jobs.j[i];
+      need += (size_t)cdiv(j.M, rows_per_wg) * ((j.g_hi - j.g_lo) * 128 + (j.db ? 128 : 0)) * 4;
     }
-    sl->used = (size_t)(at - sl->ws) * sizeof(float);
+    if (need <= sl->cap) break;
+    rows_per_wg *= 2;
   }
-  unsigned gx = (unsigned)cdiv(maxM, rows_per_wg);
+  float* at = sl->ws;
+  for (int i = 0; i < jobs.n; ++i) {
+    WgradJob& j = jobs.j[i];
+    if (j.M <= 0) continue;
+    const int nwg = (int)cdiv(j.M, rows_per_wg), n1 = (j.g_hi - j.g_lo) * 128;
+    const int stride = n1 + (j.db ? 128 : 0);
+    j.slab = at;
+    PCA_REQUIRE(sl->sums_out->n + 2 <= 40, "wgrad128: slab-sum table full");
+    sl->sums_out->j[sl->sums_out->n++] = SlabSumJob{at, j.dW + (int64_t)j.g_lo * 128, nwg, n1, 1, stride};
+    if (j.db) sl->sums_out->j[sl->sums_out->n++] = SlabSumJob{at + n1, j.db, nwg, 128, 1, stride};
+    at += (size_t)nwg * stride;
+  }
+  sl->used = (size_t)(at - sl->ws) * sizeof(float);
+  return PCA_OK;
+}
+
+// grid.x: the widest of the job rows (rows / rows per workgroup) and of the rider rows
+static int rider_extent(const SlabSumJobs& riders, unsigned& gx) {
   for (int i = 0; i < riders.n; ++i) {
     PCA_REQUIRE(slab_sum_job_ok(riders.j[i]), "wgrad128: rider alignment");
     const unsigned need = (unsigned)cdiv(riders.j[i].n, 256);
     gx = need > gx ? need : gx;
   }
+  return PCA_OK;
+}
+
+int wgrad128_launch(const WgradJobs& jobs_in, bool g_bf16, bool a_bf16, int rows_per_wg,
+                    hipStream_t st, WgradSlabs* sl) {
+  WgradJobs jobs = jobs_in;
+  const int64_t maxM = max_rows(jobs);
+  SlabSumJobs riders{};
+  if (sl != nullptr && sl->riders != nullptr) riders = *sl->riders;
+  if (maxM == 0 || jobs.n == 0) return slab_sum_jobs(riders, st);
+  PCA_TRY(wgrad128_place(jobs, rows_per_wg, sl));
+  unsigned gx = (unsigned)cdiv(maxM, rows_per_wg);
+  PCA_TRY(rider_extent(riders, gx));
   const dim3 grid(gx, (unsigned)(jobs.n + riders.n));
   // two row groups per workgroup when every workgroup has at least four tiles to share
   const bool two = rows_per_wg >= 128;
@@ -247,6 +382,20 @@ int wgrad128_launch(const WgradJobs& jobs_in, bool g_bf16, bool a_bf16, int rows
     return PCA_EUNSUPPORTED;
   }
   return check_launch("k_wgrad128");
+}
+
+int wgrad128_launch_step(const WgradJobs& bf, int rpw_bf, const WgradJobs& f32, int rpw_f32,
+                         const SlabSumJobs& riders, hipStream_t st) {
+  PCA_REQUIRE(bf.n > 0 && f32.n > 0 && max_rows(bf) > 0 && max_rows(f32) > 0,
+              "wgrad128: the step launch takes two lists with rows");
+  PCA_REQUIRE(rpw_bf >= 128 && rpw_f32 >= 128, "wgrad128: the step launch runs two row groups");
+  unsigned gx = (unsigned)cdiv(max_rows(bf), rpw_bf);
+  const unsigned gf = (unsigned)cdiv(max_rows(f32), rpw_f32);
+  gx = gf > gx ? gf : gx;
+  PCA_TRY(rider_extent(riders, gx));
+  hipLaunchKernelGGL(k_wgrad128_step, dim3(gx, (unsigned)(bf.n + f32.n + riders.n)), dim3(512), 0, st,
+                     bf, rpw_bf, f32, rpw_f32, riders);
+  return check_launch("k_wgrad128_step");
 }
 
 int wgrad128_defer(BwdDefer* defer, const WgradJobs& jobs, bool bf16, int rows_per_wg,
