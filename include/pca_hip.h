@@ -492,6 +492,62 @@ int pca_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq,
                   float weight_decay, float grad_scale, int32_t* step_count_dev,
                   int zero_grad, void* stream);
 
+/* The same Adam step behind three guards that need no host sync (csrc/optim.hip): clipping by the
+ * global gradient norm, dropping a step whose norm is not finite, and a learning rate looked up
+ * per step in a device table.  Two launches: pca_grad_sumsq leaves per-workgroup partial sums of
+ * squares, pca_adam_step_ex consumes them (the kernel boundary is the ordering; no atomics on the
+ * sums, no floating-point atomics anywhere, so the same calls give the same bits, eagerly and
+ * under graph replay).  pca_adam_step itself is unchanged.
+ *
+ * pca_grad_sumsq_partials(n): how many doubles pca_grad_sumsq writes for a vector of n elements;
+ *   a function of n alone, 1 <= count <= 1024 (0 only for n < 0).
+ * pca_grad_sumsq: partials[g] = sum of grad[i]^2 over workgroup g's grid-stride slice.  A thread
+ *   adds its own few terms in fp32; every sum across lanes, waves and (in the consumer)
+ *   workgroups is fp64 in a fixed order.  n == 0 writes one zero.  A non-finite element makes
+ *   its partial non-finite.  n_partials must be pca_grad_sumsq_partials(n). */
+int64_t pca_grad_sumsq_partials(int64_t n);
+int pca_grad_sumsq(const float* grad, int64_t n, double* partials, int n_partials, void* stream);
+
+typedef struct pca_optim_cfg {
+  float lr;               /* used when lr_table is NULL                                */
+  float beta1, beta2, eps;
+  float weight_decay;     /* coupled L2, as pca_adam_step                              */
+  float grad_scale;       /* multiplies the gradient first (1/world after a SUM)       */
+  float max_norm;         /* > 0: clip by global norm; <= 0: no clipping               */
+  int32_t skip_nonfinite; /* != 0: a step whose norm is inf / NaN changes no parameter */
+} pca_optim_cfg;
+
+typedef struct pca_optim_state {  /* device; zero-initialised by the caller           */
+  int32_t skipped;        /* steps skipped so far                                      */
+  int32_t clipped;        /* steps that were clipped (clip factor < 1)                 */
+  float last_norm;        /* norm of the last step (0 when no partials were given)     */
+  float last_lr;          /* learning rate of the last step                            */
+  double norm_sum;        /* sum of the norms of finite steps since the caller zeroed  */
+  int32_t norm_count;     /* number of those steps                                     */
+  int32_t reserved;
+} pca_optim_state;
+
+/* norm = grad_scale * sqrt(sum of partials, index order, fp64), rounded to fp32: the norm of the
+ *   gradient Adam is about to use.  max_norm > 0: clip = min(1, max_norm / (norm + 1e-6)) in fp32
+ *   (torch.nn.utils.clip_grad_norm_); the gradient used is g * (grad_scale * clip).  With
+ *   clip == 1 the arithmetic is pca_adam_step's, bit for bit.
+ * partials / n_partials: what pca_grad_sumsq(grad, n, ...) left, on the same stream.  NULL is
+ *   legal only with max_norm <= 0 and skip_nonfinite == 0.
+ * lr_table (device float[lr_table_len]) or NULL: step t = step_count_dev[0] + 1 uses
+ *   lr_table[min(t, lr_table_len) - 1]; NULL: o->lr.
+ * skip_nonfinite and a non-finite norm: param, exp_avg, exp_avg_sq stay as they are (grad is
+ *   still cleared with zero_grad) and state->skipped advances.
+ * step_count_dev[0] advances on EVERY launch, skipped or not (it is also the data cursor of
+ *   pca_pack_points_*_seq and the draw number of the stochastic packs); the bias correction uses
+ *   the number of APPLIED steps, t - state->skipped, so a run with a skipped step equals
+ *   torch.optim.Adam whose step() was not called that once.
+ * state_dev: read by every workgroup before its arrival ticket, written by the workgroup that
+ *   draws the last one, which also publishes step_count_dev[0] (pca_adam_step's protocol). */
+int pca_adam_step_ex(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                     const pca_optim_cfg* o, const double* partials, int n_partials,
+                     const float* lr_table, int64_t lr_table_len, int32_t* step_count_dev,
+                     pca_optim_state* state_dev, int zero_grad, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Whole-model engine: the train / eval step of Code/settransformer.py:100-108  *
  * for the ST classifier of Code/models.py:13-44, enqueued by ONE call (so a    *

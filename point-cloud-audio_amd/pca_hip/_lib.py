@@ -42,6 +42,17 @@ class StConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "N", "din", "d", "h", "m", "k", "C", "mode")]
 
 
+class OptimCfg(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay",
+                                         "grad_scale", "max_norm")] + [("skip_nonfinite", C.c_int32)]
+
+
+class OptimState(C.Structure):
+    _fields_ = [("skipped", C.c_int32), ("clipped", C.c_int32), ("last_norm", C.c_float),
+                ("last_lr", C.c_float), ("norm_sum", C.c_double), ("norm_count", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64),
                 ("sa_m", C.c_int64), ("sa_k", C.c_int64), ("sb_k", C.c_int64),
@@ -129,6 +140,10 @@ SIGNATURES = {
                                        c_fp, c_vp, c_vp, c_vp, c_vp]),
     "pca_adam_step": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int64, C.c_float, C.c_float,
                                 C.c_float, C.c_float, C.c_float, C.c_float, c_vp, C.c_int, c_vp]),
+    "pca_grad_sumsq_partials": (C.c_int64, [C.c_int64]),
+    "pca_grad_sumsq": (C.c_int, [c_fp, C.c_int64, c_vp, C.c_int, c_vp]),
+    "pca_adam_step_ex": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int64, C.POINTER(OptimCfg), c_vp,
+                                   C.c_int, c_fp, C.c_int64, c_vp, c_vp, C.c_int, c_vp]),
     "pca_st_param_count": (C.c_int64, [C.POINTER(StConfig)]),
     "pca_st_bucket_split": (C.c_int64, [C.POINTER(StConfig)]),
     "pca_st_ws_bytes": (C.c_size_t, [C.POINTER(StConfig), C.c_int]),

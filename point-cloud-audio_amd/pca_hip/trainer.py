@@ -26,6 +26,7 @@ or, with ``overlap`` (large models: the exchange hides under the rest of the bac
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional, Tuple
 
@@ -151,6 +152,48 @@ def allreduce_buckets(grads: torch.Tensor, split: int, group=None, first_stream=
     else:
         dist.all_reduce(grads[split:], group=group)
     return lambda: dist.all_reduce(grads[:split], group=group)
+
+
+def warmup_cosine(base_lr: float, warmup_steps: int, total_steps: int,
+                  lr_min: float = 0.0) -> list:
+    """The learning rate of steps 1 .. total_steps as a list (``Trainer(lr_schedule=)``), in float64:
+    a linear ramp base_lr * t / warmup_steps over the first ``warmup_steps`` steps (so it starts at
+    base_lr / warmup_steps), then half a cosine from base_lr down to ``lr_min`` at the last step."""
+    warmup_steps, total_steps = int(warmup_steps), int(total_steps)
+    if not 0 <= warmup_steps <= total_steps or total_steps < 1:
+        raise ValueError(f"warmup_cosine: warmup_steps={warmup_steps} total_steps={total_steps}")
+    table = []
+    for t in range(1, total_steps + 1):
+        if t <= warmup_steps:
+            table.append(float(base_lr) * t / warmup_steps)
+        else:
+            frac = (t - warmup_steps) / max(1, total_steps - warmup_steps)
+            table.append(float(lr_min) + 0.5 * (float(base_lr) - float(lr_min))
+                         * (1.0 + math.cos(math.pi * frac)))
+    return table
+
+
+def _lr_table(lr_schedule, schedule_steps) -> Optional[torch.Tensor]:
+    """``lr_schedule`` (a sequence of floats, or a callable step -> lr with ``schedule_steps``; steps
+    count from 1) as a CPU fp32 vector, or None."""
+    if lr_schedule is None:
+        if schedule_steps is not None:
+            raise ValueError("schedule_steps without lr_schedule")
+        return None
+    if callable(lr_schedule):
+        if schedule_steps is None or int(schedule_steps) < 1:
+            raise ValueError("a callable lr_schedule needs schedule_steps >= 1")
+        values = [float(lr_schedule(t)) for t in range(1, int(schedule_steps) + 1)]
+    else:
+        values = [float(x) for x in lr_schedule]
+        if schedule_steps is not None and int(schedule_steps) != len(values):
+            raise ValueError(f"schedule_steps={schedule_steps} but lr_schedule has {len(values)} entries")
+    if not values:
+        raise ValueError("lr_schedule is empty")
+    table = torch.tensor(values, dtype=torch.float64).to(torch.float32)
+    if not bool(torch.isfinite(table).all()):
+        raise ValueError("lr_schedule holds a non-finite learning rate")
+    return table
 
 
 class STEngine:
@@ -290,7 +333,15 @@ class Trainer:
                  weight_decay: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  mode: int = _lib.MODE_F32, use_graph: bool = True, seed: int = 0,
                  shuffle: bool = True, process_group=None, keep_grads: bool = False,
-                 overlap: Optional[bool] = None):
+                 overlap: Optional[bool] = None, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False, lr_schedule=None,
+                 schedule_steps: Optional[int] = None):
+        """max_grad_norm: clip the (rank-averaged) gradient to this global L2 norm before Adam
+        (torch.nn.utils.clip_grad_norm_).  skip_nonfinite: a step whose gradient norm is inf / NaN
+        changes neither parameters nor moments.  lr_schedule: the learning rate per step (step 1
+        first; the last entry holds from there on) as a sequence of floats, or a callable
+        step -> lr with ``schedule_steps``; it lives in a device table, so a captured step follows it
+        without a re-capture.  All three at their defaults: the plain pca_adam_step launch."""
         self.ds = dataset
         self.keep_grads = keep_grads    # True: gradients of the last step stay readable
         self.B = int(batch_size)
@@ -338,6 +389,22 @@ class Trainer:
             # graph, [pack .. backward | all-reduce | Adam] = one graph launch per step
             self._captured = False
             self.comm_stream = torch.cuda.Stream(self.dev) if self._split else None
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        if self.max_grad_norm is not None and not self.max_grad_norm > 0.0:
+            raise ValueError(f"max_grad_norm must be positive, got {max_grad_norm}")
+        self.skip_nonfinite = bool(skip_nonfinite)
+        table = _lr_table(lr_schedule, schedule_steps)
+        self._optim_on = (self.max_grad_norm is not None or self.skip_nonfinite
+                          or table is not None)
+        self.lr_table = self.optim_state = self.norm_partials = None
+        if self._optim_on:
+            with torch.cuda.device(self.dev):
+                self.lr_table = None if table is None else table.to(self.dev)
+                # pca_optim_state, 32 bytes: [skipped, clipped, last_norm, last_lr, norm_sum(2), count, -]
+                self.optim_state = torch.zeros(8, dtype=torch.int32, device=self.dev)
+                if self.max_grad_norm is not None or self.skip_nonfinite:
+                    self.norm_partials = torch.zeros(int(lib().pca_grad_sumsq_partials(n)),
+                                                     dtype=torch.float64, device=self.dev)
         self._cursor_mode = callable(getattr(dataset, "batch_seq", None))
         self._k = 0                       # optimiser steps issued so far (host copy)
         self.g0 = self.g1 = self.g2 = None
@@ -441,6 +508,24 @@ class Trainer:
 
     def _seg2(self):     # Adam over the flat vector
         e = self.eng
+        if self._optim_on:
+            # [sum of squares ->] guarded Adam: both launches where the plain one sits, i.e. after the
+            # all-reduce / the join, so every rank clips the same averaged gradient and skips alike
+            L, n, st = lib(), e.flat.numel(), e._stream()
+            part, npart = None, 0
+            if self.norm_partials is not None:
+                part, npart = self.norm_partials.data_ptr(), self.norm_partials.numel()
+                check(L.pca_grad_sumsq(e.grads.data_ptr(), n, part, npart, st), "pca_grad_sumsq")
+            o = _lib.OptimCfg(self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                              1.0 / self.world, self.max_grad_norm or 0.0, int(self.skip_nonfinite))
+            tab = self.lr_table
+            check(L.pca_adam_step_ex(e.flat.data_ptr(), e.grads.data_ptr(), self.m.data_ptr(),
+                                     self.v.data_ptr(), n, C.byref(o), part, npart,
+                                     None if tab is None else tab.data_ptr(),
+                                     0 if tab is None else tab.numel(), self.step_count.data_ptr(),
+                                     self.optim_state.data_ptr(), int(not self.keep_grads), st),
+                  "pca_adam_step_ex")
+            return
         check(lib().pca_adam_step(e.flat.data_ptr(), e.grads.data_ptr(), self.m.data_ptr(),
                                   self.v.data_ptr(), e.flat.numel(), self.lr, self.betas[0],
                                   self.betas[1], self.eps, self.wd, 1.0 / self.world,
@@ -451,14 +536,15 @@ class Trainer:
         """Warm up eagerly on a side stream, then capture the segments."""
         s = torch.cuda.Stream(self.dev)
         s.wait_stream(torch.cuda.current_stream(self.dev))
-        snap = (self.eng.flat.clone(), self.m.clone(), self.v.clone(),
-                self.step_count.clone(), self.eng.stats.clone())
+        live = (self.eng.flat, self.m, self.v, self.step_count, self.eng.stats)
+        if self._optim_on:
+            live += (self.optim_state,)
+        snap = tuple(t.clone() for t in live)
         with torch.cuda.stream(s):
             self._seg0(); self._seg1(); self._seg2()
         torch.cuda.current_stream(self.dev).wait_stream(s)
         torch.cuda.synchronize(self.dev)
-        for dst, src in zip((self.eng.flat, self.m, self.v, self.step_count, self.eng.stats),
-                            snap):
+        for dst, src in zip(live, snap):
             dst.copy_(src)
         # thread-local capture mode: a HIP call from another thread (e.g. the RCCL watchdog of
         # torch.distributed) must not invalidate the capture
@@ -487,8 +573,7 @@ class Trainer:
                 self._seg2()
         # a stochastic dataset's host draw number is a by-value argument: the capture froze this one
         self._draw_frozen = getattr(self.ds, "_draw", None)
-        for dst, src in zip((self.eng.flat, self.m, self.v, self.step_count, self.eng.stats),
-                            snap):
+        for dst, src in zip(live, snap):
             dst.copy_(src)
 
     def step(self) -> None:
@@ -551,12 +636,41 @@ class Trainer:
             self.eng.stats.zero_()
         return float(out[0]), float(out[1])
 
+    def _optim_fields(self) -> dict:
+        """pca_optim_state as plain values (one host read)."""
+        host = self.optim_state.cpu()
+        f32, f64 = host.view(torch.float32), host.view(torch.float64)
+        return dict(skipped=int(host[0]), clipped=int(host[1]), last_norm=float(f32[2]),
+                    last_lr=float(f32[3]), norm_sum=float(f64[2]), norm_count=int(host[6]))
+
+    def read_optim_stats(self, reset: bool = True) -> dict:
+        """grad_norm_mean (over the finite steps since the last reset), last_grad_norm, lr (of the last
+        step), clipped and skipped (steps, since the start of the run).  The norm is that of the
+        gradient Adam used, before clipping; 0 when neither clipping nor skipping is on.  One host
+        read; ``reset`` clears the mean's accumulator."""
+        if not self._optim_on:
+            raise _lib.PcaHipError("read_optim_stats: this Trainer was built without max_grad_norm, "
+                                   "skip_nonfinite or lr_schedule")
+        f = self._optim_fields()
+        if reset:
+            self.optim_state[4:7].zero_()
+        return dict(grad_norm_mean=f["norm_sum"] / f["norm_count"] if f["norm_count"] else 0.0,
+                    last_grad_norm=f["last_norm"], lr=f["last_lr"], clipped=f["clipped"],
+                    skipped=f["skipped"])
+
     # ---- exact resume ----------------------------------------------------------------
     def state_dict(self) -> dict:
         """Everything the next step depends on, as CPU tensors and plain values (one host sync): legal
         at any step boundary, mid-epoch included.  The staged epoch sequence and the current
         permutation are not stored: ``load_state_dict`` re-derives them from (seed, epoch)."""
         cpu = lambda t: t.detach().to("cpu").clone()
+        optim = {}
+        if self._optim_on:
+            # the state words as they are (norm_sum keeps its fp64 bits) next to the readable fields
+            optim = dict(optim=dict(self._optim_fields(), words=cpu(self.optim_state),
+                                    lr_schedule=None if self.lr_table is None else cpu(self.lr_table),
+                                    max_grad_norm=self.max_grad_norm,
+                                    skip_nonfinite=self.skip_nonfinite))
         return dict(format=1, B=self.B, N=self.N, mode=int(self.eng.cfg.mode), world=int(self.world),
                     flat=cpu(self.eng.flat), m=cpu(self.m), v=cpu(self.v),
                     step_count=int(self.step_count[0].item()), k=int(self._k),
@@ -564,7 +678,7 @@ class Trainer:
                     stream=self.indices.state(),
                     # stochastic datasets: the host half of the draw number (the device half is
                     # step_count); a captured step froze draw_frozen
-                    draw=getattr(self.ds, "_draw", None), draw_frozen=self._draw_frozen)
+                    draw=getattr(self.ds, "_draw", None), draw_frozen=self._draw_frozen, **optim)
 
     def load_state_dict(self, state: dict) -> None:
         """Continue a run bit for bit from ``state_dict()``.  B, N, mode and world must be this
@@ -578,8 +692,11 @@ class Trainer:
         if state["flat"].numel() != self.eng.flat.numel():
             raise ValueError(f"checkpoint mismatch: parameters is {state['flat'].numel()} in the "
                              f"checkpoint, {self.eng.flat.numel()} in this trainer")
+        self._check_optim(state.get("optim"))
         torch.cuda.synchronize(self.dev)
         self.g0 = self.g1 = self.g2 = None
+        if self._optim_on:
+            self.optim_state.copy_(state["optim"]["words"])
         # into the vectors the engines (and the module's parameters) are views of, never a re-bind
         self.eng.flat.copy_(state["flat"])
         self.m.copy_(state["m"])
@@ -603,6 +720,24 @@ class Trainer:
                 else int(state["draw"])
         self._draw_frozen = None
 
+    def _check_optim(self, saved: Optional[dict]) -> None:
+        """The checkpoint's optimiser options against this trainer's; a difference raises, naming it."""
+        mine = dict(max_grad_norm=self.max_grad_norm, skip_nonfinite=self.skip_nonfinite)
+        theirs = dict(max_grad_norm=None, skip_nonfinite=False) if saved is None else saved
+        for name, have in mine.items():
+            if theirs[name] != have:
+                raise ValueError(f"checkpoint mismatch: {name} is {theirs[name]} in the checkpoint, "
+                                 f"{have} in this trainer")
+        tab = None if saved is None else saved.get("lr_schedule")
+        mine_tab = None if self.lr_table is None else self.lr_table.cpu()
+        if (tab is None) != (mine_tab is None) or (
+                tab is not None and not (tab.shape == mine_tab.shape and torch.equal(tab, mine_tab))):
+            describe = lambda t: "absent" if t is None else f"a table of {t.numel()} steps"
+            raise ValueError(f"checkpoint mismatch: lr_schedule is {describe(tab)} in the checkpoint, "
+                             f"{describe(mine_tab)} in this trainer"
+                             + ("" if tab is None or mine_tab is None or tab.shape != mine_tab.shape
+                                else " with other values"))
+
     # ---- the reference's epoch loop --------------------------------------------------------
     def fit(self, epochs: int, test_dataset=None, eval_every: int = 10,
             checkpoint_path: Optional[str] = None, checkpoint_every: Optional[int] = None,
@@ -615,7 +750,10 @@ class Trainer:
         checkpoint (runfiles.save_checkpoint) is written every ``checkpoint_every`` epochs (default:
         every epoch) and after the last.  The only host syncs are those reads (and a checkpoint's).
         Returns one dict per epoch run: epoch, train_loss, train_acc and, where the held-out pass
-        ran, test_loss, test_acc, test_topk_acc."""
+        ran, test_loss, test_acc, test_topk_acc.  A trainer with max_grad_norm, skip_nonfinite or
+        lr_schedule adds grad_norm (mean over the epoch's finite steps), lr (of the epoch's last
+        step), clipped_steps and skipped_steps (since the start of the run): one more host read
+        (``read_optim_stats``) and one more line per epoch."""
         spe = self.indices.steps_per_epoch()
         if test_dataset is not None and (self._evaluator is None
                                          or self._evaluator.ds is not test_dataset):
@@ -631,6 +769,12 @@ class Trainer:
             entry = dict(epoch=epoch, train_loss=loss_sum / seen, train_acc=correct / seen)
             log(f"Epoch {epoch}: train loss {entry['train_loss']:.3f} train acc "
                 f"{entry['train_acc']:.3f}")
+            if self._optim_on:
+                o = self.read_optim_stats()
+                entry.update(grad_norm=o["grad_norm_mean"], lr=o["lr"], clipped_steps=o["clipped"],
+                             skipped_steps=o["skipped"])
+                log(f"Epoch {epoch}: grad norm {o['grad_norm_mean']:.3f} lr {o['lr']:.3e} clipped "
+                    f"{o['clipped']} skipped {o['skipped']}")
             if test_dataset is not None and epoch % eval_every == 0:
                 res = self._evaluator.run()
                 entry.update(test_loss=res["loss"], test_acc=res["acc"],
