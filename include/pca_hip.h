@@ -265,6 +265,48 @@ int pca_pack_points_2d_ss(const float* x_tk, const float* f_tk, const int64_t* i
                           int K, float* out, const int64_t* labels, int64_t* labels_out,
                           void* stream);
 
+/* The random part of a framed batch.  A field that is off (jitter == 0, gain_db == 0, n_win == 1) draws
+ * nothing and is exact: shift 0, gain 1.0f, window win_lengths[0]. */
+typedef struct PcaFrameAug {
+  int32_t jitter;              /* time shift: uniform integer in [-jitter, +jitter] samples; >= 0 */
+  float gain_db;               /* level: gain 10^(u * gain_db / 20), u uniform in [-1, 1); finite, >= 0 */
+  const int32_t* win_lengths;  /* device int32[n_win]: the window length is uniform over these; values
+                                  outside [1, n_fft] are clamped into it on the device */
+  int32_t n_win;               /* >= 1 */
+  int32_t norm_mode;           /* 0: |.| / n_fft (Code/settransformer.py:49); 1: |.| / the slot's window
+                                  length (Code/pceval.py:76) */
+  uint64_t seed, draw;         /* the counter-based stream of pca_subsample_points */
+  const int32_t* draw_dev;     /* nullable device int32: draw + draw_dev[0] is the draw number, so a
+                                  launch captured into a hipGraph draws afresh on every replay */
+} PcaFrameAug;
+
+/* Point sets framed from the resident waveforms, augmented on the device, in the launch that stands
+ * where the pack stood
+ * replaces: the pre-pass Code/settransformer.py:43-53 / Code/settransformertemp.py:45-61 (one
+ *           librosa.stft per clip, before training) plus Code/dataset.py:50-54,160-166
+ *           (__getitem__ + default_collate); the reference has no augmentation: with every field of
+ *           `aug` off the rows are bit-identical to pca_stft_logmag_batch + pca_pack_points_2d / _3d.
+ * waves / wave_off[n_clips + 1] / max_len / min_len: the corpus as pca_stft_logmag_batch takes it.
+ * set_off[n_clips + 1] (device): prefix sum of the sets each clip yields - T_c = 1 + L_c / hop frames
+ * (Nt = 1), or T_c / Nt whole chunks of Nt frames (the short tail is dropped, as
+ * Code/settransformertemp.py:54-58 does).  idx[B]: set ids in [0, set_off[n_clips]) (clamped into it).
+ * Batch slot b, set i = idx[b] = set s of clip c (binary search of set_off on the device): one shift
+ * delta, gain g and window length w per slot from the stream (seed, draw + draw_dev[0], b, i); frame
+ * j < Nt has its centre at clamp((s*Nt + j)*hop + delta, 0, L_c) - the range the regular grid reaches,
+ * so min_len > n_fft/2 is all the reflect padding needs - and is k_stft_logmag's transform of
+ * (double)wave * hann_w * (double)g: periodic Hann of w samples centred in n_fft (power of two,
+ * 64..4096), fp64 FFT, spectrum rounded to complex64, logf(1e-8f + |.| / norm).
+ * out[B, Nt*n_bins, 3]: point p = j*n_bins + f -> (farr[f], tarr[j], value), or out[B, Nt*n_bins, 2] =
+ * (farr[f], value) when tarr is NULL; Nt*n_bins <= 16384, B <= 65535.  labels_out[b] = clip_labels[c]
+ * (both or neither NULL).  meta_out (nullable) int32 [B, 4] = (c, centre of frame 0, w, bits of the
+ * fp32 g).  Grid (Nt, B), 24 B * n_fft of LDS per workgroup, no atomics: the same arguments give the
+ * same bits. */
+int pca_frame_points(const float* waves, const int64_t* wave_off, const int64_t* set_off,
+                     int n_clips, int64_t max_len, int64_t min_len, const int64_t* clip_labels,
+                     const int64_t* idx, int B, int n_fft, int hop, int n_bins, int Nt,
+                     const float* farr, const float* tarr, const PcaFrameAug* aug, float* out,
+                     int64_t* labels_out, int32_t* meta_out, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Fixed-input baselines (eval-mode forward; training stays stock PyTorch)    *
  * ------------------------------------------------------------------------- */

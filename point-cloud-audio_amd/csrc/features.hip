@@ -9,19 +9,16 @@
 // here the spectrogram stays resident in HBM and a batch is assembled by one launch.
 #include "pca_common.h"
 #include "pack_body.hpp"
+#include "stft_body.hpp"
 
 #include <mutex>
 
 namespace pca {
 namespace {
 
-// One workgroup per frame.  In-place radix-2 decimation-in-time FFT in LDS, in float64:
-// librosa computes the transform in double (numpy.fft) and only then rounds to complex64,
-// so matching it to ~1e-7 in log-magnitude -- including the near-silent bins that the
-// log(1e-8 + .) floor amplifies -- needs double butterflies; the op is a one-off pre-pass
-// and stays HBM/LDS-bound.  LDS: n_fft complex doubles (data) + n_fft/2 (twiddles)
-// = 24 B * n_fft (96 KiB at n_fft = 4096).  Frame t covers samples
-// [t*hop - n_fft/2, t*hop + n_fft/2) of the reflect-padded signal (center=True).
+// One workgroup per frame; the frame itself (window, fp64 FFT in LDS, magnitude) is stft_body.hpp.
+// Frame t covers samples [t*hop - n_fft/2, t*hop + n_fft/2) of the reflect-padded signal (center=True).
+// The op is a one-off pre-pass and stays HBM/LDS-bound.
 // Batched form (blockIdx.y = clip): clip c is wave[wave_off[c] .. wave_off[c + 1]) and its frame t
 // goes to output column frame_off[c] + t; a clip shorter than the longest one leaves the workgroups
 // past its last frame idle.  wave_off == nullptr: one clip of L samples, columns from 0.
@@ -46,54 +43,11 @@ __global__ __launch_bounds__(256) void k_stft_logmag(const float* __restrict__ w
     wave += w0;
     out += frame_off[c] * stride_t;
   }
-  const int lpad = (n_fft - win_length) / 2;
-  const int64_t start = t * hop - n_fft / 2;
-  const int half = n_fft >> 1;
-
-  for (int k = tid; k < half; k += 256) {
-    double sn, cs;
-    sincospi(-2.0 * (double)k / (double)n_fft, &sn, &cs);
-    tw[k] = make_double2(cs, sn);
-  }
-  for (int n = tid; n < n_fft; n += 256) {
-    int64_t src = start + n;
-    if (src < 0) src = -src;
-    if (src >= L) src = 2 * (L - 1) - src;
-    if (src < 0) src = 0;  // only reachable when L <= n_fft/2 (rejected on the host)
-    const int nw = n - lpad;
-    double w = 0.0;
-    if (nw >= 0 && nw < win_length)
-      w = 0.5 - 0.5 * cospi(2.0 * (double)nw / (double)win_length);   // periodic Hann
-    const int r = (int)(__brev((unsigned)n) >> (32 - log2n));          // bit-reversed slot
-    x[r] = make_double2((double)wave[src] * w, 0.0);
-  }
-  __syncthreads();
-
-  for (int s = 1; s <= log2n; ++s) {
-    const int hm = 1 << (s - 1);               // half butterfly span
-    const int tstride = n_fft >> s;            // twiddle index stride
-    for (int j = tid; j < half; j += 256) {
-      const int k = j & (hm - 1);
-      const int i0 = ((j - k) << 1) + k;
-      const int i1 = i0 + hm;
-      const double2 w = tw[k * tstride];
-      const double2 a = x[i0];
-      const double2 b = x[i1];
-      const double2 bw = make_double2(b.x * w.x - b.y * w.y, b.x * w.y + b.y * w.x);
-      x[i0] = make_double2(a.x + bw.x, a.y + bw.y);
-      x[i1] = make_double2(a.x - bw.x, a.y - bw.y);
-    }
-    __syncthreads();
-  }
+  stft_frame_fft(x, tw, wave, L, t * hop - n_fft / 2, n_fft, log2n, win_length, 1.0, tid);
 
   const double inv = 1.0 / norm;
-  for (int f = tid; f < n_bins; f += 256) {
-    const double2 v = x[f];
-    // the reference rounds the spectrum to complex64 before |.| (librosa dtype=complex64)
-    const float re = (float)(v.x * inv), im = (float)(v.y * inv);
-    const float mag = sqrtf(re * re + im * im);
-    out[f * stride_f + t * stride_t] = logf(1.0e-8f + mag);
-  }
+  for (int f = tid; f < n_bins; f += 256)
+    out[f * stride_f + t * stride_t] = stft_logmag_bin(x[f], inv);
 }
 
 // Smith's band-limited interpolation (resampy's resample_f restated): one thread per output sample,
@@ -224,7 +178,7 @@ int pca_stft_logmag(const float* wave, int64_t L, int n_fft, int win_length, int
   int log2n = 0;
   while ((1 << log2n) < n_fft) ++log2n;
   const int64_t T = pca_stft_num_frames(L, hop);
-  const size_t lds = ((size_t)n_fft + n_fft / 2) * sizeof(double2);
+  const size_t lds = pca::stft_lds_bytes(n_fft);
   static std::once_flag lds_once;   // allow > 64 KiB of dynamic LDS (96 KiB at n_fft 4096)
   std::call_once(lds_once, [] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pca::k_stft_logmag),
@@ -257,7 +211,7 @@ int pca_stft_logmag_batch_norm(const float* waves, const int64_t* wave_off, cons
   int log2n = 0;
   while ((1 << log2n) < n_fft) ++log2n;
   const int64_t T = pca_stft_num_frames(max_len, hop);
-  const size_t lds = ((size_t)n_fft + n_fft / 2) * sizeof(double2);
+  const size_t lds = pca::stft_lds_bytes(n_fft);
   static std::once_flag lds_once;
   std::call_once(lds_once, [] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pca::k_stft_logmag),

@@ -1,0 +1,73 @@
+// One STFT frame in LDS, shared by k_stft_logmag (features.hip: the whole-corpus pre-pass) and
+// k_frame_points (frame_points.hip: frames cut from the resident waveform per batch), so that both
+// give the same bits for the same frame.
+//
+// In-place radix-2 decimation-in-time FFT in float64: librosa computes the transform in double
+// (numpy.fft) and only then rounds to complex64, so matching it to ~1e-7 in log-magnitude --
+// including the near-silent bins that the log(1e-8 + .) floor amplifies -- needs double butterflies.
+// LDS: n_fft complex doubles (data) + n_fft/2 (twiddles) = 24 B * n_fft (96 KiB at n_fft = 4096).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace pca {
+
+inline size_t stft_lds_bytes(int n_fft) { return ((size_t)n_fft + n_fft / 2) * sizeof(double2); }
+
+// Transform of the n_fft samples of the reflect-padded signal that begin at `start` (a frame of
+// centre c begins at c - n_fft/2), times the periodic Hann of win_length samples centred and
+// zero-padded to n_fft, times `gain` (1.0: an exact no-op).  256 threads; x[n_fft] and tw[n_fft/2]
+// are LDS; on return x[f] holds bin f and the workgroup is past a barrier.
+__device__ __forceinline__ void stft_frame_fft(double2* x, double2* tw,
+                                               const float* __restrict__ wave, int64_t L,
+                                               int64_t start, int n_fft, int log2n, int win_length,
+                                               double gain, int tid) {
+  const int lpad = (n_fft - win_length) / 2;
+  const int half = n_fft >> 1;
+
+  for (int k = tid; k < half; k += 256) {
+    double sn, cs;
+    sincospi(-2.0 * (double)k / (double)n_fft, &sn, &cs);
+    tw[k] = make_double2(cs, sn);
+  }
+  for (int n = tid; n < n_fft; n += 256) {
+    int64_t src = start + n;
+    if (src < 0) src = -src;
+    if (src >= L) src = 2 * (L - 1) - src;
+    if (src < 0) src = 0;  // only reachable when L <= n_fft/2 (rejected on the host)
+    const int nw = n - lpad;
+    double w = 0.0;
+    if (nw >= 0 && nw < win_length)
+      w = 0.5 - 0.5 * cospi(2.0 * (double)nw / (double)win_length);   // periodic Hann
+    const int r = (int)(__brev((unsigned)n) >> (32 - log2n));          // bit-reversed slot
+    x[r] = make_double2((double)wave[src] * w * gain, 0.0);
+  }
+  __syncthreads();
+
+  for (int s = 1; s <= log2n; ++s) {
+    const int hm = 1 << (s - 1);               // half butterfly span
+    const int tstride = n_fft >> s;            // twiddle index stride
+    for (int j = tid; j < half; j += 256) {
+      const int k = j & (hm - 1);
+      const int i0 = ((j - k) << 1) + k;
+      const int i1 = i0 + hm;
+      const double2 w = tw[k * tstride];
+      const double2 a = x[i0];
+      const double2 b = x[i1];
+      const double2 bw = make_double2(b.x * w.x - b.y * w.y, b.x * w.y + b.y * w.x);
+      x[i0] = make_double2(a.x + bw.x, a.y + bw.y);
+      x[i1] = make_double2(a.x - bw.x, a.y - bw.y);
+    }
+    __syncthreads();
+  }
+}
+
+// log(1e-8 + |v| * inv) of one bin, inv = 1 / norm
+__device__ __forceinline__ float stft_logmag_bin(double2 v, double inv) {
+  // the reference rounds the spectrum to complex64 before |.| (librosa dtype=complex64)
+  const float re = (float)(v.x * inv), im = (float)(v.y * inv);
+  const float mag = sqrtf(re * re + im * im);
+  return logf(1.0e-8f + mag);
+}
+
+}  // namespace pca

@@ -12,6 +12,8 @@ returns.  ``DeviceBatchLoader`` is the loader the train / eval entry points use.
 """
 from typing import Iterator, Optional, Tuple
 
+import copy
+
 import numpy as np
 import torch
 from torch.utils.data import Dataset
@@ -20,7 +22,8 @@ import pca_hip
 
 __all__ = ["ESC_baseline", "ESC_pc", "ESC_pc_ss", "ESC_baseline_temporal",
            "ESC_baseline_temporal_maxK", "ESC_pc_temp", "ESC_pc_temp_maxKSS",
-           "ESC_pc_temp_randKSS", "ESC_pc_temp_importancerandKSS", "DeviceBatchLoader"]
+           "ESC_pc_temp_randKSS", "ESC_pc_temp_importancerandKSS", "ESC_wave_pc",
+           "ESC_wave_pc_temp", "DeviceBatchLoader"]
 
 
 def _dev(device) -> torch.device:
@@ -376,6 +379,154 @@ class ESC_pc_temp_importancerandKSS(_TempSS):
                                          self.seed, self._draw, lab, out=out,
                                          labels_out=labels_out, want_sel=want_sel,
                                          want_heat=want_heat, draw_dev=draw_dev)
+
+
+def wave_set_offsets(lengths, hop: int, ntemp: int = 1) -> list:
+    """Prefix sum of the sets each clip yields: 1 + L // hop frames (librosa's center=True count),
+    or, with ntemp > 1, frames // ntemp whole chunks - the short tail is dropped, as
+    Code/settransformertemp.py:54-58 does."""
+    off = [0]
+    for n in lengths:
+        off.append(off[-1] + (1 + int(n) // hop) // ntemp)
+    return off
+
+
+class ESC_wave_pc(Dataset):
+    """2-D point sets framed from the resident WAVEFORMS per batch: what the pre-pass
+    Code/settransformer.py:43-53 plus ``ESC_pc`` give, without the spectrogram - and therefore free to
+    move the frame.  Item idx = frame idx of the corpus (clip after clip, 1 + L // hop frames each),
+    float32 [F, 2] rows (farr[f], log(1e-8 + |stft| / norm)) from ONE launch per batch
+    (pca_frame_points), with per batch slot
+
+    jitter       a time shift of up to +-jitter samples (the centre stays inside the clip)
+    gain_db      a level change of up to +-gain_db dB
+    win_lengths  a window length drawn out of this sequence (each in [1, n_fft]; None: n_fft).  The first
+                 entry is the nominal one: what ``plain()`` uses
+
+    drawn from the counter-based device stream (seed, draw number, batch slot, set), as
+    ``ESC_pc_temp_randKSS`` draws its points.  With all three off the batches are bit for bit those of
+    ``ESC_pc`` over ``pca_hip.stft_logmag_batch`` of the same clips.
+
+    clips  list of 1-D float32 waveforms (numpy or torch, host or device), each longer than n_fft / 2
+    y      one label per clip
+    norm   "n_fft": magnitude / n_fft (the train scripts); "win": / the window length (Code/pceval.py:76)
+    """
+    _ntemp = 1
+
+    def __init__(self, clips, y, fs, n_fft, hop=None, drop_nyquist=False, jitter=0, gain_db=0.0,
+                 win_lengths=None, norm="n_fft", seed=0, device=None):
+        self._setup(clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
+                    device)
+
+    def _setup(self, clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
+               device):
+        if norm not in ("n_fft", "win"):
+            raise ValueError(f"norm is 'n_fft' or 'win', got {norm!r}")
+        self.clips, self.clip_labels = list(clips), np.asarray(y).astype(np.int64)
+        assert len(self.clips) == len(self.clip_labels) > 0
+        self.fs, self.n_fft = fs, int(n_fft)
+        self.hop = self.n_fft // 2 if hop is None else int(hop)
+        self.F = self.n_fft // 2 if drop_nyquist else self.n_fft // 2 + 1
+        self.farr = np.linspace(0, fs / 2, self.F) / fs
+        self.tarr = None
+        self.jitter, self.gain_db = int(jitter), float(gain_db)
+        self.win_lengths = (self.n_fft,) if win_lengths is None else tuple(int(w) for w in win_lengths)
+        if not self.win_lengths or not all(1 <= w <= self.n_fft for w in self.win_lengths):
+            raise ValueError(f"win_lengths {self.win_lengths}: each in [1, n_fft = {self.n_fft}]")
+        self.norm = norm
+        self.seed = int(seed)
+        self._draw = 0
+        self._device = device
+        self._store = {}                  # the resident tensors, shared with plain() views
+        self.lengths = [int(c.shape[0]) for c in self.clips]
+        self._max_len, self._min_len = max(self.lengths), min(self.lengths)
+        self.wave_off = [0] + list(np.cumsum(self.lengths))
+        self.set_off = wave_set_offsets(self.lengths, self.hop, self._ntemp)
+        # label of every set (what ESC_pc calls labels)
+        self.labels = np.repeat(self.clip_labels, np.diff(self.set_off))
+
+    def __len__(self):
+        return self.set_off[-1]
+
+    @property
+    def num_points(self) -> int:
+        return self._ntemp * self.F
+
+    batch_seq = None        # augmentations are drawn per call: the Trainer uploads indices per step
+
+    @property
+    def stochastic(self) -> bool:
+        """True when any augmentation is on: every call must then draw anew, so a caller that
+        captures ``batch`` into a hipGraph passes ``draw_dev`` (see ``_TempSS.stochastic``)."""
+        return self.jitter > 0 or self.gain_db > 0.0 or len(self.win_lengths) > 1
+
+    def plain(self, win_length=None):
+        """A view on the same resident waveforms with every augmentation off: deterministic, the
+        regular frame grid, the nominal window (``win_lengths[0]``, or ``win_length``).  What the
+        ``Evaluator`` and ``fit(test_dataset=...)`` take."""
+        v = copy.copy(self)
+        v.jitter, v.gain_db = 0, 0.0
+        v.win_lengths = (self.win_lengths[0] if win_length is None else int(win_length),)
+        if not 1 <= v.win_lengths[0] <= self.n_fft:
+            raise ValueError(f"win_length {v.win_lengths[0]} outside [1, n_fft = {self.n_fft}]")
+        v._draw = 0
+        return v
+
+    def _resident(self):
+        if "res" not in self._store:
+            dev = _dev(self._device)
+            i64 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.int64)).to(dev)   # noqa: E731
+            f32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64)).float().to(dev)  # noqa: E731
+            waves = torch.cat([torch.as_tensor(c).to(dev, torch.float32).reshape(-1)
+                               for c in self.clips])
+            self._store["res"] = (waves, i64(self.wave_off), i64(self.set_off), f32(self.farr),
+                                  None if self.tarr is None else f32(self.tarr),
+                                  i64(self.clip_labels))
+            self._store["win"] = {}
+        return self._store["res"]
+
+    def _win_dev(self, dev):
+        if self.win_lengths not in self._store["win"]:
+            self._store["win"][self.win_lengths] = torch.tensor(self.win_lengths, dtype=torch.int32,
+                                                                 device=dev)
+        return self._store["win"][self.win_lengths]
+
+    def batch(self, idx: torch.Tensor, out=None, labels_out=None, draw_dev=None,
+              want_meta: bool = False):
+        """idx int64[B] on the device -> (points [B, num_points, 2 or 3] float32, labels int64[B]
+        [, meta int32 [B, 4] = (clip, centre sample of frame 0, window length, bits of the gain)])."""
+        waves, woff, soff, f32, t32, lab = self._resident()
+        self._draw += 1
+        return pca_hip.frame_points(
+            waves, woff, soff, idx, self.n_fft, self.hop, self.F, f32, t32, self._ntemp,
+            max_len=self._max_len, min_len=self._min_len, clip_labels=lab,
+            jitter=self.jitter, gain_db=self.gain_db, win_lengths=self._win_dev(waves.device),
+            norm_mode=pca_hip.NORM_WIN if self.norm == "win" else pca_hip.NORM_NFFT,
+            seed=self.seed, draw=self._draw, out=out, labels_out=labels_out, draw_dev=draw_dev,
+            want_meta=want_meta)
+
+    def __getitem__(self, idx):
+        waves = self._resident()[0]
+        i = torch.tensor([int(idx)], dtype=torch.int64, device=waves.device)
+        pts, lbl = self.batch(i)
+        return pts[0].cpu(), lbl[0].cpu()
+
+
+class ESC_wave_pc_temp(ESC_wave_pc):
+    """3-D point sets framed from the resident waveforms per batch: the pre-pass
+    Code/settransformertemp.py:45-61 plus ``ESC_pc_temp`` without the spectrogram.  Item idx = chunk
+    idx of the corpus: ``Ntemp`` consecutive frames of one clip (frames // Ntemp chunks per clip, the
+    short tail dropped), float32 [Ntemp * F, 3] rows (farr[f], tarr[t], value), point p = t * F + f,
+    the Nyquist bin dropped and tarr = linspace(0, hop / fs * Ntemp, Ntemp) as
+    Code/settransformertemp.py:40-41,52.  One shift, gain and window per chunk, so its frames stay
+    ``hop`` apart and ``tarr`` keeps its meaning.  Arguments as ``ESC_wave_pc``."""
+
+    def __init__(self, clips, y, fs, n_fft, Ntemp, hop=None, jitter=0, gain_db=0.0,
+                 win_lengths=None, norm="n_fft", seed=0, device=None):
+        self._ntemp = int(Ntemp)
+        assert self._ntemp >= 1
+        self._setup(clips, y, fs, n_fft, hop, True, jitter, gain_db, win_lengths, norm, seed, device)
+        self.tarr = np.linspace(0, (self.hop / fs) * self._ntemp, self._ntemp)
 
 
 class DeviceBatchLoader:

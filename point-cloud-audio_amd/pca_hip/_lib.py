@@ -53,6 +53,12 @@ class OptimState(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class PcaFrameAug(C.Structure):
+    _fields_ = [("jitter", C.c_int32), ("gain_db", C.c_float), ("win_lengths", C.c_void_p),
+                ("n_win", C.c_int32), ("norm_mode", C.c_int32), ("seed", C.c_uint64),
+                ("draw", C.c_uint64), ("draw_dev", C.c_void_p)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64),
                 ("sa_m", C.c_int64), ("sa_k", C.c_int64), ("sb_k", C.c_int64),
@@ -130,6 +136,9 @@ SIGNATURES = {
                                         c_vp, c_vp, c_vp]),
     "pca_pack_points_2d_ss": (C.c_int, [c_fp, c_fp, c_vp, C.c_int, C.c_int, c_fp, c_vp, c_vp,
                                         c_vp]),
+    "pca_frame_points": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p, c_i64p,
+                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp,
+                                   C.POINTER(PcaFrameAug), c_fp, c_i64p, c_vp, c_vp]),
     "pca_baseline_param_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, c_vp, C.c_int, C.c_int]),
     "pca_fb_forward": (C.c_int, [c_fp, C.c_int64, C.c_int64, c_i64p, C.c_int, C.c_int, c_vp,
                                  C.c_int, C.c_int, c_fp, C.c_int64, C.c_int, C.c_int, C.c_uint64,

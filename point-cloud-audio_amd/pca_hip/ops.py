@@ -732,6 +732,63 @@ def subsample_points(spec: torch.Tensor, farr: torch.Tensor, tarr: Optional[torc
     return (out, labels_out, sel) if want_sel else (out, labels_out)
 
 
+NORM_NFFT, NORM_WIN = 0, 1
+
+
+def frame_points(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.Tensor,
+                 idx: torch.Tensor, n_fft: int, hop: int, n_bins: int, farr: torch.Tensor,
+                 tarr: Optional[torch.Tensor] = None, Nt: int = 1, *, max_len: int, min_len: int,
+                 clip_labels: Optional[torch.Tensor] = None, jitter: int = 0,
+                 gain_db: float = 0.0, win_lengths: Optional[torch.Tensor] = None,
+                 norm_mode: int = NORM_NFFT, seed: int = 0, draw: int = 0,
+                 out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None,
+                 draw_dev: Optional[torch.Tensor] = None, want_meta: bool = False):
+    """Batch of point sets framed from resident waveforms and augmented on the device
+    (pca_frame_points): no spectrogram is kept, every call cuts its frames anew.
+
+    waves float32: the clips back to back; wave_off int64[n_clips + 1] their sample offsets;
+    set_off int64[n_clips + 1] the prefix sum of the sets per clip (1 + len // hop frames with
+    Nt = 1, frames // Nt whole chunks otherwise); idx int64[B] set ids; max_len / min_len the
+    longest / shortest clip (host values).  All tensors on the device.
+    Per batch slot one time shift in [-jitter, jitter] samples, one gain of up to +-gain_db dB and
+    one window length out of ``win_lengths`` (device int32; None: n_fft) from the stream (seed,
+    draw); a field left at its default is off and exact.  ``norm_mode`` NORM_NFFT divides the
+    magnitude by n_fft, NORM_WIN by the slot's window length.  ``draw_dev`` (device int32,
+    optional): its first element is added to ``draw`` on the device, so a launch captured into a
+    hipGraph draws afresh on every replay.
+    Returns (points [B, Nt * n_bins, 2 or 3] float32, clip_labels of each slot's clip or None
+    [, meta int32 [B, 4] = (clip, centre sample of frame 0, window length, bits of the fp32 gain)])."""
+    _need_cuda(waves, wave_off, set_off, idx, farr)
+    assert waves.dtype == torch.float32 and waves.is_contiguous() and farr.dtype == torch.float32
+    assert wave_off.dtype == set_off.dtype == idx.dtype == torch.int64
+    assert wave_off.numel() == set_off.numel() >= 2 and farr.numel() >= n_bins
+    din = 2
+    if tarr is not None:
+        _need_cuda(tarr)
+        assert tarr.dtype == torch.float32 and tarr.numel() >= Nt
+        din = 3
+    B = idx.numel()
+    with torch.cuda.device(waves.device):
+        if win_lengths is None:
+            win_lengths = torch.tensor([n_fft], dtype=torch.int32, device=waves.device)
+        assert win_lengths.is_cuda and win_lengths.dtype == torch.int32
+        if out is None:
+            out = torch.empty((B, Nt * n_bins, din), dtype=torch.float32, device=waves.device)
+        if clip_labels is not None and labels_out is None:
+            labels_out = torch.empty(B, dtype=torch.int64, device=waves.device)
+        meta = torch.empty((B, 4), dtype=torch.int32, device=waves.device) if want_meta else None
+        aug = _lib.PcaFrameAug(int(jitter), float(gain_db), win_lengths.data_ptr(),
+                               win_lengths.numel(), int(norm_mode), int(seed) & (2 ** 64 - 1),
+                               int(draw) & (2 ** 64 - 1), _draw_ptr(draw_dev))
+        check(lib().pca_frame_points(_ptr(waves), _ptr(wave_off), _ptr(set_off),
+                                     wave_off.numel() - 1, int(max_len), int(min_len),
+                                     _ptr(clip_labels), _ptr(idx), B, int(n_fft), int(hop),
+                                     int(n_bins), int(Nt), _ptr(farr), _ptr(tarr), C.byref(aug),
+                                     _ptr(out), _ptr(labels_out), _ptr(meta), _stream(waves)),
+              "pca_frame_points")
+    return (out, labels_out, meta) if want_meta else (out, labels_out)
+
+
 def select_points(X: torch.Tensor, key: torch.Tensor, K: int,
                   lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                   sel: Optional[torch.Tensor] = None):
