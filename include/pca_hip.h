@@ -307,6 +307,76 @@ int pca_frame_points(const float* waves, const int64_t* wave_off, const int64_t*
                      const float* farr, const float* tarr, const PcaFrameAug* aug, float* out,
                      int64_t* labels_out, int32_t* meta_out, void* stream);
 
+/* Root mean square of every clip of a corpus: rms_out[c] = sqrt(sum x^2 / L_c) (device double[n_clips]; 0
+ * for an empty clip).  What pca_frame_points_ex scales a background by.  One workgroup per clip, the
+ * squares (exact in fp64) summed in fp64 in a fixed order, no atomics: the same clip gives the same bits.
+ * max_len: the longest clip (host value, as pca_stft_logmag_batch takes it). */
+int pca_clip_rms(const float* waves, const int64_t* wave_off, int n_clips, int64_t max_len,
+                 double* rms_out, void* stream);
+
+#define PCA_FRAME_MAX_SPEEDS 8
+
+/* The random part of a framed batch with speed change and background mix.  The first seven fields are
+ * PcaFrameAug's, with the same meaning and the same draws (0: shift, 1: level, 2: window length).
+ * Speed is off when n_speed == 1 and ratios[0] == 1.0; mixing is off when mix_prob == 0 or bg_waves is
+ * NULL.  A field that is off draws nothing and is exact. */
+typedef struct PcaFrameAugEx {
+  int32_t jitter;
+  float gain_db;
+  const int32_t* win_lengths;
+  int32_t n_win;
+  int32_t norm_mode;
+  uint64_t seed, draw;
+  const int32_t* draw_dev;
+  /* speed change: draw 3 picks one of n_speed ratios, uniformly */
+  int32_t n_speed;             /* 1 .. PCA_FRAME_MAX_SPEEDS */
+  int32_t nwin;                /* entries per filter table (> 1 when a table is read) */
+  int32_t num_table;           /* table entries per zero crossing (> 0) */
+  int32_t n_bg;                /* background clips */
+  double ratios[PCA_FRAME_MAX_SPEEDS]; /* ratio = 1 / playback speed = new length / old length, each
+                                  in [0.5, 2.0]; 1.0 exactly: the plain load, no table read */
+  const double* tables;        /* device double [n_speed][2][nwin]: win and delta of ratio k exactly as
+                                  pca_resample takes them (win pre-scaled by min(1, ratio)); nullable when
+                                  every ratio is 1.0 */
+  /* background mix: draw 4 decides (u < mix_prob); in a slot that mixes draw 5 is the background clip
+   * c2 (uniform over n_bg), draw 6 its start p (uniform in [0, Lb)), draw 7 the SNR (uniform in
+   * [snr_lo_db, snr_hi_db)) */
+  const float* bg_waves;       /* device: the background clips back to back */
+  const int64_t* bg_off;       /* device int64[n_bg + 1]: their sample offsets */
+  const double* bg_rms;        /* device double[n_bg]: pca_clip_rms of the background corpus */
+  const double* clip_rms;      /* device double[n_clips]: pca_clip_rms of the corpus */
+  int64_t bg_max_len;          /* the longest background clip (host value): meta holds int32 starts */
+  double mix_prob;             /* in [0, 1] */
+  double snr_lo_db, snr_hi_db; /* finite, lo <= hi */
+} PcaFrameAugEx;
+
+/* pca_frame_points with a speed change and a background mix applied to the samples while the frame is
+ * loaded into LDS; everything else - arguments, set lookup, clamps, stream, transform, rows - is
+ * pca_frame_points', and with speed and mix off the rows, labels and meta[:, 0:4] are its bits.
+ * replaces: nothing (the reference has no augmentation).
+ * Batch slot b = set s of clip c (L samples), shift delta, gain g, window w as pca_frame_points draws them:
+ *   speed   ratio r = ratios[draw 3].  y[t], t < Ly = (int64)((double)L * r), is pca_resample's output
+ *           sample t for (clip, n_in = L, ratio r, gain 1.0f) - the same code, so the same fp32 value -
+ *           computed for the samples the frame needs and never stored; r == 1.0: y is the clip, Ly = L.
+ *   centres q0 = floor((double)(s*Nt*hop + delta) * r + 0.5) (r == 1.0: the integer itself); frame j has
+ *           its centre at clamp(q0 + j*hop, 0, Ly) in y's timeline, and its sample n is y at
+ *           centre - n_fft/2 + n under pca_frame_points' reflect rule on [0, Ly).  Requires
+ *           (int64)(min_len * smallest ratio) > n_fft/2.
+ *   mix     alpha = (float)(clip_rms[c] / bg_rms[c2] * 10^(-snr/20)), 0 when either RMS is 0;
+ *           sample = (float)((double)y + (double)alpha * (double)bg[c2][(p + j*hop + n) mod Lb]): the
+ *           background is read circularly, at its own speed.  A slot that does not mix, or whose alpha
+ *           is 0, uses y itself and reads no background.
+ *   then    (double)sample * hann_w * (double)g, the fp64 FFT, the rows, as pca_frame_points.
+ * samples_out (nullable) float32 [B, Nt, n_fft] receives `sample`.  meta_out (nullable) int32 [B, 8] =
+ * (c, clamped centre of frame 0 in y's timeline, w, bits of g, speed index, c2 or -1, p, bits of alpha).
+ * Grid (Nt, B), 256 threads, 24 B * n_fft of LDS, no atomics: the same arguments give the same bits.  The
+ * filter taps (about 32 / min(1, r) per sample) are read through L2, as pca_resample reads them. */
+int pca_frame_points_ex(const float* waves, const int64_t* wave_off, const int64_t* set_off,
+                        int n_clips, int64_t max_len, int64_t min_len, const int64_t* clip_labels,
+                        const int64_t* idx, int B, int n_fft, int hop, int n_bins, int Nt,
+                        const float* farr, const float* tarr, const PcaFrameAugEx* aug, float* out,
+                        int64_t* labels_out, int32_t* meta_out, float* samples_out, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Fixed-input baselines (eval-mode forward; training stays stock PyTorch)    *
  * ------------------------------------------------------------------------- */

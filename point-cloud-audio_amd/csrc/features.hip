@@ -9,6 +9,7 @@
 // here the spectrogram stays resident in HBM and a batch is assembled by one launch.
 #include "pca_common.h"
 #include "pack_body.hpp"
+#include "resample_body.hpp"
 #include "stft_body.hpp"
 
 #include <mutex>
@@ -50,9 +51,8 @@ __global__ __launch_bounds__(256) void k_stft_logmag(const float* __restrict__ w
     out[f * stride_f + t * stride_t] = stft_logmag_bin(x[f], inv);
 }
 
-// Smith's band-limited interpolation (resampy's resample_f restated): one thread per output sample,
-// both wings of the filter, table entries linearly interpolated, fp64 accumulation.  Per output sample
-// 2 * num_zeros / min(1, ratio) input samples are read (L2-resident: neighbouring threads share them).
+// Smith's band-limited interpolation (resampy's resample_f restated): one thread per output sample;
+// the sample itself is resample_body.hpp, shared with k_frame_points_ex.
 __global__ __launch_bounds__(256) void k_resample(const float* __restrict__ x, int64_t n_in, double ratio,
                                                   const double* __restrict__ win,
                                                   const double* __restrict__ delta, int nwin,
@@ -60,36 +60,7 @@ __global__ __launch_bounds__(256) void k_resample(const float* __restrict__ x, i
                                                   int64_t n_out) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_out) return;
-  const double scale = ratio < 1.0 ? ratio : 1.0;
-  const int index_step = (int)(scale * num_table);
-  const double time_register = (double)t / ratio;
-  const int64_t n = (int64_t)time_register;
-  double acc = 0.0;
-  {   // left wing: x[n], x[n - 1], ...
-    const double frac = scale * (time_register - (double)n);
-    const double index_frac = frac * num_table;
-    const int offset = (int)index_frac;
-    const double eta = index_frac - offset;
-    int64_t i_max = (nwin - offset) / index_step;
-    if (n + 1 < i_max) i_max = n + 1;
-    for (int64_t i = 0; i < i_max; ++i) {
-      const int k = offset + (int)i * index_step;
-      acc += (win[k] + eta * delta[k]) * (double)x[n - i];
-    }
-  }
-  {   // right wing: x[n + 1], x[n + 2], ...
-    const double frac = scale - scale * (time_register - (double)n);
-    const double index_frac = frac * num_table;
-    const int offset = (int)index_frac;
-    const double eta = index_frac - offset;
-    int64_t k_max = (nwin - offset) / index_step;
-    if (n_in - n - 1 < k_max) k_max = n_in - n - 1;
-    for (int64_t k2 = 0; k2 < k_max; ++k2) {
-      const int k = offset + (int)k2 * index_step;
-      acc += (win[k] + eta * delta[k]) * (double)x[n + k2 + 1];
-    }
-  }
-  y[t] = (float)(acc * (double)gain);
+  y[t] = resample_sample(x, n_in, ratio, win, delta, nwin, num_table, gain, t);
 }
 
 __global__ __launch_bounds__(256) void k_pack(const PackJob a) {

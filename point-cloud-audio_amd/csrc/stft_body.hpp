@@ -1,5 +1,6 @@
-// One STFT frame in LDS, shared by k_stft_logmag (features.hip: the whole-corpus pre-pass) and
-// k_frame_points (frame_points.hip: frames cut from the resident waveform per batch), so that both
+// One STFT frame in LDS, shared by k_stft_logmag (features.hip: the whole-corpus pre-pass),
+// k_frame_points (frame_points.hip: frames cut from the resident waveform per batch) and
+// k_frame_points_ex (frame_points_ex.hip: the same with speed change and background mix), so that all
 // give the same bits for the same frame.
 //
 // In-place radix-2 decimation-in-time FFT in float64: librosa computes the transform in double
@@ -14,34 +15,58 @@ namespace pca {
 
 inline size_t stft_lds_bytes(int n_fft) { return ((size_t)n_fft + n_fft / 2) * sizeof(double2); }
 
-// Transform of the n_fft samples of the reflect-padded signal that begin at `start` (a frame of
-// centre c begins at c - n_fft/2), times the periodic Hann of win_length samples centred and
-// zero-padded to n_fft, times `gain` (1.0: an exact no-op).  256 threads; x[n_fft] and tw[n_fft/2]
-// are LDS; on return x[f] holds bin f and the workgroup is past a barrier.
-__device__ __forceinline__ void stft_frame_fft(double2* x, double2* tw,
-                                               const float* __restrict__ wave, int64_t L,
-                                               int64_t start, int n_fft, int log2n, int win_length,
-                                               double gain, int tid) {
-  const int lpad = (n_fft - win_length) / 2;
-  const int half = n_fft >> 1;
+// The frame comes in two stages so that a kernel can supply its own samples (frame_points_ex.hip
+// resamples and mixes them on the way in): a load stage that fills tw and the bit-reversed, windowed
+// x, and the butterfly stage.  stft_frame_fft is the two back to back with the plain load.
 
+// tw[k] = exp(-2 pi i k / n_fft), k < n_fft/2
+__device__ __forceinline__ void stft_twiddles(double2* tw, int n_fft, int tid) {
+  const int half = n_fft >> 1;
   for (int k = tid; k < half; k += 256) {
     double sn, cs;
     sincospi(-2.0 * (double)k / (double)n_fft, &sn, &cs);
     tw[k] = make_double2(cs, sn);
   }
-  for (int n = tid; n < n_fft; n += 256) {
-    int64_t src = start + n;
-    if (src < 0) src = -src;
-    if (src >= L) src = 2 * (L - 1) - src;
-    if (src < 0) src = 0;  // only reachable when L <= n_fft/2 (rejected on the host)
-    const int nw = n - lpad;
-    double w = 0.0;
-    if (nw >= 0 && nw < win_length)
-      w = 0.5 - 0.5 * cospi(2.0 * (double)nw / (double)win_length);   // periodic Hann
-    const int r = (int)(__brev((unsigned)n) >> (32 - log2n));          // bit-reversed slot
-    x[r] = make_double2((double)wave[src] * w * gain, 0.0);
-  }
+}
+
+// sample n of the frame -> its bit-reversed slot of x, times the periodic Hann of win_length samples
+// centred and zero-padded to n_fft, times `gain`
+__device__ __forceinline__ void stft_store_sample(double2* x, int n, float sample, int n_fft, int log2n,
+                                                  int win_length, double gain) {
+  const int lpad = (n_fft - win_length) / 2;
+  const int nw = n - lpad;
+  double w = 0.0;
+  if (nw >= 0 && nw < win_length)
+    w = 0.5 - 0.5 * cospi(2.0 * (double)nw / (double)win_length);   // periodic Hann
+  const int r = (int)(__brev((unsigned)n) >> (32 - log2n));          // bit-reversed slot
+  x[r] = make_double2((double)sample * w * gain, 0.0);
+}
+
+// index i of a signal of L samples under reflect padding (numpy's "reflect": the edge sample is not
+// repeated)
+__device__ __forceinline__ int64_t stft_reflect(int64_t src, int64_t L) {
+  if (src < 0) src = -src;
+  if (src >= L) src = 2 * (L - 1) - src;
+  if (src < 0) src = 0;  // only reachable when L <= n_fft/2 (rejected on the host)
+  return src;
+}
+
+// Load stage: the n_fft samples of the reflect-padded signal that begin at `start` (a frame of
+// centre c begins at c - n_fft/2).  No barrier: the butterfly stage begins with one.
+__device__ __forceinline__ void stft_frame_load(double2* x, double2* tw,
+                                                const float* __restrict__ wave, int64_t L,
+                                                int64_t start, int n_fft, int log2n, int win_length,
+                                                double gain, int tid) {
+  stft_twiddles(tw, n_fft, tid);
+  for (int n = tid; n < n_fft; n += 256)
+    stft_store_sample(x, n, wave[stft_reflect(start + n, L)], n_fft, log2n, win_length, gain);
+}
+
+// Butterfly stage: in-place transform of the loaded frame.  256 threads; on return x[f] holds bin f
+// and the workgroup is past a barrier.
+__device__ __forceinline__ void stft_frame_butterflies(double2* x, const double2* tw, int n_fft,
+                                                       int log2n, int tid) {
+  const int half = n_fft >> 1;
   __syncthreads();
 
   for (int s = 1; s <= log2n; ++s) {
@@ -60,6 +85,18 @@ __device__ __forceinline__ void stft_frame_fft(double2* x, double2* tw,
     }
     __syncthreads();
   }
+}
+
+// Transform of the n_fft samples of the reflect-padded signal that begin at `start`, times the
+// periodic Hann of win_length samples centred and zero-padded to n_fft, times `gain` (1.0: an exact
+// no-op).  256 threads; x[n_fft] and tw[n_fft/2] are LDS; on return x[f] holds bin f and the
+// workgroup is past a barrier.
+__device__ __forceinline__ void stft_frame_fft(double2* x, double2* tw,
+                                               const float* __restrict__ wave, int64_t L,
+                                               int64_t start, int n_fft, int log2n, int win_length,
+                                               double gain, int tid) {
+  stft_frame_load(x, tw, wave, L, start, n_fft, log2n, win_length, gain, tid);
+  stft_frame_butterflies(x, tw, n_fft, log2n, tid);
 }
 
 // log(1e-8 + |v| * inv) of one bin, inv = 1 / norm

@@ -402,10 +402,19 @@ class ESC_wave_pc(Dataset):
     gain_db      a level change of up to +-gain_db dB
     win_lengths  a window length drawn out of this sequence (each in [1, n_fft]; None: n_fft).  The first
                  entry is the nominal one: what ``plain()`` uses
+    speeds       a playback speed drawn out of this sequence (up to 8, each in [0.5, 2.0]; None: 1.0): the
+                 clip resampled by 1 / speed (``pca_hip.resample``'s filter) while the frame is cut, which
+                 moves its content along the frequency axis.  The first entry is the nominal one;
+                 ``plain()`` uses 1.0
+    mix_clips    background waveforms (a list, or "self": the dataset's own clips), one of which is added
+                 with probability ``mix_prob``, read circularly from a random start, at a signal-to-noise
+                 ratio (clip RMS over background RMS) uniform in ``mix_snr_db`` = (lo, hi) dB.  Labels
+                 stay those of the clip
 
     drawn from the counter-based device stream (seed, draw number, batch slot, set), as
     ``ESC_pc_temp_randKSS`` draws its points.  With all three off the batches are bit for bit those of
-    ``ESC_pc`` over ``pca_hip.stft_logmag_batch`` of the same clips.
+    ``ESC_pc`` over ``pca_hip.stft_logmag_batch`` of the same clips.  With speeds and mix off a batch is
+    one pca_frame_points launch; with either on, one pca_frame_points_ex launch.
 
     clips  list of 1-D float32 waveforms (numpy or torch, host or device), each longer than n_fft / 2
     y      one label per clip
@@ -414,9 +423,11 @@ class ESC_wave_pc(Dataset):
     _ntemp = 1
 
     def __init__(self, clips, y, fs, n_fft, hop=None, drop_nyquist=False, jitter=0, gain_db=0.0,
-                 win_lengths=None, norm="n_fft", seed=0, device=None):
+                 win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
+                 mix_prob=0.0, mix_snr_db=(0.0, 20.0)):
         self._setup(clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                     device)
+        self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db)
 
     def _setup(self, clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                device):
@@ -445,6 +456,39 @@ class ESC_wave_pc(Dataset):
         # label of every set (what ESC_pc calls labels)
         self.labels = np.repeat(self.clip_labels, np.diff(self.set_off))
 
+    def _setup_ex(self, speeds, mix_clips, mix_prob, mix_snr_db):
+        """Speed change and background mix: checked here, on the host, like win_lengths."""
+        self.speeds = (1.0,) if speeds is None else tuple(float(v) for v in speeds)
+        if not 1 <= len(self.speeds) <= 8 or not all(0.5 <= v <= 2.0 for v in self.speeds):
+            raise ValueError(f"speeds {self.speeds}: 1 to 8 values, each in [0.5, 2.0]")
+        self.ratios = tuple(1.0 / v for v in self.speeds)
+        self.mix_prob = float(mix_prob)
+        if not 0.0 <= self.mix_prob <= 1.0:
+            raise ValueError(f"mix_prob {mix_prob} outside [0, 1]")
+        lo, hi = (float(v) for v in mix_snr_db)
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+            raise ValueError(f"mix_snr_db {mix_snr_db}: finite (lo, hi) with lo <= hi")
+        self.mix_snr_db = (lo, hi)
+        if self.mix_prob > 0.0 and mix_clips is None:
+            raise ValueError("mix_prob > 0 needs mix_clips (a list of waveforms, or 'self')")
+        if isinstance(mix_clips, str) and mix_clips != "self":
+            raise ValueError(f"mix_clips is a list of waveforms or 'self', got {mix_clips!r}")
+        self.mix_clips = mix_clips if mix_clips is None or isinstance(mix_clips, str) else list(mix_clips)
+        if isinstance(self.mix_clips, list) and (
+                not self.mix_clips or any(int(c.shape[0]) < 1 for c in self.mix_clips)):
+            raise ValueError("mix_clips: at least one waveform, none of them empty")
+        if self._speed_on and int(self._min_len * min(self.ratios)) <= self.n_fft // 2:
+            raise ValueError(f"speeds {self.speeds}: the shortest clip ({self._min_len} samples) at speed "
+                             f"{max(self.speeds)} is no longer than n_fft / 2 = {self.n_fft // 2}")
+
+    @property
+    def _speed_on(self) -> bool:
+        return self.speeds != (1.0,)
+
+    @property
+    def _mix_on(self) -> bool:
+        return self.mix_prob > 0.0 and self.mix_clips is not None
+
     def __len__(self):
         return self.set_off[-1]
 
@@ -458,7 +502,8 @@ class ESC_wave_pc(Dataset):
     def stochastic(self) -> bool:
         """True when any augmentation is on: every call must then draw anew, so a caller that
         captures ``batch`` into a hipGraph passes ``draw_dev`` (see ``_TempSS.stochastic``)."""
-        return self.jitter > 0 or self.gain_db > 0.0 or len(self.win_lengths) > 1
+        return (self.jitter > 0 or self.gain_db > 0.0 or len(self.win_lengths) > 1
+                or self._speed_on or self._mix_on)
 
     def plain(self, win_length=None):
         """A view on the same resident waveforms with every augmentation off: deterministic, the
@@ -466,6 +511,7 @@ class ESC_wave_pc(Dataset):
         ``Evaluator`` and ``fit(test_dataset=...)`` take."""
         v = copy.copy(self)
         v.jitter, v.gain_db = 0, 0.0
+        v.speeds, v.ratios, v.mix_prob = (1.0,), (1.0,), 0.0
         v.win_lengths = (self.win_lengths[0] if win_length is None else int(win_length),)
         if not 1 <= v.win_lengths[0] <= self.n_fft:
             raise ValueError(f"win_length {v.win_lengths[0]} outside [1, n_fft = {self.n_fft}]")
@@ -483,6 +529,8 @@ class ESC_wave_pc(Dataset):
                                   None if self.tarr is None else f32(self.tarr),
                                   i64(self.clip_labels))
             self._store["win"] = {}
+            if self._mix_on:              # the RMS vectors and the background corpus: once, here
+                self._mix_resident()
         return self._store["res"]
 
     def _win_dev(self, dev):
@@ -491,12 +539,47 @@ class ESC_wave_pc(Dataset):
                                                                  device=dev)
         return self._store["win"][self.win_lengths]
 
+    def _mix_resident(self):
+        """The background corpus and both RMS vectors, computed once and kept in the shared store:
+        (clip_rms, bg_waves, bg_off, bg_rms, bg_max_len)."""
+        if "mix" not in self._store:
+            waves, woff = self._resident()[:2]
+            rms = pca_hip.clip_rms(waves, woff, self._max_len)
+            if self.mix_clips == "self":
+                self._store["mix"] = (rms, waves, woff, rms, self._max_len)
+            else:
+                lens = [int(c.shape[0]) for c in self.mix_clips]
+                bg = torch.cat([torch.as_tensor(c).to(waves.device, torch.float32).reshape(-1)
+                                for c in self.mix_clips])
+                boff = torch.as_tensor(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+                                       ).to(waves.device)
+                self._store["mix"] = (rms, bg, boff, pca_hip.clip_rms(bg, boff, max(lens)), max(lens))
+        return self._store["mix"]
+
     def batch(self, idx: torch.Tensor, out=None, labels_out=None, draw_dev=None,
-              want_meta: bool = False):
+              want_meta: bool = False, want_samples: bool = False):
         """idx int64[B] on the device -> (points [B, num_points, 2 or 3] float32, labels int64[B]
-        [, meta int32 [B, 4] = (clip, centre sample of frame 0, window length, bits of the gain)])."""
+        [, meta int32 [B, 4] = (clip, centre sample of frame 0, window length, bits of the gain)]).
+        With ``speeds`` or the mix on, meta is int32 [B, 8] (pca_hip.frame_points_ex: + speed index,
+        background clip or -1, its start, bits of its scale) and ``want_samples`` adds the float32
+        [B, Ntemp, n_fft] samples of every frame before window and gain."""
         waves, woff, soff, f32, t32, lab = self._resident()
         self._draw += 1
+        if self._speed_on or self._mix_on:
+            mix = {}
+            if self._mix_on:
+                rms, bg, boff, brms, bmax = self._mix_resident()
+                mix = dict(clip_rms=rms, bg_waves=bg, bg_off=boff, bg_rms=brms, bg_max_len=bmax,
+                           mix_prob=self.mix_prob, mix_snr_db=self.mix_snr_db)
+            return pca_hip.frame_points_ex(
+                waves, woff, soff, idx, self.n_fft, self.hop, self.F, f32, t32, self._ntemp,
+                max_len=self._max_len, min_len=self._min_len, clip_labels=lab,
+                jitter=self.jitter, gain_db=self.gain_db, win_lengths=self._win_dev(waves.device),
+                norm_mode=pca_hip.NORM_WIN if self.norm == "win" else pca_hip.NORM_NFFT,
+                seed=self.seed, draw=self._draw, ratios=self.ratios, out=out, labels_out=labels_out,
+                draw_dev=draw_dev, want_meta=want_meta, want_samples=want_samples, **mix)
+        if want_samples:
+            raise ValueError("want_samples needs speeds or the mix on (pca_hip.frame_points_ex)")
         return pca_hip.frame_points(
             waves, woff, soff, idx, self.n_fft, self.hop, self.F, f32, t32, self._ntemp,
             max_len=self._max_len, min_len=self._min_len, clip_labels=lab,
@@ -522,10 +605,12 @@ class ESC_wave_pc_temp(ESC_wave_pc):
     ``hop`` apart and ``tarr`` keeps its meaning.  Arguments as ``ESC_wave_pc``."""
 
     def __init__(self, clips, y, fs, n_fft, Ntemp, hop=None, jitter=0, gain_db=0.0,
-                 win_lengths=None, norm="n_fft", seed=0, device=None):
+                 win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
+                 mix_prob=0.0, mix_snr_db=(0.0, 20.0)):
         self._ntemp = int(Ntemp)
         assert self._ntemp >= 1
         self._setup(clips, y, fs, n_fft, hop, True, jitter, gain_db, win_lengths, norm, seed, device)
+        self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db)
         self.tarr = np.linspace(0, (self.hop / fs) * self._ntemp, self._ntemp)
 
 

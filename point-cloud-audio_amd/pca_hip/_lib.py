@@ -59,6 +59,18 @@ class PcaFrameAug(C.Structure):
                 ("draw", C.c_uint64), ("draw_dev", C.c_void_p)]
 
 
+FRAME_MAX_SPEEDS = 8
+
+
+class PcaFrameAugEx(C.Structure):
+    _fields_ = PcaFrameAug._fields_ + [
+        ("n_speed", C.c_int32), ("nwin", C.c_int32), ("num_table", C.c_int32), ("n_bg", C.c_int32),
+        ("ratios", C.c_double * FRAME_MAX_SPEEDS), ("tables", C.c_void_p),
+        ("bg_waves", C.c_void_p), ("bg_off", C.c_void_p), ("bg_rms", C.c_void_p),
+        ("clip_rms", C.c_void_p), ("bg_max_len", C.c_int64), ("mix_prob", C.c_double),
+        ("snr_lo_db", C.c_double), ("snr_hi_db", C.c_double)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64),
                 ("sa_m", C.c_int64), ("sa_k", C.c_int64), ("sb_k", C.c_int64),
@@ -139,6 +151,10 @@ SIGNATURES = {
     "pca_frame_points": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p, c_i64p,
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp,
                                    C.POINTER(PcaFrameAug), c_fp, c_i64p, c_vp, c_vp]),
+    "pca_clip_rms": (C.c_int, [c_fp, c_i64p, C.c_int, C.c_int64, c_vp, c_vp]),
+    "pca_frame_points_ex": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p, c_i64p,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp,
+                                      C.POINTER(PcaFrameAugEx), c_fp, c_i64p, c_vp, c_fp, c_vp]),
     "pca_baseline_param_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, c_vp, C.c_int, C.c_int]),
     "pca_fb_forward": (C.c_int, [c_fp, C.c_int64, C.c_int64, c_i64p, C.c_int, C.c_int, c_vp,
                                  C.c_int, C.c_int, c_fp, C.c_int64, C.c_int, C.c_int, C.c_uint64,

@@ -789,6 +789,126 @@ def frame_points(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.Ten
     return (out, labels_out, meta) if want_meta else (out, labels_out)
 
 
+def clip_rms(waves: torch.Tensor, wave_off: torch.Tensor, max_len: int) -> torch.Tensor:
+    """Root mean square of every clip of a corpus on the device (pca_clip_rms): waves float32, the
+    clips back to back, wave_off int64[n_clips + 1] their offsets, max_len the longest one.  Returns
+    float64[n_clips], fp64 sums in a fixed order (bit-reproducible); an empty clip gives 0."""
+    _need_cuda(waves, wave_off)
+    assert waves.dtype == torch.float32 and waves.is_contiguous()
+    assert wave_off.dtype == torch.int64 and wave_off.is_contiguous() and wave_off.numel() >= 2
+    n = wave_off.numel() - 1
+    with torch.cuda.device(waves.device):
+        out = torch.empty(n, dtype=torch.float64, device=waves.device)
+        check(lib().pca_clip_rms(_ptr(waves), _ptr(wave_off), n, int(max_len), _ptr(out),
+                                 _stream(waves)), "pca_clip_rms")
+    return out
+
+
+_speed_tables = {}
+
+
+def _speed_filter(ratios, device):
+    """The filter tables of pca_frame_points_ex: float64 [n_speed, 2, nwin] (win, delta) of
+    ``_resample_filter``, one pair per ratio (zeros for a ratio of 1.0: never read), cached per
+    (ratios, device).  Returns (tables or None when every ratio is 1.0, nwin, num_table)."""
+    key = (tuple(ratios), str(device))
+    if key not in _speed_tables:
+        if all(r == 1.0 for r in ratios):
+            _speed_tables[key] = (None, 0, 0)
+        else:
+            pairs, num_table = {}, 0
+            for r in ratios:
+                if r != 1.0:
+                    win, delta, num_table = _resample_filter(r, device, dict(KAISER_FAST))
+                    pairs[r] = torch.stack([win, delta])
+            nwin = next(iter(pairs.values())).shape[1]
+            zero = torch.zeros((2, nwin), dtype=torch.float64, device=device)
+            tables = torch.stack([pairs.get(r, zero) for r in ratios]).contiguous()
+            _speed_tables[key] = (tables, nwin, num_table)
+    return _speed_tables[key]
+
+
+def frame_points_ex(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.Tensor,
+                    idx: torch.Tensor, n_fft: int, hop: int, n_bins: int, farr: torch.Tensor,
+                    tarr: Optional[torch.Tensor] = None, Nt: int = 1, *, max_len: int, min_len: int,
+                    clip_labels: Optional[torch.Tensor] = None, jitter: int = 0,
+                    gain_db: float = 0.0, win_lengths: Optional[torch.Tensor] = None,
+                    norm_mode: int = NORM_NFFT, seed: int = 0, draw: int = 0,
+                    ratios=(1.0,), clip_rms: Optional[torch.Tensor] = None,
+                    bg_waves: Optional[torch.Tensor] = None, bg_off: Optional[torch.Tensor] = None,
+                    bg_rms: Optional[torch.Tensor] = None, bg_max_len: int = 0,
+                    mix_prob: float = 0.0, mix_snr_db=(0.0, 0.0),
+                    out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None,
+                    draw_dev: Optional[torch.Tensor] = None, want_meta: bool = False,
+                    want_samples: bool = False):
+    """``frame_points`` with a speed change and a background mix applied while the frame is loaded
+    (pca_frame_points_ex); the arguments they share mean the same, and with ``ratios == (1.0,)`` and
+    ``mix_prob == 0`` (or no ``bg_waves``) the points, labels and meta[:, :4] are ``frame_points``' bits.
+
+    ratios      up to 8 resampling ratios (new length / old length = 1 / playback speed), each in
+                [0.5, 2.0]; one per batch slot, uniformly.  The resampler is ``pca_hip.resample``'s
+                (kaiser_fast), evaluated for the samples the frame needs.
+    bg_waves / bg_off int64[n_bg + 1] / bg_rms float64[n_bg] / bg_max_len   the background corpus, laid
+                out as waves / wave_off, with ``clip_rms`` of it; ``clip_rms`` float64[n_clips] that of
+                the main corpus.  A slot mixes with probability ``mix_prob``: one background clip, read
+                circularly from a random start, at an SNR uniform in ``mix_snr_db`` = (lo, hi) dB.
+    Returns (points, labels or None [, meta int32 [B, 8] = (clip, centre of frame 0 in the resampled
+    clip, window length, bits of the gain, speed index, background clip or -1, its start, bits of the
+    fp32 background scale)] [, samples float32 [B, Nt, n_fft]: the frames before window and gain])."""
+    _need_cuda(waves, wave_off, set_off, idx, farr, clip_rms, bg_waves, bg_off, bg_rms)
+    assert waves.dtype == torch.float32 and waves.is_contiguous() and farr.dtype == torch.float32
+    assert wave_off.dtype == set_off.dtype == idx.dtype == torch.int64
+    assert wave_off.numel() == set_off.numel() >= 2 and farr.numel() >= n_bins
+    din = 2
+    if tarr is not None:
+        _need_cuda(tarr)
+        assert tarr.dtype == torch.float32 and tarr.numel() >= Nt
+        din = 3
+    B = idx.numel()
+    n_clips = wave_off.numel() - 1
+    ratios = tuple(float(r) for r in ratios)
+    if not 1 <= len(ratios) <= _lib.FRAME_MAX_SPEEDS:
+        raise _lib.PcaHipError(f"frame_points_ex: {len(ratios)} ratios (1 .. {_lib.FRAME_MAX_SPEEDS})")
+    n_bg = 0
+    if bg_waves is not None:
+        assert bg_waves.dtype == torch.float32 and bg_waves.is_contiguous()
+        assert bg_off is not None and bg_off.dtype == torch.int64 and bg_off.is_contiguous()
+        n_bg = bg_off.numel() - 1
+        assert bg_rms is None or (bg_rms.dtype == torch.float64 and bg_rms.numel() == n_bg)
+        assert clip_rms is None or (clip_rms.dtype == torch.float64 and clip_rms.numel() == n_clips)
+    with torch.cuda.device(waves.device):
+        tables, nwin, num_table = _speed_filter(ratios, waves.device)
+        if win_lengths is None:
+            win_lengths = torch.tensor([n_fft], dtype=torch.int32, device=waves.device)
+        assert win_lengths.is_cuda and win_lengths.dtype == torch.int32
+        if out is None:
+            out = torch.empty((B, Nt * n_bins, din), dtype=torch.float32, device=waves.device)
+        if clip_labels is not None and labels_out is None:
+            labels_out = torch.empty(B, dtype=torch.int64, device=waves.device)
+        meta = torch.empty((B, 8), dtype=torch.int32, device=waves.device) if want_meta else None
+        samples = (torch.empty((B, Nt, n_fft), dtype=torch.float32, device=waves.device)
+                   if want_samples else None)
+        aug = _lib.PcaFrameAugEx(
+            int(jitter), float(gain_db), win_lengths.data_ptr(), win_lengths.numel(), int(norm_mode),
+            int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1), _draw_ptr(draw_dev),
+            len(ratios), int(nwin), int(num_table), int(n_bg),
+            (C.c_double * _lib.FRAME_MAX_SPEEDS)(*ratios), _ptr(tables),
+            _ptr(bg_waves), _ptr(bg_off), _ptr(bg_rms), _ptr(clip_rms), int(bg_max_len),
+            float(mix_prob), float(mix_snr_db[0]), float(mix_snr_db[1]))
+        check(lib().pca_frame_points_ex(_ptr(waves), _ptr(wave_off), _ptr(set_off), n_clips,
+                                        int(max_len), int(min_len), _ptr(clip_labels), _ptr(idx), B,
+                                        int(n_fft), int(hop), int(n_bins), int(Nt), _ptr(farr),
+                                        _ptr(tarr), C.byref(aug), _ptr(out), _ptr(labels_out),
+                                        _ptr(meta), _ptr(samples), _stream(waves)),
+              "pca_frame_points_ex")
+    ret = (out, labels_out)
+    if want_meta:
+        ret += (meta,)
+    if want_samples:
+        ret += (samples,)
+    return ret
+
+
 def select_points(X: torch.Tensor, key: torch.Tensor, K: int,
                   lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                   sel: Optional[torch.Tensor] = None):
