@@ -9,6 +9,8 @@
 #include "terminal_bodies.hpp"
 #include "slab_sum_body.hpp"
 
+#include <stdlib.h>
+
 namespace pca {
 
 namespace {
@@ -203,6 +205,44 @@ bool wgrad_slabs_on() {          // (read per call: a test switches it between t
 bool wgrad_fold_on() {           // (read per call, like the switch above)
   return env_not_zero("PCA_WGRAD_FOLD");
 }
+// PCA_WGRAD_RIDE: the bf16 list in the launch of layer 1's few-queries backward (k_mab0_small_ride);
+// unset = the measured default.  Read per call, like the switches above.
+constexpr bool WGRAD_RIDE_DEFAULT = true;
+bool wgrad_ride_on() {
+  const char* e = getenv("PCA_WGRAD_RIDE");
+  if (e == nullptr || e[0] == 0) return WGRAD_RIDE_DEFAULT;
+  return e[0] != '0';
+}
+// Every workgroup costs a 64 KiB slab (16384 atomics without the slabs): aim at ~200 workgroups over all
+// bf16 jobs (512 rows for one B*N-row job, 1024 for three, ...).  (Swept before k_wgrad128 kept several
+// tiles in flight, and kept because the partition fixes the summation order: 1024 beat 512 / 768 and 2048
+// at 3 x 65536 rows.)
+static int bf16_rows_per_wg(double rows) {
+  const int rpw = 512 * (int)((rows + 98303.0) / 98304.0);
+  return rpw < 512 ? 512 : (rpw > 1024 ? 1024 : rpw);
+}
+static size_t bf16_slab_cap(const BwdDefer& D) { return D.slab_cap * 3 / 4; }
+
+bool bwd_defer_ride(BwdDefer& D, WgradJobs* jobs, int* rows_per_wg, int* rc) {
+  *rc = PCA_OK;
+  if (!(wgrad_slabs_on() && D.slab_ws != nullptr && D.slab_cap > 0 && wgrad_fold_on() && wgrad_ride_on()))
+    return false;
+  if (D.wg_bf16.n == 0 || D.ride_done) return false;
+  double rows = 0;
+  for (int i = 0; i < D.wg_bf16.n; ++i) rows += (double)D.wg_bf16.j[i].M;
+  if (rows <= 0) return false;
+  *jobs = D.wg_bf16;
+  *rows_per_wg = bf16_rows_per_wg(rows);
+  D.ride_late.n = 0;
+  WgradSlabs sl{D.slab_ws, bf16_slab_cap(D), &D.ride_late, nullptr, 0};
+  *rc = wgrad128_place(*jobs, *rows_per_wg, &sl);
+  if (*rc != PCA_OK) return false;
+  D.ride_used = (sl.used + 255) & ~(size_t)255;
+  D.ride_done = 1;
+  D.wg_bf16.n = 0;
+  return true;
+}
+
 int bwd_defer_flush(BwdDefer& D, hipStream_t st) {
   // The sums the post stages read (D.sums: dG of the few-queries blocks) ride in the first
   // weight-gradient launch as extra workgroup rows.  Slab mode (the default when the caller lent
@@ -215,18 +255,31 @@ int bwd_defer_flush(BwdDefer& D, hipStream_t st) {
   const bool slab_mode = wgrad_slabs_on() && D.slab_ws != nullptr && D.slab_cap > 0;
   SlabSumJobs late{};
   size_t used = 0;          // the two lists' slabs lie back to back
+  if (D.ride_done) {        // the bf16 list ran already: its slabs lie first, its sums come first
+    PCA_REQUIRE(slab_mode && D.wg_bf16.n == 0, "bwd_defer_flush: bf16 jobs queued after the list ran");
+    late = D.ride_late;
+    used = D.ride_used;
+  }
   double rows = 0, rows_f32 = 0;
   for (int i = 0; i < D.wg_bf16.n; ++i) rows += (double)D.wg_bf16.j[i].M;
   for (int i = 0; i < D.wg_f32.n; ++i) rows_f32 += (double)D.wg_f32.j[i].M;
-  // every workgroup costs a 64 KiB slab (16384 atomics without the slabs): aim at ~200
-  // workgroups over all bf16 jobs (512 rows for one B*N-row job, 1024 for three, ...); the fp32
-  // jobs ([B*m] rows) take 128 rows per workgroup.  (Swept before k_wgrad128 kept several tiles in
-  // flight, and kept because the partition fixes the summation order: 1024 beat 512 / 768 and 2048
-  // at 3 x 65536 rows, 128 beat 64 and 256 for the fp32 list.)
-  int rpw = 512 * (int)((rows + 98303.0) / 98304.0);
-  rpw = rpw < 512 ? 512 : (rpw > 1024 ? 1024 : rpw);
+  // the fp32 jobs ([B*m] rows) take 128 rows per workgroup (128 beat 64 and 256, swept with the bf16
+  // list's rows above)
+  int rpw = bf16_rows_per_wg(rows);
   int rpw_f32 = 128;
-  const size_t cap_bf16 = D.slab_cap * 3 / 4;
+  const size_t cap_bf16 = bf16_slab_cap(D);
+  if (D.ride_done && rows_f32 > 0 && wgrad_fold_on()) {
+    // the same launch with an empty bf16 list: the fp32 jobs and the sums that are due now
+    WgradJobs f32 = D.wg_f32;
+    ProfScope ps(PCA_K_WGRAD, st, 2.0 * rows_f32 * 128 * 128, 8.0 * rows_f32 * 128);
+    WgradSlabs sf{D.slab_ws + used / sizeof(float), D.slab_cap - used, &late, nullptr, 0};
+    PCA_TRY(wgrad128_place(f32, rpw_f32, &sf));
+    used += (sf.used + 255) & ~(size_t)255;
+    PCA_TRY(wgrad128_launch_step(WgradJobs{}, rpw, f32, rpw_f32, D.sums, st));
+    ps.end();
+    D.wg_f32.n = 0;
+    D.sums.n = 0;
+  }
   if (rows > 0 && rows_f32 > 0 && wgrad_fold_on()) {
     // ONE launch (k_wgrad128_step): the fp32 jobs run beside the bf16 rows (which leave a quarter of
     // the compute units idle) instead of paying a launch boundary and a ramp of their own: 32 us
@@ -280,6 +333,9 @@ int bwd_defer_flush(BwdDefer& D, hipStream_t st) {
   PCA_TRY(terminal_launch(D, st, &late));
   D.posts.n = 0;
   D.has_cls = D.has_sw = 0;
+  D.ride_done = 0;
+  D.ride_used = 0;
+  D.ride_late.n = 0;
   return PCA_OK;
 }
 

@@ -59,8 +59,9 @@ int wgrad128_launch(const WgradJobs& jobs, bool g_bf16, bool a_bf16, int rows_pe
                     hipStream_t st, WgradSlabs* slabs = nullptr);
 // The two halves of wgrad128_launch for a caller that puts two lists into one launch: wgrad128_place
 // gives every job of a list its slabs (slab mode; rows_per_wg doubles until they fit `slabs->cap`) and
-// appends their sum jobs; wgrad128_launch_step runs a placed bf16 list (G, A bf16) and a placed fp32
-// list, each with its own rows per workgroup (>= 128), and the riders as ONE launch (k_wgrad128_step).
+// appends their sum jobs; wgrad128_launch_step runs a placed bf16 list (G, A bf16; empty when it ran
+// beside layer 1's few-queries backward: bwd_defer_ride) and a placed fp32 list, each with its own rows
+// per workgroup (>= 128), and the riders as ONE launch (k_wgrad128_step).
 int wgrad128_place(WgradJobs& jobs, int& rows_per_wg, WgradSlabs* slabs);
 int wgrad128_launch_step(const WgradJobs& bf16_jobs, int rows_per_wg_bf16, const WgradJobs& f32_jobs,
                          int rows_per_wg_f32, const SlabSumJobs& riders, hipStream_t st);
@@ -140,14 +141,25 @@ struct BwdDefer {
   ClsWgradArgs cls;
   SmallWgradArgs sw;
   int has_cls, has_sw;
+  // the bf16 list already ran, beside layer 1's few-queries backward (bwd_defer_ride): its sum jobs, and
+  // the bytes of slab_ws its partials take (the flush places the fp32 list behind them)
+  int ride_done;
+  size_t ride_used;
+  SlabSumJobs ride_late;
 };
 int bwd_defer_flush(BwdDefer& D, hipStream_t st);
+// Whether the bf16 list collected so far may run now, in the launch of layer 1's few-queries backward
+// (slab mode with room lent, the two lists folded, PCA_WGRAD_RIDE not 0); if so `jobs` receives the list
+// placed exactly as the flush would place it (same rows per workgroup, same slabs at the start of slab_ws)
+// and D records it as done.  The caller launches it (mab0_small_ride_launch).
+bool bwd_defer_ride(BwdDefer& D, WgradJobs* jobs, int* rows_per_wg, int* rc);
 // post stages + riders (`late`: sums nobody reads before the optimizer, e.g. weight gradients)
 int terminal_launch(const BwdDefer& D, hipStream_t st, const SlabSumJobs* late = nullptr);
 int wgrad256_flush_deferred(BwdDefer& D, hipStream_t st);       // d256_host.hip
 bool wgrad_slabs_on();       // reductions of the fused d = 128 path as slabs + fixed-order sums
                              // (PCA_WGRAD_SLABS=0: fp32 atomics)
 bool wgrad_fold_on();        // the two deferred d = 128 lists in one launch (PCA_WGRAD_FOLD=0: two)
+bool wgrad_ride_on();        // the bf16 list beside layer 1's few-queries backward (PCA_WGRAD_RIDE)
 // launch `jobs` now, or append them to the matching list of `defer`
 int wgrad128_defer(BwdDefer* defer, const WgradJobs& jobs, bool bf16, int rows_per_wg,
                    hipStream_t st);

@@ -22,6 +22,7 @@
 #include "mfma_common.hpp"
 #include "pma_head_bodies.hpp"
 #include "mid_bwd_body.hpp"
+#include "mab0_bwd_small_body.hpp"
 
 #include <math.h>
 #include <stdlib.h>
@@ -107,15 +108,6 @@ struct MidSinkWide {
     sDel[row] = delta;
     sLSE[row] = lse;
   }
-};
-constexpr int MID_SMALL_FUSE_IMG = (64 * 4 + 64) * 4;       // dTf [64][4] + Delta [64]
-constexpr int MID_SMALL_FUSE_LDS = MID_SMALL_FUSE_IMG + MID_BWD_SMALL_LDS + 2 * MID_BWD_W_LDS;
-struct MidSinkSmall {
-  float *sdTf, *sDel;       // [64][4], [64]
-  __device__ __forceinline__ void dTb(int, int, int, bf16x4) const {}
-  __device__ __forceinline__ void dTt(int, int, int, int, bf16x4) const {}
-  __device__ __forceinline__ void dTf(int row, int c, float v) const { sdTf[row * 4 + c] = v; }
-  __device__ __forceinline__ void stat(int row, float delta, float) const { sDel[row] = delta; }
 };
 
 template <int RP, bool ABF>
@@ -412,8 +404,7 @@ __global__ __launch_bounds__(256, 1) void k_mab0_bwd(const Mab0BwdArgs a) {
     out[i] = s0[i] + s0[RP * DK + i] + s0[2 * RP * DK + i] + s0[3 * RP * DK + i];
 }
 
-// layer 1 (dk <= 4): thread = (query row r, point partition); accumulates DG only.  The
-// set's points are staged in LDS chunk by chunk (coalesced) and re-read from there.
+// layer 1 (dk <= 4): mab0_bwd_small_body.hpp; gridDim.y workgroups share the rows of a set.
 // MID (R == 64, an ISAB's first few-queries block): dTf / Delta are not read; every workgroup of a set
 // runs the set's mid chain in the dynamic LDS block (MID_SMALL_FUSE_LDS bytes).  An instance of its own,
 // so that the plain kernel does not carry the chain's registers.
@@ -423,86 +414,11 @@ __global__ __launch_bounds__(256) void k_mab0_bwd_small(
     const float* __restrict__ LSE, const float* __restrict__ Delta, int N, int R, int Rp, int dk,
     float* __restrict__ DG, const int32_t* __restrict__ lengths, float* __restrict__ slabs,
     const MidBwdArgs mid) {
-  constexpr int CH = PCA_POINT_CHUNK;
   __shared__ float sD[256][4];
-  __shared__ __attribute__((aligned(16))) float sX[CH * 4];
+  __shared__ __attribute__((aligned(16))) float sX[PCA_POINT_CHUNK * 4];
   extern __shared__ __attribute__((aligned(16))) char smid[];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  // gridDim.y workgroups share the rows of a set: this one owns rows [row0, row0 + Rb)
-  const int Rb = R / gridDim.y, row0 = blockIdx.y * Rb;
-  const int parts = 256 / Rb;
-  const int rl = tid % Rb, part = tid / Rb;
-  const int r = row0 + rl;
-  constexpr float LN2 = 0.6931471805599453f;
-  float gk[4], dt[4], acc[4];
-  f32x2 acc2[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-  int len = N;
-  if (lengths != nullptr) len = lengths[b] < N ? lengths[b] : N;
-  float xr[16];
-  float lse, del;
-  if constexpr (MID) {
-    // the first chunk of points, G and the statistics are in flight while the mid chain runs
-#pragma unroll
-    for (int c = 0; c < 4; ++c) gk[c] = c < dk ? Gf[r * dk + c] : 0.f;
-    lse = LSE[(int64_t)b * R + r];
-    if (len > 0) fetch_points(X + (int64_t)b * N * dk, len < CH ? len : CH, dk, xr);
-    float* const sdTf = reinterpret_cast<float*>(smid);
-    float* const sDelta = sdTf + 64 * 4;
-    char* const base = smid + MID_SMALL_FUSE_IMG;
-    const MidBwdLds m{base, base + 16 * 256, base + 2 * 16 * 256, base + MID_BWD_SMALL_LDS,
-                      base + MID_BWD_SMALL_LDS + MID_BWD_W_LDS};
-    mid_bwd_body<true>(mid, b, m, blockIdx.y == 0, MidSinkSmall{sdTf, sDelta});
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 4; ++c) dt[c] = c < dk ? sdTf[r * 4 + c] : 0.f;
-    del = sDelta[r];
-  } else {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      gk[c] = c < dk ? Gf[r * dk + c] : 0.f;
-      dt[c] = c < dk ? dTf[((int64_t)b * R + r) * dk + c] : 0.f;
-    }
-    lse = LSE[(int64_t)b * R + r];
-    del = Delta[(int64_t)b * Rp + r];
-    if (len > 0) fetch_points(X + (int64_t)b * N * dk, len < CH ? len : CH, dk, xr);
-  }
-  for (int n0 = 0; n0 < len; n0 += CH) {
-    const int cn = (len - n0 < CH) ? len - n0 : CH;
-    // [pair of points][component][2] (as k_mab0_attn_small): two points per packed-fp32 instruction;
-    // unused components and the odd point of the chunk are zero (x = 0 contributes dS.x = 0); the
-    // next chunk's loads are in flight while this one is worked on
-    const int npairs = (cn + 1) >> 1;
-    commit_points(xr, cn, dk, sX);
-    if (n0 + CH < len)
-      fetch_points(X + ((int64_t)b * N + n0 + CH) * dk, (len - n0 - CH < CH) ? len - n0 - CH : CH, dk, xr);
-    if (part < parts) {
-#pragma unroll 4
-      for (int q = part; q < npairs; q += parts) {
-        const float4 lo = *reinterpret_cast<const float4*>(&sX[q * 8]);
-        const float4 hi = *reinterpret_cast<const float4*>(&sX[q * 8 + 4]);
-        const f32x2 x0 = {lo.x, lo.y}, x1 = {lo.z, lo.w}, x2 = {hi.x, hi.y}, x3 = {hi.z, hi.w};
-        const f32x2 sc = gk[0] * x0 + gk[1] * x1 + gk[2] * x2 + gk[3] * x3;
-        const f32x2 da = dt[0] * x0 + dt[1] * x1 + dt[2] * x2 + dt[3] * x3;
-        const f32x2 pe = {__builtin_amdgcn_exp2f(sc[0] - lse), __builtin_amdgcn_exp2f(sc[1] - lse)};
-        const f32x2 ds = (LN2 * pe) * (da - del);
-        acc2[0] += ds * x0; acc2[1] += ds * x1; acc2[2] += ds * x2; acc2[3] += ds * x3;
-      }
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) acc[c] = acc2[c][0] + acc2[c][1];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) sD[tid][c] = acc[c];
-  __syncthreads();
-  if (tid < Rb) {
-    for (int c = 0; c < dk; ++c) {
-      float v = 0.f;
-      for (int p = 0; p < parts; ++p) v += sD[p * Rb + tid][c];
-      // slabs != nullptr: per-set partial [b][R][dk] (summed in a fixed order by the caller)
-      if (slabs != nullptr) slabs[((int64_t)b * R + row0 + tid) * dk + c] = v;
-      else atomicAdd(&DG[(row0 + tid) * dk + c], v);
-    }
-  }
+  mab0_bwd_small_body<MID, 256>(Mab0SmallArgs{X, Gf, dTf, LSE, Delta, N, R, Rp, dk, DG, lengths, slabs, mid},
+                                blockIdx.x, blockIdx.y, gridDim.y, sD, sX, smid);
 }
 
 }  // namespace
@@ -610,9 +526,22 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_mab0_bwd_small<true>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, MID_SMALL_FUSE_LDS);
       });
-      hipLaunchKernelGGL(k_mab0_bwd_small<true>, sgrid, dim3(256), MID_SMALL_FUSE_LDS, st,
-                         reinterpret_cast<const float*>(X), v.Gf, w.dTf, v.LSE, w.Delta, s.nk, R, Rp, dk,
-                         w.DG, s.k_lengths, sl, mid_bwd_args(*mid));
+      // the bf16 weight-gradient list collected so far needs nothing this kernel writes: when it may run
+      // now (bwd_defer_ride), both go into one launch, this backward as one 512-thread workgroup per set
+      WgradJobs ride{};
+      int ride_rpw = 0, rc = PCA_OK;
+      if (sl != nullptr && defer != nullptr && bwd_defer_ride(*defer, &ride, &ride_rpw, &rc)) {
+        PCA_TRY(mab0_small_ride_launch(
+            ride, ride_rpw,
+            Mab0SmallArgs{reinterpret_cast<const float*>(X), v.Gf, w.dTf, v.LSE, w.Delta, s.nk, R, Rp, dk,
+                          w.DG, s.k_lengths, sl, mid_bwd_args(*mid)},
+            s.B, st));
+      } else {
+        PCA_TRY(rc);
+        hipLaunchKernelGGL(k_mab0_bwd_small<true>, sgrid, dim3(256), MID_SMALL_FUSE_LDS, st,
+                           reinterpret_cast<const float*>(X), v.Gf, w.dTf, v.LSE, w.Delta, s.nk, R, Rp, dk,
+                           w.DG, s.k_lengths, sl, mid_bwd_args(*mid));
+      }
     } else {
       hipLaunchKernelGGL(k_mab0_bwd_small<false>, sgrid, dim3(256), 0, st,
                          reinterpret_cast<const float*>(X), v.Gf, w.dTf, v.LSE, w.Delta, s.nk, R, Rp, dk,

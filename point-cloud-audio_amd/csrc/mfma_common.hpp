@@ -254,26 +254,29 @@ __device__ __forceinline__ bf16x8 zero_unless(bool ok, bf16x8 v) {
 //                  staging - not the arithmetic - the cost of those kernels)
 //   commit_points  registers -> LDS.  Every thread of the 256-thread workgroup must call it (two
 //                  barriers inside: the first also ends the previous chunk's reads of sX)
+// NT: threads of the workgroup (4096 / NT registers per thread; the same element goes to the same place)
 constexpr int PCA_POINT_CHUNK = 1024;
+template <int NT = 256>
 __device__ __forceinline__ void fetch_points(const float* __restrict__ X, int cn, int dk,
-                                             float (&v)[16]) {
+                                             float (&v)[4096 / NT]) {
   const int n = cn * dk;
 #pragma unroll
-  for (int u = 0; u < 16; ++u) {
-    const int e = threadIdx.x + 256 * u;
+  for (int u = 0; u < 4096 / NT; ++u) {
+    const int e = threadIdx.x + NT * u;
     v[u] = X[e < n ? e : n - 1];
   }
 }
-__device__ __forceinline__ void commit_points(const float (&v)[16], int cn, int dk, float* sX) {
+template <int NT = 256>
+__device__ __forceinline__ void commit_points(const float (&v)[4096 / NT], int cn, int dk, float* sX) {
   const int tid = threadIdx.x;
   const int npairs = (cn + 1) >> 1, n = cn * dk;
   __syncthreads();
   if (dk < 4 || (cn & 1))
-    for (int i = tid; i < npairs * 8; i += 256) sX[i] = 0.f;
+    for (int i = tid; i < npairs * 8; i += NT) sX[i] = 0.f;
   __syncthreads();
 #pragma unroll
-  for (int u = 0; u < 16; ++u) {
-    const int e = tid + 256 * u;
+  for (int u = 0; u < 4096 / NT; ++u) {
+    const int e = tid + NT * u;
     if (e < n) {
       const int pt = e / dk, c = e - pt * dk;
       sX[(pt >> 1) * 8 + c * 2 + (pt & 1)] = v[u];

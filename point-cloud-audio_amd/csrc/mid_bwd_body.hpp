@@ -6,6 +6,8 @@
 // stage - and take the dT / Delta / LSE images straight into their own LDS.  Same MFMAs
 // on the same operands in the same summation order wherever it runs; only the sink of the images
 // differs.  256 threads, wave w = head w; ONE workgroup barrier inside (every thread must call it).
+// In a workgroup of NT > 256 threads (the set rows of k_mab0_small_ride, wgrad128.hip) waves 0-3 run the
+// chain and the others only meet them at that barrier.
 #pragma once
 #include "blocks.hpp"
 #include "mfma_common.hpp"
@@ -74,10 +76,13 @@ struct MidSinkGlobal {
 };
 
 // wr: this workgroup also writes what later launches read from global memory (dKp, dVp, dZ, dO, Th)
-template <bool SMALL, class Sink>
+template <bool SMALL, int NT = 256, class Sink>
 __device__ __forceinline__ void mid_bwd_body(const MidBwdArgs& a, int b, const MidBwdLds& m,
                                              bool wr, const Sink& sink) {
+  static_assert(NT >= 256 && NT % 64 == 0, "mid_bwd_body: four waves run the chain");
   constexpr int D = 128, MQ = 16, ROWB = 256;
+  // wave-uniform: this wave takes part (always, in the 256-thread callers)
+  const bool on = NT == 256 || threadIdx.x < 256;
   char* const sK = m.sK;
   char* const sV = m.sV;
   char* const sWk = m.sWk;
@@ -87,92 +92,97 @@ __device__ __forceinline__ void mid_bwd_body(const MidBwdArgs& a, int b, const M
   const int dk = a.dk;
   char* const sOw = m.sO + w * 16 * 64;
 
-  // every wave needs ALL of Wk1^T and Wv1^T: stage them once, cooperatively (coalesced,
-  // 16 loads of 16 B in flight per thread) instead of 4 waves chasing fragments through L2
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int c = tid + 256 * e;                 // 2048 chunks of 16 B per matrix
-    const int row = c >> 4, ch = c & 15;
-    const uint4 kv = *reinterpret_cast<const uint4*>(a.Wk1T + (int64_t)row * D + ch * 8);
-    const uint4 vv = *reinterpret_cast<const uint4*>(a.Wv1T + (int64_t)row * D + ch * 8);
-    *reinterpret_cast<uint4*>(sWk + swz(row, ch, ROWB)) = kv;
-    *reinterpret_cast<uint4*>(sWv + swz(row, ch, ROWB)) = vv;
-  }
-  // Every global operand of the chain below is fetched NOW, before the first barrier: the
-  // chain is purely latency-bound, so the round trips must overlap instead of queueing behind
-  // each other.
-  const int64_t trow = (int64_t)b * 64 + 16 * w + r;           // this lane's query row of T
+  // what the second half takes from the first in registers
   float4 zpre[8];
-#pragma unroll
-  for (int t = 0; t < 8; ++t)
-    zpre[t] = *reinterpret_cast<const float4*>(a.Z + ((int64_t)b * MQ + r) * D + 16 * t + 4 * g);
   bf16x8 wo_pre[2][4];
-#pragma unroll
-  for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4)
-      wo_pre[tt][s4] = gload8(a.Wo0TP + (int64_t)(16 * (2 * w + tt) + r) * D + 32 * s4 + 8 * g);
   bf16x8 wvp_pre[SMALL ? 1 : 8], wvt_pre[SMALL ? 1 : 8];
   float4 t_pre[SMALL ? 1 : 8];
   float wvf_pre[SMALL ? 4 : 1][8], ts_pre[SMALL ? 4 : 1];
-  if (SMALL) {
+  float lse_pre;
+  if (on) {
+    // every wave needs ALL of Wk1^T and Wv1^T: stage them once, cooperatively (coalesced,
+    // 16 loads of 16 B in flight per thread) instead of 4 waves chasing fragments through L2
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      ts_pre[c] = c < dk ? a.T[trow * dk + c] : 0.f;
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          wvf_pre[c][4 * tt + e] =
-              c < dk ? a.Wv0f[(32 * w + 16 * tt + 4 * g + e) * dk + c] : 0.f;
+    for (int e = 0; e < 8; ++e) {
+      const int c = tid + 256 * e;                 // 2048 chunks of 16 B per matrix
+      const int row = c >> 4, ch = c & 15;
+      const uint4 kv = *reinterpret_cast<const uint4*>(a.Wk1T + (int64_t)row * D + ch * 8);
+      const uint4 vv = *reinterpret_cast<const uint4*>(a.Wv1T + (int64_t)row * D + ch * 8);
+      *reinterpret_cast<uint4*>(sWk + swz(row, ch, ROWB)) = kv;
+      *reinterpret_cast<uint4*>(sWv + swz(row, ch, ROWB)) = vv;
     }
-  } else {
+    // Every global operand of the chain below is fetched NOW, before the first barrier: the
+    // chain is purely latency-bound, so the round trips must overlap instead of queueing behind
+    // each other.
+    const int64_t trow = (int64_t)b * 64 + 16 * w + r;           // this lane's query row of T
 #pragma unroll
-    for (int ct = 0; ct < 8; ++ct) {
-      wvp_pre[ct] = gload8(a.Wv0TP + (int64_t)(16 * ct + r) * D + 32 * w + 8 * g);
-      wvt_pre[ct] = gload8(a.Wv0T + (int64_t)(16 * ct + r) * D + 32 * w + 8 * g);
-      t_pre[ct] = *reinterpret_cast<const float4*>(a.T + trow * D + 16 * ct + 4 * g);
-    }
-  }
-  const float lse_pre = a.LSE[(int64_t)b * 64 + 16 * w + r];
-  for (int i = tid; i < 16 * 16; i += 256) {
-    const int row = i >> 4, ch = i & 15;
-    float k[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // four partials at a time, their loads issued together (one round trip per group, not per
-    // partial); same summation order
-    for (int p0 = 0; p0 < a.nparts; p0 += 4) {
-      float4 k0[4], k1[4], v0[4], v1[4];
+    for (int t = 0; t < 8; ++t)
+      zpre[t] = *reinterpret_cast<const float4*>(a.Z + ((int64_t)b * MQ + r) * D + 16 * t + 4 * g);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int pp = p0 + u < a.nparts ? p0 + u : p0;
-        const int64_t off = (((int64_t)b * a.nparts + pp) * MQ + row) * D + ch * 8;
-        const float4* pk = reinterpret_cast<const float4*>(a.dKpPart + off);
-        const float4* pv = reinterpret_cast<const float4*>(a.dVpPart + off);
-        k0[u] = pk[0]; k1[u] = pk[1]; v0[u] = pv[0]; v1[u] = pv[1];
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4)
+        wo_pre[tt][s4] = gload8(a.Wo0TP + (int64_t)(16 * (2 * w + tt) + r) * D + 32 * s4 + 8 * g);
+    if (SMALL) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        ts_pre[c] = c < dk ? a.T[trow * dk + c] : 0.f;
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            wvf_pre[c][4 * tt + e] =
+                c < dk ? a.Wv0f[(32 * w + 16 * tt + 4 * g + e) * dk + c] : 0.f;
       }
+    } else {
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (p0 + u >= a.nparts) continue;
-        k[0] += k0[u].x; k[1] += k0[u].y; k[2] += k0[u].z; k[3] += k0[u].w;
-        k[4] += k1[u].x; k[5] += k1[u].y; k[6] += k1[u].z; k[7] += k1[u].w;
-        v[0] += v0[u].x; v[1] += v0[u].y; v[2] += v0[u].z; v[3] += v0[u].w;
-        v[4] += v1[u].x; v[5] += v1[u].y; v[6] += v1[u].z; v[7] += v1[u].w;
+      for (int ct = 0; ct < 8; ++ct) {
+        wvp_pre[ct] = gload8(a.Wv0TP + (int64_t)(16 * ct + r) * D + 32 * w + 8 * g);
+        wvt_pre[ct] = gload8(a.Wv0T + (int64_t)(16 * ct + r) * D + 32 * w + 8 * g);
+        t_pre[ct] = *reinterpret_cast<const float4*>(a.T + trow * D + 16 * ct + 4 * g);
       }
     }
-    if (wr) {
-      const int64_t so = ((int64_t)b * MQ + row) * D + ch * 8;
-      reinterpret_cast<float4*>(a.dKp + so)[0] = float4{k[0], k[1], k[2], k[3]};
-      reinterpret_cast<float4*>(a.dKp + so)[1] = float4{k[4], k[5], k[6], k[7]};
-      reinterpret_cast<float4*>(a.dVp + so)[0] = float4{v[0], v[1], v[2], v[3]};
-      reinterpret_cast<float4*>(a.dVp + so)[1] = float4{v[4], v[5], v[6], v[7]};
-    }
-    bf16x8 kb, vb;
+    lse_pre = a.LSE[(int64_t)b * 64 + 16 * w + r];
+    for (int i = tid; i < 16 * 16; i += 256) {
+      const int row = i >> 4, ch = i & 15;
+      float k[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      // four partials at a time, their loads issued together (one round trip per group, not per
+      // partial); same summation order
+      for (int p0 = 0; p0 < a.nparts; p0 += 4) {
+        float4 k0[4], k1[4], v0[4], v1[4];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { kb[e] = (__bf16)k[e]; vb[e] = (__bf16)v[e]; }
-    *reinterpret_cast<bf16x8*>(sK + swz(row, ch, ROWB)) = kb;
-    *reinterpret_cast<bf16x8*>(sV + swz(row, ch, ROWB)) = vb;
+        for (int u = 0; u < 4; ++u) {
+          const int pp = p0 + u < a.nparts ? p0 + u : p0;
+          const int64_t off = (((int64_t)b * a.nparts + pp) * MQ + row) * D + ch * 8;
+          const float4* pk = reinterpret_cast<const float4*>(a.dKpPart + off);
+          const float4* pv = reinterpret_cast<const float4*>(a.dVpPart + off);
+          k0[u] = pk[0]; k1[u] = pk[1]; v0[u] = pv[0]; v1[u] = pv[1];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (p0 + u >= a.nparts) continue;
+          k[0] += k0[u].x; k[1] += k0[u].y; k[2] += k0[u].z; k[3] += k0[u].w;
+          k[4] += k1[u].x; k[5] += k1[u].y; k[6] += k1[u].z; k[7] += k1[u].w;
+          v[0] += v0[u].x; v[1] += v0[u].y; v[2] += v0[u].z; v[3] += v0[u].w;
+          v[4] += v1[u].x; v[5] += v1[u].y; v[6] += v1[u].z; v[7] += v1[u].w;
+        }
+      }
+      if (wr) {
+        const int64_t so = ((int64_t)b * MQ + row) * D + ch * 8;
+        reinterpret_cast<float4*>(a.dKp + so)[0] = float4{k[0], k[1], k[2], k[3]};
+        reinterpret_cast<float4*>(a.dKp + so)[1] = float4{k[4], k[5], k[6], k[7]};
+        reinterpret_cast<float4*>(a.dVp + so)[0] = float4{v[0], v[1], v[2], v[3]};
+        reinterpret_cast<float4*>(a.dVp + so)[1] = float4{v[4], v[5], v[6], v[7]};
+      }
+      bf16x8 kb, vb;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { kb[e] = (__bf16)k[e]; vb[e] = (__bf16)v[e]; }
+      *reinterpret_cast<bf16x8*>(sK + swz(row, ch, ROWB)) = kb;
+      *reinterpret_cast<bf16x8*>(sV + swz(row, ch, ROWB)) = vb;
+    }
   }
   __syncthreads();
+  if (!on) return;
 
   // ---- dH^T (all 8 feature tiles, every wave: avoids a cross-wave exchange) ----
   bf16x8 kb[4], vb[4];

@@ -3,11 +3,14 @@
 // such sums as extra workgroup rows ("riders": k_wgrad128, k_terminal1) so that the reduction costs
 // no launch of its own.  Uses the first 256 threads of the workgroup; EVERY thread of the workgroup
 // must call it (one barrier inside).  `red` = 4 x 64 float4 of LDS.
+// NF: 16-byte loads a lane keeps in flight (the sum is a chain of S / (4 NF) round trips and nothing else;
+// the order of the additions does not depend on it).
 #pragma once
 #include "bwd_defer.hpp"
 
 namespace pca {
 
+template <int NF = 8>
 __device__ __forceinline__ void slab_sum_body(const SlabSumJob& j, int bx, int tid, float4* red) {
   if (bx * 256 >= j.n) return;                       // (uniform per workgroup)
   const int64_t stride = j.stride > 0 ? j.stride : j.n;
@@ -16,9 +19,19 @@ __device__ __forceinline__ void slab_sum_body(const SlabSumJob& j, int bx, int t
   const bool on = tid < 256 && i < j.n;
   float4 t = {0.f, 0.f, 0.f, 0.f};
   if (on) {
-    // four lane groups take every fourth slab, eight 16-byte loads in flight, then a fixed-order merge
+    // four lane groups take every fourth slab, NF (then eight) 16-byte loads in flight, then a fixed-order
+    // merge
     const float* s = j.slabs + i;
     int w = sg;
+    if constexpr (NF > 8) {
+      for (; w + 4 * (NF - 1) < j.S; w += 4 * NF) {
+        float4 v[NF];
+#pragma unroll
+        for (int u = 0; u < NF; ++u) v[u] = *reinterpret_cast<const float4*>(s + (w + 4 * u) * stride);
+#pragma unroll
+        for (int u = 0; u < NF; ++u) { t.x += v[u].x; t.y += v[u].y; t.z += v[u].z; t.w += v[u].w; }
+      }
+    }
     for (; w + 28 < j.S; w += 32) {
       float4 v[8];
 #pragma unroll

@@ -6,11 +6,15 @@
 //                  a fixed order afterwards, or as fp32 atomics; column sums of G (bias gradients) ride along,
 //                  and so do slab sums that are due now (rider rows).
 //   k_wgrad128_step  the same body over the two deferred lists of a step (bf16 and fp32 operands) in one launch.
+//   k_mab0_small_ride  the bf16 list of a step beside layer 1's few-queries backward (body:
+//                  mab0_bwd_small_body.hpp), which needs the memory system as little as the list needs it.
 //   k_wgrad_small  layer 1: dW[128 x dq] += G^T.X with dq <= 4 (body: terminal_bodies.hpp).
 #include "bwd_defer.hpp"
+#include "mab0_bwd_small_body.hpp"
 #include "mfma_common.hpp"
 #include "terminal_bodies.hpp"
 #include "slab_sum_body.hpp"
+#include <mutex>
 #include <type_traits>
 
 namespace pca {
@@ -293,7 +297,35 @@ __global__ __launch_bounds__(512) void k_wgrad128_step(const WgradJobs bf, int r
   } else if (y < bf.n + f32.n) {
     wgrad128_body<float, float, 2, wgrad128_depth<float, float>()>(f32.j[y - bf.n], rpw_f32, lds);
   } else {
-    slab_sum_body(riders.j[y - bf.n - f32.n], blockIdx.x, threadIdx.x, reinterpret_cast<float4*>(lds));
+    // (32 loads in flight: when the bf16 list ran in k_mab0_small_ride nothing hides these chains)
+    slab_sum_body<32>(riders.j[y - bf.n - f32.n], blockIdx.x, threadIdx.x, reinterpret_cast<float4*>(lds));
+  }
+}
+
+// The bf16 list of a step and layer 1's few-queries backward (one 512-thread workgroup per set: the
+// partition of two 256-thread workgroups of k_mab0_bwd_small, see mab0_bwd_small_body.hpp) in one launch:
+// the list's operands are ready before that backward runs and it does not read what the list writes, the
+// list streams on three quarters of the compute units, and the set rows are a latency chain that moves
+// about 1 MB.  blockIdx.y selects the row: the jobs, and `set_rows` rows of sets as wide as the job rows
+// (set = row * gridDim.x + blockIdx.x; a workgroup that leaves at once still takes a compute unit's whole
+// LDS and register file while it does, so the grid holds as few of them as the two extents allow); which
+// kind is dispatched first is RIDE_SETS_FIRST (measured: DESIGN 4.4.4).  No workgroup waits for another.
+constexpr bool RIDE_SETS_FIRST = false;
+constexpr int RIDE_SET_LDS = 512 * 4 * 4 + PCA_POINT_CHUNK * 4 * 4 + MID_SMALL_FUSE_LDS;
+constexpr int RIDE_LDS = RIDE_SET_LDS > 4 * 32 * 256 * 2 ? RIDE_SET_LDS : 4 * 32 * 256 * 2;
+__global__ __launch_bounds__(512) void k_mab0_small_ride(const WgradJobs bf, int rpw_bf,
+                                                         const Mab0SmallArgs sets, int B, int set_rows) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int y = RIDE_SETS_FIRST ? (int)blockIdx.y - set_rows : (int)blockIdx.y;
+  if (y >= 0 && y < bf.n) {
+    wgrad128_body<__bf16, __bf16, 2, wgrad128_depth<__bf16, __bf16>()>(bf.j[y], rpw_bf, lds);
+    return;
+  }
+  const int b = (RIDE_SETS_FIRST ? (int)blockIdx.y : y - bf.n) * (int)gridDim.x + (int)blockIdx.x;
+  if (b < B) {
+    float (*sD)[4] = reinterpret_cast<float (*)[4]>(lds);
+    float* sX = reinterpret_cast<float*>(lds + 512 * 4 * 4);
+    mab0_bwd_small_body<true, 512>(sets, b, 0, 1, sD, sX, lds + 512 * 4 * 4 + PCA_POINT_CHUNK * 4 * 4);
   }
 }
 
@@ -386,16 +418,51 @@ int wgrad128_launch(const WgradJobs& jobs_in, bool g_bf16, bool a_bf16, int rows
 
 int wgrad128_launch_step(const WgradJobs& bf, int rpw_bf, const WgradJobs& f32, int rpw_f32,
                          const SlabSumJobs& riders, hipStream_t st) {
-  PCA_REQUIRE(bf.n > 0 && f32.n > 0 && max_rows(bf) > 0 && max_rows(f32) > 0,
-              "wgrad128: the step launch takes two lists with rows");
+  // (an empty bf16 list: it ran beside layer 1's few-queries backward, mab0_small_ride_launch)
+  PCA_REQUIRE((bf.n == 0 || max_rows(bf) > 0) && f32.n > 0 && max_rows(f32) > 0,
+              "wgrad128: the step launch takes lists with rows");
   PCA_REQUIRE(rpw_bf >= 128 && rpw_f32 >= 128, "wgrad128: the step launch runs two row groups");
-  unsigned gx = (unsigned)cdiv(max_rows(bf), rpw_bf);
+  unsigned gx = bf.n == 0 ? 0u : (unsigned)cdiv(max_rows(bf), rpw_bf);
   const unsigned gf = (unsigned)cdiv(max_rows(f32), rpw_f32);
   gx = gf > gx ? gf : gx;
-  PCA_TRY(rider_extent(riders, gx));
-  hipLaunchKernelGGL(k_wgrad128_step, dim3(gx, (unsigned)(bf.n + f32.n + riders.n)), dim3(512), 0, st,
-                     bf, rpw_bf, f32, rpw_f32, riders);
+  SlabSumJobs rd = riders;
+  if (bf.n == 0) {
+    // No long rows hide the workgroups that leave at once (each takes a compute unit's whole LDS and
+    // register file while it does): a rider wider than the fp32 rows is cut into column ranges of their
+    // width, rows of its own (element by element the same sums).
+    rd.n = 0;
+    const int width = (int)gx * 256;
+    for (int i = 0; i < riders.n; ++i) {
+      const SlabSumJob& j = riders.j[i];
+      for (int c = 0; c < j.n; c += width) {
+        PCA_REQUIRE(rd.n < 40, "wgrad128: slab-sum table full");
+        rd.j[rd.n++] = SlabSumJob{j.slabs + c, j.out + c, j.S, j.n - c < width ? j.n - c : width,
+                                  j.accumulate, j.stride > 0 ? j.stride : j.n};
+      }
+    }
+  }
+  PCA_TRY(rider_extent(rd, gx));
+  hipLaunchKernelGGL(k_wgrad128_step, dim3(gx, (unsigned)(bf.n + f32.n + rd.n)), dim3(512), 0, st,
+                     bf, rpw_bf, f32, rpw_f32, rd);
   return check_launch("k_wgrad128_step");
+}
+
+int mab0_small_ride_launch(const WgradJobs& bf, int rpw_bf, const Mab0SmallArgs& sets, int B,
+                           hipStream_t st) {
+  PCA_REQUIRE(bf.n > 0 && max_rows(bf) > 0 && rpw_bf >= 128,
+              "mab0_small_ride: a bf16 list with rows, two row groups");
+  PCA_REQUIRE(B > 0 && sets.R == 64 && sets.dk >= 1 && sets.dk <= 4 && sets.slabs != nullptr,
+              "mab0_small_ride: R=%d dk=%d", sets.R, sets.dk);
+  static std::once_flag once;
+  std::call_once(once, [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_mab0_small_ride),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, RIDE_LDS);
+  });
+  const unsigned gj = (unsigned)cdiv(max_rows(bf), rpw_bf);
+  const int set_rows = (int)cdiv(B, gj);
+  hipLaunchKernelGGL(k_mab0_small_ride, dim3(gj, (unsigned)(bf.n + set_rows)), dim3(512), RIDE_LDS, st, bf,
+                     rpw_bf, sets, B, set_rows);
+  return check_launch("k_mab0_small_ride");
 }
 
 int wgrad128_defer(BwdDefer* defer, const WgradJobs& jobs, bool bf16, int rows_per_wg,
