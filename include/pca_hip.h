@@ -377,6 +377,29 @@ int pca_frame_points_ex(const float* waves, const int64_t* wave_off, const int64
                         const float* farr, const float* tarr, const PcaFrameAugEx* aug, float* out,
                         int64_t* labels_out, int32_t* meta_out, float* samples_out, void* stream);
 
+/* pca_frame_points_ex that also emits the soft target of each slot: the label of the background clip and
+ * the weight of the primary clip's label, for pca_st_train_fwd_bwd_soft / pca_cross_entropy_soft.
+ * replaces: nothing (the reference neither mixes nor trains on mixed labels).
+ * bg_labels: device int64[n_bg]; labels2_out: device int64[B]; weight_out: device float[B].  All three
+ * are given or none, and they require clip_labels / labels_out; otherwise PCA_EINVAL.
+ *   a slot that mixes with alpha != 0:  labels2_out[b] = bg_labels[c2],
+ *                                       weight_out[b] = (float)(1.0 / (1.0 + u)), u = 10^(-snr/20) the
+ *                                       double alpha is computed from
+ *   every other slot:                   labels2_out[b] = labels_out[b], weight_out[b] = 1.0f
+ * w is the primary clip's share of the amplitude after RMS matching - between-class learning's rule with
+ * the RMS in place of its A-weighted level: mix_snr_db = (-20, 20) spans weights of about 0.09 .. 0.91.
+ * out, labels_out, meta_out and samples_out are pca_frame_points_ex's bits for the same arguments: the
+ * sample arithmetic is untouched and no draw is added; workgroup j == 0, thread 0 of a slot writes the two
+ * values next to the label.  pca_frame_points_ex is this call with the three NULL (one kernel).  The same
+ * arguments give the same bits. */
+int pca_frame_points_ex_targets(const float* waves, const int64_t* wave_off, const int64_t* set_off,
+                                int n_clips, int64_t max_len, int64_t min_len,
+                                const int64_t* clip_labels, const int64_t* idx, int B, int n_fft,
+                                int hop, int n_bins, int Nt, const float* farr, const float* tarr,
+                                const PcaFrameAugEx* aug, float* out, int64_t* labels_out,
+                                int32_t* meta_out, float* samples_out, const int64_t* bg_labels,
+                                int64_t* labels2_out, float* weight_out, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Fixed-input baselines (eval-mode forward; training stays stock PyTorch)    *
  * ------------------------------------------------------------------------- */
@@ -528,6 +551,36 @@ size_t pca_linear_bwd_ws_bytes(int64_t M, int din, int dout);
 int pca_cross_entropy(const float* logits, const int64_t* labels, int B, int C,
                       float grad_scale, float* loss_out, float* dlogits,
                       float* stats_out, void* stream);
+
+/* Soft targets of the cross-entropy: every set carries a second class and the weight of the first
+ * (between-class learning / mixup on two labelled clips), the batch a label smoothing.  For set b with
+ * y1 = labels[b], y2 = labels2[b], w = weight[b] in [0, 1], eps = smoothing, C classes:
+ *   t_c  = (1 - eps) (w [c == y1] + (1 - w) [c == y2]) + eps / C          (sum_c t_c = 1; y1 == y2 allowed)
+ *   loss = logsumexp(x) - sum_c t_c x_c
+ *   dx_c = (softmax(x)_c - t_c) * grad_scale / B
+ *   correct = [argmax(x) == (w >= 0.5 ? y1 : y2)]                         (the dominant label; a tie: y1)
+ * The cross-entropy is reported, not the KL divergence (they differ by the target's entropy and have the
+ * same gradient).  labels2 == NULL: y2 = y1; weight == NULL: w = 1.  Both are device values and, as
+ * labels, not validated; smoothing is a host value, finite and in [0, 1) or PCA_EINVAL before anything
+ * is enqueued.  With w = 1 and eps = 0 every term equals the hard-label term exactly for finite logits:
+ * the results are the bits of the hard-label call, whatever labels2 holds. */
+typedef struct PcaSoftTargets {
+  const int64_t* labels2;      /* device int64[B], nullable */
+  const float* weight;         /* device float[B], nullable */
+  float smoothing;
+} PcaSoftTargets;
+
+/* pca_cross_entropy on the soft targets above (soft == NULL: the hard label; pca_cross_entropy is this
+ * call with soft == NULL, one kernel serves both).
+ * replaces: torch.nn.functional.cross_entropy(logits, t) with probability targets t as above; for
+ *           w = 1 its label_smoothing=eps form.  The reference trains on hard labels only
+ *           (Code/settransformer.py:88).
+ * loss_out[0] = mean loss; dlogits[B, C] as above; stats_out (nullable) [2]: += {sum of per-sample loss,
+ * #(argmax == dominant label)}.  One wave per sample; sum_c x_c is only reduced when eps > 0.  loss_out
+ * and stats_out are float atomics over the samples, as in pca_cross_entropy; dlogits is deterministic. */
+int pca_cross_entropy_soft(const float* logits, const int64_t* labels, const PcaSoftTargets* soft,
+                           int B, int C, float grad_scale, float* loss_out, float* dlogits,
+                           float* stats_out, void* stream);
 
 /* Correct-prediction tally of an evaluation batch
  * replaces: Code/pceval.py:95, Code/pc_temp3d_eval.py:97, Code/rebut_expts.py:106
@@ -726,6 +779,22 @@ int pca_st_train_fwd_bwd(const pca_st_config* c, const float* params, const floa
                          const int32_t* lengths, const int64_t* labels, float* grads,
                          float* loss_out, float* stats, float* logits, float grad_scale,
                          int phase, void* ws, void* stream);
+
+/* pca_st_train_fwd_bwd on soft targets (PcaSoftTargets, above): the same phases, the same accumulation
+ * contract, the same launches - the targets are read by the loss stage the step already runs (the tail
+ * of the set-resident launch, the PMA head launch or the classifier head, whichever the shape takes).
+ * replaces: nothing (the reference trains on hard labels); the loss is
+ *           torch.nn.functional.cross_entropy(logits, t) with t_c as given at PcaSoftTargets.
+ * soft == NULL is the hard step: pca_st_train_fwd_bwd is this call with soft == NULL.  smoothing outside
+ * [0, 1) or non-finite: PCA_EINVAL before anything is enqueued.  stats counts against the dominant label.
+ * Pass the same targets to both phases of a split step (phase 1 does not read them).  With w = 1 and
+ * eps = 0 logits, loss and gradients are the hard step's bits; the determinism of the step is the hard
+ * step's: the targets add no atomics. */
+int pca_st_train_fwd_bwd_soft(const pca_st_config* c, const float* params, const float* X,
+                              const int32_t* lengths, const int64_t* labels,
+                              const PcaSoftTargets* soft, float* grads, float* loss_out,
+                              float* stats, float* logits, float grad_scale, int phase, void* ws,
+                              void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Building blocks (exported for unit tests and for composing other blocks)   *

@@ -4,6 +4,7 @@
 // weight_images.hpp, bwd_defer.hpp and step_ctx.hpp.
 #pragma once
 #include "pca_common.h"
+#include "soft_targets.hpp"
 #include "weight_images.hpp"
 
 namespace pca {
@@ -258,9 +259,10 @@ int isab_bf16_bwd(const pca_mab_shape& s0, const pca_mab_shape& s1, const float*
                   const void* dY, float* dI, void* dX, const pca_mab_grads& g0,
                   const pca_mab_grads& g1, void* ws, const IsabImg& im, hipStream_t st,
                   BwdDefer* defer = nullptr);
-// classifier head (train_ops.hip)
+// classifier head (train_ops.hip); soft: soft_targets.hpp (all null / 0: the hard label)
+int soft_targets_from(const PcaSoftTargets* soft, const char* who, SoftTargets* out);
 int cls_train_head(const float* P, const float* Wc, const float* bc, const int64_t* labels,
-                   int B, int d, int C, float grad_scale, float* logits, float* dlogits,
+                   const SoftTargets& soft, int B, int d, int C, float grad_scale, float* logits, float* dlogits,
                    float* dP, float* dWc, float* dbc, float* loss_out, float* stats, float* ws,
                    hipStream_t st, BwdDefer* defer = nullptr);
 // d128_fused.hip: the same single-launch forward at d = 128 / 4 heads / m = 16

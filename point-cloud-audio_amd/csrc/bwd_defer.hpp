@@ -5,6 +5,7 @@
 // job) - plus the PMA head launch that queues the classifier's job (pma_head.hip).
 #pragma once
 #include "pca_common.h"
+#include "soft_targets.hpp"
 
 namespace pca {
 
@@ -187,6 +188,7 @@ struct PmaHeadArgs {
   // classifier + loss
   const float *Wc, *bc;
   const int64_t* labels;
+  SoftTargets soft;
   int B, C;
   float grad_scale;
   float *logits, *dlogits, *dP, *lossv, *corrv;
@@ -201,7 +203,8 @@ struct PmaHeadArgs {
 // P [B, d] receives the pooled features; the classifier's weight gradient is queued in `defer`.  ws_bwd is
 // the PMA's backward workspace.
 int pma_head_args(const pca_mab_shape& s, const pca_mab_params& p, void* saved, void* ws_bwd,
-                  float* P, const float* Wc, const float* bc, const int64_t* labels, int C,
+                  float* P, const float* Wc, const float* bc, const int64_t* labels,
+                  const SoftTargets& soft, int C,
                   float grad_scale, float* logits, float* dlogits, float* dP, float* dWc,
                   float* dbc, float* loss_out, float* stats, float* cls_ws, BwdDefer* defer,
                   PmaHeadArgs* out);

@@ -46,6 +46,10 @@ struct FrameJobEx {
   const int64_t* bg_off;
   const double *bg_rms, *clip_rms;
   int n_bg;
+  // soft targets (all three or none): the background clip's label and the primary label's weight
+  const int64_t* bg_labels;
+  int64_t* labels2_out;
+  float* weight_out;
   double mix_prob, snr_lo_db, snr_hi_db;
 };
 
@@ -106,7 +110,7 @@ __global__ __launch_bounds__(256) void k_frame_points_ex(const FrameJobEx a) {
 
   int c2 = -1;
   int64_t p = 0, b0 = 0, Lb = 0;
-  float alpha = 0.f;
+  float alpha = 0.f, wgt = 1.f;         // wgt: the primary clip's share of the amplitude
   if (a.bg_waves != nullptr && frame_unit(frame_draw(stream, 4)) < a.mix_prob) {
     const int k = (int)(((frame_draw(stream, 5) >> 32) * (uint64_t)a.n_bg) >> 32);
     b0 = a.bg_off[k];
@@ -116,7 +120,11 @@ __global__ __launch_bounds__(256) void k_frame_points_ex(const FrameJobEx a) {
       p = (int64_t)__umul64hi(frame_draw(stream, 6), (uint64_t)Lb);
       const double snr = a.snr_lo_db + frame_unit(frame_draw(stream, 7)) * (a.snr_hi_db - a.snr_lo_db);
       const double rc = a.clip_rms[c], rb = a.bg_rms[k];
-      if (rc > 0.0 && rb > 0.0) alpha = (float)(rc / rb * exp2(-snr * 0.16609640474436813));
+      if (rc > 0.0 && rb > 0.0) {
+        const double u = exp2(-snr * 0.16609640474436813);            // 10^(-snr/20)
+        alpha = (float)(rc / rb * u);
+        if (alpha != 0.f) wgt = (float)(1.0 / (1.0 + u));
+      }
     }
   }
 
@@ -128,6 +136,10 @@ __global__ __launch_bounds__(256) void k_frame_points_ex(const FrameJobEx a) {
   centre = centre < 0 ? 0 : (centre > Ly ? Ly : centre);
   if (j == 0 && tid == 0) {
     if (a.clip_labels != nullptr && a.labels_out != nullptr) a.labels_out[b] = a.clip_labels[c];
+    if (a.labels2_out != nullptr) {     // (the host passes them with clip_labels only)
+      a.labels2_out[b] = alpha != 0.f ? a.bg_labels[c2] : a.clip_labels[c];
+      a.weight_out[b] = wgt;
+    }
     if (a.meta_out != nullptr) {
       int32_t* m = a.meta_out + (int64_t)b * 8;
       m[0] = c;
@@ -218,17 +230,24 @@ int pca_clip_rms(const float* waves, const int64_t* wave_off, int n_clips, int64
   return pca::check_launch("k_clip_rms");
 }
 
-int pca_frame_points_ex(const float* waves, const int64_t* wave_off, const int64_t* set_off,
-                        int n_clips, int64_t max_len, int64_t min_len, const int64_t* clip_labels,
-                        const int64_t* idx, int B, int n_fft, int hop, int n_bins, int Nt,
-                        const float* farr, const float* tarr, const PcaFrameAugEx* aug, float* out,
-                        int64_t* labels_out, int32_t* meta_out, float* samples_out, void* stream) {
+int pca_frame_points_ex_targets(const float* waves, const int64_t* wave_off, const int64_t* set_off,
+                                int n_clips, int64_t max_len, int64_t min_len,
+                                const int64_t* clip_labels, const int64_t* idx, int B, int n_fft,
+                                int hop, int n_bins, int Nt, const float* farr, const float* tarr,
+                                const PcaFrameAugEx* aug, float* out, int64_t* labels_out,
+                                int32_t* meta_out, float* samples_out, const int64_t* bg_labels,
+                                int64_t* labels2_out, float* weight_out, void* stream) {
   // everything pca_frame_points refuses
   PCA_REQUIRE(waves && wave_off && set_off && idx && farr && aug && out,
               "frame_points_ex: null pointer");
   PCA_REQUIRE(aug->win_lengths != nullptr, "frame_points_ex: null win_lengths");
   PCA_REQUIRE((clip_labels == nullptr) == (labels_out == nullptr),
               "frame_points_ex: clip_labels and labels_out go together");
+  PCA_REQUIRE((bg_labels == nullptr) == (labels2_out == nullptr) &&
+                  (bg_labels == nullptr) == (weight_out == nullptr),
+              "frame_points_ex: bg_labels, labels2_out and weight_out go together");
+  PCA_REQUIRE(bg_labels == nullptr || clip_labels != nullptr,
+              "frame_points_ex: the soft targets need clip_labels and labels_out");
   PCA_REQUIRE(n_clips > 0, "frame_points_ex: n_clips=%d", n_clips);
   PCA_REQUIRE(n_fft >= 64 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0,
               "frame_points_ex: n_fft=%d must be a power of two in [64, 4096]", n_fft);
@@ -308,6 +327,7 @@ int pca_frame_points_ex(const float* waves, const int64_t* wave_off, const int64
     j.bg_waves = aug->bg_waves; j.bg_off = aug->bg_off; j.bg_rms = aug->bg_rms;
     j.clip_rms = aug->clip_rms; j.n_bg = aug->n_bg;
   }
+  j.bg_labels = bg_labels; j.labels2_out = labels2_out; j.weight_out = weight_out;
   j.mix_prob = aug->mix_prob; j.snr_lo_db = aug->snr_lo_db; j.snr_hi_db = aug->snr_hi_db;
   static std::once_flag lds_once;   // allow > 64 KiB of dynamic LDS (96 KiB at n_fft 4096)
   std::call_once(lds_once, [] {
@@ -317,5 +337,15 @@ int pca_frame_points_ex(const float* waves, const int64_t* wave_off, const int64
   hipLaunchKernelGGL(pca::k_frame_points_ex, dim3((unsigned)Nt, (unsigned)B), dim3(256),
                      pca::stft_lds_bytes(n_fft), pca::as_stream(stream), j);
   return pca::check_launch("k_frame_points_ex");
+}
+
+int pca_frame_points_ex(const float* waves, const int64_t* wave_off, const int64_t* set_off,
+                        int n_clips, int64_t max_len, int64_t min_len, const int64_t* clip_labels,
+                        const int64_t* idx, int B, int n_fft, int hop, int n_bins, int Nt,
+                        const float* farr, const float* tarr, const PcaFrameAugEx* aug, float* out,
+                        int64_t* labels_out, int32_t* meta_out, float* samples_out, void* stream) {
+  return pca_frame_points_ex_targets(waves, wave_off, set_off, n_clips, max_len, min_len, clip_labels,
+                                     idx, B, n_fft, hop, n_bins, Nt, farr, tarr, aug, out, labels_out,
+                                     meta_out, samples_out, nullptr, nullptr, nullptr, stream);
 }
 }

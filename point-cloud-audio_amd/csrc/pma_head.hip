@@ -21,7 +21,7 @@ __global__ __launch_bounds__(256) void k_pma_head(const PmaHeadArgs a) {
   mab0_epi_body<1>(a.Tp, a.Mp, a.Lp, a.S, a.T, a.LSE, a.Qp, a.WvT, a.bv, a.WoT, a.bo, a.m, a.d,
                    a.dk, a.h, a.H, a.Osave, a.Zsave, b);
   __syncthreads();
-  cls_fwd_bwd_body(a.H, a.Wc, a.bc, a.labels, a.B, a.d, a.C, a.grad_scale, a.logits, a.dlogits,
+  cls_fwd_bwd_body(a.H, a.Wc, a.bc, a.labels, a.soft, a.B, a.d, a.C, a.grad_scale, a.logits, a.dlogits,
                    a.dP, a.lossv, a.corrv, b);
   __syncthreads();
   mab0_epi_bwd_body<1>(a.dP, a.Zsave, a.T, a.LSE, a.Wo, a.Wv, a.m, a.d, a.dk, a.h, a.Rp, a.dZ,
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void k_pma_head1(const PmaHeadArgs a) {
 #pragma unroll
     for (int k = 0; k < DH; ++k)
       w6[jj][k] = a.Wv[(int64_t)((2 * half + jj) * DH + k) * DK + f];
-  const int64_t y = a.labels[b];
+  const SoftRow y = soft_row(a.soft, a.labels, b);
   if (a.zero_ptr != nullptr)
     for (int i = b * 256 + tid; i < a.zero_n; i += gridDim.x * 256) a.zero_ptr[i] = 0.f;
 
@@ -173,19 +173,25 @@ __global__ __launch_bounds__(256) void k_pma_head1(const PmaHeadArgs a) {
     for (int j = tid; j < C; j += 64) sm += expf(sL[j] - m);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sm += __shfl_xor(sm, o, 64);
-    if (tid == 0) { red[0] = m; red[1] = sm; ramax = am; }
+    float sx = 0.f;
+    if (y.eps > 0.f) {           // (uniform) sum of the logits, for the smoothing term
+      for (int j = tid; j < C; j += 64) sx += sL[j];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) sx += __shfl_xor(sx, o, 64);
+    }
+    if (tid == 0) { red[0] = m; red[1] = sm; sDl[0] = sx; ramax = am; }   // (sDl: idle until Delta)
   }
   __syncthreads();
   {
     const float m = red[0], sm = red[1];
     const float gs = a.grad_scale / (float)a.B;
     if (tid == 0) {
-      a.lossv[b] = m + logf(sm) - sL[y];
-      a.corrv[b] = ramax == (int)y ? 1.f : 0.f;
+      a.lossv[b] = m + logf(sm) - soft_picked(y, sL[y.y1], sL[y.y2], sDl[0], C);
+      a.corrv[b] = ramax == (int)soft_dominant(y) ? 1.f : 0.f;
     }
     __syncthreads();
     for (int c = tid; c < C; c += 256) {
-      const float g = (expf(sL[c] - m) / sm - (c == y ? 1.f : 0.f)) * gs;
+      const float g = (expf(sL[c] - m) / sm - soft_target(y, c, C)) * gs;
       sL[c] = g;
       a.dlogits[(int64_t)b * C + c] = g;
     }
@@ -262,7 +268,8 @@ __global__ __launch_bounds__(256) void k_pma_head1(const PmaHeadArgs a) {
 }  // namespace
 
 int pma_head_args(const pca_mab_shape& s, const pca_mab_params& p, void* saved, void* ws_bwd,
-                  float* P, const float* Wc, const float* bc, const int64_t* labels, int C,
+                  float* P, const float* Wc, const float* bc, const int64_t* labels,
+                  const SoftTargets& soft, int C,
                   float grad_scale, float* logits, float* dlogits, float* dP, float* dWc,
                   float* dbc, float* loss_out, float* stats, float* cls_ws, BwdDefer* defer,
                   PmaHeadArgs* out) {
@@ -276,7 +283,7 @@ int pma_head_args(const pca_mab_shape& s, const pca_mab_params& p, void* saved, 
   a.Tp = v.Tp; a.Mp = v.Mp; a.Lp = v.Lp; a.S = mab0_splits(s); a.T = v.T; a.LSE = v.LSE;
   a.Qp = v.Qp; a.WvT = v.WvT; a.bv = p.bv; a.WoT = v.WoT; a.bo = p.bo;
   a.m = m; a.d = d; a.dk = dk; a.h = h; a.H = P; a.Osave = v.O; a.Zsave = v.Z;
-  a.Wc = Wc; a.bc = bc; a.labels = labels; a.B = s.B; a.C = C; a.grad_scale = grad_scale;
+  a.Wc = Wc; a.bc = bc; a.labels = labels; a.soft = soft; a.B = s.B; a.C = C; a.grad_scale = grad_scale;
   a.logits = logits; a.dlogits = dlogits; a.dP = dP; a.lossv = cls_ws; a.corrv = cls_ws + s.B;
   a.Wo = p.wo; a.Wv = p.wv; a.Rp = Rp; a.dZ = w.dZ; a.dO = w.dO; a.Th = w.Th; a.dTf = nullptr;
   a.dTb = w.dTb; a.dTt = w.dTt; a.Delta = w.Delta; a.LSEp = w.LSEp;

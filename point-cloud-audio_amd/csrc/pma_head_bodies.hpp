@@ -5,6 +5,7 @@
 // chain of dependent L2 round trips for one set, so two launches less is ~10 us of a 0.4 ms step.
 #pragma once
 #include "mfma_common.hpp"
+#include "soft_targets.hpp"
 
 #include <math.h>
 
@@ -113,13 +114,13 @@ __device__ __forceinline__ void mab0_epi_body(const float* __restrict__ Tp,   //
 
 __device__ __forceinline__ void cls_fwd_bwd_body(
     const float* __restrict__ P, const float* __restrict__ Wc, const float* __restrict__ bc,
-    const int64_t* __restrict__ labels, int B, int d, int C, float grad_scale,
-    float* __restrict__ logits, float* __restrict__ dlogits, float* __restrict__ dP,
-    float* __restrict__ lossv, float* __restrict__ corrv, int bset) {
+    const int64_t* __restrict__ labels, const SoftTargets& soft, int B, int d, int C,
+    float grad_scale, float* __restrict__ logits, float* __restrict__ dlogits,
+    float* __restrict__ dP, float* __restrict__ lossv, float* __restrict__ corrv, int bset) {
   extern __shared__ float sm[];
   float* sP = sm;            // [d]
   float* sL = sP + d;        // [C] logits, then dlogits
-  __shared__ float red[2];
+  __shared__ float red[3];
   __shared__ int ramax;
   const int b = bset, tid = threadIdx.x, NT = blockDim.x;
   for (int f = tid; f < d; f += NT) sP[f] = P[(int64_t)b * d + f];
@@ -171,6 +172,7 @@ __device__ __forceinline__ void cls_fwd_bwd_body(
     logits[(int64_t)b * C + c] = acc;
   }
   }
+  const SoftRow y = soft_row(soft, labels, b);
   __syncthreads();
   if (tid < 64) {            // one wave: max / argmax / sum over the C logits
     float m = -INFINITY;
@@ -187,19 +189,24 @@ __device__ __forceinline__ void cls_fwd_bwd_body(
     for (int j = tid; j < C; j += 64) s += expf(sL[j] - m);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (tid == 0) { red[0] = m; red[1] = s; ramax = am; }
+    float sx = 0.f;
+    if (y.eps > 0.f) {       // (uniform) sum of the logits, for the smoothing term
+      for (int j = tid; j < C; j += 64) sx += sL[j];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) sx += __shfl_xor(sx, o, 64);
+    }
+    if (tid == 0) { red[0] = m; red[1] = s; red[2] = sx; ramax = am; }
   }
   __syncthreads();
   const float m = red[0], s = red[1];
-  const int64_t y = labels[b];
   const float gs = grad_scale / (float)B;
   if (tid == 0) {
-    lossv[b] = m + logf(s) - sL[y];
-    corrv[b] = ramax == (int)y ? 1.f : 0.f;
+    lossv[b] = m + logf(s) - soft_picked(y, sL[y.y1], sL[y.y2], red[2], C);
+    corrv[b] = ramax == (int)soft_dominant(y) ? 1.f : 0.f;
   }
   __syncthreads();
   for (int c = tid; c < C; c += NT) {
-    const float g = (expf(sL[c] - m) / s - (c == y ? 1.f : 0.f)) * gs;
+    const float g = (expf(sL[c] - m) / s - soft_target(y, c, C)) * gs;
     sL[c] = g;
     dlogits[(int64_t)b * C + c] = g;
   }

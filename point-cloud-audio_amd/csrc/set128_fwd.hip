@@ -506,7 +506,7 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
   float* sL = sdO + 128;          // logits / dlogits [64]
   float* part = sL + 64;          // [8][128] partial sums of the output-index products
   float* sDl = part + 1024;       // [4][2]
-  float* red = sDl + 8;           // m, sum
+  float* red = sDl + 8;           // m, sum, (argmax), sum of the logits
   int* ramax = reinterpret_cast<int*>(red + 2);
   float* sLSE = red + 4;          // [4]
   const int tid = c.tid, b = c.b, C = a.C, B = a.B;
@@ -529,7 +529,7 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
   for (int u = 0; u < 2; ++u)
     wc4[u] = *reinterpret_cast<const float4*>(a.Wc + (int64_t)(c3 < C ? c3 : 0) * D + 8 * p3 + 4 * u);
   const float qb = a.Qp[fA] + a.bv[fA], bo_f = a.bo[fA], bc3 = a.bc[c3 < C ? c3 : 0];
-  const int64_t y = a.labels[b];
+  const SoftRow y = soft_row(a.soft, a.labels, b);
   if (wr && a.zero_ptr != nullptr)
     for (int i = b * NT + tid; i < a.zero_n; i += B * NT) a.zero_ptr[i] = 0.f;
 
@@ -633,17 +633,23 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     for (int j = tid; j < C; j += 64) sm += expf(sL[j] - m);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sm += __shfl_xor(sm, o, 64);
-    if (tid == 0) { red[0] = m; red[1] = sm; *ramax = am; }
+    float sx = 0.f;
+    if (y.eps > 0.f) {           // (uniform) sum of the logits, for the smoothing term (C <= 64)
+      sx = tid < C ? sL[tid] : 0.f;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) sx += __shfl_xor(sx, o, 64);
+    }
+    if (tid == 0) { red[0] = m; red[1] = sm; red[3] = sx; *ramax = am; }
   }
   lds_barrier();
   {
     const float m = red[0], sm = red[1];
     const float gs = a.grad_scale / (float)B;
     float g = 0.f;
-    if (tid < C) g = (expf(sL[tid] - m) / sm - (tid == y ? 1.f : 0.f)) * gs;
+    if (tid < C) g = (expf(sL[tid] - m) / sm - soft_target(y, tid, C)) * gs;
     if (wr && tid == 0) {
-      a.lossv[b] = m + logf(sm) - sL[y];
-      a.corrv[b] = *ramax == (int)y ? 1.f : 0.f;
+      a.lossv[b] = m + logf(sm) - soft_picked(y, sL[y.y1], sL[y.y2], red[3], C);
+      a.corrv[b] = *ramax == (int)soft_dominant(y) ? 1.f : 0.f;
     }
     lds_barrier();
     if (tid < C) {

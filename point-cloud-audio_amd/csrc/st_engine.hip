@@ -549,9 +549,11 @@ int st_pool_attention(const pca_st_config* c, const float* params, const float* 
 }
 
 int st_train_fwd_bwd(const pca_st_config* c, const float* p, const float* X, const int32_t* lengths,
-                     const int64_t* labels, float* g, float* loss_out, float* stats, float* logits,
-                     float grad_scale, int phase, void* ws, void* stream) {
+                     const int64_t* labels, const PcaSoftTargets* soft_in, float* g, float* loss_out,
+                     float* stats, float* logits, float grad_scale, int phase, void* ws, void* stream) {
   PCA_TRY(validate(c));
+  SoftTargets soft;
+  PCA_TRY(soft_targets_from(soft_in, "st_train_fwd_bwd", &soft));
   PCA_REQUIRE(p && X && labels && g && loss_out && ws, "st_train_fwd_bwd: null pointer");
   PCA_REQUIRE(c->k == 1, "st_train_fwd_bwd: the train step needs k == 1 (got %d)", c->k);
   PCA_REQUIRE(phase >= -1 && phase <= 1, "st_train_fwd_bwd: phase=%d", phase);
@@ -579,7 +581,7 @@ int st_train_fwd_bwd(const pca_st_config* c, const float* p, const float* X, con
     PmaHeadArgs head{};
     if (pl.pma_head)
       PCA_TRY(pma_head_args(pl.pma, params_at(p, L.pma), w.saved[4], w.scratch, w.P, p + L.wc, p + L.bc,
-                            labels, c->C, grad_scale, w.logits, w.dlogits, w.dP, g + L.wc, g + L.bc,
+                            labels, soft, c->C, grad_scale, w.logits, w.dlogits, w.dP, g + L.wc, g + L.bc,
                             loss_out, stats, w.clsws, &posts, &head));
     PCA_TRY(prepare_step(*c, L, pl, p, w, image_jobs, st));
     PCA_TRY(forward(*c, L, pl, p, X, w, st, &ctx, &head));
@@ -593,7 +595,7 @@ int st_train_fwd_bwd(const pca_st_config* c, const float* p, const float* X, con
                                deferring(&ctx, &posts, true)));
     } else {
       // dec.1 (Linear) + mean cross-entropy, forward and backward
-      PCA_TRY(cls_train_head(w.P, p + L.wc, p + L.bc, labels, c->B, c->d, c->C, grad_scale, w.logits,
+      PCA_TRY(cls_train_head(w.P, p + L.wc, p + L.bc, labels, soft, c->B, c->d, c->C, grad_scale, w.logits,
                              w.dlogits, w.dP, g + L.wc, g + L.bc, loss_out, stats, w.clsws, st, &posts));
       PCA_TRY(mab_bwd(pl.path_pma, pl.pma, p + L.S, w.Y[1], params_at(p, L.pma), w.saved[4], w.dP, g + L.S, w.dY2,
                           0, grads_at(g, L.pma), w.scratch_pma, st, deferring(&ctx, &posts, pl.pma256)));
@@ -670,15 +672,23 @@ int pca_st_pool_attention(const pca_st_config* c, const float* params, const flo
   return rc != PCA_OK ? rc : pca::no_stale_pack("pca_st_pool_attention (exit)", false);
 }
 
+int pca_st_train_fwd_bwd_soft(const pca_st_config* c, const float* params, const float* X,
+                              const int32_t* lengths, const int64_t* labels,
+                              const PcaSoftTargets* soft, float* grads, float* loss_out, float* stats,
+                              float* logits, float grad_scale, int phase, void* ws, void* stream) {
+  // phase 1 of a split step reads X again: the pack was consumed by phase 0
+  PCA_TRY(pca::no_stale_pack("pca_st_train_fwd_bwd", phase != 1));
+  const int rc = pca::st_train_fwd_bwd(c, params, X, lengths, labels, soft, grads, loss_out, stats,
+                                       logits, grad_scale, phase, ws, stream);
+  return rc != PCA_OK ? rc : pca::no_stale_pack("pca_st_train_fwd_bwd (exit)", false);
+}
+
 int pca_st_train_fwd_bwd(const pca_st_config* c, const float* params, const float* X,
                          const int32_t* lengths, const int64_t* labels, float* grads,
                          float* loss_out, float* stats,
                          float* logits, float grad_scale, int phase, void* ws,
                          void* stream) {
-  // phase 1 of a split step reads X again: the pack was consumed by phase 0
-  PCA_TRY(pca::no_stale_pack("pca_st_train_fwd_bwd", phase != 1));
-  const int rc = pca::st_train_fwd_bwd(c, params, X, lengths, labels, grads, loss_out, stats, logits,
-                                       grad_scale, phase, ws, stream);
-  return rc != PCA_OK ? rc : pca::no_stale_pack("pca_st_train_fwd_bwd (exit)", false);
+  return pca_st_train_fwd_bwd_soft(c, params, X, lengths, labels, nullptr, grads, loss_out, stats,
+                                   logits, grad_scale, phase, ws, stream);
 }
 }

@@ -6,6 +6,9 @@
 #include "bwd_defer.hpp"
 #include "terminal_bodies.hpp"
 #include "pma_head_bodies.hpp"
+#include "soft_targets.hpp"
+
+#include <cmath>
 
 namespace pca {
 namespace {
@@ -16,7 +19,8 @@ __global__ __launch_bounds__(256) void k_cross_entropy(const float* __restrict__
                                                         int B, int C, float grad_scale,
                                                         float* __restrict__ loss_out,
                                                         float* __restrict__ dlogits,
-                                                        float* __restrict__ stats) {
+                                                        float* __restrict__ stats,
+                                                        const SoftTargets soft) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
@@ -37,21 +41,27 @@ __global__ __launch_bounds__(256) void k_cross_entropy(const float* __restrict__
   for (int j = lane; j < C; j += 64) s += expf(x[j] - m);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  const int64_t y = labels[b];
+  const SoftRow t = soft_row(soft, labels, b);
+  float sx = 0.f;
+  if (t.eps > 0.f) {             // (uniform) sum of the logits: only the smoothing term reads it
+    for (int j = lane; j < C; j += 64) sx += x[j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sx += __shfl_xor(sx, o, 64);
+  }
   const float lse = m + logf(s);
   const float inv_s = 1.f / s;
   const float gs = grad_scale / (float)B;
   if (dlogits != nullptr)
     for (int j = lane; j < C; j += 64) {
       const float pj = expf(x[j] - m) * inv_s;
-      dlogits[(int64_t)b * C + j] = (pj - (j == y ? 1.f : 0.f)) * gs;
+      dlogits[(int64_t)b * C + j] = (pj - soft_target(t, j, C)) * gs;
     }
   if (lane == 0) {
-    const float li = lse - x[y];
+    const float li = lse - soft_picked(t, x[t.y1], x[t.y2], sx, C);
     atomicAdd(loss_out, li / (float)B);
     if (stats != nullptr) {
       atomicAdd(&stats[0], li);
-      if (am == (int)y) atomicAdd(&stats[1], 1.f);
+      if (am == (int)soft_dominant(t)) atomicAdd(&stats[1], 1.f);
     }
   }
 }
@@ -101,8 +111,9 @@ __global__ __launch_bounds__(128) void k_cls_fwd_bwd(
     const float* __restrict__ P, const float* __restrict__ Wc, const float* __restrict__ bc,
     const int64_t* __restrict__ labels, int B, int d, int C, float grad_scale,
     float* __restrict__ logits, float* __restrict__ dlogits, float* __restrict__ dP,
-    float* __restrict__ lossv, float* __restrict__ corrv) {
-  cls_fwd_bwd_body(P, Wc, bc, labels, B, d, C, grad_scale, logits, dlogits, dP, lossv, corrv, blockIdx.x);
+    float* __restrict__ lossv, float* __restrict__ corrv, const SoftTargets soft) {
+  cls_fwd_bwd_body(P, Wc, bc, labels, soft, B, d, C, grad_scale, logits, dlogits, dP, lossv, corrv,
+                   blockIdx.x);
 }
 
 __global__ __launch_bounds__(128) void k_cls_wgrad(
@@ -194,15 +205,26 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, float* __re
 
 }  // namespace
 
+// PcaSoftTargets of the C ABI -> the kernels' argument; NULL is the hard target.  The smoothing is the
+// one host value among the targets: refused here, before anything is enqueued.
+int soft_targets_from(const PcaSoftTargets* soft, const char* who, SoftTargets* out) {
+  *out = SoftTargets{nullptr, nullptr, 0.f};
+  if (soft == nullptr) return PCA_OK;
+  PCA_REQUIRE(std::isfinite(soft->smoothing) && soft->smoothing >= 0.f && soft->smoothing < 1.f,
+              "%s: smoothing=%g must be finite and in [0, 1)", who, (double)soft->smoothing);
+  *out = SoftTargets{soft->labels2, soft->weight, soft->smoothing};
+  return PCA_OK;
+}
+
 // classifier head of the train step; ws needs 2*B floats
 int cls_train_head(const float* P, const float* Wc, const float* bc, const int64_t* labels,
-                   int B, int d, int C, float grad_scale, float* logits, float* dlogits,
+                   const SoftTargets& soft, int B, int d, int C, float grad_scale, float* logits, float* dlogits,
                    float* dP, float* dWc, float* dbc, float* loss_out, float* stats, float* ws,
                    hipStream_t st, BwdDefer* defer) {
   float* lossv = ws;
   float* corrv = ws + B;
   hipLaunchKernelGGL(k_cls_fwd_bwd, dim3(B), dim3(128), (size_t)(d + C) * sizeof(float), st, P, Wc,
-                     bc, labels, B, d, C, grad_scale, logits, dlogits, dP, lossv, corrv);
+                     bc, labels, B, d, C, grad_scale, logits, dlogits, dP, lossv, corrv, soft);
   PCA_TRY(check_launch("k_cls_fwd_bwd"));
   if (defer != nullptr) {          // rides in the phase's terminal launch
     defer->cls = ClsWgradArgs{dlogits, P, lossv, corrv, B, d, C, dWc, dbc, loss_out, stats};
@@ -218,16 +240,25 @@ int cls_train_head(const float* P, const float* Wc, const float* bc, const int64
 
 extern "C" {
 
-int pca_cross_entropy(const float* logits, const int64_t* labels, int B, int C,
-                      float grad_scale, float* loss_out, float* dlogits, float* stats_out,
-                      void* stream) {
+int pca_cross_entropy_soft(const float* logits, const int64_t* labels, const PcaSoftTargets* soft,
+                           int B, int C, float grad_scale, float* loss_out, float* dlogits,
+                           float* stats_out, void* stream) {
   PCA_REQUIRE(logits && labels && loss_out, "cross_entropy: null pointer");
   PCA_REQUIRE(B > 0 && C > 0, "cross_entropy: B=%d C=%d", B, C);
+  pca::SoftTargets t{nullptr, nullptr, 0.f};
+  PCA_TRY(pca::soft_targets_from(soft, "cross_entropy", &t));
   hipStream_t st = pca::as_stream(stream);
   PCA_TRY(pca::fill_zero(loss_out, 1, st));
   hipLaunchKernelGGL(pca::k_cross_entropy, dim3((unsigned)pca::cdiv(B, 4)), dim3(256), 0, st,
-                     logits, labels, B, C, grad_scale, loss_out, dlogits, stats_out);
+                     logits, labels, B, C, grad_scale, loss_out, dlogits, stats_out, t);
   return pca::check_launch("k_cross_entropy");
+}
+
+int pca_cross_entropy(const float* logits, const int64_t* labels, int B, int C,
+                      float grad_scale, float* loss_out, float* dlogits, float* stats_out,
+                      void* stream) {
+  return pca_cross_entropy_soft(logits, labels, nullptr, B, C, grad_scale, loss_out, dlogits,
+                                stats_out, stream);
 }
 
 int pca_eval_tally(const float* logits, const int64_t* labels, int B, int C, int64_t* counts,

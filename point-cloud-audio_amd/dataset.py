@@ -410,6 +410,13 @@ class ESC_wave_pc(Dataset):
                  with probability ``mix_prob``, read circularly from a random start, at a signal-to-noise
                  ratio (clip RMS over background RMS) uniform in ``mix_snr_db`` = (lo, hi) dB.  Labels
                  stay those of the clip
+    mix_targets  True: the mix is between-class learning / mixup - ``batch`` also fills the soft target
+                 of every slot (``labels2_out`` = the class of the background clip, ``weight_out`` = the
+                 weight 1 / (1 + 10^(-snr/20)) of the slot's own label: the clip's share of the amplitude
+                 after RMS matching, about 0.09 .. 0.91 for ``mix_snr_db=(-20, 20)``; a slot that does not
+                 mix carries its own label twice at weight 1), for ``pca_hip.cross_entropy`` /
+                 ``STEngine.fwd_bwd`` / the ``Trainer``.  Needs ``mix_clips``, and with a list of clips
+                 ``mix_labels``, one class per background clip ("self": the clip labels)
 
     drawn from the counter-based device stream (seed, draw number, batch slot, set), as
     ``ESC_pc_temp_randKSS`` draws its points.  With all three off the batches are bit for bit those of
@@ -424,10 +431,10 @@ class ESC_wave_pc(Dataset):
 
     def __init__(self, clips, y, fs, n_fft, hop=None, drop_nyquist=False, jitter=0, gain_db=0.0,
                  win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
-                 mix_prob=0.0, mix_snr_db=(0.0, 20.0)):
+                 mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None):
         self._setup(clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                     device)
-        self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db)
+        self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db, mix_targets, mix_labels)
 
     def _setup(self, clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                device):
@@ -456,7 +463,7 @@ class ESC_wave_pc(Dataset):
         # label of every set (what ESC_pc calls labels)
         self.labels = np.repeat(self.clip_labels, np.diff(self.set_off))
 
-    def _setup_ex(self, speeds, mix_clips, mix_prob, mix_snr_db):
+    def _setup_ex(self, speeds, mix_clips, mix_prob, mix_snr_db, mix_targets=False, mix_labels=None):
         """Speed change and background mix: checked here, on the host, like win_lengths."""
         self.speeds = (1.0,) if speeds is None else tuple(float(v) for v in speeds)
         if not 1 <= len(self.speeds) <= 8 or not all(0.5 <= v <= 2.0 for v in self.speeds):
@@ -477,6 +484,19 @@ class ESC_wave_pc(Dataset):
         if isinstance(self.mix_clips, list) and (
                 not self.mix_clips or any(int(c.shape[0]) < 1 for c in self.mix_clips)):
             raise ValueError("mix_clips: at least one waveform, none of them empty")
+        self.mix_targets = bool(mix_targets)
+        self.mix_labels = None
+        if self.mix_targets:
+            if self.mix_clips is None:
+                raise ValueError("mix_targets needs mix_clips (a list of waveforms, or 'self')")
+            if isinstance(self.mix_clips, list):
+                if mix_labels is None:
+                    raise ValueError("mix_targets with a list of mix_clips needs mix_labels "
+                                     "(one class per background clip)")
+                self.mix_labels = np.asarray(mix_labels).astype(np.int64).reshape(-1)
+                if len(self.mix_labels) != len(self.mix_clips):
+                    raise ValueError(f"mix_labels: {len(self.mix_labels)} labels for "
+                                     f"{len(self.mix_clips)} mix_clips")
         if self._speed_on and int(self._min_len * min(self.ratios)) <= self.n_fft // 2:
             raise ValueError(f"speeds {self.speeds}: the shortest clip ({self._min_len} samples) at speed "
                              f"{max(self.speeds)} is no longer than n_fft / 2 = {self.n_fft // 2}")
@@ -488,6 +508,12 @@ class ESC_wave_pc(Dataset):
     @property
     def _mix_on(self) -> bool:
         return self.mix_prob > 0.0 and self.mix_clips is not None
+
+    @property
+    def soft_targets(self) -> bool:
+        """True when ``batch`` fills ``labels2_out`` / ``weight_out`` (``mix_targets``): the training
+        step then runs on soft targets (``Trainer``)."""
+        return self.mix_targets
 
     def __len__(self):
         return self.set_off[-1]
@@ -511,7 +537,7 @@ class ESC_wave_pc(Dataset):
         ``Evaluator`` and ``fit(test_dataset=...)`` take."""
         v = copy.copy(self)
         v.jitter, v.gain_db = 0, 0.0
-        v.speeds, v.ratios, v.mix_prob = (1.0,), (1.0,), 0.0
+        v.speeds, v.ratios, v.mix_prob, v.mix_targets = (1.0,), (1.0,), 0.0, False
         v.win_lengths = (self.win_lengths[0] if win_length is None else int(win_length),)
         if not 1 <= v.win_lengths[0] <= self.n_fft:
             raise ValueError(f"win_length {v.win_lengths[0]} outside [1, n_fft = {self.n_fft}]")
@@ -529,7 +555,7 @@ class ESC_wave_pc(Dataset):
                                   None if self.tarr is None else f32(self.tarr),
                                   i64(self.clip_labels))
             self._store["win"] = {}
-            if self._mix_on:              # the RMS vectors and the background corpus: once, here
+            if self._mix_on or self.mix_targets:   # the RMS vectors and the background corpus: once, here
                 self._mix_resident()
         return self._store["res"]
 
@@ -556,21 +582,34 @@ class ESC_wave_pc(Dataset):
                 self._store["mix"] = (rms, bg, boff, pca_hip.clip_rms(bg, boff, max(lens)), max(lens))
         return self._store["mix"]
 
+    def _mix_labels_dev(self):
+        """The classes of the background clips on the device (``mix_targets``)."""
+        if "mix_labels" not in self._store:
+            lab = self._resident()[5]
+            self._store["mix_labels"] = lab if self.mix_clips == "self" else torch.as_tensor(
+                self.mix_labels).to(lab.device)
+        return self._store["mix_labels"]
+
     def batch(self, idx: torch.Tensor, out=None, labels_out=None, draw_dev=None,
-              want_meta: bool = False, want_samples: bool = False):
+              want_meta: bool = False, want_samples: bool = False, labels2_out=None, weight_out=None):
         """idx int64[B] on the device -> (points [B, num_points, 2 or 3] float32, labels int64[B]
         [, meta int32 [B, 4] = (clip, centre sample of frame 0, window length, bits of the gain)]).
         With ``speeds`` or the mix on, meta is int32 [B, 8] (pca_hip.frame_points_ex: + speed index,
         background clip or -1, its start, bits of its scale) and ``want_samples`` adds the float32
-        [B, Ntemp, n_fft] samples of every frame before window and gain."""
+        [B, Ntemp, n_fft] samples of every frame before window and gain.  With ``soft_targets`` the
+        return ends with (labels2 int64[B], weight float32[B]), written into ``labels2_out`` /
+        ``weight_out`` when given, by the same launch."""
         waves, woff, soff, f32, t32, lab = self._resident()
         self._draw += 1
-        if self._speed_on or self._mix_on:
+        if self._speed_on or self._mix_on or self.mix_targets:
             mix = {}
-            if self._mix_on:
+            if self._mix_on or self.mix_targets:
                 rms, bg, boff, brms, bmax = self._mix_resident()
                 mix = dict(clip_rms=rms, bg_waves=bg, bg_off=boff, bg_rms=brms, bg_max_len=bmax,
                            mix_prob=self.mix_prob, mix_snr_db=self.mix_snr_db)
+            if self.mix_targets:
+                mix.update(bg_labels=self._mix_labels_dev(), labels2_out=labels2_out,
+                           weight_out=weight_out)
             return pca_hip.frame_points_ex(
                 waves, woff, soff, idx, self.n_fft, self.hop, self.F, f32, t32, self._ntemp,
                 max_len=self._max_len, min_len=self._min_len, clip_labels=lab,
@@ -606,11 +645,11 @@ class ESC_wave_pc_temp(ESC_wave_pc):
 
     def __init__(self, clips, y, fs, n_fft, Ntemp, hop=None, jitter=0, gain_db=0.0,
                  win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
-                 mix_prob=0.0, mix_snr_db=(0.0, 20.0)):
+                 mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None):
         self._ntemp = int(Ntemp)
         assert self._ntemp >= 1
         self._setup(clips, y, fs, n_fft, hop, True, jitter, gain_db, win_lengths, norm, seed, device)
-        self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db)
+        self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db, mix_targets, mix_labels)
         self.tarr = np.linspace(0, (self.hop / fs) * self._ntemp, self._ntemp)
 
 

@@ -71,6 +71,10 @@ class PcaFrameAugEx(C.Structure):
         ("snr_lo_db", C.c_double), ("snr_hi_db", C.c_double)]
 
 
+class PcaSoftTargets(C.Structure):
+    _fields_ = [("labels2", C.c_void_p), ("weight", C.c_void_p), ("smoothing", C.c_float)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64),
                 ("sa_m", C.c_int64), ("sa_k", C.c_int64), ("sb_k", C.c_int64),
@@ -131,6 +135,8 @@ SIGNATURES = {
     "pca_linear_bwd_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "pca_cross_entropy": (C.c_int, [c_fp, c_i64p, C.c_int, C.c_int, C.c_float, c_fp, c_fp,
                                     c_fp, c_vp]),
+    "pca_cross_entropy_soft": (C.c_int, [c_fp, c_i64p, C.POINTER(PcaSoftTargets), C.c_int, C.c_int,
+                                         C.c_float, c_fp, c_fp, c_fp, c_vp]),
     "pca_eval_tally": (C.c_int, [c_fp, c_i64p, C.c_int, C.c_int, c_i64p, C.c_int, c_vp]),
     "pca_clip_aggregate": (C.c_int, [c_fp, C.c_int64, C.c_int, c_i64p, C.c_int, c_i64p, c_fp, c_vp,
                                      c_i64p, c_i64p, C.c_int, c_vp]),
@@ -155,6 +161,10 @@ SIGNATURES = {
     "pca_frame_points_ex": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p, c_i64p,
                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp,
                                       C.POINTER(PcaFrameAugEx), c_fp, c_i64p, c_vp, c_fp, c_vp]),
+    "pca_frame_points_ex_targets": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p,
+                                              c_i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp,
+                                              c_fp, C.POINTER(PcaFrameAugEx), c_fp, c_i64p, c_vp, c_fp,
+                                              c_i64p, c_i64p, c_fp, c_vp]),
     "pca_baseline_param_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, c_vp, C.c_int, C.c_int]),
     "pca_fb_forward": (C.c_int, [c_fp, C.c_int64, C.c_int64, c_i64p, C.c_int, C.c_int, c_vp,
                                  C.c_int, C.c_int, c_fp, C.c_int64, C.c_int, C.c_int, C.c_uint64,
@@ -180,6 +190,9 @@ SIGNATURES = {
                                         c_vp]),
     "pca_st_train_fwd_bwd": (C.c_int, [C.POINTER(StConfig), c_fp, c_fp, c_vp, c_i64p, c_fp,
                                        c_fp, c_fp, c_fp, C.c_float, C.c_int, c_vp, c_vp]),
+    "pca_st_train_fwd_bwd_soft": (C.c_int, [C.POINTER(StConfig), c_fp, c_fp, c_vp, c_i64p,
+                                            C.POINTER(PcaSoftTargets), c_fp, c_fp, c_fp, c_fp,
+                                            C.c_float, C.c_int, c_vp, c_vp]),
     "pca_prof_start": (C.c_int, [C.c_int, C.c_int]),
     "pca_prof_stop": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                 C.POINTER(C.c_double), C.POINTER(C.c_double)]),

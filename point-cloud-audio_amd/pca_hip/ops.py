@@ -323,31 +323,53 @@ def linear(X, W, b):
 
 
 class _CrossEntropyFn(torch.autograd.Function):
-    """nn.CrossEntropyLoss() (mean), Code/settransformer.py:88,104."""
+    """nn.CrossEntropyLoss() (mean), Code/settransformer.py:88,104; with ``labels2`` / ``weight`` /
+    ``label_smoothing`` the soft-target form (pca_cross_entropy_soft)."""
 
     @staticmethod
-    def forward(ctx, logits, labels):
-        _need_cuda(logits, labels)
+    def forward(ctx, logits, labels, labels2=None, weight=None, label_smoothing=0.0):
+        _need_cuda(logits, labels, labels2, weight)
         logits = _f32c(logits)
         labels = labels.to(torch.int64).contiguous()
         B, Cc = logits.shape
+        soft = labels2 is not None or weight is not None or label_smoothing != 0.0
         with torch.cuda.device(logits.device):
             loss = torch.empty(1, dtype=torch.float32, device=logits.device)
             dlog = torch.empty_like(logits)
-            check(lib().pca_cross_entropy(_ptr(logits), _ptr(labels), B, Cc, 1.0, _ptr(loss),
-                                          _ptr(dlog), None, _stream(logits)),
-                  "pca_cross_entropy")
+            if soft:
+                if labels2 is not None:
+                    labels2 = labels2.to(torch.int64).contiguous()
+                    assert labels2.numel() == B
+                if weight is not None:
+                    weight = _f32c(weight)
+                    assert weight.numel() == B
+                tg = _lib.PcaSoftTargets(_ptr(labels2).value, _ptr(weight).value, float(label_smoothing))
+                check(lib().pca_cross_entropy_soft(_ptr(logits), _ptr(labels), C.byref(tg), B, Cc, 1.0,
+                                                   _ptr(loss), _ptr(dlog), None, _stream(logits)),
+                      "pca_cross_entropy_soft")
+            else:
+                check(lib().pca_cross_entropy(_ptr(logits), _ptr(labels), B, Cc, 1.0, _ptr(loss),
+                                              _ptr(dlog), None, _stream(logits)),
+                      "pca_cross_entropy")
         ctx.save_for_backward(dlog)
         return loss.squeeze(0)
 
     @staticmethod
     def backward(ctx, g):
         (dlog,) = ctx.saved_tensors
-        return dlog * g, None
+        return dlog * g, None, None, None, None
 
 
-def cross_entropy(logits, labels):
-    return _CrossEntropyFn.apply(logits, labels)
+def cross_entropy(logits, labels, labels2=None, weight=None, label_smoothing=0.0):
+    """Mean cross-entropy of ``logits`` [B, C] against ``labels`` int64 [B].  With ``labels2`` int64 [B],
+    ``weight`` float32 [B] in [0, 1] (the share of ``labels``) and / or ``label_smoothing`` in [0, 1) the
+    target of sample b is (1 - eps)(w onehot(labels) + (1 - w) onehot(labels2)) + eps / C, as
+    ``torch.nn.functional.cross_entropy`` with probability targets; ``labels2=None`` means labels,
+    ``weight=None`` means 1.  No gradient flows to the targets.  The two-argument call runs
+    pca_cross_entropy as before."""
+    if labels2 is None and weight is None and label_smoothing == 0.0:
+        return _CrossEntropyFn.apply(logits, labels)
+    return _CrossEntropyFn.apply(logits, labels, labels2, weight, float(label_smoothing))
 
 
 def eval_tally(logits: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor,
@@ -840,7 +862,9 @@ def frame_points_ex(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.
                     mix_prob: float = 0.0, mix_snr_db=(0.0, 0.0),
                     out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None,
                     draw_dev: Optional[torch.Tensor] = None, want_meta: bool = False,
-                    want_samples: bool = False):
+                    want_samples: bool = False, bg_labels: Optional[torch.Tensor] = None,
+                    labels2_out: Optional[torch.Tensor] = None,
+                    weight_out: Optional[torch.Tensor] = None):
     """``frame_points`` with a speed change and a background mix applied while the frame is loaded
     (pca_frame_points_ex); the arguments they share mean the same, and with ``ratios == (1.0,)`` and
     ``mix_prob == 0`` (or no ``bg_waves``) the points, labels and meta[:, :4] are ``frame_points``' bits.
@@ -854,8 +878,18 @@ def frame_points_ex(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.
                 circularly from a random start, at an SNR uniform in ``mix_snr_db`` = (lo, hi) dB.
     Returns (points, labels or None [, meta int32 [B, 8] = (clip, centre of frame 0 in the resampled
     clip, window length, bits of the gain, speed index, background clip or -1, its start, bits of the
-    fp32 background scale)] [, samples float32 [B, Nt, n_fft]: the frames before window and gain])."""
-    _need_cuda(waves, wave_off, set_off, idx, farr, clip_rms, bg_waves, bg_off, bg_rms)
+    fp32 background scale)] [, samples float32 [B, Nt, n_fft]: the frames before window and gain]
+    [, labels2 int64 [B], weight float32 [B]]).
+
+    bg_labels   int64[n_bg], the classes of the background clips (needs ``clip_labels``): the call
+                (pca_frame_points_ex_targets) also returns, after everything else, the soft target of each
+                slot for ``cross_entropy`` / ``STEngine.fwd_bwd``: ``labels2`` = the background clip's class
+                and ``weight`` = 1 / (1 + 10^(-snr/20)), the primary clip's share of the amplitude after
+                RMS matching (between-class learning's rule with the RMS for its A-weighted level;
+                ``mix_snr_db=(-20, 20)`` spans weights of about 0.09 .. 0.91), in a slot that mixes;
+                ``labels2`` = the slot's own label and ``weight`` = 1 in every other slot.  Everything
+                else is bit for bit what the call without ``bg_labels`` returns."""
+    _need_cuda(waves, wave_off, set_off, idx, farr, clip_rms, bg_waves, bg_off, bg_rms, bg_labels)
     assert waves.dtype == torch.float32 and waves.is_contiguous() and farr.dtype == torch.float32
     assert wave_off.dtype == set_off.dtype == idx.dtype == torch.int64
     assert wave_off.numel() == set_off.numel() >= 2 and farr.numel() >= n_bins
@@ -895,17 +929,30 @@ def frame_points_ex(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.
             (C.c_double * _lib.FRAME_MAX_SPEEDS)(*ratios), _ptr(tables),
             _ptr(bg_waves), _ptr(bg_off), _ptr(bg_rms), _ptr(clip_rms), int(bg_max_len),
             float(mix_prob), float(mix_snr_db[0]), float(mix_snr_db[1]))
-        check(lib().pca_frame_points_ex(_ptr(waves), _ptr(wave_off), _ptr(set_off), n_clips,
-                                        int(max_len), int(min_len), _ptr(clip_labels), _ptr(idx), B,
-                                        int(n_fft), int(hop), int(n_bins), int(Nt), _ptr(farr),
-                                        _ptr(tarr), C.byref(aug), _ptr(out), _ptr(labels_out),
-                                        _ptr(meta), _ptr(samples), _stream(waves)),
-              "pca_frame_points_ex")
+        args = (_ptr(waves), _ptr(wave_off), _ptr(set_off), n_clips, int(max_len), int(min_len),
+                _ptr(clip_labels), _ptr(idx), B, int(n_fft), int(hop), int(n_bins), int(Nt), _ptr(farr),
+                _ptr(tarr), C.byref(aug), _ptr(out), _ptr(labels_out), _ptr(meta), _ptr(samples))
+        if bg_labels is not None:
+            assert bg_labels.dtype == torch.int64 and bg_labels.is_contiguous()
+            assert bg_labels.numel() == n_bg, "one background label per background clip"
+            if labels2_out is None:
+                labels2_out = torch.empty(B, dtype=torch.int64, device=waves.device)
+            if weight_out is None:
+                weight_out = torch.empty(B, dtype=torch.float32, device=waves.device)
+            assert labels2_out.dtype == torch.int64 and labels2_out.numel() == B
+            assert weight_out.dtype == torch.float32 and weight_out.numel() == B
+            check(lib().pca_frame_points_ex_targets(*args, _ptr(bg_labels), _ptr(labels2_out),
+                                                    _ptr(weight_out), _stream(waves)),
+                  "pca_frame_points_ex_targets")
+        else:
+            check(lib().pca_frame_points_ex(*args, _stream(waves)), "pca_frame_points_ex")
     ret = (out, labels_out)
     if want_meta:
         ret += (meta,)
     if want_samples:
         ret += (samples,)
+    if bg_labels is not None:
+        ret += (labels2_out, weight_out)
     return ret
 
 

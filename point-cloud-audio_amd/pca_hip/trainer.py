@@ -311,7 +311,29 @@ class STEngine:
         return self.logits, attn, key
 
     def fwd_bwd(self, X: torch.Tensor, labels: torch.Tensor, phase: int = -1,
-                grad_scale: float = 1.0, lengths: Optional[torch.Tensor] = None) -> None:
+                grad_scale: float = 1.0, lengths: Optional[torch.Tensor] = None,
+                labels2: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None,
+                label_smoothing: float = 0.0) -> None:
+        """One training step's forward, loss and backward.  ``labels2`` int64[B] / ``weight`` float32[B]
+        / ``label_smoothing``: the soft targets of pca_st_train_fwd_bwd_soft (the second class of each
+        set, the weight of ``labels``, the smoothing); ``stats`` then counts accuracy against the
+        dominant label.  With none of them set this is the hard-label call, as before."""
+        if labels2 is not None or weight is not None or label_smoothing != 0.0:
+            assert labels2 is None or (labels2.is_cuda and labels2.dtype == torch.int64
+                                       and labels2.numel() == self.cfg.B)
+            assert weight is None or (weight.is_cuda and weight.dtype == torch.float32
+                                      and weight.numel() == self.cfg.B)
+            soft = _lib.PcaSoftTargets(None if labels2 is None else labels2.data_ptr(),
+                                       None if weight is None else weight.data_ptr(),
+                                       float(label_smoothing))
+            check(lib().pca_st_train_fwd_bwd_soft(C.byref(self.cfg), self.flat.data_ptr(), X.data_ptr(),
+                                                  self._len_ptr(lengths, self.cfg.B), labels.data_ptr(),
+                                                  C.byref(soft), self.grads.data_ptr(),
+                                                  self.loss.data_ptr(), self.stats.data_ptr(),
+                                                  self.logits.data_ptr(), grad_scale, phase,
+                                                  self.ws.data_ptr(), self._stream()),
+                  "pca_st_train_fwd_bwd_soft")
+            return
         check(lib().pca_st_train_fwd_bwd(C.byref(self.cfg), self.flat.data_ptr(), X.data_ptr(),
                                          self._len_ptr(lengths, self.cfg.B),
                                          labels.data_ptr(), self.grads.data_ptr(),
@@ -335,14 +357,23 @@ class Trainer:
                  shuffle: bool = True, process_group=None, keep_grads: bool = False,
                  overlap: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_schedule=None,
-                 schedule_steps: Optional[int] = None):
-        """max_grad_norm: clip the (rank-averaged) gradient to this global L2 norm before Adam
+                 schedule_steps: Optional[int] = None, label_smoothing: float = 0.0):
+        """label_smoothing: eps in [0, 1) of the loss's targets.  A dataset with ``soft_targets``
+        (dataset.ESC_wave_pc(..., mix_targets=True)) makes the step train on mixed labels: the frame
+        launch writes the second label and the label weight of every slot into buffers the Trainer
+        owns, and the loss stage reads them - no launch more, and no new state to save (the targets come
+        from the draws that resume exactly).  ``read_stats`` then counts accuracy against the dominant
+        label.  With 0 and a dataset without ``soft_targets`` the step is enqueued as it always was.
+        max_grad_norm: clip the (rank-averaged) gradient to this global L2 norm before Adam
         (torch.nn.utils.clip_grad_norm_).  skip_nonfinite: a step whose gradient norm is inf / NaN
         changes neither parameters nor moments.  lr_schedule: the learning rate per step (step 1
         first; the last entry holds from there on) as a sequence of floats, or a callable
         step -> lr with ``schedule_steps``; it lives in a device table, so a captured step follows it
         without a re-capture.  All three at their defaults: the plain pca_adam_step launch."""
         self.ds = dataset
+        self.label_smoothing = float(label_smoothing)
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
         self.keep_grads = keep_grads    # True: gradients of the last step stay readable
         self.B = int(batch_size)
         self.N = int(dataset.num_points)
@@ -364,6 +395,11 @@ class Trainer:
             self.X = torch.empty((self.B, self.N, self.eng.cfg.din), dtype=torch.float32,
                                  device=self.dev)
             self.labels = torch.zeros(self.B, dtype=torch.int64, device=self.dev)
+            # soft targets (dataset.soft_targets): second label and weight of the first, per slot
+            self.labels2 = self.weight = None
+            if getattr(dataset, "soft_targets", False):
+                self.labels2 = torch.zeros(self.B, dtype=torch.int64, device=self.dev)
+                self.weight = torch.ones(self.B, dtype=torch.float32, device=self.dev)
             # padded batches of variable-size sets (dataset.variable_length): point counts
             self.lengths = (torch.zeros(self.B, dtype=torch.int32, device=self.dev)
                             if getattr(dataset, "variable_length", False) else None)
@@ -464,7 +500,17 @@ class Trainer:
         return self.indices.next()
 
     # ---- the three device segments of a step ---------------------------------------
+    def _soft_kw(self) -> dict:
+        """What ``fwd_bwd`` takes beyond the hard step; empty: the hard step, as enqueued before."""
+        kw = {}
+        if self.labels2 is not None:
+            kw.update(labels2=self.labels2, weight=self.weight)
+        if self.label_smoothing != 0.0:
+            kw.update(label_smoothing=self.label_smoothing)
+        return kw
+
     def _seg0(self):     # pack + zero grads + forward + loss + backward(dec, enc.1)
+        tk = {} if self.labels2 is None else dict(labels2_out=self.labels2, weight_out=self.weight)
         if self._cursor_mode:
             kw = dict(lengths_out=self.lengths) if self.lengths is not None else {}
             # the pack rides in the engine's first launch (pca_pack_defer): one launch less per step
@@ -477,7 +523,7 @@ class Trainer:
                 if self.keep_grads:
                     self.eng.grads.zero_()
                 self.eng.fwd_bwd(self.X, self.labels, phase=0 if self._split else -1,
-                                 lengths=self.lengths)
+                                 lengths=self.lengths, **self._soft_kw())
             except BaseException:
                 if defer:            # disarm (drops a pending job) without masking the error in flight
                     lib().pca_pack_defer(0)
@@ -492,19 +538,19 @@ class Trainer:
             # random sub-sampling datasets: the draw number must advance per REPLAY of a captured
             # step, so it is read on the device from the optimiser's step counter
             self.ds.batch(self.idx, out=self.X, labels_out=self.labels,
-                          draw_dev=self.step_count)
+                          draw_dev=self.step_count, **tk)
         else:
-            self.ds.batch(self.idx, out=self.X, labels_out=self.labels)
+            self.ds.batch(self.idx, out=self.X, labels_out=self.labels, **tk)
         if self.keep_grads:           # otherwise the Adam pass leaves them cleared
             self.eng.grads.zero_()
         # one GPU: the whole backward in one call (the shared-query gradient kernels of all three
         # blocks then share one pair of launches); several GPUs: stop at the bucket boundary
         self.eng.fwd_bwd(self.X, self.labels, phase=0 if self._split else -1,
-                         lengths=self.lengths)
+                         lengths=self.lengths, **self._soft_kw())
 
     def _seg1(self):     # backward(enc.0)
         if self._split:
-            self.eng.fwd_bwd(self.X, self.labels, phase=1, lengths=self.lengths)
+            self.eng.fwd_bwd(self.X, self.labels, phase=1, lengths=self.lengths, **self._soft_kw())
 
     def _seg2(self):     # Adam over the flat vector
         e = self.eng
@@ -626,7 +672,9 @@ class Trainer:
     # ---- epoch statistics ------------------------------------------------------------
     def read_stats(self, reset: bool = True) -> Tuple[float, float]:
         """(sum of per-sample losses, number of correct predictions) since the last reset,
-        summed over ranks.  One host sync."""
+        summed over ranks.  One host sync.  On soft targets the loss is the cross-entropy against the
+        mixed (and smoothed) target and a prediction counts as correct when it is the dominant label:
+        the slot's own label when its weight is >= 0.5, the second label otherwise."""
         st = self.eng.stats.clone()
         if self.world > 1:
             dist.all_reduce(st, group=self.pg)
