@@ -56,8 +56,10 @@ struct WgradSlabs {          // optional slab mode of wgrad128_launch
   size_t used;               // out: bytes of ws taken
 };
 // g_bf16 / a_bf16: element type of every job's G / A (bf16 or fp32)
+// `small`: the layer-1 fc_v job (wgrad_small_f32_launch's, with a slab) as further rows of the same launch
+struct SmallWgradArgs;
 int wgrad128_launch(const WgradJobs& jobs, bool g_bf16, bool a_bf16, int rows_per_wg,
-                    hipStream_t st, WgradSlabs* slabs = nullptr);
+                    hipStream_t st, WgradSlabs* slabs = nullptr, const SmallWgradArgs* small = nullptr);
 // The two halves of wgrad128_launch for a caller that puts two lists into one launch: wgrad128_place
 // gives every job of a list its slabs (slab mode; rows_per_wg doubles until they fit `slabs->cap`) and
 // appends their sum jobs; wgrad128_launch_step runs a placed bf16 list (G, A bf16; empty when it ran
@@ -65,7 +67,8 @@ int wgrad128_launch(const WgradJobs& jobs, bool g_bf16, bool a_bf16, int rows_pe
 // per workgroup (>= 128), and the riders as ONE launch (k_wgrad128_step).
 int wgrad128_place(WgradJobs& jobs, int& rows_per_wg, WgradSlabs* slabs);
 int wgrad128_launch_step(const WgradJobs& bf16_jobs, int rows_per_wg_bf16, const WgradJobs& f32_jobs,
-                         int rows_per_wg_f32, const SlabSumJobs& riders, hipStream_t st);
+                         int rows_per_wg_f32, const SlabSumJobs& riders, hipStream_t st,
+                         const SmallWgradArgs* small = nullptr);
 
 // ---- the d = 256 job (wgrad256.hip; launchers in d256.hpp) ------------------
 // dW[256 x 256] += G^T A, db[256] += colsum(G) (nullable); G, A bf16 [M][256]
@@ -161,6 +164,8 @@ bool wgrad_slabs_on();       // reductions of the fused d = 128 path as slabs + 
                              // (PCA_WGRAD_SLABS=0: fp32 atomics)
 bool wgrad_fold_on();        // the two deferred d = 128 lists in one launch (PCA_WGRAD_FOLD=0: two)
 bool wgrad_ride_on();        // the bf16 list beside layer 1's few-queries backward (PCA_WGRAD_RIDE)
+bool post_fuse_on();         // both shared-query post stages inside k_terminal1, the layer-1 fc_v job in
+                             // k_wgrad128_step (PCA_POST_FUSE=0: k_terminal1, then k_mab0_post2)
 // launch `jobs` now, or append them to the matching list of `defer`
 int wgrad128_defer(BwdDefer* defer, const WgradJobs& jobs, bool bf16, int rows_per_wg,
                    hipStream_t st);

@@ -78,23 +78,30 @@ __device__ __forceinline__ void cls_wgrad_body(
   }
 }
 
-// dW[128 x dq] += G[M x 128]^T . X_h[M x dq] (dq <= 4), db += colsum(G); 256 threads
-template <typename GT>
-__device__ __forceinline__ void wgrad_small_body(const GT* __restrict__ G,
+// dW[128 x dq] += G[M x 128]^T . X_h[M x dq] (dq <= 4), db += colsum(G) over the rows of one block (rows_per_wg
+// rows) per 256 threads: a workgroup of NT threads takes blocks wg * (NT / 256) + (thread / 256), each group of
+// four waves exactly as a 256-thread workgroup would (a block beyond M: a wave-uniform predicate turns the
+// group off; in a 256-thread caller it is a constant).  EVERY thread has to call it (one barrier, outside the
+// predicate).  `red`: (NT / 256) x 128 x 5 floats of LDS.
+template <typename GT, int NT = 256>
+__device__ __forceinline__ void wgrad_small_rows(const GT* __restrict__ G,
                                                  const float* __restrict__ X, int64_t M, int dq,
                                                  int rows_per_wg, int64_t x_head_stride,
                                                  float* __restrict__ dW, float* __restrict__ db,
-                                                 int blk, float* __restrict__ slab = nullptr) {
+                                                 int wg, float* __restrict__ slab, float (*red)[5]) {
   constexpr int D = 128;
-  __shared__ float red[128][5];
-  const int f = threadIdx.x & 127, ph = threadIdx.x >> 7;
+  const int grp = NT == 256 ? 0 : (int)(threadIdx.x >> 8);
+  const int blk = wg * (NT / 256) + grp;
+  const bool on = NT == 256 || (int64_t)blk * rows_per_wg < M;
+  red += grp * 128;
+  const int f = threadIdx.x & 127, ph = (threadIdx.x >> 7) & 1;
   const float* __restrict__ Xh = X + (int64_t)(f >> 5) * x_head_stride;
   const int64_t r0 = (int64_t)blk * rows_per_wg;
   const int64_t r1 = (r0 + rows_per_wg < M) ? r0 + rows_per_wg : M;
   float acc[4] = {0.f, 0.f, 0.f, 0.f}, bs = 0.f;
   // batches of 16 rows: 16 independent G loads (+ the broadcast X rows) in flight; rows beyond the
   // range are read from the last valid row (unconditional loads) and zeroed
-  for (int64_t row = r0 + ph; row < r1; row += 32) {
+  for (int64_t row = r0 + ph; on && row < r1; row += 32) {
     float gv[16], xv[16][4];
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
@@ -113,12 +120,13 @@ __device__ __forceinline__ void wgrad_small_body(const GT* __restrict__ G,
       for (int c = 0; c < 4; ++c) acc[c] = fmaf(gv[u], xv[u][c], acc[c]);
     }
   }
-  if (ph == 1) {
+  if (on && ph == 1) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) red[f][c] = acc[c];
     red[f][4] = bs;
   }
   __syncthreads();
+  if (!on) return;
   if (ph == 0 && slab != nullptr) {       // this workgroup's partial (summed by rider rows later)
     float* out = slab + (int64_t)blk * (D * dq + D);
     for (int c = 0; c < dq; ++c) out[f * dq + c] = acc[c] + red[f][c];
@@ -127,6 +135,17 @@ __device__ __forceinline__ void wgrad_small_body(const GT* __restrict__ G,
     for (int c = 0; c < dq; ++c) atomicAdd(&dW[f * dq + c], acc[c] + red[f][c]);
     if (db != nullptr) atomicAdd(&db[f], bs + red[f][4]);
   }
+}
+
+// the same for a 256-thread workgroup, with LDS of its own
+template <typename GT>
+__device__ __forceinline__ void wgrad_small_body(const GT* __restrict__ G,
+                                                 const float* __restrict__ X, int64_t M, int dq,
+                                                 int rows_per_wg, int64_t x_head_stride,
+                                                 float* __restrict__ dW, float* __restrict__ db,
+                                                 int blk, float* __restrict__ slab = nullptr) {
+  __shared__ float red[128][5];
+  wgrad_small_rows<GT, 256>(G, X, M, dq, rows_per_wg, x_head_stride, dW, db, blk, slab, red);
 }
 
 }  // namespace pca

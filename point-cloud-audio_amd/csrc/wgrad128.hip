@@ -270,14 +270,23 @@ constexpr int wgrad128_depth() {
   return std::is_same<GT, __bf16>::value && std::is_same<AT, __bf16>::value ? 3 : 1;
 }
 
-// blockIdx.y selects the job; the rows beyond the jobs are rider rows
+// blockIdx.y selects the job; behind the jobs `sw_rows` rows of the layer-1 fc_v job (as in k_wgrad128_step
+// below: NG blocks of rows per workgroup), then the rider rows
 template <typename GT, typename AT, int NG>
 __global__ __launch_bounds__(256 * NG) void k_wgrad128(const WgradJobs jobs, int rows_per_wg,
+                                                       const SmallWgradArgs w, int sw_rows,
                                                        const SlabSumJobs riders) {
   __shared__ __attribute__((aligned(16))) char lds[4 * 32 * 256 * 2];
-  if ((int)blockIdx.y >= jobs.n) {          // rider rows: partial sums that are due now
-    slab_sum_body(riders.j[blockIdx.y - jobs.n], blockIdx.x, threadIdx.x,
+  if ((int)blockIdx.y >= jobs.n + sw_rows) {          // rider rows: partial sums that are due now
+    slab_sum_body(riders.j[blockIdx.y - jobs.n - sw_rows], blockIdx.x, threadIdx.x,
                   reinterpret_cast<float4*>(lds));
+    return;
+  }
+  if ((int)blockIdx.y >= jobs.n) {
+    const int wg = ((int)blockIdx.y - jobs.n) * (int)gridDim.x + (int)blockIdx.x;
+    if ((int64_t)wg * NG * w.rows_per_wg < w.M)      // (uniform per workgroup)
+      wgrad_small_rows<float, 256 * NG>(w.G, w.X, w.M, w.dq, w.rows_per_wg, w.x_head_stride, w.dW, w.db, wg,
+                                        w.slab, reinterpret_cast<float (*)[5]>(lds));
     return;
   }
   wgrad128_body<GT, AT, NG, wgrad128_depth<GT, AT>()>(jobs.j[blockIdx.y], rows_per_wg, lds);
@@ -287,8 +296,13 @@ __global__ __launch_bounds__(256 * NG) void k_wgrad128(const WgradJobs jobs, int
 // long ones, so they are placed first), then the fp32 jobs, then the rider rows.  Each list has its own
 // rows per workgroup; a row whose blockIdx.x lies beyond its range leaves at once.  The operand type
 // is uniform per workgroup, and both lists run two row groups.
+// Behind the fp32 jobs, `sw_rows` rows of the layer-1 fc_v job (its workgroup = row * gridDim.x + blockIdx.x,
+// so the rows are as wide as the grid; each half of a workgroup takes one block of rows_per_wg rows, the
+// partition and the slabs of the 256-thread launch): it reads what layer 1's few-queries backward wrote, like
+// the fp32 jobs, and its partials are summed with theirs in k_terminal1.
 __global__ __launch_bounds__(512) void k_wgrad128_step(const WgradJobs bf, int rpw_bf,
                                                        const WgradJobs f32, int rpw_f32,
+                                                       const SmallWgradArgs w, int sw_rows,
                                                        const SlabSumJobs riders) {
   __shared__ __attribute__((aligned(16))) char lds[4 * 32 * 256 * 2];
   const int y = blockIdx.y;
@@ -296,9 +310,15 @@ __global__ __launch_bounds__(512) void k_wgrad128_step(const WgradJobs bf, int r
     wgrad128_body<__bf16, __bf16, 2, wgrad128_depth<__bf16, __bf16>()>(bf.j[y], rpw_bf, lds);
   } else if (y < bf.n + f32.n) {
     wgrad128_body<float, float, 2, wgrad128_depth<float, float>()>(f32.j[y - bf.n], rpw_f32, lds);
+  } else if (y < bf.n + f32.n + sw_rows) {
+    const int wg = (y - bf.n - f32.n) * (int)gridDim.x + (int)blockIdx.x;
+    if ((int64_t)wg * 2 * w.rows_per_wg < w.M)       // (uniform per workgroup; two blocks of rows each)
+      wgrad_small_rows<float, 512>(w.G, w.X, w.M, w.dq, w.rows_per_wg, w.x_head_stride, w.dW, w.db, wg,
+                                   w.slab, reinterpret_cast<float (*)[5]>(lds));
   } else {
     // (32 loads in flight: when the bf16 list ran in k_mab0_small_ride nothing hides these chains)
-    slab_sum_body<32>(riders.j[y - bf.n - f32.n], blockIdx.x, threadIdx.x, reinterpret_cast<float4*>(lds));
+    slab_sum_body<32>(riders.j[y - bf.n - f32.n - sw_rows], blockIdx.x, threadIdx.x,
+                      reinterpret_cast<float4*>(lds));
   }
 }
 
@@ -387,28 +407,41 @@ static int rider_extent(const SlabSumJobs& riders, unsigned& gx) {
   return PCA_OK;
 }
 
+// the layer-1 fc_v job of a launch (slab mode only: its partials are summed later): rows of the grid's width
+static int small_rows(const SmallWgradArgs* sw, unsigned gx, int blocks_per_wg, int* rows) {
+  PCA_REQUIRE(sw == nullptr || (sw->slab != nullptr && sw->M > 0 && sw->rows_per_wg > 0 && sw->dq >= 1 &&
+                                sw->dq <= 4),
+              "wgrad128: the small job rides with a slab");
+  *rows = sw == nullptr ? 0 : (int)cdiv(cdiv(sw->M, (int64_t)blocks_per_wg * sw->rows_per_wg), gx);
+  return PCA_OK;
+}
+
 int wgrad128_launch(const WgradJobs& jobs_in, bool g_bf16, bool a_bf16, int rows_per_wg,
-                    hipStream_t st, WgradSlabs* sl) {
+                    hipStream_t st, WgradSlabs* sl, const SmallWgradArgs* sw) {
   WgradJobs jobs = jobs_in;
   const int64_t maxM = max_rows(jobs);
   SlabSumJobs riders{};
   if (sl != nullptr && sl->riders != nullptr) riders = *sl->riders;
+  PCA_REQUIRE(sw == nullptr || (maxM > 0 && jobs.n > 0), "wgrad128: the small job rides with a list that has rows");
   if (maxM == 0 || jobs.n == 0) return slab_sum_jobs(riders, st);
   PCA_TRY(wgrad128_place(jobs, rows_per_wg, sl));
   unsigned gx = (unsigned)cdiv(maxM, rows_per_wg);
   PCA_TRY(rider_extent(riders, gx));
-  const dim3 grid(gx, (unsigned)(jobs.n + riders.n));
   // two row groups per workgroup when every workgroup has at least four tiles to share
   const bool two = rows_per_wg >= 128;
+  int sw_rows = 0;
+  PCA_TRY(small_rows(sw, gx, two ? 2 : 1, &sw_rows));
+  const SmallWgradArgs w = sw != nullptr ? *sw : SmallWgradArgs{};
+  const dim3 grid(gx, (unsigned)(jobs.n + sw_rows + riders.n));
   if (g_bf16 && a_bf16) {
-    if (two) hipLaunchKernelGGL((k_wgrad128<__bf16, __bf16, 2>), grid, dim3(512), 0, st, jobs, rows_per_wg, riders);
-    else hipLaunchKernelGGL((k_wgrad128<__bf16, __bf16, 1>), grid, dim3(256), 0, st, jobs, rows_per_wg, riders);
+    if (two) hipLaunchKernelGGL((k_wgrad128<__bf16, __bf16, 2>), grid, dim3(512), 0, st, jobs, rows_per_wg, w, sw_rows, riders);
+    else hipLaunchKernelGGL((k_wgrad128<__bf16, __bf16, 1>), grid, dim3(256), 0, st, jobs, rows_per_wg, w, sw_rows, riders);
   } else if (g_bf16) {
-    if (two) hipLaunchKernelGGL((k_wgrad128<__bf16, float, 2>), grid, dim3(512), 0, st, jobs, rows_per_wg, riders);
-    else hipLaunchKernelGGL((k_wgrad128<__bf16, float, 1>), grid, dim3(256), 0, st, jobs, rows_per_wg, riders);
+    if (two) hipLaunchKernelGGL((k_wgrad128<__bf16, float, 2>), grid, dim3(512), 0, st, jobs, rows_per_wg, w, sw_rows, riders);
+    else hipLaunchKernelGGL((k_wgrad128<__bf16, float, 1>), grid, dim3(256), 0, st, jobs, rows_per_wg, w, sw_rows, riders);
   } else if (!a_bf16) {
-    if (two) hipLaunchKernelGGL((k_wgrad128<float, float, 2>), grid, dim3(512), 0, st, jobs, rows_per_wg, riders);
-    else hipLaunchKernelGGL((k_wgrad128<float, float, 1>), grid, dim3(256), 0, st, jobs, rows_per_wg, riders);
+    if (two) hipLaunchKernelGGL((k_wgrad128<float, float, 2>), grid, dim3(512), 0, st, jobs, rows_per_wg, w, sw_rows, riders);
+    else hipLaunchKernelGGL((k_wgrad128<float, float, 1>), grid, dim3(256), 0, st, jobs, rows_per_wg, w, sw_rows, riders);
   } else {
     set_error("wgrad128: fp32 G with bf16 A is not instantiated");
     return PCA_EUNSUPPORTED;
@@ -417,7 +450,7 @@ int wgrad128_launch(const WgradJobs& jobs_in, bool g_bf16, bool a_bf16, int rows
 }
 
 int wgrad128_launch_step(const WgradJobs& bf, int rpw_bf, const WgradJobs& f32, int rpw_f32,
-                         const SlabSumJobs& riders, hipStream_t st) {
+                         const SlabSumJobs& riders, hipStream_t st, const SmallWgradArgs* sw) {
   // (an empty bf16 list: it ran beside layer 1's few-queries backward, mab0_small_ride_launch)
   PCA_REQUIRE((bf.n == 0 || max_rows(bf) > 0) && f32.n > 0 && max_rows(f32) > 0,
               "wgrad128: the step launch takes lists with rows");
@@ -442,8 +475,10 @@ int wgrad128_launch_step(const WgradJobs& bf, int rpw_bf, const WgradJobs& f32, 
     }
   }
   PCA_TRY(rider_extent(rd, gx));
-  hipLaunchKernelGGL(k_wgrad128_step, dim3(gx, (unsigned)(bf.n + f32.n + rd.n)), dim3(512), 0, st,
-                     bf, rpw_bf, f32, rpw_f32, rd);
+  int sw_rows = 0;
+  PCA_TRY(small_rows(sw, gx, 2, &sw_rows));
+  hipLaunchKernelGGL(k_wgrad128_step, dim3(gx, (unsigned)(bf.n + f32.n + sw_rows + rd.n)), dim3(512), 0, st,
+                     bf, rpw_bf, f32, rpw_f32, sw != nullptr ? *sw : SmallWgradArgs{}, sw_rows, rd);
   return check_launch("k_wgrad128_step");
 }
 
