@@ -400,6 +400,62 @@ int pca_frame_points_ex_targets(const float* waves, const int64_t* wave_off, con
                                 int32_t* meta_out, float* samples_out, const int64_t* bg_labels,
                                 int64_t* labels2_out, float* weight_out, void* stream);
 
+#define PCA_POINT_MASK_MAX 4
+
+/* Random frequency bands and time stripes of points removed from every framed set.  A kind is on when its
+ * count and its largest width are both > 0; a kind that is off draws nothing. */
+typedef struct PcaPointMask {
+  int32_t n_freq;       /* bands per slot, 0 .. PCA_POINT_MASK_MAX */
+  int32_t freq_width;   /* a band is 0 .. freq_width bins wide; n_freq * freq_width < n_bins */
+  int32_t n_time;       /* stripes per slot, 0 .. PCA_POINT_MASK_MAX */
+  int32_t time_width;   /* a stripe is 0 .. time_width frames wide; n_time * time_width < Nt */
+  int32_t mode;         /* 0 drop: the masked points are absent; 1 floor: they carry a silent bin's value */
+} PcaPointMask;
+
+/* pca_frame_points_ex_targets that also removes random frequency bands and time stripes of points from
+ * every set, in the same launch: the augmentations before it change what a point's value is, this one
+ * which points the model sees.
+ * replaces: nothing (the reference trains on the full grid; SpecAugment overwrites the masked cells of a
+ *           spectrogram, a point set can leave them out).
+ * Every argument before `mask` is pca_frame_points_ex_targets', with the same checks.  Per batch slot,
+ * from the slot's stream (draws 0 - 7 are the ex launch's and do not move):
+ *   band k < n_freq    draw 8 + 2k: width w uniform over {0 .. freq_width};  draw 9 + 2k: start f0 uniform
+ *                      over {0 .. n_bins - w}; masks bins [f0, f0 + w) of all Nt frames of the slot
+ *   stripe k < n_time  draw 16 + 2k: width w uniform over {0 .. time_width}; draw 17 + 2k: start t0 uniform
+ *                      over {0 .. Nt - w}; masks frames [t0, t0 + w)
+ * an integer draw r reduced as ((r >> 32) * n) >> 32.  A point is masked when its bin lies in any band or
+ * its frame in any stripe (overlapping masks form their union); n_freq * freq_width < n_bins and
+ * n_time * time_width < Nt, so at least one bin and one frame always survive.
+ *   mode 0 (drop)   the kept points of slot b stand at the front of out[b] in their order p = j*n_bins + f:
+ *                   with kept_bins bins outside every band, the kept frame of rank r among the kept frames
+ *                   owns rows [r * kept_bins, (r + 1) * kept_bins).  lengths_out[b] (device int32[B],
+ *                   required when a kind is on) = kept_frames * kept_bins >= 1, and every row from there to
+ *                   N = Nt * n_bins is written as zeros, as pca_pack_points_3d_var pads: all of out is
+ *                   defined after the launch.  A bin's rank is f minus the masked bins below f, a closed form
+ *                   over at most four intervals: no scan, no atomics, no second launch, no dependence
+ *                   between the Nt workgroups of a slot - each writes n_bins rows, its kept points plus its
+ *                   share of the zero tail.
+ *   mode 1 (floor)  rows stay where they are; a masked point keeps its coordinates and its value becomes
+ *                   logf(1e-8f + 0), what a silent bin gets.  lengths_out must be NULL.
+ * In both modes a frame that a stripe masks is neither loaded nor transformed, and its [n_fft] block of
+ * samples_out (when given) is zeros.  The sample arithmetic, labels, soft targets and meta_out are
+ * untouched: with `mask` NULL or both kinds off the launch gives pca_frame_points_ex_targets' bits, and a
+ * given lengths_out receives N for every slot.  pca_frame_points_ex[_targets] are this call with `mask`
+ * NULL (one kernel).
+ * mask_meta_out (nullable) int32 [B, 16] = (f0, w) x 4 bands, then (t0, w) x 4 stripes, as drawn; unused
+ * entries 0.  Workgroup j == 0 of a slot writes lengths_out[b] and the mask meta next to the label.  The
+ * same arguments give the same bits.  PCA_EINVAL (message "frame_points_masked: ...") for a count outside
+ * [0, 4], a negative width, a kind that could mask every bin or frame, a mode other than 0 / 1, drop mode
+ * with a kind on and no lengths_out, floor mode with lengths_out. */
+int pca_frame_points_masked(const float* waves, const int64_t* wave_off, const int64_t* set_off,
+                            int n_clips, int64_t max_len, int64_t min_len, const int64_t* clip_labels,
+                            const int64_t* idx, int B, int n_fft, int hop, int n_bins, int Nt,
+                            const float* farr, const float* tarr, const PcaFrameAugEx* aug, float* out,
+                            int64_t* labels_out, int32_t* meta_out, float* samples_out,
+                            const int64_t* bg_labels, int64_t* labels2_out, float* weight_out,
+                            const PcaPointMask* mask, int32_t* lengths_out, int32_t* mask_meta_out,
+                            void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Fixed-input baselines (eval-mode forward; training stays stock PyTorch)    *
  * ------------------------------------------------------------------------- */

@@ -12,7 +12,12 @@
 // The set lookup and draws 0 - 2 restate k_frame_points' lines: that kernel stays as it is, its bits are
 // pinned against the spectrogram pipeline, and the tests here pin the two kernels against each other.
 // Also k_clip_rms: the per-clip RMS that scales the background.
+// Last, the launch decides which points a set keeps: random frequency bands and time stripes (draws 8 -
+// 23, point_mask.hpp) are left out of the rows (drop: the kept points compacted to the front, zeros behind
+// them, the count in lengths_out) or written at a silent bin's value (floor).  With the masks off the code
+// below takes the branches it always took.
 #include "pca_common.h"
+#include "point_mask.hpp"
 #include "resample_body.hpp"
 #include "select_keys.hpp"
 #include "stft_body.hpp"
@@ -51,10 +56,14 @@ struct FrameJobEx {
   int64_t* labels2_out;
   float* weight_out;
   double mix_prob, snr_lo_db, snr_hi_db;
+  // point masks: bands over the bins, stripes over the frames (a count of 0: that kind is off)
+  int n_freq, freq_width, n_time, time_width, mask_floor;
+  int32_t *lengths_out, *mask_meta_out;
 };
 
 // draw number k of a slot's stream, as k_frame_points: 0 time shift, 1 level, 2 window length; here also
-// 3 speed index, 4 mix decision, 5 background clip, 6 its start, 7 the SNR
+// 3 speed index, 4 mix decision, 5 background clip, 6 its start, 7 the SNR, 8 - 15 the frequency bands,
+// 16 - 23 the time stripes (point_mask.hpp)
 __device__ __forceinline__ uint64_t frame_draw(uint64_t stream, int k) {
   return mix64(stream + (uint64_t)k * 0xd1342543de82ef95ull);
 }
@@ -128,6 +137,20 @@ __global__ __launch_bounds__(256) void k_frame_points_ex(const FrameJobEx a) {
     }
   }
 
+  // which points the slot keeps: one set of bands for all Nt frames, one set of stripes
+  const bool masked = a.n_freq > 0 || a.n_time > 0;
+  MaskAxis mf, mt;
+  int kept_bins = a.n_bins, kept_frames = a.Nt;
+  bool frame_off = false;
+  if (masked) {
+    const auto draw_k = [stream](int k) { return frame_draw(stream, k); };
+    mask_draw(mf, draw_k, 8, a.n_freq, a.freq_width, a.n_bins);
+    mask_draw(mt, draw_k, 16, a.n_time, a.time_width, a.Nt);
+    kept_bins -= mask_below(mf, a.n_bins);
+    kept_frames -= mask_below(mt, a.Nt);
+    frame_off = mask_covers(mt, j);
+  }
+
   // centres in the timeline of the (resampled) clip y of Ly samples
   const int64_t nominal = s * a.Nt * a.hop + delta;
   const int64_t Ly = resampled ? (int64_t)((double)L * ratio) : L;
@@ -151,6 +174,39 @@ __global__ __launch_bounds__(256) void k_frame_points_ex(const FrameJobEx a) {
       m[6] = (int32_t)p;
       m[7] = (int32_t)__float_as_uint(alpha);
     }
+    if (a.lengths_out != nullptr) a.lengths_out[b] = kept_frames * kept_bins;
+    if (a.mask_meta_out != nullptr) {
+      int32_t* m = a.mask_meta_out + (int64_t)b * (4 * PCA_POINT_MASK_MAX);
+      for (int k = 0; k < PCA_POINT_MASK_MAX; ++k) {
+        m[2 * k] = masked ? mf.start[k] : 0;
+        m[2 * k + 1] = masked ? mf.width[k] : 0;
+        m[2 * PCA_POINT_MASK_MAX + 2 * k] = masked ? mt.start[k] : 0;
+        m[2 * PCA_POINT_MASK_MAX + 2 * k + 1] = masked ? mt.width[k] : 0;
+      }
+    }
+  }
+
+  const int din = a.tarr == nullptr ? 2 : 3;
+  if (frame_off) {                      // (uniform) a frame a stripe masks: no load, no transform
+    if (a.samples_out != nullptr) {
+      float* so = a.samples_out + ((int64_t)b * a.Nt + j) * a.n_fft;
+      for (int n = tid; n < a.n_fft; n += 256) so[n] = 0.f;
+    }
+    if (a.mask_floor) {                 // its rows in place, at a silent bin's value
+      const float quiet = stft_logmag_bin(make_double2(0.0, 0.0), 1.0);
+      float* o = a.out + ((int64_t)b * a.Nt + j) * a.n_bins * din;
+      for (int f = tid; f < a.n_bins; f += 256) {
+        o[f * din] = a.farr[f];
+        if (din == 3) o[f * 3 + 1] = a.tarr[j];
+        o[f * din + din - 1] = quiet;
+      }
+    } else {                            // its n_bins rows of the zero tail, behind the kept frames' shares
+      const int64_t row0 = (int64_t)b * a.Nt * a.n_bins + (int64_t)kept_frames * a.n_bins +
+                           (int64_t)mask_below(mt, j) * a.n_bins;
+      float* o = a.out + row0 * din;
+      for (int q = tid; q < a.n_bins * din; q += 256) o[q] = 0.f;
+    }
+    return;
   }
 
   const float* wave = a.waves + w0;
@@ -178,7 +234,34 @@ __global__ __launch_bounds__(256) void k_frame_points_ex(const FrameJobEx a) {
 
   const double inv = 1.0 / (double)(a.norm_mode == 0 ? a.n_fft : win);
   const int64_t p0 = ((int64_t)b * a.Nt + j) * a.n_bins;            // point p = j*n_bins + f
-  if (a.tarr == nullptr) {
+  if (masked) {
+    const float t = din == 3 ? a.tarr[j] : 0.f;
+    if (a.mask_floor) {
+      const float quiet = stft_logmag_bin(make_double2(0.0, 0.0), inv);
+      float* o = a.out + p0 * din;
+      for (int f = tid; f < a.n_bins; f += 256) {
+        o[f * din] = a.farr[f];
+        if (din == 3) o[f * 3 + 1] = t;
+        o[f * din + din - 1] = mask_covers(mf, f) ? quiet : stft_logmag_bin(x[f], inv);
+      }
+    } else {
+      // kept frame of rank r: rows [r * kept_bins, (r + 1) * kept_bins) of the slot, bin f at its rank
+      // among the kept bins; then the n_bins - kept_bins rows of the zero tail that are this frame's share
+      const int r = j - mask_below(mt, j);
+      const int64_t slot = (int64_t)b * a.Nt * a.n_bins;
+      float* o = a.out + (slot + (int64_t)r * kept_bins) * din;
+      for (int f = tid; f < a.n_bins; f += 256) {
+        if (mask_covers(mf, f)) continue;
+        const int q = f - mask_below(mf, f);
+        o[q * din] = a.farr[f];
+        if (din == 3) o[q * 3 + 1] = t;
+        o[q * din + din - 1] = stft_logmag_bin(x[f], inv);
+      }
+      const int spare = a.n_bins - kept_bins;
+      float* z = a.out + (slot + (int64_t)kept_frames * kept_bins + (int64_t)r * spare) * din;
+      for (int q = tid; q < spare * din; q += 256) z[q] = 0.f;
+    }
+  } else if (a.tarr == nullptr) {
     float2* o = reinterpret_cast<float2*>(a.out) + p0;
     for (int f = tid; f < a.n_bins; f += 256) o[f] = make_float2(a.farr[f], stft_logmag_bin(x[f], inv));
   } else {
@@ -230,13 +313,14 @@ int pca_clip_rms(const float* waves, const int64_t* wave_off, int n_clips, int64
   return pca::check_launch("k_clip_rms");
 }
 
-int pca_frame_points_ex_targets(const float* waves, const int64_t* wave_off, const int64_t* set_off,
-                                int n_clips, int64_t max_len, int64_t min_len,
-                                const int64_t* clip_labels, const int64_t* idx, int B, int n_fft,
-                                int hop, int n_bins, int Nt, const float* farr, const float* tarr,
-                                const PcaFrameAugEx* aug, float* out, int64_t* labels_out,
-                                int32_t* meta_out, float* samples_out, const int64_t* bg_labels,
-                                int64_t* labels2_out, float* weight_out, void* stream) {
+int pca_frame_points_masked(const float* waves, const int64_t* wave_off, const int64_t* set_off,
+                            int n_clips, int64_t max_len, int64_t min_len, const int64_t* clip_labels,
+                            const int64_t* idx, int B, int n_fft, int hop, int n_bins, int Nt,
+                            const float* farr, const float* tarr, const PcaFrameAugEx* aug, float* out,
+                            int64_t* labels_out, int32_t* meta_out, float* samples_out,
+                            const int64_t* bg_labels, int64_t* labels2_out, float* weight_out,
+                            const PcaPointMask* mask, int32_t* lengths_out, int32_t* mask_meta_out,
+                            void* stream) {
   // everything pca_frame_points refuses
   PCA_REQUIRE(waves && wave_off && set_off && idx && farr && aug && out,
               "frame_points_ex: null pointer");
@@ -310,7 +394,35 @@ int pca_frame_points_ex_targets(const float* waves, const int64_t* wave_off, con
                 "frame_points_ex: bg_max_len=%lld (meta holds int32 starts)",
                 (long long)aug->bg_max_len);
   }
+  // point masks
+  bool freq_on = false, time_on = false;
+  if (mask != nullptr) {
+    PCA_REQUIRE(mask->n_freq >= 0 && mask->n_freq <= PCA_POINT_MASK_MAX,
+                "frame_points_masked: n_freq=%d must be in [0, %d]", mask->n_freq, PCA_POINT_MASK_MAX);
+    PCA_REQUIRE(mask->n_time >= 0 && mask->n_time <= PCA_POINT_MASK_MAX,
+                "frame_points_masked: n_time=%d must be in [0, %d]", mask->n_time, PCA_POINT_MASK_MAX);
+    PCA_REQUIRE(mask->freq_width >= 0, "frame_points_masked: freq_width=%d", mask->freq_width);
+    PCA_REQUIRE(mask->time_width >= 0, "frame_points_masked: time_width=%d", mask->time_width);
+    freq_on = mask->n_freq > 0 && mask->freq_width > 0;
+    time_on = mask->n_time > 0 && mask->time_width > 0;
+    PCA_REQUIRE(!freq_on || (int64_t)mask->n_freq * mask->freq_width < n_bins,
+                "frame_points_masked: n_freq=%d bands of up to freq_width=%d bins could mask all "
+                "n_bins=%d (one bin must survive)", mask->n_freq, mask->freq_width, n_bins);
+    PCA_REQUIRE(!time_on || (int64_t)mask->n_time * mask->time_width < Nt,
+                "frame_points_masked: n_time=%d stripes of up to time_width=%d frames could mask all "
+                "Nt=%d (one frame must survive)", mask->n_time, mask->time_width, Nt);
+    PCA_REQUIRE(mask->mode == 0 || mask->mode == 1, "frame_points_masked: mode=%d (0 drop, 1 floor)",
+                mask->mode);
+    PCA_REQUIRE(mask->mode != 0 || !(freq_on || time_on) || lengths_out != nullptr,
+                "frame_points_masked: drop mode needs lengths_out");
+    PCA_REQUIRE(mask->mode != 1 || lengths_out == nullptr,
+                "frame_points_masked: floor mode keeps every row, lengths_out must be NULL");
+  }
   pca::FrameJobEx j{};
+  if (freq_on) { j.n_freq = mask->n_freq; j.freq_width = mask->freq_width; }
+  if (time_on) { j.n_time = mask->n_time; j.time_width = mask->time_width; }
+  j.mask_floor = mask != nullptr && mask->mode == 1;
+  j.lengths_out = lengths_out; j.mask_meta_out = mask_meta_out;
   j.waves = waves; j.wave_off = wave_off; j.set_off = set_off; j.clip_labels = clip_labels;
   j.idx = idx; j.farr = farr; j.tarr = tarr; j.win_lengths = aug->win_lengths;
   j.draw_dev = aug->draw_dev; j.out = out; j.labels_out = labels_out; j.meta_out = meta_out;
@@ -337,6 +449,19 @@ int pca_frame_points_ex_targets(const float* waves, const int64_t* wave_off, con
   hipLaunchKernelGGL(pca::k_frame_points_ex, dim3((unsigned)Nt, (unsigned)B), dim3(256),
                      pca::stft_lds_bytes(n_fft), pca::as_stream(stream), j);
   return pca::check_launch("k_frame_points_ex");
+}
+
+int pca_frame_points_ex_targets(const float* waves, const int64_t* wave_off, const int64_t* set_off,
+                                int n_clips, int64_t max_len, int64_t min_len,
+                                const int64_t* clip_labels, const int64_t* idx, int B, int n_fft,
+                                int hop, int n_bins, int Nt, const float* farr, const float* tarr,
+                                const PcaFrameAugEx* aug, float* out, int64_t* labels_out,
+                                int32_t* meta_out, float* samples_out, const int64_t* bg_labels,
+                                int64_t* labels2_out, float* weight_out, void* stream) {
+  return pca_frame_points_masked(waves, wave_off, set_off, n_clips, max_len, min_len, clip_labels, idx, B,
+                                 n_fft, hop, n_bins, Nt, farr, tarr, aug, out, labels_out, meta_out,
+                                 samples_out, bg_labels, labels2_out, weight_out, nullptr, nullptr,
+                                 nullptr, stream);
 }
 
 int pca_frame_points_ex(const float* waves, const int64_t* wave_off, const int64_t* set_off,

@@ -417,11 +417,23 @@ class ESC_wave_pc(Dataset):
                  mix carries its own label twice at weight 1), for ``pca_hip.cross_entropy`` /
                  ``STEngine.fwd_bwd`` / the ``Trainer``.  Needs ``mix_clips``, and with a list of clips
                  ``mix_labels``, one class per background clip ("self": the clip labels)
+    freq_masks / freq_mask_width   SpecAugment's frequency masking on the point set: ``freq_masks`` (0 .. 4)
+                 bands per set, each 0 .. ``freq_mask_width`` bins wide at a uniform position, are removed;
+                 ``freq_masks * freq_mask_width < F``
+    time_masks / time_mask_width   likewise stripes of whole frames of a chunk (``ESC_wave_pc_temp``;
+                 ``time_masks * time_mask_width < Ntemp``)
+    mask_mode    "drop": the masked points are absent - ``batch`` compacts the kept points to the front of
+                 every set, zero-fills behind them and appends ``lengths`` (int32 [B], the point counts) to
+                 what it returns; the dataset is then ``variable_length`` and the ``Trainer`` hands the
+                 counts to the step.  "floor": the sets stay dense, a masked point keeps its coordinates
+                 and carries a silent bin's value log(1e-8) - for runs that want the dense step (at d = 128
+                 the set-resident forward takes no ``lengths``).  ``plain()`` switches the masks off
 
     drawn from the counter-based device stream (seed, draw number, batch slot, set), as
     ``ESC_pc_temp_randKSS`` draws its points.  With all three off the batches are bit for bit those of
     ``ESC_pc`` over ``pca_hip.stft_logmag_batch`` of the same clips.  With speeds and mix off a batch is
-    one pca_frame_points launch; with either on, one pca_frame_points_ex launch.
+    one pca_frame_points launch; with either on, one pca_frame_points_ex launch; with a mask on, one
+    pca_frame_points_masked launch (the same kernel).
 
     clips  list of 1-D float32 waveforms (numpy or torch, host or device), each longer than n_fft / 2
     y      one label per clip
@@ -431,10 +443,12 @@ class ESC_wave_pc(Dataset):
 
     def __init__(self, clips, y, fs, n_fft, hop=None, drop_nyquist=False, jitter=0, gain_db=0.0,
                  win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
-                 mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None):
+                 mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None,
+                 freq_masks=0, freq_mask_width=0, time_masks=0, time_mask_width=0, mask_mode="drop"):
         self._setup(clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                     device)
         self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db, mix_targets, mix_labels)
+        self._setup_mask(freq_masks, freq_mask_width, time_masks, time_mask_width, mask_mode)
 
     def _setup(self, clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                device):
@@ -501,6 +515,25 @@ class ESC_wave_pc(Dataset):
             raise ValueError(f"speeds {self.speeds}: the shortest clip ({self._min_len} samples) at speed "
                              f"{max(self.speeds)} is no longer than n_fft / 2 = {self.n_fft // 2}")
 
+    def _setup_mask(self, freq_masks, freq_mask_width, time_masks, time_mask_width, mask_mode):
+        """Frequency bands and time stripes of points to remove: checked here, on the host, by the rules
+        of pca_frame_points_masked."""
+        pca_hip.ops.point_mask(self.F, self._ntemp, freq_masks, freq_mask_width, time_masks,
+                               time_mask_width, mask_mode)
+        self.freq_masks, self.freq_mask_width = int(freq_masks), int(freq_mask_width)
+        self.time_masks, self.time_mask_width = int(time_masks), int(time_mask_width)
+        self.mask_mode = mask_mode
+
+    @property
+    def _mask_on(self) -> bool:
+        return (self.freq_masks > 0 and self.freq_mask_width > 0) or \
+               (self.time_masks > 0 and self.time_mask_width > 0)
+
+    @property
+    def variable_length(self) -> bool:
+        """True when ``batch`` returns padded sets and their point counts (a mask on in drop mode)."""
+        return self._mask_on and self.mask_mode == "drop"
+
     @property
     def _speed_on(self) -> bool:
         return self.speeds != (1.0,)
@@ -529,7 +562,7 @@ class ESC_wave_pc(Dataset):
         """True when any augmentation is on: every call must then draw anew, so a caller that
         captures ``batch`` into a hipGraph passes ``draw_dev`` (see ``_TempSS.stochastic``)."""
         return (self.jitter > 0 or self.gain_db > 0.0 or len(self.win_lengths) > 1
-                or self._speed_on or self._mix_on)
+                or self._speed_on or self._mix_on or self._mask_on)
 
     def plain(self, win_length=None):
         """A view on the same resident waveforms with every augmentation off: deterministic, the
@@ -538,6 +571,7 @@ class ESC_wave_pc(Dataset):
         v = copy.copy(self)
         v.jitter, v.gain_db = 0, 0.0
         v.speeds, v.ratios, v.mix_prob, v.mix_targets = (1.0,), (1.0,), 0.0, False
+        v.freq_masks = v.time_masks = 0
         v.win_lengths = (self.win_lengths[0] if win_length is None else int(win_length),)
         if not 1 <= v.win_lengths[0] <= self.n_fft:
             raise ValueError(f"win_length {v.win_lengths[0]} outside [1, n_fft = {self.n_fft}]")
@@ -591,17 +625,24 @@ class ESC_wave_pc(Dataset):
         return self._store["mix_labels"]
 
     def batch(self, idx: torch.Tensor, out=None, labels_out=None, draw_dev=None,
-              want_meta: bool = False, want_samples: bool = False, labels2_out=None, weight_out=None):
+              want_meta: bool = False, want_samples: bool = False, labels2_out=None, weight_out=None,
+              lengths_out=None):
         """idx int64[B] on the device -> (points [B, num_points, 2 or 3] float32, labels int64[B]
         [, meta int32 [B, 4] = (clip, centre sample of frame 0, window length, bits of the gain)]).
         With ``speeds`` or the mix on, meta is int32 [B, 8] (pca_hip.frame_points_ex: + speed index,
         background clip or -1, its start, bits of its scale) and ``want_samples`` adds the float32
         [B, Ntemp, n_fft] samples of every frame before window and gain.  With ``soft_targets`` the
         return ends with (labels2 int64[B], weight float32[B]), written into ``labels2_out`` /
-        ``weight_out`` when given, by the same launch."""
+        ``weight_out`` when given, by the same launch.  With a mask on (pca_hip.frame_points_masked) meta
+        is int32 [B, 24] - those 8 columns, then (start, width) of the 4 bands and the 4 stripes - and in
+        drop mode the return ends with lengths int32 [B], written into ``lengths_out`` when given."""
         waves, woff, soff, f32, t32, lab = self._resident()
         self._draw += 1
-        if self._speed_on or self._mix_on or self.mix_targets:
+        if self._mask_on:
+            mask = dict(freq_masks=self.freq_masks, freq_mask_width=self.freq_mask_width,
+                        time_masks=self.time_masks, time_mask_width=self.time_mask_width,
+                        mask_mode=self.mask_mode, lengths_out=lengths_out)
+        if self._speed_on or self._mix_on or self.mix_targets or self._mask_on:
             mix = {}
             if self._mix_on or self.mix_targets:
                 rms, bg, boff, brms, bmax = self._mix_resident()
@@ -610,13 +651,15 @@ class ESC_wave_pc(Dataset):
             if self.mix_targets:
                 mix.update(bg_labels=self._mix_labels_dev(), labels2_out=labels2_out,
                            weight_out=weight_out)
-            return pca_hip.frame_points_ex(
+            launch, mask = (pca_hip.frame_points_masked, mask) if self._mask_on \
+                else (pca_hip.frame_points_ex, {})
+            return launch(
                 waves, woff, soff, idx, self.n_fft, self.hop, self.F, f32, t32, self._ntemp,
                 max_len=self._max_len, min_len=self._min_len, clip_labels=lab,
                 jitter=self.jitter, gain_db=self.gain_db, win_lengths=self._win_dev(waves.device),
                 norm_mode=pca_hip.NORM_WIN if self.norm == "win" else pca_hip.NORM_NFFT,
                 seed=self.seed, draw=self._draw, ratios=self.ratios, out=out, labels_out=labels_out,
-                draw_dev=draw_dev, want_meta=want_meta, want_samples=want_samples, **mix)
+                draw_dev=draw_dev, want_meta=want_meta, want_samples=want_samples, **mix, **mask)
         if want_samples:
             raise ValueError("want_samples needs speeds or the mix on (pca_hip.frame_points_ex)")
         return pca_hip.frame_points(
@@ -630,7 +673,10 @@ class ESC_wave_pc(Dataset):
     def __getitem__(self, idx):
         waves = self._resident()[0]
         i = torch.tensor([int(idx)], dtype=torch.int64, device=waves.device)
-        pts, lbl = self.batch(i)
+        res = self.batch(i)
+        pts, lbl = res[0], res[1]
+        if self.variable_length:                 # the un-padded set
+            return pts[0, :int(res[-1][0])].cpu(), lbl[0].cpu()
         return pts[0].cpu(), lbl[0].cpu()
 
 
@@ -645,11 +691,13 @@ class ESC_wave_pc_temp(ESC_wave_pc):
 
     def __init__(self, clips, y, fs, n_fft, Ntemp, hop=None, jitter=0, gain_db=0.0,
                  win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
-                 mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None):
+                 mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None,
+                 freq_masks=0, freq_mask_width=0, time_masks=0, time_mask_width=0, mask_mode="drop"):
         self._ntemp = int(Ntemp)
         assert self._ntemp >= 1
         self._setup(clips, y, fs, n_fft, hop, True, jitter, gain_db, win_lengths, norm, seed, device)
         self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db, mix_targets, mix_labels)
+        self._setup_mask(freq_masks, freq_mask_width, time_masks, time_mask_width, mask_mode)
         self.tarr = np.linspace(0, (self.hop / fs) * self._ntemp, self._ntemp)
 
 

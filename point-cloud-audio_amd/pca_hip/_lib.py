@@ -71,6 +71,14 @@ class PcaFrameAugEx(C.Structure):
         ("snr_lo_db", C.c_double), ("snr_hi_db", C.c_double)]
 
 
+POINT_MASK_MAX = 4
+MASK_DROP, MASK_FLOOR = 0, 1
+
+
+class PcaPointMask(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_freq", "freq_width", "n_time", "time_width", "mode")]
+
+
 class PcaSoftTargets(C.Structure):
     _fields_ = [("labels2", C.c_void_p), ("weight", C.c_void_p), ("smoothing", C.c_float)]
 
@@ -165,6 +173,11 @@ SIGNATURES = {
                                               c_i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp,
                                               c_fp, C.POINTER(PcaFrameAugEx), c_fp, c_i64p, c_vp, c_fp,
                                               c_i64p, c_i64p, c_fp, c_vp]),
+    "pca_frame_points_masked": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p,
+                                          c_i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp,
+                                          c_fp, C.POINTER(PcaFrameAugEx), c_fp, c_i64p, c_vp, c_fp,
+                                          c_i64p, c_i64p, c_fp, C.POINTER(PcaPointMask), c_vp, c_vp,
+                                          c_vp]),
     "pca_baseline_param_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, c_vp, C.c_int, C.c_int]),
     "pca_fb_forward": (C.c_int, [c_fp, C.c_int64, C.c_int64, c_i64p, C.c_int, C.c_int, c_vp,
                                  C.c_int, C.c_int, c_fp, C.c_int64, C.c_int, C.c_int, C.c_uint64,

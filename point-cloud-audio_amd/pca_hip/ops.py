@@ -864,7 +864,7 @@ def frame_points_ex(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.
                     draw_dev: Optional[torch.Tensor] = None, want_meta: bool = False,
                     want_samples: bool = False, bg_labels: Optional[torch.Tensor] = None,
                     labels2_out: Optional[torch.Tensor] = None,
-                    weight_out: Optional[torch.Tensor] = None):
+                    weight_out: Optional[torch.Tensor] = None, _mask=None):
     """``frame_points`` with a speed change and a background mix applied while the frame is loaded
     (pca_frame_points_ex); the arguments they share mean the same, and with ``ratios == (1.0,)`` and
     ``mix_prob == 0`` (or no ``bg_waves``) the points, labels and meta[:, :4] are ``frame_points``' bits.
@@ -888,7 +888,8 @@ def frame_points_ex(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.
                 RMS matching (between-class learning's rule with the RMS for its A-weighted level;
                 ``mix_snr_db=(-20, 20)`` spans weights of about 0.09 .. 0.91), in a slot that mixes;
                 ``labels2`` = the slot's own label and ``weight`` = 1 in every other slot.  Everything
-                else is bit for bit what the call without ``bg_labels`` returns."""
+                else is bit for bit what the call without ``bg_labels`` returns.
+    (``_mask``: ``frame_points_masked``'s way in - its checked options and ``lengths_out``.)"""
     _need_cuda(waves, wave_off, set_off, idx, farr, clip_rms, bg_waves, bg_off, bg_rms, bg_labels)
     assert waves.dtype == torch.float32 and waves.is_contiguous() and farr.dtype == torch.float32
     assert wave_off.dtype == set_off.dtype == idx.dtype == torch.int64
@@ -932,6 +933,18 @@ def frame_points_ex(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.
         args = (_ptr(waves), _ptr(wave_off), _ptr(set_off), n_clips, int(max_len), int(min_len),
                 _ptr(clip_labels), _ptr(idx), B, int(n_fft), int(hop), int(n_bins), int(Nt), _ptr(farr),
                 _ptr(tarr), C.byref(aug), _ptr(out), _ptr(labels_out), _ptr(meta), _ptr(samples))
+        lengths_out = mask_meta = None
+        if _mask is not None:
+            mask, lengths_out = _mask
+            if mask.mode == _lib.MASK_DROP and lengths_out is None:
+                lengths_out = torch.empty(B, dtype=torch.int32, device=waves.device)
+            if lengths_out is not None:
+                _need_cuda(lengths_out)
+                assert lengths_out.dtype == torch.int32 and lengths_out.is_contiguous()
+                assert lengths_out.numel() == B
+            if want_meta:
+                mask_meta = torch.empty((B, 4 * _lib.POINT_MASK_MAX), dtype=torch.int32,
+                                        device=waves.device)
         if bg_labels is not None:
             assert bg_labels.dtype == torch.int64 and bg_labels.is_contiguous()
             assert bg_labels.numel() == n_bg, "one background label per background clip"
@@ -941,6 +954,12 @@ def frame_points_ex(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.
                 weight_out = torch.empty(B, dtype=torch.float32, device=waves.device)
             assert labels2_out.dtype == torch.int64 and labels2_out.numel() == B
             assert weight_out.dtype == torch.float32 and weight_out.numel() == B
+        if _mask is not None:
+            check(lib().pca_frame_points_masked(*args, _ptr(bg_labels), _ptr(labels2_out),
+                                                _ptr(weight_out), C.byref(mask), _ptr(lengths_out),
+                                                _ptr(mask_meta), _stream(waves)),
+                  "pca_frame_points_masked")
+        elif bg_labels is not None:
             check(lib().pca_frame_points_ex_targets(*args, _ptr(bg_labels), _ptr(labels2_out),
                                                     _ptr(weight_out), _stream(waves)),
                   "pca_frame_points_ex_targets")
@@ -948,12 +967,65 @@ def frame_points_ex(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.
             check(lib().pca_frame_points_ex(*args, _stream(waves)), "pca_frame_points_ex")
     ret = (out, labels_out)
     if want_meta:
-        ret += (meta,)
+        ret += (meta if mask_meta is None else torch.cat([meta, mask_meta], dim=1),)
     if want_samples:
         ret += (samples,)
     if bg_labels is not None:
         ret += (labels2_out, weight_out)
+    if _mask is not None and mask.mode == _lib.MASK_DROP:
+        ret += (lengths_out,)
     return ret
+
+
+MASK_MODES = {"drop": _lib.MASK_DROP, "floor": _lib.MASK_FLOOR}
+
+
+def point_mask(n_bins: int, Nt: int, freq_masks: int = 0, freq_mask_width: int = 0, time_masks: int = 0,
+               time_mask_width: int = 0, mask_mode="drop") -> "_lib.PcaPointMask":
+    """The checked mask options of ``frame_points_masked`` as the C struct; ``ValueError`` for what
+    pca_frame_points_masked would refuse (the same rules, on the host)."""
+    nf, wf, nt, wt = int(freq_masks), int(freq_mask_width), int(time_masks), int(time_mask_width)
+    if mask_mode not in MASK_MODES:
+        raise ValueError(f"mask_mode is 'drop' or 'floor', got {mask_mode!r}")
+    for name, n in (("freq_masks", nf), ("time_masks", nt)):
+        if not 0 <= n <= _lib.POINT_MASK_MAX:
+            raise ValueError(f"{name} {n} outside [0, {_lib.POINT_MASK_MAX}]")
+    if wf < 0 or wt < 0:
+        raise ValueError(f"mask widths must be >= 0, got freq_mask_width {wf}, time_mask_width {wt}")
+    if nf > 0 and wf > 0 and nf * wf >= n_bins:
+        raise ValueError(f"{nf} bands of up to {wf} bins could mask all {n_bins} bins: one must survive")
+    if nt > 0 and wt > 0 and nt * wt >= Nt:
+        raise ValueError(f"{nt} stripes of up to {wt} frames could mask all {Nt} frames: one must survive")
+    return _lib.PcaPointMask(nf, wf, nt, wt, MASK_MODES[mask_mode])
+
+
+def frame_points_masked(*args, freq_masks: int = 0, freq_mask_width: int = 0, time_masks: int = 0,
+                        time_mask_width: int = 0, mask_mode="drop",
+                        lengths_out: Optional[torch.Tensor] = None, **kw):
+    """``frame_points_ex`` (every argument of it, with the same meaning) that also removes random
+    frequency bands and time stripes of points from every set, in the same launch
+    (pca_frame_points_masked): SpecAugment for point sets - a masked point is absent, not overwritten.
+
+    freq_masks / freq_mask_width   per batch slot ``freq_masks`` (0 .. 4) bands, each 0 .. ``freq_mask_width``
+                bins wide at a uniform position, removed from all Nt frames of the slot
+    time_masks / time_mask_width   likewise stripes of whole frames (needs Nt > 1)
+    mask_mode   "drop": the kept points of every set are compacted to its front in their order, the rows
+                behind them are zeros, and the call returns, after everything else, ``lengths`` int32 [B]
+                (``lengths_out`` when given): the point count of every set, for ``STEngine.fwd_bwd`` /
+                ``ST.forward``.  "floor": rows stay in place, a masked point keeps its coordinates and
+                carries the value of a silent bin, log(1e-8); no ``lengths``.
+    A kind whose count or width is 0 is off and draws nothing; overlapping masks form their union;
+    ``freq_masks * freq_mask_width < n_bins`` and ``time_masks * time_mask_width < Nt`` (``ValueError``),
+    so a set never becomes empty.  The masks use draws of their own: everything else the call returns is
+    bit for bit ``frame_points_ex``'s.  ``want_meta``: meta is int32 [B, 24], ``frame_points_ex``'s 8 columns,
+    then (start, width) of the 4 bands and of the 4 stripes as drawn (unused ones 0)."""
+    n_bins = kw["n_bins"] if "n_bins" in kw else args[6]
+    Nt = kw["Nt"] if "Nt" in kw else (args[9] if len(args) > 9 else 1)
+    mask = point_mask(int(n_bins), int(Nt), freq_masks, freq_mask_width, time_masks, time_mask_width,
+                      mask_mode)
+    if mask.mode == _lib.MASK_FLOOR and lengths_out is not None:
+        raise ValueError("mask_mode 'floor' keeps every row: no lengths_out")
+    return frame_points_ex(*args, _mask=(mask, lengths_out), **kw)
 
 
 def select_points(X: torch.Tensor, key: torch.Tensor, K: int,

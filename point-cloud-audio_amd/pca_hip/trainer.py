@@ -531,6 +531,11 @@ class Trainer:
             if defer:
                 check(lib().pca_pack_defer(0), "pca_pack_defer")
             return
+        elif self.lengths is not None and getattr(self.ds, "stochastic", False):
+            # sets that lose random points (the waveform datasets' masks in drop mode): the point counts
+            # and the fresh draw per replay both come from the one frame launch
+            self.ds.batch(self.idx, out=self.X, labels_out=self.labels, lengths_out=self.lengths,
+                          draw_dev=self.step_count, **tk)
         elif self.lengths is not None:
             self.ds.batch(self.idx, out=self.X, labels_out=self.labels,
                           lengths_out=self.lengths)
