@@ -1,6 +1,6 @@
-// The end of a backward pass: bwd_defer_flush runs everything the blocks of a step queued in their BwdDefer
-// (bwd_defer.hpp) - the weight-gradient launch (wgrad128.hip: both d = 128 lists in one; wgrad256.hip) with
-// the due slab sums as riders, then the post stages:
+// The end of a backward pass: bwd_defer_flush runs the plan (plan_tail, tail_plan.hip) of everything the blocks
+// of a step queued in their BwdDefer (bwd_defer.hpp) - the weight-gradient launch (wgrad128.hip: both d = 128
+// lists in one; wgrad256.hip) with the due slab sums as riders, then the post stages:
 //
 //   k_mab0_post1 / k_terminal1   dWk and dQp of the shared queries (k_terminal1: the same plus the classifier's
 //                                weight gradient, the layer-1 fc_v gradient and late slab sums as extra rows;
@@ -10,8 +10,6 @@
 #include "bwd_defer.hpp"
 #include "terminal_bodies.hpp"
 #include "slab_sum_body.hpp"
-
-#include <stdlib.h>
 
 namespace pca {
 
@@ -110,8 +108,7 @@ __device__ __forceinline__ void post1_body(const Mab0PostJob& a, int blk, bool w
 //   row workgroups [d / POST_FC, + m) (dI != null): phase 1 recomputes row q of dQp (the same bits), phase 2
 //     is dI[q][c] += <dQp row, Wq column> (fmaf over f from 0, 64 loads in flight as dot_strided).
 // I and the old dWq / dbq / dI do not depend on dQp: they are requested before phase 1.  Every thread of a
-// live workgroup reaches the barrier.  Shapes: post_fused_ok.
-constexpr int POST_FC = 4, POST_MAXM = 16;
+// live workgroup reaches the barrier.  Shapes: post_fused_ok (tail_plan.hip; POST_FC, POST_MAXM: bwd_defer.hpp).
 __device__ __forceinline__ void post_fused_body(const Mab0PostJob& a, int x) {
   const int m = a.m, d = a.d, dq = a.dq;
   const int ncol = d / POST_FC, nrow = a.dI != nullptr ? m : 0;
@@ -238,276 +235,71 @@ __global__ __launch_bounds__(256) void k_mab0_post2(const Mab0PostJobs jobs, con
 
 }  // namespace
 
-// threads the widest job needs in each post stage (one output element per thread; grid.x = cdiv(., 256))
-struct PostExtents { int n1, n2; };
-static PostExtents post_extents(const Mab0PostJobs& J) {
-  PostExtents x{0, 0};
-  for (int i = 0; i < J.n; ++i) {
-    const Mab0PostJob& a = J.j[i];
-    const int e1 = a.d * a.dk + a.m * a.d, e2 = a.d * a.dq + a.d + (a.dI ? a.m * a.dq : 0);
-    x.n1 = e1 > x.n1 ? e1 : x.n1;
-    x.n2 = e2 > x.n2 ? e2 : x.n2;
-  }
-  return x;
+int mab0_post_launch(const Mab0PostJobs& J, hipStream_t st) {     // (nothing rides: k_mab0_post1, k_mab0_post2)
+  BwdDefer D{};
+  D.posts = J;
+  return bwd_defer_flush(D, st);
 }
-
-// shapes the fused post rows cover (post_fused_body: d = 128 as m x POST_FC and d threads of 256, a thread's
-// dWq outputs in one column of I, at most POST_MAXM queries held in registers)
-static bool post_fused_ok(const Mab0PostJob& a) {
-  return a.d == 128 && a.h > 0 && a.m >= 1 && a.m <= POST_MAXM && a.dq >= 1 && a.dq <= 256 && 256 % a.dq == 0;
-}
-static bool ranges_meet(const float* p, int64_t n, const float* q, int64_t k) {
-  return p != nullptr && q != nullptr && p < q + k && q < p + n;
-}
-// whether a rider of the same launch writes where the job's second stage accumulates
-static bool post_outputs_overlap(const Mab0PostJob& a, const SlabSumJobs& riders) {
-  for (int i = 0; i < riders.n; ++i) {
-    const SlabSumJob& r = riders.j[i];
-    if (ranges_meet(r.out, r.n, a.dWq, (int64_t)a.d * a.dq) || ranges_meet(r.out, r.n, a.dbq, a.d) ||
-        ranges_meet(r.out, r.n, a.dI, (int64_t)a.m * a.dq))
-      return true;
-  }
-  return false;
-}
-bool post_fuse_on() {            // (read per call, like the switches below)
-  return env_not_zero("PCA_POST_FUSE");
-}
-
-int terminal_launch(const BwdDefer& D, hipStream_t st, const SlabSumJobs* late_in) {
-  SlabSumJobs late{};
-  if (late_in != nullptr) late = *late_in;
-  if (!D.has_cls && !D.has_sw && late.n == 0) return mab0_post_launch(D.posts, st);
-  const Mab0PostJobs& J = D.posts;
-  const PostExtents x = post_extents(J);
-  // Both post stages in this launch (PCA_POST_FUSE) when every job has a shape the fused rows cover, no rider
-  // writes what they accumulate into (in the two-launch form the launch boundary orders them) and this launch
-  // leaves no partials to sum (the layer-1 fc_v job ran in k_wgrad128_step); else k_terminal1, then k_mab0_post2.
-  bool fuse = post_fuse_on() && J.n > 0 && !(D.has_sw && D.sw.slab != nullptr);
-  for (int i = 0; fuse && i < J.n; ++i) fuse = post_fused_ok(J.j[i]) && !post_outputs_overlap(J.j[i], late);
-  int gx = (int)cdiv(x.n1, 256);
-  if (fuse) {                    // rows of fused workgroups, and rows of dWk workgroups
-    gx = 0;
-    for (int i = 0; i < J.n; ++i) {
-      const Mab0PostJob& a = J.j[i];
-      const int wk = a.DG != nullptr ? (int)cdiv(a.d * a.dk, 256) : 0;
-      const int fw = a.d / POST_FC + (a.dI != nullptr ? a.m : 0);
-      gx = wk > gx ? wk : gx;
-      gx = fw > gx ? fw : gx;
-    }
-  }
-  if (D.has_cls && D.cls.C > gx) gx = D.cls.C;
-  if (D.has_sw) {
-    const int gs = (int)cdiv(D.sw.M, D.sw.rows_per_wg);
-    gx = gs > gx ? gs : gx;
-  }
-  for (int i = 0; i < late.n; ++i) {
-    PCA_REQUIRE(slab_sum_job_ok(late.j[i]), "terminal: rider alignment");
-    const int need = (int)cdiv(late.j[i].n, 256);
-    gx = need > gx ? need : gx;
-  }
-  const int nfuse = fuse ? J.n : 0;
-  hipLaunchKernelGGL(k_terminal1,
-                     dim3(gx, nfuse + J.n + (D.has_cls ? 1 : 0) + (D.has_sw ? 1 : 0) + late.n),
-                     dim3(256), 0, st, J, nfuse, D.cls, D.has_cls ? 1 : 0, D.sw, D.has_sw ? 1 : 0, late);
-  PCA_TRY(check_launch("k_terminal1"));
-  if (fuse) return PCA_OK;
-  // the layer-1 fc_v partials k_terminal1 wrote (slab mode) are summed by rider rows of post 2
-  SlabSumJobs late2{};
-  if (D.has_sw && D.sw.slab != nullptr) {
-    const int nwg = (int)cdiv(D.sw.M, D.sw.rows_per_wg), n1 = 128 * D.sw.dq, stride = n1 + 128;
-    late2.j[late2.n++] = SlabSumJob{D.sw.slab, D.sw.dW, nwg, n1, 1, stride};
-    if (D.sw.db != nullptr) late2.j[late2.n++] = SlabSumJob{D.sw.slab + n1, D.sw.db, nwg, 128, 1, stride};
-  }
-  if (J.n == 0) return slab_sum_jobs(late2, st);
-  int n2 = x.n2;
-  for (int i = 0; i < late2.n; ++i) n2 = late2.j[i].n > n2 ? late2.j[i].n : n2;
-  hipLaunchKernelGGL(k_mab0_post2, dim3((unsigned)cdiv(n2, 256), J.n + late2.n), dim3(256), 0, st, J,
-                     late2);
-  return check_launch("k_mab0_post2");
-}
-
-int mab0_post_launch(const Mab0PostJobs& J, hipStream_t st) {
-  if (J.n == 0) return PCA_OK;
-  const PostExtents x = post_extents(J);
-  hipLaunchKernelGGL(k_mab0_post1, dim3((unsigned)cdiv(x.n1, 256), J.n), dim3(256), 0, st, J);
-  PCA_TRY(check_launch("k_mab0_post1"));
-  hipLaunchKernelGGL(k_mab0_post2, dim3((unsigned)cdiv(x.n2, 256), J.n), dim3(256), 0, st, J,
-                     SlabSumJobs{});
-  return check_launch("k_mab0_post2");
-}
-
-bool wgrad_slabs_on() {          // (read per call: a test switches it between two engines)
-  return env_not_zero("PCA_WGRAD_SLABS");
-}
-bool wgrad_fold_on() {           // (read per call, like the switch above)
-  return env_not_zero("PCA_WGRAD_FOLD");
-}
-// PCA_WGRAD_RIDE: the bf16 list in the launch of layer 1's few-queries backward (k_mab0_small_ride);
-// unset = the measured default.  Read per call, like the switches above.
-constexpr bool WGRAD_RIDE_DEFAULT = true;
-bool wgrad_ride_on() {
-  const char* e = getenv("PCA_WGRAD_RIDE");
-  if (e == nullptr || e[0] == 0) return WGRAD_RIDE_DEFAULT;
-  return e[0] != '0';
-}
-// Every workgroup costs a 64 KiB slab (16384 atomics without the slabs): aim at ~200 workgroups over all
-// bf16 jobs (512 rows for one B*N-row job, 1024 for three, ...).  (Swept before k_wgrad128 kept several
-// tiles in flight, and kept because the partition fixes the summation order: 1024 beat 512 / 768 and 2048
-// at 3 x 65536 rows.)
-static int bf16_rows_per_wg(double rows) {
-  const int rpw = 512 * (int)((rows + 98303.0) / 98304.0);
-  return rpw < 512 ? 512 : (rpw > 1024 ? 1024 : rpw);
-}
-static size_t bf16_slab_cap(const BwdDefer& D) { return D.slab_cap * 3 / 4; }
 
 bool bwd_defer_ride(BwdDefer& D, WgradJobs* jobs, int* rows_per_wg, int* rc) {
   *rc = PCA_OK;
-  if (!(wgrad_slabs_on() && D.slab_ws != nullptr && D.slab_cap > 0 && wgrad_fold_on() && wgrad_ride_on()))
+  if (!(D.form.ride && D.slab_ws != nullptr && D.slab_cap > 0) || D.wg_bf16.n == 0 || D.placed.bf16_ran)
     return false;
-  if (D.wg_bf16.n == 0 || D.ride_done) return false;
-  double rows = 0;
-  for (int i = 0; i < D.wg_bf16.n; ++i) rows += (double)D.wg_bf16.j[i].M;
-  if (rows <= 0) return false;
-  *jobs = D.wg_bf16;
-  *rows_per_wg = bf16_rows_per_wg(rows);
-  D.ride_late.n = 0;
-  WgradSlabs sl{D.slab_ws, bf16_slab_cap(D), &D.ride_late, nullptr, 0};
-  *rc = wgrad128_place(*jobs, *rows_per_wg, &sl);
-  if (*rc != PCA_OK) return false;
-  D.ride_used = (sl.used + 255) & ~(size_t)255;
-  D.ride_done = 1;
+  TailPlan P;
+  *rc = plan_tail(D, &P, true);
+  if (*rc != PCA_OK || P.bf16.n == 0) return false;
+  *jobs = P.bf16;
+  *rows_per_wg = P.rpw_bf16;
+  D.placed = P.placed;
+  D.placed.bf16_ran = true;
   D.wg_bf16.n = 0;
   return true;
 }
 
+// walks the plan: one case per launch, charged to the profiler as before
 int bwd_defer_flush(BwdDefer& D, hipStream_t st) {
-  // The sums the post stages read (D.sums: dG of the few-queries blocks) ride in the first
-  // weight-gradient launch as extra workgroup rows.  Slab mode (the default when the caller lent
-  // room; PCA_WGRAD_SLABS=0 switches back to fp32 atomics): the weight gradients themselves use no
-  // atomics either - per-workgroup partials, summed in a fixed order by rider rows of k_terminal1
-  // (`late`: only the optimizer reads them).  With EVERY reduction of the step in this form
-  // configs[1] measured 0.324 ms/step against 0.335 with the atomics (three same-box pairs), and the
-  // step is bit-reproducible.  (With only k_wgrad128 converted it was 0.343 ... 0.361 against 0.348,
-  // depending on where the partials happened to lie.)
-  const bool slab_mode = wgrad_slabs_on() && D.slab_ws != nullptr && D.slab_cap > 0;
-  SlabSumJobs late{};
-  size_t used = 0;          // the two lists' slabs lie back to back
-  if (D.ride_done) {        // the bf16 list ran already: its slabs lie first, its sums come first
-    PCA_REQUIRE(slab_mode && D.wg_bf16.n == 0, "bwd_defer_flush: bf16 jobs queued after the list ran");
-    late = D.ride_late;
-    used = D.ride_used;
-  }
-  double rows = 0, rows_f32 = 0;
-  for (int i = 0; i < D.wg_bf16.n; ++i) rows += (double)D.wg_bf16.j[i].M;
-  for (int i = 0; i < D.wg_f32.n; ++i) rows_f32 += (double)D.wg_f32.j[i].M;
-  // the fp32 jobs ([B*m] rows) take 128 rows per workgroup (128 beat 64 and 256, swept with the bf16
-  // list's rows above)
-  int rpw = bf16_rows_per_wg(rows);
-  int rpw_f32 = 128;
-  const size_t cap_bf16 = bf16_slab_cap(D);
-  // PCA_POST_FUSE: the layer-1 fc_v job (it reads what layer 1's few-queries backward wrote, as the fp32 list
-  // does) runs as rows of the folded launch instead of k_terminal1's, so that its two slab sums are riders of
-  // k_terminal1 and nothing is left for a launch behind it.  Its slab lies behind the fp32 list's, where the
-  // flush put it before; called once the lists are placed.
-  SmallWgradArgs small{};
-  auto take_small = [&](int reserve = 0) -> const SmallWgradArgs* {   // reserve: sum jobs still to be appended
-    if (!(post_fuse_on() && slab_mode && D.has_sw) || (128 * D.sw.dq) % 4 != 0 ||
-        late.n + D.late.n + reserve + 2 > 40)
-      return nullptr;
-    const int nwg = (int)cdiv(D.sw.M, D.sw.rows_per_wg), n1 = 128 * D.sw.dq, stride = n1 + 128;
-    if (used + (size_t)nwg * stride * 4 > D.slab_cap) return nullptr;
-    small = D.sw;
-    small.slab = D.slab_ws + used / sizeof(float);
-    used += ((size_t)nwg * stride * 4 + 255) & ~(size_t)255;
-    late.j[late.n++] = SlabSumJob{small.slab, small.dW, nwg, n1, 1, stride};
-    if (small.db != nullptr) late.j[late.n++] = SlabSumJob{small.slab + n1, small.db, nwg, 128, 1, stride};
-    D.has_sw = 0;
-    return &small;
-  };
-  if (D.ride_done && rows_f32 > 0 && wgrad_fold_on()) {
-    // the same launch with an empty bf16 list: the fp32 jobs and the sums that are due now
-    WgradJobs f32 = D.wg_f32;
-    ProfScope ps(PCA_K_WGRAD, st, 2.0 * rows_f32 * 128 * 128, 8.0 * rows_f32 * 128);
-    WgradSlabs sf{D.slab_ws + used / sizeof(float), D.slab_cap - used, &late, nullptr, 0};
-    PCA_TRY(wgrad128_place(f32, rpw_f32, &sf));
-    used += (sf.used + 255) & ~(size_t)255;
-    PCA_TRY(wgrad128_launch_step(WgradJobs{}, rpw, f32, rpw_f32, D.sums, st, take_small()));
-    ps.end();
-    D.wg_f32.n = 0;
-    D.sums.n = 0;
-  }
-  if (rows > 0 && rows_f32 > 0 && wgrad_fold_on()) {
-    // ONE launch (k_wgrad128_step): the fp32 jobs run beside the bf16 rows (which leave a quarter of
-    // the compute units idle) instead of paying a launch boundary and a ramp of their own: 32 us
-    // against 25 + 9.5.  Same partition, same slabs, same order of the slab sums as the two launches
-    // below: the same bits.
-    WgradJobs bf = D.wg_bf16, f32 = D.wg_f32;
-    ProfScope ps(PCA_K_WGRAD, st, 2.0 * (rows + rows_f32) * 128 * 128,
-                 4.0 * rows * 128 + 8.0 * rows_f32 * 128);
-    WgradSlabs sl{slab_mode ? D.slab_ws : nullptr, cap_bf16, &late, nullptr, 0};
-    PCA_TRY(wgrad128_place(bf, rpw, &sl));
-    used = (sl.used + 255) & ~(size_t)255;
-    WgradSlabs sf{slab_mode ? D.slab_ws + used / sizeof(float) : nullptr, D.slab_cap - used, &late,
-                  nullptr, 0};
-    PCA_TRY(wgrad128_place(f32, rpw_f32, &sf));
-    used += (sf.used + 255) & ~(size_t)255;
-    PCA_TRY(wgrad128_launch_step(bf, rpw, f32, rpw_f32, D.sums, st, take_small()));
-    ps.end();
-    D.wg_bf16.n = D.wg_f32.n = 0;
-    D.sums.n = 0;
-  }
-  if (D.wg_bf16.n > 0) {
-    ProfScope ps(PCA_K_WGRAD, st, 2.0 * rows * 128 * 128, 4.0 * rows * 128);
-    WgradSlabs sl{slab_mode ? D.slab_ws : nullptr, cap_bf16, &late, &D.sums, 0};
-    PCA_TRY(wgrad128_launch(D.wg_bf16, true, true, rpw, st, &sl));
-    used = (sl.used + 255) & ~(size_t)255;
-    ps.end();
-    D.wg_bf16.n = 0;
-    D.sums.n = 0;
-  }
-  if (D.wg_f32.n > 0) {
-    WgradSlabs sl{slab_mode ? D.slab_ws + used / sizeof(float) : nullptr, D.slab_cap - used, &late,
-                  &D.sums, 0};
-    // (the two lists as a launch each, PCA_WGRAD_FOLD=0: the fc_v job rides with the fp32 one, behind its
-    //  slabs - placed here first to learn where they end; the launch places them again, the same way)
-    const SmallWgradArgs* sw = nullptr;
-    if (slab_mode && rows_f32 > 0 && D.has_sw && post_fuse_on()) {
-      WgradJobs f32 = D.wg_f32;
-      int rpw = rpw_f32;
-      const int n_late = late.n;
-      PCA_TRY(wgrad128_place(f32, rpw, &sl));
-      const int n_f32 = late.n - n_late;
-      late.n = n_late;
-      const size_t used_jobs = used;
-      used += (sl.used + 255) & ~(size_t)255;
-      sw = take_small(n_f32);
-      used = used_jobs;
+  TailPlan P;
+  PCA_TRY(plan_tail(D, &P));
+  const Mab0PostJobs& J = D.posts;
+  const SmallWgradArgs* sw = P.fcv == FcvRuns::WgradRows ? &P.small : nullptr;
+  const int term_sw = P.fcv == FcvRuns::TerminalRows || P.fcv == FcvRuns::TerminalRowsPost2Sums;
+  const double rows = P.rows_bf16, rows_f32 = P.rows_f32;
+  const SlabSumJobs* due = &P.step.riders;       // riders of the first weight-gradient launch
+  static const char* const name[] = {"k_wgrad128_step", "k_wgrad128", "k_wgrad128", "wgrad256", "k_slab_sum_jobs",
+                                     "k_terminal1", "k_mab0_post1", "k_mab0_post2", "k_slab_sum_jobs"};
+  for (int i = 0; i < P.nseq; ++i) {
+    const TailLaunch& L = P.seq[i];
+    const dim3 grid(L.gx, L.gy);
+    switch (L.kernel) {
+      case TailKernel::WgradStep: {
+        ProfScope ps(PCA_K_WGRAD, st, 2.0 * (rows + rows_f32) * 128 * 128,
+                     4.0 * rows * 128 + 8.0 * rows_f32 * 128);
+        PCA_TRY(wgrad128_launch_step(P.bf16, P.rpw_bf16, P.f32, P.rpw_f32, P.step, st, sw));
+        ps.end();
+        break;
+      }
+      case TailKernel::Wgrad128Bf16: {
+        ProfScope ps(PCA_K_WGRAD, st, 2.0 * rows * 128 * 128, 4.0 * rows * 128);
+        PCA_TRY(wgrad128_launch(P.bf16, true, true, P.rpw_bf16, st, due));
+        ps.end();
+        due = nullptr;
+        break;
+      }
+      case TailKernel::Wgrad128F32: PCA_TRY(wgrad128_launch(P.f32, false, false, P.rpw_f32, st, due, sw)); break;
+      case TailKernel::Wgrad256: PCA_TRY(wgrad256_flush_deferred(D, st)); break;
+      case TailKernel::SumsDue: PCA_TRY(slab_sum_jobs(P.step.riders, st)); break;
+      case TailKernel::SumsLate2: PCA_TRY(slab_sum_jobs(P.late2, st)); break;
+      case TailKernel::Terminal1:
+        hipLaunchKernelGGL(k_terminal1, grid, dim3(256), 0, st, J, P.post_fused ? J.n : 0, D.cls,
+                           D.has_cls ? 1 : 0, P.small, term_sw, P.placed.late);
+        break;
+      case TailKernel::Post1: hipLaunchKernelGGL(k_mab0_post1, grid, dim3(256), 0, st, J); break;
+      case TailKernel::Post2: hipLaunchKernelGGL(k_mab0_post2, grid, dim3(256), 0, st, J, P.late2); break;
     }
-    PCA_TRY(wgrad128_launch(D.wg_f32, false, false, rpw_f32, st, &sl, sw));
-    used += (sl.used + 255) & ~(size_t)255;
-    if (sw != nullptr) used += ((size_t)cdiv(sw->M, sw->rows_per_wg) * (128 * sw->dq + 128) * 4 + 255) & ~(size_t)255;
-    D.wg_f32.n = 0;
-    D.sums.n = 0;
+    PCA_TRY(check_launch(name[(int)L.kernel]));
   }
-  if (D.wg256_n > 0) PCA_TRY(wgrad256_flush_deferred(D, st));
-  PCA_TRY(slab_sum_jobs(D.sums, st));        // (nobody carried them)
-  D.sums.n = 0;
-  for (int i = 0; i < D.late.n; ++i) {
-    PCA_REQUIRE(late.n < 40, "bwd_defer_flush: slab-sum table full");
-    late.j[late.n++] = D.late.j[i];
-  }
-  D.late.n = 0;
-  if (slab_mode && D.has_sw) {     // layer-1 fc_v gradient (rider of k_terminal1): slabs as well
-    const int nwg = (int)cdiv(D.sw.M, D.sw.rows_per_wg), stride = 128 * D.sw.dq + 128;
-    if ((128 * D.sw.dq) % 4 == 0 && used + (size_t)nwg * stride * 4 <= D.slab_cap)
-      D.sw.slab = D.slab_ws + used / sizeof(float);
-  }
-  PCA_TRY(terminal_launch(D, st, &late));
-  D.posts.n = 0;
-  D.has_cls = D.has_sw = 0;
-  D.ride_done = 0;
-  D.ride_used = 0;
-  D.ride_late.n = 0;
+  D.wg_bf16.n = D.wg_f32.n = D.sums.n = D.late.n = D.posts.n = D.has_cls = D.has_sw = 0;
+  D.placed = TailPlaced{};
   return PCA_OK;
 }
 

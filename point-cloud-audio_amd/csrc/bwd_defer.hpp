@@ -1,8 +1,8 @@
 // The end of a backward pass: the job tables of the reductions only the optimiser reads (weight gradients,
-// fixed-order slab sums, the shared-query post stages, the classifier's gradient), BwdDefer, which collects
-// them over the blocks of a step, and the launches that run them - wgrad128.hip (k_wgrad128, k_wgrad_small),
-// bwd_defer.hip (bwd_defer_flush, k_terminal1, k_mab0_post1 / 2), slab_sum.hip, wgrad256.hip (the d = 256
-// job) - plus the PMA head launch that queues the classifier's job (pma_head.hip).
+// fixed-order slab sums, the shared-query post stages, the classifier's gradient), BwdDefer, which collects them
+// over the blocks of a step, TailForm (the tail's switches) and TailPlan (every slab, rider and launch of the flush:
+// tail_plan.hip, host code only), and the launches that run a plan - bwd_defer.hip (bwd_defer_flush, k_terminal1,
+// k_mab0_post1 / 2), wgrad128.hip, slab_sum.hip, wgrad256.hip - plus the PMA head launch (pma_head.hip).
 #pragma once
 #include "pca_common.h"
 #include "soft_targets.hpp"
@@ -48,26 +48,31 @@ struct WgradJobs {
   WgradJob j[16];
   int n;
 };
-struct WgradSlabs {          // optional slab mode of wgrad128_launch
-  float* ws;                 // partials go here (cap bytes) ...
-  size_t cap;
-  SlabSumJobs* sums_out;     // ... and their sum jobs are appended here (run them afterwards)
-  const SlabSumJobs* riders; // sums that are due now: extra workgroup rows of this launch
-  size_t used;               // out: bytes of ws taken
-};
-// g_bf16 / a_bf16: element type of every job's G / A (bf16 or fp32)
-// `small`: the layer-1 fc_v job (wgrad_small_f32_launch's, with a slab) as further rows of the same launch
+inline int64_t wgrad_max_rows(const WgradJobs& jobs) {
+  int64_t m = 0;
+  for (int i = 0; i < jobs.n; ++i) m = jobs.j[i].M > m ? jobs.j[i].M : m;
+  return m;
+}
+// g_bf16 / a_bf16: element type of every job's G / A.  The jobs come placed (plan_tail; slab null: fp32
+// atomics); `riders`: sums that are due now, `small`: the layer-1 fc_v job (with a slab), both as further rows
 struct SmallWgradArgs;
-int wgrad128_launch(const WgradJobs& jobs, bool g_bf16, bool a_bf16, int rows_per_wg,
-                    hipStream_t st, WgradSlabs* slabs = nullptr, const SmallWgradArgs* small = nullptr);
-// The two halves of wgrad128_launch for a caller that puts two lists into one launch: wgrad128_place
-// gives every job of a list its slabs (slab mode; rows_per_wg doubles until they fit `slabs->cap`) and
-// appends their sum jobs; wgrad128_launch_step runs a placed bf16 list (G, A bf16; empty when it ran
-// beside layer 1's few-queries backward: bwd_defer_ride) and a placed fp32 list, each with its own rows
-// per workgroup (>= 128), and the riders as ONE launch (k_wgrad128_step).
-int wgrad128_place(WgradJobs& jobs, int& rows_per_wg, WgradSlabs* slabs);
+int wgrad128_launch(const WgradJobs& jobs, bool g_bf16, bool a_bf16, int rows_per_wg, hipStream_t st,
+                    const SlabSumJobs* riders = nullptr, const SmallWgradArgs* small = nullptr);
+// its grid (k_wgrad128): x = the widest of the job rows and the rider rows
+int wgrad128_shape(const WgradJobs& jobs, int rows_per_wg, const SlabSumJobs& riders,
+                   const SmallWgradArgs* small, unsigned* gx, unsigned* gy, int* sw_rows);
+// A placed bf16 list (empty when it ran beside layer 1's few-queries backward: bwd_defer_ride) and a placed fp32
+// list, each with its own rows per workgroup (>= 128), and the riders as ONE launch (k_wgrad128_step)
+struct WgradStepShape {
+  unsigned gx, gy;
+  int sw_rows;               // rows of the fc_v job
+  SlabSumJobs riders;        // (bf16 list empty: cut into column ranges as wide as the fp32 rows)
+};
+int wgrad128_step_shape(const WgradJobs& bf16_jobs, int rows_per_wg_bf16, const WgradJobs& f32_jobs,
+                        int rows_per_wg_f32, const SlabSumJobs& riders, const SmallWgradArgs* small,
+                        WgradStepShape* out);
 int wgrad128_launch_step(const WgradJobs& bf16_jobs, int rows_per_wg_bf16, const WgradJobs& f32_jobs,
-                         int rows_per_wg_f32, const SlabSumJobs& riders, hipStream_t st,
+                         int rows_per_wg_f32, const WgradStepShape& shape, hipStream_t st,
                          const SmallWgradArgs* small = nullptr);
 
 // ---- the d = 256 job (wgrad256.hip; launchers in d256.hpp) ------------------
@@ -119,13 +124,32 @@ struct Mab0PostJobs {
   int n;
 };
 int mab0_post_launch(const Mab0PostJobs& J, hipStream_t st);
+constexpr int POST_FC = 4, POST_MAXM = 16;      // shapes the fused post rows of k_terminal1 cover
 
-// ---- what a step collects, and its flush (bwd_defer.hip) ------------------
-// Terminal reductions of a backward pass (only the optimiser / the all-reduce reads their
-// results): a caller that runs several blocks collects them and flushes ONCE at the end of the
-// phase - one weight-gradient launch over the bf16 and the fp32 job table (PCA_WGRAD_FOLD=0: one
-// launch each) and one pair of post launches instead of one set per block.  Their operands live in per-block workspaces that
-// stay untouched until then.
+// ---- the switches of the d = 128 backward tail, read in one place ------------------
+// tail_form_from_env (tail_plan.hip) holds the defaults and resolves what depends on what in the environment (no
+// caller sees `ride` without `slabs`); what depends on shapes stays with the code that knows them.  plan() reads it
+// once per engine call, the step's BwdDefer carries it, a stand-alone block call reads it at its entry.
+struct TailForm {
+  bool slabs;          // reductions as per-workgroup slabs + fixed-order sums (PCA_WGRAD_SLABS=0: fp32 atomics)
+  bool fold;           // the two deferred lists in one k_wgrad128_step (PCA_WGRAD_FOLD=0: a k_wgrad128 each)
+  bool ride;           // the bf16 list beside layer 1's few-queries backward (PCA_WGRAD_RIDE; with slabs, fold and
+                       // midfuse_small only)
+  bool post_fuse;      // both post stages in k_terminal1, the layer-1 fc_v job in the fp32 list's launch (PCA_POST_FUSE)
+  bool midfuse_wide, midfuse_small;   // the mid chain inside layer 2's / layer 1's few-queries backward
+  bool dz_mask;        // the fc_o job masks dY itself (PCA_D128_DZ_MASK=0: the backward writes dZ)
+};
+TailForm tail_form_from_env();
+
+// ---- what a step collects, its plan and its flush (tail_plan.hip, bwd_defer.hip) ------------------
+// What the planner has handed out so far in a step (bwd_defer_ride leaves it for the flush to go on from)
+struct TailPlaced {
+  size_t used;            // bytes of slab_ws taken: 256-byte aligned ranges, bf16 list, fp32 list, fc_v job
+  SlabSumJobs late;       // the sums of what has been placed, in the order k_terminal1 runs them
+  bool bf16_ran;          // the bf16 list ran already, beside layer 1's few-queries backward
+};
+// Terminal reductions of a backward pass (only the optimiser / the all-reduce reads their results): a caller that runs
+// several blocks collects them and flushes ONCE at the end of the phase; their operands stay in place until then.
 struct BwdDefer {
   SlabSumJobs sums;       // partial sums the post stages read: run before them
   SlabSumJobs late;       // partial sums only the optimizer reads (ride in the last launches)
@@ -137,35 +161,50 @@ struct BwdDefer {
   void* wg256_ws;
   float* slab_ws;         // room for the weight-gradient partials of the two deferred lists
   size_t slab_cap;        // (bytes; null / 0: those reductions use fp32 atomics)
+  TailForm form;          // the call's switches (StepPlan::tail)
   Mab0PostJobs posts;
-  WgradJobs wg_bf16;      // G, A bf16, M = B*N rows   (512 ... 1024 rows per workgroup: bwd_defer_flush)
+  WgradJobs wg_bf16;      // G, A bf16, M = B*N rows   (512 ... 1024 rows per workgroup: plan_tail)
   WgradJobs wg_f32;       // G, A fp32, M = B*m rows   (128 rows per workgroup)
-  // classifier weight gradient + loss counters, layer-1 fc_v gradient: they ride in the first
-  // post launch (k_terminal1) as extra job rows
-  ClsWgradArgs cls;
-  SmallWgradArgs sw;
+  ClsWgradArgs cls;       // classifier weight gradient + loss counters: a row of k_terminal1
+  SmallWgradArgs sw;      // layer-1 fc_v gradient: where TailPlan::fcv says
   int has_cls, has_sw;
-  // the bf16 list already ran, beside layer 1's few-queries backward (bwd_defer_ride): its sum jobs, and
-  // the bytes of slab_ws its partials take (the flush places the fp32 list behind them)
-  int ride_done;
-  size_t ride_used;
-  SlabSumJobs ride_late;
+  TailPlaced placed;
 };
+inline TailForm tail_form_of(const BwdDefer* d) { return d != nullptr ? d->form : tail_form_from_env(); }
+
+enum class FcvRuns {      // where the layer-1 fc_v job runs, and who sums its partials
+  Nowhere,                // (no such job)
+  WgradRows,              // rows of the fp32 list's weight-gradient launch; its two sums are `late` riders
+  TerminalRows,           // rows of k_terminal1, adding atomically
+  TerminalRowsPost2Sums   // rows of k_terminal1 writing partials that rider rows of k_mab0_post2 sum
+};
+// (Wgrad256: wgrad256_flush_deferred; SumsDue / SumsLate2: k_slab_sum_jobs over the due sums no weight-gradient
+//  launch carried / over late2 when there is no post job - launchers with grids of their own: 0 here)
+enum class TailKernel { WgradStep, Wgrad128Bf16, Wgrad128F32, Wgrad256, SumsDue, Terminal1, Post1, Post2, SumsLate2 };
+struct TailLaunch { TailKernel kernel; unsigned gx, gy; };
+// Everything bwd_defer_flush runs, decided before the first launch: plan_tail launches nothing and dereferences no
+// device pointer.  Slabs come from ONE cursor (placed.used) in the order bf16 list (inside 3/4 of the room), fp32
+// list, fc_v job; rows per workgroup (bf16: 512, from 98304 rows on up to 1024; fp32: 128) double until a list fits.
+struct TailPlan {
+  int rpw_bf16, rpw_f32;
+  double rows_bf16, rows_f32;  // (all jobs of a list together)
+  WgradJobs bf16, f32;         // the lists with their slabs (a list without rows: empty)
+  FcvRuns fcv;
+  SmallWgradArgs small;        // the fc_v job with its slab
+  WgradStepShape step;         // step.riders: the due sums, as the first weight-gradient launch carries them
+  TailPlaced placed;           // placed.late: k_terminal1's riders
+  SlabSumJobs late2;           // k_mab0_post2's riders
+  bool post_fused;             // both post stages in k_terminal1
+  TailLaunch seq[6];           // the launches in order
+  int nseq;
+};
+// bf16_only: stop once the bf16 list is placed (bwd_defer_ride)
+int plan_tail(const BwdDefer& D, TailPlan* P, bool bf16_only = false);
 int bwd_defer_flush(BwdDefer& D, hipStream_t st);
-// Whether the bf16 list collected so far may run now, in the launch of layer 1's few-queries backward
-// (slab mode with room lent, the two lists folded, PCA_WGRAD_RIDE not 0); if so `jobs` receives the list
-// placed exactly as the flush would place it (same rows per workgroup, same slabs at the start of slab_ws)
-// and D records it as done.  The caller launches it (mab0_small_ride_launch).
+// Whether the bf16 list collected so far may run now, in the launch of layer 1's few-queries backward (TailForm::ride,
+// room lent); if so `jobs` receives it as plan_tail places it and D.placed records that.  The caller launches it.
 bool bwd_defer_ride(BwdDefer& D, WgradJobs* jobs, int* rows_per_wg, int* rc);
-// post stages + riders (`late`: sums nobody reads before the optimizer, e.g. weight gradients)
-int terminal_launch(const BwdDefer& D, hipStream_t st, const SlabSumJobs* late = nullptr);
 int wgrad256_flush_deferred(BwdDefer& D, hipStream_t st);       // d256_host.hip
-bool wgrad_slabs_on();       // reductions of the fused d = 128 path as slabs + fixed-order sums
-                             // (PCA_WGRAD_SLABS=0: fp32 atomics)
-bool wgrad_fold_on();        // the two deferred d = 128 lists in one launch (PCA_WGRAD_FOLD=0: two)
-bool wgrad_ride_on();        // the bf16 list beside layer 1's few-queries backward (PCA_WGRAD_RIDE)
-bool post_fuse_on();         // both shared-query post stages inside k_terminal1, the layer-1 fc_v job in
-                             // k_wgrad128_step (PCA_POST_FUSE=0: k_terminal1, then k_mab0_post2)
 // launch `jobs` now, or append them to the matching list of `defer`
 int wgrad128_defer(BwdDefer* defer, const WgradJobs& jobs, bool bf16, int rows_per_wg,
                    hipStream_t st);

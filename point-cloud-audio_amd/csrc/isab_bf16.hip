@@ -8,8 +8,6 @@
 #include "bwd_defer.hpp"
 #include "step_ctx.hpp"
 
-#include <stdlib.h>
-
 namespace pca {
 
 
@@ -19,20 +17,7 @@ bool isab_bf16_supported(const pca_mab_shape& s0, const pca_mab_shape& s1) {
          s1.nk == 16 && s0.h == 4 && s0.B == s1.B && s0.nk == s1.nq;
 }
 
-namespace {
-constexpr size_t DD = 128 * 128;
-
-// PCA_D128_MIDFUSE: 0 = k_mid_bwd as a launch in both layers, 1 = fused in both, "wide" / "small" =
-// fused in that form only (layer 2, dk = 128 / layer 1, dk <= 4); unset = each layer's measured winner
-constexpr bool MIDFUSE_DEFAULT_WIDE = true, MIDFUSE_DEFAULT_SMALL = true;
-bool midfuse_on(bool small) {
-  const char* e = getenv("PCA_D128_MIDFUSE");
-  if (e == nullptr || e[0] == 0) return small ? MIDFUSE_DEFAULT_SMALL : MIDFUSE_DEFAULT_WIDE;
-  if (e[0] == 'w') return !small;
-  if (e[0] == 's') return small;
-  return e[0] != '0';
-}
-}  // namespace
+static constexpr size_t DD = 128 * 128;
 
 // images of one ISAB: 13 bf16 [128][128] blocks
 size_t isab_img_bytes() { return 13 * align256(DD * 2); }
@@ -125,9 +110,9 @@ int isab_bf16_bwd(const pca_mab_shape& s0, const pca_mab_shape& s1, const float*
   const int64_t Bm = (int64_t)s0.B * m;
   const int Rp = 64;
   // the per-set mid chain as the prologue of the few-queries backward (every workgroup of a set runs
-  // it for itself) instead of a launch between the two point-sized kernels; read per call so that one
-  // process can compare both forms
-  const bool fuse_mid = midfuse_on(dk <= 4);
+  // it for itself) instead of a launch between the two point-sized kernels (PCA_D128_MIDFUSE)
+  const TailForm form = tail_form_of(defer);
+  const bool fuse_mid = dk <= 4 ? form.midfuse_small : form.midfuse_wide;
   // (fused: nothing runs between the two kernels, so the first one clears DG for the second)
   PCA_TRY(mab1_bf16_bwd_ex(s1, X, H, p1, saved1, dY, dX, nullptr, 0, g1, ws1,
                            PCA_F_SKIP_KV_TAIL, st, &im, fuse_mid ? w0.DG : nullptr,

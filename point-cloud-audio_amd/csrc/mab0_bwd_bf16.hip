@@ -517,7 +517,7 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
 
   if (small) {
     // slab mode: per-set partials [B][R][dk] instead of atomics, summed in a fixed order
-    float* sl = (wgrad_slabs_on() && (R * dk) % 4 == 0) ? w.slabs : nullptr;
+    float* sl = (tail_form_of(defer).slabs && (R * dk) % 4 == 0) ? w.slabs : nullptr;
     const dim3 sgrid(s.B, (R % 64 == 0 && R <= 512) ? 2 : 1);
     if (mid != nullptr) {
       PCA_REQUIRE(R == 64, "mab0_bf16_bwd: fused mid chain with %d score rows", R);

@@ -121,7 +121,7 @@ __device__ __forceinline__ void mab0_bwd_small_body(const Mab0SmallArgs& a, int 
   }
 }
 
-// The bf16 weight-gradient list of a step (placed: wgrad128_place) and the layer-1 few-queries backward with
+// The bf16 weight-gradient list of a step (placed: bwd_defer_ride) and the layer-1 few-queries backward with
 // its mid chain (R == 64, dk <= 4, per-set slabs) over B sets in ONE launch: k_mab0_small_ride, wgrad128.hip.
 int mab0_small_ride_launch(const WgradJobs& bf16_jobs, int rows_per_wg, const Mab0SmallArgs& sets, int B,
                            hipStream_t st);

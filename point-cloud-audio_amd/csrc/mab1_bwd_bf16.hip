@@ -721,8 +721,8 @@ int mab1_bf16_bwd_ex(const pca_mab_shape& s, const void* X, const float* H,
   // dZ = dY . [Z > 0] is read by the fc_o weight-gradient job only: with bf16 gradients and whole
   // 128-point mask blocks per set that job takes dY and the mask words (WgradJob::mask) and dZ is
   // never written (PCA_D128_DZ_MASK=0: the materialised form)
-  static const bool dzm_on = env_not_zero("PCA_D128_DZ_MASK");
-  const bool dz_masked = dzm_on && abf && MI == 16 && s.nq % 128 == 0;
+  const TailForm form = tail_form_of(defer);
+  const bool dz_masked = form.dz_mask && abf && MI == 16 && s.nq % 128 == 0;
   Mab1BwdArgs a{};
   a.dY = dY; a.QpS = v.QpS; a.mask = v.mask; a.KpP = v.KpP; a.VpP = v.VpP; a.Kt = v.Kt;
   a.WoTP = w.WoTP; a.WqTP = w.WqTP; a.dZ = dz_masked ? nullptr : w.dZ; a.dQp = w.dQp; a.dOs = w.dOs; a.dS = w.dS;
@@ -768,7 +768,7 @@ int mab1_bf16_bwd_ex(const pca_mab_shape& s, const void* X, const float* H,
     a.Xs = reinterpret_cast<const float*>(X); a.dWqS = gr.wq; a.dbqS = gr.bq; a.dq = s.dq;
     a.WqF = p.wq; a.bqF = p.bq;
     // slab mode: the (unused in this mode) dS block of the workspace holds the fc_q partials
-    if (fwq && wgrad_slabs_on() && (128 * s.dq) % 4 == 0 &&
+    if (fwq && form.slabs && (128 * s.dq) % 4 == 0 &&
         (size_t)a.B * a.tiles_per_set / tpw * (128 * s.dq + 128) * 4 <= (size_t)M * s.h * s.nk * 2)
       a.wq_slab = reinterpret_cast<float*>(w.dS);
     if (abf)

@@ -111,6 +111,7 @@ struct StepPlan {
   bool set128;         // the set-resident forward (set128_fwd.hip) runs            (PCA_SET128=0: per-block launches)
   bool fuse_head;      // ... with the head stages in its own tail                   (PCA_SET128_HEAD=0: as a launch)
   bool pma_bwd;        // ... and then the PMA's attention backward too              (PCA_SET128_PMABWD=0: k_mab0_bwd)
+  TailForm tail;       // the d = 128 backward tail's switches, resolved (tail_form_from_env)
 };
 
 inline StepPlan plan(const pca_st_config& c, bool training, const int32_t* lengths) {
@@ -175,6 +176,7 @@ inline StepPlan plan(const pca_st_config& c, bool training, const int32_t* lengt
               pl.isab128[0] && pl.isab128[1] && pl.pma_head && lengths == nullptr;
   pl.fuse_head = pl.set128 && c.C <= 64 && env_not_zero("PCA_SET128_HEAD");
   pl.pma_bwd = pl.fuse_head && env_not_zero("PCA_SET128_PMABWD");
+  pl.tail = tail_form_from_env();
   return pl;
 }
 
@@ -249,9 +251,9 @@ inline size_t carve(const pca_st_config& c, const StepPlan& pl, Ws* out, void* b
   for (int li = 0; li < 2; ++li)
     w.scratch_bw[li] = pl.training ? (void*)cv.take<char>(max_scratch) : w.scratch;
   w.scratch_pma = pl.pma256 ? (void*)cv.take<char>(mab_bwd_ws_bytes(pl.path_pma, pl.pma)) : w.scratch;
-  if ((pl.isab128[0] || pl.isab128[1]) && wgrad_slabs_on()) {
+  if ((pl.isab128[0] || pl.isab128[1]) && pl.tail.slabs) {
     // two lists (B*N-row and B*m-row jobs) of up to ~600 [128 x 128 (+128)] fp32 slabs each;
-    // bwd_defer_flush gives a workgroup more rows when a list would not fit
+    // plan_tail gives a workgroup more rows when a list would not fit
     constexpr int slab_mb = 40;
     w.wg_slab_bytes = 2 * (size_t)slab_mb * 1024 * 1024;
     w.wg_slabs = cv.take<float>(w.wg_slab_bytes / sizeof(float));
@@ -568,6 +570,7 @@ int st_train_fwd_bwd(const pca_st_config* c, const float* p, const float* X, con
   BwdDefer posts{};
   posts.slab_ws = w.wg_slabs;
   posts.slab_cap = w.wg_slab_bytes;
+  posts.form = pl.tail;
   if (pl.defer_wg) posts.wg256_ws = w.wg256_def;
   // d = 256: all weight images of the step in one launch (phase 1 of a split step finds the images
   // of phase 0 still in place: the parameters do not change in between)

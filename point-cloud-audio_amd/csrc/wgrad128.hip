@@ -363,76 +363,17 @@ __global__ __launch_bounds__(256) void k_wgrad_small(const GT* __restrict__ G,
 
 }  // namespace
 
-static int64_t max_rows(const WgradJobs& jobs) {
-  int64_t m = 0;
-  for (int i = 0; i < jobs.n; ++i) m = jobs.j[i].M > m ? jobs.j[i].M : m;
-  return m;
-}
-
-int wgrad128_place(WgradJobs& jobs, int& rows_per_wg, WgradSlabs* sl) {
-  if (sl == nullptr || sl->ws == nullptr) return PCA_OK;
-  // one slab per workgroup and job; more rows per workgroup until they fit
-  for (;;) {
-    size_t need = 0;
-    for (int i = 0; i < jobs.n; ++i) {
-      const WgradJob& j = jobs.j[i];
-      need += (size_t)cdiv(j.M, rows_per_wg) * ((j.g_hi - j.g_lo) * 128 + (j.db ? 128 : 0)) * 4;
-    }
-    if (need <= sl->cap) break;
-    rows_per_wg *= 2;
-  }
-  float* at = sl->ws;
-  for (int i = 0; i < jobs.n; ++i) {
-    WgradJob& j = jobs.j[i];
-    if (j.M <= 0) continue;
-    const int nwg = (int)cdiv(j.M, rows_per_wg), n1 = (j.g_hi - j.g_lo) * 128;
-    const int stride = n1 + (j.db ? 128 : 0);
-    j.slab = at;
-    PCA_REQUIRE(sl->sums_out->n + 2 <= 40, "wgrad128: slab-sum table full");
-    sl->sums_out->j[sl->sums_out->n++] = SlabSumJob{at, j.dW + (int64_t)j.g_lo * 128, nwg, n1, 1, stride};
-    if (j.db) sl->sums_out->j[sl->sums_out->n++] = SlabSumJob{at + n1, j.db, nwg, 128, 1, stride};
-    at += (size_t)nwg * stride;
-  }
-  sl->used = (size_t)(at - sl->ws) * sizeof(float);
-  return PCA_OK;
-}
-
-// grid.x: the widest of the job rows (rows / rows per workgroup) and of the rider rows
-static int rider_extent(const SlabSumJobs& riders, unsigned& gx) {
-  for (int i = 0; i < riders.n; ++i) {
-    PCA_REQUIRE(slab_sum_job_ok(riders.j[i]), "wgrad128: rider alignment");
-    const unsigned need = (unsigned)cdiv(riders.j[i].n, 256);
-    gx = need > gx ? need : gx;
-  }
-  return PCA_OK;
-}
-
-// the layer-1 fc_v job of a launch (slab mode only: its partials are summed later): rows of the grid's width
-static int small_rows(const SmallWgradArgs* sw, unsigned gx, int blocks_per_wg, int* rows) {
-  PCA_REQUIRE(sw == nullptr || (sw->slab != nullptr && sw->M > 0 && sw->rows_per_wg > 0 && sw->dq >= 1 &&
-                                sw->dq <= 4),
-              "wgrad128: the small job rides with a slab");
-  *rows = sw == nullptr ? 0 : (int)cdiv(cdiv(sw->M, (int64_t)blocks_per_wg * sw->rows_per_wg), gx);
-  return PCA_OK;
-}
-
-int wgrad128_launch(const WgradJobs& jobs_in, bool g_bf16, bool a_bf16, int rows_per_wg,
-                    hipStream_t st, WgradSlabs* sl, const SmallWgradArgs* sw) {
-  WgradJobs jobs = jobs_in;
-  const int64_t maxM = max_rows(jobs);
-  SlabSumJobs riders{};
-  if (sl != nullptr && sl->riders != nullptr) riders = *sl->riders;
-  PCA_REQUIRE(sw == nullptr || (maxM > 0 && jobs.n > 0), "wgrad128: the small job rides with a list that has rows");
-  if (maxM == 0 || jobs.n == 0) return slab_sum_jobs(riders, st);
-  PCA_TRY(wgrad128_place(jobs, rows_per_wg, sl));
-  unsigned gx = (unsigned)cdiv(maxM, rows_per_wg);
-  PCA_TRY(rider_extent(riders, gx));
-  // two row groups per workgroup when every workgroup has at least four tiles to share
-  const bool two = rows_per_wg >= 128;
+int wgrad128_launch(const WgradJobs& jobs, bool g_bf16, bool a_bf16, int rows_per_wg, hipStream_t st,
+                    const SlabSumJobs* riders_in, const SmallWgradArgs* sw) {
+  const SlabSumJobs riders = riders_in != nullptr ? *riders_in : SlabSumJobs{};
+  PCA_REQUIRE(sw == nullptr || wgrad_max_rows(jobs) > 0, "wgrad128: the small job rides with a list that has rows");
+  if (wgrad_max_rows(jobs) == 0) return slab_sum_jobs(riders, st);
+  unsigned gx, gy;
   int sw_rows = 0;
-  PCA_TRY(small_rows(sw, gx, two ? 2 : 1, &sw_rows));
+  PCA_TRY(wgrad128_shape(jobs, rows_per_wg, riders, sw, &gx, &gy, &sw_rows));
+  const bool two = rows_per_wg >= 128;       // (two row groups per workgroup: wgrad128_shape)
   const SmallWgradArgs w = sw != nullptr ? *sw : SmallWgradArgs{};
-  const dim3 grid(gx, (unsigned)(jobs.n + sw_rows + riders.n));
+  const dim3 grid(gx, gy);
   if (g_bf16 && a_bf16) {
     if (two) hipLaunchKernelGGL((k_wgrad128<__bf16, __bf16, 2>), grid, dim3(512), 0, st, jobs, rows_per_wg, w, sw_rows, riders);
     else hipLaunchKernelGGL((k_wgrad128<__bf16, __bf16, 1>), grid, dim3(256), 0, st, jobs, rows_per_wg, w, sw_rows, riders);
@@ -450,41 +391,15 @@ int wgrad128_launch(const WgradJobs& jobs_in, bool g_bf16, bool a_bf16, int rows
 }
 
 int wgrad128_launch_step(const WgradJobs& bf, int rpw_bf, const WgradJobs& f32, int rpw_f32,
-                         const SlabSumJobs& riders, hipStream_t st, const SmallWgradArgs* sw) {
-  // (an empty bf16 list: it ran beside layer 1's few-queries backward, mab0_small_ride_launch)
-  PCA_REQUIRE((bf.n == 0 || max_rows(bf) > 0) && f32.n > 0 && max_rows(f32) > 0,
-              "wgrad128: the step launch takes lists with rows");
-  PCA_REQUIRE(rpw_bf >= 128 && rpw_f32 >= 128, "wgrad128: the step launch runs two row groups");
-  unsigned gx = bf.n == 0 ? 0u : (unsigned)cdiv(max_rows(bf), rpw_bf);
-  const unsigned gf = (unsigned)cdiv(max_rows(f32), rpw_f32);
-  gx = gf > gx ? gf : gx;
-  SlabSumJobs rd = riders;
-  if (bf.n == 0) {
-    // No long rows hide the workgroups that leave at once (each takes a compute unit's whole LDS and
-    // register file while it does): a rider wider than the fp32 rows is cut into column ranges of their
-    // width, rows of its own (element by element the same sums).
-    rd.n = 0;
-    const int width = (int)gx * 256;
-    for (int i = 0; i < riders.n; ++i) {
-      const SlabSumJob& j = riders.j[i];
-      for (int c = 0; c < j.n; c += width) {
-        PCA_REQUIRE(rd.n < 40, "wgrad128: slab-sum table full");
-        rd.j[rd.n++] = SlabSumJob{j.slabs + c, j.out + c, j.S, j.n - c < width ? j.n - c : width,
-                                  j.accumulate, j.stride > 0 ? j.stride : j.n};
-      }
-    }
-  }
-  PCA_TRY(rider_extent(rd, gx));
-  int sw_rows = 0;
-  PCA_TRY(small_rows(sw, gx, 2, &sw_rows));
-  hipLaunchKernelGGL(k_wgrad128_step, dim3(gx, (unsigned)(bf.n + f32.n + sw_rows + rd.n)), dim3(512), 0, st,
-                     bf, rpw_bf, f32, rpw_f32, sw != nullptr ? *sw : SmallWgradArgs{}, sw_rows, rd);
+                         const WgradStepShape& shape, hipStream_t st, const SmallWgradArgs* sw) {
+  hipLaunchKernelGGL(k_wgrad128_step, dim3(shape.gx, shape.gy), dim3(512), 0, st, bf, rpw_bf, f32, rpw_f32,
+                     sw != nullptr ? *sw : SmallWgradArgs{}, shape.sw_rows, shape.riders);
   return check_launch("k_wgrad128_step");
 }
 
 int mab0_small_ride_launch(const WgradJobs& bf, int rpw_bf, const Mab0SmallArgs& sets, int B,
                            hipStream_t st) {
-  PCA_REQUIRE(bf.n > 0 && max_rows(bf) > 0 && rpw_bf >= 128,
+  PCA_REQUIRE(bf.n > 0 && wgrad_max_rows(bf) > 0 && rpw_bf >= 128,
               "mab0_small_ride: a bf16 list with rows, two row groups");
   PCA_REQUIRE(B > 0 && sets.R == 64 && sets.dk >= 1 && sets.dk <= 4 && sets.slabs != nullptr,
               "mab0_small_ride: R=%d dk=%d", sets.R, sets.dk);
@@ -493,7 +408,7 @@ int mab0_small_ride_launch(const WgradJobs& bf, int rpw_bf, const Mab0SmallArgs&
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_mab0_small_ride),
                               hipFuncAttributeMaxDynamicSharedMemorySize, RIDE_LDS);
   });
-  const unsigned gj = (unsigned)cdiv(max_rows(bf), rpw_bf);
+  const unsigned gj = (unsigned)cdiv(wgrad_max_rows(bf), rpw_bf);
   const int set_rows = (int)cdiv(B, gj);
   hipLaunchKernelGGL(k_mab0_small_ride, dim3(gj, (unsigned)(bf.n + set_rows)), dim3(512), RIDE_LDS, st, bf,
                      rpw_bf, sets, B, set_rows);

@@ -216,6 +216,11 @@ SIGNATURES = {
     "pca_colsum": (C.c_int, [c_fp, C.c_int64, C.c_int, c_fp, C.c_int, c_vp]),
 }
 
+# exported for tests and experiments, outside the documented ABI (not in include/pca_hip.h)
+DEBUG_SIGNATURES = {
+    "pca_debug_tail_plan": (C.c_int, [c_i64p, C.c_int, c_i64p, C.c_int]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -237,7 +242,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: build it with point-cloud-audio_amd/csrc/build.sh "
                 "(or __graft_entry__.build()); there is no fallback path")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **DEBUG_SIGNATURES}.items():
             fn = getattr(handle, name)       # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args
