@@ -769,6 +769,46 @@ int pca_adam_step_ex(float* param, float* grad, float* exp_avg, float* exp_avg_s
                      const float* lr_table, int64_t lr_table_len, int32_t* step_count_dev,
                      pca_optim_state* state_dev, int zero_grad, void* stream);
 
+/* pca_adam_step_ex with three options on top, still ONE launch (csrc/optim_groups.hip): decoupled
+ * weight decay (torch.optim.AdamW), a rate and a decay multiplier per segment of the flat vector
+ * (torch param_groups), and an averaged copy of the weights (torch.optim.swa_utils.AveragedModel
+ * with get_ema_multi_avg_fn) updated in the same pass.  A host struct holding device pointers. */
+typedef struct pca_optim_groups {
+  int32_t decoupled;         /* 0: coupled L2 as pca_adam_step; 1: AdamW                      */
+  int32_t n_seg;             /* 0: one group (scales 1); else 1..256 segments of the vector   */
+  const int64_t* seg_end;    /* device int64[n_seg], strictly ascending, seg_end[n_seg-1]==n  */
+  const float* seg_lr_scale; /* device float[n_seg] or NULL (all 1)                           */
+  const float* seg_wd_scale; /* device float[n_seg] or NULL (all 1)                           */
+  float* avg;                /* device float[n] or NULL: the averaged copy                    */
+  float avg_weight;          /* 1 - decay, rounded to fp32 once on the host; in (0, 1]        */
+  int32_t avg_start;         /* >= 1: the applied step whose result starts the average        */
+} pca_optim_groups;
+
+/* Per element i of segment s (segment s is [seg_end[s-1], seg_end[s]), the first starts at 0):
+ *   lr_e = lr * seg_lr_scale[s] (lr: the table entry or o->lr), wd_e = weight_decay * seg_wd_scale[s];
+ *   g' = g * (grad_scale * clip).  Coupled: gi = g' + wd_e * w.  Decoupled: gi = g' and w is first
+ *   multiplied by (1 - lr_e * wd_e).  Moments, bias correction by applied steps and
+ *   w -= (lr_e / bc1) * (m / denom) as pca_adam_step_ex.  A segment with seg_lr_scale == 0 keeps its
+ *   w bit for bit; its moments still move (a torch group with lr = 0).
+ * avg: with a = t - state->skipped, the applied-step number of this launch (this launch counted):
+ *   a <= avg_start: avg[i] = w_new; a > avg_start: avg[i] += avg_weight * (w_new - avg[i]).  A
+ *   skipped step leaves avg bit for bit and does not count.  The launch keeps no device state of
+ *   its own: a comes from step_count_dev[0] and state->skipped.
+ * Clip, skip, table, zero_grad, the state words, the ticket and the publication of
+ *   step_count_dev[0] are pca_adam_step_ex's; partials == NULL is legal under the same condition.
+ * Rounding: with decoupled == 0 and n_seg == 0, avg NULL or not, param, exp_avg, exp_avg_sq, the
+ *   step words and the state words are pca_adam_step_ex's bit for bit.
+ * seg_end_host: a host mirror of seg_end (host int64[n_seg]; unused with n_seg == 0), so that the
+ *   table is checked without a copy from the device.
+ * PCA_EINVAL without a launch: gr NULL; n_seg outside 0..256; a table that is not strictly
+ *   ascending from above 0 or does not end at n; avg_weight outside (0, 1] or avg_start < 1
+ *   (both checked whether or not avg is given). */
+int pca_adam_step_groups(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                         const pca_optim_cfg* o, const double* partials, int n_partials,
+                         const float* lr_table, int64_t lr_table_len, int32_t* step_count_dev,
+                         pca_optim_state* state_dev, int zero_grad, const pca_optim_groups* gr,
+                         const int64_t* seg_end_host, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Whole-model engine: the train / eval step of Code/settransformer.py:100-108  *
  * for the ST classifier of Code/models.py:13-44, enqueued by ONE call (so a    *

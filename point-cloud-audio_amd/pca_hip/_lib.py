@@ -53,6 +53,12 @@ class OptimState(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class OptimGroups(C.Structure):
+    _fields_ = [("decoupled", C.c_int32), ("n_seg", C.c_int32), ("seg_end", C.c_void_p),
+                ("seg_lr_scale", C.c_void_p), ("seg_wd_scale", C.c_void_p), ("avg", C.c_void_p),
+                ("avg_weight", C.c_float), ("avg_start", C.c_int32)]
+
+
 class PcaFrameAug(C.Structure):
     _fields_ = [("jitter", C.c_int32), ("gain_db", C.c_float), ("win_lengths", C.c_void_p),
                 ("n_win", C.c_int32), ("norm_mode", C.c_int32), ("seed", C.c_uint64),
@@ -192,6 +198,9 @@ SIGNATURES = {
     "pca_grad_sumsq": (C.c_int, [c_fp, C.c_int64, c_vp, C.c_int, c_vp]),
     "pca_adam_step_ex": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int64, C.POINTER(OptimCfg), c_vp,
                                    C.c_int, c_fp, C.c_int64, c_vp, c_vp, C.c_int, c_vp]),
+    "pca_adam_step_groups": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int64, C.POINTER(OptimCfg), c_vp,
+                                       C.c_int, c_fp, C.c_int64, c_vp, c_vp, C.c_int,
+                                       C.POINTER(OptimGroups), c_i64p, c_vp]),
     "pca_st_param_count": (C.c_int64, [C.POINTER(StConfig)]),
     "pca_st_bucket_split": (C.c_int64, [C.POINTER(StConfig)]),
     "pca_st_ws_bytes": (C.c_size_t, [C.POINTER(StConfig), C.c_int]),

@@ -196,6 +196,54 @@ def _lr_table(lr_schedule, schedule_steps) -> Optional[torch.Tensor]:
     return table
 
 
+def no_decay_groups() -> list:
+    """The usual ``Trainer(param_groups=)`` preset: no weight decay on the biases, on the inducing
+    points ``enc.*.I`` and on the seed ``dec.0.S``; every rate multiplier 1."""
+    return [(r"\.bias$", 1.0, 0.0), (r"\.I$", 1.0, 0.0), (r"\.S$", 1.0, 0.0)]
+
+
+def resolve_param_groups(model, param_groups) -> dict:
+    """``param_groups``, a sequence of (regex, lr_scale, wd_scale), against the state_dict keys of
+    ``model`` (``re.search``; the first match wins, an unmatched tensor gets (1, 1)) as segments of the
+    flat parameter vector: adjacent tensors with equal scales are one segment.  Returns ``seg_end``
+    (ascending ints, the last is the parameter count), ``lr_scale`` and ``wd_scale`` (one float per
+    segment) and ``tensors`` ({key: (lr_scale, wd_scale)}).  A pattern that matches no tensor raises
+    and names the pattern."""
+    import re
+    model = getattr(model, "module", model)
+    groups = [(str(pat), float(ls), float(ws)) for pat, ls, ws in param_groups]
+    for pat, ls, ws in groups:
+        if not (math.isfinite(ls) and math.isfinite(ws)) or ls < 0.0 or ws < 0.0:
+            raise ValueError(f"param_groups: {pat!r} has lr_scale={ls}, wd_scale={ws}; both must be "
+                             "finite and >= 0")
+    used = [False] * len(groups)
+    tensors, seg_end, lr_scale, wd_scale = {}, [], [], []
+    off = 0
+    for key, p in model.state_dict().items():
+        scales = (1.0, 1.0)
+        for gi, (pat, ls, ws) in enumerate(groups):
+            if re.search(pat, key):
+                scales = (ls, ws)
+                used[gi] = True
+                break
+        tensors[key] = scales
+        off += p.numel()
+        if seg_end and (lr_scale[-1], wd_scale[-1]) == scales:
+            seg_end[-1] = off
+        elif p.numel():
+            seg_end.append(off)
+            lr_scale.append(scales[0])
+            wd_scale.append(scales[1])
+    # a pattern shadowed by an earlier one still counts as matching if it matches a key at all
+    for gi, (pat, _, _) in enumerate(groups):
+        if not used[gi] and not any(re.search(pat, k) for k in tensors):
+            raise ValueError(f"param_groups: the pattern {pat!r} matches no tensor of the model")
+    if len(seg_end) > 256:
+        raise ValueError(f"param_groups resolve to {len(seg_end)} segments; pca_adam_step_groups "
+                         "takes at most 256")
+    return dict(seg_end=seg_end, lr_scale=lr_scale, wd_scale=wd_scale, tensors=tensors)
+
+
 class STEngine:
     """Forward / train-step of an ``models.ST`` through the pca_st_* entry points."""
 
@@ -256,11 +304,23 @@ class STEngine:
         assert tuple(lengths.shape) == (B,), lengths.shape
         return lengths.data_ptr()
 
+    def _params_ptr(self, params: Optional[torch.Tensor]) -> int:
+        """The weights a forward reads: the model's flat vector, or ``params`` in its place."""
+        if params is None:
+            return self.flat.data_ptr()
+        assert params.is_cuda and params.dtype == torch.float32 and params.is_contiguous()
+        assert params.device == self.dev and tuple(params.shape) == tuple(self.flat.shape), params.shape
+        assert params.data_ptr() % 16 == 0, "params must be 16-byte aligned, as the model's vector is"
+        return params.data_ptr()
+
     def forward(self, X: torch.Tensor, lengths: Optional[torch.Tensor] = None,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                out: Optional[torch.Tensor] = None,
+                params: Optional[torch.Tensor] = None) -> torch.Tensor:
         """lengths (optional, device int32[B]): valid points per set of a padded batch.
         out (optional, device float32 [B * k, C], contiguous): where the logits go instead of the
-        engine's own buffer (e.g. a slice of the buffer that holds a whole pass)."""
+        engine's own buffer (e.g. a slice of the buffer that holds a whole pass).
+        params (optional, flat device float32 vector of the engine's size): the weights to use in place
+        of the model's own (e.g. ``Trainer.averaged``)."""
         assert X.is_cuda and X.dtype == torch.float32 and X.is_contiguous()
         assert tuple(X.shape) == (self.cfg.B, self.cfg.N, self.cfg.din), X.shape
         if out is None:
@@ -268,20 +328,22 @@ class STEngine:
         else:
             assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
             assert tuple(out.shape) == tuple(self.logits.shape), out.shape
-        check(lib().pca_st_forward(C.byref(self.cfg), self.flat.data_ptr(), X.data_ptr(),
+        check(lib().pca_st_forward(C.byref(self.cfg), self._params_ptr(params), X.data_ptr(),
                                    self._len_ptr(lengths, self.cfg.B), out.data_ptr(),
                                    self.ws.data_ptr(), self._stream()),
               "pca_st_forward")
         return out
 
     def attention(self, X: torch.Tensor, lengths: Optional[torch.Tensor] = None, want_key: bool = True,
-                  want_attn: bool = True, key_out: Optional[torch.Tensor] = None):
+                  want_attn: bool = True, key_out: Optional[torch.Tensor] = None,
+                  params: Optional[torch.Tensor] = None):
         """(logits, attn, key) of one inference call (pca_st_pool_attention): the logits ``forward``
         returns, bit for bit, the pooling attention attn [B, k, h, N] of dec.0 (modules.PMA.attention) and
         key [B, N], its mean over seeds and heads (what pca_hip.select_points sorts by).  attn / key are
         None without ``want_attn`` / ``want_key``.  The tensors are the engine's own buffers, overwritten
         by the next call; ``key_out`` (device float32 [B, N], contiguous) receives the key instead.
-        fp32 whatever the engine's mode; not differentiable.  Needs an engine built with training=False."""
+        fp32 whatever the engine's mode; not differentiable.  Needs an engine built with training=False.
+        ``params``: as in ``forward``."""
         if self.training:
             raise _lib.PcaHipError("STEngine.attention needs an engine built with training=False")
         assert X.is_cuda and X.dtype == torch.float32 and X.is_contiguous()
@@ -303,7 +365,7 @@ class STEngine:
             key = self._key if key_out is None else key_out
             assert key.is_cuda and key.dtype == torch.float32 and key.is_contiguous()
             assert tuple(key.shape) == (cfg.B, cfg.N), key.shape
-        check(L.pca_st_pool_attention(C.byref(cfg), self.flat.data_ptr(), X.data_ptr(),
+        check(L.pca_st_pool_attention(C.byref(cfg), self._params_ptr(params), X.data_ptr(),
                                       self._len_ptr(lengths, cfg.B), self.logits.data_ptr(),
                                       None if attn is None else attn.data_ptr(),
                                       None if key is None else key.data_ptr(),
@@ -357,7 +419,10 @@ class Trainer:
                  shuffle: bool = True, process_group=None, keep_grads: bool = False,
                  overlap: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_schedule=None,
-                 schedule_steps: Optional[int] = None, label_smoothing: float = 0.0):
+                 schedule_steps: Optional[int] = None, label_smoothing: float = 0.0,
+                 decoupled_weight_decay: bool = False, param_groups=None,
+                 average_decay: Optional[float] = None, average_start: int = 1,
+                 eval_weights: str = "model"):
         """label_smoothing: eps in [0, 1) of the loss's targets.  A dataset with ``soft_targets``
         (dataset.ESC_wave_pc(..., mix_targets=True)) makes the step train on mixed labels: the frame
         launch writes the second label and the label weight of every slot into buffers the Trainer
@@ -369,7 +434,17 @@ class Trainer:
         changes neither parameters nor moments.  lr_schedule: the learning rate per step (step 1
         first; the last entry holds from there on) as a sequence of floats, or a callable
         step -> lr with ``schedule_steps``; it lives in a device table, so a captured step follows it
-        without a re-capture.  All three at their defaults: the plain pca_adam_step launch."""
+        without a re-capture.  All three at their defaults: the plain pca_adam_step launch.
+        decoupled_weight_decay: torch.optim.AdamW's decay, on the weights themselves, instead of the
+        coupled L2 of torch.optim.Adam.  param_groups: a sequence of (regex, lr_scale, wd_scale) matched
+        with ``re.search`` against each tensor's state_dict key, first match wins (``no_decay_groups()``
+        is the usual preset; ``lr_scale`` 0 freezes a tensor).  average_decay (in [0, 1)): keep an
+        exponential moving average of the weights in ``averaged``, a flat device vector updated inside
+        the step from applied step ``average_start`` on (a copy of the weights up to it); the same on
+        every rank.  Any of the four makes the optimiser launch pca_adam_step_groups, still one launch;
+        none of them: the step is enqueued as before.
+        eval_weights: which weights the held-out pass of ``fit`` scores, "model" (default), "averaged"
+        (needs ``average_decay``) or "both"; also an attribute, read when ``fit`` is called."""
         self.ds = dataset
         self.label_smoothing = float(label_smoothing)
         if not 0.0 <= self.label_smoothing < 1.0:
@@ -441,15 +516,48 @@ class Trainer:
                 if self.max_grad_norm is not None or self.skip_nonfinite:
                     self.norm_partials = torch.zeros(int(lib().pca_grad_sumsq_partials(n)),
                                                      dtype=torch.float64, device=self.dev)
+        # AdamW, per-tensor groups, the averaged copy: any of them selects pca_adam_step_groups
+        self.decoupled = bool(decoupled_weight_decay)
+        self.average_decay = None if average_decay is None else float(average_decay)
+        self.average_start = int(average_start)
+        if self.average_decay is not None and not 0.0 <= self.average_decay < 1.0:
+            raise ValueError(f"average_decay must be in [0, 1), got {average_decay}")
+        if self.average_start < 1:
+            raise ValueError(f"average_start must be >= 1, got {average_start}")
+        self.groups = None if param_groups is None else resolve_param_groups(model, param_groups)
+        self._groups_on = (self.decoupled or self.groups is not None
+                           or self.average_decay is not None)
+        self.averaged = self._seg_end = self._seg_lr = self._seg_wd = self._seg_end_host = None
+        if self._groups_on:
+            with torch.cuda.device(self.dev):
+                if self.optim_state is None:
+                    self.optim_state = torch.zeros(8, dtype=torch.int32, device=self.dev)
+                if self.groups is not None:
+                    ends = self.groups["seg_end"]
+                    assert ends[-1] == n, (ends[-1], n)
+                    self._seg_end_host = (C.c_int64 * len(ends))(*ends)
+                    self._seg_end = torch.tensor(ends, dtype=torch.int64).to(self.dev)
+                    self._seg_lr = torch.tensor(self.groups["lr_scale"], dtype=torch.float64) \
+                        .to(torch.float32).to(self.dev)
+                    self._seg_wd = torch.tensor(self.groups["wd_scale"], dtype=torch.float64) \
+                        .to(torch.float32).to(self.dev)
+                if self.average_decay is not None:
+                    # up to ``average_start`` the step overwrites it with the weights: no stale start
+                    self.averaged = self.eng.flat.clone()
         self._cursor_mode = callable(getattr(dataset, "batch_seq", None))
         self._k = 0                       # optimiser steps issued so far (host copy)
         self.g0 = self.g1 = self.g2 = None
         self._draw_frozen = None          # see _capture
         self._evaluator = None            # fit's held-out pass, built once
+        self._evaluator_avg = None        # the same pass on ``averaged``
+        self.eval_weights = eval_weights
+        self._check_eval_weights()
         self.indices = ShardedIndexStream(len(dataset), self.B, self.rank, self.world, seed,
                                           shuffle, self.dev)
         if self.world > 1:      # identical initial weights on every rank (rank 0's)
             dist.broadcast(self.eng.flat, src=0, group=self.pg)
+            if self.averaged is not None:
+                self.averaged.copy_(self.eng.flat)
 
     # ---- how the gradients are exchanged ---------------------------------------------
     def set_exchange(self, form: str) -> None:
@@ -559,6 +667,28 @@ class Trainer:
 
     def _seg2(self):     # Adam over the flat vector
         e = self.eng
+        if self._groups_on:
+            # [sum of squares ->] pca_adam_step_groups: the guarded step with AdamW, the segment table
+            # and the averaged copy, in the one launch at the same place
+            L, n, st = lib(), e.flat.numel(), e._stream()
+            part, npart = None, 0
+            if self.norm_partials is not None:
+                part, npart = self.norm_partials.data_ptr(), self.norm_partials.numel()
+                check(L.pca_grad_sumsq(e.grads.data_ptr(), n, part, npart, st), "pca_grad_sumsq")
+            o = _lib.OptimCfg(self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                              1.0 / self.world, self.max_grad_norm or 0.0, int(self.skip_nonfinite))
+            ptr = lambda t: None if t is None else t.data_ptr()
+            gr = _lib.OptimGroups(
+                int(self.decoupled), 0 if self.groups is None else len(self.groups["seg_end"]),
+                ptr(self._seg_end), ptr(self._seg_lr), ptr(self._seg_wd), ptr(self.averaged),
+                1.0 if self.average_decay is None else 1.0 - self.average_decay, self.average_start)
+            tab = self.lr_table
+            check(L.pca_adam_step_groups(e.flat.data_ptr(), e.grads.data_ptr(), self.m.data_ptr(),
+                                         self.v.data_ptr(), n, C.byref(o), part, npart, ptr(tab),
+                                         0 if tab is None else tab.numel(), self.step_count.data_ptr(),
+                                         self.optim_state.data_ptr(), int(not self.keep_grads),
+                                         C.byref(gr), self._seg_end_host, st), "pca_adam_step_groups")
+            return
         if self._optim_on:
             # [sum of squares ->] guarded Adam: both launches where the plain one sits, i.e. after the
             # all-reduce / the join, so every rank clips the same averaged gradient and skips alike
@@ -588,8 +718,10 @@ class Trainer:
         s = torch.cuda.Stream(self.dev)
         s.wait_stream(torch.cuda.current_stream(self.dev))
         live = (self.eng.flat, self.m, self.v, self.step_count, self.eng.stats)
-        if self._optim_on:
+        if self.optim_state is not None:
             live += (self.optim_state,)
+        if self.averaged is not None:
+            live += (self.averaged,)
         snap = tuple(t.clone() for t in live)
         with torch.cuda.stream(s):
             self._seg0(); self._seg1(); self._seg2()
@@ -701,15 +833,40 @@ class Trainer:
         step), clipped and skipped (steps, since the start of the run).  The norm is that of the
         gradient Adam used, before clipping; 0 when neither clipping nor skipping is on.  One host
         read; ``reset`` clears the mean's accumulator."""
-        if not self._optim_on:
+        if self.optim_state is None:
             raise _lib.PcaHipError("read_optim_stats: this Trainer was built without max_grad_norm, "
-                                   "skip_nonfinite or lr_schedule")
+                                   "skip_nonfinite, lr_schedule, decoupled_weight_decay, param_groups "
+                                   "or average_decay")
         f = self._optim_fields()
         if reset:
             self.optim_state[4:7].zero_()
         return dict(grad_norm_mean=f["norm_sum"] / f["norm_count"] if f["norm_count"] else 0.0,
                     last_grad_norm=f["last_norm"], lr=f["last_lr"], clipped=f["clipped"],
                     skipped=f["skipped"])
+
+    def _check_eval_weights(self) -> str:
+        if self.eval_weights not in ("model", "averaged", "both"):
+            raise ValueError(f"eval_weights must be 'model', 'averaged' or 'both', got "
+                             f"{self.eval_weights!r}")
+        if self.eval_weights != "model" and self.average_decay is None:
+            raise ValueError(f"eval_weights={self.eval_weights!r} needs a Trainer built with "
+                             "average_decay")
+        return self.eval_weights
+
+    def averaged_state_dict(self) -> dict:
+        """``averaged`` under the model's state_dict keys, as CPU tensors of the parameters' shapes (one
+        host sync): what ``load_state_dict`` of a second model, or ``runfiles.save_run(state_dict=)``,
+        takes to use or write the averaged weights in the reference's layout."""
+        if self.averaged is None:
+            raise _lib.PcaHipError("averaged_state_dict: this Trainer was built without average_decay")
+        model = getattr(self.eng.model, "module", self.eng.model)
+        host = self.averaged.detach().to("cpu")
+        out, off = {}, 0
+        for key, p in model.state_dict().items():
+            out[key] = host[off:off + p.numel()].view(p.shape).clone()
+            off += p.numel()
+        assert off == host.numel()
+        return out
 
     # ---- exact resume ----------------------------------------------------------------
     def state_dict(self) -> dict:
@@ -718,12 +875,16 @@ class Trainer:
         permutation are not stored: ``load_state_dict`` re-derives them from (seed, epoch)."""
         cpu = lambda t: t.detach().to("cpu").clone()
         optim = {}
-        if self._optim_on:
+        if self.optim_state is not None:
             # the state words as they are (norm_sum keeps its fp64 bits) next to the readable fields
             optim = dict(optim=dict(self._optim_fields(), words=cpu(self.optim_state),
                                     lr_schedule=None if self.lr_table is None else cpu(self.lr_table),
                                     max_grad_norm=self.max_grad_norm,
                                     skip_nonfinite=self.skip_nonfinite))
+        if self._groups_on:
+            optim["optim"].update(self._groups_options())
+            if self.averaged is not None:
+                optim["avg"] = cpu(self.averaged)
         return dict(format=1, B=self.B, N=self.N, mode=int(self.eng.cfg.mode), world=int(self.world),
                     flat=cpu(self.eng.flat), m=cpu(self.m), v=cpu(self.v),
                     step_count=int(self.step_count[0].item()), k=int(self._k),
@@ -748,8 +909,10 @@ class Trainer:
         self._check_optim(state.get("optim"))
         torch.cuda.synchronize(self.dev)
         self.g0 = self.g1 = self.g2 = None
-        if self._optim_on:
+        if self.optim_state is not None:
             self.optim_state.copy_(state["optim"]["words"])
+        if self.averaged is not None:
+            self.averaged.copy_(state["avg"])
         # into the vectors the engines (and the module's parameters) are views of, never a re-bind
         self.eng.flat.copy_(state["flat"])
         self.m.copy_(state["m"])
@@ -773,14 +936,40 @@ class Trainer:
                 else int(state["draw"])
         self._draw_frozen = None
 
+    def _groups_options(self) -> dict:
+        """The options of pca_adam_step_groups as a checkpoint stores them: plain values and CPU tensors
+        (the segment table with its scales as the launch reads them, None without param_groups)."""
+        cpu = lambda t: None if t is None else t.detach().to("cpu").clone()
+        return dict(decoupled=self.decoupled, seg_end=cpu(self._seg_end), seg_lr_scale=cpu(self._seg_lr),
+                    seg_wd_scale=cpu(self._seg_wd), average_decay=self.average_decay,
+                    average_start=self.average_start if self.average_decay is not None else None)
+
     def _check_optim(self, saved: Optional[dict]) -> None:
-        """The checkpoint's optimiser options against this trainer's; a difference raises, naming it."""
+        """The checkpoint's optimiser options against this trainer's; a difference raises, naming it.
+        A checkpoint from before the AdamW / groups / averaging options holds none of them: it is one
+        with all of them off."""
         mine = dict(max_grad_norm=self.max_grad_norm, skip_nonfinite=self.skip_nonfinite)
         theirs = dict(max_grad_norm=None, skip_nonfinite=False) if saved is None else saved
         for name, have in mine.items():
             if theirs[name] != have:
                 raise ValueError(f"checkpoint mismatch: {name} is {theirs[name]} in the checkpoint, "
                                  f"{have} in this trainer")
+        off = dict(decoupled=False, seg_end=None, seg_lr_scale=None, seg_wd_scale=None,
+                   average_decay=None, average_start=None)
+        got = {k: (saved or {}).get(k, v) for k, v in off.items()}
+        want = self._groups_options()
+        for key, name in (("decoupled", "decoupled_weight_decay"), ("average_decay", "average_decay"),
+                          ("average_start", "average_start")):
+            if got[key] != want[key]:
+                raise ValueError(f"checkpoint mismatch: {name} is {got[key]} in the checkpoint, "
+                                 f"{want[key]} in this trainer")
+        for key in ("seg_end", "seg_lr_scale", "seg_wd_scale"):
+            a, b = got[key], want[key]
+            if (a is None) != (b is None) or (a is not None and not (a.shape == b.shape
+                                                                     and torch.equal(a, b))):
+                describe = lambda t: "absent" if t is None else f"{t.numel()} segments {t.tolist()}"
+                raise ValueError(f"checkpoint mismatch: param_groups ({key}) is {describe(a)} in the "
+                                 f"checkpoint, {describe(b)} in this trainer")
         tab = None if saved is None else saved.get("lr_schedule")
         mine_tab = None if self.lr_table is None else self.lr_table.cpu()
         if (tab is None) != (mine_tab is None) or (
@@ -806,12 +995,23 @@ class Trainer:
         ran, test_loss, test_acc, test_topk_acc.  A trainer with max_grad_norm, skip_nonfinite or
         lr_schedule adds grad_norm (mean over the epoch's finite steps), lr (of the epoch's last
         step), clipped_steps and skipped_steps (since the start of the run): one more host read
-        (``read_optim_stats``) and one more line per epoch."""
+        (``read_optim_stats``) and one more line per epoch.
+        ``self.eval_weights`` (``Trainer(eval_weights=)``, or set before the call) says which weights
+        the held-out pass scores.  "model" (default): the model's.
+        "averaged" (needs ``average_decay``): ``averaged``, reported under the same test_* names.
+        "both": the model's as before, and test_avg_loss, test_avg_acc, test_avg_topk_acc from a second
+        ``Evaluator.run`` on ``averaged`` (one more host read per evaluated epoch, one more line)."""
+        eval_weights = self._check_eval_weights()
         spe = self.indices.steps_per_epoch()
-        if test_dataset is not None and (self._evaluator is None
-                                         or self._evaluator.ds is not test_dataset):
+        if test_dataset is not None and eval_weights != "averaged" and (
+                self._evaluator is None or self._evaluator.ds is not test_dataset):
             self._evaluator = Evaluator(self.eng.model, test_dataset, self.B,
                                         int(self.eng.cfg.mode), process_group=self.pg)
+        if test_dataset is not None and eval_weights != "model" and (
+                self._evaluator_avg is None or self._evaluator_avg.ds is not test_dataset):
+            self._evaluator_avg = Evaluator(self.eng.model, test_dataset, self.B,
+                                            int(self.eng.cfg.mode), process_group=self.pg
+                                            ).use_params(self.averaged)
         history = []
         first = self._k // spe
         for epoch in range(first, int(epochs)):
@@ -829,10 +1029,16 @@ class Trainer:
                 log(f"Epoch {epoch}: grad norm {o['grad_norm_mean']:.3f} lr {o['lr']:.3e} clipped "
                     f"{o['clipped']} skipped {o['skipped']}")
             if test_dataset is not None and epoch % eval_every == 0:
-                res = self._evaluator.run()
+                res = (self._evaluator_avg if eval_weights == "averaged" else self._evaluator).run()
                 entry.update(test_loss=res["loss"], test_acc=res["acc"],
                              test_topk_acc=res["topk_acc"])
                 log(f"Epoch {epoch}: test loss {res['loss']:.3f} test acc {res['acc']:.3f}")
+                if eval_weights == "both":
+                    res = self._evaluator_avg.run()
+                    entry.update(test_avg_loss=res["loss"], test_avg_acc=res["acc"],
+                                 test_avg_topk_acc=res["topk_acc"])
+                    log(f"Epoch {epoch}: averaged weights test loss {res['loss']:.3f} test acc "
+                        f"{res['acc']:.3f}")
             history.append(entry)
             if checkpoint_path is not None and self.rank == 0 and (
                     (epoch + 1) % (checkpoint_every or 1) == 0 or epoch + 1 == int(epochs)):
@@ -880,6 +1086,7 @@ class Evaluator:
     def __init__(self, model, dataset, batch_size: int, mode: int = _lib.MODE_F32, topk: int = 5,
                  process_group=None):
         self.ds, self.topk, self.pg = dataset, int(topk), process_group
+        self.params = None                # see use_params
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(process_group) if dist.is_initialized() else 0
         self.n = len(dataset)
@@ -914,6 +1121,16 @@ class Evaluator:
         self.confusion = self.acc[4:4 + self.C * self.C].view(self.C, self.C)
         self.loss_sum = self.acc[4 + self.C * self.C:].view(torch.float64)
 
+    def use_params(self, params: Optional[torch.Tensor]) -> "Evaluator":
+        """Score ``params`` (a flat device float32 vector of the model's size, e.g.
+        ``Trainer.averaged``) in place of the model's own weights from the next ``run()`` on; None goes
+        back to the model's.  The vector is read at ``run()``, so one that keeps being updated is scored
+        as it stands then.  Returns self: ``Evaluator(model, ds, B).use_params(tr.averaged).run()``."""
+        if params is not None and self.engines:
+            self.engines[0][0]._params_ptr(params)          # shape, dtype, device, alignment
+        self.params = params
+        return self
+
     def _enqueue(self) -> None:
         """The whole pass on the current stream: packs, forwards, one metrics call.  No host sync."""
         from .ops import eval_metrics
@@ -924,7 +1141,7 @@ class Evaluator:
                 kw = dict(lengths_out=ln) if ln is not None else {}
                 self.ds.batch(self.idx[done:done + b], out=X,
                               labels_out=self.labels[done:done + b], **kw)
-                eng.forward(X, ln, out=self.logits[done:done + b])
+                eng.forward(X, ln, out=self.logits[done:done + b], params=self.params)
                 done += b
         assert done == self.n_local
         self.acc.zero_()

@@ -67,15 +67,18 @@ def _arch_of(config: Dict) -> str:
     raise ValueError(f"not a Set Transformer run: architecture = {config.get('architecture')!r}")
 
 
-def save_run(model, config: Dict, directory: str, now: Optional[datetime] = None
-             ) -> Tuple[str, str]:
+def save_run(model, config: Dict, directory: str, now: Optional[datetime] = None,
+             state_dict: Optional[Dict] = None) -> Tuple[str, str]:
     """Write the weight and config files of a run; returns (pth path, json path).
 
     ``model`` may be an ``ST`` or its ``nn.DataParallel`` wrapper; the file always holds the
-    wrapped key names, like the reference's."""
+    wrapped key names, like the reference's.  ``state_dict``: the weights to write instead of the
+    model's own, under the model's keys (``Trainer.averaged_state_dict()``)."""
     arch = _arch_of(config)
-    sd = model.state_dict()
-    if not isinstance(model, nn.DataParallel):
+    sd = model.state_dict() if state_dict is None else dict(state_dict)
+    wrapped = isinstance(model, nn.DataParallel) if state_dict is None else \
+        all(k.startswith("module.") for k in sd)
+    if not wrapped:
         sd = {"module." + k: v for k, v in sd.items()}
     sd = {k: v.detach().to("cpu").contiguous() for k, v in sd.items()}
     stamp = str(now or datetime.now())
