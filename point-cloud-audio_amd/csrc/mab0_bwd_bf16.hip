@@ -126,6 +126,7 @@ __global__ __launch_bounds__(256, 1) void k_mab0_bwd(const Mab0BwdArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, g = lane >> 4;
   const int b = blockIdx.x, sp = blockIdx.y;
+  PCA_MID_STAMPS_DECL;       // (phase stamps of the fused mid chain: diagnostic builds only)
   const int per = (int)(((int64_t)(a.N + 127) / 128 + a.S - 1) / a.S) * 128;
   const int n_lo = sp * per, n_hi = (n_lo + per < a.N) ? n_lo + per : a.N;
   // variable-size sets: points at and beyond len have P = 0 (so dS = 0 and their dX rows are
@@ -148,9 +149,8 @@ __global__ __launch_bounds__(256, 1) void k_mab0_bwd(const Mab0BwdArgs a) {
   bool fuse = false;
   if constexpr (RP == 64) fuse = a.fuse_mid != 0;
   if constexpr (RP == 64) if (fuse) {
-    // the shared images and the first X tile are in flight while the set's mid chain runs: Wk1^T /
-    // Wv1^T are staged where the X and dS tiles will live (free until the main loop), the chain's small
-    // images behind the statistics, and dT / dT^T / Delta / LSE land where the loop reads them
+    // the shared images and the first X tile are in flight while the set's mid chain runs: the chain's
+    // small images live behind the statistics, and dT / dT^T / Delta / LSE land where the loop reads them
     constexpr int NA = RP * 16 / 256, NB2 = DK * (RP / 8) / 256;
     bf16x8 g1[NA], g2[NB2];
 #pragma unroll
@@ -165,8 +165,7 @@ __global__ __launch_bounds__(256, 1) void k_mab0_bwd(const Mab0BwdArgs a) {
     }
     if (n_lo + wave * 32 < n_hi) fetch_tile(n_lo + wave * 32);
     char* const tail = reinterpret_cast<char*>(sDel + RP);
-    const MidBwdLds m{tail, tail + 16 * 256, tail + 2 * 16 * 256, sX, sDS};
-    mid_bwd_body<false>(a.mid, b, m, sp == 0, MidSinkWide{sdT, sdTt, sLSE, sDel});
+    mid_bwd_body<false>(a.mid, b, mid_bwd_lds(tail), sp == 0, MidSinkWide{sdT, sdTt, sLSE, sDel} PCA_MID_STAMPS_ARG);
 #pragma unroll
     for (int e = 0; e < NA; ++e) {
       const int c = tid + 256 * e, row = c >> 4, ch = c & 15;
@@ -226,6 +225,7 @@ __global__ __launch_bounds__(256, 1) void k_mab0_bwd(const Mab0BwdArgs a) {
   constexpr float LN2 = 0.6931471805599453f;
 
   if (!fuse && n_lo + wave * 32 < n_hi) fetch_tile(n_lo + wave * 32);
+  PCA_MID_STAMP(6);
   for (int n0 = n_lo + wave * 32; n0 < n_hi; n0 += 128) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -402,6 +402,7 @@ __global__ __launch_bounds__(256, 1) void k_mab0_bwd(const Mab0BwdArgs a) {
   float* out = a.slabs + ((int64_t)b * a.S + sp) * a.R * DK;
   for (int i = tid; i < a.R * DK; i += 256)
     out[i] = s0[i] + s0[RP * DK + i] + s0[2 * RP * DK + i] + s0[3 * RP * DK + i];
+  PCA_MID_STAMPS_WRITE(a.mid, b, sp == 0);
 }
 
 // layer 1 (dk <= 4): mab0_bwd_small_body.hpp; gridDim.y workgroups share the rows of a set.
@@ -567,7 +568,7 @@ int mab0_bf16_bwd_ex(const pca_mab_shape& s, const float* I, const void* X,
       PCA_REQUIRE(Rp == 64, "mab0_bf16_bwd: fused mid chain with %d score rows", Rp);
       a.fuse_mid = 1;
       a.mid = mid_bwd_args(*mid);
-      lds += MID_BWD_SMALL_LDS;       // dKp / dVp / dO_j images of the chain, behind the statistics
+      lds += MID_BWD_SMALL_LDS;       // dKp / dVp / dO_j / dZ images of the chain, behind the statistics
     }
     if (lds < (size_t)4 * Rp * 128 * 4) lds = (size_t)4 * Rp * 128 * 4;     // merge slabs
     allow_lds160<k_mab0_bwd<64, false>, k_mab0_bwd<64, true>, k_mab0_bwd<32, false>, k_mab0_bwd<32, true>>();

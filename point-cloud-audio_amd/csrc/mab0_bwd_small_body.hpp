@@ -10,7 +10,7 @@ namespace pca {
 
 // sink of the mid chain run in the prologue: dT (fp32) and Delta stay in LDS
 constexpr int MID_SMALL_FUSE_IMG = (64 * 4 + 64) * 4;       // dTf [64][4] + Delta [64]
-constexpr int MID_SMALL_FUSE_LDS = MID_SMALL_FUSE_IMG + MID_BWD_SMALL_LDS + 2 * MID_BWD_W_LDS;
+constexpr int MID_SMALL_FUSE_LDS = MID_SMALL_FUSE_IMG + MID_BWD_SMALL_LDS;
 struct MidSinkSmall {
   float *sdTf, *sDel;       // [64][4], [64]
   __device__ __forceinline__ void dTb(int, int, int, bf16x4) const {}
@@ -55,6 +55,7 @@ __device__ __forceinline__ void mab0_bwd_small_body(const Mab0SmallArgs& a, int 
   if (a.lengths != nullptr) len = a.lengths[b] < N ? a.lengths[b] : N;
   float xr[4096 / NT];
   float lse, del;
+  PCA_MID_STAMPS_DECL;       // (phase stamps of the fused mid chain: diagnostic builds only)
   if constexpr (MID) {
     // the first chunk of points, G and the statistics are in flight while the mid chain runs
 #pragma unroll
@@ -64,9 +65,7 @@ __device__ __forceinline__ void mab0_bwd_small_body(const Mab0SmallArgs& a, int 
     float* const sdTf = reinterpret_cast<float*>(smid);
     float* const sDelta = sdTf + 64 * 4;
     char* const base = smid + MID_SMALL_FUSE_IMG;
-    const MidBwdLds m{base, base + 16 * 256, base + 2 * 16 * 256, base + MID_BWD_SMALL_LDS,
-                      base + MID_BWD_SMALL_LDS + MID_BWD_W_LDS};
-    mid_bwd_body<true, NT>(a.mid, b, m, y == 0, MidSinkSmall{sdTf, sDelta});
+    mid_bwd_body<true, NT>(a.mid, b, mid_bwd_lds(base), y == 0, MidSinkSmall{sdTf, sDelta} PCA_MID_STAMPS_ARG);
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < 4; ++c) dt[c] = c < dk ? sdTf[r * 4 + c] : 0.f;
@@ -81,6 +80,7 @@ __device__ __forceinline__ void mab0_bwd_small_body(const Mab0SmallArgs& a, int 
     del = a.Delta[(int64_t)b * a.Rp + r];
     if (len > 0) fetch_points<NT>(X + (int64_t)b * N * dk, len < CH ? len : CH, dk, xr);
   }
+  PCA_MID_STAMP(6);
   for (int n0 = 0; n0 < len; n0 += CH) {
     const int cn = (len - n0 < CH) ? len - n0 : CH;
     // [pair of points][component][2] (as k_mab0_attn_small): two points per packed-fp32 instruction;
@@ -119,6 +119,7 @@ __device__ __forceinline__ void mab0_bwd_small_body(const Mab0SmallArgs& a, int 
       else atomicAdd(&a.DG[(row0 + tid) * dk + c], v);
     }
   }
+  if constexpr (MID) PCA_MID_STAMPS_WRITE(a.mid, b, y == 0);
 }
 
 // The bf16 weight-gradient list of a step (placed: bwd_defer_ride) and the layer-1 few-queries backward with

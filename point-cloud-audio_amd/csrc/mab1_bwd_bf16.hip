@@ -687,6 +687,17 @@ int kv_dh_launch(const float* dKp, const float* dVp, const float* Wk, const floa
   return check_launch("k_kv_dh");
 }
 
+// Fused mode (m = 16): consecutive tiles per workgroup - the largest divisor of tiles_per_set that still
+// leaves >= 256 workgroups (without the dX stage the kernel needs 72 KiB of LDS, two workgroups per CU:
+// 512).  tiles_per_set / this is the number of dKp / dVp partials per set the mid chain sums.
+static int fused_tiles_per_wg(int B, int tiles_per_set, bool want_dx) {
+  const int min_wg = want_dx ? 256 : 512;
+  int tpw = 1;
+  for (int c = 1; c <= tiles_per_set; ++c)
+    if (tiles_per_set % c == 0 && (int64_t)B * tiles_per_set / c >= min_wg) tpw = c;
+  return tpw;
+}
+
 // dQ -> dX [B, nq, dq] (written; may be null), dK -> dH [B, nk, d] (written or accumulated)
 int mab1_bf16_bwd_ex(const pca_mab_shape& s, const void* X, const float* H,
                      const pca_mab_params& p, const void* saved, const void* dY, void* dX,
@@ -749,13 +760,7 @@ int mab1_bf16_bwd_ex(const pca_mab_shape& s, const void* X, const float* H,
   int rc;
   const bool fuse = MI == 16;
   if (fuse) {
-    // consecutive tiles per workgroup: the largest divisor of tiles_per_set that still
-    // leaves >= 256 workgroups
-    // (without the dX stage the kernel needs 72 KiB of LDS: two workgroups per CU)
-    const int min_wg = want_dx ? 256 : 512;
-    int tpw = 1;
-    for (int c = 1; c <= a.tiles_per_set; ++c)
-      if (a.tiles_per_set % c == 0 && (int64_t)a.B * a.tiles_per_set / c >= min_wg) tpw = c;
+    const int tpw = fused_tiles_per_wg(a.B, a.tiles_per_set, want_dx);
     a.tpw = tpw;
     a.dKpG = w.dKpPart;
     a.dVpG = w.dVpPart;
@@ -865,3 +870,12 @@ int mab1_bf16_bwd_ex(const pca_mab_shape& s, const void* X, const float* H,
 }
 
 }  // namespace pca
+
+// For tests, outside the documented ABI: the number of dKp / dVp partials per set that the many-queries
+// backward of an ISAB (m = 16) leaves for the mid chain, B sets of N points; want_dx: the layer also
+// returns dX (every layer but the first).
+extern "C" int pca_debug_mid_nparts(int B, int N, int want_dx) {
+  if (B <= 0 || N <= 0) return -1;
+  const int tiles = (int)pca::cdiv(N, pca::TP);
+  return tiles / pca::fused_tiles_per_wg(B, tiles, want_dx != 0);
+}

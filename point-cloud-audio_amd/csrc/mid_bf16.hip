@@ -17,6 +17,10 @@
 #include "mid_bwd_body.hpp"
 
 #include <math.h>
+#ifdef PCA_DEBUG_CLOCKS
+#include <stdio.h>
+#include <stdlib.h>
+#endif
 
 namespace pca {
 
@@ -215,18 +219,39 @@ __global__ __launch_bounds__(256) void k_mid_fwd(const MidFwdArgs a) {
 
 template <bool SMALL>
 __global__ __launch_bounds__(256) void k_mid_bwd(const MidBwdArgs a) {
-  __shared__ __attribute__((aligned(16))) char sKVO[MID_BWD_SMALL_LDS];   // dKp, dVp, per-wave dO_j
-  __shared__ __attribute__((aligned(16))) char sWk[MID_BWD_W_LDS];
-  __shared__ __attribute__((aligned(16))) char sWv[MID_BWD_W_LDS];
+  __shared__ __attribute__((aligned(16))) char sKVO[MID_BWD_SMALL_LDS];   // dKp, dVp, per-wave dO_j, dZ
   const int b = blockIdx.x, tid = threadIdx.x;
   if (a.zero_ptr != nullptr)
     for (int i = blockIdx.x * 256 + tid; i < a.zero_n; i += gridDim.x * 256) a.zero_ptr[i] = 0.f;
   // one workgroup per set on half the CUs: the chain (mid_bwd_body.hpp) is purely latency-bound
-  const MidBwdLds m{sKVO, sKVO + 16 * ROWB, sKVO + 2 * 16 * ROWB, sWk, sWv};
-  mid_bwd_body<SMALL>(a, b, m, true, MidSinkGlobal{a, b});
+  mid_bwd_body<SMALL>(a, b, mid_bwd_lds(sKVO), true, MidSinkGlobal{a, b});
 }
 
 }  // namespace
+
+#ifdef PCA_DEBUG_CLOCKS
+// diagnostic build: the phase stamps of the mid chain in the prologue of its carrying kernel (set PCA_DBG_WG
+// of the last launch; mid_bwd_body.hpp names the phases) are printed at exit, in microseconds from the entry
+long long* mid_debug_clock_buffer(int which) {
+  static long long* buf[2] = {nullptr, nullptr};
+  if (buf[which] == nullptr) {
+    (void)hipHostMalloc(reinterpret_cast<void**>(&buf[which]), 8 * sizeof(long long), 0);
+    for (int i = 0; i < 8; ++i) buf[which][i] = 0;
+    struct P {
+      static void dump(int w) {
+        const long long* b = buf[w];
+        const long long t0 = b[0] & 0xffffffffffffLL;
+        fprintf(stderr, "mid chain stamps, %s (phase:us):", w == 0 ? "k_mab0_bwd<64, .>" : "small carrier");
+        for (int i = 0; i < 7; ++i) fprintf(stderr, " %lld:%.2f", b[i] >> 48, ((b[i] & 0xffffffffffffLL) - t0) / 100.0);
+        fprintf(stderr, "\n");
+      }
+    };
+    if (which == 0) atexit([] { P::dump(0); });
+    else atexit([] { P::dump(1); });
+  }
+  return buf[which];
+}
+#endif
 
 int mid_fwd_launch(const MidFwdLaunch& L, hipStream_t st) {
   MidFwdArgs a{};

@@ -228,6 +228,7 @@ SIGNATURES = {
 # exported for tests and experiments, outside the documented ABI (not in include/pca_hip.h)
 DEBUG_SIGNATURES = {
     "pca_debug_tail_plan": (C.c_int, [c_i64p, C.c_int, c_i64p, C.c_int]),
+    "pca_debug_mid_nparts": (C.c_int, [C.c_int, C.c_int, C.c_int]),
 }
 
 _lib = None
