@@ -20,10 +20,13 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 namespace pca {
 
 namespace {
 
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 constexpr int TP = M1_TP;
 constexpr int NB = M1_NB;
 
@@ -86,36 +89,21 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
   char* sKV = sWqT + (WANT_DX ? D * ROWB : 0);
 
   const int tid = threadIdx.x, lane = tid & 63, wave8 = tid >> 6;
-  const int wave = wave8 & 3, sub = wave8 >> 2;
   const int r = lane & 15, g = lane >> 4;
 #ifdef PCA_DEBUG_CLOCKS
   long long stamp_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
   PCA_STAMP(0);
 
-  {
-    // all chunks of this thread first, then the LDS stores (one round trip, not one per chunk)
-    constexpr int NC = D * (D / 8) / NT;
-    uint4 wo[NC], wq[WANT_DX ? NC : 1];
-#pragma unroll
-    for (int e = 0; e < NC; ++e) {
-      const int c = tid + NT * e, row = c / (D / 8), c16 = c % (D / 8);
-      wo[e] = *reinterpret_cast<const uint4*>(a.WoTP + (int64_t)row * D + c16 * 8);
-      if (WANT_DX) wq[e] = *reinterpret_cast<const uint4*>(a.WqTP + (int64_t)row * D + c16 * 8);
-    }
-#pragma unroll
-    for (int e = 0; e < NC; ++e) {
-      const int c = tid + NT * e, row = c / (D / 8), c16 = c % (D / 8);
-      *reinterpret_cast<uint4*>(sWoT + swz(row, c16, ROWB)) = wo[e];
-      if (WANT_DX) *reinterpret_cast<uint4*>(sWqT + swz(row, c16, ROWB)) = wq[e];
-    }
-  }
-
-  PCA_STAMP(8);
+  // One batch of requests per tile.  On the workgroup's first tile the Wo / Wq image chunks
+  // lead it, on the first tile of a set the K / V images; then the tile's own operands - mask words, dY, the
+  // saved Qp or layer 1's points - which depend on nothing in LDS.  The images are stored to LDS while the
+  // tile is still in flight (vmcnt counts down to the tile's requests, not to zero: lds_barrier()), and
+  // every convert, select and mask sits at the use, not behind its load.
+  constexpr int NC = D * (D / 8) / NT;                       // Wo / Wq chunks per thread
+  constexpr int KVC = (MI * (D / 8) + NT - 1) / NT;          // KpP / VpP / Kt chunks per thread
   const int total_tiles = a.B * a.tiles_per_set;
   int cur_b = -1;
-  if (a.zero_ptr != nullptr)
-    for (int i = blockIdx.x * NT + tid; i < a.zero_n; i += gridDim.x * NT) a.zero_ptr[i] = 0.f;
   // row pitches padded by 8 bytes (40 / 72 instead of 32 / 64): with power-of-two pitches the
   // 16 point rows of a store or transposed read fall on 2 resp. 4 LDS banks repeatedly
   // (SQ_LDS_BANK_CONFLICT was 3x the LDS-active cycles of this kernel); 10 / 18 banks per row
@@ -123,15 +111,6 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
   constexpr int PS = 40, PQ = 72, KVB = 2 * 32 * PS + 2 * 32 * PQ;
   // layer 1: fc_q rows as float4 (w0, w1, w2, bias) behind the per-wave images
   float4* sWq4 = reinterpret_cast<float4*>(sKV + NW * KVB);
-  if (FUSE_WQ) {
-    for (int f = tid; f < D; f += NT)
-      sWq4[f] = float4{a.WqF[f * a.dq], a.dq > 1 ? a.WqF[f * a.dq + 1] : 0.f,
-                       a.dq > 2 ? a.WqF[f * a.dq + 2] : 0.f, a.bqF[f]};
-  }
-  char* myDS = sKV + wave8 * KVB;
-  char* myP = myDS + 32 * PS;
-  char* myQ = myP + 32 * PS;
-  char* myO = myQ + 32 * PQ;
   f32x4 dkp[FUSE_KV ? KS : 1][2], dvp[FUSE_KV ? KS : 1][2];
   if (FUSE_KV) {
 #pragma unroll
@@ -158,28 +137,30 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
   const int t_step = FUSE_KV ? 1 : gridDim.x;
   const int t_last = FUSE_KV ? t_first + a.tpw : total_tiles;
   // (fused mode with 8 waves: two consecutive tiles of the set per pass, one per wave quartet)
-  for (int tile0 = t_first; tile0 < t_last && tile0 < total_tiles; tile0 += t_step * SUBS) {
-    const int tile_id = tile0 + sub;
-    const int b = tile0 / a.tiles_per_set, tile = tile_id - b * a.tiles_per_set;
-    if (b != cur_b) {
-      __syncthreads();
-      for (int c = tid; c < MI * (D / 8); c += NT) {
-        const int row = c / (D / 8), c16 = c % (D / 8);
-        const int64_t src = ((int64_t)b * MI + row) * D + c16 * 8;
-        *reinterpret_cast<uint4*>(sKp + swz(row, c16, ROWB)) =
-            *reinterpret_cast<const uint4*>(a.KpP + src);
-        *reinterpret_cast<uint4*>(sVp + swz(row, c16, ROWB)) =
-            *reinterpret_cast<const uint4*>(a.VpP + src);
-      }
-      for (int c = tid; c < D * MI / 8; c += NT)
-        reinterpret_cast<uint4*>(sKt)[c] =
-            reinterpret_cast<const uint4*>(a.Kt + (int64_t)b * D * MI)[c];
-      cur_b = b;
-    }
-    __syncthreads();
-    PCA_STAMP(1);
-    if (tile_id >= t_last || tile_id >= total_tiles) continue;   // odd count: waves 4..7 idle
-                                                                 // (no barrier below)
+  // The pass over one tile, instantiated twice: for the workgroup's first tile, whose batch the weight images
+  // lead (straight-line code in front of the loop), and for every later one (inside the loop, where only a new
+  // set's K / V images join the tile's requests).  One body in the loop with a run-time `first` had every address
+  // of the weight staging hoisted out of the loop and kept alive through it.
+  auto pass = [&](auto first_c, const int tile0) __attribute__((always_inline)) {
+    constexpr bool first = decltype(first_c)::value;
+    // the thread index anew in each copy (rederive() of set128_fwd.hip): what is derived from it - lane, r, g,
+    // the swizzled LDS offsets - is otherwise shared between the two copies and hoisted out of the loop, kept
+    // alive across the first tile and spilled next to its requests
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    int lane = tid & 63, wave8 = tid >> 6, wave = wave8 & 3, sub = wave8 >> 2;
+    int r = lane & 15, g = lane >> 4;
+    char* myDS = sKV + wave8 * KVB;
+    char* myP = myDS + 32 * PS;
+    char* myQ = myP + 32 * PS;
+    char* myO = myQ + 32 * PQ;
+    const int b = tile0 / a.tiles_per_set;
+    // odd count: waves 4..7 have no tile; they request the quartet's tile (in bounds, discarded) and
+    // leave behind the barrier
+    const bool work = tile0 + sub < t_last && tile0 + sub < total_tiles;
+    const int tile_id = work ? tile0 + sub : tile0;
+    const int tile = tile_id - b * a.tiles_per_set;
+    const bool newset = first || b != cur_b;
 
     const int n_base = tile * TP + wave * 32;
     int nn[NB];
@@ -192,12 +173,161 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
       row[nb] = (int64_t)b * a.N + (live[nb] ? nn[nb] : 0);
     }
 
-    float xq[NB][3];                 // layer 1: this lane's points, for the Qp recomputation
+    // ---- the requests ----
+    u32x4 wo[NC], wq[WANT_DX ? NC : 1];
+    if (first) {
+#pragma unroll
+      for (int e = 0; e < NC; ++e) {
+        const int c = tid + NT * e, wrow = c / (D / 8), c16 = c % (D / 8);
+        wo[e] = *reinterpret_cast<const u32x4*>(a.WoTP + (int64_t)wrow * D + c16 * 8);
+        if (WANT_DX) wq[e] = *reinterpret_cast<const u32x4*>(a.WqTP + (int64_t)wrow * D + c16 * 8);
+      }
+    }
+    u32x4 kp[KVC], vp[KVC], kt[KVC];
+    if (newset) {
+#pragma unroll
+      for (int e = 0; e < KVC; ++e) {
+        // (chunk index clamped, the LDS store guarded: the load stays unconditional)
+        const int c = min(tid + NT * e, MI * (D / 8) - 1), krow = c / (D / 8), c16 = c % (D / 8);
+        const int64_t src = ((int64_t)b * MI + krow) * D + c16 * 8;
+        kp[e] = *reinterpret_cast<const u32x4*>(a.KpP + src);
+        vp[e] = *reinterpret_cast<const u32x4*>(a.VpP + src);
+        kt[e] = reinterpret_cast<const u32x4*>(a.Kt + (int64_t)b * D * MI)[c];
+      }
+    }
+    float wq4[4];                    // layer 1: row min(tid, D - 1) of fc_q and its bias
+    if (FUSE_WQ && first) {
+      const int f = min(tid, D - 1);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) wq4[c] = a.WqF[f * a.dq + min(c, a.dq - 1)];
+      wq4[3] = a.bqF[f];
+    }
+    // (the images first: their LDS stores then wait for them alone, vmcnt counting in order)
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t bits[NB][D / 128];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int w = 0; w < D / 128; ++w)
+        bits[nb][w] = a.mask[mab1_mask_index<D>(b, a.tiles_per_set, tile, wave, nb, w, lane)];
+    // dY^T tiles as loaded (bf16x4 when ABF; fp32 dY lands in dO itself).  Unconditional - row[] is
+    // clamped for padding points - and zeroed at the use
+    f32x4 dO[DT][NB];
+    bf16x4 dyh[ABF ? DT : 1][NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        if (ABF) {
+          dyh[ABF ? t : 0][nb] = *reinterpret_cast<const bf16x4*>(
+              reinterpret_cast<const __bf16*>(a.dY) + row[nb] * D + 16 * t + 4 * g);
+        } else {
+          const float4 v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.dY) +
+                                                            row[nb] * D + 16 * t + 4 * g);
+          dO[t][nb] = f32x4{v.x, v.y, v.z, v.w};
+        }
+      }
+    // layer 1: this lane's points for the Qp recomputation, and the points of the A operand below;
+    // components at or past dq read component dq - 1 and are discarded
+    float xq[NB][3], xa[8];
     if (FUSE_WQ) {
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) xq[nb][c] = c < a.dq ? a.Xs[row[nb] * a.dq + c] : 0.f;
+        for (int c = 0; c < 3; ++c) xq[nb][c] = a.Xs[row[nb] * a.dq + min(c, a.dq - 1)];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int pt = n_base + (k < 4 ? 4 * g + k : 16 + 4 * g + k - 4);
+        xa[k] = a.Xs[((int64_t)b * a.N + (pt < a.N ? pt : 0)) * a.dq + min(r & 3, a.dq - 1)];
+      }
+    }
+    // the saved Qp, features 32j + perm32(8g + .) of this lane's points: head 0's with the batch, head j + 1's
+    // while head j is worked on (the whole tile's - 32 registers through the fc_o adjoint - spilled)
+    bf16x4 qs[FUSE_WQ ? 1 : KS][NB][2];
+    auto request_qp = [&](const int j) __attribute__((always_inline)) {
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        qs[j][nb][0] = *reinterpret_cast<const bf16x4*>(a.QpS + row[nb] * D + 32 * j + 4 * g);
+        qs[j][nb][1] = *reinterpret_cast<const bf16x4*>(a.QpS + row[nb] * D + 32 * j + 16 + 4 * g);
+      }
+    };
+    if (!FUSE_WQ) request_qp(0);
+    // (the scheduler must not sink a request below the LDS stores to save registers)
+    __builtin_amdgcn_sched_barrier(0);
+    PCA_STAMP(8);
+
+    // ---- the images into LDS ---- (their offsets derived here, not kept from the requests)
+    asm volatile("" : "+v"(tid));
+    if (first) {
+#pragma unroll
+      for (int e = 0; e < NC; ++e) {
+        const int c = tid + NT * e, wrow = c / (D / 8), c16 = c % (D / 8);
+        *reinterpret_cast<u32x4*>(sWoT + swz(wrow, c16, ROWB)) = wo[e];
+        if (WANT_DX) *reinterpret_cast<u32x4*>(sWqT + swz(wrow, c16, ROWB)) = wq[e];
+      }
+      if (FUSE_WQ && tid < D)
+        sWq4[tid] = float4{wq4[0], a.dq > 1 ? wq4[1] : 0.f, a.dq > 2 ? wq4[2] : 0.f, wq4[3]};
+    }
+    if (newset) {
+      if (!first) lds_barrier();         // the previous set's images have been read
+#pragma unroll
+      for (int e = 0; e < KVC; ++e) {
+        const int c = tid + NT * e, krow = c / (D / 8), c16 = c % (D / 8);
+        if (c < MI * (D / 8)) {
+          *reinterpret_cast<u32x4*>(sKp + swz(krow, c16, ROWB)) = kp[e];
+          *reinterpret_cast<u32x4*>(sVp + swz(krow, c16, ROWB)) = vp[e];
+          reinterpret_cast<u32x4*>(sKt)[c] = kt[e];
+        }
+      }
+      cur_b = b;
+    }
+    lds_barrier();                       // LDS only: the tile's requests stay in flight across it
+    __builtin_amdgcn_sched_barrier(0);
+    PCA_STAMP(1);
+    if (!work) return;                   // (no barrier below)
+
+    // ---- dY^T tiles and dZ = dY . [Z > 0] ----
+    bf16x8 dzb[KS][NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      bf16x4 dzh[DT];
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        const uint32_t m4 = bits[nb][t / 8] >> ((t & 7) * 4);
+        if (ABF) {
+          // bf16 -> fp32 -> bf16 returns the bits it was given, so dZ is a select on the loaded words
+          bf16x4 h4 = dyh[ABF ? t : 0][nb];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (!live[nb]) h4[e] = (__bf16)0.f;
+            dO[t][nb][e] = (float)h4[e];
+            dzh[t][e] = ((m4 >> e) & 1u) ? h4[e] : (__bf16)0.f;
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (!live[nb]) dO[t][nb][e] = 0.f;
+            dzh[t][e] = (__bf16)(((m4 >> e) & 1u) ? dO[t][nb][e] : 0.f);
+          }
+        }
+      }
+      if (nb == 0) PCA_STAMP(9);
+#pragma unroll
+      for (int s = 0; s < KS; ++s) dzb[s][nb] = cat8(dzh[2 * s], dzh[2 * s + 1]);
+    }
+    if (a.dZ != nullptr) {               // (null: the fc_o job masks dY itself, WgradJob::mask)
+      // the materialised form: one block of stores per 16-row group, behind both groups' converts (a branch
+      // between them split the tiles' registers)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb)
+        if (live[nb]) {
+#pragma unroll
+          for (int t = 0; t < DT; ++t) {
+            const bf16x8 z = dzb[t / 2][nb];
+            *reinterpret_cast<bf16x4*>(a.dZ + row[nb] * D + 16 * t + 4 * g) =
+                (t & 1) ? bf16x4{z[4], z[5], z[6], z[7]} : bf16x4{z[0], z[1], z[2], z[3]};
+          }
+        }
     }
     bf16x8 xaug;
     if (FUSE_WQ) {
@@ -205,53 +335,19 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
       const int c = r & 3, part = r >> 2;          // part 0: hi / ones, 1: lo
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        const int pt = n_base + (k < 4 ? 4 * g + k : 16 + 4 * g + k - 4);
-        float v = 0.f;
-        if (part <= 1 && r < 7 && r != 3 && c < a.dq) {
-          const float x = a.Xs[((int64_t)b * a.N + (pt < a.N ? pt : 0)) * a.dq + c];
-          const float hi = (float)(__bf16)x;
-          v = part == 0 ? hi : x - hi;
-        } else if (r == 3) {
-          v = 1.f;
-        }
+        const float x = xa[k], hi = (float)(__bf16)x;
+        float v = part == 0 ? hi : x - hi;
+        if (!(part <= 1 && r < 7 && r != 3 && c < a.dq)) v = r == 3 ? 1.f : 0.f;
         xaug[k] = (__bf16)v;
       }
-    }
-    // ---- dY^T tiles and dZ = dY . [Z > 0] ----
-    f32x4 dO[DT][NB];
-    bf16x8 dzb[KS][NB];
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      uint32_t bits[D / 128];
+      for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-      for (int w = 0; w < D / 128; ++w)
-        bits[w] = a.mask[mab1_mask_index<D>(b, a.tiles_per_set, tile, wave, nb, w, lane)];
-      f32x4 dz[DT];
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        // (unconditional - row[] is clamped for padding points - and zeroed afterwards: under the
-        //  divergent `if (live)` each of the DT loads was waited for before the next was issued)
-        float4 v;
-        if (ABF) {
-          const bf16x4 h4 = *reinterpret_cast<const bf16x4*>(
-              reinterpret_cast<const __bf16*>(a.dY) + row[nb] * D + 16 * t + 4 * g);
-          v = float4{(float)h4[0], (float)h4[1], (float)h4[2], (float)h4[3]};
-        } else {
-          v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.dY) +
-                                               row[nb] * D + 16 * t + 4 * g);
-        }
-        if (!live[nb]) v = float4{0.f, 0.f, 0.f, 0.f};
-        dO[t][nb] = f32x4{v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          dz[t][e] = ((bits[t / 8] >> ((t & 7) * 4 + e)) & 1u) ? dO[t][nb][e] : 0.f;
-        if (live[nb] && a.dZ != nullptr)     // (null: the fc_o job masks dY itself, WgradJob::mask)
-          *reinterpret_cast<bf16x4*>(a.dZ + row[nb] * D + 16 * t + 4 * g) = pack4(dz[t]);
-      }
-#pragma unroll
-      for (int s = 0; s < KS; ++s) dzb[s][nb] = pack8(dz[2 * s], dz[2 * s + 1]);
+        for (int c2 = 0; c2 < 3; ++c2)
+          if (c2 >= a.dq) xq[nb][c2] = 0.f;
     }
 
+    __builtin_amdgcn_sched_barrier(0);
     PCA_STAMP(2);
     // ---- dO^T = dY^T + Wo^T . dZ^T ----
 #pragma unroll
@@ -275,9 +371,19 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
     }
 
     PCA_STAMP(3);
+    // (a new phase: the LDS offsets of the heads are derived here, not kept alive from the tile's start)
+    asm volatile("" : "+v"(tid));
+    lane = tid & 63; r = lane & 15; g = lane >> 4;
     // ---- attention backward per head; dO tiles of the head become dQp in place ----
 #pragma unroll
     for (int j = 0; j < KS; ++j) {
+      // (one scheduling region per head: across the four unrolled heads hipcc moved the next heads' LDS reads
+      //  up until layer 1's accumulators no longer fitted)
+      if (FUSE_KV) __builtin_amdgcn_sched_barrier(0);
+      if (!FUSE_WQ && j + 1 < KS) {
+        request_qp(j + 1);
+        __builtin_amdgcn_sched_barrier(0);     // (leaves here, a head ahead of its use)
+      }
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
         // saved Qp of this point, features 32j + perm32(8g + .)
@@ -293,8 +399,8 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
                               0.f * 0.f);
           }
         } else {
-          qlo = *reinterpret_cast<const bf16x4*>(a.QpS + row[nb] * D + 32 * j + 4 * g);
-          qhi = *reinterpret_cast<const bf16x4*>(a.QpS + row[nb] * D + 32 * j + 16 + 4 * g);
+          qlo = qs[FUSE_WQ ? 0 : j][nb][0];
+          qhi = qs[FUSE_WQ ? 0 : j][nb][1];
         }
         bf16x8 qb;
 #pragma unroll
@@ -439,8 +545,17 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
           }
         }
     }
+  };
+  if (t_first < t_last && t_first < total_tiles) {
+    pass(std::true_type{}, t_first);
+    for (int tile0 = t_first + t_step * SUBS; tile0 < t_last && tile0 < total_tiles; tile0 += t_step * SUBS)
+      pass(std::false_type{}, tile0);
   }
   PCA_STAMP(5);
+  // (behind the tiles: in front of them these stores would be the oldest entries of vmcnt, and the first
+  //  LDS store of an image would wait for them)
+  if (a.zero_ptr != nullptr)
+    for (int i = blockIdx.x * NT + tid; i < a.zero_n; i += gridDim.x * NT) a.zero_ptr[i] = 0.f;
   if (FUSE_WQ) {
     // wqa rows (4g + e) = augmented-point rows, columns = features 32j + 16tt + r: combine
     // the hi (g = 0) and lo (g = 1) rows, sum the waves through LDS, one atomic per element

@@ -70,13 +70,7 @@ __device__ __forceinline__ bf16x8 y_tr_frag(const char* img, int t, int lane) {
 __device__ __forceinline__ void put_tile(char* img, int t, int r, int g, f32x4 v) {
   *reinterpret_cast<bf16x4*>(img + swz(r, 2 * t + (g >> 1), ROWB) + 8 * (g & 1)) = pack4(v);
 }
-// workgroup barrier that orders LDS traffic only: global stores in flight (saved tensors) are not
-// waited for, as __syncthreads()'s vmcnt(0) would
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
+// (lds_barrier() of mfma_common.hpp: global stores in flight - the saved tensors - are not waited for)
 // max0 (as max_nn of mfma_common.hpp): ONE instruction (v_med3_f32 with +inf; fmaxf costs a canonicalising
 // v_max x, x in front).  A builtin, NOT inline asm: hipcc's hazard recognizer does not look inside asm, and
 // a VALU instruction reading an MFMA result needs wait states it would not insert (the first version of

@@ -6,6 +6,14 @@ order of global loads, vmcnt waits, LDS stores and barriers from the kernel's en
   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude -Ipoint-cloud-audio_amd/csrc --cuda-device-only -S \
       point-cloud-audio_amd/csrc/mab0_bwd_bf16.hip -o mab0_bwd_bf16.s
   scripts/experiments/isa_prologue.py mab0_bwd_bf16.s 'k_mab0_bwd<64, true>' 'k_mab0_bwd_small<true>'
+
+--to-mfma  for kernels whose loads lie behind more than one barrier (k_mab1_bwd: the weight images, the K / V images,
+           then the tile): the sequence from the entry to the first MFMA, barriers included, and on through the
+           MFMA phases - there only global loads, vmcnt waits, global stores, scratch traffic and the runs of
+           MFMAs - to the first s_barrier behind them (k_mab1_bwd: through the head loop and the dX stage)
+--counts   no sequence: one line per kernel with its global loads, vmcnt waits, vmcnt(0) waits, the vmcnt(0)
+           waits that have a global load among the 8 instructions in front of them (a load waited for where it
+           was issued: a serial round trip), VGPRs and scratch bytes
 """
 import re
 import subprocess
@@ -64,16 +72,81 @@ def prologue(lines):
     return seq
 
 
+def ops(lines):
+    """(mnemonic, text without the comment) of every instruction line"""
+    out = []
+    for ln in lines:
+        ln = ln.split(";")[0].strip()
+        if not ln or ln.endswith(":") or ln.startswith("."):
+            continue
+        out.append((ln.split(" ")[0], ln))
+    return out
+
+
+def is_gload(op):
+    return op.startswith("global_load") or op.startswith("buffer_load")
+
+
+def to_mfma(lines):
+    seq = []
+    seen_mfma = False
+    for op, ln in ops(lines):
+        key = None
+        if is_gload(op) or op.startswith("global_store") or op.startswith("scratch_"):
+            key = op
+        elif op.startswith("v_mfma"):
+            key, seen_mfma = "v_mfma", True
+        elif (op.startswith("ds_write") or op.startswith("ds_store")) and not seen_mfma:
+            key = op
+        elif op == "s_waitcnt" and "vmcnt" in ln:
+            key = "s_waitcnt " + re.search(r"vmcnt\(\d+\)", ln).group(0)
+        elif op == "s_barrier":
+            seq.append([op, 1])
+            if seen_mfma:
+                break
+            continue
+        elif op.startswith("s_cbranch") and not seen_mfma:
+            key = op
+        if key is None:
+            continue
+        if seq and seq[-1][0] == key and not key.startswith("s_"):
+            seq[-1][1] += 1
+        else:
+            seq.append([key, 1])
+    return seq
+
+
+def counts(lines):
+    ins = ops(lines)
+    loads = sum(is_gload(op) for op, _ in ins)
+    waits = [i for i, (op, ln) in enumerate(ins) if op == "s_waitcnt" and "vmcnt" in ln]
+    full = [i for i in waits if "vmcnt(0)" in ins[i][1]]
+    behind = sum(any(is_gload(op) for op, _ in ins[max(0, i - 8):i]) for i in full)
+    return loads, len(waits), len(full), behind
+
+
 def main():
-    path, wanted = sys.argv[1], sys.argv[2:]
+    flags = [a for a in sys.argv[1:] if a.startswith("--")]
+    rest = [a for a in sys.argv[1:] if not a.startswith("--")]
+    path, wanted = rest[0], rest[1:]
     ks = kernels(open(path).read())
-    for sym, (lines, meta) in sorted(ks.items()):
+    listing = to_mfma if "--to-mfma" in flags else prologue
+    if "--counts" in flags:
+        print(f"{'global loads':>12} {'vmcnt waits':>11} {'vmcnt(0)':>8} {'(0) <= 8 behind a load':>22} "
+              f"{'VGPRs':>5} {'scratch B':>9}  kernel")
+    for sym, (lines, meta) in sorted(ks.items(), key=lambda kv: demangle(kv[0])):
         name = demangle(sym)
-        if not any(w in name for w in wanted):
+        if wanted and not any(w in name for w in wanted):
+            continue
+        if "--counts" in flags:
+            lo, wa, fu, be = counts(lines)
+            short = re.sub(r"\(.*$", "", name.replace("(anonymous namespace)::", "").replace("void ", ""))
+            print(f"{lo:12d} {wa:11d} {fu:8d} {be:22d} {meta.get('vgpr_count', -1):5d} "
+                  f"{meta.get('private_segment_fixed_size', -1):9d}  {short}")
             continue
         print(name)
         print("  " + "  ".join(f"{k}={v}" for k, v in meta.items()))
-        for key, n in prologue(lines):
+        for key, n in listing(lines):
             print(f"    {n:3d} x {key}" if n > 1 else f"          {key}")
         print()
 
