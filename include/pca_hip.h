@@ -769,7 +769,7 @@ int pca_adam_step_ex(float* param, float* grad, float* exp_avg, float* exp_avg_s
                      const float* lr_table, int64_t lr_table_len, int32_t* step_count_dev,
                      pca_optim_state* state_dev, int zero_grad, void* stream);
 
-/* pca_adam_step_ex with three options on top, still ONE launch (csrc/optim_groups.hip): decoupled
+/* pca_adam_step_ex with three options on top, still ONE launch (csrc/optim.hip): decoupled
  * weight decay (torch.optim.AdamW), a rate and a decay multiplier per segment of the flat vector
  * (torch param_groups), and an averaged copy of the weights (torch.optim.swa_utils.AveragedModel
  * with get_ema_multi_avg_fn) updated in the same pass.  A host struct holding device pointers. */

@@ -1,7 +1,6 @@
-// Loss and optimiser of the train step (Code/settransformer.py:88-91,104-108):
-// nn.CrossEntropyLoss (mean) forward+gradient in one launch, and torch.optim.Adam with
-// coupled weight decay as one fused pass over a flat parameter vector.  Also the correct-count
-// tally of the evaluation sweeps (Code/pceval.py:95, (preds.argmax(dim=1) == lbls).sum()).
+// Loss of the train step (Code/settransformer.py:88,104-105): nn.CrossEntropyLoss (mean)
+// forward+gradient in one launch, and the fused classifier head (the optimiser: optim.hip).  Also the
+// correct-count tally of the evaluation sweeps (Code/pceval.py:95, (preds.argmax(dim=1) == lbls).sum()).
 #include "blocks.hpp"
 #include "bwd_defer.hpp"
 #include "terminal_bodies.hpp"
@@ -124,85 +123,6 @@ __global__ __launch_bounds__(128) void k_cls_wgrad(
   cls_wgrad_body(dlogits, P, lossv, corrv, B, d, C, dWc, dbc, loss_out, stats, blockIdx.x);
 }
 
-// step[0] = optimiser step count, step[1] = arrival ticket (zero between launches).  Every
-// workgroup reads step[0] before it draws its ticket; the workgroup drawing the last ticket
-// publishes step[0] + 1 and clears the ticket, so the count advances inside this launch
-// (graph replays stay correct) without a second kernel.
-__global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, float* __restrict__ g,
-                                              float* __restrict__ m, float* __restrict__ v,
-                                              int64_t n, float lr, float b1, float b2,
-                                              float eps, float wd, float gscale,
-                                              int32_t* __restrict__ step, int zero_grad) {
-  // The kernel is one dependent chain of L2 round trips long (1.2 MB of parameters at configs[1]):
-  // the step count and the first batch of operands are requested together, 16-byte accesses, each
-  // thread two float4 quadruples in flight.
-  const int ti = step[0] + 1;
-  const int64_t n4 = n >> 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  float4* p4 = reinterpret_cast<float4*>(p);
-  float4* g4 = reinterpret_cast<float4*>(g);
-  float4* m4 = reinterpret_cast<float4*>(m);
-  float4* v4 = reinterpret_cast<float4*>(v);
-  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
-  float4 w0, g0, m0, v0, w1, g1, m1, v1;
-  const bool h0 = vec && i < n4, h1 = vec && i + stride < n4;
-  if (h0) { w0 = p4[i]; g0 = g4[i]; m0 = m4[i]; v0 = v4[i]; }
-  if (h1) { w1 = p4[i + stride]; g1 = g4[i + stride]; m1 = m4[i + stride]; v1 = v4[i + stride]; }
-  const float t = (float)ti;
-  const float bc1 = 1.f - powf(b1, t);
-  const float bc2 = 1.f - powf(b2, t);
-  const float step_size = lr / bc1;
-  const float inv_sqrt_bc2 = 1.f / sqrtf(bc2);
-  auto upd = [&](float& w, float& gg, float& mm, float& vv) {
-    const float gi = gg * gscale + wd * w;            // coupled L2 (torch.optim.Adam)
-    mm = b1 * mm + (1.f - b1) * gi;
-    vv = b2 * vv + (1.f - b2) * gi * gi;
-    const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
-    w = w - step_size * (mm / denom);
-    if (zero_grad) gg = 0.f;
-  };
-  auto upd4 = [&](float4& w, float4& gg, float4& mm, float4& vv) {
-    upd(w.x, gg.x, mm.x, vv.x); upd(w.y, gg.y, mm.y, vv.y);
-    upd(w.z, gg.z, mm.z, vv.z); upd(w.w, gg.w, mm.w, vv.w);
-  };
-  if (h0) {
-    upd4(w0, g0, m0, v0);
-    p4[i] = w0; m4[i] = m0; v4[i] = v0;
-    if (zero_grad) g4[i] = g0;
-  }
-  if (h1) {
-    upd4(w1, g1, m1, v1);
-    p4[i + stride] = w1; m4[i + stride] = m1; v4[i + stride] = v1;
-    if (zero_grad) g4[i + stride] = g1;
-  }
-  if (vec) {
-    for (int64_t k = i + 2 * stride; k < n4; k += stride) {
-      float4 w = p4[k], gg = g4[k], mm = m4[k], vv = v4[k];
-      upd4(w, gg, mm, vv);
-      p4[k] = w; m4[k] = mm; v4[k] = vv;
-      if (zero_grad) g4[k] = gg;
-    }
-  }
-  // the tail (n % 4 elements), or everything when a pointer is not 16-byte aligned
-  for (int64_t k = (vec ? (n4 << 2) : 0) + i; k < n; k += stride) {
-    float w = p[k], gg = g[k], mm = m[k], vv = v[k];
-    upd(w, gg, mm, vv);
-    p[k] = w; m[k] = mm; v[k] = vv;
-    if (zero_grad) g[k] = gg;
-  }
-  // every wave of the workgroup has its step[0] (loaded at the top, consumed by the updates above)
-  // before thread 0 draws the ticket that may publish the next count
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int ticket = atomicAdd(&step[1], 1);
-    if (ticket == (int)gridDim.x - 1) {
-      step[1] = 0;
-      step[0] = ti;
-    }
-  }
-}
-
 }  // namespace
 
 // PcaSoftTargets of the C ABI -> the kernels' argument; NULL is the hard target.  The smoothing is the
@@ -270,23 +190,5 @@ int pca_eval_tally(const float* logits, const int64_t* labels, int B, int C, int
                      pca::as_stream(stream), logits, labels, B, C,
                      reinterpret_cast<unsigned long long*>(counts + slot));
   return pca::check_launch("k_eval_tally");
-}
-
-int pca_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                  float lr, float beta1, float beta2, float eps, float weight_decay,
-                  float grad_scale, int32_t* step_count_dev, int zero_grad, void* stream) {
-  PCA_REQUIRE(param && grad && exp_avg && exp_avg_sq && step_count_dev,
-              "adam_step: null pointer");
-  PCA_REQUIRE(n >= 0, "adam_step: n=%lld", (long long)n);
-  hipStream_t st = pca::as_stream(stream);
-  // few, longer workgroups: the arrival tickets are serialised atomics on one address
-  // (two float4 quadruples per thread in the first pass)
-  int64_t blocks = pca::cdiv(n, 256 * 8);
-  if (blocks > 1024) blocks = 1024;
-  if (blocks < 1) blocks = 1;                      // n == 0 still advances the step count
-  hipLaunchKernelGGL(pca::k_adam, dim3((unsigned)blocks), dim3(256), 0, st, param, grad,
-                     exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, grad_scale,
-                     step_count_dev, zero_grad);
-  return pca::check_launch("k_adam");
 }
 }

@@ -511,8 +511,6 @@ class Trainer:
         if self._optim_on:
             with torch.cuda.device(self.dev):
                 self.lr_table = None if table is None else table.to(self.dev)
-                # pca_optim_state, 32 bytes: [skipped, clipped, last_norm, last_lr, norm_sum(2), count, -]
-                self.optim_state = torch.zeros(8, dtype=torch.int32, device=self.dev)
                 if self.max_grad_norm is not None or self.skip_nonfinite:
                     self.norm_partials = torch.zeros(int(lib().pca_grad_sumsq_partials(n)),
                                                      dtype=torch.float64, device=self.dev)
@@ -528,10 +526,10 @@ class Trainer:
         self._groups_on = (self.decoupled or self.groups is not None
                            or self.average_decay is not None)
         self.averaged = self._seg_end = self._seg_lr = self._seg_wd = self._seg_end_host = None
-        if self._groups_on:
+        if self._optim_on or self._groups_on:
             with torch.cuda.device(self.dev):
-                if self.optim_state is None:
-                    self.optim_state = torch.zeros(8, dtype=torch.int32, device=self.dev)
+                # pca_optim_state, 32 bytes: [skipped, clipped, last_norm, last_lr, norm_sum(2), count, -]
+                self.optim_state = torch.zeros(8, dtype=torch.int32, device=self.dev)
                 if self.groups is not None:
                     ends = self.groups["seg_end"]
                     assert ends[-1] == n, (ends[-1], n)
@@ -667,51 +665,35 @@ class Trainer:
 
     def _seg2(self):     # Adam over the flat vector
         e = self.eng
-        if self._groups_on:
-            # [sum of squares ->] pca_adam_step_groups: the guarded step with AdamW, the segment table
-            # and the averaged copy, in the one launch at the same place
-            L, n, st = lib(), e.flat.numel(), e._stream()
-            part, npart = None, 0
-            if self.norm_partials is not None:
-                part, npart = self.norm_partials.data_ptr(), self.norm_partials.numel()
-                check(L.pca_grad_sumsq(e.grads.data_ptr(), n, part, npart, st), "pca_grad_sumsq")
-            o = _lib.OptimCfg(self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                              1.0 / self.world, self.max_grad_norm or 0.0, int(self.skip_nonfinite))
-            ptr = lambda t: None if t is None else t.data_ptr()
-            gr = _lib.OptimGroups(
-                int(self.decoupled), 0 if self.groups is None else len(self.groups["seg_end"]),
-                ptr(self._seg_end), ptr(self._seg_lr), ptr(self._seg_wd), ptr(self.averaged),
-                1.0 if self.average_decay is None else 1.0 - self.average_decay, self.average_start)
-            tab = self.lr_table
-            check(L.pca_adam_step_groups(e.flat.data_ptr(), e.grads.data_ptr(), self.m.data_ptr(),
-                                         self.v.data_ptr(), n, C.byref(o), part, npart, ptr(tab),
-                                         0 if tab is None else tab.numel(), self.step_count.data_ptr(),
-                                         self.optim_state.data_ptr(), int(not self.keep_grads),
-                                         C.byref(gr), self._seg_end_host, st), "pca_adam_step_groups")
+        L, n, st = lib(), e.flat.numel(), e._stream()
+        ptr = lambda t: None if t is None else t.data_ptr()
+        head = (e.flat.data_ptr(), e.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n)
+        if not (self._optim_on or self._groups_on):
+            check(L.pca_adam_step(*head, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                                  1.0 / self.world, self.step_count.data_ptr(),
+                                  int(not self.keep_grads), st), "pca_adam_step")
             return
-        if self._optim_on:
-            # [sum of squares ->] guarded Adam: both launches where the plain one sits, i.e. after the
-            # all-reduce / the join, so every rank clips the same averaged gradient and skips alike
-            L, n, st = lib(), e.flat.numel(), e._stream()
-            part, npart = None, 0
-            if self.norm_partials is not None:
-                part, npart = self.norm_partials.data_ptr(), self.norm_partials.numel()
-                check(L.pca_grad_sumsq(e.grads.data_ptr(), n, part, npart, st), "pca_grad_sumsq")
-            o = _lib.OptimCfg(self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                              1.0 / self.world, self.max_grad_norm or 0.0, int(self.skip_nonfinite))
-            tab = self.lr_table
-            check(L.pca_adam_step_ex(e.flat.data_ptr(), e.grads.data_ptr(), self.m.data_ptr(),
-                                     self.v.data_ptr(), n, C.byref(o), part, npart,
-                                     None if tab is None else tab.data_ptr(),
-                                     0 if tab is None else tab.numel(), self.step_count.data_ptr(),
-                                     self.optim_state.data_ptr(), int(not self.keep_grads), st),
-                  "pca_adam_step_ex")
+        # [sum of squares ->] the guarded step: both launches where the plain one sits, i.e. after the
+        # all-reduce / the join, so every rank clips the same averaged gradient and skips alike
+        part, npart = None, 0
+        if self.norm_partials is not None:
+            part, npart = self.norm_partials.data_ptr(), self.norm_partials.numel()
+            check(L.pca_grad_sumsq(e.grads.data_ptr(), n, part, npart, st), "pca_grad_sumsq")
+        o = _lib.OptimCfg(self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                          1.0 / self.world, self.max_grad_norm or 0.0, int(self.skip_nonfinite))
+        tab = self.lr_table
+        guarded = (*head, C.byref(o), part, npart, ptr(tab), 0 if tab is None else tab.numel(),
+                   self.step_count.data_ptr(), self.optim_state.data_ptr(), int(not self.keep_grads))
+        if not self._groups_on:
+            check(L.pca_adam_step_ex(*guarded, st), "pca_adam_step_ex")
             return
-        check(lib().pca_adam_step(e.flat.data_ptr(), e.grads.data_ptr(), self.m.data_ptr(),
-                                  self.v.data_ptr(), e.flat.numel(), self.lr, self.betas[0],
-                                  self.betas[1], self.eps, self.wd, 1.0 / self.world,
-                                  self.step_count.data_ptr(), int(not self.keep_grads),
-                                  e._stream()), "pca_adam_step")
+        # AdamW, the segment table and the averaged copy, in the one launch at the same place
+        gr = _lib.OptimGroups(
+            int(self.decoupled), 0 if self.groups is None else len(self.groups["seg_end"]),
+            ptr(self._seg_end), ptr(self._seg_lr), ptr(self._seg_wd), ptr(self.averaged),
+            1.0 if self.average_decay is None else 1.0 - self.average_decay, self.average_start)
+        check(L.pca_adam_step_groups(*guarded, C.byref(gr), self._seg_end_host, st),
+              "pca_adam_step_groups")
 
     def _capture(self):
         """Warm up eagerly on a side stream, then capture the segments."""

@@ -9,8 +9,8 @@ that clock and thermal drift fall on all alike; reported are the medians and the
     python scripts/optim_bench.py [--config cfg2] [--steps 200] [--windows 15]
 
 ``--launch``: the optimiser launch alone, at the parameter counts of cfg2 and cfg4 (BASELINE configs[3]):
-pca_adam_step_ex against pca_adam_step_groups with no option, with the no_decay_groups() table of that
-model, with the averaged copy, and with both under decoupled decay.  Each variant is a captured graph of
+pca_adam_step and pca_adam_step_ex against pca_adam_step_groups with no option, with the no_decay_groups()
+table of that model, with the averaged copy, and with both under decoupled decay.  Each variant is a captured graph of
 --steps launches on vectors of its own; the variants take their windows in turn, and the figure is the
 window's wall time over its launches (so it holds the gap between two launches of a graph, as in a step).
 
@@ -61,14 +61,18 @@ def launch_variants(n, groups, dev):
             st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             args = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, C.byref(cfg), None, 0,
                     None, 0, step.data_ptr(), state.data_ptr(), 0)
-            if entry == "ex":
+            if entry == "plain":
+                _lib.check(L.pca_adam_step(*args[:5], cfg.lr, cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay,
+                                           cfg.grad_scale, step.data_ptr(), 0, st), "pca_adam_step")
+            elif entry == "ex":
                 _lib.check(L.pca_adam_step_ex(*args, st), "pca_adam_step_ex")
             else:
                 _lib.check(L.pca_adam_step_groups(*args, C.byref(gr), ends_host if table else None, st),
                            "pca_adam_step_groups")
         return enqueue
 
-    out = {"adam_step_ex": variant("ex"),
+    out = {"adam_step": variant("plain"),
+           "adam_step_ex": variant("ex"),
            "groups: no option": variant("groups"),
            "groups: table": variant("groups", table=True),
            "groups: average": variant("groups", avg=True),

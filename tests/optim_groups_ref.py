@@ -1,4 +1,4 @@
-"""One pca_adam_step_groups step (csrc/optim_groups.hip) restated in torch on the CPU, and the same step by
+"""One pca_adam_step_groups step (csrc/optim.hip) restated in torch on the CPU, and the same step by
 stock parts.
 
 ``GroupsRef.step``: tests/optim_ref.py's norm, clip factor and table lookup in front of the per-segment

@@ -1,4 +1,4 @@
-"""pca_adam_step_groups on the device (csrc/optim_groups.hip): AdamW, per-segment scales and the averaged
+"""pca_adam_step_groups on the device (csrc/optim.hip): AdamW, per-segment scales and the averaged
 copy against tests/optim_groups_ref.py, stock torch and pca_adam_step_ex, and the Trainer options built
 on it (decoupled_weight_decay, param_groups, average_decay, eval_weights, Evaluator.use_params): against a stock loop, graph
 against eager, exact resume, evaluation on the averaged weights.  Run with ``-m gpu``.
