@@ -24,6 +24,7 @@
 //   k_mab0_epi    per set: O, Z, H (fp32 VALU; 2*m*d*(dk+d) MACs)
 #include "blocks.hpp"
 #include "weight_images.hpp"
+#include "prep_plan.hpp"
 #include "step_ctx.hpp"
 #include "mfma_common.hpp"
 #include "pack_body.hpp"
@@ -40,48 +41,34 @@ namespace {
 // Query-side preparation of up to 3 MABs in ONE launch (they only depend on parameters):
 //   Qp[m][d] = I Wq^T + bq (fp32) ; G[h*m][dk] = scale*log2(e) * Qp_h Wk_h (fp32 + bf16, padding
 //   rows zero) ; GtP[dk][Rp] = K-permuted transpose of G for the backward.
-// blockIdx.y = MAB, blockIdx.x = query row q (blocks beyond m exit).
+// Workgroup q of a job: query row q (d > 128: (row, head)), then the PREP_SPARE transposers, then the pad items
+// (prep_plan.hpp: prep_query_blocks).
 // ---------------------------------------------------------------------------------
-constexpr int PREP_SPARE = 16;
 __device__ __forceinline__ void mab0_prep_body(const Mab0PrepJob& a, float* sq, int q);
 
-__global__ __launch_bounds__(256) void k_mab0_prep(const Mab0PrepJobs jobs) {
+// the query-side items of a plan alone (prep_plan.hpp): block x of a segment is workgroup x of its job
+__global__ __launch_bounds__(256) void k_mab0_prep(const Mab0PrepJobs jobs, const PrepPlan pl) {
   extern __shared__ float sq[];            // Qp row [d]
-  mab0_prep_body(jobs.j[blockIdx.y], sq, blockIdx.x);
+  const PrepSeg s = prep_find_seg(pl, blockIdx.x);
+  mab0_prep_body(jobs.j[s.job], sq, (int)blockIdx.x - s.first);
 }
 
-// weight images (as k_prep_jobs, mab1_bf16.hip) and query-side tensors in one grid:
-// rows [0, Q.n) of blockIdx.y are query-side jobs, then the weight-image jobs, then (rider rows)
-// the step's deferred point-set pack - independent of everything else in this launch
-__global__ __launch_bounds__(256) void k_prep_all(const PrepJobs W, const Mab0PrepJobs Q,
-                                                  const PackJob P) {
+// The whole preparation of a step over one flat block index (prep_plan.hpp): query-side items first, then the
+// step's deferred point-set pack - independent of everything else in this launch - then the weight images by
+// tiles (as k_prep_jobs, mab1_bf16.hip) and the clears.  Every workgroup has work.
+// TILES = false runs a plan without tiles: beside the query-side body the tile body takes the kernel from 136 to 200
+// VGPRs - two workgroups per CU instead of three - which a launch of more than one round of workgroups (d = 256:
+// 520 query rows and 2048 pack items) pays for with a second round of its longest chains (prep_all_launch).
+template <bool TILES>
+__global__ __launch_bounds__(256) void k_prep_all(const PrepJobs W, const Mab0PrepJobs Q, const PackJob P,
+                                                  const PrepPlan pl) {
   extern __shared__ float sq[];
-  if ((int)blockIdx.y >= Q.n + W.n) {
-    const int blk = ((int)blockIdx.y - Q.n - W.n) * gridDim.x + blockIdx.x;
-    if (blk < P.bx * P.B) pack_body(P, blk);
-    return;
-  }
-  if ((int)blockIdx.y < Q.n) {
-    mab0_prep_body(Q.j[blockIdx.y], sq, blockIdx.x);
-    return;
-  }
-  const PrepJob jb = W.j[blockIdx.y - Q.n];
-  const int rows = jb.rows, cols = jb.cols, mode = jb.mode;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= rows * cols) return;
-  float v;
-  if (mode == 4) {                     // clear job: rows * cols 16-bit words of zeros (no source)
-    v = 0.f;
-  } else if (mode <= 1) {
-    const int n = idx / cols, k = idx - n * cols;
-    const int kk = mode == 1 ? (k & ~31) + perm32(k & 31) : k;
-    v = jb.src[(int64_t)n * cols + kk];
-  } else {
-    const int n = idx / rows, k = idx - n * rows;
-    const int kk = mode == 2 ? (k & ~31) + perm32(k & 31) : k;
-    v = jb.src[(int64_t)kk * cols + n];
-  }
-  jb.dst[idx] = (__bf16)v;
+  __shared__ __attribute__((aligned(16))) float tile[TILES ? PREP_TILE_LDS : 4];
+  const PrepSeg s = prep_find_seg(pl, blockIdx.x);
+  const int x = (int)blockIdx.x - s.first;
+  if (s.kind == PREP_QUERY) mab0_prep_body(Q.j[s.job], sq, x);
+  else if (s.kind == PREP_PACK) pack_body(P, x);
+  else prep_image_item<TILES>(W, pl, s, x, tile);
 }
 
 // d > 128: blockIdx.x = q * h + j - one workgroup per (query row, head).  A thread per output
@@ -139,25 +126,34 @@ __device__ __forceinline__ void mab0_prep_head(const Mab0PrepJob& a, float* sq, 
         a.GtP[c * a.Rp + rb32 + pos] = (__bf16)acc;
       }
     }
-    if (q == 0 && j == 0 && a.Gb != nullptr) {         // zero the padding rows (PMA: R = h < 32)
-      const int R = a.h * m;
-      for (int o = threadIdx.x; o < (a.Rp - R) * dk; o += 256) {
-        const int rr = R + o / dk, c = o % dk;
-        a.Gb[rr * dk + c] = (__bf16)0.f;
-        if (a.GtP != nullptr) {
-          const int rb32 = rr & ~31, ro = rr & 31;
-          int pos = 0;
+  }
+}
+
+// Pad item x of a job: 256 elements of the padding rows [h m, Rp) of Gb (PMA: R = h < 32) and their places in
+// GtP, zeroed.  They depend on nothing, so they are workgroups of their own (prep_query_pads) and not a loop
+// behind the chain of the job's first row.
+__device__ __forceinline__ void mab0_prep_pad(const Mab0PrepJob& a, int x) {
+  const int R = a.h * a.m, dk = a.dk;
+  const int o = x * 256 + threadIdx.x;
+  if (o >= (a.Rp - R) * dk) return;
+  const int r = R + o / dk, c = o % dk;
+  a.Gb[r * dk + c] = (__bf16)0.f;
+  if (a.GtP != nullptr) {
+    const int rb32 = r & ~31, ro = r & 31;
+    int pos = 0;
 #pragma unroll
-          for (int p = 0; p < 32; ++p)
-            if (perm32(p) == ro) pos = p;
-          a.GtP[c * a.Rp + rb32 + pos] = (__bf16)0.f;
-        }
-      }
-    }
+    for (int p = 0; p < 32; ++p)
+      if (perm32(p) == ro) pos = p;
+    a.GtP[c * a.Rp + rb32 + pos] = (__bf16)0.f;
   }
 }
 
 __device__ __forceinline__ void mab0_prep_body(const Mab0PrepJob& a, float* sq, int q) {
+  const int pad0 = prep_query_rows(a) + prep_query_spare(a);
+  if (q >= pad0) {
+    mab0_prep_pad(a, q - pad0);
+    return;
+  }
   if (a.d > 128) {
     const int nx = a.m * a.h;
     if (q < nx) {
@@ -311,20 +307,6 @@ __device__ __forceinline__ void mab0_prep_body(const Mab0PrepJob& a, float* sq, 
       for (int p = 0; p < 32; ++p)
         if (perm32(p) == ro) pos = p;
       a.GtP[c * a.Rp + rb32 + pos] = (__bf16)acc;
-    }
-  }
-  if (q == 0 && a.Gb != nullptr) {         // zero the padding rows (PMA: R = h < 32)
-    for (int o = threadIdx.x; o < (a.Rp - R) * dk; o += 256) {
-      const int r = R + o / dk, c = o % dk;
-      a.Gb[r * dk + c] = (__bf16)0.f;
-      if (a.GtP != nullptr) {
-        const int rb32 = r & ~31, ro = r & 31;
-        int pos = 0;
-#pragma unroll
-        for (int p = 0; p < 32; ++p)
-          if (perm32(p) == ro) pos = p;
-        a.GtP[c * a.Rp + rb32 + pos] = (__bf16)0.f;
-      }
     }
   }
 }
@@ -805,43 +787,27 @@ void mab0_collect_prep(const pca_mab_shape& s, const float* I, const pca_mab_par
 int prep_all_launch(const PrepJobs& W, const Mab0PrepJobs& Q, hipStream_t st) {
   if (W.n == 0) return mab0_prep_launch(Q, st);
   if (Q.n == 0) return prep_jobs_launch(W, st);
-  int maxm = 0, maxd = 0, maxe = 0;
-  bool spare = false;
-  for (int i = 0; i < Q.n; ++i) {
-    maxm = Q.j[i].m > maxm ? Q.j[i].m : maxm;
-    maxd = Q.j[i].d > maxd ? Q.j[i].d : maxd;
-    spare = spare || Q.j[i].WvT != nullptr;
-  }
-  for (int i = 0; i < W.n; ++i) {
-    const int e = W.j[i].rows * W.j[i].cols;
-    maxe = e > maxe ? e : maxe;
-  }
-  for (int i = 0; i < Q.n; ++i)              // d > 128: one workgroup per (query row, head)
-    if (Q.j[i].d > 128) maxm = Q.j[i].m * Q.j[i].h > maxm ? Q.j[i].m * Q.j[i].h : maxm;
-  int gx = maxm + (spare ? PREP_SPARE : 0);
-  const int gw = (int)cdiv(maxe, 256);
-  gx = gx > gw ? gx : gw;
   PCA_REQUIRE(pack_stream_ok(st), "deferred pack: submitted on another stream than the engine call's");
   PackJob P{};
-  const int prows = pack_take(&P) ? (int)cdiv(pack_blocks(P), gx) : 0;
-  hipLaunchKernelGGL(k_prep_all, dim3(gx, Q.n + W.n + prows), dim3(256), maxd * sizeof(float), st,
-                     W, Q, P);
+  if (!pack_take(&P)) P.kind = 0;
+  PrepPlan pl;
+  prep_plan(W, Q, P, &pl);
+  if (pl.blocks == 0) return PCA_OK;
+  // the kernel with the tile body holds two workgroups per CU: tiles where that is one round of the 256 CUs
+  if (pl.blocks <= 2 * 256) {
+    hipLaunchKernelGGL(k_prep_all<true>, dim3(pl.blocks), dim3(256), pl.lds_floats * sizeof(float), st, W, Q, P, pl);
+  } else {
+    prep_plan(W, Q, P, &pl, false);
+    hipLaunchKernelGGL(k_prep_all<false>, dim3(pl.blocks), dim3(256), pl.lds_floats * sizeof(float), st, W, Q, P, pl);
+  }
   return check_launch("k_prep_all");
 }
 
 int mab0_prep_launch(const Mab0PrepJobs& J, hipStream_t st) {
-  if (J.n == 0) return PCA_OK;
-  int maxm = 0, maxd = 0;
-  for (int i = 0; i < J.n; ++i) {
-    maxm = J.j[i].m > maxm ? J.j[i].m : maxm;
-    maxd = J.j[i].d > maxd ? J.j[i].d : maxd;
-  }
-  bool spare = false;
-  for (int i = 0; i < J.n; ++i) spare = spare || J.j[i].WvT != nullptr;
-  for (int i = 0; i < J.n; ++i)              // d > 128: one workgroup per (query row, head)
-    if (J.j[i].d > 128) maxm = J.j[i].m * J.j[i].h > maxm ? J.j[i].m * J.j[i].h : maxm;
-  hipLaunchKernelGGL(k_mab0_prep, dim3(maxm + (spare ? PREP_SPARE : 0), J.n), dim3(256),
-                     maxd * sizeof(float), st, J);
+  PrepPlan pl;
+  prep_plan(PrepJobs{}, J, PackJob{}, &pl);
+  if (pl.blocks == 0) return PCA_OK;
+  hipLaunchKernelGGL(k_mab0_prep, dim3(pl.blocks), dim3(256), pl.lds_floats * sizeof(float), st, J, pl);
   return check_launch("k_mab0_prep");
 }
 

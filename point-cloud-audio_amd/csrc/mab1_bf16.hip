@@ -13,6 +13,7 @@
 // Roofline unit: per point 2*(2 d^2 + 2 m d) FLOP forward.
 #include "blocks.hpp"
 #include "weight_images.hpp"
+#include "prep_plan.hpp"
 #include "step_ctx.hpp"
 #include "d256.hpp"
 #include "mfma_common.hpp"
@@ -117,24 +118,11 @@ __global__ __launch_bounds__(1024) void k_prep_weight_f8_jobs(const PrepF8Jobs j
   prep_weight_f8_body(jb.src, jb.img, jb.rows, jb.cols, jb.mode, jb.inv);
 }
 
-__global__ void k_prep_jobs(const PrepJobs jobs) {
-  const PrepJob jb = jobs.j[blockIdx.y];
-  const int rows = jb.rows, cols = jb.cols, mode = jb.mode;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= rows * cols) return;
-  float v;
-  if (mode == 4) {                     // clear job: rows * cols 16-bit words of zeros (no source)
-    v = 0.f;
-  } else if (mode <= 1) {
-    const int n = idx / cols, k = idx - n * cols;
-    const int kk = mode == 1 ? (k & ~31) + perm32(k & 31) : k;
-    v = jb.src[(int64_t)n * cols + kk];
-  } else {
-    const int n = idx / rows, k = idx - n * rows;
-    const int kk = mode == 2 ? (k & ~31) + perm32(k & 31) : k;
-    v = jb.src[(int64_t)kk * cols + n];
-  }
-  jb.dst[idx] = (__bf16)v;
+// the image and clear items of a plan (prep_plan.hpp): tiles of 32 source rows, each source read once
+__global__ __launch_bounds__(256) void k_prep_jobs(const PrepJobs jobs, const PrepPlan pl) {
+  __shared__ __attribute__((aligned(16))) float tile[PREP_TILE_LDS];
+  const PrepSeg s = prep_find_seg(pl, blockIdx.x);
+  prep_image_item(jobs, pl, s, (int)blockIdx.x - s.first, tile);
 }
 
 __global__ void k_transpose_f32(const float* __restrict__ src, float* __restrict__ dst, int rows,
@@ -745,14 +733,10 @@ int transpose_f32(const float* src, float* dst, int rows, int cols, hipStream_t 
   return check_launch("k_transpose_f32");
 }
 int prep_jobs_launch(const PrepJobs& jobs, hipStream_t st) {
-  if (jobs.n == 0) return PCA_OK;
-  int maxe = 0;
-  for (int i = 0; i < jobs.n; ++i) {
-    const int e = jobs.j[i].rows * jobs.j[i].cols;
-    maxe = e > maxe ? e : maxe;
-  }
-  hipLaunchKernelGGL(k_prep_jobs, dim3((unsigned)cdiv(maxe, 256), (unsigned)jobs.n), dim3(256), 0,
-                     st, jobs);
+  PrepPlan pl;
+  prep_plan(jobs, Mab0PrepJobs{}, PackJob{}, &pl);
+  if (pl.blocks == 0) return PCA_OK;
+  hipLaunchKernelGGL(k_prep_jobs, dim3((unsigned)pl.blocks), dim3(256), 0, st, jobs, pl);
   return check_launch("k_prep_jobs");
 }
 int prep_weight_f8(const float* src, void* dst, int rows, int cols, int mode, float* inv_scale,

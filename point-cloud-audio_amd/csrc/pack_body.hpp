@@ -27,39 +27,53 @@ inline int pack_blocks(const PackJob& j) { return j.bx * j.B; }
 
 // block = set * bx + x : the work of workgroup (x, set) of k_pack_2d / k_pack_3d
 __device__ __forceinline__ void pack_body(const PackJob& a, int block) {
+  // The chain is cursor -> idx[b] -> labels / nt_valid / spec.  Requests are ordered by what they depend on:
+  // the cursor's two words and the axis values (farr / tarr: no item in their index) go out together, then
+  // idx, then everything behind the item as one batch.
   const int b = block / a.bx, x = block - b * a.bx;
-  const int64_t* idx = a.idx;
+  const int e = x * 256 + threadIdx.x;               // 2-D: bin f; 3-D: point index t*F + f (time-major)
+  const bool lead = x == 0 && threadIdx.x == 0;
+  const bool want_label = lead && a.labels != nullptr && a.labels_out != nullptr;
   // device cursor: batch number (step - base) of a pre-staged index sequence, so that a
   // captured step needs no per-step index upload
-  if (a.step_dev != nullptr) idx += (int64_t)(a.step_dev[0] - a.base_dev[0]) * a.B;
-  const int64_t item = idx[b];
+  int32_t step = 0, base = 0;
+  if (a.step_dev != nullptr) {
+    step = a.step_dev[0];
+    base = a.base_dev[0];
+  }
   if (a.kind == 2) {
-    if (a.labels != nullptr && a.labels_out != nullptr && x == 0 && threadIdx.x == 0)
-      a.labels_out[b] = a.labels[item];
-    const int f = x * 256 + threadIdx.x;
-    if (f >= a.F) return;
-    float2 p;
-    p.x = a.farr[f];
-    p.y = a.spec[f * a.stride_f + item * a.stride_t];
-    reinterpret_cast<float2*>(a.out)[(int64_t)b * a.F + f] = p;
+    const bool live = e < a.F;
+    const float fa = live ? a.farr[e] : 0.f;
+    const int64_t item = a.idx[(int64_t)(step - base) * a.B + b];
+    const int64_t lab = want_label ? a.labels[item] : 0;
+    const float sp = live ? a.spec[e * a.stride_f + item * a.stride_t] : 0.f;
+    if (want_label) a.labels_out[b] = lab;
+    if (live) reinterpret_cast<float2*>(a.out)[(int64_t)b * a.F + e] = float2{fa, sp};
     return;
   }
   // variable-size sets: chunk s holds nt_valid[s] <= Nt frames; time-major point order makes
   // its points a prefix of the padded set, the padding rows are written as zeros
   const int Nt = a.Nt, F = a.F;
-  const int nt = a.nt_valid != nullptr ? (a.nt_valid[item] < Nt ? a.nt_valid[item] : Nt) : Nt;
-  if (x == 0 && threadIdx.x == 0) {
-    if (a.labels != nullptr && a.labels_out != nullptr) a.labels_out[b] = a.labels[item];
+  const bool live = e < F * Nt;
+  const int t = e / F, f = e - t * F;
+  const float fa = live ? a.farr[f] : 0.f;
+  const float ta = live ? a.tarr[t] : 0.f;
+  const int64_t item = a.idx[(int64_t)(step - base) * a.B + b];
+  const int64_t lab = want_label ? a.labels[item] : 0;
+  const int ntv = a.nt_valid != nullptr ? a.nt_valid[item] : Nt;
+  const int nt = ntv < Nt ? ntv : Nt;
+  const bool ok = live && t < nt;
+  // (spec is read for valid frames only, as before: the one request that waits for nt_valid)
+  const float sp = ok ? a.spec[f * a.stride_f + t * a.stride_t + item * a.stride_s] : 0.f;
+  if (lead) {
+    if (want_label) a.labels_out[b] = lab;
     if (a.lengths_out != nullptr) a.lengths_out[b] = nt * F;
   }
-  const int p = x * 256 + threadIdx.x;               // point index = t*F + f (time-major)
-  if (p >= F * Nt) return;
-  const int t = p / F, f = p - t * F;
-  float* o = a.out + ((int64_t)b * F * Nt + p) * 3;
-  const bool ok = t < nt;
-  o[0] = ok ? a.farr[f] : 0.f;
-  o[1] = ok ? a.tarr[t] : 0.f;
-  o[2] = ok ? a.spec[f * a.stride_f + t * a.stride_t + item * a.stride_s] : 0.f;
+  if (!live) return;
+  float* o = a.out + ((int64_t)b * F * Nt + e) * 3;
+  o[0] = ok ? fa : 0.f;
+  o[1] = ok ? ta : 0.f;
+  o[2] = sp;
 }
 
 // hand-off of a deferred pack (features.hip; thread-local: the one hand-off between public calls)

@@ -1,7 +1,7 @@
 // Weight images: the bf16 / fp8 / transposed-fp32 copies of the parameters the fused kernels read, the job
 // tables that convert a whole step's images in one launch, and the table (WeightImages) through which a
 // block finds an image its caller has already made.  Kernels: mab1_bf16.hip (prep_*), mab0_bf16.hip
-// (the query-side preparation, prep_all_launch).
+// (the query-side preparation, prep_all_launch); the plan and the image bodies they run: prep_plan.hpp.
 #pragma once
 #include "pca_common.h"
 
@@ -81,7 +81,7 @@ int weight_image2(const WeightImages* t, const float* src0, __bf16** dst0, int m
                   __bf16** dst1, int mode1, int rows, int cols, hipStream_t st);
 int mab1_fwd_wo_mode(const pca_mab_shape& s);        // image mode of fc_o the mab1 forward asks for
 // the weight images AND the query-side tensors of a step in ONE launch (both depend on the
-// parameters only; blockIdx.y selects the job, the two kinds share the grid)
+// parameters only; the launch is a plan of segments over one flat block index: prep_plan.hpp)
 int prep_all_launch(const PrepJobs& W, const Mab0PrepJobs& Q, hipStream_t st);
 
 }  // namespace pca

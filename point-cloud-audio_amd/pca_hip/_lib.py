@@ -229,6 +229,9 @@ SIGNATURES = {
 DEBUG_SIGNATURES = {
     "pca_debug_tail_plan": (C.c_int, [c_i64p, C.c_int, c_i64p, C.c_int]),
     "pca_debug_mid_nparts": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "pca_debug_prep_plan": (C.c_int, [c_i64p, C.c_int, c_i64p, C.c_int]),
+    "pca_debug_prep_images": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, c_vp]),
 }
 
 _lib = None
