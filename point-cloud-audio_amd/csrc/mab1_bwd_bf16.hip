@@ -30,6 +30,36 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 constexpr int TP = M1_TP;
 constexpr int NB = M1_NB;
 
+// ---- bf16 tile operands in 16-byte pieces ----
+// In the accumulator's shape lane (r, g) holds features 16t + 4g .. + 3 of point r: 8 bytes.  Tiles 2s and 2s + 1 of a
+// point are 64 contiguous bytes, and lane group g moves the 16-byte chunk chunk_of(g) of them: v_permlane16_swap
+// exchanges the odd 16-lane rows of its first operand with the even rows of its second, so with the first tile's dword
+// in front and the second tile's behind, groups 0 and 2 receive their odd neighbour's part of the first tile (chunks
+// 0, 1) and groups 1 and 3 their even neighbour's part of the second (chunks 2, 3).  The exchange is its own inverse:
+// a chunk as loaded goes back into the two tiles' fragments by the same two swaps.  The lanes that exchange hold the
+// same point, so a row's `live` guard holds for both.
+__device__ __forceinline__ int chunk_of(int g) { return ((g & 1) << 1) | (g >> 1); }
+__device__ __forceinline__ u32x4 frag_swap(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1) {
+  const auto x = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
+  const auto y = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
+  return u32x4{x[0], y[0], x[1], y[1]};
+}
+// this lane's four features of tiles 2s (a) and 2s + 1 (b) -> features 32s + 8 chunk_of(g) .. + 7
+__device__ __forceinline__ u32x4 to_chunk(bf16x4 a, bf16x4 b) {
+  const uint2 ua = __builtin_bit_cast(uint2, a), ub = __builtin_bit_cast(uint2, b);
+  return frag_swap(ua.x, ua.y, ub.x, ub.y);
+}
+__device__ __forceinline__ void from_chunk(u32x4 w, bf16x4& a, bf16x4& b) {
+  const u32x4 v = frag_swap(w[0], w[1], w[2], w[3]);
+  a = __builtin_bit_cast(bf16x4, uint2{v[0], v[1]});
+  b = __builtin_bit_cast(bf16x4, uint2{v[2], v[3]});
+}
+// the two halves of a chunk that was loaded as two fragments (the instances that keep the 8-byte form)
+__device__ __forceinline__ u32x4 two_frags(bf16x4 a, bf16x4 b) {
+  const uint2 ua = __builtin_bit_cast(uint2, a), ub = __builtin_bit_cast(uint2, b);
+  return u32x4{ua.x, ua.y, ub.x, ub.y};
+}
+
 struct Mab1BwdArgs {
   const void* dY;           // [B, N, D] fp32, or bf16 when ABF
   const __bf16* QpS;        // [B*N][D]
@@ -79,6 +109,9 @@ __global__ __launch_bounds__((64 * BwdWaves<WANT_DX, FUSE_KV>::value),
 void k_mab1_bwd(const Mab1BwdArgs a) {
   constexpr int NW = BwdWaves<WANT_DX, FUSE_KV>::value, NT = 64 * NW, SUBS = NW / 4;
   constexpr int DT = D / 16, KS = D / 32, ROWB = D * 2, HM = KS * MI;
+  // bf16 tile operands move as 16-byte chunks; the fp32-activation instances keep their form (fp32 dY is 16 bytes
+  // per lane as it is, and their bf16 Qp loads and dZ / dQp / dOs stores stay 8-byte fragments)
+  constexpr bool WIDE = ABF;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* sWoT = smem;
   char* sKp = sWoT + D * ROWB;
@@ -210,23 +243,26 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
 #pragma unroll
       for (int w = 0; w < D / 128; ++w)
         bits[nb][w] = a.mask[mab1_mask_index<D>(b, a.tiles_per_set, tile, wave, nb, w, lane)];
-    // dY^T tiles as loaded (bf16x4 when ABF; fp32 dY lands in dO itself).  Unconditional - row[] is
-    // clamped for padding points - and zeroed at the use
+    // dY^T tiles as loaded (bf16: the 16-byte chunk chunk_of(g) of tiles 2s, 2s + 1; fp32 dY lands in dO itself).
+    // Unconditional - row[] is clamped for padding points - and zeroed at the use
     f32x4 dO[DT][NB];
-    bf16x4 dyh[ABF ? DT : 1][NB];
+    u32x4 dyw[WIDE ? KS : 1][NB];
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
+    for (int nb = 0; nb < NB; ++nb) {
+      if (WIDE) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s)
+          dyw[WIDE ? s : 0][nb] = *reinterpret_cast<const u32x4*>(
+              reinterpret_cast<const __bf16*>(a.dY) + row[nb] * D + 32 * s + 8 * chunk_of(g));
+        continue;
+      }
 #pragma unroll
       for (int t = 0; t < DT; ++t) {
-        if (ABF) {
-          dyh[ABF ? t : 0][nb] = *reinterpret_cast<const bf16x4*>(
-              reinterpret_cast<const __bf16*>(a.dY) + row[nb] * D + 16 * t + 4 * g);
-        } else {
-          const float4 v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.dY) +
-                                                            row[nb] * D + 16 * t + 4 * g);
-          dO[t][nb] = f32x4{v.x, v.y, v.z, v.w};
-        }
+        const float4 v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.dY) +
+                                                          row[nb] * D + 16 * t + 4 * g);
+        dO[t][nb] = f32x4{v.x, v.y, v.z, v.w};
       }
+    }
     // layer 1: this lane's points for the Qp recomputation, and the points of the A operand below;
     // components at or past dq read component dq - 1 and are discarded
     float xq[NB][3], xa[8];
@@ -243,12 +279,16 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
     }
     // the saved Qp, features 32j + perm32(8g + .) of this lane's points: head 0's with the batch, head j + 1's
     // while head j is worked on (the whole tile's - 32 registers through the fc_o adjoint - spilled)
-    bf16x4 qs[FUSE_WQ ? 1 : KS][NB][2];
+    // (with bf16 activations as one chunk, swapped into the two fragments at the use)
+    u32x4 qs[FUSE_WQ ? 1 : KS][NB];
     auto request_qp = [&](const int j) __attribute__((always_inline)) {
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
-        qs[j][nb][0] = *reinterpret_cast<const bf16x4*>(a.QpS + row[nb] * D + 32 * j + 4 * g);
-        qs[j][nb][1] = *reinterpret_cast<const bf16x4*>(a.QpS + row[nb] * D + 32 * j + 16 + 4 * g);
+        if (WIDE)
+          qs[j][nb] = *reinterpret_cast<const u32x4*>(a.QpS + row[nb] * D + 32 * j + 8 * chunk_of(g));
+        else
+          qs[j][nb] = two_frags(*reinterpret_cast<const bf16x4*>(a.QpS + row[nb] * D + 32 * j + 4 * g),
+                                *reinterpret_cast<const bf16x4*>(a.QpS + row[nb] * D + 32 * j + 16 + 4 * g));
       }
     };
     if (!FUSE_WQ) request_qp(0);
@@ -291,12 +331,18 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       bf16x4 dzh[DT];
+      bf16x4 dyf[WIDE ? DT : 1];          // the chunks back in the fragments' shape
+      if (WIDE) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s)
+          from_chunk(dyw[WIDE ? s : 0][nb], dyf[WIDE ? 2 * s : 0], dyf[WIDE ? 2 * s + 1 : 0]);
+      }
 #pragma unroll
       for (int t = 0; t < DT; ++t) {
         const uint32_t m4 = bits[nb][t / 8] >> ((t & 7) * 4);
         if (ABF) {
           // bf16 -> fp32 -> bf16 returns the bits it was given, so dZ is a select on the loaded words
-          bf16x4 h4 = dyh[ABF ? t : 0][nb];
+          bf16x4 h4 = dyf[WIDE ? t : 0];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             if (!live[nb]) h4[e] = (__bf16)0.f;
@@ -319,7 +365,22 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
       // the materialised form: one block of stores per 16-row group, behind both groups' converts (a branch
       // between them split the tiles' registers)
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
+      for (int nb = 0; nb < NB; ++nb) {
+        if (WIDE) {
+          // (the swaps in front of the row's guard: every lane takes part in them)
+          u32x4 zc[KS];
+#pragma unroll
+          for (int s = 0; s < KS; ++s) {
+            const bf16x8 z = dzb[s][nb];
+            zc[s] = to_chunk(bf16x4{z[0], z[1], z[2], z[3]}, bf16x4{z[4], z[5], z[6], z[7]});
+          }
+          if (live[nb]) {
+#pragma unroll
+            for (int s = 0; s < KS; ++s)
+              *reinterpret_cast<u32x4*>(a.dZ + row[nb] * D + 32 * s + 8 * chunk_of(g)) = zc[s];
+          }
+          continue;
+        }
         if (live[nb]) {
 #pragma unroll
           for (int t = 0; t < DT; ++t) {
@@ -328,6 +389,7 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
                 (t & 1) ? bf16x4{z[4], z[5], z[6], z[7]} : bf16x4{z[0], z[1], z[2], z[3]};
           }
         }
+      }
     }
     bf16x8 xaug;
     if (FUSE_WQ) {
@@ -398,9 +460,12 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
             qhi[e] = (__bf16)(wh.w + wh.x * xq[nb][0] + wh.y * xq[nb][1] + wh.z * xq[nb][2] +
                               0.f * 0.f);
           }
+        } else if (WIDE) {
+          from_chunk(qs[FUSE_WQ ? 0 : j][nb], qlo, qhi);
         } else {
-          qlo = qs[FUSE_WQ ? 0 : j][nb][0];
-          qhi = qs[FUSE_WQ ? 0 : j][nb][1];
+          const u32x4 w = qs[FUSE_WQ ? 0 : j][nb];
+          qlo = __builtin_bit_cast(bf16x4, uint2{w[0], w[1]});
+          qhi = __builtin_bit_cast(bf16x4, uint2{w[2], w[3]});
         }
         bf16x8 qb;
 #pragma unroll
@@ -505,12 +570,24 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
       // reduced per head above
     } else {
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
+      for (int nb = 0; nb < NB; ++nb) {
+        if (WIDE) {
+          u32x4 qc[KS];
+#pragma unroll
+          for (int s = 0; s < KS; ++s) qc[s] = to_chunk(pack4(dO[2 * s][nb]), pack4(dO[2 * s + 1][nb]));
+          if (live[nb]) {
+#pragma unroll
+            for (int s = 0; s < KS; ++s)
+              *reinterpret_cast<u32x4*>(a.dQp + row[nb] * D + 32 * s + 8 * chunk_of(g)) = qc[s];
+          }
+          continue;
+        }
         if (live[nb]) {
 #pragma unroll
           for (int t = 0; t < DT; ++t)
             *reinterpret_cast<bf16x4*>(a.dQp + row[nb] * D + 16 * t + 4 * g) = pack4(dO[t][nb]);
         }
+      }
     }
 
     if (WANT_DX) {
@@ -533,7 +610,19 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
         }
       }
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
+      for (int nb = 0; nb < NB; ++nb) {
+        if (WIDE) {
+          u32x4 xc[KS];
+#pragma unroll
+          for (int s = 0; s < KS; ++s) xc[s] = to_chunk(pack4(dx[2 * s][nb]), pack4(dx[2 * s + 1][nb]));
+          if (live[nb]) {
+#pragma unroll
+            for (int s = 0; s < KS; ++s)
+              *reinterpret_cast<u32x4*>(reinterpret_cast<__bf16*>(a.dX) + row[nb] * D + 32 * s +
+                                        8 * chunk_of(g)) = xc[s];
+          }
+          continue;
+        }
         if (live[nb]) {
 #pragma unroll
           for (int t = 0; t < DT; ++t) {
@@ -544,6 +633,7 @@ void k_mab1_bwd(const Mab1BwdArgs a) {
                      float4{dx[t][nb][0], dx[t][nb][1], dx[t][nb][2], dx[t][nb][3]};
           }
         }
+      }
     }
   };
   if (t_first < t_last && t_first < total_tiles) {

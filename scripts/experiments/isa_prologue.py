@@ -13,7 +13,8 @@ order of global loads, vmcnt waits, LDS stores and barriers from the kernel's en
            MFMAs - to the first s_barrier behind them (k_mab1_bwd: through the head loop and the dX stage)
 --counts   no sequence: one line per kernel with its global loads, vmcnt waits, vmcnt(0) waits, the vmcnt(0)
            waits that have a global load among the 8 instructions in front of them (a load waited for where it
-           was issued: a serial round trip), VGPRs and scratch bytes
+           was issued: a serial round trip), the global loads and the global stores by width (4 / 8 / 12 / 16 bytes
+           per lane; narrower ones count as 4), VGPRs and scratch bytes
 """
 import re
 import subprocess
@@ -125,6 +126,17 @@ def counts(lines):
     return loads, len(waits), len(full), behind
 
 
+def by_width(lines, kind):
+    """Global `kind` ("load" / "store") instructions by bytes per lane: "n4/n8/n12/n16"."""
+    n = {4: 0, 8: 0, 12: 0, 16: 0}
+    for op, _ in ops(lines):
+        if not (op.startswith("global_" + kind) or op.startswith("buffer_" + kind)) or "lds" in op:
+            continue
+        w = re.search(r"dwordx(\d)", op)
+        n[4 * int(w.group(1)) if w else 4] += 1
+    return "/".join(str(n[k]) for k in (4, 8, 12, 16))
+
+
 def main():
     flags = [a for a in sys.argv[1:] if a.startswith("--")]
     rest = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -133,7 +145,7 @@ def main():
     listing = to_mfma if "--to-mfma" in flags else prologue
     if "--counts" in flags:
         print(f"{'global loads':>12} {'vmcnt waits':>11} {'vmcnt(0)':>8} {'(0) <= 8 behind a load':>22} "
-              f"{'VGPRs':>5} {'scratch B':>9}  kernel")
+              f"{'loads 4/8/12/16 B':>17} {'stores 4/8/12/16 B':>18} {'VGPRs':>5} {'scratch B':>9}  kernel")
     for sym, (lines, meta) in sorted(ks.items(), key=lambda kv: demangle(kv[0])):
         name = demangle(sym)
         if wanted and not any(w in name for w in wanted):
@@ -141,7 +153,8 @@ def main():
         if "--counts" in flags:
             lo, wa, fu, be = counts(lines)
             short = re.sub(r"\(.*$", "", name.replace("(anonymous namespace)::", "").replace("void ", ""))
-            print(f"{lo:12d} {wa:11d} {fu:8d} {be:22d} {meta.get('vgpr_count', -1):5d} "
+            print(f"{lo:12d} {wa:11d} {fu:8d} {be:22d} {by_width(lines, 'load'):>17} {by_width(lines, 'store'):>18} "
+                  f"{meta.get('vgpr_count', -1):5d} "
                   f"{meta.get('private_segment_fixed_size', -1):9d}  {short}")
             continue
         print(name)
