@@ -257,6 +257,43 @@ int pca_importance_points(const float* spec, int64_t stride_f, int64_t stride_t,
 int pca_select_points(const float* X, const float* key, const int32_t* lengths, int B, int N,
                       int din, int K, float* out, int32_t* sel, void* stream);
 
+/* What counts as a spectral peak, and whether it is refined (pca_peak_points). */
+typedef struct PcaPeakSpec {
+  int32_t radius_f;   /* 1..16 bins  */
+  int32_t radius_t;   /* 0..4 frames */
+  float   rel_floor;  /* >= 0, +inf = off: keep v >= vmax - rel_floor (one fp32 subtraction) */
+  float   abs_floor;  /* -inf = off: keep v >= abs_floor */
+  int32_t refine;     /* 0: bin centre and bin value; 1: parabolic refinement along frequency */
+} PcaPeakSpec;
+
+/* The spectral peaks of packed point sets, refined, ranked and packed: the first off-grid point sets
+ * replaces: nothing - no reference counterpart (the reference keeps grid points only).
+ * X[B, N, din] packed sets as every pack and frame launch writes them, N = F*Nt <= 16384, point p = t*F + f,
+ * value = column din-1, frequency = column 0, time = column 1 (din = 3; din = 2 needs Nt = 1); F >= 3,
+ * 1 <= K <= N.  lengths_in (nullable, device int32[B]): set b holds lengths_in[b] / F whole frames (a multiple
+ * of F; taken into [F, N] and rounded down to whole frames), nothing beyond them is read.  out must not
+ * overlap X.
+ * Peak: order the points of a set by the pair (value, -p).  Point (f, t), 1 <= f <= F-2, is a peak iff its pair
+ * is greater than that of every other point of the window [f-radius_f, f+radius_f] x [t-radius_t, t+radius_t]
+ * clipped to the set's valid frames and bins (edge bins are neighbours only), and its value passes both
+ * floors; vmax = the maximum over the set's valid non-NaN points.  A tie goes to the lower point index, so
+ * one point of a plateau inside a window survives; NaN is never a peak and loses every comparison.
+ * Order: raw bin value descending, equal values (-0 == +0) in ascending point order - max-K's order
+ * (pca_subsample_points mode 0, pca_select_points).  The first min(count, K) peaks are written.
+ * out[B, K, din]: rows at and beyond lengths_out[b] are zeros.  lengths_out[b] = clamp(count, 1, K);
+ * count_out (nullable) [B] = the number of peaks before truncation; sel (nullable) [B, K] = the point index,
+ * -1 behind the last row.  A set without any peak yields one row, the first valid point in max-K order,
+ * unrefined (count 0, length 1: the engine needs lengths >= 1).
+ * refine = 1, in fp64 from the fp32 inputs, each result rounded to fp32 once: a, b, c = the values at f-1, f,
+ * f+1 of the frame, delta = 0.5 (a - c) / ((a - b) + (c - b)) in (-1/2, 1/2]; frequency = x0 + delta (x+ - x0)
+ * for delta >= 0, else x0 + delta (x0 - x-), on the column-0 entries of the three points (so a non-uniform
+ * axis is served); value = b - 0.25 (a - c) delta; a, b or c not finite: the raw row.  Time is copied.
+ * One workgroup per set; values and the compacted peak keys in LDS; no atomics: the same arguments give the
+ * same bits. */
+int pca_peak_points(const float* X, const int32_t* lengths_in, int B, int F, int Nt, int din,
+                    const PcaPeakSpec* spec, int K, float* out, int32_t* lengths_out,
+                    int32_t* count_out, int32_t* sel, void* stream);
+
 /* 2-D point sets from per-frame tables (the output of pc_maxK / pc_randK)
  * replaces: Code/dataset.py:76-80  ESC_pc_ss.__getitem__ (+ default_collate)
  * x_tk[T, K] values and f_tk[T, K] coordinates, frame-major; out[B, K, 2] =

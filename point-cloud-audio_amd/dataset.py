@@ -23,7 +23,7 @@ import pca_hip
 __all__ = ["ESC_baseline", "ESC_pc", "ESC_pc_ss", "ESC_baseline_temporal",
            "ESC_baseline_temporal_maxK", "ESC_pc_temp", "ESC_pc_temp_maxKSS",
            "ESC_pc_temp_randKSS", "ESC_pc_temp_importancerandKSS", "ESC_wave_pc",
-           "ESC_wave_pc_temp", "DeviceBatchLoader"]
+           "ESC_wave_pc_temp", "PeakPoints", "DeviceBatchLoader"]
 
 
 def _dev(device) -> torch.device:
@@ -699,6 +699,118 @@ class ESC_wave_pc_temp(ESC_wave_pc):
         self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db, mix_targets, mix_labels)
         self._setup_mask(freq_masks, freq_mask_width, time_masks, time_mask_width, mask_mode)
         self.tarr = np.linspace(0, (self.hop / fs) * self._ntemp, self._ntemp)
+
+
+class PeakPoints(Dataset):
+    """The K strongest spectral peaks of every set of a dense point-set dataset, refined off the grid: a view
+    over ``ESC_pc``, ``ESC_pc_temp`` (its variable-length chunks included: their lengths are whole frames),
+    ``ESC_wave_pc`` or ``ESC_wave_pc_temp`` with any augmentation but ``mask_mode="drop"``.  No reference
+    counterpart: the reference's sets are grid points (all bins, or a subset of them).
+
+    ``batch`` runs the inner dataset's ``batch`` into a dense buffer the view owns (one per batch size, made
+    on first use) and ``pca_hip.peak_points`` from there into ``out`` [B, K, din]: two launches.  A set holds
+    min(number of peaks, K) rows - at least one: a set without peaks yields its largest point - so the view
+    is ``variable_length``: ``batch`` returns (points, labels [, labels2, weight][, sel][, count], lengths)
+    and the ``Trainer`` / ``Evaluator`` hand the counts to the step.  K, radius_f, radius_t, rel_floor,
+    abs_floor, refine: ``pca_hip.peak_points``."""
+
+    batch_seq = None        # two launches per batch, the second reading the first: indices per step
+
+    def __init__(self, inner, K, radius_f=1, radius_t=0, rel_floor=float("inf"), abs_floor=float("-inf"),
+                 refine=True):
+        if isinstance(inner, ESC_wave_pc):
+            self.F, self.Nt, self.din = inner.F, inner._ntemp, 2 if inner.tarr is None else 3
+            if inner.variable_length:
+                raise ValueError("PeakPoints: mask_mode='drop' removes points from the sets, which breaks "
+                                 "the F x Nt grid that peak picking reads its neighbours from; use "
+                                 "mask_mode='floor'")
+        elif isinstance(inner, ESC_pc_temp) and not isinstance(inner, _TempSS):
+            self.F, self.Nt, self.din = int(inner.x.shape[0]), int(inner.x.shape[1]), 3
+        elif isinstance(inner, ESC_pc):
+            self.F, self.Nt, self.din = int(inner.x.shape[0]), 1, 2
+        else:
+            raise TypeError(f"PeakPoints needs a dense point-set dataset (ESC_pc, ESC_pc_temp, ESC_wave_pc, "
+                            f"ESC_wave_pc_temp), got {type(inner).__name__}")
+        self.inner, self.K = inner, int(K)
+        if self.F < 3 or not 1 <= self.K <= self.F * self.Nt:
+            raise ValueError(f"PeakPoints: F = {self.F} (>= 3), K = {self.K} (1 .. {self.F * self.Nt})")
+        pca_hip.ops.peak_spec(radius_f, radius_t, rel_floor, abs_floor, refine)       # ValueError
+        self.spec = dict(radius_f=int(radius_f), radius_t=int(radius_t), rel_floor=float(rel_floor),
+                         abs_floor=float(abs_floor), refine=bool(refine))
+        self._dense = {}                  # B -> (X [B, N, din], lengths int32 [B] or None)
+
+    variable_length = True
+
+    @property
+    def num_points(self) -> int:
+        return self.K
+
+    @property
+    def stochastic(self) -> bool:
+        return bool(getattr(self.inner, "stochastic", False))
+
+    @property
+    def soft_targets(self) -> bool:
+        return bool(getattr(self.inner, "soft_targets", False))
+
+    @property
+    def _draw(self):
+        """The inner dataset's draw number (the ``Trainer`` checkpoints it and puts it back)."""
+        return self.inner._draw
+
+    @_draw.setter
+    def _draw(self, value):
+        self.inner._draw = value
+
+    @property
+    def labels(self):
+        return self.inner.labels
+
+    def __len__(self):
+        return len(self.inner)
+
+    def _resident(self):
+        return self.inner._resident()
+
+    def plain(self, *args, **kw):
+        """The view over ``inner.plain()`` (every augmentation off); an inner dataset without one is
+        deterministic already and the view itself is returned."""
+        if not hasattr(self.inner, "plain"):
+            return self
+        return PeakPoints(self.inner.plain(*args, **kw), self.K, **self.spec)
+
+    def batch(self, idx: torch.Tensor, out=None, labels_out=None, lengths_out=None, draw_dev=None,
+              labels2_out=None, weight_out=None, want_sel: bool = False, want_count: bool = False):
+        """idx int64[B] on the device -> (points [B, K, din] float32 - zero rows behind a set's last peak -,
+        labels int64[B] [, labels2 int64[B], weight float32[B] with ``soft_targets``][, sel int32 [B, K]]
+        [, count int32 [B]], lengths int32 [B])."""
+        B = int(idx.numel())
+        if B not in self._dense:
+            with torch.cuda.device(idx.device):
+                self._dense[B] = (
+                    torch.empty((B, self.F * self.Nt, self.din), dtype=torch.float32, device=idx.device),
+                    torch.zeros(B, dtype=torch.int32, device=idx.device)
+                    if getattr(self.inner, "variable_length", False) else None)
+        dense, ln = self._dense[B]
+        kw = {}
+        if ln is not None:
+            kw["lengths_out"] = ln
+        if isinstance(self.inner, ESC_wave_pc):
+            kw["draw_dev"] = draw_dev
+            if self.inner.soft_targets:
+                kw.update(labels2_out=labels2_out, weight_out=weight_out)
+        res = self.inner.batch(idx, out=dense, labels_out=labels_out, **kw)
+        soft = tuple(res[2:4]) if self.soft_targets else ()
+        peaks = pca_hip.peak_points(dense, self.F, self.Nt, self.K, lengths=ln, out=out,
+                                    lengths_out=lengths_out, want_sel=want_sel, want_count=want_count,
+                                    **self.spec)
+        return (peaks[0], res[1]) + soft + tuple(peaks[2:]) + (peaks[1],)
+
+    def __getitem__(self, idx):
+        """The un-padded [lengths, din] rows and the label."""
+        dev = self._resident()[0].device
+        res = self.batch(torch.tensor([int(idx)], dtype=torch.int64, device=dev))
+        return res[0][0, :int(res[-1][0])].cpu(), res[1][0].cpu()
 
 
 class DeviceBatchLoader:

@@ -30,6 +30,9 @@ The other set-model experiments run here at batch scale too:
 * ``attention_sweep``: sets reduced to the K points the model's own pooling attention weighs most
   (``STEngine.attention``, ``pca_hip.select_points``); no reference counterpart - a third curve beside
   random-K and max-K;
+* ``peak_sweep``: sets reduced to their K strongest spectral peaks, refined off the grid
+  (``pca_hip.peak_points``), evaluated as padded sets with their point counts; no reference counterpart
+  - a fourth curve;
 * ``reframe_sweep_temporal``: the (Fs, N) re-framing of the 3ST, Code/pc_temp3d_eval.py:56-107.
 * ``clip_accuracy``: the clip-level scores the datasets' literature reports (majority vote and mean
   log-probability over a clip's frames or chunks, ``pca_hip.clip_aggregate``) next to the frame score;
@@ -75,8 +78,8 @@ from pca_hip.baseline import SEL_ALL, BaselineEngine
 from pca_hip.trainer import STEngine, st_config
 
 __all__ = ["reframe_sweep", "framewise_dataset", "default_list_K", "sweep_draw", "subsample_sweep",
-           "importance_sweep", "attention_sweep", "chunk_plan", "temporal_axes", "temporal_dataset",
-           "reframe_sweep_temporal", "baseline_subsample_sweep", "baseline_frames",
+           "importance_sweep", "attention_sweep", "peak_sweep", "most_peaks", "chunk_plan",
+           "temporal_axes", "temporal_dataset", "reframe_sweep_temporal", "baseline_subsample_sweep", "baseline_frames",
            "baseline_chunks", "baseline_reframe_sweep", "baseline_reframe_sweep_temporal",
            "trim_dB_of", "trim_clips", "clip_accuracy"]
 
@@ -238,11 +241,13 @@ def _engine_cache(model, npts: int, mode: int, dev, *bufs):
 
 
 def _run_pieces(model, npts: int, din: int, mode: int, cap: int, pieces, select,
-                counts: torch.Tensor) -> None:
+                counts: torch.Tensor, with_lengths: bool = False) -> None:
     """Evaluate ``pieces`` = [(slot, draw, p0, p1)] (set positions p0 <= p < p1 selected with draw
     number ``draw``, their correct predictions tallied into counts[slot]) through engine calls of at
     most ``cap`` sets.  ``select(slot, draw, pos, out, labels_out)`` writes the point sets of the
     positions ``pos`` (device int64) into ``out`` [n, npts, din] and their labels into labels_out.
+    ``with_lengths``: every call also has an int32 buffer of point counts; ``select`` takes its slice as a
+    sixth argument, ``lengths_out``, and fills it, and the forward reads it (padded sets).
     Enqueues only: nothing here waits for the device."""
     calls, cur, fill = [], [], 0
     for slot, draw, p0, p1 in pieces:
@@ -257,13 +262,15 @@ def _run_pieces(model, npts: int, din: int, mode: int, cap: int, pieces, select,
     if cur:
         calls.append((cur, fill))
     dev = counts.device
-    engines = _engine_cache(model, npts, mode, dev, ((npts, din), torch.float32), ((), torch.int64))
+    bufs = [((npts, din), torch.float32), ((), torch.int64)] + ([((), torch.int32)] if with_lengths else [])
+    engines = _engine_cache(model, npts, mode, dev, *bufs)
     for parts, b in calls:
-        eng, X, lab = engines(b)
+        eng, X, lab, *ln = engines(b)
         for slot, draw, p0, p1, off in parts:
             pos = torch.arange(p0, p1, dtype=torch.int64, device=dev)
-            select(slot, draw, pos, X[off:off + p1 - p0], lab[off:off + p1 - p0])
-        logits = eng.forward(X)
+            select(slot, draw, pos, X[off:off + p1 - p0], lab[off:off + p1 - p0],
+                   *(t[off:off + p1 - p0] for t in ln))
+        logits = eng.forward(X, *ln)
         for slot, draw, p0, p1, off in parts:
             pca_hip.eval_tally(logits[off:off + p1 - p0], lab[off:off + p1 - p0], counts, slot)
 
@@ -529,6 +536,71 @@ def attention_sweep(model, spec, labels, farr, tarr=None, list_K: Optional[Itera
                         [(0, 0, 0, full)], select_of_K(K), counts)
             data[K] = [int(counts.item()) / full, 0]           # the one host read of this K
     out = {"data": data, "list_K": list_K}
+    _write_json(out, json_file)
+    return out
+
+
+def most_peaks(F: int, Nt: int = 1) -> int:
+    """The most peaks a set of Nt frames of F bins can hold: ceil((F - 2) / 2) per frame (two neighbouring
+    bins are never both peaks, and the edge bins never are)."""
+    return (int(F) - 1) // 2 * int(Nt)
+
+
+@torch.no_grad()
+def peak_sweep(model, spec, labels, farr, tarr=None, list_K: Optional[Iterable[int]] = None,
+               radius_f: int = 1, radius_t: int = 0, rel_floor: float = float("inf"),
+               abs_floor: float = float("-inf"), refine: bool = True, batch_size: int = 8,
+               mode: int = _lib.MODE_F32, json_file: Optional[str] = None,
+               sets_per_call: Optional[int] = None):
+    """Accuracy of ``model`` on point sets reduced to their K strongest spectral peaks
+    (``pca_hip.peak_points``: local maxima of the log-magnitude within ``radius_f`` bins and ``radius_t``
+    frames, above the floors, frequency and level refined by a parabola when ``refine``), for every K in
+    ``list_K``.  **No reference counterpart**: a fourth curve beside random-K, max-K and attention-K, and
+    the first whose points leave the STFT grid.
+
+    Arguments as subsample_sweep: FST ``spec`` [F, T] frames with ``tarr`` None, 3ST ``spec`` [F, Nt, S]
+    chunks with ``tarr`` [Nt]; F >= 3.  Default list_K: default_list_K(most_peaks(F, Nt)), the most peaks a
+    set can hold.
+
+    For every K the sets are packed piece by piece, reduced by ``peak_points`` at that K, evaluated by
+    ``STEngine.forward(X, lengths)`` at N = K - a set with fewer than K peaks is padded and its count masks
+    the padding; a set without any peak is its one largest point - and tallied by pca_eval_tally.  One host
+    read per K: the tally and the sum of the point counts together.
+
+    Returns (and, with ``json_file``, writes) the max-K shape with the sets' mean size beside it:
+    ``{"data": {K: [acc, 0]}, "list_K": [...], "mean_points": {K: mean points per scored set}}``."""
+    dev = _model_device(model)
+    x, lab, f32, t32 = _resident_sets(spec, labels, farr, tarr, dev)
+    n_sets, npts_all, din, _ = _set_geometry(x, tarr is not None)
+    F, Nt = int(x.shape[0]), (int(x.shape[1]) if tarr is not None else 1)
+    list_K = _norm_list_K(list_K, most_peaks(F, Nt), npts_all)
+    pca_hip.ops.peak_spec(radius_f, radius_t, rel_floor, abs_floor, refine)          # ValueError
+    full = (n_sets // batch_size) * batch_size
+    data, mean_points = {}, {}
+    full_buf = {}
+
+    def select_of_K(K, acc):
+        def select(slot, draw, pos, out, labels_out, lengths_out):
+            n = pos.numel()
+            if n not in full_buf:              # the full-size sets of a piece
+                full_buf[n] = torch.empty((n, npts_all, din), dtype=torch.float32, device=dev)
+            _pack_sets(x, f32, t32, pos, full_buf[n])
+            pca_hip.peak_points(full_buf[n], F, Nt, K, radius_f, radius_t, rel_floor, abs_floor, refine,
+                                out=out, lengths_out=lengths_out)
+            torch.index_select(lab, 0, pos, out=labels_out)
+            acc[1:] += lengths_out.sum()
+        return select
+
+    for K in list_K:
+        if full == 0:
+            data[K], mean_points[K] = [float("nan"), 0], float("nan")
+            continue
+        acc = torch.zeros(2, dtype=torch.int64, device=dev)         # [correct, points]
+        _run_pieces(model, K, din, mode, _sets_per_call(model, K, mode, sets_per_call),
+                    [(0, 0, 0, full)], select_of_K(K, acc), acc, with_lengths=True)
+        correct, points = acc.tolist()                              # the one host read of this K
+        data[K], mean_points[K] = [correct / full, 0], points / full
+    out = {"data": data, "list_K": list_K, "mean_points": mean_points}
     _write_json(out, json_file)
     return out
 

@@ -85,6 +85,11 @@ class PcaPointMask(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_freq", "freq_width", "n_time", "time_width", "mode")]
 
 
+class PcaPeakSpec(C.Structure):
+    _fields_ = [("radius_f", C.c_int32), ("radius_t", C.c_int32), ("rel_floor", C.c_float),
+                ("abs_floor", C.c_float), ("refine", C.c_int32)]
+
+
 class PcaSoftTargets(C.Structure):
     _fields_ = [("labels2", C.c_void_p), ("weight", C.c_void_p), ("smoothing", C.c_float)]
 
@@ -143,6 +148,8 @@ SIGNATURES = {
                                     c_vp, c_vp]),
     "pca_select_points": (C.c_int, [c_fp, c_fp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_vp,
                                     c_vp]),
+    "pca_peak_points": (C.c_int, [c_fp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PcaPeakSpec),
+                                  C.c_int, c_fp, c_vp, c_vp, c_vp, c_vp]),
     "pca_linear_fwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int64, C.c_int, C.c_int, c_vp]),
     "pca_linear_bwd": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_int64, C.c_int,
                                  C.c_int, c_vp, c_vp]),

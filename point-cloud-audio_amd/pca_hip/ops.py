@@ -1055,6 +1055,71 @@ def select_points(X: torch.Tensor, key: torch.Tensor, K: int,
     return out, sel
 
 
+def peak_spec(radius_f: int = 1, radius_t: int = 0, rel_floor: float = float("inf"),
+              abs_floor: float = float("-inf"), refine: bool = True) -> "_lib.PcaPeakSpec":
+    """``PcaPeakSpec`` checked on the host by the rules of pca_peak_points (``ValueError``)."""
+    radius_f, radius_t, rel_floor, abs_floor = int(radius_f), int(radius_t), float(rel_floor), float(abs_floor)
+    if not 1 <= radius_f <= 16:
+        raise ValueError(f"radius_f {radius_f} outside [1, 16] bins")
+    if not 0 <= radius_t <= 4:
+        raise ValueError(f"radius_t {radius_t} outside [0, 4] frames")
+    if not rel_floor >= 0.0:
+        raise ValueError(f"rel_floor {rel_floor}: >= 0 (inf switches it off)")
+    if abs_floor != abs_floor:
+        raise ValueError("abs_floor is NaN (-inf switches it off)")
+    return _lib.PcaPeakSpec(radius_f, radius_t, rel_floor, abs_floor, int(bool(refine)))
+
+
+def peak_points(X: torch.Tensor, F: int, Nt: int, K: int, radius_f: int = 1, radius_t: int = 0,
+                rel_floor: float = float("inf"), abs_floor: float = float("-inf"), refine: bool = True,
+                lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                lengths_out: Optional[torch.Tensor] = None, want_sel: bool = False,
+                want_count: bool = False):
+    """The K strongest spectral peaks of every packed set (pca_peak_points): X [B, F * Nt, din] float32 as
+    the pack and frame launches write it (point p = t * F + f, value in the last column, frequency in
+    column 0; din 2 needs Nt = 1), F >= 3, 1 <= K <= N <= 16384.
+
+    A peak is a point with 1 <= f <= F - 2 whose (value, -p) is greater than that of every other point within
+    ``radius_f`` bins and ``radius_t`` frames (a tie goes to the lower index; NaN never wins) and whose value
+    is at least ``abs_floor`` and at least the set's maximum minus ``rel_floor``.  Peaks are ranked by raw
+    value, descending, equal values in ascending point order (subsample_points' MAXK rule).  ``refine``:
+    frequency and value come from the parabola through the values at f - 1, f, f + 1 (fp64, rounded once);
+    off: the bin's own row.  ``lengths`` (device int32[B], whole frames): the points at and beyond
+    lengths[b] take no part.
+
+    Returns (out [B, K, din] - rows behind a set's last peak are zeros -, lengths int32 [B] =
+    clamp(number of peaks, 1, K): a set without peaks yields its largest point) [, sel int32 [B, K], the
+    point indices, -1 behind the last][, count int32 [B], the peaks before truncation]; ``out`` and
+    ``lengths_out`` may be passed in (contiguous)."""
+    _need_cuda(X, lengths, out, lengths_out)
+    assert X.dim() == 3 and X.dtype == torch.float32 and X.is_contiguous()
+    B, N, din = X.shape
+    F, Nt, K = int(F), int(Nt), int(K)
+    assert N == F * Nt, (N, F, Nt)
+    if lengths is not None:
+        assert lengths.dtype == torch.int32 and lengths.is_contiguous() and tuple(lengths.shape) == (B,)
+    spec = peak_spec(radius_f, radius_t, rel_floor, abs_floor, refine)
+    with torch.cuda.device(X.device):
+        if out is None:
+            out = torch.empty((B, K, din), dtype=torch.float32, device=X.device)
+        if lengths_out is None:
+            lengths_out = torch.empty(B, dtype=torch.int32, device=X.device)
+        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, K, din)
+        assert lengths_out.dtype == torch.int32 and lengths_out.is_contiguous() \
+            and tuple(lengths_out.shape) == (B,)
+        sel = torch.empty((B, K), dtype=torch.int32, device=X.device) if want_sel else None
+        count = torch.empty(B, dtype=torch.int32, device=X.device) if want_count else None
+        check(lib().pca_peak_points(_ptr(X), _ptr(lengths), B, F, Nt, din, C.byref(spec), K, _ptr(out),
+                                    _ptr(lengths_out), _ptr(count), _ptr(sel), _stream(X)),
+              "pca_peak_points")
+    res = (out, lengths_out)
+    if want_sel:
+        res += (sel,)
+    if want_count:
+        res += (count,)
+    return res
+
+
 def pack_points_2d_ss(x_tk: torch.Tensor, f_tk: torch.Tensor, idx: torch.Tensor,
                       labels: Optional[torch.Tensor] = None,
                       out: Optional[torch.Tensor] = None,
