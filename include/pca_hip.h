@@ -344,6 +344,52 @@ int pca_frame_points(const float* waves, const int64_t* wave_off, const int64_t*
                      const float* farr, const float* tarr, const PcaFrameAug* aug, float* out,
                      int64_t* labels_out, int32_t* meta_out, void* stream);
 
+/* Which points of a framed batch move to where their energy lies, and how far (pca_frame_points_reassigned). */
+typedef struct PcaReassignSpec {
+  int32_t axes;       /* bit 0: frequency, bit 1: time; 1..3.  Bit 1 needs tarr and Nt >= 2 */
+  float   rel_floor;  /* >= 0, +inf = off: reassign a bin iff v >= vmax - rel_floor (one fp32 subtraction),
+                         vmax = the maximum of the FRAME's n_bins values (NaN loses) */
+  float   abs_floor;  /* -inf = off: and v >= abs_floor */
+  float   max_df;     /* (0, 64]: clamp of the frequency shift, in bins */
+  float   max_dt;     /* (0, 4]:  clamp of the time shift, in frames (hops) */
+  float   strength;   /* [0, 1]: the shift is multiplied by it after the clamp */
+} PcaReassignSpec;
+
+/* pca_frame_points with every point written at its reassigned coordinates (Auger-Flandrin time-frequency
+ * reassignment, librosa.reassigned_spectrogram's sign conventions): the value column is unchanged, the
+ * coordinates become real-valued
+ * replaces: nothing - no reference counterpart (the reference keeps grid points only).
+ * Every argument before `spec` is pca_frame_points', with the same meaning, checks, draws, labels_out and
+ * meta_out; additionally n_bins >= 2, and spec->axes bit 1 needs tarr and Nt >= 2.
+ * Frame j of slot b: clip, centre, window w, gain g and norm as pca_frame_points derives them.  x[n] = the
+ * gained samples of the frame, lpad = (n_fft - w) / 2, nw = n - lpad.  Three windows: h[n] the periodic Hann
+ * of the plain launch; dh[n] = (pi / w) sin(2 pi nw / w) inside the window, 0 outside (its derivative per
+ * sample); th[n] = (n - n_fft/2) h[n].  X_h, X_dh, X_th = the fp64 transforms of x h, x dh, x th; X_h is the
+ * plain launch's transform, butterfly for butterfly, and v = its fp32 value: the value column is
+ * pca_frame_points' bits for the same arguments.  With p = |X_h[k]|^2:
+ *   db = -Im(X_dh conj(X_h)) / p * n_fft / (2 pi)   in bins
+ *   dt =  Re(X_th conj(X_h)) / p / hop              in frames
+ * Bin k is reassigned iff v >= vmax - rel_floor, v >= abs_floor, p > 0 and db, dt are finite; otherwise the
+ * whole row is the grid row, bit for bit.  Reassigned, in fp64 from the fp32 axes, each coordinate rounded to
+ * fp32 once:
+ *   frequency (axes bit 0): pos = clamp(k + strength * clamp(db, +-max_df), 0, n_bins - 1),
+ *     i = min(floor(pos), n_bins - 2), f = farr[i] + (pos - i)(farr[i+1] - farr[i]): piecewise-linear on the
+ *     caller's axis, so the dropped-Nyquist axis and a non-uniform one are served;
+ *   time (axes bit 1): pos = j + strength * clamp(dt, +-max_dt), i = clamp(floor(pos), 0, Nt - 2),
+ *     t = tarr[i] + (pos - i)(tarr[i+1] - tarr[i]): extrapolated with the edge spacing, since a chunk's
+ *     energy may lie half a window outside tarr.
+ * A coordinate whose scaled shift is exactly 0 is the grid coordinate, bit for bit; an axis that is not
+ * selected is copied.  spec: no field NaN, each in the range its comment gives.
+ * Grid (Nt, B), 256 threads, 24 B * n_fft of LDS per workgroup as the plain launch; two transforms per frame
+ * (X_h, then x th + i x dh as one complex transform in the same LDS, separated by symmetry); no atomics: the
+ * same arguments give the same bits. */
+int pca_frame_points_reassigned(const float* waves, const int64_t* wave_off, const int64_t* set_off,
+                                int n_clips, int64_t max_len, int64_t min_len,
+                                const int64_t* clip_labels, const int64_t* idx, int B, int n_fft, int hop,
+                                int n_bins, int Nt, const float* farr, const float* tarr,
+                                const PcaFrameAug* aug, const PcaReassignSpec* spec, float* out,
+                                int64_t* labels_out, int32_t* meta_out, void* stream);
+
 /* Root mean square of every clip of a corpus: rms_out[c] = sqrt(sum x^2 / L_c) (device double[n_clips]; 0
  * for an empty clip).  What pca_frame_points_ex scales a background by.  One workgroup per clip, the
  * squares (exact in fp64) summed in fp64 in a fixed order, no atomics: the same clip gives the same bits.

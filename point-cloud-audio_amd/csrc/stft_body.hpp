@@ -1,7 +1,9 @@
 // One STFT frame in LDS, shared by k_stft_logmag (features.hip: the whole-corpus pre-pass),
-// k_frame_points (frame_points.hip: frames cut from the resident waveform per batch) and
-// k_frame_points_ex (frame_points_ex.hip: the same with speed change and background mix), so that all
-// give the same bits for the same frame.
+// k_frame_points (frame_points.hip: frames cut from the resident waveform per batch),
+// k_frame_points_ex (frame_points_ex.hip: the same with speed change and background mix) and
+// k_frame_points_reassigned (frame_points_reassigned.hip: the same frame, its points moved to their
+// reassigned coordinates by one more transform in the same LDS), so that all give the same bits for the
+// same frame.
 //
 // In-place radix-2 decimation-in-time FFT in float64: librosa computes the transform in double
 // (numpy.fft) and only then rounds to complex64, so matching it to ~1e-7 in log-magnitude --
@@ -97,6 +99,41 @@ __device__ __forceinline__ void stft_frame_fft(double2* x, double2* tw,
                                                double gain, int tid) {
   stft_frame_load(x, tw, wave, L, start, n_fft, log2n, win_length, gain, tid);
   stft_frame_butterflies(x, tw, n_fft, log2n, tid);
+}
+
+// Load stage of the transform that time-frequency reassignment adds (frame_points_reassigned.hip): the
+// same samples, window position and gain as stft_frame_load, packed as one complex sequence
+//   z[n] = x th / n_fft + i x dh,   x = sample * gain,  h = the periodic Hann of stft_store_sample,
+//   th[n] = (n - n_fft/2) h[n],     dh[n] = (pi / w) sin(2 pi nw / w) inside the window, 0 outside.
+// th is scaled by the exact power of two 1/n_fft so that the two halves have comparable magnitude and
+// neither loses bits to the other in the butterflies.  tw is left as stft_frame_load filled it.  No barrier.
+__device__ __forceinline__ void stft_reassign_load(double2* x, const float* __restrict__ wave, int64_t L,
+                                                   int64_t start, int n_fft, int log2n, int win_length,
+                                                   double gain, int tid) {
+  const int lpad = (n_fft - win_length) / 2;
+  const double inv_n = 1.0 / (double)n_fft;
+  for (int n = tid; n < n_fft; n += 256) {
+    const int nw = n - lpad;
+    double h = 0.0, dh = 0.0;
+    if (nw >= 0 && nw < win_length) {
+      double sn, cs;
+      sincospi(2.0 * (double)nw / (double)win_length, &sn, &cs);
+      h = 0.5 - 0.5 * cs;
+      dh = (3.14159265358979323846 / (double)win_length) * sn;
+    }
+    const double s = (double)wave[stft_reflect(start + n, L)] * gain;
+    const int r = (int)(__brev((unsigned)n) >> (32 - log2n));
+    x[r] = make_double2(s * ((double)(n - n_fft / 2) * inv_n * h), s * dh);
+  }
+}
+
+// The spectra of the two real sequences packed by stft_reassign_load, for bin k <= n_fft/2 of the
+// transformed z: th = X_th[k] / n_fft, dh = X_dh[k].
+__device__ __forceinline__ void stft_reassign_split(const double2* z, int k, int n_fft, double2* th,
+                                                    double2* dh) {
+  const double2 a = z[k], b = z[(n_fft - k) & (n_fft - 1)];
+  *th = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
+  *dh = make_double2(0.5 * (a.y + b.y), -0.5 * (a.x - b.x));
 }
 
 // log(1e-8 + |v| * inv) of one bin, inv = 1 / norm

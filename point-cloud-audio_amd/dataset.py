@@ -13,6 +13,7 @@ returns.  ``DeviceBatchLoader`` is the loader the train / eval entry points use.
 from typing import Iterator, Optional, Tuple
 
 import copy
+import math
 
 import numpy as np
 import torch
@@ -438,17 +439,29 @@ class ESC_wave_pc(Dataset):
     clips  list of 1-D float32 waveforms (numpy or torch, host or device), each longer than n_fft / 2
     y      one label per clip
     norm   "n_fft": magnitude / n_fft (the train scripts); "win": / the window length (Code/pceval.py:76)
+    reassign  None: the grid rows above.  True, or a dict of ``axes``, ``rel_floor``, ``abs_floor``,
+           ``max_df``, ``max_dt``, ``strength`` (``pca_hip.frame_points_reassigned``): every bin that carries
+           energy is written at its instantaneous frequency (and, 3-D, group delay) instead of its grid
+           coordinates, with the same value - one pca_frame_points_reassigned launch per batch.  Defaults:
+           axes "f" for 2-D sets and "ft" for 3-D sets (Ntemp >= 2), rel_floor log(1e3), abs_floor -inf,
+           max_df 2 bins, max_dt 1 frame, strength 1.  A representation, not an augmentation: ``plain()``
+           keeps it, ``stochastic`` ignores it, the sets stay dense.  It composes with jitter, gain_db,
+           win_lengths and norm; with speeds, the mix or the masks it raises ``ValueError`` (those live in
+           pca_frame_points_ex: out of scope).  ``with_reassign(spec_or_None)`` gives a view on the same
+           resident waveforms with another setting
     """
     _ntemp = 1
 
     def __init__(self, clips, y, fs, n_fft, hop=None, drop_nyquist=False, jitter=0, gain_db=0.0,
                  win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
                  mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None,
-                 freq_masks=0, freq_mask_width=0, time_masks=0, time_mask_width=0, mask_mode="drop"):
+                 freq_masks=0, freq_mask_width=0, time_masks=0, time_mask_width=0, mask_mode="drop",
+                 reassign=None):
         self._setup(clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                     device)
         self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db, mix_targets, mix_labels)
         self._setup_mask(freq_masks, freq_mask_width, time_masks, time_mask_width, mask_mode)
+        self._setup_reassign(reassign)
 
     def _setup(self, clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                device):
@@ -523,6 +536,37 @@ class ESC_wave_pc(Dataset):
         self.freq_masks, self.freq_mask_width = int(freq_masks), int(freq_mask_width)
         self.time_masks, self.time_mask_width = int(time_masks), int(time_mask_width)
         self.mask_mode = mask_mode
+
+    def _setup_reassign(self, reassign):
+        """``reassign``: None, True or a dict of the fields of pca_frame_points_reassigned's spec; checked
+        here, on the host, by that launch's rules."""
+        self.reassign = None
+        if reassign is None or reassign is False:
+            return
+        spec = dict(axes="ft" if self.tarr is not None and self._ntemp >= 2 else "f",
+                    rel_floor=math.log(1e3), abs_floor=float("-inf"), max_df=2.0, max_dt=1.0, strength=1.0)
+        if reassign is not True:
+            unknown = set(reassign) - set(spec)
+            if unknown:
+                raise ValueError(f"reassign: unknown fields {sorted(unknown)} (known: {sorted(spec)})")
+            spec.update(reassign)
+        if self._speed_on or self._mix_on or self.mix_targets or self._mask_on:
+            raise ValueError("reassign does not combine with speeds, the mix or the masks: those live in "
+                             "pca_frame_points_ex, reassignment in pca_frame_points_reassigned")
+        c = pca_hip.ops.reassign_spec(**spec)
+        if c.axes & 2 and (self.tarr is None or self._ntemp < 2):
+            raise ValueError(f"reassign axes {spec['axes']!r}: the time axis needs a 3-D dataset with "
+                             f"Ntemp >= 2")
+        if self.F < 2:
+            raise ValueError("reassign needs at least 2 frequency bins")
+        self.reassign = spec
+
+    def with_reassign(self, reassign):
+        """A view on the same resident waveforms with another ``reassign`` (None: the grid dataset);
+        everything else, the augmentations and the draw counter's value included, is kept."""
+        v = copy.copy(self)
+        v._setup_reassign(reassign)
+        return v
 
     @property
     def _mask_on(self) -> bool:
@@ -662,6 +706,14 @@ class ESC_wave_pc(Dataset):
                 draw_dev=draw_dev, want_meta=want_meta, want_samples=want_samples, **mix, **mask)
         if want_samples:
             raise ValueError("want_samples needs speeds or the mix on (pca_hip.frame_points_ex)")
+        if self.reassign is not None:
+            return pca_hip.frame_points_reassigned(
+                waves, woff, soff, idx, self.n_fft, self.hop, self.F, f32, t32, self._ntemp,
+                max_len=self._max_len, min_len=self._min_len, clip_labels=lab,
+                jitter=self.jitter, gain_db=self.gain_db, win_lengths=self._win_dev(waves.device),
+                norm_mode=pca_hip.NORM_WIN if self.norm == "win" else pca_hip.NORM_NFFT,
+                seed=self.seed, draw=self._draw, out=out, labels_out=labels_out, draw_dev=draw_dev,
+                want_meta=want_meta, **self.reassign)
         return pca_hip.frame_points(
             waves, woff, soff, idx, self.n_fft, self.hop, self.F, f32, t32, self._ntemp,
             max_len=self._max_len, min_len=self._min_len, clip_labels=lab,
@@ -692,13 +744,15 @@ class ESC_wave_pc_temp(ESC_wave_pc):
     def __init__(self, clips, y, fs, n_fft, Ntemp, hop=None, jitter=0, gain_db=0.0,
                  win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
                  mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None,
-                 freq_masks=0, freq_mask_width=0, time_masks=0, time_mask_width=0, mask_mode="drop"):
+                 freq_masks=0, freq_mask_width=0, time_masks=0, time_mask_width=0, mask_mode="drop",
+                 reassign=None):
         self._ntemp = int(Ntemp)
         assert self._ntemp >= 1
         self._setup(clips, y, fs, n_fft, hop, True, jitter, gain_db, win_lengths, norm, seed, device)
         self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db, mix_targets, mix_labels)
         self._setup_mask(freq_masks, freq_mask_width, time_masks, time_mask_width, mask_mode)
         self.tarr = np.linspace(0, (self.hop / fs) * self._ntemp, self._ntemp)
+        self._setup_reassign(reassign)
 
 
 class PeakPoints(Dataset):

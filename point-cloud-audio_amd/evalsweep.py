@@ -33,6 +33,8 @@ The other set-model experiments run here at batch scale too:
 * ``peak_sweep``: sets reduced to their K strongest spectral peaks, refined off the grid
   (``pca_hip.peak_points``), evaluated as padded sets with their point counts; no reference counterpart
   - a fourth curve;
+* ``reassign_sweep``: sets whose points slide from the grid to their reassigned time-frequency coordinates
+  (``pca_hip.frame_points_reassigned``), one pass per strength; no reference counterpart;
 * ``reframe_sweep_temporal``: the (Fs, N) re-framing of the 3ST, Code/pc_temp3d_eval.py:56-107.
 * ``clip_accuracy``: the clip-level scores the datasets' literature reports (majority vote and mean
   log-probability over a clip's frames or chunks, ``pca_hip.clip_aggregate``) next to the frame score;
@@ -72,13 +74,13 @@ import torch
 import ctypes as C
 
 import pca_hip
-from dataset import ESC_pc, ESC_pc_temp
+from dataset import ESC_pc, ESC_pc_temp, ESC_wave_pc, ESC_wave_pc_temp
 from pca_hip import _lib
 from pca_hip.baseline import SEL_ALL, BaselineEngine
 from pca_hip.trainer import STEngine, st_config
 
 __all__ = ["reframe_sweep", "framewise_dataset", "default_list_K", "sweep_draw", "subsample_sweep",
-           "importance_sweep", "attention_sweep", "peak_sweep", "most_peaks", "chunk_plan",
+           "importance_sweep", "attention_sweep", "peak_sweep", "most_peaks", "reassign_sweep", "chunk_plan",
            "temporal_axes", "temporal_dataset", "reframe_sweep_temporal", "baseline_subsample_sweep", "baseline_frames",
            "baseline_chunks", "baseline_reframe_sweep", "baseline_reframe_sweep_temporal",
            "trim_dB_of", "trim_clips", "clip_accuracy"]
@@ -601,6 +603,46 @@ def peak_sweep(model, spec, labels, farr, tarr=None, list_K: Optional[Iterable[i
         correct, points = acc.tolist()                              # the one host read of this K
         data[K], mean_points[K] = [correct / full, 0], points / full
     out = {"data": data, "list_K": list_K, "mean_points": mean_points}
+    _write_json(out, json_file)
+    return out
+
+
+@torch.no_grad()
+def reassign_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float, n_fft: int,
+                   Ntemp: Optional[int] = None, list_strength: Iterable[float] = (0, .25, .5, .75, 1),
+                   batch_size: int = 8, json_file: Optional[str] = None, mode: int = _lib.MODE_F32,
+                   sets_per_call: Optional[int] = None, hop: Optional[int] = None,
+                   drop_nyquist: bool = False, norm: str = "n_fft", **spec) -> Dict:
+    """Accuracy of ``model`` as its inputs slide from the STFT grid (strength 0: the grid rows, bit for bit)
+    to full time-frequency reassignment (strength 1; ``pca_hip.frame_points_reassigned``).  **No reference
+    counterpart**: the reference's sets are grid points.
+
+    ``clips`` / ``labels`` / ``fs`` / ``n_fft`` [/ ``hop`` / ``norm``] as ``ESC_wave_pc`` takes them; with
+    ``Ntemp`` the 3-D sets of ``ESC_wave_pc_temp`` (Nyquist dropped), else the 2-D sets
+    (``drop_nyquist``).  ``spec``: the other fields of ``reassign`` (axes, rel_floor, abs_floor, max_df,
+    max_dt; the datasets' defaults).  The corpus is resident once; every strength is one
+    ``_dataset_accuracy`` pass over a ``with_reassign`` view of it, one host read each.
+
+    Returns (and, with ``json_file``, writes)
+    ``{"data": {strength: [acc, 0]}, "list_strength": [...], "spec": {...}}``."""
+    if "strength" in spec:
+        raise ValueError("strength is the swept axis: pass list_strength")
+    dev = _model_device(model)
+    if Ntemp is None:
+        ds = ESC_wave_pc(clips, labels, fs, n_fft, hop=hop, drop_nyquist=drop_nyquist, norm=norm,
+                         device=dev, reassign=dict(spec))
+    else:
+        ds = ESC_wave_pc_temp(clips, labels, fs, n_fft, Ntemp, hop=hop, norm=norm, device=dev,
+                              reassign=dict(spec))
+    din = 2 if Ntemp is None else 3
+    list_strength = [float(v) for v in list_strength]
+    data = {}
+    for strength in list_strength:
+        view = ds.with_reassign(dict(spec, strength=strength))                      # ValueError
+        data[strength] = [_dataset_accuracy(model, view, None, din, batch_size, mode, sets_per_call), 0]
+    shown = {k: (v if isinstance(v, str) or math.isfinite(v) else str(v))
+             for k, v in ds.reassign.items() if k != "strength"}
+    out = {"data": data, "list_strength": list_strength, "spec": shown}
     _write_json(out, json_file)
     return out
 

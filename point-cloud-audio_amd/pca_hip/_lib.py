@@ -90,6 +90,11 @@ class PcaPeakSpec(C.Structure):
                 ("abs_floor", C.c_float), ("refine", C.c_int32)]
 
 
+class PcaReassignSpec(C.Structure):
+    _fields_ = [("axes", C.c_int32), ("rel_floor", C.c_float), ("abs_floor", C.c_float),
+                ("max_df", C.c_float), ("max_dt", C.c_float), ("strength", C.c_float)]
+
+
 class PcaSoftTargets(C.Structure):
     _fields_ = [("labels2", C.c_void_p), ("weight", C.c_void_p), ("smoothing", C.c_float)]
 
@@ -178,6 +183,10 @@ SIGNATURES = {
     "pca_frame_points": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p, c_i64p,
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp,
                                    C.POINTER(PcaFrameAug), c_fp, c_i64p, c_vp, c_vp]),
+    "pca_frame_points_reassigned": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p,
+                                              c_i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp,
+                                              c_fp, C.POINTER(PcaFrameAug), C.POINTER(PcaReassignSpec),
+                                              c_fp, c_i64p, c_vp, c_vp]),
     "pca_clip_rms": (C.c_int, [c_fp, c_i64p, C.c_int, C.c_int64, c_vp, c_vp]),
     "pca_frame_points_ex": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p, c_i64p,
                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp,

@@ -811,6 +811,89 @@ def frame_points(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.Ten
     return (out, labels_out, meta) if want_meta else (out, labels_out)
 
 
+REASSIGN_AXES = {"f": 1, "t": 2, "ft": 3, "tf": 3}
+
+
+def reassign_spec(axes: str = "f", rel_floor: float = math.log(1e3), abs_floor: float = float("-inf"),
+                  max_df: float = 2.0, max_dt: float = 1.0, strength: float = 1.0) -> "_lib.PcaReassignSpec":
+    """``PcaReassignSpec`` checked on the host by the rules of pca_frame_points_reassigned
+    (``ValueError``)."""
+    if axes not in REASSIGN_AXES:
+        raise ValueError(f"axes {axes!r}: one of 'f', 't', 'ft'")
+    rel_floor, abs_floor = float(rel_floor), float(abs_floor)
+    max_df, max_dt, strength = float(max_df), float(max_dt), float(strength)
+    if not rel_floor >= 0.0:
+        raise ValueError(f"rel_floor {rel_floor}: >= 0 (inf switches it off)")
+    if abs_floor != abs_floor:
+        raise ValueError("abs_floor is NaN (-inf switches it off)")
+    if not 0.0 < max_df <= 64.0:
+        raise ValueError(f"max_df {max_df} outside (0, 64] bins")
+    if not 0.0 < max_dt <= 4.0:
+        raise ValueError(f"max_dt {max_dt} outside (0, 4] frames")
+    if not 0.0 <= strength <= 1.0:
+        raise ValueError(f"strength {strength} outside [0, 1]")
+    return _lib.PcaReassignSpec(REASSIGN_AXES[axes], rel_floor, abs_floor, max_df, max_dt, strength)
+
+
+def frame_points_reassigned(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.Tensor,
+                            idx: torch.Tensor, n_fft: int, hop: int, n_bins: int, farr: torch.Tensor,
+                            tarr: Optional[torch.Tensor] = None, Nt: int = 1, *, max_len: int,
+                            min_len: int, clip_labels: Optional[torch.Tensor] = None, jitter: int = 0,
+                            gain_db: float = 0.0, win_lengths: Optional[torch.Tensor] = None,
+                            norm_mode: int = NORM_NFFT, seed: int = 0, draw: int = 0,
+                            axes: str = "f", rel_floor: float = math.log(1e3),
+                            abs_floor: float = float("-inf"), max_df: float = 2.0, max_dt: float = 1.0,
+                            strength: float = 1.0, out: Optional[torch.Tensor] = None,
+                            labels_out: Optional[torch.Tensor] = None,
+                            draw_dev: Optional[torch.Tensor] = None, want_meta: bool = False):
+    """``frame_points`` with every point written where its energy lies (pca_frame_points_reassigned):
+    time-frequency reassignment in the form of ``librosa.reassigned_spectrogram``.  The value column,
+    the labels and meta are ``frame_points``' bits for the same arguments; the coordinates become
+    real-valued.
+
+    Every argument of ``frame_points`` with the same meaning, plus: ``axes`` "f" (frequency), "t" (time;
+    needs tarr and Nt >= 2) or "ft"; a bin moves iff its value is at least the frame's maximum minus
+    ``rel_floor`` (inf: off) and at least ``abs_floor`` (-inf: off); the frequency shift is clamped to
+    +-``max_df`` bins (0 < . <= 64), the time shift to +-``max_dt`` frames (0 < . <= 4), and both are
+    then multiplied by ``strength`` in [0, 1] (0: the grid rows, bit for bit).  The moved frequency is
+    piecewise-linear on ``farr``, the moved time on ``tarr`` (extrapolated with the edge spacing).
+    n_bins >= 2.  Argument errors raise ``ValueError`` before any launch.
+    Returns what ``frame_points`` returns."""
+    spec = reassign_spec(axes, rel_floor, abs_floor, max_df, max_dt, strength)
+    if int(n_bins) < 2:
+        raise ValueError(f"n_bins {n_bins}: the frequency axis is interpolated, at least 2 bins")
+    if spec.axes & 2 and (tarr is None or int(Nt) < 2):
+        raise ValueError(f"axes {axes!r}: the time axis needs tarr and Nt >= 2 (Nt = {Nt})")
+    _need_cuda(waves, wave_off, set_off, idx, farr)
+    assert waves.dtype == torch.float32 and waves.is_contiguous() and farr.dtype == torch.float32
+    assert wave_off.dtype == set_off.dtype == idx.dtype == torch.int64
+    assert wave_off.numel() == set_off.numel() >= 2 and farr.numel() >= n_bins
+    din = 2
+    if tarr is not None:
+        _need_cuda(tarr)
+        assert tarr.dtype == torch.float32 and tarr.numel() >= Nt
+        din = 3
+    B = idx.numel()
+    with torch.cuda.device(waves.device):
+        if win_lengths is None:
+            win_lengths = torch.tensor([n_fft], dtype=torch.int32, device=waves.device)
+        assert win_lengths.is_cuda and win_lengths.dtype == torch.int32
+        if out is None:
+            out = torch.empty((B, Nt * n_bins, din), dtype=torch.float32, device=waves.device)
+        if clip_labels is not None and labels_out is None:
+            labels_out = torch.empty(B, dtype=torch.int64, device=waves.device)
+        meta = torch.empty((B, 4), dtype=torch.int32, device=waves.device) if want_meta else None
+        aug = _lib.PcaFrameAug(int(jitter), float(gain_db), win_lengths.data_ptr(),
+                               win_lengths.numel(), int(norm_mode), int(seed) & (2 ** 64 - 1),
+                               int(draw) & (2 ** 64 - 1), _draw_ptr(draw_dev))
+        check(lib().pca_frame_points_reassigned(
+            _ptr(waves), _ptr(wave_off), _ptr(set_off), wave_off.numel() - 1, int(max_len),
+            int(min_len), _ptr(clip_labels), _ptr(idx), B, int(n_fft), int(hop), int(n_bins), int(Nt),
+            _ptr(farr), _ptr(tarr), C.byref(aug), C.byref(spec), _ptr(out), _ptr(labels_out),
+            _ptr(meta), _stream(waves)), "pca_frame_points_reassigned")
+    return (out, labels_out, meta) if want_meta else (out, labels_out)
+
+
 def clip_rms(waves: torch.Tensor, wave_off: torch.Tensor, max_len: int) -> torch.Tensor:
     """Root mean square of every clip of a corpus on the device (pca_clip_rms): waves float32, the
     clips back to back, wave_off int64[n_clips + 1] their offsets, max_len the longest one.  Returns
