@@ -84,25 +84,31 @@ __device__ __forceinline__ void mab0_bwd_small_body(const Mab0SmallArgs& a, int 
   for (int n0 = 0; n0 < len; n0 += CH) {
     const int cn = (len - n0 < CH) ? len - n0 : CH;
     // [pair of points][component][2] (as k_mab0_attn_small): two points per packed-fp32 instruction;
-    // unused components and the odd point of the chunk are zero (x = 0 contributes dS.x = 0); the
-    // next chunk's loads are in flight while this one is worked on
-    const int npairs = (cn + 1) >> 1;
+    // unused components and the odd point of the chunk are zero; the next chunk's loads are in flight
+    // while this one is worked on
+    const int nfull = cn >> 1;       // pairs of two real points; an odd chunk ends in a half-filled one
     commit_points<NT>(xr, cn, dk, sX);
     if (n0 + CH < len)
       fetch_points<NT>(X + ((int64_t)b * N + n0 + CH) * dk, (len - n0 - CH < CH) ? len - n0 - CH : CH, dk,
                        xr);
+    // half: the pair's second point is the chunk's zero padding.  Its score is 0 whatever the row, so
+    // exp2(0 - lse) is +inf for a row whose scores all lie below -128 and inf * (x = 0) is NaN: its dS is
+    // dropped, not multiplied by zero (k_mab0_attn_small masks the same point to -inf)
+    auto pair = [&](int q, bool half) {
+      const float4 lo = *reinterpret_cast<const float4*>(&sX[q * 8]);
+      const float4 hi = *reinterpret_cast<const float4*>(&sX[q * 8 + 4]);
+      const f32x2 x0 = {lo.x, lo.y}, x1 = {lo.z, lo.w}, x2 = {hi.x, hi.y}, x3 = {hi.z, hi.w};
+      const f32x2 sc = gk[0] * x0 + gk[1] * x1 + gk[2] * x2 + gk[3] * x3;
+      const f32x2 da = dt[0] * x0 + dt[1] * x1 + dt[2] * x2 + dt[3] * x3;
+      const f32x2 pe = {__builtin_amdgcn_exp2f(sc[0] - lse), __builtin_amdgcn_exp2f(sc[1] - lse)};
+      f32x2 ds = (LN2 * pe) * (da - del);
+      if (half) ds[1] = 0.f;
+      acc2[0] += ds * x0; acc2[1] += ds * x1; acc2[2] += ds * x2; acc2[3] += ds * x3;
+    };
     if (part < parts) {
 #pragma unroll 4
-      for (int q = part; q < npairs; q += parts) {
-        const float4 lo = *reinterpret_cast<const float4*>(&sX[q * 8]);
-        const float4 hi = *reinterpret_cast<const float4*>(&sX[q * 8 + 4]);
-        const f32x2 x0 = {lo.x, lo.y}, x1 = {lo.z, lo.w}, x2 = {hi.x, hi.y}, x3 = {hi.z, hi.w};
-        const f32x2 sc = gk[0] * x0 + gk[1] * x1 + gk[2] * x2 + gk[3] * x3;
-        const f32x2 da = dt[0] * x0 + dt[1] * x1 + dt[2] * x2 + dt[3] * x3;
-        const f32x2 pe = {__builtin_amdgcn_exp2f(sc[0] - lse), __builtin_amdgcn_exp2f(sc[1] - lse)};
-        const f32x2 ds = (LN2 * pe) * (da - del);
-        acc2[0] += ds * x0; acc2[1] += ds * x1; acc2[2] += ds * x2; acc2[3] += ds * x3;
-      }
+      for (int q = part; q < nfull; q += parts) pair(q, false);
+      if ((cn & 1) && nfull % parts == part) pair(nfull, true);
     }
   }
 #pragma unroll
