@@ -918,6 +918,14 @@ int64_t pca_st_param_count(const pca_st_config* c);
  * [0, offset) (enc.0) after phase 1 -- the two all-reduce buckets of SURVEY.md 8e. */
 int64_t pca_st_bucket_split(const pca_st_config* c);
 size_t pca_st_ws_bytes(const pca_st_config* c, int training);
+/* 1 when the library guarantees that two identical pca_st_train_fwd_bwd calls of this configuration give
+ * identical bits - logits, loss, statistics and every gradient, launched eagerly or replayed from a captured
+ * graph - so that a run resumed from a checkpoint equals the uninterrupted one; 0 when it does not guarantee
+ * that (the call may still happen to repeat itself).  has_lengths: the calls pass `lengths`.  1 today: in
+ * PCA_MODE_BF16, the fused d = 128 plans (dense sets, PCA_WGRAD_SLABS not 0), the fused d = 256 plans (dense
+ * sets) and the d = 64 chain with the fused attention core (head dims <= 16, din = 64 or <= 4) up to B = 256,
+ * every buffer 16-byte aligned.  PCA_MODE_F32 and every other width: 0. */
+int pca_st_step_reproducible(const pca_st_config* c, int has_lengths);
 /* Diagnostics only: byte offsets inside the workspace of the training step's per-block areas, so that
  * a test can compare what two kernel variants left there.  out[0..4] = saved areas of enc.0.mab0,
  * enc.0.mab1, enc.1.mab0, enc.1.mab1, dec.0; out[5..6] = H of the two ISABs (fp32 [B, m, d]);

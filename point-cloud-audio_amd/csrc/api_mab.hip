@@ -95,7 +95,7 @@ int mab_bwd(BlockPath path, const pca_mab_shape& s, const void* Q, const void* K
     case BlockPath::Exact: case BlockPath::ExactCore: case BlockPath::Sd64: break;
   }
   return mab_f32_bwd(s, (const float*)Q, (const float*)K, p, saved, (const float*)dY, (float*)dQ,
-                     (float*)dK, dk_accumulate, g, ws, st, path == BlockPath::ExactCore);
+                     (float*)dK, dk_accumulate, g, ws, st, path == BlockPath::ExactCore, ctx);
 }
 
 int no_stale_pack(const char* where, bool pack_allowed) {

@@ -116,10 +116,15 @@ int attn_core_bwd(const pca_mab_shape& s, const float* Qp, const float* Kp, cons
                   const float* O, const float* LSE, const float* dO, float* dQp, float* dKp, float* dVp,
                   float* Delta, hipStream_t st);
 // weight + bias gradient of a 64 -> 64 (or <= 4 -> 64) Linear over a tall activation in one launch
-// (wgrad64.hip)
-bool wgrad64_ok(const float* dY, const float* X, int64_t M, int din, int dout);
-int wgrad64(const float* dY, const float* X, float* dW, float* db, int64_t M, int din,
-            hipStream_t st);
+// (wgrad64.hip) that writes per-workgroup slabs into `part` (wgrad64_slab_elems floats: a function of the
+// shape alone, 0 for a shape the kernels do not take) and appends the two fixed-order sums that finish
+// dW += .. / db += .. to `jobs`: the caller runs them (slab_sum_jobs), several calls' jobs in one launch
+struct SlabSumJobs;  // bwd_defer.hpp
+size_t wgrad64_slab_elems(int64_t M, int din, int dout);
+bool wgrad64_ok(const float* dY, const float* X, const float* dW, const float* db, int64_t M, int din,
+                int dout);
+int wgrad64(const float* dY, const float* X, float* dW, float* db, int64_t M, int din, float* part,
+            SlabSumJobs* jobs, hipStream_t st);
 // the 64 -> 64 / <= 4 -> 64 Linear layers over a tall activation with the weights in registers
 // (linear64.hip): forward, input gradient, fc_o with the block's epilogue Y = O + relu(Z)
 bool lin64_ok(const float* X, const float* Y, int64_t M, int din, int dout);
@@ -142,7 +147,7 @@ int mab_f32_fwd(const pca_mab_shape& s, const float* Q, const float* K,
 int mab_f32_bwd(const pca_mab_shape& s, const float* Q, const float* K,
                 const pca_mab_params& p, const void* saved, const float* dY, float* dQ,
                 float* dK, int dk_accumulate, const pca_mab_grads& g, void* ws,
-                hipStream_t st, bool sab = false);
+                hipStream_t st, bool sab = false, StepCtx* ctx = nullptr);
 // dW[dout][din] += dY[M][dout]^T X[M][din], db += colsum(dY) with bf16 MFMA operands, bitwise reproducible
 // (wgrad_rows.hip); ws: wgrad_rows_ws_elems floats
 size_t wgrad_rows_ws_elems(int64_t M, int dout, int din);

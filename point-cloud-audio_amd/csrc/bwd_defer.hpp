@@ -13,7 +13,9 @@ namespace pca {
 struct SlabSumJob {
   const float* slabs;
   float* out;
-  int S, n, accumulate;
+  int S, n;
+  int accumulate;         // 0: out = sum; 1: out + sum, out first in the chain of additions; 2: out + sum, the
+                          // sum formed as with 0 and added ONCE (|acc - (P + fresh)| is one fp32 rounding)
   int stride;             // floats between consecutive slabs (0: n)
 };
 struct SlabSumJobs {

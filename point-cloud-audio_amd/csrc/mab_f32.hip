@@ -8,6 +8,8 @@
 // (modules.py:52,63 `I.repeat(B,1,1)`) is projected once (q_shared) and broadcast through
 // a zero batch stride.
 #include "blocks.hpp"
+#include "bwd_defer.hpp"
+#include "step_ctx.hpp"
 #include "weight_images.hpp"
 
 #include <math.h>
@@ -67,6 +69,9 @@ struct BwdWsF32 {
   float* dYp;       // ln = 1: gradient w.r.t. the input of ln1
   float* Wt;        // [d][d]: a transposed weight (linear_dx of large bf16-mode problems)
   float* wpart;     // self-attention blocks (BlockPath::ExactCore): the slabs of the deterministic weight gradients
+  // the bf16-operand chain at d = 64: the slabs of the block's wgrad64 calls (fc_o, fc_k, fc_v, fc_q; null: the
+  // call's shape is not wgrad64's).  They stay in place until the block's one slab_sum_jobs launch.
+  float *wg_o, *wg_k, *wg_v, *wg_q;
 };
 
 inline size_t bwd_ws_elems(const pca_mab_shape& s, BwdWsF32* out, void* base, bool core, bool sab) {
@@ -88,6 +93,22 @@ inline size_t bwd_ws_elems(const pca_mab_shape& s, BwdWsF32* out, void* base, bo
     const size_t b = wgrad_rows_ws_elems((int64_t)s.B * s.nq, s.d, s.dq);
     const size_t o = wgrad_rows_ws_elems((int64_t)s.B * s.nq, s.d, s.d);
     v.wpart = c.take<float>(a > b ? (a > o ? a : o) : (b > o ? b : o));
+  }
+  v.wg_o = v.wg_k = v.wg_v = v.wg_q = nullptr;
+  if (!sab && s.mode != PCA_MODE_F32) {
+    // Sized and placed from the shape alone.  fc_o's job runs after the attention's adjoint, so its slabs
+    // may lie over dO and those of the three jobs after it over dZ, both dead by then, where they fit: a
+    // block over many rows needs no room of its own (at most 4 x 128 slabs of 4160 floats otherwise).
+    const int64_t Mq = (int64_t)s.B * s.nq, Mk = (int64_t)s.B * s.nk;
+    const size_t eo = wgrad64_slab_elems(Mq, s.d, s.d), ek = wgrad64_slab_elems(Mk, s.dk, s.d);
+    const size_t eq = wgrad64_slab_elems(s.q_shared ? s.nq : Mq, s.dq, s.d);
+    const size_t dead = (size_t)Mq * s.d, rest = 2 * ek + eq;
+    if (eo > 0) v.wg_o = eo <= dead ? v.dO : c.take<float>(eo);
+    if (rest > 0) {
+      float* r = rest <= dead ? v.dZ : c.take<float>(rest);
+      if (ek > 0) { v.wg_k = r; v.wg_v = r + ek; }
+      if (eq > 0) v.wg_q = r + 2 * ek;
+    }
   }
   if (out) *out = v;
   return c.off;
@@ -142,10 +163,12 @@ inline int linear_dw(const float* dY, const float* X, float* dW, int64_t M, int 
 }
 
 // dW += dY^T X and db += colsum(dY): one launch that reads each operand once where the shape has
-// one (wgrad64.hip: 64 -> 64 layers in the bf16-operand chain), the GEMM and the column sum otherwise
+// one (wgrad64.hip: 64 -> 64 layers in the bf16-operand chain; `part` = its slabs, and the gradients are
+// complete once the caller has run the sums it appends to `sums`), the GEMM and the column sum otherwise
 inline int linear_dw_db(const float* dY, const float* X, float* dW, float* db, int64_t M, int din,
-                        int dout, hipStream_t st) {
-  if (t_bf16_operands == 1 && wgrad64_ok(dY, X, M, din, dout)) return wgrad64(dY, X, dW, db, M, din, st);
+                        int dout, float* part, SlabSumJobs* sums, hipStream_t st) {
+  if (t_bf16_operands == 1 && part != nullptr && wgrad64_ok(dY, X, dW, db, M, din, dout))
+    return wgrad64(dY, X, dW, db, M, din, part, sums, st);
   PCA_TRY(linear_dw(dY, X, dW, M, din, dout, st));
   return colsum(dY, M, dout, db, 1, st);
 }
@@ -236,17 +259,38 @@ int mab_f32_fwd(const pca_mab_shape& s, const float* Q, const float* K,
 int mab_f32_bwd(const pca_mab_shape& s, const float* Q, const float* K,
                 const pca_mab_params& p, const void* saved, const float* dY, float* dQ,
                 float* dK, int dk_accumulate, const pca_mab_grads& g, void* ws,
-                hipStream_t st, bool sab) {
+                hipStream_t st, bool sab, StepCtx* ctx) {
   OperandMode om(s);
   const bool core = sab || attn_core_ok(s);
   SavedF32 v;
   saved_elems(s, &v, const_cast<void*>(saved), core);
   BwdWsF32 w;
   bwd_ws_elems(s, &w, ws, core, sab);
-  // weight + bias gradients: a self-attention block takes the deterministic row-slab kernels (wgrad_rows.hip)
-  auto wgrad = [&](const float* dYg, const float* X, float* dW, float* db, int64_t M, int din, int dout) {
+  // weight + bias gradients: a self-attention block takes the deterministic row-slab kernels (wgrad_rows.hip);
+  // the others collect the sums of their wgrad64 calls, which ONE launch runs before this call returns
+  SlabSumJobs sums{};
+  SlabSumJobs* jobs = &sums;
+  if (ctx != nullptr && ctx->wg64_late != nullptr && w.wg_o != nullptr) {
+    // a step that lends room until its flush: the slabs go there and the sums ride in its terminal launch
+    const size_t eo = wgrad64_slab_elems((int64_t)s.B * s.nq, s.d, s.d);
+    const size_t ek = wgrad64_slab_elems((int64_t)s.B * s.nk, s.dk, s.d);
+    const size_t eq = wgrad64_slab_elems(s.q_shared ? s.nq : (int64_t)s.B * s.nq, s.dq, s.d);
+    const size_t need = eo + 2 * ek + eq;
+    const int cap = (int)(sizeof(sums.j) / sizeof(sums.j[0]));
+    if (need <= ctx->wg64_room_elems && ctx->wg64_late->n + 8 <= cap) {
+      float* r = ctx->wg64_room;
+      ctx->wg64_room += need;
+      ctx->wg64_room_elems -= need;
+      w.wg_o = r;
+      if (ek > 0) { w.wg_k = r + eo; w.wg_v = r + eo + ek; }
+      if (eq > 0) w.wg_q = r + eo + 2 * ek;
+      jobs = ctx->wg64_late;
+    }
+  }
+  auto wgrad = [&](const float* dYg, const float* X, float* dW, float* db, int64_t M, int din, int dout,
+                   float* part) {
     return sab ? wgrad_rows(dYg, X, dW, db, M, din, dout, w.wpart, st)
-               : linear_dw_db(dYg, X, dW, db, M, din, dout, st);
+               : linear_dw_db(dYg, X, dW, db, M, din, dout, part, jobs, st);
   };
   const int d = s.d, h = s.h, dh = d / h, nq = s.nq, nk = s.nk;
   const int64_t Mq = (int64_t)s.B * nq, Mk = (int64_t)s.B * nk;
@@ -266,10 +310,8 @@ int mab_f32_bwd(const pca_mab_shape& s, const float* Q, const float* K,
       lin64_ok(v.Z, w.dZ, Mq, d, d)) {
     // dZ = dY . [Z > 0] and dO = dY + dZ Wo in one launch (linear64.hip)
     PCA_TRY(lin64_fc_o_bwd(dYe, v.Z, p.wo, w.dZ, w.dO, Mq, st));
-    PCA_TRY(wgrad(w.dZ, Oe, g.wo, g.bo, Mq, d, d));
   } else {
     PCA_TRY(relu_bwd(dYe, v.Z, w.dZ, Mq * d, st));
-    PCA_TRY(wgrad(w.dZ, Oe, g.wo, g.bo, Mq, d, d));
     PCA_TRY(copy_rows(dYe, Mq, w.dO, Mq, d, st));
     PCA_TRY(linear_dx(w.dZ, p.wo, w.dO, Mq, d, d, 1, st, w.Wt));
   }
@@ -313,9 +355,11 @@ int mab_f32_bwd(const pca_mab_shape& s, const float* Q, const float* K,
   }
   }
 
+  // fc_o: after the last reader of dO, over which its slabs may lie (bwd_ws_elems); dZ is free from here on
+  PCA_TRY(wgrad(w.dZ, Oe, g.wo, g.bo, Mq, d, d, w.wg_o));
   // fc_k / fc_v
-  PCA_TRY(wgrad(w.dKp, K, g.wk, g.bk, Mk, s.dk, d));
-  PCA_TRY(wgrad(w.dVp, K, g.wv, g.bv, Mk, s.dk, d));
+  PCA_TRY(wgrad(w.dKp, K, g.wk, g.bk, Mk, s.dk, d, w.wg_k));
+  PCA_TRY(wgrad(w.dVp, K, g.wv, g.bv, Mk, s.dk, d, w.wg_v));
   if (dK != nullptr) {
     PCA_TRY(linear_dx(w.dKp, p.wk, dK, Mk, s.dk, d, dk_accumulate ? 1 : 0, st, w.Wt));
     PCA_TRY(linear_dx(w.dVp, p.wv, dK, Mk, s.dk, d, 1, st, w.Wt));
@@ -324,13 +368,13 @@ int mab_f32_bwd(const pca_mab_shape& s, const float* Q, const float* K,
   // fc_q
   if (s.q_shared) {
     PCA_TRY(colsum(w.dQp, s.B, nq * d, w.dQps, 0, st));   // sum over sets
-    PCA_TRY(linear_dw_db(w.dQps, Q, g.wq, g.bq, nq, s.dq, d, st));
+    PCA_TRY(linear_dw_db(w.dQps, Q, g.wq, g.bq, nq, s.dq, d, sab ? nullptr : w.wg_q, jobs, st));
     if (dQ != nullptr) PCA_TRY(linear_dx(w.dQps, p.wq, dQ, nq, s.dq, d, 1, st));
   } else {
-    PCA_TRY(wgrad(w.dQp, Q, g.wq, g.bq, Mq, s.dq, d));
+    PCA_TRY(wgrad(w.dQp, Q, g.wq, g.bq, Mq, s.dq, d, w.wg_q));
     if (dQ != nullptr) PCA_TRY(linear_dx(w.dQp, p.wq, dQ, Mq, s.dq, d, 0, st, w.Wt));
   }
-  return PCA_OK;
+  return slab_sum_jobs(sums, st);      // (nothing collected: no launch)
 }
 
 // Scope guard for callers outside this file (the d = 256 blocks): the linear_* helpers below run
@@ -349,12 +393,9 @@ int linear_dx_acc_f32(const float* dY, const float* W, float* dX, int64_t M, int
 }
 int linear_bwd_f32(const float* X, const float* W, const float* dY, float* dX, float* dW,
                    float* db, int64_t M, int din, int dout, hipStream_t st) {
-  if (dW && db) {
-    PCA_TRY(linear_dw_db(dY, X, dW, db, M, din, dout, st));
-  } else {
-    if (dW) PCA_TRY(linear_dw(dY, X, dW, M, din, dout, st));
-    if (db) PCA_TRY(colsum(dY, M, dout, db, 1, st));
-  }
+  // (never wgrad64: this call has no workspace for its slabs, pca_linear_bwd_ws_bytes)
+  if (dW) PCA_TRY(linear_dw(dY, X, dW, M, din, dout, st));
+  if (db) PCA_TRY(colsum(dY, M, dout, db, 1, st));
   if (dX) PCA_TRY(linear_dx(dY, W, dX, M, din, dout, 0, st));
   return PCA_OK;
 }

@@ -1,4 +1,4 @@
-// Fixed-order sum of per-workgroup partial tensors: out[n] (+)= sum_w slabs[w * stride + i].
+// Fixed-order sum of per-workgroup partial tensors: out[n] (+)= sum_w slabs[w * stride + i] (SlabSumJob::accumulate).
 // Shared by the stand-alone launch (k_slab_sum_jobs, slab_sum.hip) and by the kernels that carry
 // such sums as extra workgroup rows ("riders": k_wgrad128, k_terminal1) so that the reduction costs
 // no launch of its own.  Uses the first 256 threads of the workgroup; EVERY thread of the workgroup
@@ -47,11 +47,16 @@ __device__ __forceinline__ void slab_sum_body(const SlabSumJob& j, int bx, int t
   if (tid < 256) red[sg * 64 + c] = t;
   __syncthreads();
   if (on && sg == 0) {
-    float4 o = j.accumulate ? *reinterpret_cast<float4*>(j.out + i) : float4{0.f, 0.f, 0.f, 0.f};
+    // accumulate 1: the merge starts from out; 2: the merge as with 0, then ONE addition onto out
+    float4 o = j.accumulate == 1 ? *reinterpret_cast<float4*>(j.out + i) : float4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float4 v = red[q * 64 + c];
       o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
+    }
+    if (j.accumulate == 2) {
+      const float4 p = *reinterpret_cast<float4*>(j.out + i);
+      o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w;
     }
     *reinterpret_cast<float4*>(j.out + i) = o;
   }

@@ -180,11 +180,37 @@ inline StepPlan plan(const pca_st_config& c, bool training, const int32_t* lengt
   return pl;
 }
 
+// Whether two identical training calls of this configuration give identical bits - logits, loss, statistics and
+// every gradient, launched eagerly or replayed from a graph.  Conservative: true only in PCA_MODE_BF16 and only
+// for the plans whose every reduction runs in a fixed order,
+//   d = 128, all blocks on the fused kernels, the tail's reductions as slabs (TailForm::slabs), dense sets;
+//   d = 256, all blocks on the fused kernels, dense sets;
+//   d = 64: the bf16-operand chain with every block's attention on the fused core and every
+//          weight gradient on wgrad64 (slabs + fixed-order sums); the sum over sets of a shared query's
+//          gradient is colsum()'s one-thread-per-column form up to 256 sets only, so B <= 256.
+// The exact fp32 mode (split-K GEMMs add with atomics) and every other chain width: false.  Buffers are taken to
+// be 16-byte aligned, as the engine's own are: the chain leaves a misaligned tensor to the split-K GEMM.
+inline bool step_reproducible(const pca_st_config& c, bool has_lengths) {
+  static const int32_t some_lengths = 1;      // (plan() and block_path() look at the pointer only)
+  if (c.mode != PCA_MODE_BF16 || c.k != 1) return false;      // (the fp8 mode: nobody has asserted it yet)
+  const StepPlan pl = plan(c, true, has_lengths ? &some_lengths : nullptr);
+  if (pl.isab128[0] && pl.isab128[1] && pl.pma_head) return pl.tail.slabs && !has_lengths;
+  if (pl.isab256[0] && pl.isab256[1] && pl.pma256) return !has_lengths;
+  if (c.d != 64 || c.B > 256 || !(c.din == 64 || (c.din >= 1 && c.din <= 4)))
+    return false;
+  const pca_mab_shape* blocks[5] = {&pl.m0[0], &pl.m1[0], &pl.m0[1], &pl.m1[1], &pl.pma};
+  const BlockPath path[5] = {pl.path_m0[0], pl.path_m1[0], pl.path_m0[1], pl.path_m1[1], pl.path_pma};
+  for (int i = 0; i < 5; ++i)
+    if (path[i] != BlockPath::Exact || !attn_core_ok(*blocks[i])) return false;
+  return true;
+}
+
 struct Ws {
   void* saved[5];            // mab0[0], mab1[0], mab0[1], mab1[1], pma
   float *H[2], *Y[2], *P, *logits, *dlogits;
   float *dP, *dY2, *dY1, *dH, *clsws;
   void* scratch;             // forward + PMA backward
+  size_t scratch_bytes;
   void* scratch_bw[2];       // backward of enc.0 / enc.1: separate, because the deferred reductions and
                              // post stages read each block's operands at the end of the step
                              // (bwd_defer_flush), after the other layer's backward has run
@@ -248,6 +274,7 @@ inline size_t carve(const pca_st_config& c, const StepPlan& pl, Ws* out, void* b
     w.clsws = cv.take<float>(2 * (size_t)c.B);
   }
   w.scratch = cv.take<char>(max_scratch);
+  w.scratch_bytes = max_scratch;
   for (int li = 0; li < 2; ++li)
     w.scratch_bw[li] = pl.training ? (void*)cv.take<char>(max_scratch) : w.scratch;
   w.scratch_pma = pl.pma256 ? (void*)cv.take<char>(mab_bwd_ws_bytes(pl.path_pma, pl.pma)) : w.scratch;
@@ -580,6 +607,16 @@ int st_train_fwd_bwd(const pca_st_config* c, const float* p, const float* X, con
   // what this call hands from block to block (StepCtx)
   StepCtx ctx{};
   ctx.images = images.n > 0 ? &images : nullptr;
+  if (c->mode != PCA_MODE_F32 && c->d == 64 && pl.path_pma == BlockPath::Exact) {
+    // the d = 64 chain: after the PMA's backward nothing of this call uses `scratch`, so the ISAB blocks leave
+    // their weight-gradient slabs behind the PMA's area and the sums ride in the terminal launch (D.late)
+    const size_t used = align256(mab_bwd_ws_bytes(pl.path_pma, pl.pma));
+    if (used < w.scratch_bytes) {
+      ctx.wg64_late = &posts.late;
+      ctx.wg64_room = reinterpret_cast<float*>(static_cast<char*>(w.scratch) + used);
+      ctx.wg64_room_elems = (w.scratch_bytes - used) / sizeof(float);
+    }
+  }
   if (phase != 1) {
     PmaHeadArgs head{};
     if (pl.pma_head)
@@ -622,6 +659,11 @@ int64_t pca_st_param_count(const pca_st_config* c) {
 int64_t pca_st_bucket_split(const pca_st_config* c) {
   if (pca::validate(c) != PCA_OK) return -1;
   return pca::layout(*c).enc1_begin;
+}
+
+int pca_st_step_reproducible(const pca_st_config* c, int has_lengths) {
+  if (pca::validate(c) != PCA_OK) return 0;
+  return pca::step_reproducible(*c, has_lengths != 0) ? 1 : 0;
 }
 
 size_t pca_st_ws_bytes(const pca_st_config* c, int training) {

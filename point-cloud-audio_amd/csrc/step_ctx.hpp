@@ -32,6 +32,12 @@ struct StepCtx {
   bool armed, has, has_dx;
   Wgrad256Job job;
   DxHandoff dx;
+  // d = 64 chain backward (mab_f32_bwd): where a block may leave the slabs of its wgrad64 calls until the flush
+  // (room the step no longer uses; the block advances the cursor) and the list their sums join - rider rows of
+  // the step's terminal launch instead of a launch per block.  Null: the block sums before it returns.
+  SlabSumJobs* wg64_late;
+  float* wg64_room;
+  size_t wg64_room_elems;
 };
 inline BwdDefer* defer_of(const StepCtx* c) { return c != nullptr ? c->defer : nullptr; }
 inline const WeightImages* images_of(const StepCtx* c) { return c != nullptr ? c->images : nullptr; }

@@ -1,4 +1,4 @@
-// Weight and bias gradient of a 64 -> 64 Linear over a tall activation, one launch:
+// Weight and bias gradient of a 64 -> 64 Linear over a tall activation, one launch and one fixed-order sum:
 //   dW[64][64] += dY[M][64]^T X[M][64],  db[64] += colsum(dY)
 // (the adjoint of fc_q / fc_k / fc_v / fc_o, set_transformer-master/modules.py:13-16, for the shipped
 // d = 64 models, Code/models.py:34-44 with dim_hidden = 64).  The generic split-K GEMM reads the
@@ -13,11 +13,17 @@
 // to bf16 (RNE) as the generic bf16-operand GEMM does, accumulation is fp32, the bias sum is fp32 of the
 // unrounded dY.  The next group's rows are loaded under the current group's products.  Each wave
 // leaves its block in an LDS slab of its own (float atomics in LDS measured 4 x slower), the workgroup
-// sums the slabs and adds the result with coalesced atomics (as the split-K GEMM it replaces).
+// sums the slabs and stores the result to a slab of its own in global memory, part[blockIdx.x][64 * 64 + 64]
+// (dW first, db behind it), with coalesced 16-byte stores.  No workgroup adds onto dW / db: the launcher
+// hands back two SlabSumJobs (bwd_defer.hpp) per call, dW += sum_wg slab and db += sum_wg slab, which the
+// caller runs in k_slab_sum_jobs - as many calls' jobs in one launch as it likes.  The workgroup count is a
+// function of M alone and the sums run in index order, so the bits of dW / db depend on the arguments only:
+// not on the device, not on how the launch is issued, not on the order the workgroups finish in.
 #include "pca_common.h"
 
 #include <stdint.h>
 #include "blocks.hpp"
+#include "bwd_defer.hpp"
 #include "mfma_common.hpp"
 
 namespace pca {
@@ -43,12 +49,13 @@ __device__ __forceinline__ bf16x4 col_of(const float4 (&t)[4], int j) {
 
 constexpr int WG_WAVES = 16;       // waves per workgroup
 constexpr int WG_SLABS = 8;        // LDS slabs: waves w and w + 8 share one (two rounds)
+constexpr int SLAB_W = 64 * 64 + 64;   // floats of a slab, in LDS and in `part`: dW, then db at float 4096
 
+// part [gridDim.x][SLAB_W]: every workgroup writes its whole slab (a wave without a row group adds zeros)
 __global__ __launch_bounds__(64 * WG_WAVES) void k_wgrad64(const float* __restrict__ dY,
                                                            const float* __restrict__ X,
-                                                           float* __restrict__ dW,
-                                                           float* __restrict__ db, int64_t M) {
-  extern __shared__ float sW[];                 // [WG_SLABS][64 * 64 + 64]
+                                                           float* __restrict__ part, int64_t M) {
+  extern __shared__ __align__(16) float sW[];   // [WG_SLABS][SLAB_W]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int og = lane & 15, kg = lane >> 4;
 
@@ -102,7 +109,7 @@ __global__ __launch_bounds__(64 * WG_WAVES) void k_wgrad64(const float* __restri
   bs.x += __shfl_xor(bs.x, 32); bs.y += __shfl_xor(bs.y, 32);
   bs.z += __shfl_xor(bs.z, 32); bs.w += __shfl_xor(bs.w, 32);
   // waves 0..7 store their blocks, waves 8..15 add theirs on top (each lane its own elements)
-  float* slab = sW + (wave & (WG_SLABS - 1)) * (64 * 64 + 64);
+  float* slab = sW + (wave & (WG_SLABS - 1)) * SLAB_W;
 #pragma unroll
   for (int round = 0; round < WG_WAVES / WG_SLABS; ++round) {
     if (wave / WG_SLABS == round) {
@@ -125,13 +132,16 @@ __global__ __launch_bounds__(64 * WG_WAVES) void k_wgrad64(const float* __restri
     }
     __syncthreads();
   }
-  // (few, wide workgroups: atomics of different workgroups onto one cache line serialise, ~25 ns each -
-  // 256 workgroups x 130 lines cost ~6 us per call)
-  for (int i = tid; i < 64 * 64 + (db != nullptr ? 64 : 0); i += 64 * WG_WAVES) {
-    float v = 0.f;
+  // the workgroup's sum, LDS slabs in index order, to its own slab: 16 bytes per lane, whole lines per wave
+  float* __restrict__ out = part + (int64_t)blockIdx.x * SLAB_W;
+  for (int i = 4 * tid; i < SLAB_W; i += 4 * 64 * WG_WAVES) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-    for (int w = 0; w < WG_SLABS; ++w) v += sW[w * (64 * 64 + 64) + i];
-    atomicAdd(i < 64 * 64 ? dW + i : db + (i - 64 * 64), v);
+    for (int w = 0; w < WG_SLABS; ++w) {
+      const float4 p = *reinterpret_cast<const float4*>(sW + w * SLAB_W + i);
+      v.x += p.x; v.y += p.y; v.z += p.z; v.w += p.w;
+    }
+    *reinterpret_cast<float4*>(out + i) = v;
   }
 }
 
@@ -140,12 +150,12 @@ __global__ __launch_bounds__(64 * WG_WAVES) void k_wgrad64(const float* __restri
 // Lane (og, kg) of a wave takes columns 4 og .. 4 og + 3 of four rows of the wave's 16-row group.
 constexpr int NWN = 16;            // waves per workgroup of the narrow kernel
 
+// part [gridDim.x][64 * DQ + 64]: dW, then db at float 64 DQ; every workgroup writes its whole slab
 template <int DQ>
 __global__ __launch_bounds__(64 * NWN) void k_wgrad64_narrow(const float* __restrict__ dY,
                                                         const float* __restrict__ X,
-                                                        float* __restrict__ dW,
-                                                        float* __restrict__ db, int64_t M) {
-  __shared__ float sP[NWN][64 * (DQ + 1)];
+                                                        float* __restrict__ part, int64_t M) {
+  __shared__ __align__(16) float sP[NWN][64 * (DQ + 1)];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int og = lane & 15, kg = lane >> 4;
   float acc[4][DQ];
@@ -218,36 +228,65 @@ __global__ __launch_bounds__(64 * NWN) void k_wgrad64_narrow(const float* __rest
     }
   }
   __syncthreads();
-  // few, wide workgroups on purpose: the 64 DQ + 64 results are a handful of cache lines, and atomics of
-  // different workgroups onto ONE line serialise at ~25 ns each - 512 workgroups cost 13 us here
-  for (int i = tid; i < 64 * DQ + (db != nullptr ? 64 : 0); i += 64 * NWN) {
-    float v = 0.f;
+  // the waves' results in index order to the workgroup's slab (a handful of cache lines: few, wide workgroups
+  // keep the sum that follows short)
+  float* __restrict__ out = part + (int64_t)blockIdx.x * (64 * (DQ + 1));
+  for (int i = 4 * tid; i < 64 * (DQ + 1); i += 4 * 64 * NWN) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-    for (int w = 0; w < NWN; ++w) v += sP[w][i];
-    atomicAdd(i < 64 * DQ ? dW + i : db + (i - 64 * DQ), v);
+    for (int w = 0; w < NWN; ++w) {
+      const float4 p = *reinterpret_cast<const float4*>(&sP[w][i]);
+      v.x += p.x; v.y += p.y; v.z += p.z; v.w += p.w;
+    }
+    *reinterpret_cast<float4*>(out + i) = v;
   }
 }
 
 }  // namespace
 
-bool wgrad64_ok(const float* dY, const float* X, int64_t M, int din, int dout) {
+// workgroups of a call: a function of M alone (a 16-row group per wave before anyone gets a second; few, wide
+// workgroups keep the slabs and their sum small; the wide kernel's 8 LDS slabs take 130 KB, one workgroup per CU)
+static int64_t wgrad64_wgs(int64_t M) {
+  const int64_t wgs = cdiv(cdiv(M, 16), WG_WAVES);
+  return wgs > 128 ? 128 : wgs < 1 ? 1 : wgs;
+}
+static_assert(WG_WAVES == NWN, "one workgroup count for both kernels");
+
+// floats of the slabs of one call (0: not a shape of these kernels), from the shape alone
+size_t wgrad64_slab_elems(int64_t M, int din, int dout) {
+  if (dout != 64 || M < 1 || !(din == 64 || (din >= 1 && din <= 4))) return 0;
+  return (size_t)wgrad64_wgs(M) * 64 * (din + 1);
+}
+
+// (dW, db: the sums add onto them 16 bytes at a time; db may be null)
+bool wgrad64_ok(const float* dY, const float* X, const float* dW, const float* db, int64_t M, int din,
+                int dout) {
+  if (((reinterpret_cast<uintptr_t>(dW) | reinterpret_cast<uintptr_t>(db)) & 15) != 0) return false;
   if (dout == 64 && din >= 1 && din <= 4 && M >= 1)
     return (reinterpret_cast<uintptr_t>(dY) & 15) == 0;
   return din == 64 && dout == 64 && M >= 1 && ((reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(X)) & 15) == 0;
 }
 
-// dW += dY^T X and (db != nullptr) db += colsum(dY); both outputs are accumulated into
-int wgrad64(const float* dY, const float* X, float* dW, float* db, int64_t M, int din,
-            hipStream_t st) {
-  PCA_REQUIRE(dY && X && dW && M > 0 && (din == 64 || (din >= 1 && din <= 4)),
+// dW += dY^T X and (db != nullptr) db += colsum(dY): the launch writes part [wgs][64 din + 64]
+// (wgrad64_slab_elems floats, 16-byte aligned) and the two sums that finish the call are appended to `jobs`;
+// dW and db are complete once the caller has run them (slab_sum_jobs), each with ONE addition onto what was there
+int wgrad64(const float* dY, const float* X, float* dW, float* db, int64_t M, int din, float* part,
+            SlabSumJobs* jobs, hipStream_t st) {
+  PCA_REQUIRE(dY && X && dW && part && jobs && M > 0 && (din == 64 || (din >= 1 && din <= 4)),
               "wgrad64: bad arguments");
+  PCA_REQUIRE(jobs->n + 2 <= (int)(sizeof(jobs->j) / sizeof(jobs->j[0])), "wgrad64: job list full");
+  const int64_t wgs = wgrad64_wgs(M);
+  const int stride = 64 * (din + 1);
+  const SlabSumJob jw{part, dW, (int)wgs, 64 * din, 2, stride};
+  const SlabSumJob jb{part + 64 * din, db, (int)wgs, 64, 2, stride};
+  PCA_REQUIRE(slab_sum_job_ok(jw) && (db == nullptr || slab_sum_job_ok(jb)), "wgrad64: alignment");
+  jobs->j[jobs->n++] = jw;
+  if (db != nullptr) jobs->j[jobs->n++] = jb;
   if (din <= 4) {
-    int64_t wgs = cdiv(cdiv(M, 16), NWN);       // a 16-row group per wave before anyone gets a second
-    if (wgs > 128) wgs = 128;                   // (see the kernel's last loop)
 #define PCA_NARROW(Q)                                                                          \
   case Q:                                                                                      \
-    hipLaunchKernelGGL((k_wgrad64_narrow<Q>), dim3((unsigned)wgs), dim3(64 * NWN), 0, st, dY, X, dW, \
-                       db, M);                                                                 \
+    hipLaunchKernelGGL((k_wgrad64_narrow<Q>), dim3((unsigned)wgs), dim3(64 * NWN), 0, st, dY, X, part, \
+                       M);                                                                     \
     break;
     switch (din) {
       PCA_NARROW(1) PCA_NARROW(2) PCA_NARROW(3) PCA_NARROW(4)
@@ -255,20 +294,14 @@ int wgrad64(const float* dY, const float* X, float* dW, float* db, int64_t M, in
 #undef PCA_NARROW
     return check_launch("k_wgrad64_narrow");
   }
-  const int64_t groups = (M + 15) / 16;
-  // one workgroup per CU at most (its 8 slabs take 130 KB of LDS); 128 x 4160 atomics per call
-  int64_t wgs = cdiv(groups, WG_WAVES);
-  if (wgs > 128) wgs = 128;
-  if (wgs < 1) wgs = 1;
   static const int once = [] {
     return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad64),
                                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    WG_SLABS * (64 * 64 + 64) * (int)sizeof(float));
+                                    WG_SLABS * SLAB_W * (int)sizeof(float));
   }();
-  PCA_REQUIRE(once == 0, "wgrad64: cannot reserve %d bytes of LDS",
-              WG_SLABS * (64 * 64 + 64) * (int)sizeof(float));
-  hipLaunchKernelGGL(k_wgrad64, dim3((unsigned)wgs), dim3(64 * WG_WAVES),
-                     WG_SLABS * (64 * 64 + 64) * sizeof(float), st, dY, X, dW, db, M);
+  PCA_REQUIRE(once == 0, "wgrad64: cannot reserve %d bytes of LDS", WG_SLABS * SLAB_W * (int)sizeof(float));
+  hipLaunchKernelGGL(k_wgrad64, dim3((unsigned)wgs), dim3(64 * WG_WAVES), WG_SLABS * SLAB_W * sizeof(float),
+                     st, dY, X, part, M);
   return check_launch("k_wgrad64");
 }
 

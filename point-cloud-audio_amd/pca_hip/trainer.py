@@ -281,6 +281,18 @@ class STEngine:
                 self._handoff_word = self.ws[off:off + 4].view(torch.int32)
                 self._handoff_word.zero_()
 
+    def reproducible(self, lengths: bool = False) -> bool:
+        """Whether the library guarantees that two identical ``fwd_bwd`` calls of this engine (with
+        ``lengths``, if set) give identical bits: logits, loss, statistics and every gradient, launched
+        eagerly or replayed from a graph (pca_st_step_reproducible)."""
+        return bool(lib().pca_st_step_reproducible(C.byref(self.cfg), int(bool(lengths))))
+
+    @property
+    def bit_reproducible(self) -> bool:
+        """``reproducible()`` for dense batches: True for the fused d = 128 / d = 256 steps and the d = 64
+        step of the shipped shapes in the bf16 mode (B <= 256), False in the exact fp32 mode."""
+        return self.reproducible(False)
+
     def check_handoffs(self) -> None:
         """Raise if a pair hand-off of the set-resident forward ever timed out (one host sync): a
         workgroup whose partner was not scheduled within ~1 s went on with stale data, i.e. every
@@ -556,6 +568,13 @@ class Trainer:
             dist.broadcast(self.eng.flat, src=0, group=self.pg)
             if self.averaged is not None:
                 self.averaged.copy_(self.eng.flat)
+
+    @property
+    def bit_reproducible(self) -> bool:
+        """Whether the library guarantees this Trainer's forward + backward bit for bit (STEngine.reproducible,
+        for the batches of this dataset: padded ones if it is ``variable_length``): then a graph replay equals
+        the eager launches, and a run resumed from ``state_dict()`` equals the uninterrupted one."""
+        return self.eng.reproducible(self.lengths is not None)
 
     # ---- how the gradients are exchanged ---------------------------------------------
     def set_exchange(self, form: str) -> None:
