@@ -961,7 +961,11 @@ int pca_st_pool_attention(const pca_st_config* c, const float* params, const flo
 /* phase 0: forward, mean cross-entropy (loss_out[0]; stats += {sum loss, #correct}),
  *          backward through dec and enc.1 ; phase 1: backward through enc.0.
  * phase -1 runs both.  grads is ACCUMULATED into (caller zeroes it once per step).
- * grad_scale multiplies dlogits (1.0 normally).  labels int64[B]. */
+ * grad_scale multiplies dlogits (1.0 normally).  labels int64[B].
+ * lengths: as at pca_st_forward (NULL, or 1 <= lengths[b] <= N with finite padding rows).  It does not
+ * choose the launches: at the shapes of the set-resident d = 128 forward (d = 128, 4 heads, m = 16,
+ * N = 256 or 512, bf16) a step with lengths is that one launch, as the dense step is, and the padding is
+ * masked inside it; pca_st_ws_bytes is the same either way. */
 int pca_st_train_fwd_bwd(const pca_st_config* c, const float* params, const float* X,
                          const int32_t* lengths, const int64_t* labels, float* grads,
                          float* loss_out, float* stats, float* logits, float grad_scale,

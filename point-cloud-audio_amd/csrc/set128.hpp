@@ -1,7 +1,10 @@
 // Set-resident kernels of the d = 128 / 4 heads / m = 16 / k = 1 train step (BASELINE configs[1]):
 // a PAIR of workgroups carries a whole set through ISAB -> ISAB -> PMA (set_transformer-master/
 // modules.py:51-53, 62-63 with :19-33 inside; Code/models.py:34-44), each its half of the set's
-// [N, 128] activations resident in LDS.  Declarations shared by set128_fwd.hip and the ST engine.
+// [N, 128] activations resident in LDS.  The sets are dense, or padded with a length per set
+// (Set128FwdArgs::lengths): the padding is masked out of the three attentions over the points, and the
+// pair protocol - barriers, flags, hand-off payloads - is the same whatever the lengths are.
+// Declarations shared by set128_fwd.hip and the ST engine.
 #pragma once
 #include "bwd_defer.hpp"
 
@@ -60,6 +63,12 @@ struct Set128FwdArgs {
   __bf16* dY2;            // [B][N][128] bf16 (written, not accumulated)
   float* pma_slabs;       // [B][S][4][128], slab b S + sp over the points [sp N / S, (sp + 1) N / S)
   int pma_S;              // k_mab0_bwd's point splits per set (mab0_bwd_splits): 2, or 4 at N = 512
+  // variable-length sets: device int32 [B], 1 <= lengths[b] <= N (pca_hip.h, "variable-size sets"), or null for
+  // dense sets.  The points at and beyond lengths[b] are no keys of the three attentions over the points
+  // (both ISABs' few-queries blocks, the PMA) and get exact-zero dY2 rows from the tail's PMA backward; their
+  // rows of the many-queries blocks are computed from the (finite) padding and stored, as k_mab1_fwd does.
+  // (Last member: the dense instantiations read every other argument at the offset it always had.)
+  const int32_t* lengths;
 };
 
 // bytes of `flags` (the block the preparation launch clears) / of the whole exchange area

@@ -31,6 +31,7 @@
 // PMA epilogue and the classifier run in k_pma_head1); algorithmic bytes 4 N din + 4 (2 N d) per set.
 #include "set128.hpp"
 #include "mfma_common.hpp"
+#include "softmax_merge.hpp"
 
 #include <math.h>
 
@@ -123,6 +124,22 @@ __device__ unsigned long long g_set_stamps[16 * 32];
 #else
 #define STAMP(i) do { } while (0)
 #endif
+
+// ---- variable-length sets (template parameter LEN of the kernel; Set128FwdArgs::lengths) ---------
+// The points at and beyond len = min(lengths[b], N) are no keys: their scores are -inf before the running
+// max, a 32-point unit (a wave's range of pairs in layer 1) that lies wholly beyond len skips its arithmetic
+// and leaves the EMPTY partial (m, l, t) = (-inf, 0, 0), and every merge of two partials takes its factors
+// from fac<LEN> (softmax_merge.hpp), for which the empty partial is the identity.  len is uniform over the
+// workgroup, so is every skip; masking and skipping remove ARITHMETIC ONLY: whatever len is, every
+// workgroup of a pair reaches every barrier, stores every flag, waits for every flag and writes complete
+// hand-off payloads (an empty partial travels as zeros with m = -inf).  len >= 1: point 0 is a key, so half 0
+// of a set, and with it every merge across the halves, has a finite max.  LEN = false: the dense kernel,
+// the expressions it always had.
+template <bool LEN>
+__device__ __forceinline__ float fac(float m, float M) {
+  if constexpr (LEN) return merge_factor(m, M);
+  else return __builtin_amdgcn_exp2f(m - M);
+}
 
 struct Ctx {
   int b, half, N, NH, tid, lane, wave, q, j, r, g;
@@ -487,6 +504,7 @@ struct PmaBwdLds {
                        RED = 32768;
 };
 
+template <bool LEN>
 __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, const float* sPm,
                                             const float* theirs, float* sh, bool wr, char* bw) {
   constexpr int DH = 32, R = 4;
@@ -537,7 +555,7 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     const int rr = tid >> 7;
     const float m0 = P0[512 + rr], m1 = P1[512 + rr];
     const float M = fmaxf(m0, m1);
-    const float f0 = __builtin_amdgcn_exp2f(m0 - M), f1 = __builtin_amdgcn_exp2f(m1 - M);
+    const float f0 = fac<LEN>(m0, M), f1 = fac<LEN>(m1, M);     // (half 1 of a short set: the empty partial)
     const float Lt = f0 * P0[516 + rr] + f1 * P1[516 + rr];
     const float v = (f0 * P0[tid] + f1 * P1[tid]) / Lt;
     sT[tid] = v;
@@ -780,8 +798,12 @@ __device__ __forceinline__ bf16x8 tr_frag_img(const char* img, int rowb, int t, 
   return r;
 }
 
+// LEN: a point at or beyond `len` (an index within the set) has P = 0 exactly, as in k_mab0_bwd with lengths: its
+// dS is 0, its dY2 row is written as exact zeros, and the dG slab of a split without a valid point is exact
+// zeros (0 times the finite rows of sY).  Every stage still runs over all the rows.
+template <bool LEN>
 __device__ __forceinline__ void pma_bwd_tail(const __bf16* Gpma, __bf16* dY2, float* slabs, int S,
-                                             const Ctx& c, char* sY, char* bw) {
+                                             const Ctx& c, char* sY, char* bw, int len) {
   constexpr float LN2 = 0.6931471805599453f;
   const int tid = c.tid, lane = c.lane, r = c.r, g = c.g;
   const int ntile = c.NH >> 5, sph = S >> 1, tps = ntile / sph;      // tiles, splits of this half, tiles per split
@@ -818,9 +840,10 @@ __device__ __forceinline__ void pma_bwd_tail(const __bf16* Gpma, __bf16* dY2, fl
         da = mfma32(*reinterpret_cast<const bf16x8*>(bw + PmaBwdLds::DT + y_off(r, 4 * ks + g)), xr, da);
       }
       f32x4 pt, dst;
+      const bool key = !LEN || c.half * c.NH + 32 * c.wave + 16 * pb + r < len;     // column r = the point
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float p = g == 0 ? exp2f(sv[e] - lse[e]) : 0.f;
+        const float p = g == 0 && key ? exp2f(sv[e] - lse[e]) : 0.f;
         pt[e] = p;
         dst[e] = g == 0 ? LN2 * p * (da[e] - del[e]) : 0.f;     // (+0, as the padded rows were)
       }
@@ -934,7 +957,19 @@ __device__ __forceinline__ void rederive(Ctx& c) {
 //  constant address space back, the loads stay scalar)
 #define LAYER(i) (*(const Set128Layer*)(&ap->L[i]))
 
-template <int DIN, int UPQ>
+// the set's number of valid points: min(lengths[b], N) - a scalar load at the phase that asks, like every
+// other argument - or N itself in the dense kernel
+template <bool LEN>
+__device__ __forceinline__ int set_len(karg_t* ap, int b, int N) {
+  if constexpr (LEN) {
+    const int l = ap->lengths[b];
+    return l < N ? l : N;
+  } else {
+    return N;
+  }
+}
+
+template <int DIN, int UPQ, bool LEN>
 __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_value) {
   (void)a_by_value;
   karg_t* ap = launder((karg_t*)__builtin_amdgcn_kernarg_segment_ptr());
@@ -1008,20 +1043,30 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
     }
     lds_barrier();
     const int npw = N >> 5, q0 = c.wave * npw;       // 8 or 16 pairs of points per wave
+    // LEN: the wave walks the pairs that hold a valid point (none: both loops are empty and the wave keeps
+    // (m, l, t) = (-inf, 0, 0) without an exp2 of -inf - -inf); the second point of the set's last pair is
+    // masked when len is odd - the pair's first point is valid, so m is finite and its p is exp2(-inf) = 0
+    const int len = set_len<LEN>(ap, b, N);
+    int np = npw;
+    if (LEN) {
+      const int left = len - 2 * q0;                 // valid points from the wave's first one on
+      np = left <= 0 ? 0 : (left + 1) >> 1 < npw ? (left + 1) >> 1 : npw;
+    }
     float m = -INFINITY;
 #pragma unroll 8
-    for (int i = 0; i < npw; ++i) {
+    for (int i = 0; i < np; ++i) {
       const float* px = sXp + (q0 + i) * 8;
       f32x2 sv = gk[0] * *reinterpret_cast<const f32x2*>(px);
 #pragma unroll
       for (int cc = 1; cc < DIN; ++cc) sv += gk[cc] * *reinterpret_cast<const f32x2*>(px + 2 * cc);
+      if (LEN && 2 * (q0 + i) + 1 >= len) sv[1] = -INFINITY;
       m = max_nn(m, max_nn(sv[0], sv[1]));
     }
     f32x2 l2 = {0.f, 0.f}, t2[DIN];
 #pragma unroll
     for (int cc = 0; cc < DIN; ++cc) t2[cc] = f32x2{0.f, 0.f};
 #pragma unroll 8
-    for (int i = 0; i < npw; ++i) {
+    for (int i = 0; i < np; ++i) {
       const float* px = sXp + (q0 + i) * 8;
       f32x2 xv[DIN];
 #pragma unroll
@@ -1029,6 +1074,7 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
       f32x2 sv = gk[0] * xv[0];
 #pragma unroll
       for (int cc = 1; cc < DIN; ++cc) sv += gk[cc] * xv[cc];
+      if (LEN && 2 * (q0 + i) + 1 >= len) sv[1] = -INFINITY;
       const f32x2 p = {__builtin_amdgcn_exp2f(sv[0] - m), __builtin_amdgcn_exp2f(sv[1] - m)};
       l2 += p;
 #pragma unroll
@@ -1099,9 +1145,15 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
     f32x4 T[8];
 #pragma unroll
     for (int ft = 0; ft < 8; ++ft) T[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int len = set_len<LEN>(ap, b, c.N);
 #pragma unroll
     for (int u = 0; u < UPQ; ++u) {
       const char* img = sY + (c.qn0 + 32 * u) * ROWB;
+      // LEN: the unit's first point within the set; a unit wholly beyond len adds nothing to (m, l, T)
+      // (wave-uniform: c.qn0 comes from the wave's index).  A unit that runs holds a valid point, so its
+      // running max is finite
+      const int p0 = c.half * NH + c.qn0 + 32 * u;
+      if (LEN && p0 >= len) continue;
       f32x4 s[2];
 #pragma unroll
       for (int pb = 0; pb < 2; ++pb) {
@@ -1112,6 +1164,14 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
                          s[pb]);
       }
       // rows of s = points 16 pb + 4 g + e ; column = query row r of this head
+      if (LEN) {
+        const int left = len - p0 - 4 * g;
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (16 * pb + e >= left) s[pb][e] = -INFINITY;
+      }
       float mt = -INFINITY;
 #pragma unroll
       for (int pb = 0; pb < 2; ++pb)
@@ -1153,7 +1213,7 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
     auto take_partial = [&](int slot, int from_wave) {
       const float2 ml = *reinterpret_cast<const float2*>(sML + (from_wave * 16 + r) * 2);
       const float mn = max_nn(mrow, ml.x);
-      const float f1 = __builtin_amdgcn_exp2f(mrow - mn), f2 = __builtin_amdgcn_exp2f(ml.x - mn);
+      const float f1 = fac<LEN>(mrow, mn), f2 = fac<LEN>(ml.x, mn);
       lrow = lrow * f1 + ml.y * f2;
       mrow = mn;
       if (g == 0) {
@@ -1217,7 +1277,8 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
         return h0 ? __builtin_fmaf(fp_, xp_, fo_ * xo_) : __builtin_fmaf(fo_, xo_, fp_ * xp_);
       };
       const float Mx = fmaxf(mrow, pml.x);
-      const float fo = __builtin_amdgcn_exp2f(mrow - Mx), fp = __builtin_amdgcn_exp2f(pml.x - Mx);
+      // (LEN: half 1 of a set with len <= N / 2 published the empty partial; half 0 holds point 0: Mx is finite)
+      const float fo = fac<LEN>(mrow, Mx), fp = fac<LEN>(pml.x, Mx);
       const float Lt = comb(fo, lrow, fp, pml.y);
       const float inv = 1.f / Lt;
       if (g == 0) {
@@ -1278,7 +1339,11 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
 #pragma unroll
     for (int ft = 0; ft < 8; ++ft) T[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int nun = NH >> 5;                    // 4 or 8 units
-    if (c.wave < nun) {
+    // LEN: a unit wholly beyond len keeps the empty partial (-inf, 0, 0) - its slab is written all the same -
+    // and the merges below pass over it (fac)
+    const int len = set_len<LEN>(ap, b, c.N);
+    const int p0 = c.half * NH + 32 * c.wave;   // the unit's first point within the set
+    if (c.wave < nun && (!LEN || p0 < len)) {
       const char* img = sY + (32 * c.wave) * ROWB;
       f32x4 s[2];
 #pragma unroll
@@ -1288,6 +1353,14 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
         for (int ks = 0; ks < 4; ++ks)
           s[pb] = mfma32(*reinterpret_cast<const bf16x8*>(img + y_off(16 * pb + r, 4 * ks + g)),
                          gload8(ap->Gpma + (int64_t)r * D + 32 * ks + 8 * g), s[pb]);
+      }
+      if (LEN) {
+        const int left = len - p0 - 4 * g;      // rows of s = points 16 pb + 4 g + e
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (16 * pb + e >= left) s[pb][e] = -INFINITY;
       }
       float mt = -INFINITY;
 #pragma unroll
@@ -1332,7 +1405,7 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
         for (int w = p * upp; w < (p + 1) * upp; ++w) M = fmaxf(M, s0[w * 520 + 512 + rr]);
         float Ls = 0.f, t = 0.f;
         for (int w = p * upp; w < (p + 1) * upp; ++w) {
-          const float fs = __builtin_amdgcn_exp2f(s0[w * 520 + 512 + rr] - M);
+          const float fs = fac<LEN>(s0[w * 520 + 512 + rr], M);
           Ls += fs * s0[w * 520 + 516 + rr];
           t += fs * s0[w * 520 + rr * D + f];
         }
@@ -1355,7 +1428,7 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
       for (int w = 0; w < nun; ++w) M = fmaxf(M, s0[w * 520 + 512 + rr]);
       float Ls = 0.f, t = 0.f;
       for (int w = 0; w < nun; ++w) {
-        const float fs = __builtin_amdgcn_exp2f(s0[w * 520 + 512 + rr] - M);
+        const float fs = fac<LEN>(s0[w * 520 + 512 + rr], M);
         Ls += fs * s0[w * 520 + 516 + rr];
         t += fs * s0[w * 520 + rr * D + f];
       }
@@ -1382,13 +1455,13 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
     }
     if (c.wave == 0) flag_wait(flags + 4 + (b * 2 + 0) * 2 + (c.half ^ 1), 3u, flags);
     lds_barrier();
-    head_stages(*(const PmaHeadArgs*)(&ap->head), c, sPm, exTheirs, reinterpret_cast<float*>(sS) + 1024,
-                c.half == 0, pbwd ? sO : nullptr);
+    head_stages<LEN>(*(const PmaHeadArgs*)(&ap->head), c, sPm, exTheirs, reinterpret_cast<float*>(sS) + 1024,
+                     c.half == 0, pbwd ? sO : nullptr);
     STAMP(19);
     if (pbwd) {
       ap = launder(ap);
       rederive(c);
-      pma_bwd_tail(ap->Gpma, ap->dY2, ap->pma_slabs, ap->pma_S, c, sY, sO);
+      pma_bwd_tail<LEN>(ap->Gpma, ap->dY2, ap->pma_slabs, ap->pma_S, c, sY, sO, set_len<LEN>(ap, c.b, c.N));
       STAMP(27);
     }
   }
@@ -1401,6 +1474,12 @@ extern "C" int pca_debug_set_stamps(unsigned long long* out) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_set_stamps), sizeof(g_set_stamps));
 }
 #endif
+
+// softmax_merge.hpp on the host, for the tests: the factor of a partial with max m against the merged max M as
+// the kernel's merges form it (guarded != 0), or the bare 2^(m - M) they formed before sets had lengths
+extern "C" float pca_debug_merge_factor(float m, float M, int guarded) {
+  return guarded ? merge_factor(m, M) : merge_exp2(m - M);
+}
 
 size_t set128_flag_bytes(int B) { return align256((size_t)(4 + B * 4) * sizeof(uint32_t)); }
 
@@ -1423,13 +1502,28 @@ bool set128_shape_ok(int B, int N, int din, int d, int h, int m, int k) {
   return 16 * (int)cdiv(B, 8) <= cus;
 }
 
+// the eight (din, N / 256) instantiations of one LEN: 160 KiB of LDS allowed once, the one of `key` launched
+template <bool LEN>
+static void launch_instance(int key, dim3 grid, size_t lds, hipStream_t st, const Set128FwdArgs& a) {
+  allow_lds160<k_set128_fwd<1, 1, LEN>, k_set128_fwd<2, 1, LEN>, k_set128_fwd<3, 1, LEN>, k_set128_fwd<4, 1, LEN>,
+               k_set128_fwd<1, 2, LEN>, k_set128_fwd<2, 2, LEN>, k_set128_fwd<3, 2, LEN>, k_set128_fwd<4, 2, LEN>>();
+  switch (key) {
+    case 2: hipLaunchKernelGGL((k_set128_fwd<1, 1, LEN>), grid, dim3(NT), lds, st, a); break;
+    case 3: hipLaunchKernelGGL((k_set128_fwd<1, 2, LEN>), grid, dim3(NT), lds, st, a); break;
+    case 4: hipLaunchKernelGGL((k_set128_fwd<2, 1, LEN>), grid, dim3(NT), lds, st, a); break;
+    case 5: hipLaunchKernelGGL((k_set128_fwd<2, 2, LEN>), grid, dim3(NT), lds, st, a); break;
+    case 6: hipLaunchKernelGGL((k_set128_fwd<3, 1, LEN>), grid, dim3(NT), lds, st, a); break;
+    case 7: hipLaunchKernelGGL((k_set128_fwd<3, 2, LEN>), grid, dim3(NT), lds, st, a); break;
+    case 8: hipLaunchKernelGGL((k_set128_fwd<4, 1, LEN>), grid, dim3(NT), lds, st, a); break;
+    default: hipLaunchKernelGGL((k_set128_fwd<4, 2, LEN>), grid, dim3(NT), lds, st, a); break;
+  }
+}
+
 int set128_fwd_launch(const Set128FwdArgs& a, hipStream_t st) {
   PCA_REQUIRE(set128_shape_ok(a.B, a.N, a.din, 128, 4, 16, 1), "set128_fwd: B=%d N=%d din=%d not built",
               a.B, a.N, a.din);
   PCA_REQUIRE(a.Sp == 2 || a.Sp == 4, "set128_fwd: %d PMA partials", a.Sp);
   PCA_REQUIRE(a.Sp <= a.N / 128, "set128_fwd: %d PMA partials of %d points", a.Sp, a.N);
-  allow_lds160<k_set128_fwd<1, 1>, k_set128_fwd<2, 1>, k_set128_fwd<3, 1>, k_set128_fwd<4, 1>,
-               k_set128_fwd<1, 2>, k_set128_fwd<2, 2>, k_set128_fwd<3, 2>, k_set128_fwd<4, 2>>();
   const size_t lds = (size_t)512 * ROWB + 32768;
   // reference-formulation FLOPs of the three blocks this launch covers (the PMA's
   // epilogue and the classifier run in k_pma_head1), algorithmic bytes: X in, two [N, d] bf16 tensors
@@ -1448,16 +1542,8 @@ int set128_fwd_launch(const Set128FwdArgs& a, hipStream_t st) {
   ProfScope ps(PCA_K_SET_FWD, st, 2.0 * macs * a.B, (double)a.B * (4.0 * Nn * a.din + 4.0 * Nn * dd * nout));
   const dim3 grid(16 * (unsigned)cdiv(a.B, 8));
   const int key = a.din * 2 + (a.N == 512 ? 1 : 0);       // units per quad of waves: N / 256
-  switch (key) {
-    case 2: hipLaunchKernelGGL((k_set128_fwd<1, 1>), grid, dim3(NT), lds, st, a); break;
-    case 3: hipLaunchKernelGGL((k_set128_fwd<1, 2>), grid, dim3(NT), lds, st, a); break;
-    case 4: hipLaunchKernelGGL((k_set128_fwd<2, 1>), grid, dim3(NT), lds, st, a); break;
-    case 5: hipLaunchKernelGGL((k_set128_fwd<2, 2>), grid, dim3(NT), lds, st, a); break;
-    case 6: hipLaunchKernelGGL((k_set128_fwd<3, 1>), grid, dim3(NT), lds, st, a); break;
-    case 7: hipLaunchKernelGGL((k_set128_fwd<3, 2>), grid, dim3(NT), lds, st, a); break;
-    case 8: hipLaunchKernelGGL((k_set128_fwd<4, 1>), grid, dim3(NT), lds, st, a); break;
-    default: hipLaunchKernelGGL((k_set128_fwd<4, 2>), grid, dim3(NT), lds, st, a); break;
-  }
+  if (a.lengths == nullptr) launch_instance<false>(key, grid, lds, st, a);
+  else launch_instance<true>(key, grid, lds, st, a);      // variable-length sets: the masking instantiations
   ps.end();
   return check_launch("k_set128_fwd");
 }

@@ -108,7 +108,8 @@ struct StepPlan {
                        // flush - needs every block's operands in place until then
   bool set128_room;    // the shape fits the set-resident launch: carve() reserves its exchange area on this alone
   // per-call switches (environment read on every call: tests compare the two forms in-process)
-  bool set128;         // the set-resident forward (set128_fwd.hip) runs            (PCA_SET128=0: per-block launches)
+  bool set128;         // the set-resident forward (set128_fwd.hip) runs, with or without `lengths`
+                       //                                                            (PCA_SET128=0: per-block launches)
   bool fuse_head;      // ... with the head stages in its own tail                   (PCA_SET128_HEAD=0: as a launch)
   bool pma_bwd;        // ... and then the PMA's attention backward too              (PCA_SET128_PMABWD=0: k_mab0_bwd)
   TailForm tail;       // the d = 128 backward tail's switches, resolved (tail_form_from_env)
@@ -117,8 +118,9 @@ struct StepPlan {
 inline StepPlan plan(const pca_st_config& c, bool training, const int32_t* lengths) {
   // `lengths` changes no answer here and no workspace size: only the q_shared blocks carry it, which
   // mab1_bf16_supported never takes, and neither mab0_bf16_supported, mab0_d256_supported, sd64_kind's
-  // q_shared branch nor any *_bytes function reads k_lengths.  So pca_st_ws_bytes, which has no lengths,
-  // and the calls carve alike.
+  // q_shared branch nor any *_bytes function reads k_lengths.  The set-resident d = 128 launch takes dense
+  // and variable-length steps alike (Set128FwdArgs::lengths) in the exchange area reserved on the shape.  So
+  // pca_st_ws_bytes, which has no lengths, and the calls carve alike.
   StepPlan pl{};
   pl.training = training;
   for (int li = 0; li < 2; ++li) {
@@ -170,10 +172,10 @@ inline StepPlan plan(const pca_st_config& c, bool training, const int32_t* lengt
   pl.fq_defer[1] = pl.armed[1] = pl.isab256[1];      // (enc.0's mab1 reads the fp32 set: nothing to hand over)
   pl.defer_wg = pl.isab256[0] && pl.isab256[1] && pl.pma256;
   pl.set128_room = set128_shape_ok(c.B, c.N, c.din, c.d, c.h, c.m, c.k);
-  // the set-resident forward takes a step whose blocks are all on the fused d = 128 kernels, whose sets fit
-  // one workgroup's LDS and are dense
+  // the set-resident forward takes a step whose blocks are all on the fused d = 128 kernels and whose sets fit
+  // one workgroup's LDS - dense sets or padded ones with `lengths` (it masks the padding itself)
   pl.set128 = env_not_zero("PCA_SET128") && c.mode == PCA_MODE_BF16 && pl.act_bf16 && pl.set128_room &&
-              pl.isab128[0] && pl.isab128[1] && pl.pma_head && lengths == nullptr;
+              pl.isab128[0] && pl.isab128[1] && pl.pma_head;
   pl.fuse_head = pl.set128 && c.C <= 64 && env_not_zero("PCA_SET128_HEAD");
   pl.pma_bwd = pl.fuse_head && env_not_zero("PCA_SET128_PMABWD");
   pl.tail = tail_form_from_env();
@@ -409,6 +411,7 @@ Set128FwdArgs set128_args(const pca_st_config& c, const Layout& L, const StepPla
                           const float* X, const Ws& w, const PmaHeadArgs& head) {
   Set128FwdArgs a{};
   a.X = X; a.B = c.B; a.N = c.N; a.din = c.din;
+  a.lengths = pl.pma.k_lengths;          // (plan(): the call's `lengths`, the keys of all three attentions)
   a.scale_log2e = LOG2E / sqrtf((float)c.d);
   for (int li = 0; li < 2; ++li) {
     Mab0Saved v0;
