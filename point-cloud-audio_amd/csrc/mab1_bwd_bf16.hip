@@ -26,34 +26,10 @@ namespace pca {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 constexpr int TP = M1_TP;
 constexpr int NB = M1_NB;
 
-// ---- bf16 tile operands in 16-byte pieces ----
-// In the accumulator's shape lane (r, g) holds features 16t + 4g .. + 3 of point r: 8 bytes.  Tiles 2s and 2s + 1 of a
-// point are 64 contiguous bytes, and lane group g moves the 16-byte chunk chunk_of(g) of them: v_permlane16_swap
-// exchanges the odd 16-lane rows of its first operand with the even rows of its second, so with the first tile's dword
-// in front and the second tile's behind, groups 0 and 2 receive their odd neighbour's part of the first tile (chunks
-// 0, 1) and groups 1 and 3 their even neighbour's part of the second (chunks 2, 3).  The exchange is its own inverse:
-// a chunk as loaded goes back into the two tiles' fragments by the same two swaps.  The lanes that exchange hold the
-// same point, so a row's `live` guard holds for both.
-__device__ __forceinline__ int chunk_of(int g) { return ((g & 1) << 1) | (g >> 1); }
-__device__ __forceinline__ u32x4 frag_swap(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1) {
-  const auto x = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
-  const auto y = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
-  return u32x4{x[0], y[0], x[1], y[1]};
-}
-// this lane's four features of tiles 2s (a) and 2s + 1 (b) -> features 32s + 8 chunk_of(g) .. + 7
-__device__ __forceinline__ u32x4 to_chunk(bf16x4 a, bf16x4 b) {
-  const uint2 ua = __builtin_bit_cast(uint2, a), ub = __builtin_bit_cast(uint2, b);
-  return frag_swap(ua.x, ua.y, ub.x, ub.y);
-}
-__device__ __forceinline__ void from_chunk(u32x4 w, bf16x4& a, bf16x4& b) {
-  const u32x4 v = frag_swap(w[0], w[1], w[2], w[3]);
-  a = __builtin_bit_cast(bf16x4, uint2{v[0], v[1]});
-  b = __builtin_bit_cast(bf16x4, uint2{v[2], v[3]});
-}
+// (to_chunk / from_chunk, the 16-byte pieces of DESIGN.md 4.4.8: mfma_common.hpp)
 // the two halves of a chunk that was loaded as two fragments (the instances that keep the 8-byte form)
 __device__ __forceinline__ u32x4 two_frags(bf16x4 a, bf16x4 b) {
   const uint2 ua = __builtin_bit_cast(uint2, a), ub = __builtin_bit_cast(uint2, b);

@@ -35,6 +35,8 @@
 
 #include <math.h>
 
+#include <type_traits>
+
 namespace pca {
 
 namespace {
@@ -80,6 +82,43 @@ __device__ __forceinline__ float max0(float x) { return __builtin_amdgcn_fmed3f(
 // bits = 2 bits + (z > 0)
 __device__ __forceinline__ uint32_t push_gt0(uint32_t bits, float z) {
   return (bits << 1) | (z > 0.f ? 1u : 0u);
+}
+
+// ---- global accesses: workgroup-uniform base + UNSIGNED 32-bit byte offset of the lane (+ a constant) ----
+// Every tensor this kernel touches has a base that is uniform over the workgroup (kernel argument, set index,
+// half, wave): the base stays in a scalar register pair, the lane contributes one 32-bit VGPR, and hipcc emits
+// `global_* v_off, .., s[base:base+1] offset:imm` - no 64-bit address pair, no v_lshl_add_u64 / v_ashrrev per
+// access.  Offsets that differ by a compile-time constant share the VGPR (`cbytes`, the immediate where it
+// fits).  set128_shape_ok() keeps every tensor below 2^31 bytes.
+// The part of `cbytes` beyond the 12-bit immediate is added to the lane offset (one 32-bit v_add): left in the
+// address, hipcc adds it to (base + lane offset) on the vector ALU as a 64-bit pair.  (NOT to the base behind an
+// empty asm that pins the sum to scalar registers: hipcc's hazard recognizer counts an empty asm as one wait
+// state, and one landed between an MFMA and the first VALU read of its result - the read then came one s_nop
+// early and the <2, 2> instances returned different bits from pass to pass.)
+template <class T>
+__device__ __forceinline__ T* lane_ptr(T* base, uint32_t bytes, int cbytes = 0) {
+  typedef typename std::conditional<std::is_const<T>::value, const char, char>::type byte_t;
+  if (__builtin_constant_p(cbytes) && (cbytes < 0 || cbytes > 4095)) {
+    bytes += (uint32_t)(cbytes & ~4095);
+    cbytes &= 4095;
+  }
+  return reinterpret_cast<T*>(reinterpret_cast<byte_t*>(base) + bytes + cbytes);
+}
+template <class V, class T>
+__device__ __forceinline__ V& lane_ref(T* base, uint32_t bytes, int cbytes = 0) {
+  return *reinterpret_cast<V*>(lane_ptr(base, bytes, cbytes));
+}
+template <class V, class T>
+__device__ __forceinline__ const V& lane_ref(const T* base, uint32_t bytes, int cbytes = 0) {
+  return *reinterpret_cast<const V*>(lane_ptr(base, bytes, cbytes));
+}
+
+// a lane-dependent index at the top of a basic block, as a value the optimiser forms offsets from afresh.
+// (An empty asm like rederive()'s: only right behind a barrier - hipcc's hazard recognizer counts it as a wait
+// state, so it must never stand between an MFMA and the reader of its result.)
+__device__ __forceinline__ int relane(int t) {
+  asm volatile("" : "+v"(t));
+  return t;
 }
 
 // ---- cross-workgroup hand-off (cdna_hip_programming.md Guideline 16, form R1): payload by sc1
@@ -171,31 +210,34 @@ __device__ __forceinline__ void mid_prefetch(const Set128Layer& L, const Ctx& c,
   {
     // (waves 8-15 load the fragments of tile wave - 8 and never use them: under `if (wave < 8)` hipcc
     //  spilled every value of this block right behind its load, each with an s_waitcnt vmcnt(0))
+    // (the tile is the wave's: it goes into the scalar bases; oW: the lane's 16 bytes of row r of a bf16 image)
     const int t = c.wave & 7;
-    P.qp = *reinterpret_cast<const float4*>(L.Qp0 + r * D + 16 * t + 4 * g);
-    P.bv0 = *reinterpret_cast<const float4*>(L.bv0 + 16 * t + 4 * g);
-    P.bo0 = *reinterpret_cast<const float4*>(L.bo0 + 16 * t + 4 * g);
+    const uint32_t oW = 256u * r + 16u * g, o16 = 16u * g;
+    P.qp = lane_ref<float4>(L.Qp0 + 16 * t, 512u * r + 16u * g);
+    P.bv0 = lane_ref<float4>(L.bv0 + 16 * t, o16);
+    P.bo0 = lane_ref<float4>(L.bo0 + 16 * t, o16);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      if (!SMALL) P.wa[ks] = gload8(L.Wv0 + (int64_t)(16 * t + r) * D + 32 * ks + 8 * g);
-      P.wb[ks] = gload8(L.Wo0 + (int64_t)(16 * t + r) * D + 32 * ks + 8 * g);
+      if (!SMALL) P.wa[ks] = lane_ref<bf16x8>(L.Wv0 + 16 * t * D, oW, 64 * ks);
+      P.wb[ks] = lane_ref<bf16x8>(L.Wo0 + 16 * t * D, oW, 64 * ks);
     }
     if (SMALL) {
 #pragma unroll
       for (int e = 0; e < 4; ++e)
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc)
-          P.wvf[e][cc] = cc < dk ? L.Wv0f[(16 * t + 4 * g + e) * dk + cc] : 0.f;
+          P.wvf[e][cc] = cc < dk ? lane_ref<float>(L.Wv0f + 16 * t * dk, 16u * g * dk, 4 * (e * dk + cc)) : 0.f;
     }
   }
   {
     const int tc = c.wave >> 1, which = c.wave & 1;
     const __bf16* W = which ? L.Wv1 : L.Wk1;
     const float* bias = which ? L.bv1 : L.bk1;
+    const uint32_t oW = 256u * r + 16u * g;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) P.wc[ks] = gload8(W + (int64_t)(16 * tc + r) * D + 32 * ks + 8 * g);
-    P.bkv = *reinterpret_cast<const float4*>(bias + 16 * tc + 4 * g);
-    P.bkvc = bias[16 * tc + r];
+    for (int ks = 0; ks < 4; ++ks) P.wc[ks] = lane_ref<bf16x8>(W + 16 * tc * D, oW, 64 * ks);
+    P.bkv = lane_ref<float4>(bias + 16 * tc, 16u * g);
+    P.bkvc = lane_ref<float>(bias + 16 * tc, 4u * r);
   }
 }
 
@@ -223,8 +265,7 @@ __device__ __forceinline__ void mid_stage(const Set128Layer& L, const Ctx& c, co
     }
     put_tile(sA, t, r, g, o);
     if (save)
-      *reinterpret_cast<float4*>(L.O0 + ((int64_t)b * MQ + r) * D + 16 * t + 4 * g) =
-          float4{o[0], o[1], o[2], o[3]};
+      lane_ref<float4>(L.O0 + (int64_t)b * MQ * D + 16 * t, 512u * r + 16u * g) = float4{o[0], o[1], o[2], o[3]};
   }
   lds_barrier();
   if (c.wave < 8) {                                   // ---- B
@@ -237,9 +278,10 @@ __device__ __forceinline__ void mid_stage(const Set128Layer& L, const Ctx& c, co
 #pragma unroll
     for (int e = 0; e < 4; ++e) hq[e] = o[e] + max0(z[e]);
     if (save) {
-      const int64_t off = ((int64_t)b * MQ + r) * D + 16 * t + 4 * g;
-      *reinterpret_cast<float4*>(L.Z0 + off) = float4{z[0], z[1], z[2], z[3]};
-      *reinterpret_cast<float4*>(L.H + off) = float4{hq[0], hq[1], hq[2], hq[3]};
+      const int64_t base = (int64_t)b * MQ * D + 16 * t;
+      const uint32_t off = 512u * r + 16u * g;
+      lane_ref<float4>(L.Z0 + base, off) = float4{z[0], z[1], z[2], z[3]};
+      lane_ref<float4>(L.H + base, off) = float4{hq[0], hq[1], hq[2], hq[3]};
     }
     put_tile(sH, t, r, g, hq);
   }
@@ -265,8 +307,8 @@ __device__ __forceinline__ void mid_stage(const Set128Layer& L, const Ctx& c, co
     if (save) {
       __bf16* PP = which ? L.VpP : L.KpP;
       __bf16* TT = which ? L.Vt : L.Kt;
-      *reinterpret_cast<bf16x4*>(TT + (int64_t)b * D * MQ + o_t) = krp;
-      *reinterpret_cast<bf16x4*>(PP + (int64_t)b * MQ * D + o_p) = frp;
+      lane_ref<bf16x4>(TT + (int64_t)b * D * MQ, 2u * o_t) = krp;
+      lane_ref<bf16x4>(PP + (int64_t)b * MQ * D, 2u * o_p) = frp;
     }
   }
   lds_barrier();
@@ -296,12 +338,12 @@ __device__ __forceinline__ void mab1_phase(const Set128Layer& L, const Ctx& c, c
       for (int e = 0; e < 4; ++e)
 #pragma unroll
         for (int cc = 0; cc < DQ; ++cc)
-          wqs[t][e][SMALL ? cc : 0] = L.WqF[(32 * j + 16 * t + 4 * g + e) * DQ + cc];
+          wqs[t][e][SMALL ? cc : 0] = lane_ref<float>(L.WqF + 32 * j * DQ, 16u * g * DQ, 4 * ((16 * t + e) * DQ + cc));
   }
   f32x4 bqv[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    const float4 q4 = *reinterpret_cast<const float4*>(L.bq1 + 32 * j + 16 * t + 4 * g);
+    const float4 q4 = lane_ref<float4>(L.bq1 + 32 * j, 16u * g, 64 * t);
     bqv[t] = f32x4{q4.x, q4.y, q4.z, q4.w};
   }
   // the head's 16 keys: A operand [key r][k-slots 8 g .. of the head's 32 features] and
@@ -316,6 +358,9 @@ __device__ __forceinline__ void mab1_phase(const Set128Layer& L, const Ctx& c, c
   // set is computed where its phase starts - held from the top they cost 14 registers the kernel does
   // not have (a spilled index reloaded next to a prefetch makes the reload's vmcnt(0) wait for it)
   int oB[KS], oD[2];
+  // saved Qp: the head's 64 bytes of the quad's rows; the lane's chunk of row r
+  __bf16* const qps = (SMALL && DQ != 4) ? nullptr : L.QpS + (c.row0 + c.qn0) * D + 32 * j;
+  const uint32_t oQ = 256u * r + 16u * chunk_of(g);
 #pragma unroll
   for (int s = 0; s < KS; ++s) oB[s] = y_off(r, 4 * s + g);
 #pragma unroll
@@ -346,10 +391,7 @@ __device__ __forceinline__ void mab1_phase(const Set128Layer& L, const Ctx& c, c
         // points only for up to three columns); the same stores as the hidden layer's below
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-            *reinterpret_cast<bf16x4*>(L.QpS + (c.row0 + n0 + 16 * nb + r) * D + 32 * j + 16 * t + 4 * g) =
-                pack4(acc[t][nb]);
+          lane_ref<u32x4>(qps, oQ, (32 * u + 16 * nb) * ROWB) = to_chunk(pack4(acc[0][nb]), pack4(acc[1][nb]));
       }
     } else {
 #pragma unroll
@@ -365,13 +407,11 @@ __device__ __forceinline__ void mab1_phase(const Set128Layer& L, const Ctx& c, c
           acc[0][nb] = mfma32(wa[s][0], bx, acc[0][nb]);
           acc[1][nb] = mfma32(wa[s][1], bx, acc[1][nb]);
         }
-      // saved for the backward: straight from the accumulators (8-byte pieces of 16 rows)
+      // saved for the backward: straight from the accumulators, as the 16-byte chunk chunk_of(g) of the
+      // head's 64 bytes of a row (to_chunk)
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-          *reinterpret_cast<bf16x4*>(L.QpS + (c.row0 + n0 + 16 * nb + r) * D + 32 * j + 16 * t + 4 * g) =
-              pack4(acc[t][nb]);
+        lane_ref<u32x4>(qps, oQ, (32 * u + 16 * nb) * ROWB) = to_chunk(pack4(acc[0][nb]), pack4(acc[1][nb]));
     }
     // attention over the 16 inducing keys, all inside the wave
 #pragma unroll
@@ -407,13 +447,14 @@ __device__ __forceinline__ void mab1_phase(const Set128Layer& L, const Ctx& c, c
   for (int s = 0; s < KS; ++s)
 #pragma unroll
     for (int t = 0; t < 2; ++t)
-      wa[s][t] = gload8(L.WoP + (int64_t)(32 * j + 16 * t + r) * D + 32 * s + 8 * g);
+      wa[s][t] = lane_ref<bf16x8>(L.WoP + 32 * j * D, 256u * r + 16u * g, 2 * (16 * t * D + 32 * s));
   f32x4 bov[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    const float4 o4 = *reinterpret_cast<const float4*>(L.bo1 + 32 * j + 16 * t + 4 * g);
+    const float4 o4 = lane_ref<float4>(L.bo1 + 32 * j, 16u * g, 64 * t);
     bov[t] = f32x4{o4.x, o4.y, o4.z, o4.w};
   }
+  uint8_t* const msk = reinterpret_cast<uint8_t*>(L.mask) + (c.row0 + c.qn0) * 16 + j;
   int oP[KS][2];
 #pragma unroll
   for (int s = 0; s < KS; ++s)
@@ -463,23 +504,37 @@ __device__ __forceinline__ void mab1_phase(const Set128Layer& L, const Ctx& c, c
 #pragma unroll
       for (int t = 0; t < 2; ++t)
         *reinterpret_cast<bf16x4*>(sY + (n0 + 16 * nb) * ROWB + oD[t]) = pack4(y[t]);
-      const int64_t blk = (c.row0 + n0) / 16 + nb;
-      reinterpret_cast<uint8_t*>(L.mask)[(blk * 64 + c.lane) * 4 + j] = (uint8_t)bits;
+      // byte j of word `lane` of the block's 64 mask words (mab1_mask_index<128>: 64 words per 16-row block,
+      // block after block from word 4 row0 on).  (Whole words through an LDS image behind the barrier below
+      // were no faster: DESIGN.md 4.4.1.)
+      lane_ref<uint8_t>(msk, 4u * c.lane, (32 * u + 16 * nb) * 16) = (uint8_t)bits;
     }
   }
   STAMP(stamp0 + 2);
   lds_barrier();                        // Y rows complete (and every head has read the O rows)
   STAMP(stamp0 + 3);
   // saved O and the block's output: coalesced 16-byte pieces of full rows (no output when nothing
-  // after this launch reads it)
-  const bool store_y = L.Y != nullptr;
-  for (int p = c.tid; p < c.NH * 16; p += NT) {
-    const int row = p >> 4, ch = p & 15;
-    *reinterpret_cast<uint4*>(L.OS + (c.row0 + row) * D + ch * 8) =
-        *reinterpret_cast<const uint4*>(sO + y_off(row, ch));
-    if (store_y)
-      *reinterpret_cast<uint4*>(L.Y + (c.row0 + row) * D + ch * 8) =
-          *reinterpret_cast<const uint4*>(sY + y_off(row, ch));
+  // after this launch reads it).  Chunk p = tid + 1024 k is the 16 bytes ch = tid & 15 of row (tid >> 4) + 64 k:
+  // 16 tid + 16384 k bytes from the workgroup's first row, in LDS y_off of k = 0 plus 16384 k.
+  // The branch below opens a basic block: the lane offset is formed again INSIDE it (relane), since hipcc
+  // matches `scalar base + 32-bit offset` only where it sees the 32-bit value in the block of the access.
+  {
+    const int t = c.tid;
+    const uint32_t oT = 16u * t;
+    const int oL = y_off(t >> 4, t & 15);
+    __bf16* const os = L.OS + c.row0 * D;
+#pragma unroll
+    for (int k = 0; k < 2 * UPQ; ++k)                 // NH * 16 = 2048 UPQ chunks
+      lane_ref<uint4>(os, oT, 16384 * k) = *reinterpret_cast<const uint4*>(sO + oL + 16384 * k);
+  }
+  if (L.Y != nullptr) {
+    const int t = relane(c.tid);
+    const uint32_t oT = 16u * t;
+    const int oL = y_off(t >> 4, t & 15);
+    __bf16* const ys = L.Y + c.row0 * D;
+#pragma unroll
+    for (int k = 0; k < 2 * UPQ; ++k)
+      lane_ref<uint4>(ys, oT, 16384 * k) = *reinterpret_cast<const uint4*>(sY + oL + 16384 * k);
   }
   STAMP(stamp0 + 4);
 }
@@ -528,19 +583,20 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
   // everything the first three stages read from memory, requested together
   float pth = 0.f;
   if (tid < 520)
-    pth = __hip_atomic_load((__attribute__((address_space(1))) const float*)(theirs + tid), __ATOMIC_RELAXED,
-                            __HIP_MEMORY_SCOPE_AGENT);
+    pth = __hip_atomic_load((__attribute__((address_space(1))) const float*)lane_ptr(theirs, 4u * tid),
+                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   float4 wv4[4], wo4[4], wc4[2];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
-    wv4[u] = *reinterpret_cast<const float4*>(a.Wv + (int64_t)fA * D + 16 * pA + 4 * u);
-    wo4[u] = *reinterpret_cast<const float4*>(a.Wo + (int64_t)fA * D + 16 * pA + 4 * u);
+    wv4[u] = lane_ref<float4>(a.Wv, 64u * tid, 16 * u);      // (fA D + 16 pA = 16 tid floats)
+    wo4[u] = lane_ref<float4>(a.Wo, 64u * tid, 16 * u);
   }
   const int c3 = tid >> 4, p3 = tid & 15;
 #pragma unroll
   for (int u = 0; u < 2; ++u)
-    wc4[u] = *reinterpret_cast<const float4*>(a.Wc + (int64_t)(c3 < C ? c3 : 0) * D + 8 * p3 + 4 * u);
-  const float qb = a.Qp[fA] + a.bv[fA], bo_f = a.bo[fA], bc3 = a.bc[c3 < C ? c3 : 0];
+    wc4[u] = lane_ref<float4>(a.Wc, 512u * (c3 < C ? c3 : 0) + 32u * p3, 16 * u);
+  const float qb = lane_ref<float>(a.Qp, 4u * fA) + lane_ref<float>(a.bv, 4u * fA), bo_f = lane_ref<float>(a.bo, 4u * fA),
+              bc3 = lane_ref<float>(a.bc, 4u * (c3 < C ? c3 : 0));
   const SoftRow y = soft_row(a.soft, a.labels, b);
   if (wr && a.zero_ptr != nullptr)
     for (int i = b * NT + tid; i < a.zero_n; i += B * NT) a.zero_ptr[i] = 0.f;
@@ -559,10 +615,10 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     const float Lt = f0 * P0[516 + rr] + f1 * P1[516 + rr];
     const float v = (f0 * P0[tid] + f1 * P1[tid]) / Lt;
     sT[tid] = v;
-    if (wr) a.T[(int64_t)b * R * D + tid] = v;
+    if (wr) lane_ref<float>(a.T + (int64_t)b * R * D, 4u * tid) = v;
     if ((tid & 127) == 0) {
       const float lse = M + log2f(Lt);
-      if (wr) a.LSE[(int64_t)b * R + rr] = lse;
+      if (wr) lane_ref<float>(a.LSE + (int64_t)b * R, 4u * rr) = lse;
       sLSE[rr] = lse;
     }
   }
@@ -590,11 +646,11 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     const float z1 = bo_f + dot16(wo4, sOv + 16 * pA);
     if (pA == 0) {
       const float o1 = sOv[fA], hv = o1 + fmaxf(z1, 0.f);
-      const int64_t o = (int64_t)b * D + fA;
+      const int64_t o = (int64_t)b * D;
       if (wr) {
-        a.H[o] = hv;
-        a.Osave[o] = o1;
-        a.Zsave[o] = z1;
+        lane_ref<float>(a.H + o, 4u * fA) = hv;
+        lane_ref<float>(a.Osave + o, 4u * fA) = o1;
+        lane_ref<float>(a.Zsave + o, 4u * fA) = z1;
       }
       sP[fA] = hv;
       sZ[fA] = z1;
@@ -606,10 +662,10 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
 #pragma unroll
   for (int u = 0; u < 8; ++u) {
     const int cc = pB + 8 * u;
-    wcB[u] = a.Wc[(int64_t)(cc < C ? cc : 0) * D + fB];
+    wcB[u] = lane_ref<float>(a.Wc, 512u * (cc < C ? cc : 0) + 4u * fB);
   }
 #pragma unroll
-  for (int u = 0; u < 16; ++u) woB[u] = a.Wo[(int64_t)(pB + 8 * u) * D + fB];
+  for (int u = 0; u < 16; ++u) woB[u] = lane_ref<float>(a.Wo, 512u * pB + 4u * fB, 4096 * u);
   // logits
   {
     float acc = 0.f;
@@ -626,7 +682,7 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     if (c3 < C && p3 == 0) {
       acc += bc3;
       sL[c3] = acc;
-      if (wr) a.logits[(int64_t)b * C + c3] = acc;
+      if (wr) lane_ref<float>(a.logits + (int64_t)b * C, 4u * c3) = acc;
     }
   }
   lds_barrier();
@@ -666,7 +722,7 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     lds_barrier();
     if (tid < C) {
       sL[tid] = g;
-      if (wr) a.dlogits[(int64_t)b * C + tid] = g;
+      if (wr) lane_ref<float>(a.dlogits + (int64_t)b * C, 4u * tid) = g;
     }
     lds_barrier();
   }
@@ -685,11 +741,11 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     float dp = 0.f;
 #pragma unroll
     for (int p = 0; p < 8; ++p) dp += part[p * D + tid];
-    if (wr) a.dP[(int64_t)b * D + tid] = dp;
+    if (wr) lane_ref<float>(a.dP + (int64_t)b * D, 4u * tid) = dp;
     sdP[tid] = dp;
     const float v = sZ[tid] > 0.f ? dp : 0.f;          // dZ = dP . [Z > 0]
     sdZ[tid] = v;
-    if (wr) a.dZ[(int64_t)b * D + tid] = v;
+    if (wr) lane_ref<float>(a.dZ + (int64_t)b * D, 4u * tid) = v;
   }
   lds_barrier();
   // dO = dP + dZ Wo
@@ -697,7 +753,7 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
   {
     const int j = (tid >> 7) & 3, hlf = tid >> 9;      // stage after this one: (column, head, half of the head)
 #pragma unroll
-    for (int u = 0; u < 16; ++u) wvB[u] = a.Wv[(int64_t)(j * DH + 16 * hlf + u) * D + fB];
+    for (int u = 0; u < 16; ++u) wvB[u] = lane_ref<float>(a.Wv, 512u * (j * DH + 16 * hlf) + 4u * fB, 512 * u);
     float acc = 0.f;
 #pragma unroll
     for (int u = 0; u < 16; ++u) acc = fmaf(sdZ[pB + 8 * u], woB[u], acc);
@@ -709,7 +765,7 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
 #pragma unroll
     for (int p = 0; p < 8; ++p) v += part[p * D + tid];
     sdO[tid] = v;
-    if (wr) a.dO[(int64_t)b * D + tid] = v;
+    if (wr) lane_ref<float>(a.dO + (int64_t)b * D, 4u * tid) = v;
   }
   lds_barrier();
   // dT_h = dO_h Wv_h ; Delta = rowdot(dT, T) ; the images k_mab0_bwd reads (bw: the tail's, in LDS)
@@ -725,7 +781,7 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
     const int j = tid >> 7, f = tid & 127;
     const float acc = part[j * D + f] + part[(4 + j) * D + f];
     const float tv = sT[j * D + f];
-    if (wr) a.Th[((int64_t)j * B + b) * D + f] = tv;
+    if (wr) lane_ref<float>(a.Th + (int64_t)b * D, 512u * j * B + 4u * f) = tv;
     if (bw != nullptr) {
       const __bf16 v = (__bf16)acc;
       *reinterpret_cast<__bf16*>(bw + PmaBwdLds::DT + y_off(j, f >> 3) + 2 * (f & 7)) = v;
@@ -810,7 +866,7 @@ __device__ __forceinline__ void pma_bwd_tail(const __bf16* Gpma, __bf16* dY2, fl
   // G' image (rows 4 .. 15 of Gpma are zero), its transpose, the zero rows of the dT image
   if (tid < 256) {
     const int row = tid >> 4, ch = tid & 15;
-    const bf16x8 v = gload8(Gpma + (int64_t)row * D + ch * 8);
+    const bf16x8 v = lane_ref<bf16x8>(Gpma, 16u * tid);          // (row D + 8 ch = 8 tid elements)
     *reinterpret_cast<bf16x8*>(bw + PmaBwdLds::G + y_off(row, ch)) = v;
     if (row < 4) {
 #pragma unroll
@@ -912,17 +968,18 @@ __device__ __forceinline__ void pma_bwd_tail(const __bf16* Gpma, __bf16* dY2, fl
       }
     }
     // (the tile's rows were last read in stage 2, before the barrier)
+    __bf16* const dy = dY2 + (c.row0 + 32 * c.wave) * D;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int cidx = lane + 64 * k, row = cidx >> 4, ch = cidx & 15;
-      *reinterpret_cast<uint4*>(dY2 + (c.row0 + 32 * c.wave + row) * D + ch * 8) =
-          *reinterpret_cast<const uint4*>(img + y_off(row, ch));
+      lane_ref<uint4>(dy, 16u * lane, 1024 * k) = *reinterpret_cast<const uint4*>(img + y_off(row, ch));
     }
   } else if (tid >= 512) {
     const int i = tid - 512;
     for (int sp = 0; sp < sph; ++sp) {
       const float* rs = red + sp * 4 * 512;
-      slabs[((int64_t)c.b * S + c.half * sph + sp) * 512 + i] = rs[i] + rs[512 + i] + rs[1024 + i] + rs[1536 + i];
+      lane_ref<float>(slabs + ((int64_t)c.b * S + c.half * sph + sp) * 512, 4u * i) =
+          rs[i] + rs[512 + i] + rs[1024 + i] + rs[1536 + i];
     }
   }
 }
@@ -932,7 +989,7 @@ __device__ __forceinline__ void mab1_load_wq(const Set128Layer& L, const Ctx& c,
   for (int s = 0; s < 4; ++s)
 #pragma unroll
     for (int t = 0; t < 2; ++t)
-      wa[s][t] = gload8(L.WqB + (int64_t)(32 * c.j + 16 * t + c.r) * D + 32 * s + 8 * c.g);
+      wa[s][t] = lane_ref<bf16x8>(L.WqB + 32 * c.j * D, 256u * c.r + 16u * c.g, 2 * (16 * t * D + 32 * s));
 }
 
 typedef __attribute__((address_space(4))) const Set128FwdArgs karg_t;
@@ -1022,12 +1079,12 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
       const int i = tid + NT * it;
       const int pt = i >> 2, cc = i & 3;
       const int ptc = pt < N ? pt : N - 1, ccc = cc < dk ? cc : 0;      // unconditional, clamped
-      const float v = ap->X[((int64_t)b * N + ptc) * dk + ccc];
+      const float v = lane_ref<float>(ap->X + (int64_t)b * N * dk, 4u * (ptc * dk + ccc));
       xs[it] = cc < dk ? v : 0.f;
     }
     float gk[DIN];
 #pragma unroll
-    for (int cc = 0; cc < DIN; ++cc) gk[cc] = L.Gf[lane * dk + cc];
+    for (int cc = 0; cc < DIN; ++cc) gk[cc] = lane_ref<float>(L.Gf, 4u * dk * lane, 4 * cc);
     // two images of the points: [point][4] for the layer-1 projection of the many-queries block, and
     // [pair of points][component][2] - the operand pairs of the packed-fp32 loop below (v_pk_fma_f32 /
     // v_pk_mul_f32 work on two points per issue slot, as in k_mab0_attn_small)
@@ -1113,8 +1170,8 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
       for (int cc = 0; cc < 4; ++cc) tt[cc] *= inv;
       *reinterpret_cast<float4*>(sTf + lane * 4) = float4{tt[0], tt[1], tt[2], tt[3]};
       if (c.half == 0) {
-        for (int cc = 0; cc < dk; ++cc) L.T[((int64_t)b * 64 + lane) * dk + cc] = tt[cc];
-        L.LSE[(int64_t)b * 64 + lane] = M + log2f(Ls);
+        for (int cc = 0; cc < dk; ++cc) lane_ref<float>(L.T + (int64_t)b * 64 * dk, 4u * dk * lane, 4 * cc) = tt[cc];
+        lane_ref<float>(L.LSE + (int64_t)b * 64, 4u * lane) = M + log2f(Ls);
       }
     }
     lds_barrier();
@@ -1139,7 +1196,7 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
     const int tid = c.tid, lane = c.lane, r = c.r, g = c.g;
     bf16x8 gf[4];                     // this head's G rows: B operand of the score MFMAs
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) gf[ks] = gload8(L.Gb + (int64_t)(16 * c.j + r) * D + 32 * ks + 8 * g);
+    for (int ks = 0; ks < 4; ++ks) gf[ks] = lane_ref<bf16x8>(L.Gb + 16 * c.j * D, 256u * r + 16u * g, 64 * ks);
     float* myAl = sAl + c.wave * 32;
     float mrow = -INFINITY, lrow = 0.f;
     f32x4 T[8];
@@ -1310,10 +1367,10 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
 #pragma unroll
       for (int k = 0; k < 8; ++k) { t[k] *= il.x; v[k] = (__bf16)t[k]; }
       if (c.half == 0) {
-        float4* tg = reinterpret_cast<float4*>(L.T + ((int64_t)b * 64 + row) * D + ch * 8);
-        tg[0] = float4{t[0], t[1], t[2], t[3]};
-        tg[1] = float4{t[4], t[5], t[6], t[7]};
-        if (ch == 0) L.LSE[(int64_t)b * 64 + row] = il.y;
+        float* const tg = L.T + (int64_t)b * 64 * D;             // (row D + 8 ch = 8 tid floats)
+        lane_ref<float4>(tg, 32u * tid) = float4{t[0], t[1], t[2], t[3]};
+        lane_ref<float4>(tg, 32u * tid, 16) = float4{t[4], t[5], t[6], t[7]};
+        if (ch == 0) lane_ref<float>(L.LSE + (int64_t)b * 64, 4u * row) = il.y;
       }
       *reinterpret_cast<bf16x8*>(sT + swz(row, ch, ROWB)) = v;
     }
@@ -1352,7 +1409,7 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
           s[pb] = mfma32(*reinterpret_cast<const bf16x8*>(img + y_off(16 * pb + r, 4 * ks + g)),
-                         gload8(ap->Gpma + (int64_t)r * D + 32 * ks + 8 * g), s[pb]);
+                         lane_ref<bf16x8>(ap->Gpma, 256u * r + 16u * g, 64 * ks), s[pb]);
       }
       if (LEN) {
         const int left = len - p0 - 4 * g;      // rows of s = points 16 pb + 4 g + e
@@ -1446,7 +1503,7 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
       // hand-off 3 (R1 again: 4-byte write-through stores, drained, barrier, one flag): half 1 is done,
       // or (pma_bwd) both halves publish and both go on
       if (tid < 520)
-        __hip_atomic_store((__attribute__((address_space(1))) float*)(exMine + tid), sPm[tid],
+        __hip_atomic_store((__attribute__((address_space(1))) float*)lane_ptr(exMine, 4u * tid), sPm[tid],
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       drain_vm();
       lds_barrier();
@@ -1488,18 +1545,30 @@ size_t set128_fwd_ws_bytes(int B) {
          align256((size_t)B * 2 * 528 * sizeof(float));
 }
 
-bool set128_shape_ok(int B, int N, int din, int d, int h, int m, int k) {
+// the shape rule on `cus` compute units (pca_debug_set128_shape_ok: the host tests)
+static bool shape_ok_on(int B, int N, int din, int d, int h, int m, int k, int cus) {
   if (!(d == 128 && h == 4 && m == 16 && k == 1 && din >= 1 && din <= 4 && (N == 256 || N == 512)))
     return false;
+  // the kernel addresses every tensor as a scalar base plus an UNSIGNED 32-bit byte offset of the lane
+  // (lane_ptr): the largest tensor of a launch, a [B N, 128] bf16 activation, stays below 2^31 bytes
+  if ((int64_t)B * N * 128 * 2 >= (int64_t)1 << 31) return false;
   // the two workgroups of a set wait for each other: every pair must be resident at once - one
   // workgroup per CU (160 KiB of LDS), workgroup ids dealt in order
+  return 16 * cdiv((int64_t)B, 8) <= cus;
+}
+
+extern "C" int pca_debug_set128_shape_ok(int B, int N, int din, int d, int h, int m, int k, int cus) {
+  return shape_ok_on(B, N, din, d, h, m, k, cus) ? 1 : 0;
+}
+
+bool set128_shape_ok(int B, int N, int din, int d, int h, int m, int k) {
   static const int cus = [] {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
     return n;
   }();
-  return 16 * (int)cdiv(B, 8) <= cus;
+  return shape_ok_on(B, N, din, d, h, m, k, cus);
 }
 
 // the eight (din, N / 256) instantiations of one LEN: 160 KiB of LDS allowed once, the one of `key` launched

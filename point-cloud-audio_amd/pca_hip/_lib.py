@@ -250,6 +250,7 @@ DEBUG_SIGNATURES = {
     "pca_debug_prep_images": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int),
                                         C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, c_vp]),
     "pca_debug_merge_factor": (C.c_float, [C.c_float, C.c_float, C.c_int]),
+    "pca_debug_set128_shape_ok": (C.c_int, [C.c_int] * 8),
 }
 
 _lib = None
