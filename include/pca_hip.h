@@ -344,6 +344,50 @@ int pca_frame_points(const float* waves, const int64_t* wave_off, const int64_t*
                      const float* farr, const float* tarr, const PcaFrameAug* aug, float* out,
                      int64_t* labels_out, int32_t* meta_out, void* stream);
 
+/* One resolution of a multi-resolution point set (pca_frame_points_multires). */
+#define PCA_FRAME_MAX_LEVELS 4
+typedef struct PcaFrameLevel {
+  int32_t n_fft, hop, n_bins, Nt;   /* as pca_frame_points: n_fft a power of two in [64, 4096], hop > 0,
+                                       1 <= n_bins <= n_fft/2 + 1, Nt >= 1 */
+  int32_t offset;                   /* centre of this level's frame 0 relative to the set's anchor, samples,
+                                       |offset| <= 2^30 */
+  const float* farr;                /* device float[n_bins] */
+  const float* tarr;                /* device float[Nt], or NULL in EVERY level (2-D rows) */
+  const int32_t* win_lengths;       /* device int32[aug->n_win]: this level's window for each window index */
+} PcaFrameLevel;
+
+/* Point sets that hold several STFT resolutions at once, framed from the resident waveforms in ONE launch
+ * replaces: nothing - no reference counterpart (Code/pceval.py:55-105 varies the analysis length one at a
+ *           time); what a caller otherwise builds from one pca_frame_points per level plus a concatenation.
+ * waves / wave_off / set_off / n_clips / max_len / min_len / clip_labels / idx / B: as pca_frame_points;
+ * set_off counts the sets each clip yields at `span` samples a set (the datasets use L_c / span).
+ * Batch slot b, set i = idx[b] (clamped) = set s of clip c by the same binary search.  ONE stream per slot,
+ * (seed, draw + draw_dev[0], b, i), with pca_frame_points' draw numbers: 0 shift delta, 1 gain g, 2 window
+ * index wi.  All levels of a slot share c, delta, g and wi; level r windows with
+ * clamp(levels[r].win_lengths[wi], 1, n_fft_r).  aug->win_lengths is ignored and may be NULL; aug->n_win >= 1
+ * is the length of every level's array.
+ * The set's anchor is first = s * span + delta; frame j < Nt_r of level r has its centre at
+ * clamp(first + offset_r + j * hop_r, 0, L_c) and is pca_frame_points' transform at n_fft_r with norm n_fft_r
+ * (norm_mode 0) or the level's window (1): the same frame gives the same bits.
+ * out[B, N, din], N = sum_r Nt_r * n_bins_r <= 16384: the levels lie in the caller's order, level r from
+ * point P_r = sum_{q<r} Nt_q * n_bins_q; point P_r + j * n_bins_r + f = (farr_r[f], tarr_r[j], value), or
+ * (farr_r[f], value) with din = 2 when every tarr is NULL.  labels_out as pca_frame_points.
+ * meta_out (nullable) int32 [B, 8] = (c, clamped centre of level 0's frame 0, level 0's window, bits of the
+ * fp32 g, delta, wi, 0, 0): the first four are pca_frame_points' columns when level 0 is a plain configuration.
+ * One launch, grid (sum_r Nt_r, B), 256 threads, 24 B * max_r n_fft_r of LDS per workgroup; a workgroup finds
+ * its (r, j) in a table of at most 4 entries passed by value, in which the level with the largest n_fft has
+ * the lowest block indices (the output layout does not depend on it).  No atomics: the same arguments give
+ * the same bits.
+ * PCA_EINVAL (message "frame_points_multires: ...") before any HIP call for: a null pointer; n_levels outside
+ * [1, 4]; per level n_fft, hop, n_bins, Nt by pca_frame_points' rules, |offset| > 2^30, a NULL farr or
+ * win_lengths; tarr set in some levels only; N > 16384; span outside (0, 2^30]; min_len <= max_r n_fft_r / 2;
+ * and pca_frame_points' rules for max_len, jitter, gain_db, n_win, norm_mode, B, clip_labels / labels_out. */
+int pca_frame_points_multires(const float* waves, const int64_t* wave_off, const int64_t* set_off,
+                              int n_clips, int64_t max_len, int64_t min_len, const int64_t* clip_labels,
+                              const int64_t* idx, int B, const PcaFrameLevel* levels, int n_levels,
+                              int64_t span, const PcaFrameAug* aug, float* out, int64_t* labels_out,
+                              int32_t* meta_out, void* stream);
+
 /* Which points of a framed batch move to where their energy lies, and how far (pca_frame_points_reassigned). */
 typedef struct PcaReassignSpec {
   int32_t axes;       /* bit 0: frequency, bit 1: time; 1..3.  Bit 1 needs tarr and Nt >= 2 */

@@ -24,7 +24,8 @@ import pca_hip
 __all__ = ["ESC_baseline", "ESC_pc", "ESC_pc_ss", "ESC_baseline_temporal",
            "ESC_baseline_temporal_maxK", "ESC_pc_temp", "ESC_pc_temp_maxKSS",
            "ESC_pc_temp_randKSS", "ESC_pc_temp_importancerandKSS", "ESC_wave_pc",
-           "ESC_wave_pc_temp", "PeakPoints", "DeviceBatchLoader"]
+           "ESC_wave_pc_temp", "ESC_wave_pc_multires", "multires_layout", "wave_span_offsets",
+           "PeakPoints", "DeviceBatchLoader"]
 
 
 def _dev(device) -> torch.device:
@@ -755,6 +756,214 @@ class ESC_wave_pc_temp(ESC_wave_pc):
         self._setup_reassign(reassign)
 
 
+def wave_span_offsets(lengths, span: int) -> list:
+    """Prefix sum of the sets each clip yields when a set spans ``span`` samples: L // span whole spans,
+    the short tail dropped."""
+    off = [0]
+    for n in lengths:
+        off.append(off[-1] + int(n) // int(span))
+    return off
+
+
+MULTIRES_MAX_LEVELS, MULTIRES_MAX_POINTS = 4, 16384
+_LEVEL_KEYS = ("n_fft", "hop", "Ntemp", "drop_nyquist", "offset", "win_lengths")
+
+
+def multires_layout(fs, levels, span, time_axis: bool = True) -> dict:
+    """Host-side geometry of a multi-resolution point set (``ESC_wave_pc_multires``), checked by the rules
+    of pca_frame_points_multires (``ValueError``).
+
+    ``levels``: 1 to 4 dicts of ``n_fft`` (a power of two in [64, 4096]), ``hop`` (default n_fft // 2),
+    ``Ntemp`` (frames per set; default span // hop, which must be >= 1), ``drop_nyquist`` (default True),
+    ``offset`` (samples from the set's anchor to the centre of the level's frame 0; default 0) and
+    ``win_lengths`` (default (n_fft,); each in [1, n_fft], the same count in every level; the first entry is
+    the nominal one).  ``span``: samples per set, in (0, 2^30].
+    Returns lists with one entry per level - ``n_fft``, ``hop``, ``Ntemp``, ``offset``, ``win_lengths``,
+    ``F`` (bins), ``farr`` = linspace(0, fs / 2, F) / fs as ``ESC_wave_pc`` builds it, ``tarr`` (None without
+    ``time_axis``, which requires Ntemp == 1 everywhere) and ``point_off`` (the level's first point inside a
+    set) - and ``N``, the points per set (at most 16384).
+    ``tarr[j] = (offset + j * hop) / fs`` is the TRUE time of frame j in seconds from the set's anchor.  It is
+    not the reference's linspace(0, hop / fs * Ntemp, Ntemp) (Code/settransformertemp.py:52), which stretches
+    the spacing by Ntemp / (Ntemp - 1) and would put levels of different Ntemp on different clocks."""
+    levels = list(levels)
+    span = int(span)
+    if not 1 <= len(levels) <= MULTIRES_MAX_LEVELS:
+        raise ValueError(f"multires: {len(levels)} levels (1 .. {MULTIRES_MAX_LEVELS})")
+    if not 0 < span <= 1 << 30:
+        raise ValueError(f"multires: span {span} outside (0, 2^30]")
+    out = {k: [] for k in ("n_fft", "hop", "Ntemp", "offset", "win_lengths", "F", "farr", "tarr",
+                           "point_off")}
+    N = 0
+    for r, lv in enumerate(levels):
+        unknown = set(lv) - set(_LEVEL_KEYS)
+        if unknown or "n_fft" not in lv:
+            raise ValueError(f"multires level {r}: needs n_fft, knows {_LEVEL_KEYS}, got {sorted(lv)}")
+        n_fft = int(lv["n_fft"])
+        if not (64 <= n_fft <= 4096 and n_fft & (n_fft - 1) == 0):
+            raise ValueError(f"multires level {r}: n_fft {n_fft} must be a power of two in [64, 4096]")
+        hop = n_fft // 2 if lv.get("hop") is None else int(lv["hop"])
+        if hop < 1:
+            raise ValueError(f"multires level {r}: hop {hop}")
+        ntemp = span // hop if lv.get("Ntemp") is None else int(lv["Ntemp"])
+        if ntemp < 1:
+            raise ValueError(f"multires level {r}: Ntemp {ntemp} (span {span}, hop {hop})")
+        if not time_axis and ntemp != 1:
+            raise ValueError(f"multires level {r}: time_axis=False needs Ntemp == 1, got {ntemp}")
+        offset = int(lv.get("offset", 0))
+        if abs(offset) > 1 << 30:
+            raise ValueError(f"multires level {r}: offset {offset} outside [-2^30, 2^30]")
+        wins = (n_fft,) if lv.get("win_lengths") is None else tuple(int(w) for w in lv["win_lengths"])
+        if not wins or not all(1 <= w <= n_fft for w in wins):
+            raise ValueError(f"multires level {r}: win_lengths {wins}: each in [1, n_fft = {n_fft}]")
+        if out["win_lengths"] and len(wins) != len(out["win_lengths"][0]):
+            raise ValueError(f"multires level {r}: {len(wins)} win_lengths, level 0 has "
+                             f"{len(out['win_lengths'][0])} (one window index serves every level)")
+        F = n_fft // 2 if lv.get("drop_nyquist", True) else n_fft // 2 + 1
+        for k, v in (("n_fft", n_fft), ("hop", hop), ("Ntemp", ntemp), ("offset", offset),
+                     ("win_lengths", wins), ("F", F), ("farr", np.linspace(0, fs / 2, F) / fs),
+                     ("tarr", (offset + np.arange(ntemp) * hop) / fs if time_axis else None),
+                     ("point_off", N)):
+            out[k].append(v)
+        N += ntemp * F
+    if N > MULTIRES_MAX_POINTS:
+        raise ValueError(f"multires: {N} points per set (max {MULTIRES_MAX_POINTS})")
+    out["N"] = N
+    return out
+
+
+class ESC_wave_pc_multires(Dataset):
+    """Point sets that hold SEVERAL STFT resolutions at once, framed from the resident waveforms per batch:
+    long-window points sharp in frequency and short-window points sharp in time in one (f, t, value) set.
+    No reference counterpart (Code/pceval.py:55-105 varies the analysis length one at a time); for a Set
+    Transformer it is just a longer set.  One pca_frame_points_multires launch per batch.
+
+    Item idx = set idx of the corpus: clip after clip, L_c // span sets each (``wave_span_offsets``); set s
+    of a clip has its anchor at sample s * span.  ``levels`` and the layout of a set: ``multires_layout`` -
+    the levels' rows lie back to back in the order given, float32 [N, 3] = (farr_r[f], tarr_r[j], value),
+    point ``point_off[r] + j * F_r + f``, with tarr in seconds from the anchor on one clock for all levels;
+    ``time_axis=False``: [N, 2] rows (farr_r[f], value), one frame per level.
+    ``jitter`` / ``gain_db`` / ``norm`` / ``seed`` as ``ESC_wave_pc``; a batch slot draws one shift, one gain
+    and one window INDEX, which every level looks up in its own ``win_lengths``.  Speed change, background
+    mix, soft targets, masks and reassignment live in other launches and are not offered here;
+    ``PeakPoints`` refuses this dataset (it reads one F x Nt grid).
+
+    ``plain(win_index=0)``: the deterministic view (what the ``Evaluator`` takes); ``with_levels(indices)``:
+    a view that keeps only those levels - same span, sets and draws, so a level's rows in the view are its
+    rows in the full set.  Views share the resident tensors."""
+
+    batch_seq = None        # augmentations are drawn per call: the Trainer uploads indices per step
+    variable_length = False
+    soft_targets = False
+
+    def __init__(self, clips, y, fs, levels, span, jitter=0, gain_db=0.0, norm="n_fft", seed=0,
+                 device=None, time_axis=True):
+        if norm not in ("n_fft", "win"):
+            raise ValueError(f"norm is 'n_fft' or 'win', got {norm!r}")
+        self.fs, self.span, self.time_axis = fs, int(span), bool(time_axis)
+        self.layout = multires_layout(fs, levels, span, self.time_axis)
+        self._level_ids = tuple(range(len(self.layout["n_fft"])))       # positions in the resident store
+        self.clips, self.clip_labels = list(clips), np.asarray(y).astype(np.int64)
+        assert len(self.clips) == len(self.clip_labels) > 0
+        self.jitter, self.gain_db = int(jitter), float(gain_db)
+        self.norm, self.seed = norm, int(seed)
+        self._draw = 0
+        self._device = device
+        self._store = {}                  # the resident tensors, shared between views
+        self.lengths = [int(c.shape[0]) for c in self.clips]
+        self._max_len, self._min_len = max(self.lengths), min(self.lengths)
+        if self._min_len <= max(self.layout["n_fft"]) // 2:
+            raise ValueError(f"multires: the shortest clip ({self._min_len} samples) is no longer than "
+                             f"n_fft / 2 of the largest level ({max(self.layout['n_fft']) // 2})")
+        self.wave_off = [0] + list(np.cumsum(self.lengths))
+        self.set_off = wave_span_offsets(self.lengths, self.span)
+        self.labels = np.repeat(self.clip_labels, np.diff(self.set_off))   # label of every set
+
+    def __len__(self):
+        return self.set_off[-1]
+
+    @property
+    def num_points(self) -> int:
+        return self.layout["N"]
+
+    @property
+    def stochastic(self) -> bool:
+        """True when any augmentation is on: every call must then draw anew, so a caller that captures
+        ``batch`` into a hipGraph passes ``draw_dev``."""
+        return self.jitter > 0 or self.gain_db > 0.0 or len(self.layout["win_lengths"][0]) > 1
+
+    def plain(self, win_index: int = 0):
+        """A view on the same resident waveforms with every augmentation off: deterministic, the anchors
+        on the regular grid, every level at its window number ``win_index`` (0: the nominal one)."""
+        wins = self.layout["win_lengths"]
+        if not 0 <= int(win_index) < len(wins[0]):
+            raise ValueError(f"win_index {win_index} outside [0, {len(wins[0])})")
+        v = copy.copy(self)
+        v.jitter, v.gain_db = 0, 0.0
+        v.layout = dict(self.layout, win_lengths=[(w[int(win_index)],) for w in wins])
+        v._draw = 0
+        return v
+
+    def with_levels(self, indices):
+        """A view on the same resident waveforms that keeps only the levels ``indices`` (positions in this
+        dataset's levels, in the order given): the same span, sets, labels and draws."""
+        indices = [int(k) for k in indices]
+        n = len(self._level_ids)
+        if not indices or len(set(indices)) != len(indices) or not all(0 <= k < n for k in indices):
+            raise ValueError(f"with_levels {indices}: distinct positions in [0, {n})")
+        v = copy.copy(self)
+        v._level_ids = tuple(self._level_ids[k] for k in indices)
+        lay = {k: [val[i] for i in indices] for k, val in self.layout.items() if k != "N"}
+        ends = np.cumsum([t * f for t, f in zip(lay["Ntemp"], lay["F"])]).tolist()
+        lay["point_off"], lay["N"] = [0] + ends[:-1], ends[-1]
+        v.layout = lay
+        return v
+
+    def _resident(self):
+        """(waves, wave_off, set_off, clip_labels) on the device, uploaded once for all views."""
+        if "res" not in self._store:
+            dev = _dev(self._device)
+            i64 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.int64)).to(dev)   # noqa: E731
+            waves = torch.cat([torch.as_tensor(c).to(dev, torch.float32).reshape(-1)
+                               for c in self.clips])
+            self._store["res"] = (waves, i64(self.wave_off), i64(self.set_off), i64(self.clip_labels))
+            self._store["axes"], self._store["win"] = {}, {}
+        return self._store["res"]
+
+    def _levels_dev(self, dev):
+        """The ``pca_hip.FrameLevel`` of every level of this view; axes and window tables are uploaded on
+        first use and kept in the shared store (a level's axes do not depend on the view)."""
+        f32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64)).float().to(dev)   # noqa: E731
+        lay, out = self.layout, []
+        for r, k in enumerate(self._level_ids):
+            if k not in self._store["axes"]:
+                self._store["axes"][k] = (f32(lay["farr"][r]),
+                                          None if lay["tarr"][r] is None else f32(lay["tarr"][r]))
+            wkey = (k, lay["win_lengths"][r])
+            if wkey not in self._store["win"]:
+                self._store["win"][wkey] = torch.tensor(lay["win_lengths"][r], dtype=torch.int32, device=dev)
+            f, t = self._store["axes"][k]
+            out.append(pca_hip.FrameLevel(lay["n_fft"][r], lay["hop"][r], lay["F"][r], lay["Ntemp"][r], f, t,
+                                          self._store["win"][wkey], lay["offset"][r]))
+        return out
+
+    def batch(self, idx: torch.Tensor, out=None, labels_out=None, draw_dev=None, want_meta: bool = False):
+        """idx int64[B] on the device -> (points [B, num_points, 2 or 3] float32, labels int64[B][, meta
+        int32 [B, 8] = (clip, centre sample of level 0's frame 0, level 0's window length, bits of the gain,
+        shift, window index, 0, 0)]): one pca_frame_points_multires launch."""
+        waves, woff, soff, lab = self._resident()
+        self._draw += 1
+        return pca_hip.frame_points_multires(
+            waves, woff, soff, idx, self._levels_dev(waves.device), self.span, max_len=self._max_len,
+            min_len=self._min_len, clip_labels=lab, jitter=self.jitter, gain_db=self.gain_db,
+            norm_mode=pca_hip.NORM_WIN if self.norm == "win" else pca_hip.NORM_NFFT, seed=self.seed,
+            draw=self._draw, out=out, labels_out=labels_out, draw_dev=draw_dev, want_meta=want_meta)
+
+    def __getitem__(self, idx):
+        waves = self._resident()[0]
+        pts, lbl = self.batch(torch.tensor([int(idx)], dtype=torch.int64, device=waves.device))
+        return pts[0].cpu(), lbl[0].cpu()
+
+
 class PeakPoints(Dataset):
     """The K strongest spectral peaks of every set of a dense point-set dataset, refined off the grid: a view
     over ``ESC_pc``, ``ESC_pc_temp`` (its variable-length chunks included: their lengths are whole frames),
@@ -772,6 +981,10 @@ class PeakPoints(Dataset):
 
     def __init__(self, inner, K, radius_f=1, radius_t=0, rel_floor=float("inf"), abs_floor=float("-inf"),
                  refine=True):
+        if isinstance(inner, ESC_wave_pc_multires):
+            raise ValueError("PeakPoints: a multi-resolution set is several F x Nt grids back to back, and "
+                             "peak picking reads its neighbours from one; pick peaks per level "
+                             "(ESC_wave_pc / ESC_wave_pc_temp) instead")
         if isinstance(inner, ESC_wave_pc):
             self.F, self.Nt, self.din = inner.F, inner._ntemp, 2 if inner.tarr is None else 3
             if inner.variable_length:

@@ -35,6 +35,8 @@ The other set-model experiments run here at batch scale too:
   - a fourth curve;
 * ``reassign_sweep``: sets whose points slide from the grid to their reassigned time-frequency coordinates
   (``pca_hip.frame_points_reassigned``), one pass per strength; no reference counterpart;
+* ``multires_sweep``: sets that hold several STFT resolutions at once (``pca_hip.frame_points_multires``),
+  scored with all levels and with subsets of them, one pass per subset; no reference counterpart;
 * ``reframe_sweep_temporal``: the (Fs, N) re-framing of the 3ST, Code/pc_temp3d_eval.py:56-107.
 * ``clip_accuracy``: the clip-level scores the datasets' literature reports (majority vote and mean
   log-probability over a clip's frames or chunks, ``pca_hip.clip_aggregate``) next to the frame score;
@@ -74,13 +76,14 @@ import torch
 import ctypes as C
 
 import pca_hip
-from dataset import ESC_pc, ESC_pc_temp, ESC_wave_pc, ESC_wave_pc_temp
+from dataset import ESC_pc, ESC_pc_temp, ESC_wave_pc, ESC_wave_pc_multires, ESC_wave_pc_temp
 from pca_hip import _lib
 from pca_hip.baseline import SEL_ALL, BaselineEngine
 from pca_hip.trainer import STEngine, st_config
 
 __all__ = ["reframe_sweep", "framewise_dataset", "default_list_K", "sweep_draw", "subsample_sweep",
-           "importance_sweep", "attention_sweep", "peak_sweep", "most_peaks", "reassign_sweep", "chunk_plan",
+           "importance_sweep", "attention_sweep", "peak_sweep", "most_peaks", "reassign_sweep", "multires_sweep",
+           "default_level_subsets", "chunk_plan",
            "temporal_axes", "temporal_dataset", "reframe_sweep_temporal", "baseline_subsample_sweep", "baseline_frames",
            "baseline_chunks", "baseline_reframe_sweep", "baseline_reframe_sweep_temporal",
            "trim_dB_of", "trim_clips", "clip_accuracy"]
@@ -643,6 +646,50 @@ def reassign_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], 
     shown = {k: (v if isinstance(v, str) or math.isfinite(v) else str(v))
              for k, v in ds.reassign.items() if k != "strength"}
     out = {"data": data, "list_strength": list_strength, "spec": shown}
+    _write_json(out, json_file)
+    return out
+
+
+def default_level_subsets(n_levels: int) -> List[tuple]:
+    """Every single level, then every set with one level left out (without repeats, without the full set)."""
+    singles = [(k,) for k in range(n_levels)]
+    rest = [tuple(q for q in range(n_levels) if q != k) for k in range(n_levels)]
+    return singles + [s for s in rest if s and s not in singles and len(s) < n_levels]
+
+
+@torch.no_grad()
+def multires_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float, levels, span: int,
+                   subsets: Optional[Iterable[Iterable[int]]] = None, batch_size: int = 8,
+                   json_file: Optional[str] = None, mode: int = _lib.MODE_F32,
+                   sets_per_call: Optional[int] = None, **dataset_kw) -> Dict:
+    """Accuracy of ``model`` over multi-resolution point sets (``ESC_wave_pc_multires``) when it sees all
+    levels and when it sees each of ``subsets`` of them (default: ``default_level_subsets``): which
+    resolutions a model trained on the mixed set leans on.  **No reference counterpart**: Code/pceval.py:55-105
+    varies the analysis length one at a time.
+
+    ``clips`` / ``labels`` / ``fs`` / ``levels`` / ``span`` and ``dataset_kw`` (norm, time_axis, ...) as the
+    dataset takes them.  The corpus is resident once; every entry is one ``_dataset_accuracy`` pass over a
+    ``with_levels`` view of it, one host read each.
+
+    Returns (and, with ``json_file``, writes) ``{"data": {"0+1": [acc, 0], "0": [acc, 0], ...},
+    "list_subsets": [[0, 1], [0], ...], "levels": [...], "span": span}``: the key joins a subset's level
+    positions with "+", the full set first."""
+    ds = ESC_wave_pc_multires(clips, labels, fs, levels, span, device=_model_device(model),
+                              **dataset_kw)
+    n = len(ds.layout["n_fft"])
+    full = tuple(range(n))
+    subsets = default_level_subsets(n) if subsets is None else [tuple(int(k) for k in s) for s in subsets]
+    list_subsets = [full] + [s for s in subsets if s != full]
+    din = 3 if ds.time_axis else 2
+    data = {}
+    for s in list_subsets:
+        view = ds if s == full else ds.with_levels(s)                               # ValueError
+        data["+".join(str(k) for k in s)] = [
+            _dataset_accuracy(model, view, None, din, batch_size, mode, sets_per_call), 0]
+    shown = [dict(n_fft=ds.layout["n_fft"][r], hop=ds.layout["hop"][r], Ntemp=ds.layout["Ntemp"][r],
+                  F=ds.layout["F"][r], offset=ds.layout["offset"][r],
+                  win_lengths=list(ds.layout["win_lengths"][r])) for r in range(n)]
+    out = {"data": data, "list_subsets": [list(s) for s in list_subsets], "levels": shown, "span": int(span)}
     _write_json(out, json_file)
     return out
 

@@ -65,6 +65,15 @@ class PcaFrameAug(C.Structure):
                 ("draw", C.c_uint64), ("draw_dev", C.c_void_p)]
 
 
+FRAME_MAX_LEVELS = 4
+
+
+class PcaFrameLevel(C.Structure):
+    _fields_ = [("n_fft", C.c_int32), ("hop", C.c_int32), ("n_bins", C.c_int32), ("Nt", C.c_int32),
+                ("offset", C.c_int32), ("farr", C.c_void_p), ("tarr", C.c_void_p),
+                ("win_lengths", C.c_void_p)]
+
+
 FRAME_MAX_SPEEDS = 8
 
 
@@ -183,6 +192,9 @@ SIGNATURES = {
     "pca_frame_points": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p, c_i64p,
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp,
                                    C.POINTER(PcaFrameAug), c_fp, c_i64p, c_vp, c_vp]),
+    "pca_frame_points_multires": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p,
+                                            c_i64p, C.c_int, C.POINTER(PcaFrameLevel), C.c_int, C.c_int64,
+                                            C.POINTER(PcaFrameAug), c_fp, c_i64p, c_vp, c_vp]),
     "pca_frame_points_reassigned": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p,
                                               c_i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp,
                                               c_fp, C.POINTER(PcaFrameAug), C.POINTER(PcaReassignSpec),

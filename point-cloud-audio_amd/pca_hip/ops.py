@@ -7,7 +7,7 @@ path runs in libpca_hip.so.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import math
 
@@ -808,6 +808,89 @@ def frame_points(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.Ten
                                      int(n_bins), int(Nt), _ptr(farr), _ptr(tarr), C.byref(aug),
                                      _ptr(out), _ptr(labels_out), _ptr(meta), _stream(waves)),
               "pca_frame_points")
+    return (out, labels_out, meta) if want_meta else (out, labels_out)
+
+
+class FrameLevel(NamedTuple):
+    """One resolution of a multi-resolution point set (``frame_points_multires``): ``Nt`` frames of
+    ``n_fft`` samples, ``hop`` apart, the first centred ``offset`` samples from the set's anchor, ``n_bins``
+    bins each; ``farr`` float32 [n_bins] and ``tarr`` float32 [Nt] (None in every level: 2-D rows) on the
+    device; ``win_lengths`` device int32, this level's window for each window index (None: [n_fft])."""
+    n_fft: int
+    hop: int
+    n_bins: int
+    Nt: int
+    farr: torch.Tensor
+    tarr: Optional[torch.Tensor] = None
+    win_lengths: Optional[torch.Tensor] = None
+    offset: int = 0
+
+
+def frame_points_multires(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.Tensor,
+                          idx: torch.Tensor, levels: Sequence[FrameLevel], span: int, *, max_len: int,
+                          min_len: int, clip_labels: Optional[torch.Tensor] = None, jitter: int = 0,
+                          gain_db: float = 0.0, norm_mode: int = NORM_NFFT, seed: int = 0, draw: int = 0,
+                          out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None,
+                          draw_dev: Optional[torch.Tensor] = None, want_meta: bool = False):
+    """Batch of point sets that hold several STFT resolutions at once, framed from resident waveforms in
+    ONE launch (pca_frame_points_multires): what one ``frame_points`` per level plus ``torch.cat`` gives,
+    without the batch's second trip through memory and with one set of draws.
+
+    waves / wave_off / idx / max_len / min_len / clip_labels / jitter / gain_db / norm_mode / seed / draw /
+    draw_dev as ``frame_points``; set_off int64[n_clips + 1] the prefix sum of the sets per clip at ``span``
+    samples a set.  Set s of a clip has its anchor at s * span + the slot's shift; frame j of a level is
+    centred at anchor + level.offset + j * level.hop, clamped into the clip.  A slot draws one shift, one
+    gain and one window INDEX for all its levels; every level's ``win_lengths`` has the same number of
+    entries (``ValueError`` otherwise).  At most 4 levels, at most 16384 points a set.
+    Returns (points [B, N, 2 or 3] float32 - the levels' rows back to back in the order given, point
+    j * n_bins + f inside a level -, clip_labels of each slot's clip or None [, meta int32 [B, 8] = (clip,
+    centre sample of level 0's frame 0, level 0's window length, bits of the fp32 gain, shift, window index,
+    0, 0)])."""
+    levels = [lv if isinstance(lv, FrameLevel) else FrameLevel(*lv) for lv in levels]
+    if not 1 <= len(levels) <= _lib.FRAME_MAX_LEVELS:
+        raise ValueError(f"frame_points_multires: {len(levels)} levels (1 .. {_lib.FRAME_MAX_LEVELS})")
+    _need_cuda(waves, wave_off, set_off, idx)
+    assert waves.dtype == torch.float32 and waves.is_contiguous()
+    assert wave_off.dtype == set_off.dtype == idx.dtype == torch.int64
+    assert wave_off.numel() == set_off.numel() >= 2
+    three = [lv.tarr is not None for lv in levels]
+    if any(three) != all(three):
+        raise ValueError("frame_points_multires: tarr is given in every level or in none")
+    din = 3 if three[0] else 2
+    B = idx.numel()
+    with torch.cuda.device(waves.device):
+        wins = [torch.tensor([lv.n_fft], dtype=torch.int32, device=waves.device)
+                if lv.win_lengths is None else lv.win_lengths for lv in levels]
+        n_win = wins[0].numel()
+        if any(w.numel() != n_win for w in wins) or n_win < 1:
+            raise ValueError(f"frame_points_multires: every level needs the same number of window lengths, "
+                             f"got {[w.numel() for w in wins]}")
+        arr = (_lib.PcaFrameLevel * len(levels))()
+        N = 0
+        for lv, w, a in zip(levels, wins, arr):
+            _need_cuda(lv.farr, w)
+            assert lv.farr.dtype == torch.float32 and lv.farr.numel() >= lv.n_bins
+            assert w.dtype == torch.int32 and w.is_contiguous()
+            if lv.tarr is not None:
+                _need_cuda(lv.tarr)
+                assert lv.tarr.dtype == torch.float32 and lv.tarr.numel() >= lv.Nt
+            a.n_fft, a.hop, a.n_bins, a.Nt, a.offset = (int(lv.n_fft), int(lv.hop), int(lv.n_bins),
+                                                        int(lv.Nt), int(lv.offset))
+            a.farr, a.tarr, a.win_lengths = lv.farr.data_ptr(), _ptr(lv.tarr), w.data_ptr()
+            N += int(lv.Nt) * int(lv.n_bins)
+        if out is None:
+            out = torch.empty((B, N, din), dtype=torch.float32, device=waves.device)
+        assert out.is_contiguous() and out.numel() == B * N * din
+        if clip_labels is not None and labels_out is None:
+            labels_out = torch.empty(B, dtype=torch.int64, device=waves.device)
+        meta = torch.empty((B, 8), dtype=torch.int32, device=waves.device) if want_meta else None
+        aug = _lib.PcaFrameAug(int(jitter), float(gain_db), None, n_win, int(norm_mode),
+                               int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1), _draw_ptr(draw_dev))
+        check(lib().pca_frame_points_multires(_ptr(waves), _ptr(wave_off), _ptr(set_off),
+                                              wave_off.numel() - 1, int(max_len), int(min_len),
+                                              _ptr(clip_labels), _ptr(idx), B, arr, len(levels), int(span),
+                                              C.byref(aug), _ptr(out), _ptr(labels_out), _ptr(meta),
+                                              _stream(waves)), "pca_frame_points_multires")
     return (out, labels_out, meta) if want_meta else (out, labels_out)
 
 
