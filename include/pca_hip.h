@@ -388,6 +388,50 @@ int pca_frame_points_multires(const float* waves, const int64_t* wave_off, const
                               int64_t span, const PcaFrameAug* aug, float* out, int64_t* labels_out,
                               int32_t* meta_out, void* stream);
 
+/* A bank of non-negative band filters over the FFT bins (pca_frame_points_bands), in banded form: band m
+ * covers the source bins band_lo[m] .. band_lo[m] + (band_off[m+1] - band_off[m]) - 1 with the weights
+ * weights[band_off[m] .. band_off[m+1]). */
+typedef struct PcaFrameBands {
+  int32_t n_bands;            /* >= 1 */
+  int32_t nnz;                /* length of weights, >= n_bands */
+  const int32_t* band_lo;     /* device int32[n_bands]: first FFT bin of band m */
+  const int32_t* band_off;    /* device int32[n_bands + 1]: weights of band m are weights[band_off[m] .. band_off[m+1]) */
+  const float*   weights;     /* device float[nnz] */
+  int32_t power;              /* 1: magnitude, 2: power */
+  float   amin;               /* > 0, finite: value = logf(amin + E) */
+} PcaFrameBands;
+
+/* pca_frame_points with the bins of every frame summed into bands (log-mel, or any other filter bank) while
+ * the spectrum lies in LDS: one point per band, not per FFT bin
+ * replaces: nothing - no reference counterpart (the reference's sets have one point per bin); what a caller
+ *           otherwise builds from pca_frame_points plus exp -> matmul -> log and a re-pack.
+ * Every argument up to `aug` is pca_frame_points' (n_bins is the bank's n_bands), with the same meaning and
+ * checks: clip, centre, shift, gain and window length of batch slot b come from pca_frame_points' stream and
+ * draw numbers, and labels_out and meta_out [B, 4] are that launch's bits for the same arguments.  The frame
+ * transform is pca_frame_points', butterfly for butterfly.  For every source bin k < n_fft/2 + 1, mag[k] is
+ * the fp32 magnitude of that launch (re and im scaled by 1 / norm and rounded to fp32, sqrtf(re^2 + im^2)),
+ * p[k] = (double)mag[k] (power 1) or (double)mag[k] * (double)mag[k] (power 2), and
+ *   E_m = sum_i (double)weights[band_off[m] + i] * p[band_lo[m] + i]
+ * in fp64, in an order that depends on the bank alone (four interleaved partial sums, each in ascending i,
+ * combined as (s0 + s1) + (s2 + s3)), never on timing or on the grid; value = logf(amin + (float)E_m).
+ * out[B, Nt*n_bands, 3]: point j*n_bands + m = (farr[m], tarr[j], value), or out[B, Nt*n_bands, 2] =
+ * (farr[m], value) when tarr is NULL; farr is a device float[n_bands], the caller's band axis.
+ * Nt*n_bands <= 16384, B <= 65535.  With the identity bank (band_lo[m] = m, one weight 1.0f per band,
+ * n_bands = n_bins), power 1 and amin 1e-8f the output is pca_frame_points' bits.
+ * The bank's arrays are device memory, clamped on the device, not checked on the host: a band's bin range is
+ * clipped into [0, n_fft/2 + 1) and its weight range into [0, nnz); a band that is empty after the clip
+ * yields logf(amin).  Nothing outside band_lo[n_bands], band_off[n_bands + 1] and weights[nnz] is read.
+ * Grid (Nt, B), 256 threads, 24 B * n_fft of LDS per workgroup as the plain launch (p[k] takes the place of
+ * the twiddles); no atomics: the same arguments give the same bits.
+ * PCA_EINVAL (message "frame_points_bands: ...") before any HIP call for: a null pointer (the bank's
+ * included); n_bands < 1; nnz < n_bands; power outside {1, 2}; amin not finite or <= 0; Nt*n_bands > 16384;
+ * and every case pca_frame_points rejects (n_fft, hop, Nt, B, min_len, max_len, the aug fields, label pairing). */
+int pca_frame_points_bands(const float* waves, const int64_t* wave_off, const int64_t* set_off,
+                           int n_clips, int64_t max_len, int64_t min_len, const int64_t* clip_labels,
+                           const int64_t* idx, int B, int n_fft, int hop, int Nt, const float* farr,
+                           const float* tarr, const PcaFrameAug* aug, const PcaFrameBands* bands,
+                           float* out, int64_t* labels_out, int32_t* meta_out, void* stream);
+
 /* Which points of a framed batch move to where their energy lies, and how far (pca_frame_points_reassigned). */
 typedef struct PcaReassignSpec {
   int32_t axes;       /* bit 0: frequency, bit 1: time; 1..3.  Bit 1 needs tarr and Nt >= 2 */

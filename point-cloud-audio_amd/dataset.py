@@ -450,6 +450,16 @@ class ESC_wave_pc(Dataset):
            win_lengths and norm; with speeds, the mix or the masks it raises ``ValueError`` (those live in
            pca_frame_points_ex: out of scope).  ``with_reassign(spec_or_None)`` gives a view on the same
            resident waveforms with another setting
+    bands  None: one point per FFT bin, as above.  A ``pca_hip.FilterBank`` over this n_fft
+           (``pca_hip.mel_bank(fs, n_fft, n_mels)`` for log-mel): one point per band,
+           (centres[m] / fs, [t,] log(amin + sum_k W[m, k] |stft|^power)), the bins summed inside the frame
+           launch - one pca_frame_points_bands launch per batch.  ``F`` becomes ``n_bands``, ``farr`` the
+           bands' centres / fs, ``num_points`` follows.  No reference counterpart.  A representation, not an
+           augmentation: ``plain()`` keeps it, ``stochastic`` ignores it, the sets stay dense.  It composes
+           with jitter, gain_db, win_lengths and norm; with speeds, the mix, the masks, ``reassign`` or
+           ``drop_nyquist=True`` it raises ``ValueError`` (those live in other launches, or cut the bins the
+           bank is defined over: out of scope).  ``with_bands(bank_or_None)`` gives a view on the same
+           resident waveforms with another bank (None: the grid dataset, bit for bit)
     """
     _ntemp = 1
 
@@ -457,12 +467,13 @@ class ESC_wave_pc(Dataset):
                  win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
                  mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None,
                  freq_masks=0, freq_mask_width=0, time_masks=0, time_mask_width=0, mask_mode="drop",
-                 reassign=None):
+                 reassign=None, bands=None):
         self._setup(clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                     device)
         self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db, mix_targets, mix_labels)
         self._setup_mask(freq_masks, freq_mask_width, time_masks, time_mask_width, mask_mode)
         self._setup_reassign(reassign)
+        self._setup_bands(bands)
 
     def _setup(self, clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                device):
@@ -474,6 +485,8 @@ class ESC_wave_pc(Dataset):
         self.hop = self.n_fft // 2 if hop is None else int(hop)
         self.F = self.n_fft // 2 if drop_nyquist else self.n_fft // 2 + 1
         self.farr = np.linspace(0, fs / 2, self.F) / fs
+        self._grid = (self.F, self.farr, bool(drop_nyquist))   # what with_bands(None) puts back
+        self.bands = None
         self.tarr = None
         self.jitter, self.gain_db = int(jitter), float(gain_db)
         self.win_lengths = (self.n_fft,) if win_lengths is None else tuple(int(w) for w in win_lengths)
@@ -565,9 +578,51 @@ class ESC_wave_pc(Dataset):
     def with_reassign(self, reassign):
         """A view on the same resident waveforms with another ``reassign`` (None: the grid dataset);
         everything else, the augmentations and the draw counter's value included, is kept."""
+        if self.bands is not None and reassign not in (None, False):
+            raise ValueError("reassign does not combine with bands: reassignment moves FFT bins, a band "
+                             "set has none (pca_frame_points_reassigned / pca_frame_points_bands)")
         v = copy.copy(self)
         v._setup_reassign(reassign)
         return v
+
+    def _setup_bands(self, bands):
+        """``bands``: None or a ``pca_hip.FilterBank`` over this n_fft; checked here, on the host."""
+        self.bands = None
+        self.F, self.farr = self._grid[0], self._grid[1]
+        if bands is None:
+            return
+        if not isinstance(bands, pca_hip.FilterBank):
+            raise TypeError(f"bands is a pca_hip.FilterBank (pca_hip.mel_bank(...)) or None, got "
+                            f"{type(bands).__name__}")
+        if self._speed_on or self._mix_on or self.mix_targets or self._mask_on or self.reassign is not None:
+            raise ValueError("bands do not combine with speeds, the mix, the masks or reassign: those live in "
+                             "other launches (pca_frame_points_ex, pca_frame_points_reassigned), the band "
+                             "sums in pca_frame_points_bands - out of scope")
+        if self._grid[2] and not isinstance(self, ESC_wave_pc_temp):   # the 3-D grid's own drop is not the caller's
+            raise ValueError("bands do not combine with drop_nyquist=True: a bank is defined over all "
+                             "n_fft/2 + 1 bins (leave the Nyquist bin out of the bank instead) - out of scope")
+        if bands.n_src != self.n_fft // 2 + 1:
+            raise ValueError(f"bands cover {bands.n_src} bins, n_fft = {self.n_fft} has "
+                             f"{self.n_fft // 2 + 1}")
+        if self._ntemp * bands.n_bands > 16384:
+            raise ValueError(f"bands: {self._ntemp * bands.n_bands} points per set (max 16384)")
+        self.bands = bands
+        self.F = bands.n_bands
+        self.farr = np.asarray(bands.centres, dtype=np.float64) / self.fs
+
+    def with_bands(self, bands):
+        """A view on the same resident waveforms with another filter bank (None: the grid dataset, bit for
+        bit); everything else, the augmentations and the draw counter's value included, is kept."""
+        v = copy.copy(self)
+        v._setup_bands(bands)
+        return v
+
+    def _bands_farr(self, dev):
+        """The band axis on the device, once per bank, in the store the views share."""
+        held = self._store.setdefault("bands_farr", {})
+        if id(self.bands) not in held:       # the entry keeps the bank alive, so its id stays its own
+            held[id(self.bands)] = (self.bands, torch.as_tensor(self.farr).float().to(dev))
+        return held[id(self.bands)][1]
 
     @property
     def _mask_on(self) -> bool:
@@ -630,7 +685,7 @@ class ESC_wave_pc(Dataset):
             f32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64)).float().to(dev)  # noqa: E731
             waves = torch.cat([torch.as_tensor(c).to(dev, torch.float32).reshape(-1)
                                for c in self.clips])
-            self._store["res"] = (waves, i64(self.wave_off), i64(self.set_off), f32(self.farr),
+            self._store["res"] = (waves, i64(self.wave_off), i64(self.set_off), f32(self._grid[1]),
                                   None if self.tarr is None else f32(self.tarr),
                                   i64(self.clip_labels))
             self._store["win"] = {}
@@ -707,6 +762,14 @@ class ESC_wave_pc(Dataset):
                 draw_dev=draw_dev, want_meta=want_meta, want_samples=want_samples, **mix, **mask)
         if want_samples:
             raise ValueError("want_samples needs speeds or the mix on (pca_hip.frame_points_ex)")
+        if self.bands is not None:
+            return pca_hip.frame_points_bands(
+                waves, woff, soff, idx, self.n_fft, self.hop, self.bands, self._bands_farr(waves.device), t32,
+                self._ntemp, max_len=self._max_len, min_len=self._min_len, clip_labels=lab,
+                jitter=self.jitter, gain_db=self.gain_db, win_lengths=self._win_dev(waves.device),
+                norm_mode=pca_hip.NORM_WIN if self.norm == "win" else pca_hip.NORM_NFFT,
+                seed=self.seed, draw=self._draw, out=out, labels_out=labels_out, draw_dev=draw_dev,
+                want_meta=want_meta)
         if self.reassign is not None:
             return pca_hip.frame_points_reassigned(
                 waves, woff, soff, idx, self.n_fft, self.hop, self.F, f32, t32, self._ntemp,
@@ -740,13 +803,15 @@ class ESC_wave_pc_temp(ESC_wave_pc):
     short tail dropped), float32 [Ntemp * F, 3] rows (farr[f], tarr[t], value), point p = t * F + f,
     the Nyquist bin dropped and tarr = linspace(0, hop / fs * Ntemp, Ntemp) as
     Code/settransformertemp.py:40-41,52.  One shift, gain and window per chunk, so its frames stay
-    ``hop`` apart and ``tarr`` keeps its meaning.  Arguments as ``ESC_wave_pc``."""
+    ``hop`` apart and ``tarr`` keeps its meaning.  Arguments as ``ESC_wave_pc``; with ``bands`` the rows
+    are (centres[m] / fs, tarr[t], value), point p = t * n_bands + m, and the bank sees all n_fft/2 + 1
+    bins (the grid's dropped Nyquist bin is the grid's affair)."""
 
     def __init__(self, clips, y, fs, n_fft, Ntemp, hop=None, jitter=0, gain_db=0.0,
                  win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
                  mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None,
                  freq_masks=0, freq_mask_width=0, time_masks=0, time_mask_width=0, mask_mode="drop",
-                 reassign=None):
+                 reassign=None, bands=None):
         self._ntemp = int(Ntemp)
         assert self._ntemp >= 1
         self._setup(clips, y, fs, n_fft, hop, True, jitter, gain_db, win_lengths, norm, seed, device)
@@ -754,6 +819,7 @@ class ESC_wave_pc_temp(ESC_wave_pc):
         self._setup_mask(freq_masks, freq_mask_width, time_masks, time_mask_width, mask_mode)
         self.tarr = np.linspace(0, (self.hop / fs) * self._ntemp, self._ntemp)
         self._setup_reassign(reassign)
+        self._setup_bands(bands)
 
 
 def wave_span_offsets(lengths, span: int) -> list:

@@ -37,6 +37,8 @@ The other set-model experiments run here at batch scale too:
   (``pca_hip.frame_points_reassigned``), one pass per strength; no reference counterpart;
 * ``multires_sweep``: sets that hold several STFT resolutions at once (``pca_hip.frame_points_multires``),
   scored with all levels and with subsets of them, one pass per subset; no reference counterpart;
+* ``band_sweep``: log-mel / filter-bank point sets (``pca_hip.frame_points_bands``) at several band counts,
+  one pass per bank over one resident corpus; no reference counterpart;
 * ``reframe_sweep_temporal``: the (Fs, N) re-framing of the 3ST, Code/pc_temp3d_eval.py:56-107.
 * ``clip_accuracy``: the clip-level scores the datasets' literature reports (majority vote and mean
   log-probability over a clip's frames or chunks, ``pca_hip.clip_aggregate``) next to the frame score;
@@ -83,6 +85,7 @@ from pca_hip.trainer import STEngine, st_config
 
 __all__ = ["reframe_sweep", "framewise_dataset", "default_list_K", "sweep_draw", "subsample_sweep",
            "importance_sweep", "attention_sweep", "peak_sweep", "most_peaks", "reassign_sweep", "multires_sweep",
+           "band_sweep",
            "default_level_subsets", "chunk_plan",
            "temporal_axes", "temporal_dataset", "reframe_sweep_temporal", "baseline_subsample_sweep", "baseline_frames",
            "baseline_chunks", "baseline_reframe_sweep", "baseline_reframe_sweep_temporal",
@@ -690,6 +693,51 @@ def multires_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], 
                   F=ds.layout["F"][r], offset=ds.layout["offset"][r],
                   win_lengths=list(ds.layout["win_lengths"][r])) for r in range(n)]
     out = {"data": data, "list_subsets": [list(s) for s in list_subsets], "levels": shown, "span": int(span)}
+    _write_json(out, json_file)
+    return out
+
+
+@torch.no_grad()
+def band_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float, n_fft: int, banks,
+               Ntemp: Optional[int] = None, batch_size: int = 8, json_file: Optional[str] = None,
+               mode: int = _lib.MODE_F32, sets_per_call: Optional[int] = None, hop: Optional[int] = None,
+               norm: str = "n_fft", **mel_kw) -> Dict:
+    """Accuracy of ``model`` on band point sets (``pca_hip.frame_points_bands``: log-mel and other filter
+    banks) for every bank of ``banks``: the band count as one more resolution axis - a Set Transformer
+    trained at 64 bands can be scored at 32 or 128, since it takes any N.  **No reference counterpart**: the
+    reference's sets have one point per FFT bin.
+
+    ``clips`` / ``labels`` / ``fs`` / ``n_fft`` [/ ``hop`` / ``norm``] as ``ESC_wave_pc`` takes them; with
+    ``Ntemp`` the 3-D sets of ``ESC_wave_pc_temp``, else the 2-D sets.  ``banks``: a dict name ->
+    ``pca_hip.FilterBank``, or a list of ``n_mels`` - then every bank is ``pca_hip.mel_bank(fs, n_fft,
+    n_mels, **mel_kw)`` (fmin, fmax, htk, norm as ``mel_norm``, power, amin) under the name ``str(n_mels)``.
+    The corpus is resident once; every bank is one ``_dataset_accuracy`` pass over a ``with_bands`` view of
+    it, one host read each.
+
+    Returns (and, with ``json_file``, writes) ``{"data": {name: [acc, 0]}, "list_banks": [names],
+    "banks": [{"n_bands", "power", "amin", "nnz"}, ...]}``, the banks in the order given."""
+    if isinstance(banks, dict):
+        if mel_kw:
+            raise ValueError(f"band_sweep: {sorted(mel_kw)} describe mel banks; banks is a dict of FilterBanks")
+        named = [(str(k), b) for k, b in banks.items()]
+    else:
+        if "mel_norm" in mel_kw:
+            mel_kw["norm"] = mel_kw.pop("mel_norm")
+        named = [(str(int(n)), pca_hip.mel_bank(fs, n_fft, int(n), **mel_kw)) for n in banks]   # ValueError
+    if not named:
+        raise ValueError("band_sweep: no banks")
+    dev = _model_device(model)
+    if Ntemp is None:
+        ds = ESC_wave_pc(clips, labels, fs, n_fft, hop=hop, norm=norm, device=dev)
+    else:
+        ds = ESC_wave_pc_temp(clips, labels, fs, n_fft, Ntemp, hop=hop, norm=norm, device=dev)
+    din = 2 if Ntemp is None else 3
+    data = {}
+    for name, bank in named:
+        view = ds.with_bands(bank)                                                  # ValueError
+        data[name] = [_dataset_accuracy(model, view, None, din, batch_size, mode, sets_per_call), 0]
+    out = {"data": data, "list_banks": [name for name, _ in named],
+           "banks": [bank.summary() for _, bank in named]}
     _write_json(out, json_file)
     return out
 

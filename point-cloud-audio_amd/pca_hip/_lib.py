@@ -74,6 +74,12 @@ class PcaFrameLevel(C.Structure):
                 ("win_lengths", C.c_void_p)]
 
 
+class PcaFrameBands(C.Structure):
+    _fields_ = [("n_bands", C.c_int32), ("nnz", C.c_int32), ("band_lo", C.c_void_p),
+                ("band_off", C.c_void_p), ("weights", C.c_void_p), ("power", C.c_int32),
+                ("amin", C.c_float)]
+
+
 FRAME_MAX_SPEEDS = 8
 
 
@@ -195,6 +201,10 @@ SIGNATURES = {
     "pca_frame_points_multires": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p,
                                             c_i64p, C.c_int, C.POINTER(PcaFrameLevel), C.c_int, C.c_int64,
                                             C.POINTER(PcaFrameAug), c_fp, c_i64p, c_vp, c_vp]),
+    "pca_frame_points_bands": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p, c_i64p,
+                                         C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp,
+                                         C.POINTER(PcaFrameAug), C.POINTER(PcaFrameBands), c_fp, c_i64p,
+                                         c_vp, c_vp]),
     "pca_frame_points_reassigned": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p,
                                               c_i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp,
                                               c_fp, C.POINTER(PcaFrameAug), C.POINTER(PcaReassignSpec),

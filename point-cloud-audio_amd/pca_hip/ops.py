@@ -11,6 +11,7 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -891,6 +892,213 @@ def frame_points_multires(waves: torch.Tensor, wave_off: torch.Tensor, set_off: 
                                               _ptr(clip_labels), _ptr(idx), B, arr, len(levels), int(span),
                                               C.byref(aug), _ptr(out), _ptr(labels_out), _ptr(meta),
                                               _stream(waves)), "pca_frame_points_multires")
+    return (out, labels_out, meta) if want_meta else (out, labels_out)
+
+
+class FilterBank:
+    """A bank of non-negative band filters over the ``n_fft/2 + 1`` bins of a frame, for
+    ``frame_points_bands``: value of band m = log(amin + sum_k W[m, k] * |X[k]|^power).
+
+    ``W`` float64 [n_bands, n_fft/2 + 1] on the host (anything ``numpy.asarray`` takes), ``centres`` the
+    bands' centre frequencies in Hz [n_bands] (the datasets' frequency axis), ``power`` 1 (magnitude) or 2
+    (power), ``amin`` > 0.  Packed once to the banded form of ``PcaFrameBands``: per band the span from its
+    first to its last non-zero weight (as the device sees them: rounded to fp32), zeros inside the span
+    kept; uploaded once per device.  ``ValueError`` for a wrong shape, a negative or non-finite weight and a
+    band without a non-zero weight (the message names the band)."""
+
+    def __init__(self, W, centres, power: int = 2, amin: float = 1e-8):
+        W = np.asarray(W, dtype=np.float64)
+        centres = np.asarray(centres, dtype=np.float64)
+        if W.ndim != 2 or W.shape[0] < 1 or W.shape[1] < 2:
+            raise ValueError(f"FilterBank: W of shape {W.shape}, expected [n_bands, n_fft/2 + 1]")
+        n_fft = 2 * (W.shape[1] - 1)
+        if n_fft & (n_fft - 1):
+            raise ValueError(f"FilterBank: W has {W.shape[1]} columns, expected n_fft/2 + 1 for a power of "
+                             "two n_fft")
+        if centres.shape != (W.shape[0],):
+            raise ValueError(f"FilterBank: centres of shape {centres.shape} for {W.shape[0]} bands")
+        if not np.isfinite(W).all() or (W < 0).any():
+            raise ValueError("FilterBank: a negative or non-finite weight")
+        if not np.isfinite(centres).all():
+            raise ValueError("FilterBank: a non-finite centre")
+        w32 = W.astype(np.float32)
+        if not np.isfinite(w32).all():
+            raise ValueError("FilterBank: a weight beyond the fp32 range")
+        lo, off, parts = [], [0], []
+        for m in range(W.shape[0]):
+            nz = np.flatnonzero(w32[m])
+            if nz.size == 0:
+                raise ValueError(f"FilterBank: band {m} has no non-zero weight (too many bands for "
+                                 f"{W.shape[1]} bins?)")
+            lo.append(int(nz[0]))
+            parts.append(w32[m, nz[0]:nz[-1] + 1])
+            off.append(off[-1] + parts[-1].size)
+        self._init(np.asarray(lo, np.int32), np.asarray(off, np.int32), np.concatenate(parts), W.shape[1],
+                   centres, power, amin)
+        self.W = W                        # as given, in fp64; dense() is what the device applies
+
+    def _init(self, band_lo, band_off, weights, n_src, centres, power, amin):
+        power, amin = int(power), float(amin)
+        if power not in (1, 2):
+            raise ValueError(f"FilterBank: power {power} (1: magnitude, 2: power)")
+        if not (0.0 < amin < float("inf")) or not float(np.float32(amin)) > 0.0:
+            raise ValueError(f"FilterBank: amin {amin} must be finite and > 0 (in fp32)")
+        self.band_lo, self.band_off, self.weights = band_lo, band_off, weights
+        self.n_src, self.n_fft = int(n_src), 2 * (int(n_src) - 1)
+        self.n_bands, self.nnz = int(band_lo.size), int(weights.size)
+        self.centres, self.power, self.amin = centres, power, amin
+        self._dev = {}
+
+    @classmethod
+    def from_packed(cls, band_lo, band_off, weights, n_src: int, centres=None, power: int = 2,
+                    amin: float = 1e-8) -> "FilterBank":
+        """A bank from its banded arrays, values unchecked (the launch clips every band's range into the
+        frame's bins on the device): band_lo int32 [n_bands], band_off int32 [n_bands + 1], weights float32
+        [nnz >= n_bands].  ``centres`` defaults to the band index."""
+        band_lo = np.ascontiguousarray(band_lo, dtype=np.int32).reshape(-1)
+        band_off = np.ascontiguousarray(band_off, dtype=np.int32).reshape(-1)
+        weights = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        if band_lo.size < 1 or band_off.size != band_lo.size + 1 or weights.size < band_lo.size:
+            raise ValueError(f"FilterBank.from_packed: {band_lo.size} bands, {band_off.size} offsets, "
+                             f"{weights.size} weights")
+        centres = (np.arange(band_lo.size, dtype=np.float64) if centres is None
+                   else np.asarray(centres, dtype=np.float64))
+        if centres.shape != (band_lo.size,):
+            raise ValueError(f"FilterBank.from_packed: centres of shape {centres.shape}")
+        self = cls.__new__(cls)
+        self._init(band_lo, band_off, weights, n_src, centres, power, amin)
+        self.W = self.dense()
+        return self
+
+    def dense(self) -> "np.ndarray":
+        """The bank as the device applies it: float64 [n_bands, n_src] from the packed fp32 weights, every
+        band clipped into the bins as the launch clips it."""
+        W = np.zeros((self.n_bands, self.n_src), dtype=np.float64)
+        for m in range(self.n_bands):
+            o0 = min(max(int(self.band_off[m]), 0), self.nnz)
+            o1 = min(max(int(self.band_off[m + 1]), o0), self.nnz)
+            lo = int(self.band_lo[m])
+            for i in range(max(-lo, 0), min(o1 - o0, self.n_src - lo)):
+                W[m, lo + i] = float(self.weights[o0 + i])
+        return W
+
+    def summary(self) -> dict:
+        return {"n_bands": self.n_bands, "power": self.power, "amin": self.amin, "nnz": self.nnz}
+
+    def on(self, device) -> "_lib.PcaFrameBands":
+        """The C struct with the arrays on ``device`` (uploaded on first use, kept for the bank's life)."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._dev:
+            if device.type != "cuda":
+                raise _lib.PcaHipError("FilterBank.on: a bank is applied on the device (no CPU fallback)")
+            self._dev[device] = tuple(torch.from_numpy(a).to(device)
+                                      for a in (self.band_lo, self.band_off, self.weights))
+        lo, off, w = self._dev[device]
+        return _lib.PcaFrameBands(self.n_bands, self.nnz, lo.data_ptr(), off.data_ptr(), w.data_ptr(),
+                                  self.power, self.amin)
+
+
+def _hz_to_mel(f, htk: bool):
+    f = np.asarray(f, dtype=np.float64)
+    if htk:
+        return 2595.0 * np.log10(1.0 + f / 700.0)
+    lin = f / (200.0 / 3.0)
+    with np.errstate(divide="ignore"):
+        log = 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) / (math.log(6.4) / 27.0)
+    return np.where(f >= 1000.0, log, lin)
+
+
+def _mel_to_hz(m, htk: bool):
+    m = np.asarray(m, dtype=np.float64)
+    if htk:
+        return 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+    return np.where(m >= 15.0, 1000.0 * np.exp((math.log(6.4) / 27.0) * (m - 15.0)), m * (200.0 / 3.0))
+
+
+def mel_bank(fs: float, n_fft: int, n_mels: int, fmin: float = 0.0, fmax: Optional[float] = None,
+             htk: bool = False, norm: Optional[str] = "slaney", power: int = 2,
+             amin: float = 1e-8) -> FilterBank:
+    """Triangular mel filters as a ``FilterBank``, in the form of ``librosa.filters.mel`` (written from the
+    published formulae; parity with librosa itself is not pinned by a test: it is not a dependency).
+
+    Slaney scale (default): mel = f / (200/3) below 1000 Hz, 15 + ln(f / 1000) / (ln(6.4) / 27) from there;
+    ``htk``: 2595 log10(1 + f / 700).  ``n_mels + 2`` points p equally spaced in mel between ``fmin`` and
+    ``fmax`` (None: fs / 2), mapped back to Hz; band i is the triangle
+    max(0, min((f_k - p_i) / (p_i+1 - p_i), (p_i+2 - f_k) / (p_i+2 - p_i+1))) over f_k = k fs / n_fft,
+    times 2 / (p_i+2 - p_i) with ``norm="slaney"`` (None: peaks of up to 1).  ``centres`` = p_i+1.
+    ``ValueError`` when a band falls between two bins (no non-zero weight): fewer bands or a longer frame."""
+    n_fft, n_mels = int(n_fft), int(n_mels)
+    if n_mels < 1:
+        raise ValueError(f"mel_bank: n_mels {n_mels}")
+    if norm not in (None, "slaney"):
+        raise ValueError(f"mel_bank: norm {norm!r} (None or 'slaney')")
+    fmax = float(fs) / 2.0 if fmax is None else float(fmax)
+    if not 0.0 <= float(fmin) < fmax <= float(fs) / 2.0 + 1e-9:
+        raise ValueError(f"mel_bank: fmin {fmin}, fmax {fmax} outside 0 <= fmin < fmax <= fs/2")
+    pts = _mel_to_hz(np.linspace(float(_hz_to_mel(fmin, htk)), float(_hz_to_mel(fmax, htk)), n_mels + 2), htk)
+    fk = np.arange(n_fft // 2 + 1, dtype=np.float64) * (float(fs) / n_fft)
+    d = np.diff(pts)
+    lower = (fk[None, :] - pts[:-2, None]) / d[:-1, None]
+    upper = (pts[2:, None] - fk[None, :]) / d[1:, None]
+    W = np.maximum(0.0, np.minimum(lower, upper))
+    if norm == "slaney":
+        W = W * (2.0 / (pts[2:] - pts[:-2]))[:, None]
+    return FilterBank(W, pts[1:-1], power=power, amin=amin)
+
+
+def frame_points_bands(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.Tensor,
+                       idx: torch.Tensor, n_fft: int, hop: int, bank: FilterBank, farr: torch.Tensor,
+                       tarr: Optional[torch.Tensor] = None, Nt: int = 1, *, max_len: int, min_len: int,
+                       clip_labels: Optional[torch.Tensor] = None, jitter: int = 0,
+                       gain_db: float = 0.0, win_lengths: Optional[torch.Tensor] = None,
+                       norm_mode: int = NORM_NFFT, seed: int = 0, draw: int = 0,
+                       out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None,
+                       draw_dev: Optional[torch.Tensor] = None, want_meta: bool = False):
+    """``frame_points`` with the bins of every frame summed into the bands of ``bank`` inside the launch
+    (pca_frame_points_bands): log-mel and other filter-bank point sets, one point per band.
+
+    Every argument of ``frame_points`` with the same meaning (``n_bins`` is ``bank.n_bands``); ``farr``
+    float32 [n_bands] on the device is the band axis.  Slot b's clip, shift, gain and window are
+    ``frame_points``' for the same arguments, and so are the labels and meta; the value of band m is
+    logf(amin + sum_k W[m, k] * |X[k]|^power), the sum in fp64 in an order the bank alone fixes.
+    Returns (points [B, Nt * n_bands, 2 or 3] float32, labels or None [, meta int32 [B, 4]])."""
+    if not isinstance(bank, FilterBank):
+        raise TypeError(f"frame_points_bands: bank is a {type(bank).__name__}, expected a FilterBank")
+    if bank.n_src != int(n_fft) // 2 + 1:
+        raise ValueError(f"frame_points_bands: the bank covers {bank.n_src} bins, n_fft {n_fft} has "
+                         f"{int(n_fft) // 2 + 1}")
+    _need_cuda(waves, wave_off, set_off, idx, farr)
+    assert waves.dtype == torch.float32 and waves.is_contiguous() and farr.dtype == torch.float32
+    assert wave_off.dtype == set_off.dtype == idx.dtype == torch.int64
+    assert wave_off.numel() == set_off.numel() >= 2 and farr.numel() >= bank.n_bands
+    din = 2
+    if tarr is not None:
+        _need_cuda(tarr)
+        assert tarr.dtype == torch.float32 and tarr.numel() >= Nt
+        din = 3
+    B = idx.numel()
+    with torch.cuda.device(waves.device):
+        if win_lengths is None:
+            win_lengths = torch.tensor([n_fft], dtype=torch.int32, device=waves.device)
+        assert win_lengths.is_cuda and win_lengths.dtype == torch.int32
+        if out is None:
+            out = torch.empty((B, Nt * bank.n_bands, din), dtype=torch.float32, device=waves.device)
+        assert out.is_contiguous() and out.numel() == B * Nt * bank.n_bands * din
+        if clip_labels is not None and labels_out is None:
+            labels_out = torch.empty(B, dtype=torch.int64, device=waves.device)
+        meta = torch.empty((B, 4), dtype=torch.int32, device=waves.device) if want_meta else None
+        aug = _lib.PcaFrameAug(int(jitter), float(gain_db), win_lengths.data_ptr(),
+                               win_lengths.numel(), int(norm_mode), int(seed) & (2 ** 64 - 1),
+                               int(draw) & (2 ** 64 - 1), _draw_ptr(draw_dev))
+        bands = bank.on(waves.device)
+        check(lib().pca_frame_points_bands(_ptr(waves), _ptr(wave_off), _ptr(set_off),
+                                           wave_off.numel() - 1, int(max_len), int(min_len),
+                                           _ptr(clip_labels), _ptr(idx), B, int(n_fft), int(hop), int(Nt),
+                                           _ptr(farr), _ptr(tarr), C.byref(aug), C.byref(bands),
+                                           _ptr(out), _ptr(labels_out), _ptr(meta), _stream(waves)),
+              "pca_frame_points_bands")
     return (out, labels_out, meta) if want_meta else (out, labels_out)
 
 
