@@ -432,6 +432,58 @@ int pca_frame_points_bands(const float* waves, const int64_t* wave_off, const in
                            const float* tarr, const PcaFrameAug* aug, const PcaFrameBands* bands,
                            float* out, int64_t* labels_out, int32_t* meta_out, void* stream);
 
+/* Per-channel energy normalisation of band energies (pca_frame_points_pcen). */
+typedef struct PcaPcen {
+  int32_t context;    /* W, frames of history before the set, in [0, 255] */
+  float   s;          /* smoothing coefficient, in (0, 1] */
+  float   gain;       /* exponent of the smoothed energy in the divisor, in [0, 4] */
+  float   bias;       /* in [0, 1e6] */
+  float   r;          /* the root, in (0, 1] */
+  float   eps;        /* > 0, finite */
+  float   scale;      /* > 0, finite: applied to the band energy first */
+} PcaPcen;
+
+/* pca_frame_points_bands with per-channel energy normalisation (PCEN: Wang et al. 2017; Lostanlen et al. 2019,
+ * "PCEN: why and how"; librosa.pcen) in place of the log: each band divided by a smoothed version of itself
+ * over the frames before it (automatic gain control), then a root.
+ * replaces: nothing - no reference counterpart; what a caller otherwise builds from a band launch over a longer
+ *           span plus exp, a loop over the frames, pow and a re-pack.
+ * Every argument up to `bands` is pca_frame_points_bands': for batch slot b the clip, shift delta, gain g,
+ * window, labels_out and meta_out [B, 4] are that launch's bits for the same arguments (the same stream, draw
+ * numbers 0, 1, 2, no new draws).  bands->amin is checked and not used.
+ * With W = pcen->context the launch looks at T = W + Nt frames u = 0 .. T-1, centred at
+ * clamp(first + (u - W) * hop, 0, L) with first = s_set * Nt * hop + delta as in that launch: context before the
+ * start of a clip repeats the frame at sample 0, which leaves the smoother in its steady state there.
+ * E[u][m] is that launch's fp64 band sum of frame u (the same fp32 magnitudes, four-lane order and clipping of
+ * the bank).  Then in fp64, per band m, with the struct's floats converted to double and no fused
+ * multiply-add:
+ *   x[u] = scale * E[u][m]
+ *   M[0] = x[0];   M[u] = (1 - s) * M[u-1] + s * x[u]           (u = 1 .. T-1, in this order)
+ *   y[u] = pow(bias + x[u] * exp(-gain * log(eps + M[u])), r) - pow(bias, r)
+ * rounded to fp32 once.  Rows exist for u >= W only: point (u - W) * n_bands + m of out[B, Nt*n_bands, 3] =
+ * (farr[m], tarr[u - W], y), or out[B, Nt*n_bands, 2] = (farr[m], y) when tarr is NULL.
+ * M[0] = x[0] is librosa.pcen's initial state (its lfilter_zi scaling makes the first output the first input).
+ * One launch, grid (W + Nt, B), 256 threads, the band launch's LDS.  Every workgroup stores the n_bands sums of
+ * its frame to energy_ws [B][W + Nt][n_bands] (device fp64, energy_ws_elems doubles, contents undefined on
+ * entry and exit) with agent-scope write-through stores (the release), drains them and then draws a ticket: a
+ * fetch_add on tickets[b] (device int32[B], ZERO on entry).  The workgroup that draws W + Nt - 1 is the slot's
+ * last; after an agent-scope acquire it alone runs the recursion (one lane per output point, each from u = 0
+ * up to its own frame in ascending order: the bits of one lane per band), writes the Nt rows and stores 0 back
+ * to tickets[b], so the tickets are zero again when the launch ends (a captured launch replays without a
+ * memset).  No workgroup waits for another - one that is not last exits - so the launch cannot hang, whatever
+ * the grid size or the other work on the device; which workgroup is last does not affect the result: the same
+ * arguments give the same bits.  Two launches that share energy_ws or tickets must not overlap in time.
+ * PCA_EINVAL (message "frame_points_pcen: ...") before any HIP call for: a null pointer; context outside
+ * [0, 255]; s outside (0, 1]; gain outside [0, 4]; bias outside [0, 1e6]; r outside (0, 1]; eps or scale not
+ * finite or <= 0; B * (context + Nt) * n_bands > energy_ws_elems; and every case pca_frame_points_bands
+ * rejects. */
+int pca_frame_points_pcen(const float* waves, const int64_t* wave_off, const int64_t* set_off, int n_clips,
+                          int64_t max_len, int64_t min_len, const int64_t* clip_labels, const int64_t* idx,
+                          int B, int n_fft, int hop, int Nt, const float* farr, const float* tarr,
+                          const PcaFrameAug* aug, const PcaFrameBands* bands, const PcaPcen* pcen,
+                          double* energy_ws, int64_t energy_ws_elems, int32_t* tickets, float* out,
+                          int64_t* labels_out, int32_t* meta_out, void* stream);
+
 /* Which points of a framed batch move to where their energy lies, and how far (pca_frame_points_reassigned). */
 typedef struct PcaReassignSpec {
   int32_t axes;       /* bit 0: frequency, bit 1: time; 1..3.  Bit 1 needs tarr and Nt >= 2 */

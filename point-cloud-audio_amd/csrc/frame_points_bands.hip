@@ -21,8 +21,9 @@
 //      consecutive rows per store.
 // The bank is device memory: a band's range is clipped into [0, n_fft/2] and its weight offsets into
 // [0, nnz] here, so nothing outside band_lo[n_bands], band_off[n_bands + 1] and weights[nnz] is read.
+// The slot's draws and stages 1 - 2 live in band_sums.hpp, which k_frame_points_pcen shares.
+#include "band_sums.hpp"
 #include "pca_common.h"
-#include "select_keys.hpp"
 #include "stft_body.hpp"
 
 #include <float.h>
@@ -33,26 +34,6 @@
 namespace pca {
 namespace {
 
-struct BandsJob {
-  const float* waves;
-  const int64_t *wave_off, *set_off, *clip_labels, *idx;
-  const float *farr, *tarr;
-  const int32_t *win_lengths, *draw_dev;
-  const int32_t *band_lo, *band_off;
-  const float* weights;
-  float* out;
-  int64_t* labels_out;
-  int32_t* meta_out;
-  uint64_t seed, draw;
-  int n_clips, n_fft, log2n, hop, n_bands, nnz, power, Nt, jitter, n_win, norm_mode;
-  float gain_db, amin;
-};
-
-// draw number k of a slot's stream, as k_frame_points: 0 time shift, 1 level, 2 window length
-__device__ __forceinline__ uint64_t bands_draw(uint64_t stream, int k) {
-  return mix64(stream + (uint64_t)k * 0xd1342543de82ef95ull);
-}
-
 // Workgroup (j, b): frame j of the set in batch slot b, as k_frame_points.
 __global__ __launch_bounds__(256) void k_frame_points_bands(const BandsJob a) {
   extern __shared__ __attribute__((aligned(16))) double2 lds_c[];
@@ -60,66 +41,16 @@ __global__ __launch_bounds__(256) void k_frame_points_bands(const BandsJob a) {
   double2* tw = lds_c + a.n_fft;        // [n_fft/2]
   const int tid = threadIdx.x, j = blockIdx.x, b = blockIdx.y;
 
-  const int64_t total = a.set_off[a.n_clips];
-  if (total <= 0) return;               // (uniform) a corpus that yields no set
-  int64_t i = a.idx[b];
-  i = i < 0 ? 0 : (i >= total ? total - 1 : i);
-  int lo = 0, hi = a.n_clips;           // first clip whose set_off exceeds i (set_off[n_clips] does)
-  while (lo < hi) {
-    const int m = (lo + hi) >> 1;
-    if (a.set_off[m] > i) hi = m; else lo = m + 1;
-  }
-  const int c = lo > 0 ? lo - 1 : 0;    // set_off[c] <= i < set_off[c + 1]  (set_off[0] is 0)
-  const int64_t s = i - a.set_off[c];
-  const int64_t w0 = a.wave_off[c];
-  const int64_t L = a.wave_off[c + 1] - w0;
+  BandsSlot s;
+  if (!bands_slot(a, b, s)) return;     // (uniform) a corpus that yields no set
+  int64_t centre = s.first + (int64_t)j * a.hop;
+  centre = centre < 0 ? 0 : (centre > s.L ? s.L : centre);   // the range the regular grid can reach
+  if (j == 0 && tid == 0) bands_write_meta(a, b, s, centre);
 
-  // k_frame_points' stream and draws: a field that is off draws nothing and is exact
-  uint64_t draw = a.draw;
-  if (a.draw_dev != nullptr) draw += (uint64_t)(uint32_t)a.draw_dev[0];   // device-side counter
-  const uint64_t stream = select_stream(a.seed, draw, i, b);
-  int64_t delta = 0;
-  if (a.jitter > 0) {
-    const uint64_t r = bands_draw(stream, 0) >> 32;
-    delta = (int64_t)((r * (uint64_t)(2 * (int64_t)a.jitter + 1)) >> 32) - a.jitter;
-  }
-  float g = 1.0f;
-  if (a.gain_db > 0.f) {
-    const double u = (double)(bands_draw(stream, 1) >> 11) * (2.0 / 9007199254740992.0) - 1.0;  // [-1, 1)
-    g = (float)exp2(u * (double)a.gain_db * 0.16609640474436813);          // 10^(u dB / 20)
-  }
-  int wi = 0;
-  if (a.n_win > 1) wi = (int)(((bands_draw(stream, 2) >> 32) * (uint64_t)a.n_win) >> 32);
-  int win = a.win_lengths[wi];          // device values: clamped here, not checked on the host
-  win = win < 1 ? 1 : (win > a.n_fft ? a.n_fft : win);
-
-  const int64_t first = s * a.Nt * a.hop + delta;       // centre of frame 0 before the clamp
-  int64_t centre = first + (int64_t)j * a.hop;
-  centre = centre < 0 ? 0 : (centre > L ? L : centre);  // the range the regular grid can reach
-  if (j == 0 && tid == 0) {
-    if (a.clip_labels != nullptr && a.labels_out != nullptr) a.labels_out[b] = a.clip_labels[c];
-    if (a.meta_out != nullptr) {
-      int32_t* m = a.meta_out + (int64_t)b * 4;
-      m[0] = c;
-      m[1] = (int32_t)centre;
-      m[2] = win;
-      m[3] = (int32_t)__float_as_uint(g);
-    }
-  }
-
-  stft_frame_fft(x, tw, a.waves + w0, L, centre - a.n_fft / 2, a.n_fft, a.log2n, win, (double)g, tid);
+  stft_frame_fft(x, tw, a.waves + s.w0, s.L, centre - a.n_fft / 2, a.n_fft, a.log2n, s.win, (double)s.g, tid);
 
   // 1. the energy term of every source bin, over the dead twiddles
-  const double inv = 1.0 / (double)(a.norm_mode == 0 ? a.n_fft : win);
-  const int nb = a.n_fft / 2 + 1;
-  double* p = reinterpret_cast<double*>(tw);            // [n_fft] doubles of room, nb used
-  for (int k = tid; k < nb; k += 256) {
-    const double2 v = x[k];
-    const float re = (float)(v.x * inv), im = (float)(v.y * inv);   // stft_logmag_bin's magnitude
-    const double mag = (double)sqrtf(re * re + im * im);
-    p[k] = a.power == 1 ? mag : mag * mag;
-  }
-  __syncthreads();
+  const double* p = bands_energy_terms(a, x, tw, s.win, tid);
 
   // 2. + 3. four lanes a band; the trip count is uniform, so every lane reaches the shuffles
   const int q = tid & 3;
@@ -127,19 +58,7 @@ __global__ __launch_bounds__(256) void k_frame_points_bands(const BandsJob a) {
   const float t = a.tarr != nullptr ? a.tarr[j] : 0.f;
   for (int m0 = 0; m0 < a.n_bands; m0 += 64) {
     const int m = m0 + (tid >> 2);
-    double e = 0.0;
-    if (m < a.n_bands) {
-      int64_t o0 = a.band_off[m], o1 = a.band_off[m + 1];
-      o0 = o0 < 0 ? 0 : (o0 > a.nnz ? a.nnz : o0);
-      o1 = o1 < o0 ? o0 : (o1 > a.nnz ? a.nnz : o1);
-      const int64_t blo = a.band_lo[m];
-      const int64_t i0 = blo < 0 ? -blo : 0;                        // first term whose bin is >= 0
-      const int64_t i1 = (o1 - o0) < (nb - blo) ? (o1 - o0) : (nb - blo);   // one past the last, bin < nb
-      const float* w = a.weights + o0;
-      for (int64_t ii = i0 + q; ii < i1; ii += 4) e = fma((double)w[ii], p[blo + ii], e);
-    }
-    e += __shfl_xor(e, 1);              // s0 + s1 | s2 + s3: the same bits in both lanes of a pair
-    e += __shfl_xor(e, 2);              // (s0 + s1) + (s2 + s3)
+    const double e = bands_sum(a, p, m, q);
     if (q == 0 && m < a.n_bands) {
       const float v = logf(a.amin + (float)e);
       if (a.tarr == nullptr) {

@@ -460,6 +460,14 @@ class ESC_wave_pc(Dataset):
            ``drop_nyquist=True`` it raises ``ValueError`` (those live in other launches, or cut the bins the
            bank is defined over: out of scope).  ``with_bands(bank_or_None)`` gives a view on the same
            resident waveforms with another bank (None: the grid dataset, bit for bit)
+    pcen   None: the band value above, log(amin + E).  A ``pca_hip.Pcen`` (needs ``bands``): per-channel energy
+           normalisation in its place - each band's energy divided by a smoothed version of itself over
+           ``pcen.context`` frames before the set and the set's own, then a root (``librosa.pcen``'s formula,
+           parity by formula and unpinned) - one pca_frame_points_pcen launch per batch.  The smoother's
+           coefficient follows from ``pcen.time_constant``, ``fs`` and ``hop``.  Shapes, axes, labels, meta and
+           the draws are those of the band dataset.  A representation like ``bands``: ``plain()`` keeps it,
+           ``with_pcen(None)`` is the band dataset bit for bit, the refusals of ``bands`` carry over, and
+           ``pcen`` without ``bands`` raises ``ValueError``
     """
     _ntemp = 1
 
@@ -467,13 +475,14 @@ class ESC_wave_pc(Dataset):
                  win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
                  mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None,
                  freq_masks=0, freq_mask_width=0, time_masks=0, time_mask_width=0, mask_mode="drop",
-                 reassign=None, bands=None):
+                 reassign=None, bands=None, pcen=None):
         self._setup(clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                     device)
         self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db, mix_targets, mix_labels)
         self._setup_mask(freq_masks, freq_mask_width, time_masks, time_mask_width, mask_mode)
         self._setup_reassign(reassign)
         self._setup_bands(bands)
+        self._setup_pcen(pcen)
 
     def _setup(self, clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                device):
@@ -487,6 +496,7 @@ class ESC_wave_pc(Dataset):
         self.farr = np.linspace(0, fs / 2, self.F) / fs
         self._grid = (self.F, self.farr, bool(drop_nyquist))   # what with_bands(None) puts back
         self.bands = None
+        self.pcen = None
         self.tarr = None
         self.jitter, self.gain_db = int(jitter), float(gain_db)
         self.win_lengths = (self.n_fft,) if win_lengths is None else tuple(int(w) for w in win_lengths)
@@ -612,9 +622,30 @@ class ESC_wave_pc(Dataset):
 
     def with_bands(self, bands):
         """A view on the same resident waveforms with another filter bank (None: the grid dataset, bit for
-        bit); everything else, the augmentations and the draw counter's value included, is kept."""
+        bit); everything else, the augmentations and the draw counter's value included, is kept.  ``pcen``
+        is kept with a bank and leaves with it."""
         v = copy.copy(self)
         v._setup_bands(bands)
+        v._setup_pcen(self.pcen if bands is not None else None)
+        return v
+
+    def _setup_pcen(self, pcen):
+        """``pcen``: None or a ``pca_hip.Pcen``; checked here, on the host."""
+        self.pcen = None
+        if pcen is None:
+            return
+        if not isinstance(pcen, pca_hip.Pcen):
+            raise TypeError(f"pcen is a pca_hip.Pcen or None, got {type(pcen).__name__}")
+        if self.bands is None:
+            raise ValueError("pcen needs bands (a pca_hip.FilterBank): PCEN on grid sets without a bank is out "
+                             "of scope")
+        self.pcen = pcen
+
+    def with_pcen(self, pcen):
+        """A view on the same resident waveforms with another ``pcen`` (None: the band dataset, bit for bit);
+        everything else, the bank, the augmentations and the draw counter's value included, is kept."""
+        v = copy.copy(self)
+        v._setup_pcen(pcen)
         return v
 
     def _bands_farr(self, dev):
@@ -762,6 +793,15 @@ class ESC_wave_pc(Dataset):
                 draw_dev=draw_dev, want_meta=want_meta, want_samples=want_samples, **mix, **mask)
         if want_samples:
             raise ValueError("want_samples needs speeds or the mix on (pca_hip.frame_points_ex)")
+        if self.pcen is not None:
+            return pca_hip.frame_points_pcen(
+                waves, woff, soff, idx, self.n_fft, self.hop, self.bands, self._bands_farr(waves.device), t32,
+                self._ntemp, pcen=self.pcen, fs=self.fs, max_len=self._max_len, min_len=self._min_len,
+                clip_labels=lab, jitter=self.jitter, gain_db=self.gain_db,
+                win_lengths=self._win_dev(waves.device),
+                norm_mode=pca_hip.NORM_WIN if self.norm == "win" else pca_hip.NORM_NFFT,
+                seed=self.seed, draw=self._draw, out=out, labels_out=labels_out, draw_dev=draw_dev,
+                want_meta=want_meta)
         if self.bands is not None:
             return pca_hip.frame_points_bands(
                 waves, woff, soff, idx, self.n_fft, self.hop, self.bands, self._bands_farr(waves.device), t32,
@@ -811,7 +851,7 @@ class ESC_wave_pc_temp(ESC_wave_pc):
                  win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
                  mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None,
                  freq_masks=0, freq_mask_width=0, time_masks=0, time_mask_width=0, mask_mode="drop",
-                 reassign=None, bands=None):
+                 reassign=None, bands=None, pcen=None):
         self._ntemp = int(Ntemp)
         assert self._ntemp >= 1
         self._setup(clips, y, fs, n_fft, hop, True, jitter, gain_db, win_lengths, norm, seed, device)
@@ -820,6 +860,7 @@ class ESC_wave_pc_temp(ESC_wave_pc):
         self.tarr = np.linspace(0, (self.hop / fs) * self._ntemp, self._ntemp)
         self._setup_reassign(reassign)
         self._setup_bands(bands)
+        self._setup_pcen(pcen)
 
 
 def wave_span_offsets(lengths, span: int) -> list:

@@ -39,6 +39,8 @@ The other set-model experiments run here at batch scale too:
   scored with all levels and with subsets of them, one pass per subset; no reference counterpart;
 * ``band_sweep``: log-mel / filter-bank point sets (``pca_hip.frame_points_bands``) at several band counts,
   one pass per bank over one resident corpus; no reference counterpart;
+* ``pcen_sweep``: band point sets with per-channel energy normalisation (``pca_hip.frame_points_pcen``) for
+  several ``Pcen`` specs beside the log-band column, one pass each; no reference counterpart;
 * ``reframe_sweep_temporal``: the (Fs, N) re-framing of the 3ST, Code/pc_temp3d_eval.py:56-107.
 * ``clip_accuracy``: the clip-level scores the datasets' literature reports (majority vote and mean
   log-probability over a clip's frames or chunks, ``pca_hip.clip_aggregate``) next to the frame score;
@@ -85,7 +87,7 @@ from pca_hip.trainer import STEngine, st_config
 
 __all__ = ["reframe_sweep", "framewise_dataset", "default_list_K", "sweep_draw", "subsample_sweep",
            "importance_sweep", "attention_sweep", "peak_sweep", "most_peaks", "reassign_sweep", "multires_sweep",
-           "band_sweep",
+           "band_sweep", "pcen_sweep",
            "default_level_subsets", "chunk_plan",
            "temporal_axes", "temporal_dataset", "reframe_sweep_temporal", "baseline_subsample_sweep", "baseline_frames",
            "baseline_chunks", "baseline_reframe_sweep", "baseline_reframe_sweep_temporal",
@@ -738,6 +740,47 @@ def band_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], fs: 
         data[name] = [_dataset_accuracy(model, view, None, din, batch_size, mode, sets_per_call), 0]
     out = {"data": data, "list_banks": [name for name, _ in named],
            "banks": [bank.summary() for _, bank in named]}
+    _write_json(out, json_file)
+    return out
+
+
+@torch.no_grad()
+def pcen_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float, n_fft: int, bank, specs,
+               Ntemp: Optional[int] = None, batch_size: int = 8, json_file: Optional[str] = None,
+               mode: int = _lib.MODE_F32, sets_per_call: Optional[int] = None, hop: Optional[int] = None,
+               norm: str = "n_fft") -> Dict:
+    """Accuracy of ``model`` on band point sets of one ``bank`` whose value column is the log of the band
+    energy (the first column, ``"log"``) and then per-channel energy normalisation for every ``pca_hip.Pcen``
+    of ``specs`` (``pca_hip.frame_points_pcen``).  **No reference counterpart**.
+
+    ``clips`` / ``labels`` / ``fs`` / ``n_fft`` [/ ``hop`` / ``norm``] / ``Ntemp`` as ``band_sweep`` takes
+    them; ``specs``: a dict name -> ``Pcen``, or a list of ``Pcen`` (named ``"pcen0"``, ``"pcen1"``, ...); a
+    ``None`` among them is the log-band dataset again.  The corpus is resident once; every column is one
+    ``_dataset_accuracy`` pass over a ``with_pcen`` view of it, one host read each.
+
+    Returns (and, with ``json_file``, writes) ``{"data": {name: [acc, 0]}, "list_specs": [names],
+    "specs": [None or the spec's fields, ...], "bank": {...}}``, ``"log"`` first, then the specs in the
+    order given."""
+    named = list(specs.items()) if isinstance(specs, dict) else [(f"pcen{i}", p) for i, p in enumerate(specs)]
+    named = [("log", None)] + [(str(k), p) for k, p in named]
+    if len(named) < 2:
+        raise ValueError("pcen_sweep: no specs")
+    if len({k for k, _ in named}) != len(named):
+        raise ValueError("pcen_sweep: two columns of one name ('log' is the log-band column)")
+    for k, p in named:
+        if p is not None and not isinstance(p, pca_hip.Pcen):
+            raise TypeError(f"pcen_sweep: spec {k!r} is a {type(p).__name__}, expected a pca_hip.Pcen or None")
+    dev = _model_device(model)
+    if Ntemp is None:
+        ds = ESC_wave_pc(clips, labels, fs, n_fft, hop=hop, norm=norm, device=dev, bands=bank)   # ValueError
+    else:
+        ds = ESC_wave_pc_temp(clips, labels, fs, n_fft, Ntemp, hop=hop, norm=norm, device=dev, bands=bank)
+    din = 2 if Ntemp is None else 3
+    data = {}
+    for name, spec in named:
+        data[name] = [_dataset_accuracy(model, ds.with_pcen(spec), None, din, batch_size, mode, sets_per_call), 0]
+    out = {"data": data, "list_specs": [name for name, _ in named],
+           "specs": [None if p is None else p.summary() for _, p in named], "bank": bank.summary()}
     _write_json(out, json_file)
     return out
 

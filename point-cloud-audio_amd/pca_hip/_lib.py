@@ -80,6 +80,11 @@ class PcaFrameBands(C.Structure):
                 ("amin", C.c_float)]
 
 
+class PcaPcen(C.Structure):
+    _fields_ = [("context", C.c_int32), ("s", C.c_float), ("gain", C.c_float), ("bias", C.c_float),
+                ("r", C.c_float), ("eps", C.c_float), ("scale", C.c_float)]
+
+
 FRAME_MAX_SPEEDS = 8
 
 
@@ -205,6 +210,10 @@ SIGNATURES = {
                                          C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp,
                                          C.POINTER(PcaFrameAug), C.POINTER(PcaFrameBands), c_fp, c_i64p,
                                          c_vp, c_vp]),
+    "pca_frame_points_pcen": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p, c_i64p,
+                                        C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp,
+                                        C.POINTER(PcaFrameAug), C.POINTER(PcaFrameBands), C.POINTER(PcaPcen),
+                                        c_vp, C.c_int64, c_vp, c_fp, c_i64p, c_vp, c_vp]),
     "pca_frame_points_reassigned": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p,
                                               c_i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp,
                                               c_fp, C.POINTER(PcaFrameAug), C.POINTER(PcaReassignSpec),

@@ -1102,6 +1102,168 @@ def frame_points_bands(waves: torch.Tensor, wave_off: torch.Tensor, set_off: tor
     return (out, labels_out, meta) if want_meta else (out, labels_out)
 
 
+class Pcen:
+    """Per-channel energy normalisation of band energies, for ``frame_points_pcen`` and the datasets'
+    ``pcen=``: ``librosa.pcen``'s parameters (Wang et al. 2017; Lostanlen et al. 2019) as an immutable spec.
+
+        M[0] = x[0];  M[u] = (1 - s) M[u-1] + s x[u];   y = (bias + x / (eps + M)^gain)^power - bias^power
+
+    with x = ``scale`` * the band energy.  ``context`` frames of history before each set feed the smoother
+    (its truncation error falls as (1 - s)^context; every frame of context is one more frame transform per
+    set).  ``s`` is given, or follows from ``time_constant`` (seconds) by ``coefficient(fs, hop)``.  Parity
+    with librosa is by formula and not pinned by a test: it is not a dependency.  ``ValueError`` outside
+    context [0, 255], s (0, 1], gain [0, 4], bias [0, 1e6], power (0, 1], eps > 0, scale > 0,
+    time_constant > 0 (the launch's rules)."""
+
+    __slots__ = ("context", "time_constant", "gain", "bias", "power", "eps", "scale", "s")
+
+    def __init__(self, context: int = 32, time_constant: float = 0.4, gain: float = 0.98, bias: float = 2.0,
+                 power: float = 0.5, eps: float = 1e-6, scale: float = 1.0, s: Optional[float] = None):
+        v = dict(context=int(context), time_constant=float(time_constant), gain=float(gain), bias=float(bias),
+                 power=float(power), eps=float(eps), scale=float(scale), s=None if s is None else float(s))
+
+        def fin(a):                       # finite and > 0 as the fp32 the launch gets
+            with np.errstate(over="ignore"):
+                return 0.0 < float(np.float32(a)) < float("inf")
+
+        if not 0 <= v["context"] <= 255:
+            raise ValueError(f"Pcen: context {context} outside [0, 255]")
+        if v["s"] is None and not 0.0 < v["time_constant"] < float("inf"):
+            raise ValueError(f"Pcen: time_constant {time_constant} must be finite and > 0")
+        if v["s"] is not None and not 0.0 < float(np.float32(v["s"])) <= 1.0:
+            raise ValueError(f"Pcen: s {s} outside (0, 1]")
+        if not 0.0 <= v["gain"] <= 4.0:
+            raise ValueError(f"Pcen: gain {gain} outside [0, 4]")
+        if not 0.0 <= v["bias"] <= 1e6:
+            raise ValueError(f"Pcen: bias {bias} outside [0, 1e6]")
+        if not 0.0 < float(np.float32(v["power"])) <= 1.0:
+            raise ValueError(f"Pcen: power {power} outside (0, 1]")
+        if not fin(v["eps"]):
+            raise ValueError(f"Pcen: eps {eps} must be finite and > 0 (in fp32)")
+        if not fin(v["scale"]):
+            raise ValueError(f"Pcen: scale {scale} must be finite and > 0 (in fp32)")
+        for k, x in v.items():
+            object.__setattr__(self, k, x)
+
+    def __setattr__(self, k, x):
+        raise AttributeError("Pcen is immutable")
+
+    def __repr__(self):
+        return "Pcen(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+    def _key(self):
+        return tuple(getattr(self, k) for k in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, Pcen) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def coefficient(self, fs: float, hop: int) -> float:
+        """The smoother's coefficient: ``s`` when given, else librosa's (sqrt(1 + 4 t^2) - 1) / (2 t^2) with
+        t = time_constant * fs / hop frames."""
+        if self.s is not None:
+            return self.s
+        t = self.time_constant * float(fs) / float(hop)
+        return (math.sqrt(1.0 + 4.0 * t * t) - 1.0) / (2.0 * t * t)
+
+    def summary(self) -> dict:
+        return {k: getattr(self, k) for k in self.__slots__}
+
+    def struct(self, fs: float, hop: int) -> "_lib.PcaPcen":
+        return _lib.PcaPcen(self.context, self.coefficient(fs, hop), self.gain, self.bias, self.power, self.eps,
+                            self.scale)
+
+
+_PCEN_WS = {}     # (device, B, T, n_bands) -> (energy float64 [B, T, n_bands], tickets int32 [B], all zero)
+
+
+def pcen_workspace(device, B: int, T: int, n_bands: int):
+    """The launch's workspace, kept per (device, B, T, n_bands): the tickets are zeroed once, here - every
+    launch leaves them zero.  Launches that share it run one after the other (one stream); callers that
+    overlap launches pass workspaces of their own.  Under stream capture nothing is kept: a first use
+    inside a capture gets tensors of the graph's own pool, zeroed by a node of that graph."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (device, int(B), int(T), int(n_bands))
+    held = _PCEN_WS.get(key)
+    if held is None:
+        held = (torch.empty((B, T, n_bands), dtype=torch.float64, device=device),
+                torch.zeros(B, dtype=torch.int32, device=device))
+        if not torch.cuda.is_current_stream_capturing():
+            _PCEN_WS[key] = held
+    return held
+
+
+def frame_points_pcen(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.Tensor,
+                      idx: torch.Tensor, n_fft: int, hop: int, bank: FilterBank, farr: torch.Tensor,
+                      tarr: Optional[torch.Tensor] = None, Nt: int = 1, *, pcen: Pcen, fs: float,
+                      max_len: int, min_len: int, clip_labels: Optional[torch.Tensor] = None,
+                      jitter: int = 0, gain_db: float = 0.0, win_lengths: Optional[torch.Tensor] = None,
+                      norm_mode: int = NORM_NFFT, seed: int = 0, draw: int = 0,
+                      out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None,
+                      draw_dev: Optional[torch.Tensor] = None, want_meta: bool = False,
+                      workspace: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """``frame_points_bands`` with per-channel energy normalisation in place of the log
+    (pca_frame_points_pcen): every argument of ``frame_points_bands`` with the same meaning - the clip,
+    shift, gain, window, labels and meta of slot b are that launch's bits - plus ``pcen``, a ``Pcen``, and
+    ``fs`` (``Pcen.coefficient(fs, hop)`` turns its time constant into the smoother's coefficient).  The
+    value of band m in frame j is (bias + x / (eps + M)^gain)^power - bias^power with x = scale * the band
+    launch's fp64 band sum and M its smoothed history over ``pcen.context`` frames before the set and the
+    set's own; ``bank.amin`` is not used.  One launch over context + Nt frames per slot.
+
+    ``workspace``: (energy float64 with >= B * (context + Nt) * n_bands elements, tickets int32 [>= B], ZERO)
+    on the device, for callers that overlap launches; None: ``pcen_workspace``'s, kept per shape.
+    Returns (points [B, Nt * n_bands, 2 or 3] float32, labels or None [, meta int32 [B, 4]])."""
+    if not isinstance(bank, FilterBank):
+        raise TypeError(f"frame_points_pcen: bank is a {type(bank).__name__}, expected a FilterBank")
+    if not isinstance(pcen, Pcen):
+        raise TypeError(f"frame_points_pcen: pcen is a {type(pcen).__name__}, expected a Pcen")
+    if bank.n_src != int(n_fft) // 2 + 1:
+        raise ValueError(f"frame_points_pcen: the bank covers {bank.n_src} bins, n_fft {n_fft} has "
+                         f"{int(n_fft) // 2 + 1}")
+    _need_cuda(waves, wave_off, set_off, idx, farr)
+    assert waves.dtype == torch.float32 and waves.is_contiguous() and farr.dtype == torch.float32
+    assert wave_off.dtype == set_off.dtype == idx.dtype == torch.int64
+    assert wave_off.numel() == set_off.numel() >= 2 and farr.numel() >= bank.n_bands
+    din = 2
+    if tarr is not None:
+        _need_cuda(tarr)
+        assert tarr.dtype == torch.float32 and tarr.numel() >= Nt
+        din = 3
+    B = idx.numel()
+    T = pcen.context + int(Nt)
+    with torch.cuda.device(waves.device):
+        if win_lengths is None:
+            win_lengths = torch.tensor([n_fft], dtype=torch.int32, device=waves.device)
+        assert win_lengths.is_cuda and win_lengths.dtype == torch.int32
+        if out is None:
+            out = torch.empty((B, Nt * bank.n_bands, din), dtype=torch.float32, device=waves.device)
+        assert out.is_contiguous() and out.numel() == B * Nt * bank.n_bands * din
+        if clip_labels is not None and labels_out is None:
+            labels_out = torch.empty(B, dtype=torch.int64, device=waves.device)
+        meta = torch.empty((B, 4), dtype=torch.int32, device=waves.device) if want_meta else None
+        energy, tickets = pcen_workspace(waves.device, B, T, bank.n_bands) if workspace is None else workspace
+        _need_cuda(energy, tickets)
+        assert energy.dtype == torch.float64 and energy.is_contiguous()
+        assert tickets.dtype == torch.int32 and tickets.is_contiguous() and tickets.numel() >= B
+        aug = _lib.PcaFrameAug(int(jitter), float(gain_db), win_lengths.data_ptr(),
+                               win_lengths.numel(), int(norm_mode), int(seed) & (2 ** 64 - 1),
+                               int(draw) & (2 ** 64 - 1), _draw_ptr(draw_dev))
+        bands = bank.on(waves.device)
+        spec = pcen.struct(fs, hop)
+        check(lib().pca_frame_points_pcen(_ptr(waves), _ptr(wave_off), _ptr(set_off),
+                                          wave_off.numel() - 1, int(max_len), int(min_len),
+                                          _ptr(clip_labels), _ptr(idx), B, int(n_fft), int(hop), int(Nt),
+                                          _ptr(farr), _ptr(tarr), C.byref(aug), C.byref(bands),
+                                          C.byref(spec), _ptr(energy), energy.numel(), _ptr(tickets),
+                                          _ptr(out), _ptr(labels_out), _ptr(meta), _stream(waves)),
+              "pca_frame_points_pcen")
+    return (out, labels_out, meta) if want_meta else (out, labels_out)
+
+
 REASSIGN_AXES = {"f": 1, "t": 2, "ft": 3, "tf": 3}
 
 
