@@ -484,6 +484,55 @@ int pca_frame_points_pcen(const float* waves, const int64_t* wave_off, const int
                           double* energy_ws, int64_t energy_ws_elems, int32_t* tickets, float* out,
                           int64_t* labels_out, int32_t* meta_out, void* stream);
 
+/* Which differences a delta set carries next to its value (pca_frame_points_delta). */
+typedef struct PcaDelta {
+  int32_t axes;       /* 1: along time; 2: along frequency; 3: time, then frequency */
+  int32_t width;      /* W, the regression's half width, in [1, 4] */
+} PcaDelta;
+
+/* pca_frame_points (bands NULL) or pca_frame_points_bands (bands given) with regression deltas of the value
+ * column as further point columns: how a point's value compares with the frames around it and with the rows
+ * above and below it, which a set model has no neighbourhood to see.
+ * replaces: nothing - no reference counterpart; what a caller otherwise builds from a launch over a longer span
+ *           plus slicing, padding and a re-pack in torch.
+ * Every argument up to `aug` is pca_frame_points', `bands` is pca_frame_points_bands' or NULL: for batch slot b
+ * the clip, shift delta, gain g, window, labels_out and meta_out [B, 4] are that launch's bits for the same
+ * arguments (the same stream, draw numbers 0, 1, 2, no new draws).  A frame has F rows: n_bins (bands NULL) or
+ * bands->n_bands (n_bins is then checked and not used).
+ * With W = delta->width, Wt = W when axes has bit 0 (time) and 0 otherwise, the launch looks at T = Nt + 2 Wt
+ * frames u = 0 .. T-1, centred at clamp(first + (u - Wt) * hop, 0, L) with first = s_set * Nt * hop + delta as
+ * in those launches: context before the start of a clip repeats the frame at sample 0, context past its end the
+ * frame at sample L.  v[u][m] is the fp32 value those launches write for row m of frame u: log(1e-8 + |stft|/norm)
+ * (bands NULL) or logf(amin + (float)E) with E that launch's fp64 band sum.  With D = 2 (1 + 4 + .. + W^2) =
+ * 2, 10, 28, 60 for W = 1 .. 4, for frame j = 0 .. Nt-1 of the set, in fp64 with no fused multiply-add:
+ *   dt[j][m] = (float)((sum_{n = 1..W} n * ((double)v[Wt+j+n][m] - (double)v[Wt+j-n][m])) / D)
+ *   df[j][m] = (float)((sum_{n = 1..W} n * ((double)v[Wt+j][min(m+n, F-1)] - (double)v[Wt+j][max(m-n, 0)])) / D)
+ * the accumulator starting at 0.0, n ascending, every step a subtraction, a multiplication by (double)n and an
+ * addition, then one division by (double)D and one rounding to fp32: the regression delta, rows replicated at
+ * the edges of the frequency axis.  Every step is a basic IEEE operation, so a float64 restatement on the host
+ * gives the same bits.
+ * Point j * F + m of out[B, Nt*F, din] = (farr[m], [tarr[j],] v[Wt+j][m], then dt (axes bit 0), then df (axes
+ * bit 1)); din = (tarr ? 3 : 2) + the number of axes, at most 4: a set with tarr takes one axis.
+ * One launch, grid (T, B), 256 threads, the frame launch's LDS.  Every workgroup stores the F values of its
+ * frame to value_ws [B][T][F] (device fp32, value_ws_elems floats, contents undefined on entry; on exit rows
+ * Wt .. Wt+Nt-1 of a slot are its value column) with agent-scope write-through stores (the release), drains
+ * them and then draws a ticket: a fetch_add on tickets[b] (device int32[B], ZERO on entry).  The workgroup that
+ * draws T - 1 is the slot's last; after an agent-scope acquire it alone forms the deltas (one lane per output
+ * point), writes the Nt * F rows and stores 0 back to tickets[b], so the tickets are zero again when the
+ * launch ends (a captured launch replays without a memset).  No workgroup waits for another - one that is not
+ * last exits - so the launch cannot hang, whatever the grid size or the other work on the device; which
+ * workgroup is last does not affect the result: the same arguments give the same bits.  Two launches that
+ * share value_ws or tickets must not overlap in time.
+ * PCA_EINVAL (message "frame_points_delta: ...") before any HIP call for: a null pointer; axes outside [1, 3];
+ * width outside [1, 4]; din > 4; B * T * F > value_ws_elems; B > 65535; every case pca_frame_points rejects
+ * and, with bands, every case pca_frame_points_bands rejects. */
+int pca_frame_points_delta(const float* waves, const int64_t* wave_off, const int64_t* set_off, int n_clips,
+                           int64_t max_len, int64_t min_len, const int64_t* clip_labels, const int64_t* idx,
+                           int B, int n_fft, int hop, int n_bins, int Nt, const float* farr, const float* tarr,
+                           const PcaFrameAug* aug, const PcaFrameBands* bands, const PcaDelta* delta,
+                           float* value_ws, int64_t value_ws_elems, int32_t* tickets, float* out,
+                           int64_t* labels_out, int32_t* meta_out, void* stream);
+
 /* Which points of a framed batch move to where their energy lies, and how far (pca_frame_points_reassigned). */
 typedef struct PcaReassignSpec {
   int32_t axes;       /* bit 0: frequency, bit 1: time; 1..3.  Bit 1 needs tarr and Nt >= 2 */
@@ -1062,7 +1111,7 @@ size_t pca_st_ws_bytes(const pca_st_config* c, int training);
  * identical bits - logits, loss, statistics and every gradient, launched eagerly or replayed from a captured
  * graph - so that a run resumed from a checkpoint equals the uninterrupted one; 0 when it does not guarantee
  * that (the call may still happen to repeat itself).  has_lengths: the calls pass `lengths`.  1 today: in
- * PCA_MODE_BF16, the fused d = 128 plans (dense sets, PCA_WGRAD_SLABS not 0), the fused d = 256 plans (dense
+ * PCA_MODE_BF16, the fused d = 128 plans (dense sets, din <= 3, PCA_WGRAD_SLABS not 0), the fused d = 256 plans (dense
  * sets) and the d = 64 chain with the fused attention core (head dims <= 16, din = 64 or <= 4) up to B = 256,
  * every buffer 16-byte aligned.  PCA_MODE_F32 and every other width: 0. */
 int pca_st_step_reproducible(const pca_st_config* c, int has_lengths);

@@ -185,7 +185,9 @@ inline StepPlan plan(const pca_st_config& c, bool training, const int32_t* lengt
 // Whether two identical training calls of this configuration give identical bits - logits, loss, statistics and
 // every gradient, launched eagerly or replayed from a graph.  Conservative: true only in PCA_MODE_BF16 and only
 // for the plans whose every reduction runs in a fixed order,
-//   d = 128, all blocks on the fused kernels, the tail's reductions as slabs (TailForm::slabs), dense sets;
+//   d = 128, all blocks on the fused kernels, the tail's reductions as slabs (TailForm::slabs), dense sets,
+//          din <= 3: at din 4 layer 1's fc_q gradient leaves the chain kernel for k_wgrad_small's fp32 atomics
+//          (mab1_bwd_bf16.hip; measured on delta sets: a captured and an eager run part ways);
 //   d = 256, all blocks on the fused kernels, dense sets;
 //   d = 64: the bf16-operand chain with every block's attention on the fused core and every
 //          weight gradient on wgrad64 (slabs + fixed-order sums); the sum over sets of a shared query's
@@ -196,7 +198,7 @@ inline bool step_reproducible(const pca_st_config& c, bool has_lengths) {
   static const int32_t some_lengths = 1;      // (plan() and block_path() look at the pointer only)
   if (c.mode != PCA_MODE_BF16 || c.k != 1) return false;      // (the fp8 mode: nobody has asserted it yet)
   const StepPlan pl = plan(c, true, has_lengths ? &some_lengths : nullptr);
-  if (pl.isab128[0] && pl.isab128[1] && pl.pma_head) return pl.tail.slabs && !has_lengths;
+  if (pl.isab128[0] && pl.isab128[1] && pl.pma_head) return pl.tail.slabs && !has_lengths && c.din <= 3;
   if (pl.isab256[0] && pl.isab256[1] && pl.pma256) return !has_lengths;
   if (c.d != 64 || c.B > 256 || !(c.din == 64 || (c.din >= 1 && c.din <= 4)))
     return false;

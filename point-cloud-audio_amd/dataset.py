@@ -468,6 +468,17 @@ class ESC_wave_pc(Dataset):
            the draws are those of the band dataset.  A representation like ``bands``: ``plain()`` keeps it,
            ``with_pcen(None)`` is the band dataset bit for bit, the refusals of ``bands`` carry over, and
            ``pcen`` without ``bands`` raises ``ValueError``
+    deltas None: rows (f, [t,] value).  A ``pca_hip.Deltas(axes, width)``: regression deltas of the value column
+           ride along as further point columns - dt, how the value moves over ``width`` frames before and after
+           (the context frames are cut from the clip around the set; outside the clip its end frames repeat),
+           and / or df, how it moves over ``width`` rows below and above (edge rows replicated) - rows
+           (f, [t,] value, deltas in the order of ``axes``), one pca_frame_points_delta launch per batch.
+           ``din`` becomes 2 or 3 plus the number of axes and is at most 4: a 3-D set takes one axis, a 2-D set
+           one or two.  ``F``, ``farr``, ``num_points``, labels, meta and the draws are those of the underlying
+           grid or band dataset.  A representation: ``plain()`` keeps it, ``stochastic`` ignores it,
+           ``with_deltas(None)`` is the underlying dataset bit for bit.  It composes with jitter, gain_db,
+           win_lengths, norm, ``drop_nyquist`` and ``bands``; with speeds, the mix, ``mix_targets``, the masks,
+           ``reassign`` or ``pcen`` it raises ``ValueError`` (out of scope), and ``PeakPoints`` refuses it
     """
     _ntemp = 1
 
@@ -475,7 +486,7 @@ class ESC_wave_pc(Dataset):
                  win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
                  mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None,
                  freq_masks=0, freq_mask_width=0, time_masks=0, time_mask_width=0, mask_mode="drop",
-                 reassign=None, bands=None, pcen=None):
+                 reassign=None, bands=None, pcen=None, deltas=None):
         self._setup(clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                     device)
         self._setup_ex(speeds, mix_clips, mix_prob, mix_snr_db, mix_targets, mix_labels)
@@ -483,6 +494,7 @@ class ESC_wave_pc(Dataset):
         self._setup_reassign(reassign)
         self._setup_bands(bands)
         self._setup_pcen(pcen)
+        self._setup_deltas(deltas)
 
     def _setup(self, clips, y, fs, n_fft, hop, drop_nyquist, jitter, gain_db, win_lengths, norm, seed,
                device):
@@ -497,6 +509,7 @@ class ESC_wave_pc(Dataset):
         self._grid = (self.F, self.farr, bool(drop_nyquist))   # what with_bands(None) puts back
         self.bands = None
         self.pcen = None
+        self.deltas = None
         self.tarr = None
         self.jitter, self.gain_db = int(jitter), float(gain_db)
         self.win_lengths = (self.n_fft,) if win_lengths is None else tuple(int(w) for w in win_lengths)
@@ -591,6 +604,9 @@ class ESC_wave_pc(Dataset):
         if self.bands is not None and reassign not in (None, False):
             raise ValueError("reassign does not combine with bands: reassignment moves FFT bins, a band "
                              "set has none (pca_frame_points_reassigned / pca_frame_points_bands)")
+        if self.deltas is not None and reassign not in (None, False):
+            raise ValueError("reassign does not combine with deltas: a delta differences grid neighbours, "
+                             "reassigned points have left the grid - out of scope")
         v = copy.copy(self)
         v._setup_reassign(reassign)
         return v
@@ -644,9 +660,44 @@ class ESC_wave_pc(Dataset):
     def with_pcen(self, pcen):
         """A view on the same resident waveforms with another ``pcen`` (None: the band dataset, bit for bit);
         everything else, the bank, the augmentations and the draw counter's value included, is kept."""
+        if self.deltas is not None and pcen is not None:
+            raise ValueError("pcen does not combine with deltas: each is a ticketed launch of its own "
+                             "(pca_frame_points_pcen / pca_frame_points_delta) - out of scope")
         v = copy.copy(self)
         v._setup_pcen(pcen)
         return v
+
+    def _setup_deltas(self, deltas):
+        """``deltas``: None or a ``pca_hip.Deltas``; checked here, on the host."""
+        self.deltas = None
+        if deltas is None:
+            return
+        if not isinstance(deltas, pca_hip.Deltas):
+            raise TypeError(f"deltas is a pca_hip.Deltas or None, got {type(deltas).__name__}")
+        if (self._speed_on or self._mix_on or self.mix_targets or self._mask_on or self.reassign is not None
+                or self.pcen is not None):
+            raise ValueError("deltas do not combine with speeds, the mix, mix_targets, the masks, reassign or "
+                             "pcen: those live in other launches (pca_frame_points_ex, "
+                             "pca_frame_points_reassigned, pca_frame_points_pcen), the deltas in "
+                             "pca_frame_points_delta - out of scope")
+        din = (2 if self.tarr is None else 3) + deltas.count
+        if din > 4:
+            raise ValueError(f"deltas {deltas.axes!r} on a 3-D dataset give din = {din}: a point has at most 4 "
+                             f"columns, a 3-D set takes one axis")
+        self.deltas = deltas
+
+    def with_deltas(self, deltas):
+        """A view on the same resident waveforms with another ``deltas`` (None: the underlying grid or band
+        dataset, bit for bit); everything else, the bank, the augmentations and the draw counter's value
+        included, is kept."""
+        v = copy.copy(self)
+        v._setup_deltas(deltas)
+        return v
+
+    @property
+    def din(self) -> int:
+        """Columns of a point: 2 (f, value) or 3 (f, t, value), plus one per delta axis."""
+        return (2 if self.tarr is None else 3) + (0 if self.deltas is None else self.deltas.count)
 
     def _bands_farr(self, dev):
         """The band axis on the device, once per bank, in the store the views share."""
@@ -793,6 +844,16 @@ class ESC_wave_pc(Dataset):
                 draw_dev=draw_dev, want_meta=want_meta, want_samples=want_samples, **mix, **mask)
         if want_samples:
             raise ValueError("want_samples needs speeds or the mix on (pca_hip.frame_points_ex)")
+        if self.deltas is not None:
+            banded = self.bands is not None
+            return pca_hip.frame_points_delta(
+                waves, woff, soff, idx, self.n_fft, self.hop, self.F,
+                self._bands_farr(waves.device) if banded else f32, t32, self._ntemp, deltas=self.deltas,
+                bank=self.bands, max_len=self._max_len, min_len=self._min_len, clip_labels=lab,
+                jitter=self.jitter, gain_db=self.gain_db, win_lengths=self._win_dev(waves.device),
+                norm_mode=pca_hip.NORM_WIN if self.norm == "win" else pca_hip.NORM_NFFT,
+                seed=self.seed, draw=self._draw, out=out, labels_out=labels_out, draw_dev=draw_dev,
+                want_meta=want_meta)
         if self.pcen is not None:
             return pca_hip.frame_points_pcen(
                 waves, woff, soff, idx, self.n_fft, self.hop, self.bands, self._bands_farr(waves.device), t32,
@@ -851,7 +912,7 @@ class ESC_wave_pc_temp(ESC_wave_pc):
                  win_lengths=None, norm="n_fft", seed=0, device=None, speeds=None, mix_clips=None,
                  mix_prob=0.0, mix_snr_db=(0.0, 20.0), mix_targets=False, mix_labels=None,
                  freq_masks=0, freq_mask_width=0, time_masks=0, time_mask_width=0, mask_mode="drop",
-                 reassign=None, bands=None, pcen=None):
+                 reassign=None, bands=None, pcen=None, deltas=None):
         self._ntemp = int(Ntemp)
         assert self._ntemp >= 1
         self._setup(clips, y, fs, n_fft, hop, True, jitter, gain_db, win_lengths, norm, seed, device)
@@ -861,6 +922,7 @@ class ESC_wave_pc_temp(ESC_wave_pc):
         self._setup_reassign(reassign)
         self._setup_bands(bands)
         self._setup_pcen(pcen)
+        self._setup_deltas(deltas)
 
 
 def wave_span_offsets(lengths, span: int) -> list:
@@ -1093,6 +1155,9 @@ class PeakPoints(Dataset):
                              "peak picking reads its neighbours from one; pick peaks per level "
                              "(ESC_wave_pc / ESC_wave_pc_temp) instead")
         if isinstance(inner, ESC_wave_pc):
+            if inner.deltas is not None:
+                raise ValueError("PeakPoints: a delta dataset has din > 3 and pca_peak_points takes din 2 or 3; "
+                                 "pick peaks on with_deltas(None)")
             self.F, self.Nt, self.din = inner.F, inner._ntemp, 2 if inner.tarr is None else 3
             if inner.variable_length:
                 raise ValueError("PeakPoints: mask_mode='drop' removes points from the sets, which breaks "

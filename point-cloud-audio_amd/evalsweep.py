@@ -41,6 +41,8 @@ The other set-model experiments run here at batch scale too:
   one pass per bank over one resident corpus; no reference counterpart;
 * ``pcen_sweep``: band point sets with per-channel energy normalisation (``pca_hip.frame_points_pcen``) for
   several ``Pcen`` specs beside the log-band column, one pass each; no reference counterpart;
+* ``delta_sweep``: grid or band point sets with delta columns (``pca_hip.frame_points_delta``) at several
+  regression widths, one pass each; no reference counterpart;
 * ``reframe_sweep_temporal``: the (Fs, N) re-framing of the 3ST, Code/pc_temp3d_eval.py:56-107.
 * ``clip_accuracy``: the clip-level scores the datasets' literature reports (majority vote and mean
   log-probability over a clip's frames or chunks, ``pca_hip.clip_aggregate``) next to the frame score;
@@ -87,7 +89,7 @@ from pca_hip.trainer import STEngine, st_config
 
 __all__ = ["reframe_sweep", "framewise_dataset", "default_list_K", "sweep_draw", "subsample_sweep",
            "importance_sweep", "attention_sweep", "peak_sweep", "most_peaks", "reassign_sweep", "multires_sweep",
-           "band_sweep", "pcen_sweep",
+           "band_sweep", "pcen_sweep", "delta_sweep",
            "default_level_subsets", "chunk_plan",
            "temporal_axes", "temporal_dataset", "reframe_sweep_temporal", "baseline_subsample_sweep", "baseline_frames",
            "baseline_chunks", "baseline_reframe_sweep", "baseline_reframe_sweep_temporal",
@@ -781,6 +783,46 @@ def pcen_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], fs: 
         data[name] = [_dataset_accuracy(model, ds.with_pcen(spec), None, din, batch_size, mode, sets_per_call), 0]
     out = {"data": data, "list_specs": [name for name, _ in named],
            "specs": [None if p is None else p.summary() for _, p in named], "bank": bank.summary()}
+    _write_json(out, json_file)
+    return out
+
+
+@torch.no_grad()
+def delta_sweep(model, clips: Sequence[torch.Tensor], labels: Sequence[int], fs: float, n_fft: int, widths,
+                axes: str = "t", bank=None, Ntemp: Optional[int] = None, batch_size: int = 8,
+                json_file: Optional[str] = None, mode: int = _lib.MODE_F32,
+                sets_per_call: Optional[int] = None, hop: Optional[int] = None, norm: str = "n_fft",
+                drop_nyquist: bool = False) -> Dict:
+    """Accuracy of ``model`` on point sets with delta columns (``pca_hip.frame_points_delta``) for every
+    regression width of ``widths`` (each in 1..4) at fixed ``axes``, so every column has the model's ``din``:
+    2 (``Ntemp`` None) or 3, plus ``len(axes)``.  **No reference counterpart**.
+
+    ``clips`` / ``labels`` / ``fs`` / ``n_fft`` [/ ``hop`` / ``norm``] / ``Ntemp`` as ``band_sweep`` takes
+    them; ``bank``: a ``pca_hip.FilterBank`` for band sets, None for grid sets (``drop_nyquist`` as
+    ``ESC_wave_pc`` takes it).  The corpus is resident once; every width is one ``_dataset_accuracy`` pass over
+    a ``with_deltas`` view of it, one host read each.
+
+    Returns (and, with ``json_file``, writes) ``{"data": {name: [acc, 0]}, "list_specs": [names],
+    "specs": [the spec's fields, ...], "bank": {...} or None}``, the widths in the order given, named
+    ``"w1"``, ``"w2"``, ..."""
+    named = [(f"w{int(w)}", pca_hip.Deltas(axes, w)) for w in widths]                     # ValueError
+    if not named:
+        raise ValueError("delta_sweep: no widths")
+    if len({k for k, _ in named}) != len(named):
+        raise ValueError("delta_sweep: a width given twice")
+    dev = _model_device(model)
+    if Ntemp is None:
+        ds = ESC_wave_pc(clips, labels, fs, n_fft, hop=hop, drop_nyquist=drop_nyquist, norm=norm, device=dev,
+                         bands=bank, deltas=named[0][1])                                  # ValueError
+    else:
+        ds = ESC_wave_pc_temp(clips, labels, fs, n_fft, Ntemp, hop=hop, norm=norm, device=dev, bands=bank,
+                              deltas=named[0][1])
+    data = {}
+    for name, spec in named:
+        data[name] = [_dataset_accuracy(model, ds.with_deltas(spec), None, ds.din, batch_size, mode,
+                                        sets_per_call), 0]
+    out = {"data": data, "list_specs": [name for name, _ in named],
+           "specs": [p.summary() for _, p in named], "bank": None if bank is None else bank.summary()}
     _write_json(out, json_file)
     return out
 

@@ -85,6 +85,10 @@ class PcaPcen(C.Structure):
                 ("r", C.c_float), ("eps", C.c_float), ("scale", C.c_float)]
 
 
+class PcaDelta(C.Structure):
+    _fields_ = [("axes", C.c_int32), ("width", C.c_int32)]
+
+
 FRAME_MAX_SPEEDS = 8
 
 
@@ -214,6 +218,10 @@ SIGNATURES = {
                                         C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp,
                                         C.POINTER(PcaFrameAug), C.POINTER(PcaFrameBands), C.POINTER(PcaPcen),
                                         c_vp, C.c_int64, c_vp, c_fp, c_i64p, c_vp, c_vp]),
+    "pca_frame_points_delta": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p, c_i64p,
+                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp,
+                                         C.POINTER(PcaFrameAug), C.POINTER(PcaFrameBands), C.POINTER(PcaDelta),
+                                         c_fp, C.c_int64, c_vp, c_fp, c_i64p, c_vp, c_vp]),
     "pca_frame_points_reassigned": (C.c_int, [c_fp, c_i64p, c_i64p, C.c_int, C.c_int64, C.c_int64, c_i64p,
                                               c_i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp,
                                               c_fp, C.POINTER(PcaFrameAug), C.POINTER(PcaReassignSpec),

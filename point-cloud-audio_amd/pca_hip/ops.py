@@ -1264,6 +1264,158 @@ def frame_points_pcen(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torc
     return (out, labels_out, meta) if want_meta else (out, labels_out)
 
 
+DELTA_AXES = {"t": 1, "f": 2, "tf": 3}
+
+
+class Deltas:
+    """Regression deltas of a point set's value column as further point columns, for ``frame_points_delta``
+    and the datasets' ``deltas=``: an immutable spec.
+
+        dt[j][m] = sum_{n=1..W} n (v[j+n][m] - v[j-n][m]) / (2 sum n^2)      along the frames
+        df[j][m] = sum_{n=1..W} n (v[j][m+n] - v[j][m-n]) / (2 sum n^2)      along the rows, edges replicated
+
+    ``axes``: "t", "f" or "tf" (dt, then df); ``width``: W in 1..4.  A time delta reads ``width`` context frames
+    before and after each set (frames outside the clip repeat its end frames): ``2 * width`` more frame
+    transforms per set.  ``ValueError`` for anything else (the launch's rules)."""
+
+    __slots__ = ("axes", "width")
+
+    def __init__(self, axes: str = "t", width: int = 2):
+        if not isinstance(axes, str) or axes not in DELTA_AXES:
+            raise ValueError(f"Deltas: axes {axes!r} is not one of {sorted(DELTA_AXES)}")
+        if isinstance(width, bool) or width not in (1, 2, 3, 4):
+            raise ValueError(f"Deltas: width {width!r} outside 1..4")
+        object.__setattr__(self, "axes", axes)
+        object.__setattr__(self, "width", int(width))
+
+    def __setattr__(self, k, x):
+        raise AttributeError("Deltas is immutable")
+
+    def __repr__(self):
+        return f"Deltas(axes={self.axes!r}, width={self.width})"
+
+    def _key(self):
+        return (self.axes, self.width)
+
+    def __eq__(self, other):
+        return isinstance(other, Deltas) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    @property
+    def count(self) -> int:
+        """How many columns the spec adds to a point."""
+        return len(self.axes)
+
+    @property
+    def context(self) -> int:
+        """Context frames before, and after, each set: ``width`` with a time delta, else 0."""
+        return self.width if "t" in self.axes else 0
+
+    def summary(self) -> dict:
+        return {"axes": self.axes, "width": self.width}
+
+    def struct(self) -> "_lib.PcaDelta":
+        return _lib.PcaDelta(DELTA_AXES[self.axes], self.width)
+
+
+_DELTA_WS = {}    # (device, B, T, F) -> (values float32 [B, T, F], tickets int32 [B], all zero)
+
+
+def delta_workspace(device, B: int, T: int, F: int):
+    """The launch's workspace, kept per (device, B, T, F), as ``pcen_workspace``: the tickets are zeroed once,
+    here - every launch leaves them zero.  Launches that share it run one after the other (one stream);
+    callers that overlap launches pass workspaces of their own.  Under stream capture nothing is kept."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (device, int(B), int(T), int(F))
+    held = _DELTA_WS.get(key)
+    if held is None:
+        held = (torch.empty((B, T, F), dtype=torch.float32, device=device),
+                torch.zeros(B, dtype=torch.int32, device=device))
+        if not torch.cuda.is_current_stream_capturing():
+            _DELTA_WS[key] = held
+    return held
+
+
+def frame_points_delta(waves: torch.Tensor, wave_off: torch.Tensor, set_off: torch.Tensor,
+                       idx: torch.Tensor, n_fft: int, hop: int, n_bins: int, farr: torch.Tensor,
+                       tarr: Optional[torch.Tensor] = None, Nt: int = 1, *, deltas: Deltas,
+                       bank: Optional[FilterBank] = None, max_len: int, min_len: int,
+                       clip_labels: Optional[torch.Tensor] = None, jitter: int = 0, gain_db: float = 0.0,
+                       win_lengths: Optional[torch.Tensor] = None, norm_mode: int = NORM_NFFT, seed: int = 0,
+                       draw: int = 0, out: Optional[torch.Tensor] = None,
+                       labels_out: Optional[torch.Tensor] = None, draw_dev: Optional[torch.Tensor] = None,
+                       want_meta: bool = False,
+                       workspace: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """``frame_points`` (``bank`` None) or ``frame_points_bands`` (a ``FilterBank``) with regression deltas of
+    the value column as further columns (pca_frame_points_delta): every argument of those with the same
+    meaning - the coordinates, the value column, labels and meta of slot b are that launch's bits - plus
+    ``deltas``, a ``Deltas``.  A frame has F rows: ``n_bins``, or ``bank.n_bands`` (``n_bins`` is then not
+    used).  Rows are (f, [t,] value, dt and / or df in the order of ``deltas.axes``); din = 2 or 3 plus
+    ``deltas.count`` is at most 4, so a set with ``tarr`` takes one axis.  One launch over
+    Nt + 2 * ``deltas.context`` frames per slot.
+
+    ``workspace``: (values float32 with >= B * (Nt + 2 * context) * F elements, tickets int32 [>= B], ZERO) on
+    the device, for callers that overlap launches or read the values back; None: ``delta_workspace``'s, kept
+    per shape.
+    Returns (points [B, Nt * F, din] float32, labels or None [, meta int32 [B, 4]])."""
+    if not isinstance(deltas, Deltas):
+        raise TypeError(f"frame_points_delta: deltas is a {type(deltas).__name__}, expected a Deltas")
+    if bank is not None:
+        if not isinstance(bank, FilterBank):
+            raise TypeError(f"frame_points_delta: bank is a {type(bank).__name__}, expected a FilterBank or None")
+        if bank.n_src != int(n_fft) // 2 + 1:
+            raise ValueError(f"frame_points_delta: the bank covers {bank.n_src} bins, n_fft {n_fft} has "
+                             f"{int(n_fft) // 2 + 1}")
+    F = int(n_bins) if bank is None else bank.n_bands
+    _need_cuda(waves, wave_off, set_off, idx, farr)
+    assert waves.dtype == torch.float32 and waves.is_contiguous() and farr.dtype == torch.float32
+    assert wave_off.dtype == set_off.dtype == idx.dtype == torch.int64
+    assert wave_off.numel() == set_off.numel() >= 2 and farr.numel() >= F
+    din = 2
+    if tarr is not None:
+        _need_cuda(tarr)
+        assert tarr.dtype == torch.float32 and tarr.numel() >= Nt
+        din = 3
+    din += deltas.count
+    if din > 4:
+        raise ValueError(f"frame_points_delta: Deltas {deltas.axes!r} on 3-D sets gives din {din} (max 4: one "
+                         f"axis)")
+    B = idx.numel()
+    T = int(Nt) + 2 * deltas.context
+    with torch.cuda.device(waves.device):
+        if win_lengths is None:
+            win_lengths = torch.tensor([n_fft], dtype=torch.int32, device=waves.device)
+        assert win_lengths.is_cuda and win_lengths.dtype == torch.int32
+        if out is None:
+            out = torch.empty((B, Nt * F, din), dtype=torch.float32, device=waves.device)
+        assert out.is_contiguous() and out.numel() == B * Nt * F * din
+        if clip_labels is not None and labels_out is None:
+            labels_out = torch.empty(B, dtype=torch.int64, device=waves.device)
+        meta = torch.empty((B, 4), dtype=torch.int32, device=waves.device) if want_meta else None
+        values, tickets = delta_workspace(waves.device, B, T, F) if workspace is None else workspace
+        _need_cuda(values, tickets)
+        assert values.dtype == torch.float32 and values.is_contiguous()
+        assert tickets.dtype == torch.int32 and tickets.is_contiguous() and tickets.numel() >= B
+        aug = _lib.PcaFrameAug(int(jitter), float(gain_db), win_lengths.data_ptr(),
+                               win_lengths.numel(), int(norm_mode), int(seed) & (2 ** 64 - 1),
+                               int(draw) & (2 ** 64 - 1), _draw_ptr(draw_dev))
+        bands = None if bank is None else C.byref(bank.on(waves.device))
+        spec = deltas.struct()
+        check(lib().pca_frame_points_delta(_ptr(waves), _ptr(wave_off), _ptr(set_off),
+                                           wave_off.numel() - 1, int(max_len), int(min_len),
+                                           _ptr(clip_labels), _ptr(idx), B, int(n_fft), int(hop),
+                                           int(n_bins) if bank is None else int(n_fft) // 2 + 1, int(Nt),
+                                           _ptr(farr), _ptr(tarr), C.byref(aug), bands, C.byref(spec),
+                                           _ptr(values), values.numel(), _ptr(tickets), _ptr(out),
+                                           _ptr(labels_out), _ptr(meta), _stream(waves)),
+              "pca_frame_points_delta")
+    return (out, labels_out, meta) if want_meta else (out, labels_out)
+
+
 REASSIGN_AXES = {"f": 1, "t": 2, "ft": 3, "tf": 3}
 
 
