@@ -1154,7 +1154,9 @@ int pca_st_pool_attention(const pca_st_config* c, const float* params, const flo
  * lengths: as at pca_st_forward (NULL, or 1 <= lengths[b] <= N with finite padding rows).  It does not
  * choose the launches: at the shapes of the set-resident d = 128 forward (d = 128, 4 heads, m = 16,
  * N = 256 or 512, bf16) a step with lengths is that one launch, as the dense step is, and the padding is
- * masked inside it; pca_st_ws_bytes is the same either way. */
+ * masked inside it; pca_st_ws_bytes is the same either way.
+ * Any d % h == 0 (a width that is no multiple of four included); d + C <= 16368, the floats of a set the
+ * classifier head keeps in LDS - a wider head is refused before anything is enqueued. */
 int pca_st_train_fwd_bwd(const pca_st_config* c, const float* params, const float* X,
                          const int32_t* lengths, const int64_t* labels, float* grads,
                          float* loss_out, float* stats, float* logits, float grad_scale,

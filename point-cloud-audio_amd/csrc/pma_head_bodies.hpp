@@ -125,7 +125,10 @@ __device__ __forceinline__ void cls_fwd_bwd_body(
   const int b = bset, tid = threadIdx.x, NT = blockDim.x;
   for (int f = tid; f < d; f += NT) sP[f] = P[(int64_t)b * d + f];
   __syncthreads();
-  if (d % 128 == 0 && 4 * C <= NT) {
+  // 16-byte loads of a class row only where every row starts on a 16-byte boundary; any other width or
+  // base takes scalar loads (same products, same order where both apply)
+  const bool w_v4 = d % 4 == 0 && (reinterpret_cast<uintptr_t>(Wc) & 15) == 0;
+  if (d % 128 == 0 && 4 * C <= NT && w_v4) {
     // four lanes per class, each a quarter of the contraction: one round of 8 loads instead of
     // four (this stage sits in the middle of a per-set chain of dependent L2 round trips)
     const int c = tid >> 2, part = tid & 3, seg = d / 4;
@@ -155,19 +158,22 @@ __device__ __forceinline__ void cls_fwd_bwd_body(
     const float* w = Wc + (int64_t)c * d;
     float acc = bc[c];
     int f = 0;
-    for (; f + 32 <= d; f += 32) {          // 8 independent 16-byte loads in flight
-      float4 w4[8];
+    if (w_v4) {
+      for (; f + 32 <= d; f += 32) {        // 8 independent 16-byte loads in flight
+        float4 w4[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) w4[u] = *reinterpret_cast<const float4*>(w + f + 4 * u);
+        for (int u = 0; u < 8; ++u) w4[u] = *reinterpret_cast<const float4*>(w + f + 4 * u);
 #pragma unroll
-      for (int u = 0; u < 8; ++u)
-        acc += sP[f + 4 * u] * w4[u].x + sP[f + 4 * u + 1] * w4[u].y + sP[f + 4 * u + 2] * w4[u].z +
-               sP[f + 4 * u + 3] * w4[u].w;
+        for (int u = 0; u < 8; ++u)
+          acc += sP[f + 4 * u] * w4[u].x + sP[f + 4 * u + 1] * w4[u].y + sP[f + 4 * u + 2] * w4[u].z +
+                 sP[f + 4 * u + 3] * w4[u].w;
+      }
+      for (; f + 4 <= d; f += 4) {
+        const float4 w4 = *reinterpret_cast<const float4*>(w + f);
+        acc += sP[f] * w4.x + sP[f + 1] * w4.y + sP[f + 2] * w4.z + sP[f + 3] * w4.w;
+      }
     }
-    for (; f < d; f += 4) {
-      const float4 w4 = *reinterpret_cast<const float4*>(w + f);
-      acc += sP[f] * w4.x + sP[f + 1] * w4.y + sP[f + 2] * w4.z + sP[f + 3] * w4.w;
-    }
+    for (; f < d; ++f) acc += sP[f] * w[f];   // a width that is no multiple of four, or a misaligned Wc
     sL[c] = acc;
     logits[(int64_t)b * C + c] = acc;
   }

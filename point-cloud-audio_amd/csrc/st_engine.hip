@@ -591,6 +591,10 @@ int st_train_fwd_bwd(const pca_st_config* c, const float* p, const float* X, con
   PCA_REQUIRE(p && X && labels && g && loss_out && ws, "st_train_fwd_bwd: null pointer");
   PCA_REQUIRE(c->k == 1, "st_train_fwd_bwd: the train step needs k == 1 (got %d)", c->k);
   PCA_REQUIRE(phase >= -1 && phase <= 1, "st_train_fwd_bwd: phase=%d", phase);
+  // the classifier head (cls_fwd_bwd_body) keeps a set's pooled features and its logits in LDS
+  PCA_REQUIRE((int64_t)c->d + c->C <= 16368,
+              "st_train_fwd_bwd: d + C = %lld floats do not fit the classifier head's LDS (max 16368)",
+              (long long)((int64_t)c->d + c->C));
   hipStream_t st = as_stream(stream);
   const StepPlan pl = plan(*c, true, lengths);
   Ws w;
