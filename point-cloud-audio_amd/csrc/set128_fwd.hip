@@ -204,10 +204,11 @@ struct MidPre {
   float bkvc;
 };
 
-template <bool SMALL>
+// PART: 1 = what stages A and B read (qp, bv0, bo0, wa, wb), 2 = stage C's (wc, bkv, bkvc), 3 = both
+template <bool SMALL, int PART = 3>
 __device__ __forceinline__ void mid_prefetch(const Set128Layer& L, const Ctx& c, int dk, MidPre& P) {
   const int r = c.r, g = c.g;
-  {
+  if (PART & 1) {
     // (waves 8-15 load the fragments of tile wave - 8 and never use them: under `if (wave < 8)` hipcc
     //  spilled every value of this block right behind its load, each with an s_waitcnt vmcnt(0))
     // (the tile is the wave's: it goes into the scalar bases; oW: the lane's 16 bytes of row r of a bf16 image)
@@ -229,7 +230,7 @@ __device__ __forceinline__ void mid_prefetch(const Set128Layer& L, const Ctx& c,
           P.wvf[e][cc] = cc < dk ? lane_ref<float>(L.Wv0f + 16 * t * dk, 16u * g * dk, 4 * (e * dk + cc)) : 0.f;
     }
   }
-  {
+  if (PART & 2) {
     const int tc = c.wave >> 1, which = c.wave & 1;
     const __bf16* W = which ? L.Wv1 : L.Wk1;
     const float* bias = which ? L.bv1 : L.bk1;
@@ -268,6 +269,7 @@ __device__ __forceinline__ void mid_stage(const Set128Layer& L, const Ctx& c, co
       lane_ref<float4>(L.O0 + (int64_t)b * MQ * D + 16 * t, 512u * r + 16u * g) = float4{o[0], o[1], o[2], o[3]};
   }
   lds_barrier();
+  STAMP(SMALL ? 28 : 30);                           // stage A done (the stamps of B: 29 / 31)
   if (c.wave < 8) {                                   // ---- B
     const int t = c.wave;
     f32x4 z = f32x4{P.bo0.x, P.bo0.y, P.bo0.z, P.bo0.w};
@@ -286,6 +288,7 @@ __device__ __forceinline__ void mid_stage(const Set128Layer& L, const Ctx& c, co
     put_tile(sH, t, r, g, hq);
   }
   lds_barrier();
+  STAMP(SMALL ? 29 : 31);
   {                                                   // ---- C
     const int tc = c.wave >> 1, which = c.wave & 1;
     f32x4 fr = f32x4{P.bkv.x, P.bkv.y, P.bkv.z, P.bkv.w};     // rows = features, col = key
@@ -559,9 +562,38 @@ struct PmaBwdLds {
                        RED = 32768;
 };
 
+// The weights and biases of the first three stages: requested by head_prefetch() in front of hand-off 3's
+// flag wait (behind the publishing waves' drain_vm() and its barrier, so no publish waits for them) and in
+// flight while the partner's flag is polled.  The partner's partial is read behind the flag, and so is the
+// set's label row: soft_row() selects between two loaded values, which is a wait where it stands - in front of
+// the poll it would put a round trip of its own there.  (qp, bv: added where they are used, for the same reason.)
+struct HeadPre {
+  float4 wv4[4], wo4[4], wc4[2];
+  float qp, bv, bo_f, bc3;
+};
+
+__device__ __forceinline__ void head_prefetch(const PmaHeadArgs& a, const Ctx& c, HeadPre& P) {
+  const int tid = c.tid, C = a.C;
+  const int fA = tid >> 3;                          // mapping A of head_stages
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    P.wv4[u] = lane_ref<float4>(a.Wv, 64u * tid, 16 * u);      // (fA D + 16 pA = 16 tid floats)
+    P.wo4[u] = lane_ref<float4>(a.Wo, 64u * tid, 16 * u);
+  }
+  const int c3 = tid >> 4, p3 = tid & 15;
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+    P.wc4[u] = lane_ref<float4>(a.Wc, 512u * (c3 < C ? c3 : 0) + 32u * p3, 16 * u);
+  P.qp = lane_ref<float>(a.Qp, 4u * fA);
+  P.bv = lane_ref<float>(a.bv, 4u * fA);
+  P.bo_f = lane_ref<float>(a.bo, 4u * fA);
+  P.bc3 = lane_ref<float>(a.bc, 4u * (c3 < C ? c3 : 0));
+}
+
 template <bool LEN>
-__device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, const float* sPm,
-                                            const float* theirs, float* sh, bool wr, char* bw) {
+__device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, const HeadPre& P,
+                                            const float* sPm, const float* theirs, float* sh, bool wr,
+                                            char* bw) {
   constexpr int DH = 32, R = 4;
   float* sT = sh;                 // [4][128] merged, normalised T
   float* sOv = sT + 512;          // O, P, Z, dP, dZ, dO: [128] each
@@ -580,23 +612,14 @@ __device__ __forceinline__ void head_stages(const PmaHeadArgs& a, const Ctx& c, 
   const int fA = tid >> 3, pA = tid & 7;            // mapping A: 8 adjacent lanes per output f
   const int fB = tid & 127, pB = tid >> 7;          // mapping B: column f, eighth pB of the rows
 
-  // everything the first three stages read from memory, requested together
+  // the partner's partial; everything else the first three stages read from memory is on its way (HeadPre)
   float pth = 0.f;
   if (tid < 520)
     pth = __hip_atomic_load((__attribute__((address_space(1))) const float*)lane_ptr(theirs, 4u * tid),
                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  float4 wv4[4], wo4[4], wc4[2];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    wv4[u] = lane_ref<float4>(a.Wv, 64u * tid, 16 * u);      // (fA D + 16 pA = 16 tid floats)
-    wo4[u] = lane_ref<float4>(a.Wo, 64u * tid, 16 * u);
-  }
+  const float4 (&wv4)[4] = P.wv4, (&wo4)[4] = P.wo4, (&wc4)[2] = P.wc4;
   const int c3 = tid >> 4, p3 = tid & 15;
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-    wc4[u] = lane_ref<float4>(a.Wc, 512u * (c3 < C ? c3 : 0) + 32u * p3, 16 * u);
-  const float qb = lane_ref<float>(a.Qp, 4u * fA) + lane_ref<float>(a.bv, 4u * fA), bo_f = lane_ref<float>(a.bo, 4u * fA),
-              bc3 = lane_ref<float>(a.bc, 4u * (c3 < C ? c3 : 0));
+  const float qb = P.qp + P.bv, bo_f = P.bo_f, bc3 = P.bc3;
   const SoftRow y = soft_row(a.soft, a.labels, b);
   if (wr && a.zero_ptr != nullptr)
     for (int i = b * NT + tid; i < a.zero_n; i += B * NT) a.zero_ptr[i] = 0.f;
@@ -1313,17 +1336,26 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
     STAMP(23);
     lds_barrier();                       // every storing wave has drained
     if (tid == 0) flag_store(flags + 4 + (b * 2 + 1) * 2 + c.half, 2u);
+    // stages A and B of the mid stage: their fragments are in flight from here on, through the flag wait, the
+    // payload loads, the merge and the image block (behind quad 0's drain_vm(): the publish does not wait for
+    // them); stage C's follow one barrier ahead of the stage, where layer 1 requests everything
+    mid_prefetch<false, 1>(L, c, D, pre);
     if (c.wave == 0) flag_wait(flags + 4 + (b * 2 + 1) * 2 + (c.half ^ 1), 2u, flags);
     lds_barrier();
     STAMP(24);
     float* sTs = reinterpret_cast<float*>(sO) + 8192;       // staging [64][128] fp32 behind the slots
     if (c.q == 0) {
-      f32x4 pt[8];
+      // the partner's T in two batches of four feature tiles: beside T[8] and the mid stage's fragments that
+      // are in flight (MidPre) there is no room for all eight
+      f32x4 pt[4];
       f32x4 pml = ld16_sc1(theirs + 8192 + (c.j * 64 + lane) * 4);
+      auto take_batch = [&](int f0) {
 #pragma unroll
-      for (int ft = 0; ft < 8; ++ft) pt[ft] = ld16_sc1(theirs + ((ft * 4 + c.j) * 64 + lane) * 4);
+        for (int ft = 0; ft < 4; ++ft) pt[ft] = ld16_sc1(theirs + (((f0 + ft) * 4 + c.j) * 64 + lane) * 4);
 #pragma unroll
-      for (int ft = 0; ft < 8; ++ft) landed(pt[ft]);
+        for (int ft = 0; ft < 4; ++ft) landed(pt[ft]);
+      };
+      take_batch(0);
       landed(pml);
       STAMP(26);
       // the SAME expression in both halves - f_1 x_1 + (f_0 x_0), the half-0 product rounded first, whoever
@@ -1347,14 +1379,19 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
       const float4 a2 = *reinterpret_cast<const float4*>(&myAl[16 + 4 * g]);
       const float a1v[4] = {a1.x, a1.y, a1.z, a1.w}, a2v[4] = {a2.x, a2.y, a2.z, a2.w};
 #pragma unroll
-      for (int ft = 0; ft < 8; ++ft) {
-        const float pv[4] = {pt[ft].x, pt[ft].y, pt[ft].z, pt[ft].w};
+      for (int f0 = 0; f0 < 8; f0 += 4) {
+        if (f0 != 0) take_batch(f0);
 #pragma unroll
-        for (int e = 0; e < 4; ++e)       // unnormalised; row 16 j + 4 g + e, feature 16 ft + r
-          sTs[(16 * c.j + 4 * g + e) * D + 16 * ft + r] = comb(a1v[e], T[ft][e], a2v[e], pv[e]);
+        for (int fb = 0; fb < 4; ++fb) {
+          const int ft = f0 + fb;
+          const float pv[4] = {pt[fb].x, pt[fb].y, pt[fb].z, pt[fb].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e)     // unnormalised; row 16 j + 4 g + e, feature 16 ft + r
+            sTs[(16 * c.j + 4 * g + e) * D + 16 * ft + r] = comb(a1v[e], T[ft][e], a2v[e], pv[e]);
+        }
       }
     }
-    mid_prefetch<false>(L, c, D, pre);   // one barrier ahead of the mid stage (see layer 1)
+    mid_prefetch<false, 2>(L, c, D, pre);   // one barrier ahead of the mid stage (see layer 1)
     STAMP(25);
     lds_barrier();
     {                                  // T (global fp32, saved) and its bf16 image; (inv, lse) of row: lane `row & 15` of wave j
@@ -1510,10 +1547,12 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
       if (tid == 0) flag_store(flags + 4 + (b * 2 + 0) * 2 + c.half, 3u);
       if (!pbwd) return;
     }
+    HeadPre hp;
+    head_prefetch(*(const PmaHeadArgs*)(&ap->head), c, hp);      // in flight under the flag wait
     if (c.wave == 0) flag_wait(flags + 4 + (b * 2 + 0) * 2 + (c.half ^ 1), 3u, flags);
     lds_barrier();
-    head_stages<LEN>(*(const PmaHeadArgs*)(&ap->head), c, sPm, exTheirs, reinterpret_cast<float*>(sS) + 1024,
-                     c.half == 0, pbwd ? sO : nullptr);
+    head_stages<LEN>(*(const PmaHeadArgs*)(&ap->head), c, hp, sPm, exTheirs,
+                     reinterpret_cast<float*>(sS) + 1024, c.half == 0, pbwd ? sO : nullptr);
     STAMP(19);
     if (pbwd) {
       ap = launder(ap);
