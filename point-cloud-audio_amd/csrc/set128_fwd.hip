@@ -129,15 +129,20 @@ __device__ __forceinline__ void st16_sc1(float* p, float4 v4) {
   const f32x4 v = {v4.x, v4.y, v4.z, v4.w};
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
-__device__ __forceinline__ f32x4 ld16_sc1(const float* p) {       // caller: s_waitcnt vmcnt(0) before use
-  f32x4 v;
-  asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(v) : "v"(p) : "memory");
-  return v;
+// the payload loads: buffer_load_dwordx4 .. sc1 through the builtin (cache-policy bit 4 = sc1 on gfx942 / gfx950),
+// NOT an asm load: an asm hands the compiler the destination registers of a load that is still in flight as an
+// ordinary value and needs a hand-counted wait; these hipcc counts in vmcnt like every other load, so it waits for
+// them alone in front of their first use and leaves younger plain loads in flight.  `bytes`: the range of the
+// descriptor (raw buffer, stride 0; word 3 = 32-bit data format, as for every gfx9 raw buffer)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t payload_rsrc(const float* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);
+}
+__device__ __forceinline__ f32x4 ld16_buf_sc1(__amdgpu_buffer_rsrc_t rs, uint32_t lane_bytes, int wave_bytes) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, lane_bytes, wave_bytes, 16);
+  return __builtin_bit_cast(f32x4, v);
 }
 __device__ __forceinline__ void drain_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// the wait as part of the data flow of a value loaded by ld16_sc1: hipcc does not know that the asm load
-// is still in flight and would otherwise be free to schedule uses of `v` above a bare s_waitcnt
-__device__ __forceinline__ void landed(f32x4& v) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(v)::"memory"); }
 __device__ __forceinline__ void flag_store(uint32_t* f, uint32_t v) {
   __hip_atomic_store((gu32*)(f), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -180,6 +185,21 @@ __device__ __forceinline__ float fac(float m, float M) {
   else return __builtin_amdgcn_exp2f(m - M);
 }
 
+// round B of layer 2's quad merge: take_partial's line T a1 + o a2 for one tile, written out as the instructions
+// hipcc made of it in every instance while quad 0 ran it over its eight tiles (the saved tensors and the hashes
+// of the tests are those bits): elements 0 and 1 round T a1 and fuse o a2 onto it (v_pk_mul, v_pk_fma), elements
+// 2 and 3 round both products and add them (v_mul, v_mul, v_pk_add).  Contraction is off in here, so that the
+// products that were rounded stay rounded whatever the surrounding code makes the vectoriser do.
+__device__ __forceinline__ f32x4 round_b_tile(float4 t, float4 a1, float4 o, float4 a2) {
+#pragma clang fp contract(off)
+  f32x4 v;
+  v[0] = __builtin_fmaf(o.x, a2.x, t.x * a1.x);
+  v[1] = __builtin_fmaf(o.y, a2.y, t.y * a1.y);
+  v[2] = t.z * a1.z + o.z * a2.z;
+  v[3] = t.w * a1.w + o.w * a2.w;
+  return v;
+}
+
 struct Ctx {
   int b, half, N, NH, tid, lane, wave, q, j, r, g;
   int UPQ;          // 32-point units per quad (N / 256)
@@ -212,9 +232,12 @@ __device__ __forceinline__ void mid_prefetch(const Set128Layer& L, const Ctx& c,
     // (waves 8-15 load the fragments of tile wave - 8 and never use them: under `if (wave < 8)` hipcc
     //  spilled every value of this block right behind its load, each with an s_waitcnt vmcnt(0))
     // (the tile is the wave's: it goes into the scalar bases; oW: the lane's 16 bytes of row r of a bf16 image)
+    // waves 8-15 never use what they load here: all their lanes ask for the tile's first 16 bytes (one line per
+    // request instead of sixteen)
     const int t = c.wave & 7;
-    const uint32_t oW = 256u * r + 16u * g, o16 = 16u * g;
-    P.qp = lane_ref<float4>(L.Qp0 + 16 * t, 512u * r + 16u * g);
+    const uint32_t used = c.wave < 8 ? ~0u : 0u;
+    const uint32_t oW = (256u * r + 16u * g) & used, o16 = (16u * g) & used;
+    P.qp = lane_ref<float4>(L.Qp0 + 16 * t, (512u * r + 16u * g) & used);
     P.bv0 = lane_ref<float4>(L.bv0 + 16 * t, o16);
     P.bo0 = lane_ref<float4>(L.bo0 + 16 * t, o16);
 #pragma unroll
@@ -227,7 +250,7 @@ __device__ __forceinline__ void mid_prefetch(const Set128Layer& L, const Ctx& c,
       for (int e = 0; e < 4; ++e)
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc)
-          P.wvf[e][cc] = cc < dk ? lane_ref<float>(L.Wv0f + 16 * t * dk, 16u * g * dk, 4 * (e * dk + cc)) : 0.f;
+          P.wvf[e][cc] = cc < dk ? lane_ref<float>(L.Wv0f + 16 * t * dk, (16u * g * dk) & used, 4 * (e * dk + cc)) : 0.f;
     }
   }
   if (PART & 2) {
@@ -244,10 +267,12 @@ __device__ __forceinline__ void mid_prefetch(const Set128Layer& L, const Ctx& c,
 
 // sT: bf16 image [64][256 B] of the merged T (swz rows; !SMALL) / sTf: fp32 [64][4] (SMALL);
 // sA, sH: [16][256 B] bf16 images of O and H.  Ends with a barrier.
-template <bool SMALL>
+// after_a(): requests of the NEXT phase, issued behind the barrier that ends stage A (a wave issues its loads in
+// order: in front of stage A they would hold waves 0-7 back while the memory pipeline takes them in)
+template <bool SMALL, class AfterA>
 __device__ __forceinline__ void mid_stage(const Set128Layer& L, const Ctx& c, const MidPre& P,
                                           const char* sT, const float* sTf, char* sA, char* sH,
-                                          char* sKp, char* sVt) {
+                                          char* sKp, char* sVt, AfterA after_a) {
   const int r = c.r, g = c.g, b = c.b;
   const bool save = c.half == 0;
   f32x4 o = {0.f, 0.f, 0.f, 0.f};
@@ -270,6 +295,7 @@ __device__ __forceinline__ void mid_stage(const Set128Layer& L, const Ctx& c, co
   }
   lds_barrier();
   STAMP(SMALL ? 28 : 30);                           // stage A done (the stamps of B: 29 / 31)
+  after_a();
   if (c.wave < 8) {                                   // ---- B
     const int t = c.wave;
     f32x4 z = f32x4{P.bo0.x, P.bo0.y, P.bo0.z, P.bo0.w};
@@ -1177,16 +1203,23 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
     STAMP(1);
     lds_barrier();
     if (c.wave == 0) {
+      // the sixteen m are read once and kept, and the partials are requested eight at a time (unrolled whole, the
+      // loop spills beside the mid stage's fragments in flight); p = 0 .. 15 and the expressions as they were,
+      // the fused multiply-adds that hipcc made of them written out
+      float mv[16];
+#pragma unroll
+      for (int p = 0; p < 16; ++p) mv[p] = sM[p * 64 + lane];
       float M = -INFINITY;
-#pragma unroll 4
-      for (int p = 0; p < 16; ++p) M = max_nn(M, sM[p * 64 + lane]);
+#pragma unroll
+      for (int p = 0; p < 16; ++p) M = max_nn(M, mv[p]);
       float Ls = 0.f, tt[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
+#pragma unroll 8
       for (int p = 0; p < 16; ++p) {
-        const float f = __builtin_amdgcn_exp2f(sM[p * 64 + lane] - M);
+        const float f = __builtin_amdgcn_exp2f(mv[p] - M);
         const float4 tp = *reinterpret_cast<const float4*>(sTp + (p * 64 + lane) * 4);
-        Ls += sL[p * 64 + lane] * f;
-        tt[0] += tp.x * f; tt[1] += tp.y * f; tt[2] += tp.z * f; tt[3] += tp.w * f;
+        Ls = __builtin_fmaf(sL[p * 64 + lane], f, Ls);
+        tt[0] = __builtin_fmaf(tp.x, f, tt[0]); tt[1] = __builtin_fmaf(tp.y, f, tt[1]);
+        tt[2] = __builtin_fmaf(tp.z, f, tt[2]); tt[3] = __builtin_fmaf(tp.w, f, tt[3]);
       }
       const float inv = 1.f / Ls;
 #pragma unroll
@@ -1202,7 +1235,7 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
   STAMP(2);
   ap = launder(ap);
   rederive(c);
-  mid_stage<true>(LAYER(0), c, pre, sT, sTf, sA, sH, sKp, sVt);
+  mid_stage<true>(LAYER(0), c, pre, sT, sTf, sA, sH, sKp, sVt, [] {});
   STAMP(3);
 
   // ================= layer 1, many-queries block ================================================
@@ -1319,44 +1352,68 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
     if (!(c.q & 1)) take_partial((c.q >> 1) * 4 + c.j, c.wave + 4);
     lds_barrier();
     STAMP(21);
+    // ---- round B, the publish, the fetch and the cross-half merge on ALL sixteen waves: quads 0 and 2 both put
+    // their round-A result into LDS (quad 0 into the slots 4 - 7 that round A has emptied), then wave (q, j)
+    // owns the feature tiles 2 q and 2 q + 1 of head j - two float4 per lane of the lane-linear image instead
+    // of the eight (plus the partner's eight) that a quad-0 lane carried while twelve waves waited
     if (c.q == 2) put_partial(c.j);
+    if (c.q == 0) put_partial(4 + c.j);
     lds_barrier();
     STAMP(22);
     float* mine = ap->ex2 + (int64_t)(b * 2 + c.half) * 9216;
     float* theirs = ap->ex2 + (int64_t)(b * 2 + (c.half ^ 1)) * 9216;
-    if (c.q == 0) {
-      take_partial(c.j, c.wave + 8);
-      // hand-off 2: the workgroup's partial of head j (unnormalised T, m, l)
+    const int ft0 = 2 * c.q;
+    f32x4 Tm[2];
+    {
+      // take_partial's expressions on quad 0's (m, l, T) (slot 4 + j) and quad 2's (slot j): every wave of head
+      // j forms the same (m, l) and the same factors from the same two sML entries
+      const float2 mlA = *reinterpret_cast<const float2*>(sML + (c.j * 16 + r) * 2);
+      const float2 mlB = *reinterpret_cast<const float2*>(sML + ((8 + c.j) * 16 + r) * 2);
+      const float mn = max_nn(mlA.x, mlB.x);
+      const float f1 = fac<LEN>(mlA.x, mn), f2 = fac<LEN>(mlB.x, mn);
+      lrow = mlA.y * f1 + mlB.y * f2;
+      mrow = mn;
+      if (g == 0) {
+        myAl[r] = f1;
+        myAl[16 + r] = f2;
+      }
+      const float4 a1 = *reinterpret_cast<const float4*>(&myAl[4 * g]);
+      const float4 a2 = *reinterpret_cast<const float4*>(&myAl[16 + 4 * g]);
+      const float4* srcA = reinterpret_cast<const float4*>(sO) + (4 + c.j) * 512;
+      const float4* srcB = reinterpret_cast<const float4*>(sO) + c.j * 512;
 #pragma unroll
-      for (int ft = 0; ft < 8; ++ft)
-        st16_sc1(mine + ((ft * 4 + c.j) * 64 + lane) * 4, float4{T[ft][0], T[ft][1], T[ft][2], T[ft][3]});
-      st16_sc1(mine + 8192 + (c.j * 64 + lane) * 4, float4{mrow, lrow, 0.f, 0.f});
-      drain_vm();
+      for (int k = 0; k < 2; ++k)
+        Tm[k] = round_b_tile(srcA[(ft0 + k) * 64 + lane], a1, srcB[(ft0 + k) * 64 + lane], a2);
     }
+    // hand-off 2: the workgroup's partial (unnormalised T, m, l) at the addresses it always had; (m, l) of head
+    // j once, by quad 0's wave.  Every wave stores, every wave drains, the barrier, one lane signals
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      st16_sc1(mine + (((ft0 + k) * 4 + c.j) * 64 + lane) * 4, float4{Tm[k][0], Tm[k][1], Tm[k][2], Tm[k][3]});
+    if (c.q == 0) st16_sc1(mine + 8192 + (c.j * 64 + lane) * 4, float4{mrow, lrow, 0.f, 0.f});
+    drain_vm();
     STAMP(23);
     lds_barrier();                       // every storing wave has drained
     if (tid == 0) flag_store(flags + 4 + (b * 2 + 1) * 2 + c.half, 2u);
-    // stages A and B of the mid stage: their fragments are in flight from here on, through the flag wait, the
-    // payload loads, the merge and the image block (behind quad 0's drain_vm(): the publish does not wait for
-    // them); stage C's follow one barrier ahead of the stage, where layer 1 requests everything
-    mid_prefetch<false, 1>(L, c, D, pre);
-    if (c.wave == 0) flag_wait(flags + 4 + (b * 2 + 1) * 2 + (c.half ^ 1), 2u, flags);
+    if (c.wave == 0) flag_wait(flags + 4 + (b * 2 + 1) * 2 + (c.half ^ 1), 2u, flags);   // nothing in front of the poll
     lds_barrier();
     STAMP(24);
-    float* sTs = reinterpret_cast<float*>(sO) + 8192;       // staging [64][128] fp32 behind the slots
-    if (c.q == 0) {
-      // the partner's T in two batches of four feature tiles: beside T[8] and the mid stage's fragments that
-      // are in flight (MidPre) there is no room for all eight
-      f32x4 pt[4];
-      f32x4 pml = ld16_sc1(theirs + 8192 + (c.j * 64 + lane) * 4);
-      auto take_batch = [&](int f0) {
+    float* sTs = reinterpret_cast<float*>(sO) + 8192;       // staging [64][128] fp32 (the slots 4 - 7 are dead)
+    {
+      // the partner's two tiles and its (m, l) of the lane's row: the oldest requests of every wave, as sc1 BUFFER
+      // loads - instructions that hipcc counts, so that it places the wait for them itself, in front of the first
+      // use and behind the mid stage's fragments requested below, which stay in flight
+      const __amdgpu_buffer_rsrc_t rs = payload_rsrc(theirs, 9216 * 4);
+      f32x4 pt[2];
 #pragma unroll
-        for (int ft = 0; ft < 4; ++ft) pt[ft] = ld16_sc1(theirs + (((f0 + ft) * 4 + c.j) * 64 + lane) * 4);
-#pragma unroll
-        for (int ft = 0; ft < 4; ++ft) landed(pt[ft]);
-      };
-      take_batch(0);
-      landed(pml);
+      for (int k = 0; k < 2; ++k) pt[k] = ld16_buf_sc1(rs, 16u * lane, (((ft0 + k) * 4 + c.j) * 64) * 16);
+      const f32x4 pml = ld16_buf_sc1(rs, 16u * lane, (8192 + c.j * 64 * 4) * 4);
+      // the mid stage's fragments, all three stages': in flight from here on, through the merge and the image
+      // block (two tiles per lane in the merge leave the registers for stage C's too)
+      mid_prefetch<false, 3>(L, c, D, pre);
+#ifdef PCA_SET_STAMPS
+      asm volatile("" ::"v"(pt[0]), "v"(pt[1]), "v"(pml) : "memory");
+#endif
       STAMP(26);
       // the SAME expression in both halves - f_1 x_1 + (f_0 x_0), the half-0 product rounded first, whoever
       // "own" is - so that the two workgroups of a set merge to bit-identical T (hipcc contracts
@@ -1374,24 +1431,19 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
         myAl[r] = fo;
         myAl[16 + r] = fp;
       }
-      if (g == 0) *reinterpret_cast<float2*>(sML + (c.wave * 16 + r) * 2) = float2{inv, Mx + log2f(Lt)};
+      // (inv, lse) of head j's rows where the image block reads them: once, by quad 0's wave
+      if (c.q == 0 && g == 0) *reinterpret_cast<float2*>(sML + (c.wave * 16 + r) * 2) = float2{inv, Mx + log2f(Lt)};
       const float4 a1 = *reinterpret_cast<const float4*>(&myAl[4 * g]);
       const float4 a2 = *reinterpret_cast<const float4*>(&myAl[16 + 4 * g]);
       const float a1v[4] = {a1.x, a1.y, a1.z, a1.w}, a2v[4] = {a2.x, a2.y, a2.z, a2.w};
 #pragma unroll
-      for (int f0 = 0; f0 < 8; f0 += 4) {
-        if (f0 != 0) take_batch(f0);
+      for (int k = 0; k < 2; ++k) {
+        const float pv[4] = {pt[k].x, pt[k].y, pt[k].z, pt[k].w};
 #pragma unroll
-        for (int fb = 0; fb < 4; ++fb) {
-          const int ft = f0 + fb;
-          const float pv[4] = {pt[fb].x, pt[fb].y, pt[fb].z, pt[fb].w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e)     // unnormalised; row 16 j + 4 g + e, feature 16 ft + r
-            sTs[(16 * c.j + 4 * g + e) * D + 16 * ft + r] = comb(a1v[e], T[ft][e], a2v[e], pv[e]);
-        }
+        for (int e = 0; e < 4; ++e)       // unnormalised; row 16 j + 4 g + e, feature 16 ft + r
+          sTs[(16 * c.j + 4 * g + e) * D + 16 * (ft0 + k) + r] = comb(a1v[e], Tm[k][e], a2v[e], pv[e]);
       }
     }
-    mid_prefetch<false, 2>(L, c, D, pre);   // one barrier ahead of the mid stage (see layer 1)
     STAMP(25);
     lds_barrier();
     {                                  // T (global fp32, saved) and its bf16 image; (inv, lse) of row: lane `row & 15` of wave j
@@ -1413,8 +1465,8 @@ __global__ __launch_bounds__(NT) void k_set128_fwd(const Set128FwdArgs a_by_valu
     }
     lds_barrier();
     STAMP(10);
-    mab1_load_wq(L, c, wa);            // fc_q's slice of the many-queries block, a stage ahead
-    mid_stage<false>(L, c, pre, sT, sTf, sA, sH, sKp, sVt);
+    // fc_q's slice of the many-queries block: two stages ahead, behind stage A
+    mid_stage<false>(L, c, pre, sT, sTf, sA, sH, sKp, sVt, [&] { mab1_load_wq(L, c, wa); });
     STAMP(11);
   }
 
